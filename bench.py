@@ -89,6 +89,42 @@ def kernel_code_hash():
     return h.hexdigest()
 
 
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: everything written, .npy headers included, stays under this
+DUMP_SEED = 20261015
+
+
+def dump_outputs(solver, out_dir):
+    """What the timed path hands its caller after a step -- the global stiffness matrix (scalar CSR in the caller's dof
+    ids, feahip_get_matrix_yale64) and the residual forces -- as float64 .npy files in out_dir.  Rows are taken in a
+    fixed seeded order until the files would pass DUMP_BYTES (all rows when they fit), then written in ascending order:
+      rows                   the dof ids of the rows written
+      stiffness_row_offsets  offsets of those rows into the next two arrays (len(rows) + 1)
+      stiffness_columns      the column (dof) ids of their non-zeros
+      stiffness_values       their values
+      residual               the residual forces at those dofs
+    Ids are stored as float64 (exact below 2^53).  Returns a short description for the JSON line."""
+    off, idx, val = solver.matrix_yale64()
+    f = solver.forces()
+    ndof = len(off) - 1
+    rowlen = np.diff(off)
+    order = np.random.default_rng(DUMP_SEED).permutation(ndof)
+    # bytes after taking the first r rows of `order`: rows + residual + offsets (8 B each per row, +8) + 16 B per non-zero
+    cost = 8 * (3 * np.arange(1, ndof + 1) + 1) + 16 * np.cumsum(rowlen[order]) + 5 * 128
+    r = int(np.searchsorted(cost, DUMP_BYTES, side="right"))
+    rows = np.sort(order[:r])
+    lens = rowlen[rows]
+    sub_off = np.zeros(r + 1, dtype=np.int64)
+    np.cumsum(lens, out=sub_off[1:])
+    take = np.repeat(off[rows] - sub_off[:-1], lens) + np.arange(sub_off[-1])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rows": rows, "stiffness_row_offsets": sub_off, "stiffness_columns": idx[take], "stiffness_values": val[take],
+              "residual": f[rows]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": os.path.abspath(out_dir), "rows": r, "of_rows": ndof, "nonzeros": int(sub_off[-1]), "of_nonzeros": int(off[-1]),
+            "seed": DUMP_SEED}
+
+
 def cpu_baseline(n_sample, quadratic=False, model=None):
     """The oracle (CPU restatement of the reference loops, 1 thread) timed on
     a bounded sample of the same workload: a smaller Kuhn block of the same
@@ -246,7 +282,16 @@ def main():
                          "TetGen deck, 8 x 8 x 7 copies) as THE workload, assembly only -- for rocprofv3 / PMC passes of that case")
     ap.add_argument("--no-off-lattice", action="store_true", help="skip the off-lattice legs of extras (jittered + permuted block, tiled TetGen deck)")
     ap.add_argument("--pcg-variant", type=int, default=-1, help="-1: the context's default; 0: two-reduction PCG; 1: single-reduction PCG")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (stiffness matrix rows and residual, a fixed "
+                         "seeded sample of at most 64 MB in all) to DIR/<name>.npy, float64 (one GPU only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
     if args.mesh == "tetgen":                       # assembly of that mesh only: no solve, no other element, no CPU leg
         args.no_newton = args.no_tet10 = args.no_off_lattice = True
         args.cpu_sample = 0
@@ -370,6 +415,11 @@ def main():
         dt = float(tt.item())
     ms_per_step = 1e3 * dt / args.steps
     value = E_total * args.steps / dt
+    dumped = None
+    if args.dump_outputs is not None:
+        # before anything below assembles again: the matrix and residual of the last timed step (the headline is
+        # measured; the kernel timings of extras below then follow seconds of host work instead of the timed steps)
+        dumped = dump_outputs(solver, args.dump_outputs)
 
     share = 1.0 / world
     # dominant kernel, HIP events on the library's own stream (local, no collective), right behind the timed steps: the
@@ -536,6 +586,8 @@ def main():
         extras["tet10"] = tet10
     if hex8 is not None:
         extras["hex8"] = hex8
+    if dumped is not None:
+        extras["dumped_outputs"] = dumped
     out = {
         "metric": "element-stiffness assemblies/sec", "value": value, "unit": "elements/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
