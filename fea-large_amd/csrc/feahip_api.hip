@@ -44,14 +44,15 @@ static int dev_zeros(feahip_ctx *c, T **dst, size_t n)
 
 int ensure_generic_maps(feahip_ctx *c)
 {
-  if (c->generic_maps) return FEAHIP_OK;
+  GenericMaps &g = c->generic;
+  if (g.built()) return FEAHIP_OK;
   if (!c->h_pat) { c->err = "incidence maps unavailable"; return FEAHIP_ESTATE; }
   const HostPattern &hp = *c->h_pat;
   int rc;
-  if ((rc = dev_upload(c, &c->d_incptr, hp.incptr.data(), hp.incptr.size()))) return rc;
-  if ((rc = dev_upload(c, &c->d_inc, hp.inc.data(), hp.inc.size()))) return rc;
-  if (!hp.incslot.empty() && (rc = dev_upload(c, &c->d_incslot, hp.incslot.data(), hp.incslot.size()))) return rc;
-  c->generic_maps = true;
+  if ((rc = dev_upload(c, &g.d_incptr, hp.incptr.data(), hp.incptr.size()))) return rc;
+  if ((rc = dev_upload(c, &g.d_inc, hp.inc.data(), hp.inc.size()))) return rc;
+  if (!hp.incslot.empty() && (rc = dev_upload(c, &g.d_incslot, hp.incslot.data(), hp.incslot.size()))) return rc;
+  g.record(MapOutcome::built, 0, c->N);
   return FEAHIP_OK;
 }
 
@@ -83,39 +84,38 @@ void release_k(feahip_ctx *c)
 // shared-state maps of 10-node elements for the assembly chunks this rank owns
 int ensure_quad(feahip_ctx *c)
 {
-  if (c->have_quad && c->quad_a0 == c->achunk0 && c->quad_n == c->nachunks_local) return FEAHIP_OK;
-  if (c->quad_failed || c->npe != 10 || !c->h_pat || c->h_conn.empty()) return FEAHIP_OK;
+  QuadMaps &q = c->quad;
+  const int a0 = c->achunk0, a1 = c->achunk0 + c->nachunks_local;
+  if (q.settled(a0, a1) || c->npe != 10 || !c->h_pat || c->h_conn.empty()) return FEAHIP_OK;
   HostQuad hq;
-  build_host_quad(c->N, c->E, c->npe, c->h_conn.data(), *c->h_pat, c->achunk0, c->achunk0 + c->nachunks_local, hq);
-  for (void *p : {(void *)c->d_qdesc, (void *)c->d_qelem, (void *)c->d_qpair, (void *)c->d_qnode})
-    if (p) (void)hipFree(p);
-  c->d_qdesc = nullptr; c->d_qelem = c->d_qpair = nullptr; c->d_qnode = nullptr;
-  c->have_quad = false;
-  if (!hq.ok) { if (c->nranks == 1) c->quad_failed = true; return FEAHIP_OK; }
+  build_host_quad(c->N, c->E, c->npe, c->h_conn.data(), *c->h_pat, a0, a1, hq);
+  q.release();
+  if (!hq.ok) { q.record(MapOutcome::failed, a0, a1); return FEAHIP_OK; }
   int rc;
-  if ((rc = dev_upload(c, &c->d_qdesc, hq.desc.data(), hq.desc.size()))) return rc;
-  if ((rc = dev_upload(c, &c->d_qelem, hq.qelem.data(), hq.qelem.size()))) return rc;
-  if ((rc = dev_upload(c, &c->d_qpair, hq.qpair.data(), hq.qpair.size()))) return rc;
-  if ((rc = dev_upload(c, &c->d_qnode, hq.qnode.data(), hq.qnode.size()))) return rc;
-  c->have_quad = true;
-  c->quad_a0 = c->achunk0; c->quad_n = c->nachunks_local;
-  c->quad_bytes = (long long)(hq.desc.size() * sizeof(QuadDesc) + hq.qelem.size() * 4 + hq.qpair.size() * 4 + hq.qnode.size() * 4);
+  if ((rc = dev_upload(c, &q.d_desc, hq.desc.data(), hq.desc.size()))) return rc;
+  if ((rc = dev_upload(c, &q.d_elem, hq.qelem.data(), hq.qelem.size()))) return rc;
+  if ((rc = dev_upload(c, &q.d_pair, hq.qpair.data(), hq.qpair.size()))) return rc;
+  if ((rc = dev_upload(c, &q.d_node, hq.qnode.data(), hq.qnode.size()))) return rc;
+  q.nchunks = c->nachunks_local;
+  q.bytes = (long long)(hq.desc.size() * sizeof(QuadDesc) + hq.qelem.size() * 4 + hq.qpair.size() * 4 + hq.qnode.size() * 4);
+  q.record(MapOutcome::built, a0, a1);
   return FEAHIP_OK;
 }
 
 int ensure_visits(feahip_ctx *c)
 {
-  if (c->have_visits || c->visits_failed || !c->h_pat || c->h_conn.empty()) return FEAHIP_OK;
+  VisitMaps &v = c->visits;
+  if (v.settled(0, c->N) || !c->h_pat || c->h_conn.empty()) return FEAHIP_OK;
   HostVisits hv;
   build_host_visits(c->N, c->E, c->h_conn.data(), *c->h_pat, hv);
-  if (!hv.ok) { c->visits_failed = true; return FEAHIP_OK; }
+  if (!hv.ok) { v.record(MapOutcome::failed, 0, c->N); return FEAHIP_OK; }
   int rc;
-  if ((rc = dev_upload(c, &c->d_vdesc, hv.desc.data(), hv.desc.size()))) return rc;
-  if ((rc = dev_upload(c, &c->d_vnode, hv.vnode.data(), hv.vnode.size()))) return rc;
-  if ((rc = dev_upload(c, &c->d_vrec, hv.vrec.data(), hv.vrec.size()))) return rc;
-  c->have_visits = true;
-  c->nvisit_records = (int)(hv.vrec.size() / 2);
-  c->visit_bytes = (long long)(hv.desc.size() * sizeof(VisitDesc) + hv.vnode.size() * 4 + hv.vrec.size() * 4);
+  if ((rc = dev_upload(c, &v.d_desc, hv.desc.data(), hv.desc.size()))) return rc;
+  if ((rc = dev_upload(c, &v.d_node, hv.vnode.data(), hv.vnode.size()))) return rc;
+  if ((rc = dev_upload(c, &v.d_rec, hv.vrec.data(), hv.vrec.size()))) return rc;
+  v.nrecords = (int)(hv.vrec.size() / 2);
+  v.bytes = (long long)(hv.desc.size() * sizeof(VisitDesc) + hv.vnode.size() * 4 + hv.vrec.size() * 4);
+  v.record(MapOutcome::built, 0, c->N);
   return FEAHIP_OK;
 }
 
@@ -229,7 +229,7 @@ static int create_impl(feahip_ctx *c, int device, int n_nodes, int n_elems, int 
   if ((rc = dev_upload(c, &c->d_colidx, hp.colidx.data(), hp.colidx.size()))) return rc;
   if ((rc = dev_upload(c, &c->d_chunk, hp.chunk.data(), hp.chunk.size()))) return rc;
   if ((rc = dev_upload(c, &c->d_diag, hp.diag.data(), hp.diag.size()))) return rc;
-  c->aux_bytes = (long long)(hp.incptr.size() * 4 + hp.inc.size() * 4 + hp.incslot.size() +
+  c->generic.bytes = (long long)(hp.incptr.size() * 4 + hp.inc.size() * 4 + hp.incslot.size() +
                              hp.chunk.size() * 4 + hp.rowptr.size() * 4 + hp.diag.size() * 4);
 
   const bool lin1 = c->linear_tet && gauss_count == 1;
@@ -400,10 +400,9 @@ extern "C" void feahip_destroy(feahip_ctx *c)
 {
   if (!c) return;
   delete c->h_pat; c->h_pat = nullptr;
-  delete c->gather_lay; c->gather_lay = nullptr;
-  delete c->gather10_lay; c->gather10_lay = nullptr;
-  void *ptrs[] = {(void *)c->d_gmaps, (void *)c->d_g10_elist, (void *)c->d_g10_state, c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
-                  c->d_incptr, c->d_inc, c->d_incslot, c->d_chunk, c->d_diag, c->d_vdesc, c->d_vnode, c->d_vrec, c->d_qdesc, c->d_qelem, c->d_qpair, c->d_qnode, c->d_f, c->d_u, c->d_r, c->d_p,
+  c->generic.release(); c->visits.release(); c->quad.release(); c->gather.release(); c->gather10.release();
+  void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
+                  c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
                   c->d_dofmask, c->d_F, c->d_S};
   for (void *p : ptrs)
@@ -995,10 +994,11 @@ extern "C" int feahip_copy_bandwidth(feahip_ctx *c, long long bytes, double *gby
 extern "C" int feahip_assembly_stats(feahip_ctx *c, double *o)
 {
   if (!c || !o) return FEAHIP_EINVAL;
-  o[0] = c->have_gather ? c->gather_evals_per_element : 0.0;
-  o[1] = c->have_gather ? (double)c->ngchunks : 0.0;
-  o[2] = c->have_gather ? (double)c->gather_same_words : 0.0;
-  o[3] = c->have_gather ? (double)c->gather_bytes : 0.0;
+  const GatherCache &g = c->gather10.built() ? (const GatherCache &)c->gather10 : c->gather;
+  o[0] = g.built() ? g.evals_per_element : 0.0;
+  o[1] = g.built() ? (double)g.nchunks : 0.0;
+  o[2] = g.built() ? (double)g.same_words : 0.0;
+  o[3] = g.built() ? (double)g.bytes : 0.0;
   return FEAHIP_OK;
 }
 
@@ -1022,9 +1022,10 @@ extern "C" int feahip_sizes(feahip_ctx *c, long long *o)
   if (!c || !o) return FEAHIP_EINVAL;
   o[0] = c->N; o[1] = c->E; o[2] = c->npe; o[3] = c->G; o[4] = c->nnzb; o[5] = c->nchunks;
   // bytes of the maps the default assembly kernel reads besides the algorithmic inputs
-  o[6] = c->have_gather ? c->gather_bytes
-       : c->have_visits ? c->visit_bytes + (long long)(c->N + 1) * 8
-       : c->have_quad ? c->quad_bytes + (long long)(c->N + 1) * 8 : c->aux_bytes;
+  o[6] = c->gather.built() ? c->gather.bytes
+       : c->gather10.built() ? c->gather10.bytes
+       : c->visits.built() ? c->visits.bytes + (long long)(c->N + 1) * 8
+       : c->quad.built() ? c->quad.bytes + (long long)(c->N + 1) * 8 : c->generic.bytes;
   o[7] = c->max_rowlen;
   return FEAHIP_OK;
 }

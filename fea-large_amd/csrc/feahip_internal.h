@@ -2,9 +2,13 @@
 // libfeahip.so.  Not part of the ABI (include/fea_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
+#include <thread>
+#include <type_traits>
 #include <vector>
 #include "../../include/fea_hip.h"
 
@@ -32,145 +36,6 @@ struct ElemTable {            // element plug-in, tabulated by the host
   double dN[FEA_MAX_GAUSS][3][FEA_MAX_NPE];
 };
 
-struct feahip_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-
-  // sizes
-  int N = 0, E = 0, npe = 0, G = 0, ndof = 0;
-  int nnzb = 0;               // 3x3 blocks in the full symmetric pattern
-  int nchunks = 0;
-  int chunk0 = 0, nchunks_local = 0;  // this rank's share of the chunks (row shard)
-  int nachunks = 0, achunk0 = 0, nachunks_local = 0;   // same for the staged kernel's partition
-  std::vector<int> h_super_achunk, h_chunk;
-  // row shard of a multi-rank solve: this rank owns nodes [row0, row1)
-  int rank = 0, nranks = 1, row0 = 0, row1 = 0;
-  struct Transport *tr = nullptr;      // null: single rank, no exchange
-  bool owns_tr = false;
-  std::vector<int> peer, send_off, recv_off;   // halo plan: per peer, ranges into the index lists
-  int nsend = 0, nrecv = 0;
-  int *d_send_idx = nullptr, *d_recv_idx = nullptr;
-  double *d_send_buf = nullptr, *d_recv_buf = nullptr;
-  int max_rowlen = 0;
-  bool linear_tet = false;    // npe == 4 and dN is the constant-strain table
-  int model = 0;
-  double lambda = 0, mu = 0;
-  int strategy = FEAHIP_ASM_AUTO;
-  int last_strategy = FEAHIP_ASM_AUTO;   // what the most recent assembly launch ran
-
-  ElemTable table;
-  ElemTable *d_table = nullptr;
-
-  // mesh (device)
-  int *d_conn = nullptr;       // [E][npe]
-  double *d_X0 = nullptr;      // [N][4] padded to 32 B (two dwordx4 per node)
-  double *d_x = nullptr;       // [N][4] current configuration
-  // block-CSR pattern of K (built once; topology never changes)
-  int *d_rowptr = nullptr;     // [N+1]
-  int *d_colidx = nullptr;     // [nnzb]
-  // K holds the block rows this rank owns and nothing else: blocks [kb0, kb1) = rowptr[row0] .. rowptr[row1] (all of
-  // them for an unsharded context).  It is allocated on first use, for the shard installed by then, so a rank of a
-  // sharded run never holds the other ranks' rows (the reference keeps one row-wise store, fea_solver.c:444-448,
-  // and its modified-Newton copy, :179).  Kernels index by GLOBAL block number through d_K = d_K_base - 9 kb0.
-  double *d_K = nullptr;       // [nnzb][3][3], valid for blocks [kb0, kb1) only
-  double *d_Kstash = nullptr;  // modified-Newton copy (fea_solver.c:179), same window
-  double *d_K_base = nullptr, *d_Kstash_base = nullptr;   // first owned value (block kb0) of each
-  double *d_K_alloc = nullptr, *d_Kstash_alloc = nullptr; // the allocations: d_K_base = d_K_alloc + (kb0 & 1), so that even GLOBAL value indices are 16-byte aligned on every rank
-  long long kb0 = 0, kb1 = 0;
-  bool have_stash = false;
-  // node -> element incidence (row-owner assembly)
-  int *d_incptr = nullptr;     // [N+1]
-  uint32_t *d_inc = nullptr;   // [npe*E]  elem | local<<28
-  uint8_t *d_incslot = nullptr;// [npe*E][npe] slot of column conn[e][b] in row
-  int *d_chunk = nullptr;      // [nchunks+1] first row of every chunk
-  int *d_diag = nullptr;       // [N] index of the diagonal block of every row
-  // LDS-staged visit assembly maps (linear tetrahedra)
-  bool have_visits = false, visits_failed = false;
-  struct VisitDesc *d_vdesc = nullptr;
-  int *d_vnode = nullptr;
-  uint32_t *d_vrec = nullptr;
-  long long visit_bytes = 0;
-  int nvisit_records = 0;      // length of vrec in records (whole passes per chunk)
-  bool have_quad = false, quad_failed = false;
-  int quad_a0 = -1, quad_n = 0;        // assembly chunks the quad maps were built for (this rank's)
-  struct QuadDesc *d_qdesc = nullptr;
-  uint32_t *d_qelem = nullptr, *d_qpair = nullptr;
-  int *d_qnode = nullptr;
-  long long quad_bytes = 0;
-  // GATHER assembly maps (linear tetrahedra, kernels_gather.hip): built for the rows this rank owns
-  bool have_gather = false, gather_failed = false;   // gather_failed: the maps did not build for rows [gather_fail_row0, gather_fail_row1)
-  int gather_fail_row0 = -1, gather_fail_row1 = -1;
-  int gather_declined_row0 = -1, gather_declined_row1 = -1;   // AUTO looked at the gather chunks of these rows and chose another kernel (linear tets)
-  int gather_row0 = -1, gather_row1 = -1, ngchunks = 0;
-  unsigned char *d_gmaps = nullptr;
-  struct GatherLayout *gather_lay = nullptr;
-  long long gather_bytes = 0;
-  double gather_evals_per_element = 0;   // element evaluations the gather chunks make per element this rank touches
-  int gather_same_words = 0;             // gather chunks whose map words equal their predecessor's
-  // the same for 10-node tetrahedra (kernels_gather10.hip); shares d_gmaps / ngchunks / gather_row0.. with the above
-  struct Gather10Layout *gather10_lay = nullptr;
-  int *d_g10_elist = nullptr;            // this rank's elements
-  double *d_g10_state = nullptr;         // [G][elements of the rank][18]: Gauss-point state records (kernels_gather10.hip)
-  int g10_nloc = 0;
-  // vectors (3N doubles)
-  double *d_f = nullptr, *d_u = nullptr;
-  double *d_r = nullptr, *d_p = nullptr, *d_q = nullptr, *d_minv = nullptr;
-  double *d_part = nullptr;    // reduction partials, 6 x FEA_RED_BLOCKS
-  // single-reduction PCG (kernels_solve.hip): preconditioned residual z = M r and w = K z (allocated on first use);
-  // pcg_variant: -1 = single-reduction when sharded, the reference-shaped two-reduction loop otherwise; 0 / 1 force
-  double *d_z = nullptr, *d_w = nullptr, *d_s = nullptr;
-  int pcg_variant = -1;
-  // SpMV chunks [chunk0 + ichunk_lo, chunk0 + ichunk_hi) of this rank touch no halo column: they run while the halo
-  // rows are in flight (everything, for an unsharded context)
-  int ichunk_lo = 0, ichunk_hi = 0;
-  hipStream_t comm_stream = nullptr;   // RCCL transport: halo exchange beside the interior product
-  hipEvent_t ev_packed = nullptr, ev_unpacked = nullptr;
-  double *d_scal = nullptr;    // device scalars of the CG recurrences
-  int *d_flag = nullptr;       // [0] converged-at iteration, [1] bad Gauss pts
-  // prescribed displacements
-  int n_presc = 0;             // nodes in the deck
-  int n_cdof = 0;              // constrained dofs, deck order x,y,z per node
-  int *d_cdof = nullptr;
-  double *d_cval = nullptr;    // prescribed value per constrained dof
-  uint8_t *d_dofmask = nullptr;// [3N] 1 = constrained
-  // cached per-Gauss-point state for the getters
-  double *d_F = nullptr, *d_S = nullptr;   // [E][G][9]
-  bool state_valid = false;
-
-  // host copies needed by getters / pattern export
-  std::vector<int> h_rowptr, h_colidx;
-  // The maps of a strategy (gather chunks, staged visits, generic incidence lists) are built the first time it is
-  // asked for, from these host copies.
-  std::vector<int> h_conn;
-  struct HostPattern *h_pat = nullptr;
-  bool generic_maps = false;   // incptr / inc / incslot uploaded
-  bool incslot_ok = false;     // the mesh has them (row length <= 255)
-  long long aux_bytes = 0;
-
-  int last_bad = 0;
-
-  // library-side node numbering (renumber.cpp): everything in the context -- mesh arrays, pattern, K, vectors, shard
-  // ranges -- lives in the library's numbering; the ABI translates at its boundary.  Empty = the caller's numbering.
-  std::vector<int> perm, iperm;        // perm[caller id] = library id, iperm = its inverse
-  // a rank context (feahip_create_rank): this context IS one rank's sub-mesh, locally indexed; its "caller ids" are the
-  // local ids, rank_node_global / rank_elem_global say which nodes and elements of the whole mesh they are
-  int rank_own = -1;                   // nodes it owns (local ids [0, rank_own)); -1: an ordinary context
-  std::vector<int> rank_node_global, rank_elem_global;
-  int rank_n_global = 0;
-
-  // preconditioner of PCG_ILU / CHOLESKY solves: 0 = 3x3 block-Jacobi, 1 = aggregation multigrid (amg.h)
-  // which matrix d_K holds: bumped by every stiffness assembly, copied by stash / restore; k_bc = prescribed-dof
-  // masking applied since.  Only used to skip numeric re-setup of the multigrid hierarchy for an unchanged K
-  // (modified Newton restores the same matrix every iteration); a stale hierarchy would cost iterations, not accuracy.
-  unsigned long long k_epoch = 0, stash_epoch = 0;
-  bool k_bc = false;
-  // golden-section line search along the Newton step: iterations (0 = off, the reference's solve())
-  int linesearch_max = 0;
-  int precond = 0;
-  void *amg = nullptr;         // AmgHierarchy, built on first use
-};
-
 #define FEA_HIP_CHECK(ctx, call)                                            \
   do {                                                                      \
     hipError_t _e = (call);                                                 \
@@ -179,6 +44,24 @@ struct feahip_ctx {
       return FEAHIP_EHIP;                                                   \
     }                                                                       \
   } while (0)
+
+// host map construction: f(lo, hi) on equal consecutive ranges of [0, n), one thread each (up to 32); a single
+// call below serial_below items
+template <class F>
+void parallel_ranges(int n, int serial_below, F f)
+{
+  unsigned hw = std::thread::hardware_concurrency();
+  int nt = (int)std::min<unsigned>(hw ? hw : 4, 32);
+  if (n < serial_below) nt = 1;
+  if (nt <= 1) { f(0, n); return; }
+  std::vector<std::thread> th;
+  for (int t = 0; t < nt; ++t) {
+    int lo = (int)((long long)n * t / nt), hi = (int)((long long)n * (t + 1) / nt);
+    th.emplace_back([=] { f(lo, hi); });
+  }
+  for (auto &x : th) x.join();
+}
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // pattern.cpp
 struct HostPattern {
@@ -364,6 +247,181 @@ int ensure_gather10(feahip_ctx *c);
 int launch_assemble_gather10(feahip_ctx *c, bool doK, bool doF);
 
 int launch_assemble_visit(feahip_ctx *c, bool doK, bool doF);
+
+// ---- maps of the assembly strategies.  Each family's maps are built for one key: the rows [row0, row1) of the shard
+// for the gather kernels, the assembly chunks [achunk0, achunk0 + nachunks_local) for the shared-state kernel, the
+// whole mesh for the staged visits and the incidence lists.  The maps and the outcome of their build are valid for
+// that key only; release() frees the buffers and forgets both.
+enum class MapOutcome { none, built, failed, declined };   // declined: built, looked at and dropped by AUTO
+struct MapCache {
+  int key0 = -1, key1 = -1;
+  MapOutcome outcome = MapOutcome::none;
+  long long bytes = 0;                 // device bytes of the maps
+  bool built() const { return outcome == MapOutcome::built; }
+  bool is(MapOutcome o, int k0, int k1) const { return outcome == o && key0 == k0 && key1 == k1; }
+  // nothing to build for this key (a declined build is made again when the strategy is asked for)
+  bool settled(int k0, int k1) const { return is(MapOutcome::built, k0, k1) || is(MapOutcome::failed, k0, k1); }
+  void record(MapOutcome o, int k0, int k1) { outcome = o; key0 = k0; key1 = k1; }
+};
+inline void dev_free(std::initializer_list<void *> ptrs) { for (void *p : ptrs) if (p) (void)hipFree(p); }
+struct GenericMaps : MapCache {        // node -> element incidence (row-owner and atomic assembly)
+  int *d_incptr = nullptr;             // [N+1]
+  uint32_t *d_inc = nullptr;           // [npe*E]  elem | local<<28
+  uint8_t *d_incslot = nullptr;        // [npe*E][npe] slot of column conn[e][b] in row
+  void release() { dev_free({d_incptr, d_inc, d_incslot}); *this = GenericMaps(); }
+};
+struct VisitMaps : MapCache {          // LDS-staged visits (linear tetrahedra)
+  VisitDesc *d_desc = nullptr;
+  int *d_node = nullptr;
+  uint32_t *d_rec = nullptr;
+  int nrecords = 0;                    // length of rec in records (whole passes per chunk)
+  void release() { dev_free({d_desc, d_node, d_rec}); *this = VisitMaps(); }
+};
+struct QuadMaps : MapCache {           // shared-state kernel: this rank's assembly chunks
+  QuadDesc *d_desc = nullptr;
+  uint32_t *d_elem = nullptr, *d_pair = nullptr;
+  int *d_node = nullptr;
+  int nchunks = 0;
+  void release() { dev_free({d_desc, d_elem, d_pair, d_node}); *this = QuadMaps(); }
+};
+struct GatherCache : MapCache {        // either gather kernel: one map record per chunk of the rows this rank owns
+  unsigned char *d_maps = nullptr;
+  int nchunks = 0;
+  double evals_per_element = 0;        // element evaluations the chunks make per element the rows touch
+  int same_words = 0;                  // chunks whose map words equal their predecessor's (4-node maps)
+};
+struct GatherMaps : GatherCache {
+  GatherLayout lay{};
+  void release() { dev_free({d_maps}); *this = GatherMaps(); }
+};
+struct Gather10Maps : GatherCache {
+  Gather10Layout lay{};
+  int *d_elist = nullptr;              // this rank's elements
+  double *d_state = nullptr;           // [G][elements of the rank][18]: Gauss-point state records (kernels_gather10.hip)
+  int nloc = 0;
+  void release() { dev_free({d_maps, d_elist, d_state}); *this = Gather10Maps(); }
+};
+
+struct feahip_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+
+  // sizes
+  int N = 0, E = 0, npe = 0, G = 0, ndof = 0;
+  int nnzb = 0;               // 3x3 blocks in the full symmetric pattern
+  int nchunks = 0;
+  int chunk0 = 0, nchunks_local = 0;  // this rank's share of the chunks (row shard)
+  int nachunks = 0, achunk0 = 0, nachunks_local = 0;   // same for the staged kernel's partition
+  std::vector<int> h_super_achunk, h_chunk;
+  // row shard of a multi-rank solve: this rank owns nodes [row0, row1)
+  int rank = 0, nranks = 1, row0 = 0, row1 = 0;
+  struct Transport *tr = nullptr;      // null: single rank, no exchange
+  bool owns_tr = false;
+  std::vector<int> peer, send_off, recv_off;   // halo plan: per peer, ranges into the index lists
+  int nsend = 0, nrecv = 0;
+  int *d_send_idx = nullptr, *d_recv_idx = nullptr;
+  double *d_send_buf = nullptr, *d_recv_buf = nullptr;
+  int max_rowlen = 0;
+  bool linear_tet = false;    // npe == 4 and dN is the constant-strain table
+  int model = 0;
+  double lambda = 0, mu = 0;
+  int strategy = FEAHIP_ASM_AUTO;
+  int last_strategy = FEAHIP_ASM_AUTO;   // what the most recent assembly launch ran
+
+  ElemTable table;
+  ElemTable *d_table = nullptr;
+
+  // mesh (device)
+  int *d_conn = nullptr;       // [E][npe]
+  double *d_X0 = nullptr;      // [N][4] padded to 32 B (two dwordx4 per node)
+  double *d_x = nullptr;       // [N][4] current configuration
+  // block-CSR pattern of K (built once; topology never changes)
+  int *d_rowptr = nullptr;     // [N+1]
+  int *d_colidx = nullptr;     // [nnzb]
+  // K holds the block rows this rank owns and nothing else: blocks [kb0, kb1) = rowptr[row0] .. rowptr[row1] (all of
+  // them for an unsharded context).  It is allocated on first use, for the shard installed by then, so a rank of a
+  // sharded run never holds the other ranks' rows (the reference keeps one row-wise store, fea_solver.c:444-448,
+  // and its modified-Newton copy, :179).  Kernels index by GLOBAL block number through d_K = d_K_base - 9 kb0.
+  double *d_K = nullptr;       // [nnzb][3][3], valid for blocks [kb0, kb1) only
+  double *d_Kstash = nullptr;  // modified-Newton copy (fea_solver.c:179), same window
+  double *d_K_base = nullptr, *d_Kstash_base = nullptr;   // first owned value (block kb0) of each
+  double *d_K_alloc = nullptr, *d_Kstash_alloc = nullptr; // the allocations: d_K_base = d_K_alloc + (kb0 & 1), so that even GLOBAL value indices are 16-byte aligned on every rank
+  long long kb0 = 0, kb1 = 0;
+  bool have_stash = false;
+  int *d_chunk = nullptr;      // [nchunks+1] first row of every chunk
+  int *d_diag = nullptr;       // [N] index of the diagonal block of every row
+  // maps of the assembly strategies (MapCache), built the first time a launch asks for them
+  GenericMaps generic;         // ROWOWNER, ATOMIC
+  VisitMaps visits;            // STAGED
+  QuadMaps quad;               // SHARED
+  GatherMaps gather;           // GATHER of linear tetrahedra
+  Gather10Maps gather10;       // GATHER of 10-node tetrahedra and 8-node bricks
+  // vectors (3N doubles)
+  double *d_f = nullptr, *d_u = nullptr;
+  double *d_r = nullptr, *d_p = nullptr, *d_q = nullptr, *d_minv = nullptr;
+  double *d_part = nullptr;    // reduction partials, 6 x FEA_RED_BLOCKS
+  // single-reduction PCG (kernels_solve.hip): preconditioned residual z = M r and w = K z (allocated on first use);
+  // pcg_variant: -1 = single-reduction when sharded, the reference-shaped two-reduction loop otherwise; 0 / 1 force
+  double *d_z = nullptr, *d_w = nullptr, *d_s = nullptr;
+  int pcg_variant = -1;
+  // SpMV chunks [chunk0 + ichunk_lo, chunk0 + ichunk_hi) of this rank touch no halo column: they run while the halo
+  // rows are in flight (everything, for an unsharded context)
+  int ichunk_lo = 0, ichunk_hi = 0;
+  hipStream_t comm_stream = nullptr;   // RCCL transport: halo exchange beside the interior product
+  hipEvent_t ev_packed = nullptr, ev_unpacked = nullptr;
+  double *d_scal = nullptr;    // device scalars of the CG recurrences
+  int *d_flag = nullptr;       // [0] converged-at iteration, [1] bad Gauss pts
+  // prescribed displacements
+  int n_presc = 0;             // nodes in the deck
+  int n_cdof = 0;              // constrained dofs, deck order x,y,z per node
+  int *d_cdof = nullptr;
+  double *d_cval = nullptr;    // prescribed value per constrained dof
+  uint8_t *d_dofmask = nullptr;// [3N] 1 = constrained
+  // cached per-Gauss-point state for the getters
+  double *d_F = nullptr, *d_S = nullptr;   // [E][G][9]
+  bool state_valid = false;
+
+  // host copies needed by getters / pattern export
+  std::vector<int> h_rowptr, h_colidx;
+  // The maps of a strategy (gather chunks, staged visits, generic incidence lists) are built the first time it is
+  // asked for, from these host copies.
+  std::vector<int> h_conn;
+  struct HostPattern *h_pat = nullptr;
+  bool incslot_ok = false;     // the mesh has incidence slots (row length <= 255)
+
+  int last_bad = 0;
+
+  // library-side node numbering (renumber.cpp): everything in the context -- mesh arrays, pattern, K, vectors, shard
+  // ranges -- lives in the library's numbering; the ABI translates at its boundary.  Empty = the caller's numbering.
+  std::vector<int> perm, iperm;        // perm[caller id] = library id, iperm = its inverse
+  // a rank context (feahip_create_rank): this context IS one rank's sub-mesh, locally indexed; its "caller ids" are the
+  // local ids, rank_node_global / rank_elem_global say which nodes and elements of the whole mesh they are
+  int rank_own = -1;                   // nodes it owns (local ids [0, rank_own)); -1: an ordinary context
+  std::vector<int> rank_node_global, rank_elem_global;
+  int rank_n_global = 0;
+
+  // preconditioner of PCG_ILU / CHOLESKY solves: 0 = 3x3 block-Jacobi, 1 = aggregation multigrid (amg.h)
+  // which matrix d_K holds: bumped by every stiffness assembly, copied by stash / restore; k_bc = prescribed-dof
+  // masking applied since.  Only used to skip numeric re-setup of the multigrid hierarchy for an unchanged K
+  // (modified Newton restores the same matrix every iteration); a stale hierarchy would cost iterations, not accuracy.
+  unsigned long long k_epoch = 0, stash_epoch = 0;
+  bool k_bc = false;
+  // golden-section line search along the Newton step: iterations (0 = off, the reference's solve())
+  int linesearch_max = 0;
+  int precond = 0;
+  void *amg = nullptr;         // AmgHierarchy, built on first use
+};
+
+// calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
+// K alone or f alone -- the three instantiations every assembly kernel has
+template <class F>
+void with_kf(bool doK, bool doF, F &&f)
+{
+  if (doK && doF) f(std::true_type(), std::true_type());
+  else if (doK)   f(std::true_type(), std::false_type());
+  else            f(std::false_type(), std::true_type());
+}
 
 // launchers (kernels_assemble.hip / kernels_patch.hip / kernels_solve.hip)
 int launch_assemble(feahip_ctx *c, bool doK, bool doF);

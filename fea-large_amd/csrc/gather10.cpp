@@ -19,25 +19,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
-
-namespace {
-template <class F>
-void par_chunks10(int n, F f)
-{
-  unsigned hw = std::thread::hardware_concurrency();
-  int nt = (int)std::min<unsigned>(hw ? hw : 4, 32);
-  if (n < 256) nt = 1;
-  if (nt <= 1) { f(0, n); return; }
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) {
-    int lo = (int)((long long)n * t / nt), hi = (int)((long long)n * (t + 1) / nt);
-    th.emplace_back([=] { f(lo, hi); });
-  }
-  for (auto &x : th) x.join();
-}
-inline int up10(int v, int m) { return (v + m - 1) / m * m; }
-}  // namespace
 
 #define Q_RS 0
 #define Q_RD 66
@@ -62,7 +43,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
   // ---- pass A: chunk boundaries by the shortest-path recurrence of gather.cpp (cost = element evaluations)
   const int L = max_rows;
   std::vector<uint16_t> cost((size_t)nrows_all * L, 0xFFFFu);
-  par_chunks10(nrows_all, [&](int lo, int hi) {
+  parallel_ranges(nrows_all, 256, [&](int lo, int hi) {
     for (int i = lo; i < hi; ++i) {
       const int r0 = row_lo + i;
       int nel = 0, ntask = 0, nb = 0, nfl = 0;
@@ -130,7 +111,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
   std::vector<Local> loc((size_t)nch);
   std::vector<char> bad((size_t)nch, 0);
   const int elem_cap = std::max(max_elems, 1);
-  par_chunks10(nch, [&](int lo, int hi) {
+  parallel_ranges(nch, 256, [&](int lo, int hi) {
     std::vector<int> el, tid_of, order;
     std::vector<uint32_t> tp;
     std::vector<std::vector<uint16_t>> lists;
@@ -271,14 +252,14 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
   lay.tile_blocks = tile_blocks;
   lay.o_nodes = 0;
   lay.o_elems = (int)sizeof(Gather10Header);
-  lay.o_rows = lay.o_elems + up10(4 * (FEA_Q_MAX_ELEMS + 1), 64);
-  lay.o_tpos = lay.o_rows + up10(2 * FEA_Q_ROWS_U16, 64);
+  lay.o_rows = lay.o_elems + round_up(4 * (FEA_Q_MAX_ELEMS + 1), 64);
+  lay.o_tpos = lay.o_rows + round_up(2 * FEA_Q_ROWS_U16, 64);
   lay.o_flist = lay.o_tpos + 4 * Q_MAX_TASKS;
-  lay.o_clist = lay.o_flist + up10(4 * lay.max_fdw * FEA_Q_FLANES, 64);
-  lay.stride = up10(lay.o_clist + 4 * lay.max_cw * FEA_Q_THREADS, 128);
+  lay.o_clist = lay.o_flist + round_up(4 * lay.max_fdw * FEA_Q_FLANES, 64);
+  lay.stride = round_up(lay.o_clist + 4 * lay.max_cw * FEA_Q_THREADS, 128);
   if ((long long)nch * lay.stride > 0x7FFFFFFF00LL) return;
   out.blob.assign((size_t)nch * lay.stride, 0);
-  par_chunks10(nch, [&](int lo, int hi) {
+  parallel_ranges(nch, 256, [&](int lo, int hi) {
     for (int p = lo; p < hi; ++p) {
       const Local &Lc = loc[p];
       unsigned char *rec = out.blob.data() + (size_t)p * lay.stride;

@@ -274,7 +274,7 @@ static AsmArgs make_args(feahip_ctx *c)
   A.lambda = c->lambda; A.mu = c->mu;
   A.tab = c->d_table; A.conn = c->d_conn; A.X0 = c->d_X0; A.x = c->d_x;
   A.rowptr = c->d_rowptr; A.colidx = c->d_colidx; A.K = c->d_K; A.f = c->d_f;
-  A.incptr = c->d_incptr; A.inc = c->d_inc; A.incslot = c->d_incslot;
+  A.incptr = c->generic.d_incptr; A.inc = c->generic.d_inc; A.incslot = c->generic.d_incslot;
   A.chunk = c->d_chunk; A.diag = c->d_diag; A.bad = c->d_flag + 1;
   A.Fout = c->d_F; A.Sout = c->d_S; A.Gout = nullptr; A.Dout = nullptr;
   return A;
@@ -284,27 +284,27 @@ template <int NPE, bool LINTET>
 static void launch_rowowner_t(feahip_ctx *c, const AsmArgs &A, bool doK, bool doF)
 {
   const int grid = (c->nchunks_local + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
-  const dim3 blk(64 * FEA_WAVES_PER_WG);
-  if (doK && doF) hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, true, true>), dim3(grid), blk, 0, c->stream, A);
-  else if (doK)   hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, true, false>), dim3(grid), blk, 0, c->stream, A);
-  else            hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, false, true>), dim3(grid), blk, 0, c->stream, A);
+  with_kf(doK, doF, [&](auto K, auto F) {
+    hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, K, F>), dim3(grid), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, A);
+  });
 }
 
 template <int NPE, bool LINTET>
 static void launch_atomic_t(feahip_ctx *c, const AsmArgs &A, bool doK, bool doF)
 {
   const int grid = (c->E + 255) / 256;
-  if (doK && doF) hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, true, true>), dim3(grid), dim3(256), 0, c->stream, A);
-  else if (doK)   hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, true, false>), dim3(grid), dim3(256), 0, c->stream, A);
-  else            hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, false, true>), dim3(grid), dim3(256), 0, c->stream, A);
+  with_kf(doK, doF, [&](auto K, auto F) {
+    hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, K, F>), dim3(grid), dim3(256), 0, c->stream, A);
+  });
 }
 
-int launch_assemble(feahip_ctx *c, bool doK, bool doF)
+static bool rowowner_fits(const feahip_ctx *c) { return c->incslot_ok && c->max_rowlen <= FEA_CHUNK_BLOCKS; }
+
+// The strategy the assembly runs: the one set, or what AUTO chooses, after the residual-only fallbacks; or an error
+// (< 0).  Builds the maps the choice depends on; those of a strategy that is set are built by dispatch_assembly.
+static int resolve_assembly(feahip_ctx *c, bool doK)
 {
-  { const int rc = ensure_k(c); if (rc) return rc; }
-  AsmArgs A = make_args(c);
-  const bool rowowner_ok = c->incslot_ok && c->max_rowlen <= FEA_CHUNK_BLOCKS;
-  int strat = c->strategy;
+  int strat = c->strategy, rc;
   // AUTO: the gather kernels where their maps build and their chunks are compact, the staged visits / the
   // shared-state kernel behind them, the generic row-owner visits or the atomic scatter behind those
   if (strat == FEAHIP_ASM_AUTO) {
@@ -312,83 +312,75 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF)
       // GATHER where the chunks of consecutive rows are compact enough that an element is evaluated at most ~2.5
       // times (locality numberings: bricks, space-filling curves); the staged visits otherwise (measured on the
       // 10M-tet block: 0.97 ms against 1.00 with bricks of 4x2x2 nodes, 1.24 against 1.00 with lexicographic ids)
-      const bool declined = c->gather_declined_row0 == c->row0 && c->gather_declined_row1 == c->row1;
-      if (!declined) { const int rc = ensure_gather(c); if (rc) return rc; }
-      if (!declined && c->have_gather && c->gather_evals_per_element <= 2.5) strat = FEAHIP_ASM_GATHER;
+      GatherMaps &g = c->gather;
+      if (!g.is(MapOutcome::declined, c->row0, c->row1) && (rc = ensure_gather(c))) return rc;
+      if (g.built() && g.evals_per_element <= 2.5) strat = FEAHIP_ASM_GATHER;
       else {
-        if (!declined && c->have_gather) {
+        if (g.built()) {
           // the maps were built to learn what the chunks cost; AUTO does not run them: they do not stay resident
           // (84 B per element), and the sizes reported are those of the kernel that runs
-          (void)hipFree(c->d_gmaps); c->d_gmaps = nullptr;
-          c->have_gather = false; c->ngchunks = 0; c->gather_row0 = c->gather_row1 = -1; c->gather_bytes = 0;
-          c->gather_declined_row0 = c->row0; c->gather_declined_row1 = c->row1;
+          g.release();
+          g.record(MapOutcome::declined, c->row0, c->row1);
         }
-        { const int rc = ensure_visits(c); if (rc) return rc; }
-        if (c->have_visits) strat = FEAHIP_ASM_STAGED;
+        if ((rc = ensure_visits(c))) return rc;
+        if (c->visits.built()) strat = FEAHIP_ASM_STAGED;
       }
     }
     if (strat == FEAHIP_ASM_AUTO && (c->npe == 10 || c->npe == 8)) {
       // 10-node tetrahedra, 8-node bricks: gather chunks of up to 64 rows where the numbering keeps them compact (an element's
       // records are expanded in ~3 chunks with a brick numbering; lexicographic ids on the 497 664-element block: ~7
       // chunks, 1.42 ms against the 2.27 of the shared-state kernel, whose 3-row chunks evaluate an element 8 times)
-      { const int rc = ensure_gather10(c); if (rc) return rc; }
-      if (c->have_gather && c->gather_evals_per_element <= 12.0) strat = FEAHIP_ASM_GATHER;
+      if ((rc = ensure_gather10(c))) return rc;
+      if (c->gather10.built() && c->gather10.evals_per_element <= 12.0) strat = FEAHIP_ASM_GATHER;
     }
-    if (strat == FEAHIP_ASM_AUTO && c->npe == 10) { const int rc = ensure_quad(c); if (rc) return rc; }
+    if (strat == FEAHIP_ASM_AUTO && c->npe == 10 && (rc = ensure_quad(c))) return rc;
     if (strat == FEAHIP_ASM_AUTO)
-      strat = (c->have_quad && doK) ? FEAHIP_ASM_SHARED : (rowowner_ok ? FEAHIP_ASM_ROWOWNER : FEAHIP_ASM_ATOMIC);
+      strat = (c->quad.built() && doK) ? FEAHIP_ASM_SHARED : (rowowner_fits(c) ? FEAHIP_ASM_ROWOWNER : FEAHIP_ASM_ATOMIC);
   }
-  if (strat == FEAHIP_ASM_SHARED) { const int rc = ensure_quad(c); if (rc) return rc; }
-  if (strat == FEAHIP_ASM_SHARED && !doK && c->have_quad) strat = rowowner_ok ? FEAHIP_ASM_ROWOWNER : FEAHIP_ASM_ATOMIC;   // residual alone: visit kernel
-  c->last_strategy = strat;                          // the kernel that runs, after the residual-only fallbacks
-  if (strat == FEAHIP_ASM_SHARED) {
-    if (!c->have_quad) {
-      c->err = "shared-state assembly needs 10-node elements whose chunks fit the LDS tiles";
-      return FEAHIP_EINVAL;
-    }
-    FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag + 1, 0, sizeof(int), c->stream));
-    return launch_assemble_quad(c, doF);
-  }
-  if (strat == FEAHIP_ASM_GATHER && (c->npe == 10 || c->npe == 8)) {
-    { const int rc = ensure_gather10(c); if (rc) return rc; }
-    if (!c->have_gather) {
-      c->err = "gather assembly of 10-node tetrahedra / 8-node bricks needs rows that fit the LDS tiles";
-      return FEAHIP_EINVAL;
-    }
-    if (doK) FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag + 1, 0, sizeof(int), c->stream));
-    return launch_assemble_gather10(c, doK, doF);
-  }
-  if (strat == FEAHIP_ASM_GATHER) {
-    { const int rc = ensure_gather(c); if (rc) return rc; }
-    if (!c->have_gather) {
-      c->err = "gather assembly needs linear tetrahedra (one Gauss point) whose rows fit the LDS tiles";
-      return FEAHIP_EINVAL;
-    }
-    if (doK) FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag + 1, 0, sizeof(int), c->stream));
-    return launch_assemble_gather(c, doK, doF);
-  }
-  if (strat == FEAHIP_ASM_PAIRED || strat == FEAHIP_ASM_PATCH || strat == FEAHIP_ASM_PIPELINED) {
-    c->err = "this assembly strategy was retired (measured slower than the staged visits and the gather kernel: DESIGN.md)";
-    return FEAHIP_EINVAL;
-  }
-  if (strat == FEAHIP_ASM_STAGED) {
-    { const int rc = ensure_visits(c); if (rc) return rc; }
-    if (!c->have_visits) {
-      c->err = "staged assembly needs linear tetrahedra whose chunks fit the LDS tiles";
-      return FEAHIP_EINVAL;
-    }
-    if (doK) FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag + 1, 0, sizeof(int), c->stream));
-    return launch_assemble_visit(c, doK, doF);
-  }
-  { const int rc = ensure_generic_maps(c); if (rc) return rc; }     // the generic kernels walk the incidence lists
-  A.incptr = c->d_incptr; A.inc = c->d_inc; A.incslot = c->d_incslot;
-  if (strat == FEAHIP_ASM_ROWOWNER && !rowowner_ok) {
-    c->err = "row-owner assembly needs block rows of at most " +
-             std::to_string(FEA_CHUNK_BLOCKS) + " blocks (mesh has " +
-             std::to_string(c->max_rowlen) + ")";
-    return FEAHIP_EINVAL;
+  if (strat == FEAHIP_ASM_SHARED && (rc = ensure_quad(c))) return rc;
+  if (strat == FEAHIP_ASM_SHARED && !doK && c->quad.built())     // residual alone: visit kernel
+    strat = rowowner_fits(c) ? FEAHIP_ASM_ROWOWNER : FEAHIP_ASM_ATOMIC;
+  return strat;
+}
+
+// Builds the maps of the strategy resolve_assembly chose, checks that it can run here, and launches it.
+static int dispatch_assembly(feahip_ctx *c, int strat, bool doK, bool doF)
+{
+  const bool gather10 = c->npe == 10 || c->npe == 8;
+  auto refuse = [c](std::string why) { c->err = std::move(why); return FEAHIP_EINVAL; };
+  int rc;
+  switch (strat) {
+  case FEAHIP_ASM_SHARED:
+    if (!c->quad.built()) return refuse("shared-state assembly needs 10-node elements whose chunks fit the LDS tiles");
+    break;
+  case FEAHIP_ASM_GATHER:
+    if ((rc = gather10 ? ensure_gather10(c) : ensure_gather(c))) return rc;
+    if (gather10 && !c->gather10.built())
+      return refuse("gather assembly of 10-node tetrahedra / 8-node bricks needs rows that fit the LDS tiles");
+    if (!gather10 && !c->gather.built())
+      return refuse("gather assembly needs linear tetrahedra (one Gauss point) whose rows fit the LDS tiles");
+    break;
+  case FEAHIP_ASM_PAIRED:
+  case FEAHIP_ASM_PATCH:
+  case FEAHIP_ASM_PIPELINED:
+    return refuse("this assembly strategy was retired (measured slower than the staged visits and the gather kernel: DESIGN.md)");
+  case FEAHIP_ASM_STAGED:
+    if ((rc = ensure_visits(c))) return rc;
+    if (!c->visits.built()) return refuse("staged assembly needs linear tetrahedra whose chunks fit the LDS tiles");
+    break;
+  default:                                           // ROWOWNER, ATOMIC: the generic kernels walk the incidence lists
+    if ((rc = ensure_generic_maps(c))) return rc;
+    if (strat == FEAHIP_ASM_ROWOWNER && !rowowner_fits(c))
+      return refuse("row-owner assembly needs block rows of at most " + std::to_string(FEA_CHUNK_BLOCKS) +
+                    " blocks (mesh has " + std::to_string(c->max_rowlen) + ")");
   }
   if (doK) FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag + 1, 0, sizeof(int), c->stream));
+  switch (strat) {
+  case FEAHIP_ASM_SHARED: return launch_assemble_quad(c, doF);
+  case FEAHIP_ASM_GATHER: return gather10 ? launch_assemble_gather10(c, doK, doF) : launch_assemble_gather(c, doK, doF);
+  case FEAHIP_ASM_STAGED: return launch_assemble_visit(c, doK, doF);
+  }
+  const AsmArgs A = make_args(c);
   if (strat == FEAHIP_ASM_ATOMIC) {
     if (doK) FEA_HIP_CHECK(c, hipMemsetAsync(c->d_K_base, 0, sizeof(double) * 9 * (size_t)(c->kb1 - c->kb0), c->stream));
     if (doF) FEA_HIP_CHECK(c, hipMemsetAsync(c->d_f, 0, sizeof(double) * (size_t)c->ndof, c->stream));
@@ -402,6 +394,15 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF)
   }
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
+}
+
+int launch_assemble(feahip_ctx *c, bool doK, bool doF)
+{
+  if (const int rc = ensure_k(c)) return rc;
+  const int strat = resolve_assembly(c, doK);
+  if (strat < 0) return strat;
+  c->last_strategy = strat;                          // the kernel that runs, after the residual-only fallbacks
+  return dispatch_assembly(c, strat, doK, doF);
 }
 
 int launch_state_export(feahip_ctx *c, double *d_grads, double *d_detj)

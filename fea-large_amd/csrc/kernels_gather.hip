@@ -314,26 +314,23 @@ void k_assemble_gather(GatherArgs A, int run_len)
 
 int ensure_gather(feahip_ctx *c)
 {
-  if (c->have_gather && c->gather_row0 == c->row0 && c->gather_row1 == c->row1) return FEAHIP_OK;
+  GatherMaps &g = c->gather;
+  if (g.settled(c->row0, c->row1)) return FEAHIP_OK;
   if (!c->h_pat || c->h_conn.empty() || !c->linear_tet || c->G != 1) return FEAHIP_OK;
   // a new row range (re-shard): the old maps describe rows K no longer holds (release_k re-allocates the window), so
-  // they go before anything else can launch them -- also when the new range is known not to fit, or turns out not to
-  if (c->d_gmaps) { (void)hipFree(c->d_gmaps); c->d_gmaps = nullptr; }
-  c->have_gather = false; c->ngchunks = 0; c->gather_row0 = c->gather_row1 = -1;
-  if (c->gather_failed && c->gather_fail_row0 == c->row0 && c->gather_fail_row1 == c->row1) return FEAHIP_OK;
+  // they go before anything else can launch them -- also when the new range turns out not to fit
+  g.release();
   HostGather hg;
   build_host_gather(c->N, c->E, c->h_conn.data(), *c->h_pat, c->row0, c->row1, hg);
-  if (!hg.ok) { c->gather_failed = true; c->gather_fail_row0 = c->row0; c->gather_fail_row1 = c->row1; return FEAHIP_OK; }   // this row range only: another shard of the same context may fit
-  FEA_HIP_CHECK(c, hipMalloc((void **)&c->d_gmaps, hg.blob.size() ? hg.blob.size() : 1));
-  FEA_HIP_CHECK(c, hipMemcpy(c->d_gmaps, hg.blob.data(), hg.blob.size(), hipMemcpyHostToDevice));
-  if (!c->gather_lay) c->gather_lay = new GatherLayout();
-  *c->gather_lay = hg.lay;
-  c->ngchunks = hg.nchunks;
-  c->gather_row0 = c->row0; c->gather_row1 = c->row1;
-  c->gather_bytes = (long long)hg.blob.size();
-  c->gather_evals_per_element = hg.distinct_elems ? (double)hg.total_evals / (double)hg.distinct_elems : 0.0;
-  c->gather_same_words = hg.same_as_previous;
-  c->have_gather = true;
+  if (!hg.ok) { g.record(MapOutcome::failed, c->row0, c->row1); return FEAHIP_OK; }   // this row range only: another shard of the same context may fit
+  FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_maps, hg.blob.size() ? hg.blob.size() : 1));
+  FEA_HIP_CHECK(c, hipMemcpy(g.d_maps, hg.blob.data(), hg.blob.size(), hipMemcpyHostToDevice));
+  g.lay = hg.lay;
+  g.nchunks = hg.nchunks;
+  g.bytes = (long long)hg.blob.size();
+  g.evals_per_element = hg.distinct_elems ? (double)hg.total_evals / (double)hg.distinct_elems : 0.0;
+  g.same_words = hg.same_as_previous;
+  g.record(MapOutcome::built, c->row0, c->row1);
   return FEAHIP_OK;
 }
 
@@ -342,32 +339,34 @@ int ensure_gather(feahip_ctx *c)
 extern "C" int feahip_debug_gather_record(feahip_ctx *c, int chunk, int *layout_ints, unsigned char *record)
 {
   int rc = ensure_gather(c);
-  if (rc || !c->have_gather) return FEAHIP_ESTATE;
-  if (chunk < 0) chunk = c->ngchunks / 2;
-  memcpy(layout_ints, c->gather_lay, sizeof(GatherLayout));
-  if (record) (void)hipMemcpy(record, c->d_gmaps + (size_t)chunk * c->gather_lay->stride, c->gather_lay->stride, hipMemcpyDeviceToHost);
+  const GatherMaps &g = c->gather;
+  if (rc || !g.built()) return FEAHIP_ESTATE;
+  if (chunk < 0) chunk = g.nchunks / 2;
+  memcpy(layout_ints, &g.lay, sizeof(GatherLayout));
+  if (record) (void)hipMemcpy(record, g.d_maps + (size_t)chunk * g.lay.stride, g.lay.stride, hipMemcpyDeviceToHost);
   return (int)(sizeof(GatherLayout) / sizeof(int));
 }
 #endif
 
 int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
 {
+  const GatherMaps &g = c->gather;
   GatherArgs A;
-  A.chunk0 = 0; A.nchunks = c->ngchunks; A.model = c->model; A.lambda = c->lambda; A.mu = c->mu;
-  A.tab = c->d_table; A.maps = c->d_gmaps; A.lay = *c->gather_lay; A.X0 = c->d_X0; A.x = c->d_x;
+  A.chunk0 = 0; A.nchunks = g.nchunks; A.model = c->model; A.lambda = c->lambda; A.mu = c->mu;
+  A.tab = c->d_table; A.maps = g.d_maps; A.lay = g.lay; A.X0 = c->d_X0; A.x = c->d_x;
   A.K = c->d_K; A.f = c->d_f; A.bad = c->d_flag + 1; A.stamps = nullptr; A.ablate = 0;
-  if (c->ngchunks <= 0) return FEAHIP_OK;
+  if (g.nchunks <= 0) return FEAHIP_OK;
 #ifdef FEAHIP_DEBUG
   static unsigned long long *d_stamps = nullptr;
   static int stamps_cap = 0;
   { const char *e = getenv("FEAHIP_GATHER_ABLATE"); A.ablate = e ? atoi(e) : 0; }
   const char *dbg = getenv("FEAHIP_GATHER_STAMPS");
   if (dbg && atoi(dbg)) {
-    if (!d_stamps || stamps_cap < c->ngchunks) {
+    if (!d_stamps || stamps_cap < g.nchunks) {
       if (d_stamps) (void)hipFree(d_stamps);
-      (void)hipMalloc((void **)&d_stamps, sizeof(unsigned long long) * 8 * (FEA_G_THREADS / 64) * (size_t)c->ngchunks);
-      (void)hipMemset(d_stamps, 0, sizeof(unsigned long long) * 8 * (FEA_G_THREADS / 64) * (size_t)c->ngchunks);
-      stamps_cap = c->ngchunks;
+      (void)hipMalloc((void **)&d_stamps, sizeof(unsigned long long) * 8 * (FEA_G_THREADS / 64) * (size_t)g.nchunks);
+      (void)hipMemset(d_stamps, 0, sizeof(unsigned long long) * 8 * (FEA_G_THREADS / 64) * (size_t)g.nchunks);
+      stamps_cap = g.nchunks;
     }
     A.stamps = d_stamps;
   }
@@ -387,28 +386,27 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
   else if (FEA_G_BIG == 1) {
     long best = -1;
     for (int k = 2; k >= 1; --k) {
-      const int rl = std::max(1, (c->ngchunks + k * ncu - 1) / (k * ncu)), nr = (c->ngchunks + rl - 1) / rl;
+      const int rl = std::max(1, (g.nchunks + k * ncu - 1) / (k * ncu)), nr = (g.nchunks + rl - 1) / rl;
       const long cost = (long)((nr + ncu - 1) / ncu) * rl;
       if (best < 0 || cost < best) { best = cost; run_len = rl; }
     }
   }
-  const int nruns = (c->ngchunks + run_len - 1) / run_len;
+  const int nruns = (g.nchunks + run_len - 1) / run_len;
   const dim3 grid((nruns + 7) & ~7), blk(FEA_G_THREADS);
   // LDS: coordinates (48 bytes per node slot) | element records, later the K tile (+1 double of alignment slack) and the residual partials
   const int regK = std::max(A.lay.max_elems * GREC, ((A.lay.max_tile * 9 + 3) & ~1) + 3 * FEA_G_THREADS);
   const int regF = std::max(A.lay.max_elems * GREC_F, 3 * FEA_G_THREADS);
   const int ldsK = A.lay.max_nodes * 48 + ((regK + 1) & ~1) * 8, ldsF = A.lay.max_nodes * 48 + ((regF + 1) & ~1) * 8;
   const bool nh = c->model == FEAHIP_MODEL_COMPRESSIBLE_NEOHOOKEAN;
-#define G_LAUNCH(K, F, M, LDS)                                                                                         \
-  do {                                                                                                               \
-    FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M>),                \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS));                         \
-    hipLaunchKernelGGL((k_assemble_gather<K, F, M>), grid, blk, LDS, c->stream, A, run_len);                                  \
-  } while (0)
-  if (doK && doF) { if (nh) G_LAUNCH(true, true, true, ldsK); else G_LAUNCH(true, true, false, ldsK); }
-  else if (doK)   { if (nh) G_LAUNCH(true, false, true, ldsK); else G_LAUNCH(true, false, false, ldsK); }
-  else            { if (nh) G_LAUNCH(false, true, true, ldsF); else G_LAUNCH(false, true, false, ldsF); }
-#undef G_LAUNCH
+  auto launch = [&](auto K, auto F, auto M) -> int {
+    const int lds = K ? ldsK : ldsF;
+    FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((k_assemble_gather<K, F, M>), grid, blk, lds, c->stream, A, run_len);
+    return FEAHIP_OK;
+  };
+  int rc;
+  with_kf(doK, doF, [&](auto K, auto F) { rc = nh ? launch(K, F, std::true_type()) : launch(K, F, std::false_type()); });
+  if (rc) return rc;
   FEA_HIP_CHECK(c, hipGetLastError());
 #ifdef FEAHIP_DEBUG
   if (A.stamps) {
@@ -416,7 +414,7 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
     if (++calls == 50) {
       (void)hipStreamSynchronize(c->stream);
       constexpr int NW = FEA_G_THREADS / 64;
-      std::vector<unsigned long long> hst((size_t)c->ngchunks * 8 * NW);
+      std::vector<unsigned long long> hst((size_t)g.nchunks * 8 * NW);
       (void)hipMemcpy(hst.data(), A.stamps, hst.size() * 8, hipMemcpyDeviceToHost);
       double sum[NW][8] = {};
       for (int i = 0; i < nruns; ++i)
@@ -426,8 +424,8 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
               sum[0][7] > 0 ? 100.0 * sum[0][6] / sum[0][7] : 0.0, sum[0][6] / nruns, run_len);
       for (int w = 0; w < NW; w += (NW > 4 ? 5 : 1))
         fprintf(stderr, "[gather stamps K=%d F=%d wave %d, per chunk] state %.0f  gather %.0f  barrier B %.0f  tile writes %.0f  wait for the prefetched words + coordinates + barrier C %.0f  rows out (+ barrier D) %.0f cycles\n",
-                (int)doK, (int)doF, w, sum[w][0] / c->ngchunks, sum[w][1] / c->ngchunks, sum[w][2] / c->ngchunks, sum[w][3] / c->ngchunks,
-                sum[w][4] / c->ngchunks, sum[w][5] / c->ngchunks);
+                (int)doK, (int)doF, w, sum[w][0] / g.nchunks, sum[w][1] / g.nchunks, sum[w][2] / g.nchunks, sum[w][3] / g.nchunks,
+                sum[w][4] / g.nchunks, sum[w][5] / g.nchunks);
     }
   }
 #endif

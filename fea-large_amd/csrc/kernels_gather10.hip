@@ -472,36 +472,31 @@ void k_assemble_gather10(G10Args A, int run_len)
 
 int ensure_gather10(feahip_ctx *c)
 {
-  if (c->have_gather && c->gather10_lay && c->gather_row0 == c->row0 && c->gather_row1 == c->row1) return FEAHIP_OK;
+  Gather10Maps &g = c->gather10;
+  if (g.settled(c->row0, c->row1)) return FEAHIP_OK;
   if (!c->h_pat || c->h_conn.empty() || (c->npe != 10 && c->npe != 8) || c->G > T_GMAX) return FEAHIP_OK;
   // a new row range (re-shard): the old maps describe rows K no longer holds (release_k re-allocates the window), so
-  // they go before anything else can launch them -- also when the new range is known not to fit, or turns out not to
-  for (void *p : {(void *)c->d_gmaps, (void *)c->d_g10_elist, (void *)c->d_g10_state})
-    if (p) (void)hipFree(p);
-  c->d_gmaps = nullptr; c->d_g10_elist = nullptr; c->d_g10_state = nullptr;
-  c->have_gather = false; c->ngchunks = 0; c->g10_nloc = 0; c->gather_row0 = c->gather_row1 = -1;
-  if (c->gather_failed && c->gather_fail_row0 == c->row0 && c->gather_fail_row1 == c->row1) return FEAHIP_OK;
+  // they go before anything else can launch them -- also when the new range turns out not to fit
+  g.release();
   HostGather10 hg;
   build_host_gather10(c->N, c->E, c->npe, c->h_conn.data(), *c->h_pat, c->row0, c->row1, hg);
-  if (!hg.ok) { c->gather_failed = true; c->gather_fail_row0 = c->row0; c->gather_fail_row1 = c->row1; return FEAHIP_OK; }   // this row range only: another shard of the same context may fit
-  c->g10_nloc = (int)hg.elist.size();
-  const size_t state_bytes = sizeof(double) * T_HDR * (size_t)c->G * (size_t)std::max(c->g10_nloc, 1);
-  FEA_HIP_CHECK(c, hipMalloc((void **)&c->d_gmaps, hg.blob.size() ? hg.blob.size() : 1));
-  FEA_HIP_CHECK(c, hipMemcpy(c->d_gmaps, hg.blob.data(), hg.blob.size(), hipMemcpyHostToDevice));
-  FEA_HIP_CHECK(c, hipMalloc((void **)&c->d_g10_elist, sizeof(int) * (size_t)std::max(c->g10_nloc, 1)));
-  FEA_HIP_CHECK(c, hipMemcpy(c->d_g10_elist, hg.elist.data(), sizeof(int) * hg.elist.size(), hipMemcpyHostToDevice));
-  FEA_HIP_CHECK(c, hipMalloc((void **)&c->d_g10_state, state_bytes));
-  FEA_HIP_CHECK(c, hipMemset(c->d_g10_state, 0, state_bytes));
-  if (!c->gather10_lay) c->gather10_lay = new Gather10Layout();
-  *c->gather10_lay = hg.lay;
-  c->ngchunks = hg.nchunks;
-  c->gather_row0 = c->row0; c->gather_row1 = c->row1;
-  c->gather_bytes = (long long)hg.blob.size() + (long long)state_bytes + 4LL * c->g10_nloc;
-  c->gather_evals_per_element = hg.distinct_elems ? (double)hg.total_evals / (double)hg.distinct_elems : 0.0;
-  c->have_gather = true;
+  if (!hg.ok) { g.record(MapOutcome::failed, c->row0, c->row1); return FEAHIP_OK; }   // this row range only: another shard of the same context may fit
+  g.nloc = (int)hg.elist.size();
+  const size_t state_bytes = sizeof(double) * T_HDR * (size_t)c->G * (size_t)std::max(g.nloc, 1);
+  FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_maps, hg.blob.size() ? hg.blob.size() : 1));
+  FEA_HIP_CHECK(c, hipMemcpy(g.d_maps, hg.blob.data(), hg.blob.size(), hipMemcpyHostToDevice));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_elist, sizeof(int) * (size_t)std::max(g.nloc, 1)));
+  FEA_HIP_CHECK(c, hipMemcpy(g.d_elist, hg.elist.data(), sizeof(int) * hg.elist.size(), hipMemcpyHostToDevice));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_state, state_bytes));
+  FEA_HIP_CHECK(c, hipMemset(g.d_state, 0, state_bytes));
+  g.lay = hg.lay;
+  g.nchunks = hg.nchunks;
+  g.bytes = (long long)hg.blob.size() + (long long)state_bytes + 4LL * g.nloc;
+  g.evals_per_element = hg.distinct_elems ? (double)hg.total_evals / (double)hg.distinct_elems : 0.0;
+  g.record(MapOutcome::built, c->row0, c->row1);
 #ifdef FEAHIP_DEBUG
   fprintf(stderr, "[gather10] %d chunks over %d rows, an element in %.2f chunks, map record %d bytes, max elems %d list rows %d visit words %d tile %d blocks, %d elements\n",
-          hg.nchunks, c->row1 - c->row0, c->gather_evals_per_element, hg.lay.stride, hg.lay.max_elems, hg.lay.max_cw, hg.lay.max_fdw, hg.lay.tile_blocks, c->g10_nloc);
+          hg.nchunks, c->row1 - c->row0, g.evals_per_element, hg.lay.stride, hg.lay.max_elems, hg.lay.max_cw, hg.lay.max_fdw, hg.lay.tile_blocks, g.nloc);
 #endif
   return FEAHIP_OK;
 }
@@ -513,32 +508,33 @@ static int gather10_lds_bytes(const Gather10Layout &lay, int G, int npe)
 
 int launch_assemble_gather10(feahip_ctx *c, bool doK, bool doF)
 {
-  if (c->ngchunks <= 0) return FEAHIP_OK;
+  const Gather10Maps &g = c->gather10;
+  if (g.nchunks <= 0) return FEAHIP_OK;
   {
     S10Args S;
-    S.nloc = c->g10_nloc; S.G = c->G; S.model = c->model; S.row0 = c->row0; S.row1 = c->row1; S.lambda = c->lambda; S.mu = c->mu;
-    S.tab = c->d_table; S.elist = c->d_g10_elist; S.conn = c->d_conn; S.X0 = c->d_X0; S.x = c->d_x;
-    S.state = c->d_g10_state; S.bad = doK ? c->d_flag + 1 : nullptr;      // the counter is reset by stiffness assemblies only
-    if (c->g10_nloc > 0) {
-      if (c->npe == 10) hipLaunchKernelGGL(k_state10<10>, dim3((unsigned)((c->g10_nloc + 255) / 256)), dim3(256), 0, c->stream, S);
-      else              hipLaunchKernelGGL(k_state10<8>, dim3((unsigned)((c->g10_nloc + 255) / 256)), dim3(256), 0, c->stream, S);
+    S.nloc = g.nloc; S.G = c->G; S.model = c->model; S.row0 = c->row0; S.row1 = c->row1; S.lambda = c->lambda; S.mu = c->mu;
+    S.tab = c->d_table; S.elist = g.d_elist; S.conn = c->d_conn; S.X0 = c->d_X0; S.x = c->d_x;
+    S.state = g.d_state; S.bad = doK ? c->d_flag + 1 : nullptr;      // the counter is reset by stiffness assemblies only
+    if (g.nloc > 0) {
+      if (c->npe == 10) hipLaunchKernelGGL(k_state10<10>, dim3((unsigned)((g.nloc + 255) / 256)), dim3(256), 0, c->stream, S);
+      else              hipLaunchKernelGGL(k_state10<8>, dim3((unsigned)((g.nloc + 255) / 256)), dim3(256), 0, c->stream, S);
     }
   }
   G10Args A;
-  A.nchunks = c->ngchunks; A.G = c->G; A.tab = c->d_table; A.maps = c->d_gmaps; A.lay = *c->gather10_lay;
-  A.state = c->d_g10_state; A.nloc = c->g10_nloc; A.K = c->d_K; A.f = c->d_f; A.stamps = nullptr;
+  A.nchunks = g.nchunks; A.G = c->G; A.tab = c->d_table; A.maps = g.d_maps; A.lay = g.lay;
+  A.state = g.d_state; A.nloc = g.nloc; A.K = c->d_K; A.f = c->d_f; A.stamps = nullptr;
 #ifdef FEAHIP_DEBUG
   static unsigned long long *d_stamps = nullptr;
   static int cap = 0;
   if (getenv("FEAHIP_GATHER10_STAMPS")) {
-    if (!d_stamps || cap < c->ngchunks) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void **)&d_stamps, 8 * 32 * (size_t)c->ngchunks); cap = c->ngchunks; }
-    (void)hipMemset(d_stamps, 0, 8 * 32 * (size_t)c->ngchunks);
+    if (!d_stamps || cap < g.nchunks) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void **)&d_stamps, 8 * 32 * (size_t)g.nchunks); cap = g.nchunks; }
+    (void)hipMemset(d_stamps, 0, 8 * 32 * (size_t)g.nchunks);
     A.stamps = d_stamps;
   }
 #endif
   static int run_len = -1;           // chunks per workgroup run (FEAHIP_GATHER10_RUN: tuning only, results unchanged)
   if (run_len < 0) { const char *e = getenv("FEAHIP_GATHER10_RUN"); run_len = e && atoi(e) > 0 ? atoi(e) : 2; }
-  const int nruns = (c->ngchunks + run_len - 1) / run_len;
+  const int nruns = (g.nchunks + run_len - 1) / run_len;
   const dim3 grid((nruns + 7) & ~7), blk(FEA_Q_THREADS);
   const int lds = gather10_lds_bytes(A.lay, c->G, c->npe);
   const bool tl = c->G <= T_GLDS;
@@ -558,13 +554,13 @@ int launch_assemble_gather10(feahip_ctx *c, bool doK, bool doF)
     static int calls = 0;
     if (++calls == 8) {
       (void)hipStreamSynchronize(c->stream);
-      std::vector<unsigned long long> h((size_t)c->ngchunks * 8 * FEA_Q_WAVES);
+      std::vector<unsigned long long> h((size_t)g.nchunks * 8 * FEA_Q_WAVES);
       (void)hipMemcpy(h.data(), A.stamps, h.size() * 8, hipMemcpyDeviceToHost);
       for (int w = 0; w < 4; ++w) {
         double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < nruns; ++i) for (int q = 0; q < 8; ++q) sum[q] += (double)h[((size_t)i * FEA_Q_WAVES + w) * 8 + q];
         fprintf(stderr, "[gather10 stamps wave %d, per chunk] stage %.0f  state wait %.0f  expand %.0f  barrier %.0f  gather %.0f  barrier %.0f  partials+barrier %.0f  write-out %.0f\n",
-                w, sum[0] / c->ngchunks, sum[7] / c->ngchunks, sum[1] / c->ngchunks, sum[2] / c->ngchunks, sum[3] / c->ngchunks, sum[4] / c->ngchunks, sum[5] / c->ngchunks, sum[6] / c->ngchunks);
+                w, sum[0] / g.nchunks, sum[7] / g.nchunks, sum[1] / g.nchunks, sum[2] / g.nchunks, sum[3] / g.nchunks, sum[4] / g.nchunks, sum[5] / g.nchunks, sum[6] / g.nchunks);
       }
     }
   }

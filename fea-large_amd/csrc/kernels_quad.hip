@@ -334,40 +334,40 @@ void k_assemble_quad(QuadArgs A, int run_len)
 int launch_assemble_quad(feahip_ctx *c, bool doF)
 {
   if (c->npe != 10) { c->err = "shared-state assembly is built for 10-node elements"; return FEAHIP_EINVAL; }
+  const QuadMaps &q = c->quad;
   QuadArgs A;
-  A.chunk0 = 0; A.nchunks = c->quad_n; A.model = c->model; A.G = c->G;      // the maps hold this rank's chunks only
-  A.lambda = c->lambda; A.mu = c->mu; A.tab = c->d_table; A.desc = c->d_qdesc; A.qelem = c->d_qelem; A.qpair = c->d_qpair;
-  A.qnode = c->d_qnode; A.X0 = c->d_X0; A.x = c->d_x; A.rowptr = c->d_rowptr; A.diag = c->d_diag;
+  A.chunk0 = 0; A.nchunks = q.nchunks; A.model = c->model; A.G = c->G;      // the maps hold this rank's chunks only
+  A.lambda = c->lambda; A.mu = c->mu; A.tab = c->d_table; A.desc = q.d_desc; A.qelem = q.d_elem; A.qpair = q.d_pair;
+  A.qnode = q.d_node; A.X0 = c->d_X0; A.x = c->d_x; A.rowptr = c->d_rowptr; A.diag = c->d_diag;
   A.K = c->d_K; A.f = c->d_f; A.bad = c->d_flag + 1; A.stamps = nullptr;
-  if (c->quad_n <= 0) return FEAHIP_OK;
+  if (q.nchunks <= 0) return FEAHIP_OK;
 #ifdef FEAHIP_DEBUG
   static unsigned long long *d_stamps = nullptr;
   static int cap = 0;
   if (getenv("FEAHIP_QUAD_STAMPS")) {
-    if (!d_stamps || cap < c->quad_n) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void **)&d_stamps, 8 * 32 * (size_t)c->quad_n); cap = c->quad_n; }
-    (void)hipMemset(d_stamps, 0, 8 * 32 * (size_t)c->quad_n);
+    if (!d_stamps || cap < q.nchunks) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void **)&d_stamps, 8 * 32 * (size_t)q.nchunks); cap = q.nchunks; }
+    (void)hipMemset(d_stamps, 0, 8 * 32 * (size_t)q.nchunks);
     A.stamps = d_stamps;
   }
 #endif
   static int run_len = -1;           // chunks per workgroup run (FEAHIP_QUAD_RUN: tuning only, results unchanged)
   if (run_len < 0) { const char *e = getenv("FEAHIP_QUAD_RUN"); run_len = e && atoi(e) > 0 ? atoi(e) : 16; }
-  const int nruns = (c->quad_n + run_len - 1) / run_len;
+  const int nruns = (q.nchunks + run_len - 1) / run_len;
   const dim3 grid((nruns + 7) & ~7), blk(QUAD_NT);
-  if (doF) hipLaunchKernelGGL((k_assemble_quad<10, true>), grid, blk, 0, c->stream, A, run_len);
-  else     hipLaunchKernelGGL((k_assemble_quad<10, false>), grid, blk, 0, c->stream, A, run_len);
+  with_kf(true, doF, [&](auto, auto F) { hipLaunchKernelGGL((k_assemble_quad<10, F>), grid, blk, 0, c->stream, A, run_len); });
   FEA_HIP_CHECK(c, hipGetLastError());
 #ifdef FEAHIP_DEBUG
   if (A.stamps) {
     static int calls = 0;
     if (++calls == 8) {
       (void)hipStreamSynchronize(c->stream);
-      std::vector<unsigned long long> h((size_t)c->quad_n * 32);
+      std::vector<unsigned long long> h((size_t)q.nchunks * 32);
       (void)hipMemcpy(h.data(), A.stamps, h.size() * 8, hipMemcpyDeviceToHost);
       for (int w = 0; w < 4; ++w) {
         double sum[7] = {0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < nruns; ++i) for (int q = 0; q < 7; ++q) sum[q] += (double)h[((size_t)i * 4 + w) * 8 + q];
         fprintf(stderr, "[quad stamps wave %d, per chunk] setup %.0f  batch-top(sync+table) %.0f  state %.0f  barrier %.0f  pairs %.0f  barrier %.0f  diag+writeout %.0f\n",
-                w, sum[0] / c->quad_n, sum[1] / c->quad_n, sum[2] / c->quad_n, sum[3] / c->quad_n, sum[4] / c->quad_n, sum[5] / c->quad_n, sum[6] / c->quad_n);
+                w, sum[0] / q.nchunks, sum[1] / q.nchunks, sum[2] / q.nchunks, sum[3] / q.nchunks, sum[4] / q.nchunks, sum[5] / q.nchunks, sum[6] / q.nchunks);
       }
     }
   }

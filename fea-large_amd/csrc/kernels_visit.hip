@@ -187,9 +187,9 @@ int launch_assemble_visit(feahip_ctx *c, bool doK, bool doF)
 {
   VisitArgs A;
   A.chunk0 = c->achunk0; A.nchunks = c->nachunks_local; A.model = c->model;
-  A.lambda = c->lambda; A.mu = c->mu; A.tab = c->d_table; A.desc = c->d_vdesc; A.vnode = c->d_vnode;
-  A.vrec = reinterpret_cast<const uint2 *>(c->d_vrec); A.X0 = c->d_X0; A.x = c->d_x;
-  A.rowptr = c->d_rowptr; A.diag = c->d_diag; A.nvisits = c->nvisit_records; A.nrows_total = c->N; A.K = c->d_K; A.f = c->d_f; A.bad = c->d_flag + 1;
+  A.lambda = c->lambda; A.mu = c->mu; A.tab = c->d_table; A.desc = c->visits.d_desc; A.vnode = c->visits.d_node;
+  A.vrec = reinterpret_cast<const uint2 *>(c->visits.d_rec); A.X0 = c->d_X0; A.x = c->d_x;
+  A.rowptr = c->d_rowptr; A.diag = c->d_diag; A.nvisits = c->visits.nrecords; A.nrows_total = c->N; A.K = c->d_K; A.f = c->d_f; A.bad = c->d_flag + 1;
   A.dbg = 0; A.stamps = nullptr;
 #ifdef FEAHIP_DEBUG
   // Diagnostic build only (make debug -> libfeahip_dbg.so): FEAHIP_DBG selects the timing experiments of DESIGN.md,
@@ -206,18 +206,13 @@ int launch_assemble_visit(feahip_ctx *c, bool doK, bool doF)
 #endif
   if (c->nachunks_local <= 0) return FEAHIP_OK;
   const dim3 grid((c->nachunks_local + 7) & ~7), blk(64);
+  auto launch = [&](auto DBG) {
+    with_kf(doK, doF, [&](auto K, auto F) { hipLaunchKernelGGL((k_assemble_visit<K, F, DBG>), grid, blk, 0, c->stream, A); });
+  };
 #ifdef FEAHIP_DEBUG
-  if (A.dbg) {
-    if (doK && doF) hipLaunchKernelGGL((k_assemble_visit<true, true, true>), grid, blk, 0, c->stream, A);
-    else if (doK)   hipLaunchKernelGGL((k_assemble_visit<true, false, true>), grid, blk, 0, c->stream, A);
-    else            hipLaunchKernelGGL((k_assemble_visit<false, true, true>), grid, blk, 0, c->stream, A);
-  } else
+  if (A.dbg) launch(std::true_type()); else
 #endif
-  {
-    if (doK && doF) hipLaunchKernelGGL((k_assemble_visit<true, true, false>), grid, blk, 0, c->stream, A);
-    else if (doK)   hipLaunchKernelGGL((k_assemble_visit<true, false, false>), grid, blk, 0, c->stream, A);
-    else            hipLaunchKernelGGL((k_assemble_visit<false, true, false>), grid, blk, 0, c->stream, A);
-  }
+  launch(std::false_type());
   FEA_HIP_CHECK(c, hipGetLastError());
 #ifdef FEAHIP_DEBUG
   if (A.dbg & 4) {                                  // diagnostic build path: phase shares, never a timing

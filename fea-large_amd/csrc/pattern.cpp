@@ -9,27 +9,7 @@
 // column order sp_matrix_yale has).
 #include "feahip_internal.h"
 #include <algorithm>
-#include <thread>
 #include <utility>
-
-namespace {
-
-template <class F>
-void parallel_ranges(int n, F f)
-{
-  unsigned hw = std::thread::hardware_concurrency();
-  int nt = (int)std::min<unsigned>(hw ? hw : 4, 32);
-  if (n < 65536) nt = 1;
-  if (nt <= 1) { f(0, n, 0); return; }
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) {
-    int lo = (int)((long long)n * t / nt), hi = (int)((long long)n * (t + 1) / nt);
-    th.emplace_back([=] { f(lo, hi, t); });
-  }
-  for (auto &x : th) x.join();
-}
-
-}  // namespace
 
 int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
                        std::string &err, int row_break)
@@ -68,7 +48,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
     std::sort(tmp.begin(), tmp.end());
     tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
   };
-  parallel_ranges(N, [&](int lo, int hi, int) {
+  parallel_ranges(N, 65536, [&](int lo, int hi) {
     std::vector<int> tmp;
     for (int a = lo; a < hi; ++a) { row_nodes(a, tmp); hp.rowptr[a + 1] = (int)tmp.size(); }
   });
@@ -84,7 +64,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
   }
   hp.max_rowlen = maxlen;
   hp.colidx.resize((size_t)tot);
-  parallel_ranges(N, [&](int lo, int hi, int) {
+  parallel_ranges(N, 65536, [&](int lo, int hi) {
     std::vector<int> tmp;
     for (int a = lo; a < hi; ++a) {
       row_nodes(a, tmp);
@@ -123,7 +103,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
 
   // position of the diagonal block of every row
   hp.diag.resize((size_t)N);
-  parallel_ranges(N, [&](int lo, int hi, int) {
+  parallel_ranges(N, 65536, [&](int lo, int hi) {
     for (int a = lo; a < hi; ++a) {
       const int *cb = hp.colidx.data() + hp.rowptr[a];
       const int *ce = hp.colidx.data() + hp.rowptr[a + 1];
@@ -229,7 +209,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
   // rows: the 64 lanes of one pass then work on as many different rows as the
   // chunk has, which keeps LDS adds to one address few (same-address
   // ds_add_f64 serialise, ~11 clk per extra lane on gfx950).
-  parallel_ranges(nchunks, [&](int lo, int hi, int) {
+  parallel_ranges(nchunks, 65536, [&](int lo, int hi) {
     std::vector<uint32_t> tmp;
     for (int ch = lo; ch < hi; ++ch) {
       const int r0 = hp.chunk[ch], r1 = hp.chunk[ch + 1];
@@ -246,7 +226,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
   // slot of every (visit, local column node) inside the visit's block row
   if (maxlen <= 255) {
     hp.incslot.resize((size_t)E * npe * npe);
-    parallel_ranges((int)((long long)E * npe > 0x7FFFFFFF ? 0x7FFFFFFF : (long long)E * npe), [&](int lo, int hi, int) {
+    parallel_ranges((int)((long long)E * npe > 0x7FFFFFFF ? 0x7FFFFFFF : (long long)E * npe), 65536, [&](int lo, int hi) {
       for (int p = lo; p < hi; ++p) {
         const int e = (int)(hp.inc[p] & 0x0FFFFFFFu), la = (int)(hp.inc[p] >> 28);
         const int a = conn[(size_t)e * npe + la];

@@ -4,24 +4,6 @@
 #include "feahip_internal.h"
 #include <algorithm>
 #include <cstdlib>
-#include <thread>
-
-namespace {
-template <class F>
-void par_for(int n, F f)
-{
-  unsigned hw = std::thread::hardware_concurrency();
-  int nt = (int)std::min<unsigned>(hw ? hw : 4, 32);
-  if (n < 4096) nt = 1;
-  if (nt <= 1) { f(0, n); return; }
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) {
-    int lo = (int)((long long)n * t / nt), hi = (int)((long long)n * (t + 1) / nt);
-    th.emplace_back([=] { f(lo, hi); });
-  }
-  for (auto &x : th) x.join();
-}
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // visit records for kernels_visit.hip
@@ -50,7 +32,7 @@ void build_host_visits(int N, int E, const int *conn, const HostPattern &hp, Hos
   const bool interleave_rows = !(ord && ord[0] == '1');
   const bool bank_aware = !(ord && (ord[0] == '0' || ord[0] == '1'));
   const int nsweeps = (ord && ord[0] == '3') ? 2 : 0;
-  par_for(np, [&](int lo, int hi) {
+  parallel_ranges(np, 4096, [&](int lo, int hi) {
     std::vector<int> halo;
     for (int p = lo; p < hi; ++p) {
       const int r0 = hp.achunk[p], r1 = hp.achunk[p + 1];
@@ -350,7 +332,7 @@ void build_host_quad(int N, int E, int npe, const int *conn, const HostPattern &
   out.desc.resize((size_t)np);
   // sizes first (prefix sums), then fill in parallel
   std::vector<int> nel((size_t)np, 0), nnd((size_t)np, 0);
-  par_for(np, [&](int lo, int hi) {
+  parallel_ranges(np, 4096, [&](int lo, int hi) {
     std::vector<int> el, nd;
     for (int p = lo; p < hi; ++p) {
       const int r0 = achunk[p], r1 = achunk[p + 1];
@@ -377,7 +359,7 @@ void build_host_quad(int N, int E, int npe, const int *conn, const HostPattern &
         hp.incptr[r1] - hp.incptr[r0] > FEA_QUAD_VISITS || po > 0x7FFFFFFFull) { out.desc.clear(); return; }
   }
   out.qelem.assign(eo * 3, 0u); out.qpair.resize(po); out.qnode.resize(no);
-  par_for(np, [&](int lo, int hi) {
+  parallel_ranges(np, 4096, [&](int lo, int hi) {
     std::vector<int> el, nd;
     for (int p = lo; p < hi; ++p) {
       const QuadDesc &d = out.desc[p];

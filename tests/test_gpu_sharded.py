@@ -63,6 +63,38 @@ def test_sharded_assembly_is_the_unsharded_one(n, strategy, quadratic):
     g.close(); one.close()
 
 
+def test_resharding_one_context_rebuilds_the_10_node_gather_maps():
+    """One context of 10-node tetrahedra moved between row shards (set_row_shard): the gather maps are built for the
+    rows of the shard installed, so after every switch -- to another shard, back, and back to the whole mesh -- K and
+    f of the owned rows are those of the unsharded assembly and AUTO still runs the gather kernel."""
+    deck = mesh.bar_deck(dims=(3, 20, 3), quadratic=True, brick=(3, 4, 4))
+    s = feahip.FeaSolver(deck)
+    s.set_nodes(mesh.deformed_state(deck.nodes))
+    s.create_stiffness_and_residual()
+    assert s.assembly_in_use() == feahip.ASM_GATHER
+    off, idx, val = s.matrix_yale()
+    f = s.forces()
+    kscale, fscale = np.abs(val).max(), np.abs(f).max()
+    row_of_value = np.repeat(np.arange(s.ndof), np.diff(off))
+    for rank in (1, 2, 1):
+        s.set_row_shard(rank, 3)
+        s.create_stiffness_and_residual()
+        assert s.assembly_in_use() == feahip.ASM_GATHER
+        d = s.owned_dofs()
+        own = np.zeros(s.ndof, dtype=bool); own[d] = True
+        mine = own[row_of_value]
+        o2, i2, v = s.matrix_yale()
+        assert np.array_equal(o2, off) and np.array_equal(i2, idx)
+        assert np.abs(v[mine] - val[mine]).max() < 4e-16 * kscale
+        assert np.all(v[~mine] == 0)
+        assert np.abs(s.forces()[d] - f[d]).max() < 4e-16 * fscale
+    s.set_row_shard(0, 1)
+    s.create_stiffness_and_residual()
+    assert s.assembly_in_use() == feahip.ASM_GATHER
+    assert np.array_equal(s.matrix_yale()[2], val) and np.array_equal(s.forces(), f)
+    s.close()
+
+
 @pytest.mark.parametrize("rank_contexts", [False, True])
 @pytest.mark.parametrize("precond", [0, 1])
 def test_interior_product_never_reads_a_halo_row(rank_contexts, precond, monkeypatch):
