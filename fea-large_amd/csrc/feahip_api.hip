@@ -401,6 +401,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   if (!c) return;
   delete c->h_pat; c->h_pat = nullptr;
   c->generic.release(); c->visits.release(); c->quad.release(); c->gather.release(); c->gather10.release();
+  c->surf.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -476,6 +477,7 @@ extern "C" int feahip_update_nodes_with_bc(feahip_ctx *c, double lambda)
 {
   CTX_GUARD_NOK(c);
   c->state_valid = false;
+  c->load_factor += lambda;                          // one increment of the surface loads, as of the displacements
   return launch_update_nodes_bc(c, lambda);
 }
 
@@ -561,6 +563,60 @@ extern "C" int feahip_solve(feahip_ctx *c, int load_increments, int max_newton, 
   std::vector<feahip_ctx *> R(1, c);
   return dist_newton(R, load_increments, max_newton, modified_newton, desired_tolerance, solver_type,
                      solver_tolerance, solver_max_iter, tol_log, tol_log_cap, its_log, steps_done);
+}
+
+// ---- surface loads (kernels_surface.hip) ------------------------------------
+
+static int get_node_vec(feahip_ctx *c, const double *d, double *h);
+
+extern "C" int feahip_set_surface_loads(feahip_ctx *c, int n_faces, int nodes_per_face, const int *face_nodes,
+                                        const int *kind, const double *values)
+{
+  CTX_GUARD_NOK(c);
+  return set_surface_loads(c, n_faces, nodes_per_face, face_nodes, kind, values);
+}
+
+extern "C" int feahip_get_surface_forces(feahip_ctx *c, double *f)
+{
+  CTX_GUARD_NOK(c);
+  if (!f) return FEAHIP_EINVAL;
+  double *d = nullptr;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (size_t)c->ndof));
+  int rc = hipMemsetAsync(d, 0, sizeof(double) * (size_t)c->ndof, c->stream) == hipSuccess ? launch_surface_loads(c, d) : FEAHIP_EHIP;
+  if (rc == FEAHIP_OK) rc = get_node_vec(c, d, f);
+  (void)hipFree(d);
+  return rc;
+}
+
+extern "C" int feahip_set_load_factor(feahip_ctx *c, double lambda)
+{
+  CTX_GUARD_NOK(c);
+  c->load_factor = lambda;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_load_factor(feahip_ctx *c, double *lambda)
+{
+  if (!c || !lambda) return FEAHIP_EINVAL;
+  *lambda = c->load_factor;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_host_surface_faces(int n_nodes, int n_elems, int npe, const int *elements, int n_faces,
+                                         int nodes_per_face, const int *face_nodes, int *face_elem, int *face_local,
+                                         int *bad)
+{
+  if (bad) *bad = -1;
+  if (!elements || n_nodes <= 0 || n_elems <= 0 || n_faces < 0 || (n_faces > 0 && (!face_nodes || !face_elem || !face_local)))
+    return FEAHIP_EINVAL;
+  for (long long i = 0; i < (long long)n_elems * npe; ++i)
+    if (elements[i] < 0 || elements[i] >= n_nodes) return FEAHIP_EINVAL;
+  if (n_faces == 0) return FEAHIP_OK;
+  std::string why;
+  const int b = resolve_surface_faces(n_nodes, n_elems, npe, elements, n_faces, nodes_per_face, face_nodes, face_elem, face_local, why);
+  if (b < 0) return FEAHIP_OK;
+  if (bad) *bad = b;
+  return FEAHIP_EINVAL;
 }
 
 // ---- sharding ------------------------------------------------------------
@@ -884,12 +940,14 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
   CTX_GUARD(c);
   if (!avg_ms || iters <= 0 || warmup < 0) return FEAHIP_EINVAL;
   if (what == 4) return time_pcg_iteration(c, warmup, iters, avg_ms);
+  if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   auto one = [&]() -> int {
     switch (what) {
     case 0: return launch_assemble(c, true, true);
     case 1: return launch_assemble(c, true, false);
     case 2: return launch_assemble(c, false, true);
     case 3: return launch_spmv(c, c->d_p, c->d_q);
+    case 5: return launch_surface_loads(c, c->d_f);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   };

@@ -302,6 +302,19 @@ struct Gather10Maps : GatherCache {
   void release() { dev_free({d_maps, d_elist, d_state}); *this = Gather10Maps(); }
 };
 
+// surface loads (kernels_surface.hip): the loaded boundary faces in library ids, each in its element's face order
+// (outward normal), and the node -> (face, slot) incidence kernel 2 sums in a fixed order
+struct SurfaceLoads {
+  int nfaces = 0, npf = 0;             // faces; nodes per face (3, 6 or 4)
+  std::vector<int> h_lnode;            // the loaded nodes, ascending (library ids)
+  int *d_fnode = nullptr;              // [nfaces][npf]
+  int *d_kind = nullptr;               // [nfaces] FEAHIP_LOAD_*
+  double *d_val = nullptr;             // [nfaces][3]: pressure in [0], or the dead traction t0
+  double *d_fc = nullptr;              // [nfaces][npf][3] contributions of kernel 1 (lambda applied)
+  int *d_lnode = nullptr, *d_lptr = nullptr, *d_lslot = nullptr;   // [nloaded], [nloaded + 1], slot = face * npf + k
+  void release() { dev_free({d_fnode, d_kind, d_val, d_fc, d_lnode, d_lptr, d_lslot}); *this = SurfaceLoads(); }
+};
+
 struct feahip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -411,6 +424,10 @@ struct feahip_ctx {
   int linesearch_max = 0;
   int precond = 0;
   void *amg = nullptr;         // AmgHierarchy, built on first use
+  // surface loads: f = load_factor * F_ext(x) - T(x) in every residual assembly; feahip_update_nodes_with_bc adds its
+  // lambda to load_factor (one increment of the loads per step, as of the prescribed displacements)
+  SurfaceLoads surf;
+  double load_factor = 0;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -428,6 +445,13 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF);
 int launch_state_export(feahip_ctx *c, double *d_grads = nullptr, double *d_detj = nullptr);
 int launch_apply_bc(feahip_ctx *c, double lambda);
 int launch_update_nodes_bc(feahip_ctx *c, double lambda);
+// kernels_surface.hip: adds load_factor * F_ext of the loaded faces to the owned rows of f (nothing without loads)
+int launch_surface_loads(feahip_ctx *c, double *d_fv);
+// kernels_surface.hip, host only: (owning element, local face) of every face, node ids in the numbering of conn;
+// -1 when all resolve, else the index of the first bad face with the reason in why
+int resolve_surface_faces(int N, int E, int npe, const int *conn, int nfaces, int npf, const int *face_nodes,
+                          int *face_elem, int *face_local, std::string &why);
+int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, const int *kind, const double *values);
 int ensure_generic_maps(feahip_ctx *c);
 int ensure_k(feahip_ctx *c);
 void release_k(feahip_ctx *c);

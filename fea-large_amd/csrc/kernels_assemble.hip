@@ -402,7 +402,9 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF)
   const int strat = resolve_assembly(c, doK);
   if (strat < 0) return strat;
   c->last_strategy = strat;                          // the kernel that runs, after the residual-only fallbacks
-  return dispatch_assembly(c, strat, doK, doF);
+  const int rc = dispatch_assembly(c, strat, doK, doF);
+  if (rc || !doF) return rc;
+  return launch_surface_loads(c, c->d_f);            // f = lambda F_ext - T (nothing to launch without loads)
 }
 
 int launch_state_export(feahip_ctx *c, double *d_grads, double *d_detj)

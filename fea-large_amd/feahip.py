@@ -20,6 +20,7 @@ MODEL_A5, MODEL_COMPRESSIBLE_NEOHOOKEAN = 0, 1
 CG, PCG_ILU, CHOLESKY = 0, 1, 2
 ASM_AUTO, ASM_ROWOWNER, ASM_ATOMIC, ASM_PATCH, ASM_STAGED, ASM_PAIRED, ASM_PIPELINED, ASM_SHARED, ASM_GATHER = 0, 1, 2, 3, 4, 5, 6, 7, 8
 TETRAHEDRA10, TETRAHEDRA4, HEXAHEDRA8 = 0, 1, 2
+LOAD_PRESSURE, LOAD_TRACTION = 0, 1
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -90,6 +91,11 @@ ABI = {
     "feahip_assembly_stats": [C.c_void_p, _dp],
     "feahip_device_layout": [C.c_void_p, C.POINTER(C.c_longlong)],
     "feahip_host_numbering": [C.c_int, C.c_int, C.c_int, _ip, _dp, _ip],
+    "feahip_set_surface_loads": [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp],
+    "feahip_get_surface_forces": [C.c_void_p, _dp],
+    "feahip_set_load_factor": [C.c_void_p, C.c_double],
+    "feahip_get_load_factor": [C.c_void_p, _dp],
+    "feahip_host_surface_faces": [C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip, _ip, _ip],
 }
 
 _lib = None
@@ -128,6 +134,8 @@ class FeaDeck(C.Structure):
         ("modified_newton", C.c_int), ("nodes_per_element", C.c_int), ("gauss_nodes_count", C.c_int),
         ("nodes_count", C.c_int), ("nodes", _dp), ("elements_count", C.c_int), ("elements", _ip),
         ("prescribed_nodes_count", C.c_int), ("presc_node", _ip), ("presc_type", _ip), ("presc_values", _dp),
+        ("surface_faces_count", C.c_int), ("surface_nodes_per_face", C.c_int), ("surface_nodes", _ip),
+        ("surface_kind", _ip), ("surface_values", _dp),
     ]
 
 
@@ -219,6 +227,12 @@ class Deck:
         self.presc_node = np.ascontiguousarray(kw.get("presc_node", []), dtype=np.int32)
         self.presc_type = np.ascontiguousarray(kw.get("presc_type", []), dtype=np.int32)
         self.presc_values = np.ascontiguousarray(kw.get("presc_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+        # surface loads (feahip_set_surface_loads): faces[F][nodes per face] in any node order, kind[F] LOAD_*,
+        # values[F][3] (pressure in [0], or the dead traction t0), per load increment
+        faces = np.asarray(kw.get("surface_faces", np.zeros((0, 0))), dtype=np.int32)
+        self.surface_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
+        self.surface_kind = np.ascontiguousarray(kw.get("surface_kind", []), dtype=np.int32)
+        self.surface_values = np.ascontiguousarray(kw.get("surface_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
 
     @staticmethod
     def load(path):
@@ -230,6 +244,7 @@ class Deck:
             raise FeaHipError(f"{path}: {err.value.decode()}")
         try:
             n, e, npe, nb = fd.nodes_count, fd.elements_count, fd.nodes_per_element, fd.prescribed_nodes_count
+            ns, npf = fd.surface_faces_count, fd.surface_nodes_per_face
             deck = Deck(
                 model=fd.model, parameters=[fd.parameters[0], fd.parameters[1]], solver_type=fd.solver_type,
                 solver_tolerance=fd.solver_tolerance, solver_max_iter=fd.solver_max_iter, ele_type=fd.ele_type,
@@ -240,7 +255,10 @@ class Deck:
                 elements=np.ctypeslib.as_array(fd.elements, (e, npe)).copy(),
                 presc_node=np.ctypeslib.as_array(fd.presc_node, (nb,)).copy() if nb else [],
                 presc_type=np.ctypeslib.as_array(fd.presc_type, (nb,)).copy() if nb else [],
-                presc_values=np.ctypeslib.as_array(fd.presc_values, (nb, 3)).copy() if nb else np.zeros((0, 3)))
+                presc_values=np.ctypeslib.as_array(fd.presc_values, (nb, 3)).copy() if nb else np.zeros((0, 3)),
+                surface_faces=np.ctypeslib.as_array(fd.surface_nodes, (ns, npf)).copy() if ns else np.zeros((0, 0)),
+                surface_kind=np.ctypeslib.as_array(fd.surface_kind, (ns,)).copy() if ns else [],
+                surface_values=np.ctypeslib.as_array(fd.surface_values, (ns, 3)).copy() if ns else np.zeros((0, 3)))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -260,6 +278,9 @@ class Deck:
         fd.elements_count, fd.elements = len(self.elements), _i(self.elements)
         fd.prescribed_nodes_count = len(self.presc_node)
         fd.presc_node, fd.presc_type, fd.presc_values = _i(self.presc_node), _i(self.presc_type), _d(self.presc_values)
+        fd.surface_faces_count = len(self.surface_kind)
+        fd.surface_nodes_per_face = self.surface_faces.shape[1] if len(self.surface_kind) else 0
+        fd.surface_nodes, fd.surface_kind, fd.surface_values = _i(self.surface_faces), _i(self.surface_kind), _d(self.surface_values)
         return fd
 
     def save(self, path):
@@ -292,6 +313,12 @@ class FeaSolver:
         if rc != 0:
             self._ctx = C.c_void_p()
             raise FeaHipError(f"feahip_create failed ({rc}): {self._lib.feahip_create_error().decode()}")
+        self._deck_surface_loads()
+
+    def _deck_surface_loads(self):
+        if len(getattr(self.deck, "surface_kind", [])):
+            d = self.deck
+            self.set_surface_loads(d.surface_faces, d.surface_kind, d.surface_values)
 
     def close(self):
         if self._ctx:
@@ -376,6 +403,30 @@ class FeaSolver:
             _d(tol_log), cap, _i(its), C.byref(done)))
         n = int(its[:max(done.value, 0) + (1 if done.value < li else 0)].sum())
         return done.value, its, tol_log[:n]
+
+    # ---- surface loads ---------------------------------------------------
+    def set_surface_loads(self, faces, kind, values):
+        """Replaces the loaded faces (an empty list clears them): faces[F][nodes per face] in the caller's node ids,
+        any order; kind[F] LOAD_PRESSURE / LOAD_TRACTION; values[F][3] (pressure in [0], or t0)."""
+        kind = np.ascontiguousarray(kind, dtype=np.int32).reshape(-1)
+        n = len(kind)
+        faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(n, -1) if n else np.zeros((0, 1), dtype=np.int32)
+        values = np.ascontiguousarray(values, dtype=np.float64).reshape(n, 3) if n else np.zeros((0, 3))
+        self._chk(self._lib.feahip_set_surface_loads(self._ctx, n, faces.shape[1] if n else 0, _i(faces), _i(kind), _d(values)))
+
+    def surface_forces(self):
+        """load factor x F_ext at the current nodes, [3N] in the caller's dof order."""
+        f = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_get_surface_forces(self._ctx, _d(f)))
+        return f
+
+    def load_factor(self):
+        v = C.c_double(0)
+        self._chk(self._lib.feahip_get_load_factor(self._ctx, C.byref(v)))
+        return v.value
+
+    def set_load_factor(self, lam):
+        self._chk(self._lib.feahip_set_load_factor(self._ctx, lam))
 
     # ---- views -----------------------------------------------------------
     def set_nodes(self, x):
@@ -545,6 +596,21 @@ def host_numbering(elements, nodes):
     return out, bool(rc)
 
 
+def host_surface_faces(elements, n_nodes, faces):
+    """(owning element[F], local face[F], index of the first bad face or -1) of the faces, as feahip_set_surface_loads
+    resolves them (host only).  Local faces: tetrahedra 0..3 opposite vertex 3, 2, 1, 0; bricks t-, t+, s-, r+, s+, r-."""
+    el = np.ascontiguousarray(elements, dtype=np.int32)
+    fc = np.ascontiguousarray(faces, dtype=np.int32)
+    fc = fc.reshape(len(fc), -1)
+    fe, fl = np.full(len(fc), -1, dtype=np.int32), np.full(len(fc), -1, dtype=np.int32)
+    bad = C.c_int(-1)
+    rc = load_library().feahip_host_surface_faces(n_nodes, el.shape[0], el.shape[1], _i(el), len(fc), fc.shape[1],
+                                                  _i(fc), _i(fe), _i(fl), C.byref(bad))
+    if rc not in (0, -1):
+        raise FeaHipError(f"feahip_host_surface_faces failed ({rc})")
+    return fe, fl, int(bad.value)
+
+
 def host_gather_stats(elements, n_nodes):
     """Shape of the GATHER maps of a mesh (4-, 10- or 8-node elements) in the numbering given (host only): dict + chunks by row count."""
     el = np.ascontiguousarray(elements, dtype=np.int32)
@@ -629,6 +695,7 @@ class RankSolver(FeaSolver):
         self.node_global = np.empty(self.N, dtype=np.int32)
         self.elem_global = np.empty(self.E, dtype=np.int32)
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
+        self._deck_surface_loads()                              # the whole face list: the rank keeps what touches its nodes
 
 
 def host_rank_mesh(deck, rank, nranks, pattern=False):

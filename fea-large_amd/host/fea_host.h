@@ -49,6 +49,15 @@ typedef struct fea_deck {
   int prescribed_nodes_count;
   int *presc_node, *presc_type;
   double *presc_values;         /* [count][3]                                */
+  /* surface loads, deck order: (surface-loads (pressure :value p :nodes (...))
+   * (traction :x :y :z :nodes (...)) ...) inside (boundary-conditions ...);
+   * node ids as :node-id of prescribed-displacements.  Values are per load
+   * increment (feahip_set_surface_loads)                                     */
+  int surface_faces_count;
+  int surface_nodes_per_face;
+  int *surface_nodes;           /* [count][nodes_per_face]                   */
+  int *surface_kind;            /* [count] FEAHIP_LOAD_*                     */
+  double *surface_values;       /* [count][3]: pressure in [0], or t0        */
 } fea_deck;
 
 /* sexp_data_load (sexp_loader.c:275-327).  Returns 0, or -1 with a message
@@ -65,7 +74,7 @@ int fea_deck_save(const char *path, const fea_deck *deck);
 int fea_element_tables(int ele_type, int gauss_count, double *weights,
                        double *forms, double *dforms);
 
-/* creates the device context for a deck */
+/* creates the device context for a deck, its surface loads installed */
 int fea_deck_create_solver(const fea_deck *deck, int device, feahip_ctx **ctx,
                            char *errbuf, int errlen);
 

@@ -26,7 +26,17 @@ int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char
   rc = feahip_create(ctx, device, d->nodes_count, d->elements_count, npe, d->gauss_nodes_count, w, dforms,
                      d->elements, d->nodes, d->model, d->parameters, d->parameters_count,
                      d->prescribed_nodes_count, d->presc_node, d->presc_type, d->presc_values);
-  if (rc && errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_create_error());
+  if (rc) {
+    if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_create_error());
+    return rc;
+  }
+  if (d->surface_faces_count > 0 &&
+      (rc = feahip_set_surface_loads(*ctx, d->surface_faces_count, d->surface_nodes_per_face, d->surface_nodes,
+                                     d->surface_kind, d->surface_values))) {
+    if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
+    feahip_destroy(*ctx);
+    *ctx = NULL;
+  }
   return rc;
 }
 

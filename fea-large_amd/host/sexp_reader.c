@@ -236,6 +236,81 @@ static int read_prescribed(reader *r, fea_deck *d)
   return 0;
 }
 
+/* (surface-loads (pressure :value p :nodes (n ...)) (traction :x :y :z :nodes (n ...)) ...): no counterpart in the
+ * reference, whose loader skips lists it does not know (sexp_loader.c:249-272).  Every face has the node count of
+ * the first one; whether the nodes form a boundary face is checked by feahip_set_surface_loads. */
+static int read_surface(reader *r, fea_deck *d)
+{
+  char buf[TOK_MAX];
+  size_t cap = 64, n = 0;
+  int npf = 0, rc = 0;
+  int *nodes = (int *)malloc(cap * 8 * sizeof(int)), *kind = (int *)malloc(cap * sizeof(int));
+  double *val = (double *)malloc(cap * 3 * sizeof(double));
+  for (;;) {
+    int t = next_token(r, buf), k = 0, got_nodes = 0, ids[8];
+    double v[3] = {0, 0, 0};
+    int have[3] = {0, 0, 0};
+    if (t == T_CLOSE) break;
+    if (t != T_OPEN || next_token(r, buf) != T_ATOM || !(ieq(buf, "pressure") || ieq(buf, "traction"))) {
+      rc = fail(r, "expected (pressure ...) or (traction ...)"); break;
+    }
+    if (n == cap) {
+      cap *= 2;
+      nodes = (int *)realloc(nodes, cap * 8 * sizeof(int));
+      kind = (int *)realloc(kind, cap * sizeof(int));
+      val = (double *)realloc(val, cap * 3 * sizeof(double));
+    }
+    kind[n] = ieq(buf, "pressure") ? FEAHIP_LOAD_PRESSURE : FEAHIP_LOAD_TRACTION;
+    for (;;) {
+      char key[48], *end;
+      t = next_token(r, buf);
+      if (t == T_CLOSE) break;
+      if (t != T_ATOM || buf[0] != ':') { rc = fail(r, "surface load: expected :key value"); break; }
+      snprintf(key, sizeof key, "%s", buf + 1);
+      if (ieq(key, "nodes")) {
+        if (next_token(r, buf) != T_OPEN) { rc = fail(r, ":nodes must be a list of node ids"); break; }
+        for (k = 0; (t = next_token(r, buf)) == T_ATOM; ++k) {
+          if (k == 6) { rc = fail(r, "a face has at most 6 nodes"); break; }
+          ids[k] = (int)strtol(buf, &end, 10);
+          if (end == buf) { rc = fail(r, "bad node id in :nodes"); break; }
+        }
+        if (rc) break;
+        if (t != T_CLOSE) { rc = fail(r, ":nodes must be a list of node ids"); break; }
+        got_nodes = 1;
+        continue;
+      }
+      if (next_token(r, buf) != T_ATOM) { rc = fail(r, "attribute without a value"); break; }
+      {
+        const int slot = ieq(key, "value") || ieq(key, "x") ? 0 : ieq(key, "y") ? 1 : ieq(key, "z") ? 2 : -1;
+        if (slot < 0) continue;
+        v[slot] = strtod(buf, &end);
+        if (end == buf) { rc = fail(r, "surface load value is not a number"); break; }
+        have[slot] = 1;
+      }
+    }
+    if (rc) break;
+    if (!got_nodes || k == 0) { rc = fail(r, "surface load without :nodes"); break; }
+    if (n == 0) npf = k;
+    else if (k != npf) { rc = fail(r, "every loaded face must have the same number of nodes"); break; }
+    if (kind[n] == FEAHIP_LOAD_PRESSURE ? !have[0] : !(have[0] && have[1] && have[2])) {
+      rc = fail(r, kind[n] == FEAHIP_LOAD_PRESSURE ? "pressure needs :value" : "traction needs :x :y :z"); break;
+    }
+    if (kind[n] == FEAHIP_LOAD_PRESSURE) v[1] = v[2] = 0;
+    memcpy(nodes + n * 8, ids, sizeof(int) * (size_t)k);
+    memcpy(val + n * 3, v, sizeof v);
+    n++;
+  }
+  if (rc) { free(nodes); free(kind); free(val); return rc; }
+  {
+    size_t i;
+    for (i = 0; i < n; ++i) memmove(nodes + i * (size_t)npf, nodes + i * 8, sizeof(int) * (size_t)npf);   /* pack */
+  }
+  free(d->surface_nodes); free(d->surface_kind); free(d->surface_values);
+  d->surface_nodes = nodes; d->surface_kind = kind; d->surface_values = val;
+  d->surface_faces_count = (int)n; d->surface_nodes_per_face = npf;
+  return 0;
+}
+
 /* one list, '(' consumed: dispatch on the head like traverse_function
  * (sexp_loader.c:249-272) */
 static int read_list(reader *r, fea_deck *d)
@@ -255,6 +330,7 @@ static int read_list(reader *r, fea_deck *d)
   if (ieq(head, "nodes")) return read_nodes(r, d);
   if (ieq(head, "elements")) return read_elements(r, d);
   if (ieq(head, "prescribed-displacements")) return read_prescribed(r, d);
+  if (ieq(head, "surface-loads")) return read_surface(r, d);
 
   if (read_attrs(r, d, a, &na, 1)) return -1;
 
@@ -370,9 +446,11 @@ void fea_deck_free(fea_deck *d)
   if (!d) return;
   free(d->nodes); free(d->elements);
   free(d->presc_node); free(d->presc_type); free(d->presc_values);
+  free(d->surface_nodes); free(d->surface_kind); free(d->surface_values);
   d->nodes = NULL; d->elements = NULL;
   d->presc_node = d->presc_type = NULL; d->presc_values = NULL;
-  d->nodes_count = d->elements_count = d->prescribed_nodes_count = 0;
+  d->surface_nodes = d->surface_kind = NULL; d->surface_values = NULL;
+  d->nodes_count = d->elements_count = d->prescribed_nodes_count = d->surface_faces_count = 0;
 }
 
 int fea_deck_save(const char *path, const fea_deck *d)
@@ -406,6 +484,19 @@ int fea_deck_save(const char *path, const fea_deck *d)
   for (i = 0; i < d->prescribed_nodes_count; ++i)
     fprintf(f, "\n    (presc-node :y %.17g :x %.17g :z %.17g :type %d :node-id %d)", d->presc_values[3 * i + 1],
             d->presc_values[3 * i], d->presc_values[3 * i + 2], d->presc_type[i], d->presc_node[i]);
-  fprintf(f, "))))\n");
+  fprintf(f, ")");
+  if (d->surface_faces_count > 0) {                  /* written only when there are faces: other decks save as before */
+    fprintf(f, "\n   (surface-loads");
+    for (i = 0; i < d->surface_faces_count; ++i) {
+      const double *v = d->surface_values + 3 * (size_t)i;
+      if (d->surface_kind[i] == FEAHIP_LOAD_PRESSURE) fprintf(f, "\n    (pressure :value %.17g :nodes (", v[0]);
+      else fprintf(f, "\n    (traction :x %.17g :y %.17g :z %.17g :nodes (", v[0], v[1], v[2]);
+      for (k = 0; k < d->surface_nodes_per_face; ++k)
+        fprintf(f, k ? " %d" : "%d", d->surface_nodes[(size_t)i * d->surface_nodes_per_face + k]);
+      fprintf(f, "))");
+    }
+    fprintf(f, ")");
+  }
+  fprintf(f, ")))\n");
   return fclose(f);
 }

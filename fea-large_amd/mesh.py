@@ -277,6 +277,8 @@ def jitter_permute(deck, amp=0.2, seed=4, spacing=None):
     out.nodes[new_id] = nodes
     out.elements = np.ascontiguousarray(new_id[deck.elements].astype(np.int32))
     out.presc_node = np.ascontiguousarray(new_id[deck.presc_node].astype(np.int32)) if len(deck.presc_node) else deck.presc_node
+    if len(getattr(deck, "surface_kind", [])):
+        out.surface_faces = np.ascontiguousarray(new_id[deck.surface_faces].astype(np.int32))
     return out
 
 
@@ -327,3 +329,72 @@ def corner_tets(deck):
         out.presc_type = np.ascontiguousarray(deck.presc_type[keep])
         out.presc_values = np.ascontiguousarray(deck.presc_values[keep])
     return out
+
+
+# Local faces of the element types, outward for a positively oriented element (the order the library takes a loaded
+# face's nodes in, include/fea_hip.h): tetrahedra one face per opposite vertex 3, 2, 1, 0 -- 10-node faces as their
+# three corners, then the mid-side nodes of the face's edges (0,1) (1,2) (2,0); bricks t-, t+, s-, r+, s+, r-.
+TET4_FACES = np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]])
+TET10_FACES = np.array([[0, 2, 1, 6, 5, 4], [0, 1, 3, 4, 8, 7], [0, 3, 2, 7, 9, 6], [1, 2, 3, 5, 9, 8]])
+HEX8_FACES = np.array([[0, 3, 2, 1], [4, 5, 6, 7], [0, 1, 5, 4], [1, 2, 6, 5], [2, 3, 7, 6], [3, 0, 4, 7]])
+
+
+def element_faces(npe):
+    return {4: TET4_FACES, 10: TET10_FACES, 8: HEX8_FACES}[npe]
+
+
+def boundary_faces(elements):
+    """Every face of exactly one element: (faces[F][nodes per face] in the element's outward order, element[F],
+    local face[F]).  Mid-side nodes of 10-node elements included."""
+    el = np.asarray(elements)
+    table = element_faces(el.shape[1])
+    allf = el[:, table]                                   # [E][faces][npf]
+    ncorner = 4 if el.shape[1] == 8 else 3
+    key = np.sort(allf[:, :, :ncorner], axis=2).reshape(-1, ncorner)
+    _, inv, cnt = np.unique(key, axis=0, return_inverse=True, return_counts=True)
+    once = cnt[inv.ravel()] == 1
+    idx = np.nonzero(once)[0]
+    nf = table.shape[0]
+    return allf.reshape(-1, table.shape[1])[idx].astype(np.int32), (idx // nf).astype(np.int32), (idx % nf).astype(np.int32)
+
+
+def block_side_faces(nodes, elements, axis, upper):
+    """The boundary faces of a kuhn_block / hex_block on one side: the plane coordinate[axis] = its min (upper=False)
+    or max (upper=True); TET10 mid-side nodes included.  Element face order (outward)."""
+    faces, _, _ = boundary_faces(elements)
+    c = nodes[:, axis]
+    v = c.max() if upper else c.min()
+    tol = 1e-9 * max(c.max() - c.min(), 1.0)
+    on = np.all(np.abs(c[faces] - v) < tol, axis=1)
+    return np.ascontiguousarray(faces[on])
+
+
+def lame_quarter_deck(nr, nt, nz, quadratic=True, ri=1.0, ro=2.0, zlo=0.0, zhi=0.5, p=0.0, model=None, gauss=None, **kw):
+    """A quarter of the Lame cylinder (r in [ri, ro], theta in [0, pi/2]) under internal pressure p per load increment:
+    the Kuhn block in (r, axial, theta) mapped to (r cos t, -r sin t, axial) as cylinder_deck, TET10 mid-side nodes
+    mapped like the vertices.  Symmetry planes: theta = 0 (y = 0) keeps y (type 2), theta = pi/2 (x = 0) keeps x
+    (type 1); both end faces keep z (type 4).  The faces of the inner surface carry the pressure (deck.surface_*).
+    A full ring under pressure alone would leave its in-plane rigid motions free."""
+    if model is None:
+        model = MODEL_COMPRESSIBLE_NEOHOOKEAN
+    pn, pe = kuhn_block(nr, nz, nt, quadratic, origin=(ri, zlo, 0.0), size=(ro - ri, zhi - zlo, 0.5 * math.pi))
+    m = 2 if quadratic else 1
+    gx, gy, gz = m * nr + 1, m * nz + 1, m * nt + 1
+    ids = np.arange(gx * gy * gz)
+    i, k, j = ids % gx, (ids // gx) % gz, ids // (gx * gz)
+    r, ax, th = pn[:, 0], pn[:, 1], pn[:, 2]
+    nodes = np.stack([r * np.cos(th), -r * np.sin(th), ax], axis=1)
+    nodes[k == 0, 1] = 0.0                                # exactly on the symmetry planes
+    nodes[k == gz - 1, 0] = 0.0
+    types = np.where(k == 0, 2, 0) | np.where(k == gz - 1, 1, 0) | np.where((j == 0) | (j == gy - 1), 4, 0)
+    sel = np.nonzero(types)[0].astype(np.int32)
+    inner = i == 0
+    faces, _, _ = boundary_faces(pe)
+    faces = np.ascontiguousarray(faces[np.all(inner[faces], axis=1)])
+    if gauss is None:
+        gauss = 5 if quadratic else 1
+    kw.setdefault("solver_type", CG)
+    return Deck(model=model, parameters=[100.0, 100.0], ele_type=TETRAHEDRA10 if quadratic else TETRAHEDRA4,
+                gauss_nodes_count=gauss, nodes=nodes, elements=pe, presc_node=sel, presc_type=types[sel].astype(np.int32),
+                presc_values=np.zeros((len(sel), 3)), surface_faces=faces,
+                surface_kind=np.zeros(len(faces), dtype=np.int32), surface_values=np.tile([p, 0.0, 0.0], (len(faces), 1)), **kw)

@@ -150,6 +150,53 @@ int feahip_solve(feahip_ctx *ctx, int load_increments, int max_newton,
                  double *tol_log, int tol_log_cap, int *its_log,
                  int *steps_done);
 
+/* ---- surface loads ------------------------------------------------------ */
+/* What the reference leaves unwritten (solver_create_forces_bc, fea_solver.c:
+ * 1191-1198).  A loaded face is a boundary face of exactly one element: a
+ * 3-node triangle of a TET4, a 6-node triangle of a TET10 (corners, then
+ * mid-side nodes), a 4-node quad of a HEX8.  Its node ids come in any order;
+ * the library matches the set against the faces of the owning element and
+ * takes node order and OUTWARD normal from it.  Two kinds:
+ *   FEAHIP_LOAD_PRESSURE  follower pressure p on the CURRENT face,
+ *                         t da = -p n da (p > 0 pushes into the body)
+ *   FEAHIP_LOAD_TRACTION  dead traction t0 per REFERENCE area, t da = t0 dA
+ * F_a = int N_a t da, integrated exactly for the pressure (tri3: 1 point,
+ * tri6: 6-point degree-4 rule, quad4: 2 x 2 Gauss); the dead traction uses
+ * the same points.  Every assembly that writes the residual then produces
+ * f = lambda F_ext(x) - T(x) (feahip_apply_prescribed_bc still overwrites the
+ * prescribed dofs); stiffness-only assembly is unchanged.  NO load stiffness
+ * is assembled: the follower-pressure tangent is non-symmetric and the CG /
+ * PCG solvers need a symmetric K, so Newton converges to the exact answer of
+ * the exact residual, possibly in more iterations.  lambda is the context's
+ * load factor: 0 at creation, feahip_update_nodes_with_bc(ctx, l) adds l to it
+ * (deck values are per increment, as prescribed displacements), so after load
+ * step s of feahip_solve the load applied is (s+1) x the values given.  With
+ * no loaded faces nothing is launched and nothing changes.  Row shards and
+ * in-process groups add the loads of the rows they own; a feahip_create_rank
+ * context takes the whole face list and keeps the faces touching its owned
+ * nodes.                                                                    */
+enum { FEAHIP_LOAD_PRESSURE = 0, FEAHIP_LOAD_TRACTION = 1 };
+/* replaces the set; n_faces = 0 clears it.  face_nodes[n_faces][nodes_per_face]
+ * in the CALLER's node ids, kind[n_faces], values[n_faces][3] (pressure in [0];
+ * the traction vector t0 otherwise).  A node set that is not exactly one
+ * element's boundary face (interior face, unknown face, wrong node count) is
+ * refused with FEAHIP_EINVAL, feahip_last_error naming the face.            */
+int feahip_set_surface_loads(feahip_ctx *ctx, int n_faces, int nodes_per_face, const int *face_nodes,
+                             const int *kind, const double *values);
+/* lambda * F_ext at the current nodes, [3N] in the caller's dof order (test /
+ * post-processing hook; authoritative on the owned rows of a shard)         */
+int feahip_get_surface_forces(feahip_ctx *ctx, double *f);
+int feahip_set_load_factor(feahip_ctx *ctx, double lambda);
+int feahip_get_load_factor(feahip_ctx *ctx, double *lambda);
+/* Host-only (no device): resolve faces to (owning element, local face) exactly
+ * as feahip_set_surface_loads does; returns FEAHIP_EINVAL with the index of
+ * the first bad face in *bad (-1 when all resolve).  Local faces: TET4 / TET10
+ * 0..3 = opposite vertex 3, 2, 1, 0; HEX8 0..5 = t = -1, t = +1, s = -1,
+ * r = +1, s = +1, r = -1.                                                   */
+int feahip_host_surface_faces(int n_nodes, int n_elems, int npe, const int *elements, int n_faces,
+                              int nodes_per_face, const int *face_nodes, int *face_elem, int *face_local,
+                              int *bad);
+
 /* ---- multi-GPU: row-sharded operation ---------------------------------- */
 /* The reference is one process; sharding is new.  Nodes (block rows of K,
  * entries of f, u, x) are owned by one rank each, in contiguous ranges; a rank
@@ -345,7 +392,8 @@ int feahip_sync(feahip_ctx *ctx);
 /* Runs `iters` timed launches of one hot-path kernel after `warmup` untimed
  * ones, bracketed by HIP events on the context's own stream; *avg_ms is the
  * mean device time of one launch.  what: 0 stiffness+residual assembly,
- * 1 stiffness only, 2 residual only, 3 SpMV, 4 one PCG iteration.           */
+ * 1 stiffness only, 2 residual only, 3 SpMV, 4 one PCG iteration, 5 the
+ * surface-load kernels alone (refused on a context without loaded faces).   */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
