@@ -41,6 +41,7 @@ struct AmgLevel {
   int *cbptr = nullptr, *cblist = nullptr;     // aggregate pair -> fine blocks entering its 4 coarse blocks
   int *prow = nullptr;                   // aggregate pair -> its row aggregate
   int *cbrow = nullptr;                  // fine block -> its block row
+  int *tpos = nullptr;                   // coarse levels: block (a, b) -> block (b, a) of the same matrix (k_mirror_lower)
   // work vectors [3N]
   double *r = nullptr, *x = nullptr, *y = nullptr;
 };
@@ -98,4 +99,14 @@ int amg_create(feahip_ctx *c);
 void amg_destroy(feahip_ctx *c);
 int amg_prepare(feahip_ctx *c);                      // hierarchy for the current row range, numeric part for the current K
 double *amg_apply(feahip_ctx *c, const double *r);    // z = M^-1 r on the rank's rows; returns z
-double *amg_result(feahip_ctx *c);                    // the z of the last amg_apply
+double *amg_result(feahip_ctx *c);                    // the z of the last amg_apply; null if it failed to launch (c->err)
+// read-only view of the hierarchy (feahip_amg_info / feahip_amg_level), library ids; level 0's matrix in the context's
+// block order, the rank's rows only
+int amg_export_info(feahip_ctx *c, long long *out16, double *over);
+struct AmgLevelExport {
+  int N = 0, nnzb = 0, Nc = 0, bits = 64;
+  double omega = 0;
+  std::vector<int> rowptr, colidx, agg, type;
+  std::vector<double> K, doff;
+};
+int amg_export_level(feahip_ctx *c, int l, AmgLevelExport &e);

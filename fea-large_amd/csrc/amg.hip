@@ -1,6 +1,7 @@
 // amg.hip -- device side of the aggregation multigrid preconditioner (amg.h).
 #include "amg.h"
 #include "dpp_device.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -109,6 +110,29 @@ void k_galerkin(int npair, const int *prow, const int *crowptr, const int *cbptr
   for (int e = 0; e < 9; ++e) {
     const double v = sub == 0 ? acc[0][e] : (sub == 1 ? acc[1][e] : (sub == 2 ? acc[2][e] : acc[3][e]));
     o[e] = (TOUT)v;
+  }
+}
+
+// Galerkin blocks (I, J) and (J, I) are summed over different lists in different orders and rounded to single precision
+// apart: a stored coarse matrix came out symmetric to an ulp, not exactly, and the cycle with it (the smoother and the
+// tail multiply with the stored matrix) was not the symmetric operator CG is promised.  One thread per block row keeps
+// the upper triangle and writes every block below the diagonal as the transpose of its mirror (and the lower triangle
+// of the diagonal block from its upper one); it reads only what no thread writes.
+template <class T>
+__global__ void k_mirror_lower(int N, const int *rowptr, const int *colidx, const int *tpos, T *K)
+{
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= N) return;
+  for (int k = rowptr[a]; k < rowptr[a + 1]; ++k) {
+    const int b = colidx[k];
+    if (b > a) continue;
+    T *o = K + (size_t)k * 9;
+    if (b == a) { o[3] = o[1]; o[6] = o[2]; o[7] = o[5]; continue; }
+    const T *m = K + (size_t)tpos[k] * 9;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) o[3 * i + j] = m[3 * j + i];
   }
 }
 
@@ -243,25 +267,44 @@ __global__ void k_fill_pattern(int t0, int t1, int n, double *v)
   if (t < n) v[t] = (t >= t0 && t < t1) ? 1.0 + 0.37 * (double)((t * 2654435761u) >> 24) / 256.0 : 0.0;   // fixed pseudo-random start
 }
 // copies of the fine matrix for the smoother of level 0 (the CG itself multiplies with the double one): float, or
-// bfloat16 rounded to nearest even from the float
-__global__ void k_to_f32(size_t n, const double *src, float *dst)
+// bfloat16 rounded to nearest even from the float.  Both copies are made symmetric bit for bit: K's two triangles are
+// summed in different orders and can differ in the last bit, and the copy is what the smoother multiplies with, so a
+// block below the diagonal is rounded from its mirror block above it, a diagonal block's lower triangle from its upper
+// one.  cbrow[q]: the row of block q, -1 for a block outside the rank's diagonal block (taken as it is).
+__device__ __forceinline__ double sym_value(const double *K, const int *rowptr, const int *colidx, const int *cbrow, size_t q, int i, int j)
 {
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) dst[t] = (float)src[t];
+  const int a = cbrow[q], b = colidx[q];
+  if (a < 0 || b > a) return K[q * 9 + 3 * i + j];
+  if (b == a) return i <= j ? K[q * 9 + 3 * i + j] : K[q * 9 + 3 * j + i];
+  int lo = rowptr[b], hi = rowptr[b + 1];               // block (b, a): the pattern is symmetric
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (colidx[mid] < a) lo = mid + 1; else hi = mid; }
+  if (lo == rowptr[b + 1] || colidx[lo] != a) return K[q * 9 + 3 * i + j];
+  return K[(size_t)lo * 9 + 3 * j + i];
+}
+__global__ void k_to_f32(size_t q0, size_t n, const double *K, const int *rowptr, const int *colidx, const int *cbrow, float *dst)
+{
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+    const size_t q = q0 + t / 9;
+    const int e = (int)(t % 9);
+    dst[q0 * 9 + t] = (float)sym_value(K, rowptr, colidx, cbrow, q, e / 3, e % 3);
+  }
 }
 // (n rows of three values -> rows of four, 8 bytes: three values and a pad.  The pads of a block's first two rows carry
 // the low and the high half of its column index: the smoother's product reads 24 bytes per block and no index array)
-__global__ void k_to_bf16(size_t nrows3, const double *src, const int *col, unsigned short *dst)
+__global__ void k_to_bf16(size_t q0, size_t nrows3, const double *K, const int *rowptr, const int *colidx, const int *cbrow,
+                          unsigned short *dst)
 {
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < nrows3; t += (size_t)gridDim.x * blockDim.x) {
     unsigned short o[4] = {0, 0, 0, 0};
+    const size_t q = q0 + t / 3;
     for (int j = 0; j < 3; ++j) {
-      const unsigned u = __float_as_uint((float)src[t * 3 + j]);
+      const unsigned u = __float_as_uint((float)sym_value(K, rowptr, colidx, cbrow, q, (int)(t % 3), j));
       o[j] = (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
     }
-    const unsigned c = (unsigned)col[t / 3];
+    const unsigned c = (unsigned)colidx[q];
     const int rib = (int)(t % 3);
     o[3] = rib == 0 ? (unsigned short)(c & 0xFFFFu) : (rib == 1 ? (unsigned short)(c >> 16) : (unsigned short)0);
-    reinterpret_cast<uint2 *>(dst)[t] = make_uint2((unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16));
+    reinterpret_cast<uint2 *>(dst)[q0 * 3 + t] = make_uint2((unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16));
   }
 }
 
@@ -792,6 +835,16 @@ int amg_create(feahip_ctx *c)
       if ((rc = zeros(c, &L.x, (size_t)L.N * 3, h->bytes))) return rc;
       if ((rc = zeros(c, &L.y, (size_t)L.N * 3, h->bytes))) return rc;
       if ((rc = up(c, &L.type, S.type, h->bytes))) return rc;
+      std::vector<int> tpos(S.colidx.size());
+      for (int a = 0; a < S.N; ++a)
+        for (int k = S.rowptr[a]; k < S.rowptr[a + 1]; ++k) {
+          const int b = S.colidx[k];
+          const int *cb = S.colidx.data() + S.rowptr[b], *ce = S.colidx.data() + S.rowptr[b + 1];
+          const int *p = std::lower_bound(cb, ce, a);
+          if (p == ce || *p != a) { c->err = "multigrid: coarse pattern is not symmetric"; return FEAHIP_ESTATE; }
+          tpos[k] = (int)(p - S.colidx.data());
+        }
+      if ((rc = up(c, &L.tpos, tpos, h->bytes))) return rc;
     }
     if ((rc = zeros(c, &L.minv, (size_t)L.N * 9, h->bytes))) return rc;
     if (S.Sc > 0) {
@@ -841,7 +894,7 @@ void amg_destroy(feahip_ctx *c)
   AmgHierarchy *h = H(c);
   if (!h) return;
   for (AmgLevel &L : h->lv) {
-    void *own[] = {L.minv, L.agg, L.doff, L.aptr, L.anodes, L.cbptr, L.cblist, L.prow, L.cbrow, L.r, L.x, L.y, L.type};
+    void *own[] = {L.minv, L.agg, L.doff, L.aptr, L.anodes, L.cbptr, L.cblist, L.prow, L.cbrow, L.r, L.x, L.y, L.type, L.tpos};
     for (void *p : own) if (p) (void)hipFree(p);
     if (L.owns_matrix) { void *m[] = {L.rowptr, L.colidx, L.diag, L.chunk, L.K, L.K32}; for (void *p : m) if (p) (void)hipFree(p); }
     else { if (L.K32) (void)hipFree(L.K32); if (L.K16) (void)hipFree(L.K16); }
@@ -890,8 +943,8 @@ static int amg_numeric(feahip_ctx *c)
     const LevelRange R = level_range(c, l);
     if (l == 0 && (L.K32 || L.K16)) {                    // the rank's rows only
       const size_t q0 = (size_t)c->h_rowptr[(size_t)h->row0] * 9, q1 = (size_t)c->h_rowptr[(size_t)h->row1] * 9;
-      if (L.K16) hipLaunchKernelGGL(k_to_bf16, dim3(4096), dim3(256), 0, c->stream, (q1 - q0) / 3, (const double *)L.K + q0, L.colidx + q0 / 9, L.K16 + q0 / 3 * 4);
-      else hipLaunchKernelGGL(k_to_f32, dim3(4096), dim3(256), 0, c->stream, q1 - q0, (const double *)L.K + q0, L.K32 + q0);
+      if (L.K16) hipLaunchKernelGGL(k_to_bf16, dim3(4096), dim3(256), 0, c->stream, q0 / 9, (q1 - q0) / 3, (const double *)L.K, L.rowptr, L.colidx, L.cbrow, L.K16);
+      else hipLaunchKernelGGL(k_to_f32, dim3(4096), dim3(256), 0, c->stream, q0 / 9, q1 - q0, (const double *)L.K, L.rowptr, L.colidx, L.cbrow, L.K32);
     }
     if (l > 0 && L.K32) hipLaunchKernelGGL(k_block_inverse<float>, GROWS(R), R.a0, R.a1, L.diag, L.K32, L.minv);
     else hipLaunchKernelGGL(k_block_inverse<double>, GROWS(R), R.a0, R.a1, L.diag, L.K, L.minv);
@@ -904,6 +957,8 @@ static int amg_numeric(feahip_ctx *c)
       else if (C.K32) GALERKIN(double, float, L.K, C.K32);
       else GALERKIN(double, double, L.K, C.K);
 #undef GALERKIN
+      if (C.K32) hipLaunchKernelGGL(k_mirror_lower<float>, G256(C.N), C.N, C.rowptr, C.colidx, C.tpos, C.K32);
+      else hipLaunchKernelGGL(k_mirror_lower<double>, G256(C.N), C.N, C.rowptr, C.colidx, C.tpos, C.K);
     }
     // lambda_max(D^-1 K) by a few power iterations -> omega = 4 / (3 lambda_max).  The iteration stays on the device:
     // the squared norm of every step lands in d_lam[l] and the next step scales by it there (k_scale_by_norm); the
@@ -1002,7 +1057,7 @@ static TailArgs tail_args(feahip_ctx *c)
   return A;
 }
 
-static void launch_tail(feahip_ctx *c)
+static int launch_tail(feahip_ctx *c)
 {
   TailArgs A = tail_args(c);
   const int off = A.lds_doubles;
@@ -1025,12 +1080,20 @@ static void launch_tail(feahip_ctx *c)
   }
 #endif
   const int lds = off * 8;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_amg_tail), hipFuncAttributeMaxDynamicSharedMemorySize, lds);   // per device, per size
+  // a launch that fails would leave the last cycle's x of the entry level in place: the error reaches the caller
+  if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_amg_tail), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {   // per device, per size
+    (void)hipGetLastError();
+    c->err = "multigrid: the one-workgroup tail's LDS size was refused";
+    return FEAHIP_EHIP;
+  }
   hipLaunchKernelGGL(k_amg_tail, dim3(1), dim3(FEA_TAIL_T), lds, c->stream, A);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { c->err = std::string("multigrid: tail launch failed: ") + hipGetErrorString(e); return FEAHIP_EHIP; }
+  return FEAHIP_OK;
 }
 
 // returns where the level's result is: x or y (the post-smoothing sweep is fused with its product and writes the other
-// vector); `part`: partial sums of result . r from that last launch (level 0: the CG's r.z), or null
+// vector), or null when the tail failed to launch (c->err); `part`: partial sums of result . r from that last launch (level 0: the CG's r.z), or null
 static double *amg_cycle(feahip_ctx *c, int l, const double *r, double *x, double *y, double *part = nullptr)
 {
   AmgHierarchy *h = H(c);
@@ -1060,8 +1123,8 @@ static double *amg_cycle(feahip_ctx *c, int l, const double *r, double *x, doubl
     level_spmv(c, L, R, x, y);
     hipLaunchKernelGGL(k_restrict, G256((C.N / 2) * 16), C.N / 2, L.aptr, L.anodes, L.type, L.doff, r, y, mask, C.r);
     const double *xc = C.x;
-    if (l + 1 == h->tail_from) launch_tail(c);
-    else xc = amg_cycle(c, l + 1, C.r, C.x, C.y);
+    if (l + 1 == h->tail_from) { if (launch_tail(c)) return nullptr; }
+    else if (!(xc = amg_cycle(c, l + 1, C.r, C.x, C.y))) return nullptr;
     // over-correction only where the correction is applied twice: (I - aE)^2 >= 0 for any a <= 2, while a single
     // over-corrected step can flip the sign of the preconditioner on part of the spectrum (seen: 6 492 iterations)
     hipLaunchKernelGGL(k_prolong, G256(L.N), L.N, L.agg, L.type, L.doff, xc, mask, gamma >= 2 ? h->over : fmin(h->over, 1.0), x);
@@ -1102,4 +1165,84 @@ double *amg_apply(feahip_ctx *c, const double *r)
   AmgHierarchy *h = H(c);
   h->result = amg_vcycle(c, r, h->d_z);
   return h->result;
+}
+
+// ---- read-only view (feahip_amg_info / feahip_amg_level) ---------------------
+static int fetch(feahip_ctx *c, void *dst, const void *src, size_t bytes)
+{
+  if (!bytes) return FEAHIP_OK;
+  FEA_HIP_CHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+int amg_export_info(feahip_ctx *c, long long *o, double *over)
+{
+  AmgHierarchy *h = H(c);
+  for (int k = 0; k < 16; ++k) o[k] = 0;
+  o[0] = (long long)h->lv.size(); o[1] = h->gamma; o[2] = h->gamma_from; o[3] = h->gamma_until; o[4] = h->coarse_sweeps;
+  o[5] = h->fine_bits; o[6] = h->coarse_f32; o[7] = h->fused_post; o[8] = h->tail_from;
+  if (h->tail_from >= 0) {
+    const TailArgs A = tail_args(c);
+    o[9] = A.lv[0].o_K >= 0 ? 1 : (A.ell ? 2 : 3);      // the entry level's product: LDS, lane-major ELL, L2
+    o[10] = A.cop != nullptr;
+    for (int k = 0; k < A.nl; ++k) if (A.lv[k].o_K >= 0) o[11] |= 1LL << (h->tail_from + k);
+    o[14] = A.blob != nullptr;
+  }
+  o[12] = h->row0; o[13] = h->row1;
+  *over = h->over;
+  return FEAHIP_OK;
+}
+
+int amg_export_level(feahip_ctx *c, int l, AmgLevelExport &e)
+{
+  AmgHierarchy *h = H(c);
+  if (l < 0 || l >= (int)h->lv.size()) { c->err = "multigrid: no such level"; return FEAHIP_EINVAL; }
+  const AmgLevel &L = h->lv[(size_t)l];
+  int rc;
+  e.N = L.N; e.nnzb = L.nnzb; e.Nc = L.Nc; e.omega = L.omega;
+  e.bits = l == 0 ? h->fine_bits : (L.K32 ? 32 : 64);
+  e.K.assign((size_t)L.nnzb * 9, 0.0);
+  e.type.assign((size_t)L.N, 0);
+  e.agg.assign((size_t)L.N, -1);
+  e.doff.assign((size_t)L.N * 3, 0.0);
+  if (l == 0) {
+    // the context's whole pattern (a rank's level 0 keeps its own diagonal block's pattern on the host only)
+    e.rowptr = c->h_rowptr; e.colidx = c->h_colidx;
+    e.nnzb = (int)c->h_colidx.size();
+    e.K.assign(c->h_colidx.size() * 9, 0.0);
+    const size_t q0 = (size_t)c->h_rowptr[(size_t)h->row0], q1 = (size_t)c->h_rowptr[(size_t)h->row1];
+    if (L.K16) {
+      std::vector<unsigned short> b((q1 - q0) * 12);
+      if ((rc = fetch(c, b.data(), L.K16 + q0 * 12, b.size() * 2))) return rc;
+      for (size_t q = 0; q < q1 - q0; ++q)
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            const unsigned u = (unsigned)b[q * 12 + 4 * i + j] << 16;
+            float f; memcpy(&f, &u, 4);
+            e.K[(q0 + q) * 9 + 3 * i + j] = f;
+          }
+    } else if (L.K32) {
+      std::vector<float> b((q1 - q0) * 9);
+      if ((rc = fetch(c, b.data(), L.K32 + q0 * 9, b.size() * 4))) return rc;
+      for (size_t t = 0; t < b.size(); ++t) e.K[q0 * 9 + t] = b[t];
+    } else if ((rc = fetch(c, e.K.data() + q0 * 9, L.K + q0 * 9, (q1 - q0) * 9 * 8))) return rc;
+  } else {
+    e.rowptr.resize((size_t)L.N + 1); e.colidx.resize((size_t)L.nnzb);
+    if ((rc = fetch(c, e.rowptr.data(), L.rowptr, e.rowptr.size() * 4))) return rc;
+    if ((rc = fetch(c, e.colidx.data(), L.colidx, e.colidx.size() * 4))) return rc;
+    if (L.K32) {
+      std::vector<float> b((size_t)L.nnzb * 9);
+      if ((rc = fetch(c, b.data(), L.K32, b.size() * 4))) return rc;
+      for (size_t t = 0; t < b.size(); ++t) e.K[t] = b[t];
+    } else if ((rc = fetch(c, e.K.data(), L.K, e.K.size() * 8))) return rc;
+    std::vector<uint8_t> t((size_t)L.N);
+    if ((rc = fetch(c, t.data(), L.type, t.size()))) return rc;
+    for (int i = 0; i < L.N; ++i) e.type[(size_t)i] = t[(size_t)i];
+  }
+  if (L.Nc > 0) {
+    if ((rc = fetch(c, e.agg.data(), L.agg, e.agg.size() * 4))) return rc;
+    if ((rc = fetch(c, e.doff.data(), L.doff, e.doff.size() * 8))) return rc;
+  }
+  return FEAHIP_OK;
 }

@@ -78,7 +78,7 @@ void release_k(feahip_ctx *c)
   if (c->d_K_alloc) (void)hipFree(c->d_K_alloc);
   if (c->d_Kstash_alloc) (void)hipFree(c->d_Kstash_alloc);
   c->d_K_alloc = c->d_Kstash_alloc = c->d_K_base = c->d_Kstash_base = c->d_K = c->d_Kstash = nullptr;
-  c->have_stash = false; c->k_bc = false; ++c->k_epoch;
+  c->have_stash = false; c->k_bc = false; c->k_valid = false; ++c->k_epoch;
 }
 
 // shared-state maps of 10-node elements for the assembly chunks this rank owns
@@ -933,6 +933,81 @@ extern "C" int feahip_spmv(feahip_ctx *c, const double *x, double *y)
   rc = launch_spmv(c, c->d_p, c->d_q);
   if (rc) return rc;
   return get_node_vec(c, c->d_q, y);
+}
+
+extern "C" int feahip_apply_preconditioner(feahip_ctx *c, const double *r, double *z)
+{
+  CTX_GUARD(c);
+  if (!r || !z) return FEAHIP_EINVAL;
+  if (!c->k_valid) { c->err = "apply_preconditioner: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+  int rc = set_node_vec(c, c->d_r, r);
+  if (rc) return rc;
+  const double *dz = nullptr;
+  if ((rc = precond_apply(c, c->d_r, &dz))) return rc;
+  std::vector<double> tmp((size_t)c->ndof, 0.0);                 // rows of other ranks: 0
+  if ((rc = get_vec(c, dz + (size_t)3 * c->row0, tmp.data() + (size_t)3 * c->row0, (size_t)3 * (c->row1 - c->row0)))) return rc;
+  for (int a = 0; a < c->N; ++a)
+    for (int j = 0; j < 3; ++j) z[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+  return FEAHIP_OK;
+}
+
+// the hierarchy as the next PCG solve would use it (prepared here when K changed since)
+static int amg_ready(feahip_ctx *c)
+{
+  if (c->precond != 1) { c->err = "multigrid view: the preconditioner is not the multigrid (feahip_set_preconditioner(1))"; return FEAHIP_ESTATE; }
+  if (!c->k_valid) { c->err = "multigrid view: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+  return amg_prepare(c);
+}
+
+extern "C" int feahip_amg_info(feahip_ctx *c, long long *out16, double *over)
+{
+  CTX_GUARD(c);
+  if (!out16 || !over) return FEAHIP_EINVAL;
+  int rc = amg_ready(c);
+  if (rc) return rc;
+  return amg_export_info(c, out16, over);
+}
+
+extern "C" int feahip_amg_level(feahip_ctx *c, int level, long long *counts, double *omega, int *rowptr, int *colidx,
+                                double *K, int *agg, double *doff, int *type)
+{
+  CTX_GUARD(c);
+  if (!counts) return FEAHIP_EINVAL;
+  int rc = amg_ready(c);
+  if (rc) return rc;
+  AmgLevelExport e;
+  if ((rc = amg_export_level(c, level, e))) return rc;
+  counts[0] = e.N; counts[1] = e.nnzb; counts[2] = e.Nc; counts[3] = e.bits;
+  if (omega) *omega = e.omega;
+  if (!rowptr || !colidx || !K || !agg || !doff || !type) return FEAHIP_OK;    // sizing call
+  if (level > 0 || c->perm.empty()) {
+    std::copy(e.rowptr.begin(), e.rowptr.end(), rowptr);
+    std::copy(e.colidx.begin(), e.colidx.end(), colidx);
+    std::copy(e.K.begin(), e.K.end(), K);
+    std::copy(e.agg.begin(), e.agg.end(), agg);
+    std::copy(e.doff.begin(), e.doff.end(), doff);
+    std::copy(e.type.begin(), e.type.end(), type);
+    return FEAHIP_OK;
+  }
+  // level 0 in the caller's node ids, every row's blocks sorted by the caller's column (feahip_get_matrix_yale's order)
+  std::vector<std::pair<int, int>> row;
+  size_t pos = 0;
+  rowptr[0] = 0;
+  for (int a = 0; a < c->N; ++a) {
+    const int la = lib_id(c, a);
+    row.clear();
+    for (int q = e.rowptr[(size_t)la]; q < e.rowptr[(size_t)la + 1]; ++q) row.emplace_back(c->iperm[(size_t)e.colidx[(size_t)q]], q);
+    std::sort(row.begin(), row.end());
+    for (const auto &cb : row) {
+      colidx[pos] = cb.first;
+      for (int t = 0; t < 9; ++t) K[pos * 9 + t] = e.K[(size_t)cb.second * 9 + t];
+      pos++;
+    }
+    rowptr[a + 1] = (int)pos;
+    agg[a] = e.agg[(size_t)la]; type[a] = e.type[(size_t)la];
+    for (int d = 0; d < 3; ++d) doff[(size_t)a * 3 + d] = e.doff[(size_t)la * 3 + d];
+  }
+  return FEAHIP_OK;
 }
 
 extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters, double *avg_ms)

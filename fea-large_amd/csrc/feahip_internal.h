@@ -420,6 +420,7 @@ struct feahip_ctx {
   // (modified Newton restores the same matrix every iteration); a stale hierarchy would cost iterations, not accuracy.
   unsigned long long k_epoch = 0, stash_epoch = 0;
   bool k_bc = false;
+  bool k_valid = false;                // a stiffness assembly has filled d_K since it was (re)allocated
   // golden-section line search along the Newton step: iterations (0 = off, the reference's solve())
   int linesearch_max = 0;
   int precond = 0;
@@ -459,6 +460,7 @@ int ensure_visits(feahip_ctx *c);
 int dist_nodes_add_scaled(std::vector<feahip_ctx *> &R, double eta, bool exchange);
 int launch_update_nodes_solution(feahip_ctx *c, const double *d_u);
 int launch_spmv(feahip_ctx *c, const double *d_xv, double *d_yv);
+int precond_apply(feahip_ctx *c, const double *r, const double **z);   // kernels_solve.hip
 int solve_pcg(feahip_ctx *c, int type, double tol, int max_iter, int *iters,
               double *resid);
 int time_pcg_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);

@@ -403,6 +403,7 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF)
   if (strat < 0) return strat;
   c->last_strategy = strat;                          // the kernel that runs, after the residual-only fallbacks
   const int rc = dispatch_assembly(c, strat, doK, doF);
+  if (!rc && doK) c->k_valid = true;
   if (rc || !doF) return rc;
   return launch_surface_loads(c, c->d_f);            // f = lambda F_ext - T (nothing to launch without loads)
 }

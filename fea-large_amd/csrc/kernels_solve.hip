@@ -777,6 +777,33 @@ static void enq_precond(feahip_ctx *c, int mode)
                      own0(c), own1(c), c->d_diag, c->d_K, mode, c->d_minv);
 }
 
+// z = M^-1 r on the rank's rows with the preconditioner a PCG solve would use now (feahip_apply_preconditioner); r, z
+// device vectors in library ids.  Block-Jacobi leaves z in q, the multigrid where its cycle ends.  Either way only the
+// scratch a solve overwrites at its start is touched, and the multigrid is prepared exactly as enq_cg_start does.
+__global__ void k_precond_apply(int a0, int a1, const double *minv, const double *r, double *z)
+{
+  const int a = a0 + blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= a1) return;
+  const double *m = minv + (size_t)a * 9, *v = r + (size_t)a * 3;
+  for (int i = 0; i < 3; ++i) z[(size_t)a * 3 + i] = m[3 * i] * v[0] + m[3 * i + 1] * v[1] + m[3 * i + 2] * v[2];
+}
+int precond_apply(feahip_ctx *c, const double *r, const double **z)
+{
+  int rc;
+  if (c->precond == 1) {
+    if ((rc = amg_prepare(c))) return rc;
+    if (!(*z = amg_apply(c, r))) return FEAHIP_EHIP;
+    return FEAHIP_OK;
+  }
+  enq_precond(c, 1);
+  const int n = own1(c) - own0(c);
+  hipLaunchKernelGGL(k_precond_apply, dim3((n + 255) / 256 > 0 ? (n + 255) / 256 : 1), dim3(256), 0, c->stream, own0(c), own1(c),
+                     c->d_minv, r, c->d_q);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  *z = c->d_q;
+  return FEAHIP_OK;
+}
+
 static void enq_spmv_dot(feahip_ctx *c, const double *xv, double *yv, const double *dotwith, double *part)
 {
   hipLaunchKernelGGL(k_spmv, dim3(spmv_grid(c)), dim3(256), 0, c->stream, c->chunk0, c->nchunks_local, c->d_chunk,
@@ -980,6 +1007,7 @@ static int enq_cg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it, 
                        T ? c->d_scal + 8 : (const double *)nullptr, c->d_scal, c->d_flag, amg ? (double *)nullptr : c->d_q);
     if (amg) {
       const double *z = amg_apply(c, c->d_r);                      // local: block-Jacobi over the ranks, a W-cycle inside
+      if (!z) return FEAHIP_EHIP;
       hipLaunchKernelGGL(k_dot_partial, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), c->d_r, z, c->d_part + RB);
     }
     if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, gv, 2, RB, c->d_part + RB, c->d_scal + 9);
@@ -1012,6 +1040,7 @@ static int enq_cg_start(std::vector<feahip_ctx *> &R, Transport *T, int mode, do
                        amg ? (const double *)nullptr : c->d_minv, c->d_r, c->d_p, c->d_part);
     if (amg) {                                                   // p = z = M^-1 r from the cycle, r.z from it
       const double *z = amg_apply(c, c->d_r);
+      if (!z) return FEAHIP_EHIP;
       hipLaunchKernelGGL(k_dot_partial, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), c->d_r, z, c->d_part + RB);
       FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_p + (size_t)3 * own0(c), z + (size_t)3 * own0(c),
                                       sizeof(double) * 3 * (size_t)(own1(c) - own0(c)), hipMemcpyDeviceToDevice, c->stream));
@@ -1098,6 +1127,7 @@ static int enq_cgcg_start(std::vector<feahip_ctx *> &R, Transport *T, int mode, 
                        amg ? (const double *)nullptr : c->d_minv, c->d_r, c->d_z, c->d_part);
     if (amg) {
       const double *z = amg_apply(c, c->d_r);
+      if (!z) return FEAHIP_EHIP;
       hipLaunchKernelGGL(k_copy_dot, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), z, c->d_r, c->d_z, c->d_part + RB, (const int *)nullptr);
     }
   }
@@ -1127,6 +1157,7 @@ static int enq_cgcg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it
                        c->d_scal + 8, c->d_scal, c->d_flag);
     if (amg) {
       const double *z = amg_apply(c, c->d_r);                      // local: block-Jacobi over the ranks, a W-cycle inside
+      if (!z) return FEAHIP_EHIP;
       hipLaunchKernelGGL(k_copy_dot, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), z, c->d_r, c->d_z, c->d_part + RB, (const int *)c->d_flag);
     }
   }

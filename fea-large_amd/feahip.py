@@ -96,7 +96,13 @@ ABI = {
     "feahip_set_load_factor": [C.c_void_p, C.c_double],
     "feahip_get_load_factor": [C.c_void_p, _dp],
     "feahip_host_surface_faces": [C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip, _ip, _ip],
+    "feahip_apply_preconditioner": [C.c_void_p, _dp, _dp],
+    "feahip_amg_info": [C.c_void_p, C.POINTER(C.c_longlong), _dp],
+    "feahip_amg_level": [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), _dp, _ip, _ip, _dp, _ip, _dp, _ip],
 }
+AMG_INFO_KEYS = ("levels", "gamma", "gamma_from", "gamma_until", "coarse_sweeps", "fine_bits", "coarse_f32", "fused_post",
+                 "tail_from", "tail_entry", "tail_cop", "tail_lds_levels", "row0", "row1", "tail_blob")
+TAIL_ENTRY = {0: None, 1: "lds", 2: "ell", 3: "l2"}
 
 _lib = None
 _host = None
@@ -500,6 +506,40 @@ class FeaSolver:
     def set_preconditioner(self, kind):
         self._chk(self._lib.feahip_set_preconditioner(self._ctx, kind))
 
+    def apply_preconditioner(self, r):
+        """z = M^-1 r with the preconditioner the next PCG solve would use (set_preconditioner), for the current K."""
+        r = np.ascontiguousarray(r, dtype=np.float64).ravel()
+        z = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_apply_preconditioner(self._ctx, _d(r), _d(z)))
+        return z
+
+    def amg_info(self):
+        """The multigrid hierarchy's parameters and which paths its one-workgroup tail takes (feahip_amg_info)."""
+        o = (C.c_longlong * 16)()
+        over = C.c_double(0)
+        self._chk(self._lib.feahip_amg_info(self._ctx, o, C.byref(over)))
+        d = dict(zip(AMG_INFO_KEYS, [int(v) for v in o]))
+        d["tail_entry"] = TAIL_ENTRY[d["tail_entry"]]
+        d["coarse_f32"], d["fused_post"], d["tail_cop"], d["tail_blob"] = (bool(d[k]) for k in ("coarse_f32", "fused_post", "tail_cop", "tail_blob"))
+        d["tail_lds_levels"] = [l for l in range(d["levels"]) if d["tail_lds_levels"] >> l & 1]
+        d["over"] = over.value
+        return d
+
+    def amg_level(self, level):
+        """One level of the hierarchy as stored (feahip_amg_level): dict N, nnzb, Nc, bits, omega, rowptr, colidx,
+        K [nnzb][3][3] widened to double, agg, doff [N][3], type.  Level 0 in the caller's node ids."""
+        cnt = (C.c_longlong * 4)()
+        om = C.c_double(0)
+        self._chk(self._lib.feahip_amg_level(self._ctx, level, cnt, C.byref(om), None, None, None, None, None, None))
+        N, nnzb, Nc, bits = (int(v) for v in cnt)
+        rowptr, colidx = np.zeros(N + 1, dtype=np.int32), np.zeros(max(nnzb, 1), dtype=np.int32)
+        K, agg = np.zeros((max(nnzb, 1), 3, 3)), np.zeros(max(N, 1), dtype=np.int32)
+        doff, typ = np.zeros((max(N, 1), 3)), np.zeros(max(N, 1), dtype=np.int32)
+        self._chk(self._lib.feahip_amg_level(self._ctx, level, cnt, C.byref(om), _i(rowptr), _i(colidx), _d(K), _i(agg),
+                                             _d(doff), _i(typ)))
+        return dict(N=N, nnzb=nnzb, Nc=Nc, bits=bits, omega=om.value, rowptr=rowptr, colidx=colidx[:nnzb], K=K[:nnzb],
+                    agg=agg[:N], doff=doff[:N], type=typ[:N])
+
     def set_pcg_variant(self, variant):
         self._chk(self._lib.feahip_set_pcg_variant(self._ctx, variant))
 
@@ -769,6 +809,25 @@ class FeaGroup:
 
     def each(self, name, *args):
         return [getattr(r, name)(*args) for r in self.ranks]
+
+    def apply_preconditioner(self, r):
+        """Every rank's z = M^-1 r on its own rows, stitched together: the block-diagonal preconditioner the group's PCG
+        uses.  r in the deck's node ids."""
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 3)
+        z = np.zeros_like(r)
+        for rk, nd in zip(self.ranks, self.nodes):
+            if self.rank_contexts:
+                zr = rk.apply_preconditioner(r[rk.node_global]).reshape(-1, 3)
+                z[nd] += zr[:rk.n_own]
+            else:
+                z[nd] += rk.apply_preconditioner(r).reshape(-1, 3)[nd]
+        return z.ravel()
+
+    def amg_info(self):
+        return self.each("amg_info")
+
+    def amg_level(self, level):
+        return self.each("amg_level", level)
 
     def solve_slae(self, solver_type, tolerance, max_iterations):
         it, res = C.c_int(0), C.c_double(0)

@@ -364,6 +364,41 @@ int feahip_set_assembly(feahip_ctx *ctx, int strategy);
  * way the solve runs to the requested residual, so the solution is the same
  * to that tolerance.                                                          */
 int feahip_set_preconditioner(feahip_ctx *ctx, int kind);
+/* z = M^-1 r with the preconditioner a PCG solve (feahip_solve_slae with
+ * PCG_ILU) would use now, for the current K: kind 0 the 3x3 block-Jacobi,
+ * kind 1 one multigrid W-cycle, prepared as the solve prepares it.  r and z
+ * are [N][3] in the caller's node ids.  On a sharded context z covers the
+ * rank's rows and is 0 elsewhere.  FEAHIP_ESTATE before the first stiffness
+ * assembly.  Touches only scratch that a solve overwrites at its start.  A
+ * solve's multigrid cycles (and this) return FEAHIP_EHIP if the tail kernel
+ * of the small levels fails to launch.                                       */
+int feahip_apply_preconditioner(feahip_ctx *ctx, const double *r, double *z);
+/* Read-only view of the multigrid hierarchy (preconditioner 1) for the
+ * current K; prepared here if K changed since the last solve.
+ * out16: 0 levels, 1 gamma, 2 gamma_from, 3 gamma_until, 4 coarse_sweeps,
+ * 5 fine_bits (level-0 smoother matrix: 16 bfloat16, 32 float, 64 K),
+ * 6 coarse matrices in float, 7 fused post-smoothing, 8 tail_from (first
+ * level of the one-workgroup tail, -1 none), 9 the tail's entry-level
+ * product (0 no tail, 1 matrix in LDS, 2 lane-major ELL copy, 3 CSR from L2),
+ * 10 the coarsest level as one dense operator, 11 bit l set: level l's
+ * matrix sits in the tail's LDS, 12/13 the rank's rows [row0, row1) in
+ * library ids, 14 the tail's packed blob in use.  *over: the over-correction.
+ * FEAHIP_ESTATE unless preconditioner 1 is set and K was assembled.          */
+int feahip_amg_info(feahip_ctx *ctx, long long *out16, double *over);
+/* One level.  counts[4]: N block rows, nnzb blocks, Nc block rows of the
+ * next level (0 on the coarsest), bits of the stored matrix (level 0: the
+ * smoother's copy; below: 32 or 64).  *omega: the level's Jacobi damping.
+ * With rowptr..type null only counts and omega are written (sizing call);
+ * otherwise rowptr[N+1], colidx[nnzb], K[nnzb][3][3] (the matrix as stored,
+ * widened to double), agg[N], doff[N][3], type[N] (0 translation row,
+ * 1 rotation row).  agg / doff map to the next level (-1 / 0 on the
+ * coarsest).  Level 0 speaks the caller's node ids, its blocks ordered as
+ * feahip_get_matrix_yale orders them, and only the rank's rows carry values
+ * (agg = -1 elsewhere).  Coarse levels speak the library's own aggregate ids:
+ * aggregate A of level l is block rows 2A (translation) and 2A+1 (rotation)
+ * of level l+1.                                                              */
+int feahip_amg_level(feahip_ctx *ctx, int level, long long *counts, double *omega, int *rowptr, int *colidx,
+                     double *K, int *agg, double *doff, int *type);
 /* The CG / PCG loop of feahip_solve_slae.  0: the textbook loop (what the
  * reference's sp_matrix_yale_solve_cg / _pcg_ilu run, fea_solver.c:245-280):
  * two reductions per iteration (p.Kp, then r.z and r.r), halo rows exchanged
