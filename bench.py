@@ -15,6 +15,15 @@ With N > 1 the block rows (hence the elements that touch them) are sharded
 over the ranks as slabs across the long axis; assembly needs no collective,
 so the data path has none -- torch.distributed (RCCL) only carries the
 barrier and the max-over-ranks of the wall time.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, ramp the clocks, warm
+up, time the K steps, write --dump-outputs if asked, print the line.  Everything
+else the benchmark measures or checks runs with --full, after the timed steps:
+per-kernel timings and the roofline, the cross-check of the timed K, the copy
+bandwidth, the TET10, HEX8 and off-lattice legs, the PCG / Newton solve legs
+(with N > 1: the RCCL communicator they need) and the CPU baselines (the
+all-cores ones before the GPU is touched).  The --cpu-sample, --no-newton,
+--cpu-single-only, --no-tet10 and --no-off-lattice switches choose among those.
 """
 import argparse
 import json
@@ -269,22 +278,25 @@ def main():
     ap.add_argument("--hex", action="store_true", help="HEXAHEDRA8 / 8 Gauss points: one trilinear brick per cube (n x 6n x n bricks)")
     ap.add_argument("--model", default="neohookean", choices=["neohookean", "a5"])
     ap.add_argument("--cpu-sample", type=int, default=None,
-                    help="n of the CPU-baseline sample block (0 = skip; default: ~10 s of single-core work, 48 for TET4, 14 for TET10)")
-    ap.add_argument("--no-newton", action="store_true", help="skip the single full Newton iteration")
+                    help="--full: n of the CPU-baseline sample block (0 = skip; default: ~10 s of single-core work, 48 for TET4, 14 for TET10)")
+    ap.add_argument("--no-newton", action="store_true", help="--full: skip the single full Newton iteration")
     ap.add_argument("--assembly", default="auto", help="assembly strategy: auto | gather | staged | ... (fea_hip.h)")
     ap.add_argument("--numbering", default="lex", help="node numbering the CALLER hands in: 'lex' = x fastest, z, y slowest (default; the "
                     "library numbers the nodes itself, csrc/renumber.cpp), 'brick' = bricks of 4x4x4 nodes (3x4x4 half-grid nodes with "
                     "--quadratic), or bx,by,bz")
-    ap.add_argument("--cpu-single-only", action="store_true", help="skip the one-oracle-copy-per-core CPU baseline")
-    ap.add_argument("--no-tet10", action="store_true", help="skip the small TET10 leg of extras")
+    ap.add_argument("--cpu-single-only", action="store_true", help="--full: skip the one-oracle-copy-per-core CPU baseline")
+    ap.add_argument("--no-tet10", action="store_true", help="--full: skip the small TET10 and HEX8 legs of extras")
     ap.add_argument("--mesh", default="block", choices=["block", "tetgen"],
                     help="tetgen: the unstructured linear-tet mesh of the third off-lattice leg (corner tetrahedra of the reference's "
                          "TetGen deck, 8 x 8 x 7 copies) as THE workload, assembly only -- for rocprofv3 / PMC passes of that case")
-    ap.add_argument("--no-off-lattice", action="store_true", help="skip the off-lattice legs of extras (jittered + permuted block, tiled TetGen deck)")
+    ap.add_argument("--no-off-lattice", action="store_true", help="--full: skip the off-lattice legs of extras (jittered + permuted block, tiled TetGen deck)")
     ap.add_argument("--pcg-variant", type=int, default=-1, help="-1: the context's default; 0: two-reduction PCG; 1: single-reduction PCG")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (stiffness matrix rows and residual, a fixed "
                          "seeded sample of at most 64 MB in all) to DIR/<name>.npy, float64 (one GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: kernel timings and roofline, the check of the timed K, "
+                         "copy bandwidth, the TET10 / HEX8 / off-lattice legs, the solve legs and the CPU baselines")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -308,7 +320,7 @@ def main():
     import mesh
     model = feahip.MODEL_COMPRESSIBLE_NEOHOOKEAN if args.model == "neohookean" else feahip.MODEL_A5
     cpu_all = cpu_omp = None
-    if world == 1 and args.cpu_sample > 0 and not args.cpu_single_only:
+    if args.full and world == 1 and args.cpu_sample > 0 and not args.cpu_single_only:
         # before anything touches the GPU: child processes, one oracle copy per host core (at most 16)
         try:
             cpu_all = cpu_baseline_all_cores(args.cpu_sample, args.quadratic, model, min(16, os.cpu_count() or 1))
@@ -421,69 +433,74 @@ def main():
         # measured; the kernel timings of extras below then follow seconds of host work instead of the timed steps)
         dumped = dump_outputs(solver, args.dump_outputs)
 
-    share = 1.0 / world
-    # dominant kernel, HIP events on the library's own stream (local, no collective), right behind the timed steps: the
-    # device is at the clocks it held there
-    k_ms = solver.time_kernel(0, warmup=5, iters=max(5, args.steps))
-    renumbered = True if world > 1 else not np.array_equal(solver.node_numbering(), np.arange(N))
-    # ---- one untimed cross-check of the K the timed launches assemble: its product with a random vector against the
-    # product of the K a second, independent kernel assembles from the same state (staged visits / the generic
-    # row-owner kernel), K . translation = 0, and symmetry by <a, K b> = <b, K a>
-    verified = None
-    if world == 1:
+    measured = {}
+    if args.full:
+        share = 1.0 / world
+        # dominant kernel, HIP events on the library's own stream (local, no collective), right behind the timed steps: the
+        # device is at the clocks it held there
+        k_ms = solver.time_kernel(0, warmup=5, iters=max(5, args.steps))
+        # ---- one untimed cross-check of the K the timed launches assemble: its product with a random vector against the
+        # product of the K a second, independent kernel assembles from the same state (staged visits / the generic
+        # row-owner kernel), K . translation = 0, and symmetry by <a, K b> = <b, K a>
+        verified = None
+        if world == 1:
+            try:
+                rng = np.random.default_rng(66)
+                va, vb = rng.normal(size=3 * N), rng.normal(size=3 * N)
+                ya, yb = solver.spmv(va), solver.spmv(vb)
+                tr = np.zeros(3 * N); tr[1::3] = 1.0
+                ok = bool(np.abs(solver.spmv(tr)).max() < 1e-10 * np.abs(ya).max() and abs(vb @ ya - va @ yb) < 1e-10 * abs(vb @ ya))
+                other = feahip.ASM_ROWOWNER if (args.quadratic or args.hex) else feahip.ASM_STAGED
+                if in_use != other:
+                    solver.set_assembly(other)
+                    solver.create_stiffness_and_residual()
+                    ok = ok and bool(np.abs(solver.spmv(va) - ya).max() < 1e-11 * np.abs(ya).max())
+                    solver.set_assembly(getattr(feahip, "ASM_" + args.assembly.upper()))
+                    solver.create_stiffness_and_residual()
+                    solver.sync()
+                verified = ok
+            except Exception as e:                      # noqa: BLE001
+                verified = f"check failed to run: {e}"
+        copy_gbps = copy3 = None
         try:
-            rng = np.random.default_rng(66)
-            va, vb = rng.normal(size=3 * N), rng.normal(size=3 * N)
-            ya, yb = solver.spmv(va), solver.spmv(vb)
-            tr = np.zeros(3 * N); tr[1::3] = 1.0
-            ok = bool(np.abs(solver.spmv(tr)).max() < 1e-10 * np.abs(ya).max() and abs(vb @ ya - va @ yb) < 1e-10 * abs(vb @ ya))
-            other = feahip.ASM_ROWOWNER if (args.quadratic or args.hex) else feahip.ASM_STAGED
-            if in_use != other:
-                solver.set_assembly(other)
-                solver.create_stiffness_and_residual()
-                ok = ok and bool(np.abs(solver.spmv(va) - ya).max() < 1e-11 * np.abs(ya).max())
-                solver.set_assembly(getattr(feahip, "ASM_" + args.assembly.upper()))
-                solver.create_stiffness_and_residual()
-                solver.sync()
-            verified = ok
-        except Exception as e:                      # noqa: BLE001
-            verified = f"check failed to run: {e}"
-    copy_gbps = copy3 = None
-    try:
-        copy3 = solver.copy_bandwidth_detail(1 << 30)
-        copy_gbps = max(copy3)
-    except Exception as e:                          # noqa: BLE001
-        print(f"copy bandwidth not measured: {e}", file=sys.stderr)
-    B = algorithmic_bytes(sz["npe"], E_total, N, nnz) * share
-    achieved = B / (k_ms * 1e-3) / 1e9
-    spmv_ms = solver.time_kernel(3, warmup=2, iters=10)
+            copy3 = solver.copy_bandwidth_detail(1 << 30)
+            copy_gbps = max(copy3)
+        except Exception as e:                          # noqa: BLE001
+            print(f"copy bandwidth not measured: {e}", file=sys.stderr)
+        B = algorithmic_bytes(sz["npe"], E_total, N, nnz) * share
+        achieved = B / (k_ms * 1e-3) / 1e9
+        spmv_ms = solver.time_kernel(3, warmup=2, iters=10)
+        measured = {
+            "assembly_kernel_ms": k_ms,
+            "residual_only_ms": solver.time_kernel(2, warmup=2, iters=10),
+            "spmv_ms": spmv_ms,
+            "spmv_GBps": spmv_bytes(nnz, N) * share / (spmv_ms * 1e-3) / 1e9,
+            "verified": verified,
+            "copy_bandwidth_GBps": copy_gbps,
+            "copy_bandwidth_GBps_by_method": (dict(zip(("one_16B_load_per_lane", "four_16B_loads_in_flight", "hipMemcpyDtoDAsync", "four_16B_nontemporal"), copy3))
+                                              if copy3 else None),
+            "assembly_frac_of_copy_bandwidth": achieved / copy_gbps if copy_gbps else None,
+        }
+    renumbered = True if world > 1 else not np.array_equal(solver.node_numbering(), np.arange(N))
     extras = {
-        "assembly_kernel_ms": k_ms,
-        "residual_only_ms": solver.time_kernel(2, warmup=2, iters=10),
-        "spmv_ms": spmv_ms,
-        "spmv_GBps": spmv_bytes(nnz, N) * share / (spmv_ms * 1e-3) / 1e9,
         "setup_s": t_setup,
         "aux_map_bytes_per_element": sz["aux_bytes"] / E_total,
-        "rccl_sharded_solve": comm_ok if world > 1 else None,
+        "rccl_sharded_solve": comm_ok if world > 1 and args.full else None,
         "device_bytes_this_rank": int(dev_bytes),
         "node_numbering": ("caller: " + ("deck order (TetGen), copy by copy" if args.mesh == "tetgen" else "lexicographic (x fastest, z, y slowest)" if brick is None else "bricks of %dx%dx%d nodes" % brick) +
                            "; library: " + (("renumbered by recursive coordinate bisection (csrc/renumber.cpp)" if args.mesh == "tetgen" else
                                              "renumbered to compact cells (csrc/renumber.cpp)") if renumbered else "the caller's ids kept")),
-        "verified": verified,
         "gather_maps": solver.assembly_stats(),
-        "copy_bandwidth_GBps": copy_gbps,
-        "copy_bandwidth_GBps_by_method": (dict(zip(("one_16B_load_per_lane", "four_16B_loads_in_flight", "hipMemcpyDtoDAsync", "four_16B_nontemporal"), copy3))
-                                          if copy3 else None),
-        "assembly_frac_of_copy_bandwidth": achieved / copy_gbps if copy_gbps else None,
         "device_addresses_mod_2MiB": {k: v % (1 << 21) for k, v in solver.device_layout().items()},
         "rank0_holds": ({"nodes": solver.N, "owned_nodes": solver.n_own, "elements": solver.E, "rows_sent_per_exchange": solver.rows_sent}
                         if world > 1 else None),
     }
+    extras.update(measured)
 
     # ---- the reference's own element next to the headline: 10-node tetrahedra / 5 Gauss points on a small block
     # (24 x 144 x 24 cubes, 497 664 elements, a few ms), same deformed state, what AUTO runs
     tet10 = None
-    if world == 1 and not args.quadratic and not args.hex and not args.no_tet10:
+    if args.full and world == 1 and not args.quadratic and not args.hex and not args.no_tet10:
         try:
             d10 = mesh.bar_deck(n=24, quadratic=True, recipe="clamped", model=model)
             s10 = feahip.FeaSolver(d10, device=local)
@@ -506,7 +523,7 @@ def main():
     # ---- the extension element that rides the same templates: 8-node bricks / 8 Gauss points (40 x 240 x 40 bricks,
     # 384 000 elements), measured the same way
     hex8 = None
-    if world == 1 and not args.quadratic and not args.hex and not args.no_tet10:
+    if args.full and world == 1 and not args.quadratic and not args.hex and not args.no_tet10:
         try:
             d8 = mesh.bar_deck(n=40, hexa=True, recipe="clamped", model=model)
             s8 = feahip.FeaSolver(d8, device=local)
@@ -530,7 +547,7 @@ def main():
     # reference's TetGen deck brick_fine.sexp (22 934 TET10, deck order kept as sexp_loader.c:170-215 does), 48 copies
     # side by side = 1.1 M TET10 / 5 GP.  Which kernel AUTO takes, element evaluations per element, time, roofline fraction.
     off = None
-    if world == 1 and not args.quadratic and not args.hex and not args.no_off_lattice:
+    if args.full and world == 1 and not args.quadratic and not args.hex and not args.no_off_lattice:
         off = {}
 
         def leg(name, d, what):
@@ -579,7 +596,6 @@ def main():
                 "an unstructured linear-tet mesh for the headline kernel (library numbering: recursive coordinate bisection, csrc/renumber.cpp)")
         except Exception as e:                      # noqa: BLE001
             off["brick_fine_tiled"] = {"failed": str(e)}
-    traffic, traffic_src = pmc_traffic(args, world, kernel)
     if off is not None:
         extras["off_lattice"] = off
     if tet10 is not None:
@@ -601,11 +617,13 @@ def main():
                    "elements": E_total, "nodes": N, "scalar_nnz": nnz, "clock_ramp_launches_before_warmup": RAMP,
                    "sharding": f"{world} slab(s) across y; a rank holds only its slab (owned nodes, the elements around them, their halo, "
                                f"locally indexed); ghost elements recomputed, no collective in assembly"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": kernel, "algorithmic_bytes_per_launch": B},
         "extras": extras,
     }
+    if args.full:
+        traffic, traffic_src = pmc_traffic(args, world, kernel)
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "kernel": kernel, "algorithmic_bytes_per_launch": B}
 
     printed = threading.Event()
 
@@ -627,7 +645,7 @@ def main():
     watchdog.daemon = True
     watchdog.start()
     rc_exit = 0
-    if world > 1:
+    if args.full and world > 1:
         # RCCL communicator for the sharded linear solve (halo rows + scalar all-reduces).  RCCL refuses ranks that
         # share a device, so the gloo rehearsal (several ranks on one GPU) does not attempt it.
         why = None
@@ -650,7 +668,7 @@ def main():
             extras["solve_leg"] = next(f[1] for f in flags if not f[0])
             if backend == "nccl":
                 rc_exit = 4                         # the line is printed, but a dead solve path is a failed run
-    if world == 1 or comm_ok:
+    if args.full and (world == 1 or comm_ok):
         try:
             extras["pcg_iteration_ms"] = solver.time_kernel(4, warmup=2, iters=10)      # collective when sharded
             if not args.no_newton:
@@ -694,7 +712,7 @@ def main():
             rc_exit = 5
     if world == 1:
         watchdog.cancel()                           # (with several ranks it also covers the closing barrier below)
-    if rank == 0 and args.cpu_sample > 0 and world == 1:
+    if args.full and rank == 0 and args.cpu_sample > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.quadratic, model)
         if cpu_all is not None:
             cpu_all["unit"] = "elements/s"

@@ -24,7 +24,7 @@ for P in "${PASSES[@]}"; do
   [ $i -ge $NP ] && break
   if [ $((i+1)) -lt $FIRST ]; then i=$((i+1)); continue; fi
   i=$((i+1))
-  timeout -k 10 240 rocprofv3 --pmc $P --output-format csv -d "$OUT/pass$i" -- python3 "$ROOTDIR/bench.py" --no-newton --no-tet10 --no-off-lattice --cpu-sample 0 --steps 3 --warmup 1 "$@" > "$OUT/pass$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$OUT/pass$i.log"; exit 1; }
+  timeout -k 10 240 rocprofv3 --pmc $P --output-format csv -d "$OUT/pass$i" -- python3 "$ROOTDIR/bench.py" --full --no-newton --no-tet10 --no-off-lattice --cpu-sample 0 --steps 3 --warmup 1 "$@" > "$OUT/pass$i.log" 2>&1 || { echo "pass $i failed"; tail -5 "$OUT/pass$i.log"; exit 1; }
   echo "pass $i done"
 done
 python3 "$ROOTDIR/tools/pmc_summary.py" "$OUT" > "$OUT/summary.txt" 2>&1
