@@ -232,6 +232,11 @@ struct Gather10Layout {
   int o_nodes, o_elems, o_rows, o_tpos, o_flist, o_clist;
   int max_nodes, max_elems, max_cw, max_fdw, tile_blocks;      // max_cw: clist rows (256 words each) of the longest chunk
 };
+enum Gather10Limit {                 // why build_host_gather10 gave up (feahip_host_gather10_shape reports it)
+  G10_FITS = FEAHIP_G10_LIMIT_NONE, G10_ELEMS = FEAHIP_G10_LIMIT_ELEMS, G10_ROW_LENGTH = FEAHIP_G10_LIMIT_ROW_LENGTH,
+  G10_TASKS = FEAHIP_G10_LIMIT_TASKS, G10_RESIDUAL_LANES = FEAHIP_G10_LIMIT_RESIDUAL_LANES,
+  G10_LIST_LENGTH = FEAHIP_G10_LIMIT_LIST_LENGTH, G10_PASSES = FEAHIP_G10_LIMIT_PASSES, G10_OTHER = FEAHIP_G10_LIMIT_OTHER
+};
 struct HostGather10 {
   Gather10Layout lay;
   std::vector<unsigned char> blob;
@@ -241,6 +246,9 @@ struct HostGather10 {
   long long total_evals = 0, distinct_elems = 0;
   int nchunks = 0;
   bool ok = false;
+  int limit = G10_FITS;              // when !ok: the limit the maps ran into first
+  int limit_row = -1;                // ... at this row (the row that fits no chunk, or the first row of the chunk that failed)
+  int tile_blocks = 0;               // blocks of the K tile the chunks are cut for (set also when the maps fail)
 };
 void build_host_gather10(int N, int E, int npe, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather10 &out);
 int ensure_gather10(feahip_ctx *c);

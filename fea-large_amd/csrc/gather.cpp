@@ -685,6 +685,24 @@ extern "C" int feahip_host_gather_stats(int n_nodes, int n_elems, int npe, const
   return FEAHIP_OK;
 }
 
+// Host-only (no device): per chunk of the 4-node gather maps, in chunk order (include/fea_hip.h)
+extern "C" int feahip_host_gather_chunks(int n_nodes, int n_elems, const int *elements, int capacity, int *flags)
+{
+  if (!elements || n_nodes <= 0 || n_elems <= 0 || capacity < 0 || (capacity > 0 && !flags)) return FEAHIP_EINVAL;
+  HostPattern hp;
+  std::string err;
+  int rc = build_host_pattern(n_nodes, n_elems, 4, elements, hp, err);
+  if (rc) return rc;
+  HostGather hg;
+  build_host_gather(n_nodes, n_elems, elements, hp, 0, n_nodes, hg);
+  if (!hg.ok) return FEAHIP_EINVAL;
+  for (int p = 0; p < hg.nchunks && p < capacity; ++p) {
+    const GatherHeader &gh = *reinterpret_cast<const GatherHeader *>(hg.blob.data() + (size_t)p * hg.lay.stride);
+    flags[p] = (gh.flags & 1) | (gh.depth > FEA_G_REGW ? 2 : 0) | (gh.ddepth > FEA_G_REGW ? 4 : 0);
+  }
+  return hg.nchunks;
+}
+
 #ifdef FEAHIP_DEBUG
 // diagnostic build only, host only: one chunk's map record and the layout, for the LDS bank model (dbg/lds_model.py)
 extern "C" int feahip_debug_gather_record_host(int n_nodes, int n_elems, const int *elements, int chunk, int *layout_ints,

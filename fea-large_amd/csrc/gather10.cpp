@@ -29,7 +29,8 @@
 void build_host_gather10(int N, int E, int npe, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather10 &out)
 {
   (void)E; (void)N;
-  out.ok = false; out.nchunks = 0; out.blob.clear(); out.first_row.clear(); out.npe = npe;
+  out.ok = false; out.nchunks = 0; out.blob.clear(); out.first_row.clear(); out.npe = npe; out.tile_blocks = 0;
+  out.limit = G10_OTHER; out.limit_row = -1;
   if (npe < 2 || npe > 15) return;                     // 4-bit local node ids
   if (row_lo < 0 || row_hi > N || row_lo >= row_hi) return;
   // limits of one chunk: two workgroups' records (496 bytes per element) in one CU's LDS
@@ -38,6 +39,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
   if (const char *e = getenv("FEAHIP_GATHER10_ELEMS")) max_elems = std::max(4, std::min(FEA_Q_MAX_ELEMS, atoi(e)));
   if (const char *e = getenv("FEAHIP_GATHER10_ALPHA")) alpha = std::max(0, atoi(e));
   const int tile_blocks = (max_elems * (3 * npe + 1) * 16) / 72 - 1;   // the K tile takes the records' place
+  out.tile_blocks = tile_blocks;
   const int nrows_all = row_hi - row_lo;
 
   // ---- pass A: chunk boundaries by the shortest-path recurrence of gather.cpp (cost = element evaluations)
@@ -83,7 +85,14 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
         const long long v = best[j - l] + c + alpha;
         if (b < 0 || v < b) { b = v; bl = l; }
       }
-      if (b < 0) return;                           // a single row does not fit
+      if (b < 0) {                                 // a single row does not fit: the limit of pass A it exceeds first
+        const int r = row_lo + j - 1, ninc = hp.incptr[r + 1] - hp.incptr[r], rowlen = hp.rowptr[r + 1] - hp.rowptr[r];
+        out.limit_row = r;
+        out.limit = ninc > FEA_Q_MAX_ELEMS ? G10_ELEMS : rowlen > tile_blocks / 2 ? G10_ROW_LENGTH
+                  : rowlen - 1 > Q_MAX_TASKS ? G10_TASKS : (ninc + Q_FENT - 1) / Q_FENT > FEA_Q_FLANES ? G10_RESIDUAL_LANES
+                  : rowlen > (FEA_Q_MAX_PASS - 2) * tile_blocks ? G10_PASSES : G10_OTHER;
+        return;
+      }
       best[j] = b; from[j] = (unsigned char)bl;
     }
     std::vector<int> cuts;
@@ -124,7 +133,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
       std::sort(el.begin(), el.end());
       el.erase(std::unique(el.begin(), el.end()), el.end());
       const int nelem = (int)el.size();
-      if (nelem > FEA_Q_MAX_ELEMS || nrows > FEA_Q_MAX_ROWS || nb >= 0xFFFF) { bad[p] = 1; continue; }
+      if (nelem > FEA_Q_MAX_ELEMS || nrows > FEA_Q_MAX_ROWS || nb >= 0xFFFF) { bad[p] = nelem > FEA_Q_MAX_ELEMS ? G10_ELEMS : G10_OTHER; continue; }
       auto lelem = [&](int e) { return (int)(std::lower_bound(el.begin(), el.end(), e) - el.begin()); };
       tid_of.assign((size_t)nb, -1);
       tp.clear();
@@ -147,7 +156,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
       }
       Lc.rows[Q_RS + nrows] = (uint16_t)nb;
       const int ntask = (int)tp.size();
-      if (ntask > Q_MAX_TASKS) { bad[p] = 1; continue; }
+      if (ntask > Q_MAX_TASKS) { bad[p] = G10_TASKS; continue; }
       lists.assign((size_t)ntask, std::vector<uint16_t>());
       for (int a = r0; a < r1; ++a) {
         const int *cb = hp.colidx.data() + hp.rowptr[a], *ce = hp.colidx.data() + hp.rowptr[a + 1];
@@ -184,7 +193,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
         h.cnt[FEA_Q_WAVES * s + wv] = (unsigned char)std::max((int)h.cnt[FEA_Q_WAVES * s + wv], std::min(len, 250));
         h.sw[s] = (unsigned char)std::max((int)h.sw[s], (std::min(len, 250) + 1) / 2);
       }
-      if (too_long) { bad[p] = 1; continue; }
+      if (too_long) { bad[p] = G10_LIST_LENGTH; continue; }
       // write-out passes: whole rows, as many as fit the tile
       {
         int np = 0, a = 0;
@@ -200,7 +209,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
           h.prow[++np] = (unsigned char)b;
           a = b;
         }
-        if (np < 0) { bad[p] = 1; continue; }
+        if (np < 0) { bad[p] = G10_PASSES; continue; }
         h.npass = np;
       }
       // residual lanes: slices of 2*fdw visits of one row
@@ -211,7 +220,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
         if (need <= FEA_Q_FLANES) break;
         if (2 * fdw >= Q_FENT) { fdw = -1; break; }
       }
-      if (fdw < 0) { bad[p] = 1; continue; }
+      if (fdw < 0) { bad[p] = G10_RESIDUAL_LANES; continue; }
       int nft = 0;
       for (int a = r0; a < r1; ++a) {
         Lc.rows[Q_FF + (a - r0)] = (uint16_t)nft;
@@ -236,7 +245,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
     }
   });
   for (int p = 0; p < nch; ++p)
-    if (bad[p]) return;
+    if (bad[p]) { out.limit = bad[p]; out.limit_row = out.first_row[p]; return; }
 
   Gather10Layout &lay = out.lay;
   memset(&lay, 0, sizeof(lay));
@@ -257,7 +266,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
   lay.o_flist = lay.o_tpos + 4 * Q_MAX_TASKS;
   lay.o_clist = lay.o_flist + round_up(4 * lay.max_fdw * FEA_Q_FLANES, 64);
   lay.stride = round_up(lay.o_clist + 4 * lay.max_cw * FEA_Q_THREADS, 128);
-  if ((long long)nch * lay.stride > 0x7FFFFFFF00LL) return;
+  if ((long long)nch * lay.stride > 0x7FFFFFFF00LL) { out.limit = G10_OTHER; return; }
   out.blob.assign((size_t)nch * lay.stride, 0);
   parallel_ranges(nch, 256, [&](int lo, int hi) {
     for (int p = lo; p < hi; ++p) {
@@ -303,6 +312,7 @@ void build_host_gather10(int N, int E, int npe, const int *conn, const HostPatte
     out.distinct_elems = d;
   }
   out.ok = true;
+  out.limit = G10_FITS;
 }
 
 // what the maps say, row by row (gather.cpp: feahip_host_assembly_digest)
@@ -341,4 +351,53 @@ void gather10_row_digest(const HostGather10 &hg, const HostPattern &hp, const in
       row0 += h.sw[s];
     }
   }
+}
+
+// Host-only (no device): the edges the 10-node / 8-node maps of a mesh reach, over all chunks (include/fea_hip.h)
+extern "C" int feahip_host_gather10_shape(int n_nodes, int n_elems, int npe, const int *elements, long long *out)
+{
+  if (!elements || !out || n_nodes <= 0 || n_elems <= 0 || (npe != 10 && npe != 8)) return FEAHIP_EINVAL;
+  HostPattern hp;
+  std::string err;
+  int rc = build_host_pattern(n_nodes, n_elems, npe, elements, hp, err);
+  if (rc) return rc;
+  HostGather10 hg;
+  build_host_gather10(n_nodes, n_elems, npe, elements, hp, 0, n_nodes, hg);
+  for (int i = 0; i < FEAHIP_G10_SHAPE_LEN; ++i) out[i] = 0;
+  out[0] = hg.ok;
+  out[1] = hg.ok ? G10_FITS : hg.limit;
+  out[13] = -1;
+  out[14] = hg.ok ? -1 : hg.limit_row;
+  out[10] = hg.tile_blocks;
+  if (!hg.ok) return FEAHIP_OK;
+  const Gather10Layout &lay = hg.lay;
+  std::vector<int> nodes;
+  out[2] = hg.nchunks;
+  out[6] = FEA_Q_MAX_PASS + 1;
+  for (int p = 0; p < hg.nchunks; ++p) {
+    const unsigned char *rec = hg.blob.data() + (size_t)p * lay.stride;
+    const Gather10Header &h = *reinterpret_cast<const Gather10Header *>(rec);
+    const uint32_t *elems = reinterpret_cast<const uint32_t *>(rec + lay.o_elems);
+    nodes.clear();
+    for (int i = 0; i < h.nelem; ++i)
+      for (int k = 0; k < npe; ++k) nodes.push_back(elements[(size_t)hg.elist[elems[i]] * npe + k]);
+    std::sort(nodes.begin(), nodes.end());
+    const int nnode = (int)(std::unique(nodes.begin(), nodes.end()) - nodes.begin());
+    int longest = 0, words = 0;
+    for (int s = 0; s < FEA_Q_SLOTS; ++s) {
+      words = std::max(words, (int)h.sw[s]);
+      for (int w = 0; w < FEA_Q_WAVES; ++w) longest = std::max(longest, (int)h.cnt[FEA_Q_WAVES * s + w]);
+    }
+    out[3] = std::max(out[3], (long long)h.nelem);
+    out[4] = std::max(out[4], (long long)nnode);
+    out[5] = std::max(out[5], (long long)h.npass);
+    out[6] = std::min(out[6], (long long)h.npass);
+    out[7] = std::max(out[7], (long long)longest);
+    if (words > FEA_Q_REGW) { ++out[8]; if (out[13] < 0) out[13] = p; }
+    out[9] = std::max(out[9], (long long)h.fdw);
+    out[11] += h.nelem == FEA_Q_MAX_ELEMS;
+    out[15] = std::max(out[15], (long long)(h.r1 - h.r0));
+  }
+  out[12] = lay.max_elems;
+  return FEAHIP_OK;
 }

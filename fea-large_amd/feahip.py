@@ -76,6 +76,8 @@ ABI = {
     "feahip_time_kernel": [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp],
     "feahip_sizes": [C.c_void_p, C.POINTER(C.c_longlong)],
     "feahip_host_gather_stats": [C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong), _ip],
+    "feahip_host_gather10_shape": [C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong)],
+    "feahip_host_gather_chunks": [C.c_int, C.c_int, _ip, C.c_int, _ip],
     "feahip_host_assembly_digest": [C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), _ip],
     "feahip_assembly_in_use": [C.c_void_p, _ip],
     "feahip_node_numbering": [C.c_void_p, _ip],
@@ -663,6 +665,40 @@ def host_gather_stats(elements, n_nodes):
             "evals_per_element": float(st[1]) / float(st[2]), "rows_per_chunk": float(st[3]) / float(st[0]),
             "chunks_with_predecessors_words": int(st[4]), "map_bytes": int(st[5]),
             "chunks_with_long_block_lists": int(st[6]), "chunks_with_long_diagonal_lists": int(st[7])}, hist
+
+
+def host_gather_chunks(elements, n_nodes):
+    """Per chunk of the 4-node GATHER maps, in chunk order (host only): int array of flags -- bit 0 the next chunk
+    repeats this chunk's map words, bit 1 a block list, bit 2 a diagonal list longer than the registers hold."""
+    el = np.ascontiguousarray(elements, dtype=np.int32)
+    lib = load_library()
+    n = lib.feahip_host_gather_chunks(n_nodes, el.shape[0], _i(el), 0, None)
+    if n < 0:
+        raise FeaHipError(f"feahip_host_gather_chunks failed ({n})")
+    flags = np.zeros(n, dtype=np.int32)
+    if lib.feahip_host_gather_chunks(n_nodes, el.shape[0], _i(el), n, _i(flags)) != n:
+        raise FeaHipError("feahip_host_gather_chunks: chunk count changed")
+    return flags
+
+
+G10_LIMITS = {0: None, 1: "elements", 2: "row length", 3: "tasks", 4: "residual lanes", 5: "list length", 6: "passes",
+              7: "other"}
+
+
+def host_gather10_shape(elements, n_nodes):
+    """The edges the 10-node / 8-node GATHER maps of a mesh reach, in the numbering given (host only; pass library ids,
+    host_numbering, to see what a context builds).  FEAHIP_GATHER10_ROWS / _ELEMS / _ALPHA apply as they do there."""
+    el = np.ascontiguousarray(elements, dtype=np.int32)
+    o = np.zeros(16, dtype=np.int64)
+    rc = load_library().feahip_host_gather10_shape(n_nodes, el.shape[0], el.shape[1], _i(el), o.ctypes.data_as(C.POINTER(C.c_longlong)))
+    if rc:
+        raise FeaHipError(f"feahip_host_gather10_shape failed ({rc})")
+    ok = bool(o[0])
+    return {"ok": ok, "limit": G10_LIMITS[int(o[1])], "chunks": int(o[2]), "max_elems": int(o[3]), "max_nodes": int(o[4]),
+            "max_passes": int(o[5]), "min_passes": int(o[6]) if ok else 0, "longest_list": int(o[7]),
+            "chunks_with_long_lists": int(o[8]), "max_fdw": int(o[9]), "tile_blocks": int(o[10]),
+            "chunks_at_elem_limit": int(o[11]), "zero_slot": int(o[12]), "first_long_list_chunk": int(o[13]),
+            "limit_row": int(o[14]), "max_rows": int(o[15])}
 
 
 def host_assembly_digest(elements, n_nodes, rank=0, nranks=1):

@@ -303,6 +303,40 @@ int feahip_host_assembly_digest(int n_nodes, int n_elems, int npe, const int *el
 int feahip_host_gather_stats(int n_nodes, int n_elems, int npe, const int *elements,
                              long long *stats, int *rows_hist);
 
+/* Host-only (no device): the chunks of the 4-node GATHER maps of a mesh of
+ * linear tetrahedra, in chunk order, in the numbering given (as
+ * feahip_host_gather_stats).  flags[capacity] (may be null when capacity is
+ * 0): bit 0 the next chunk's map words equal this chunk's (the kernel keeps
+ * them in registers), bit 1 a block list, bit 2 a diagonal list longer than
+ * a thread keeps in registers.  Returns the number of chunks, or negative.   */
+int feahip_host_gather_chunks(int n_nodes, int n_elems, const int *elements, int capacity, int *flags);
+
+/* Host-only (no device): the edges the GATHER maps of 10-node tetrahedra or
+ * 8-node bricks reach, for a mesh in the numbering it is given (library ids:
+ * what a context builds), under the FEAHIP_GATHER10_ROWS / _ELEMS / _ALPHA
+ * settings of the environment.  out[FEAHIP_G10_SHAPE_LEN] =
+ *   0 the maps built          1 when not, the limit they ran into first:
+ *                               FEAHIP_G10_LIMIT_* below
+ *   2 chunks                  3 largest elements of a chunk (record slots)
+ *   4 largest nodes those elements touch
+ *   5 largest write-out passes  6 smallest write-out passes
+ *   7 longest contribution list of a block (entries, 2 per word)
+ *   8 chunks with a block list longer than the words a thread keeps in
+ *     registers              9 largest words per residual lane (fdw)
+ *  10 blocks of the K tile   11 chunks with the most elements a record holds
+ *  12 slot of the all-zero element record
+ *  13 first chunk counted in 8 (-1: none)
+ *  14 when the maps do not build, the row they fail at (-1 otherwise)
+ *  15 largest rows of a chunk.
+ * Returns FEAHIP_OK also when the maps do not build (out[0] = 0).           */
+#define FEAHIP_G10_SHAPE_LEN 16
+enum {
+  FEAHIP_G10_LIMIT_NONE = 0, FEAHIP_G10_LIMIT_ELEMS = 1, FEAHIP_G10_LIMIT_ROW_LENGTH = 2,
+  FEAHIP_G10_LIMIT_TASKS = 3, FEAHIP_G10_LIMIT_RESIDUAL_LANES = 4, FEAHIP_G10_LIMIT_LIST_LENGTH = 5,
+  FEAHIP_G10_LIMIT_PASSES = 6, FEAHIP_G10_LIMIT_OTHER = 7
+};
+int feahip_host_gather10_shape(int n_nodes, int n_elems, int npe, const int *elements, long long *out);
+
 /* ---- node numbering ---------------------------------------------------- */
 /* The reference keeps the nodes in deck order (sexp_loader.c:170-215) and its
  * dof index is node * 3 + axis (fea_solver.c:377-384).  The kernels here own
