@@ -79,6 +79,15 @@ struct HostPattern {
 };
 int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
                        std::string &err, int row_break = -1);
+// an incidence word of inc / inc_rows: element | local node << 28
+inline int inc_elem(uint32_t w) { return (int)(w & 0x0FFFFFFFu); }
+inline int inc_node(uint32_t w) { return (int)(w >> 28); }
+// CSR position of the block (a, b)
+inline int csr_pos(const HostPattern &hp, int a, int b)
+{
+  const int *cb = hp.colidx.data() + hp.rowptr[a], *ce = hp.colidx.data() + hp.rowptr[a + 1];
+  return hp.rowptr[a] + (int)(std::lower_bound(cb, ce, b) - cb);
+}
 
 // visits.cpp
 // LDS-staged visit assembly (kernels_visit.hip): per chunk, the nodes its
@@ -127,6 +136,70 @@ struct HostQuad {
 void build_host_quad(int N, int E, int npe, const int *conn, const HostPattern &hp, int p_lo, int p_hi, HostQuad &out);
 int ensure_quad(feahip_ctx *c);
 int launch_assemble_quad(feahip_ctx *c, bool doF);
+
+// ---- stages shared by the builders of the chunked maps (gather.cpp).  A chunk is a run of consecutive block rows
+// [r0, r1); the builders pass their scratch vectors in, so that a parallel_ranges worker reuses them chunk after chunk.
+// true when the element of incidence word w, visited at row r, has no other node among the rows [r0, r): it is new
+// to the rows [r0, r]
+inline bool first_visit(const HostPattern &hp, const int *conn, int npe, uint32_t w, int r0, int r)
+{
+  const int e = inc_elem(w), la = inc_node(w);
+  for (int k = 0; k < npe; ++k) {
+    const int g = conn[(size_t)e * npe + k];
+    if (k != la && g >= r0 && g < r) return false;
+  }
+  return true;
+}
+// Pass A, the cost row of the chunks that start at row r0: cost[l-1] = distinct elements touching the rows
+// [r0, r0 + l), for l = 1, 2, ... while fits(r, l, nel, ntask, fresh) says the chunk ending at row r = r0 + l - 1
+// still fits (every longer one fails too; cost[] stays 0xFFFF there).  nel: its elements; ntask: its off-diagonal
+// blocks with a thread of their own (a block whose column is a lower row of the chunk is its mirror's transpose);
+// fresh: the elements row r adds.
+template <class Fits>
+void chunk_costs(const HostPattern &hp, const int *conn, int npe, int r0, int row_hi, int L, std::vector<int> &fresh,
+                 uint16_t *cost, Fits fits)
+{
+  int nel = 0, ntask = 0;
+  for (int l = 1; l <= L && r0 + l <= row_hi; ++l) {
+    const int r = r0 + l - 1;
+    fresh.clear();
+    for (int q = hp.incptr[r]; q < hp.incptr[r + 1]; ++q)
+      if (first_visit(hp, conn, npe, hp.inc_rows[q], r0, r)) fresh.push_back(inc_elem(hp.inc_rows[q]));
+    nel += (int)fresh.size();
+    const int *cb = hp.colidx.data() + hp.rowptr[r], *ce = hp.colidx.data() + hp.rowptr[r + 1];
+    ntask += (int)(ce - cb) - 1 - (int)(std::lower_bound(cb, ce, r) - std::lower_bound(cb, ce, r0));
+    if (!fits(r, l, nel, ntask, fresh)) break;
+    cost[l - 1] = (uint16_t)nel;
+  }
+}
+// Pass A, the chunk boundaries.  Every element evaluation a chunk makes is work, so the partition that minimises
+// their total (plus a per-chunk overhead alpha) is found by a shortest-path recurrence over the rows; it finds the
+// natural clusters of whatever numbering the mesh came with (bricks, lines) instead of cutting through them.
+// cost[i * L + l - 1]: the chunk_costs of row row_lo + i.  Returns -1 and the first row of every chunk and row_hi
+// in first_row, or the first row that fits no chunk (first_row is left as it was).
+int partition_rows(const std::vector<uint16_t> &cost, int row_lo, int row_hi, int L, int alpha, std::vector<int> &first_row);
+// the distinct elements touching the rows [r0, r1), ascending
+void chunk_elements(const HostPattern &hp, int r0, int r1, std::vector<int> &el);
+// the off-diagonal blocks of the rows [r0, r1) that get a thread, in CSR order (see chunk_costs): tpos[t] = tile
+// position of the block of task t | tile position of its mirror (b, a) << 16 when b is a row of the chunk too,
+// 0xFFFF << 16 otherwise; task_of[pos] = the task of the block at tile position pos, -1 for none
+void chunk_block_tasks(const HostPattern &hp, int r0, int r1, std::vector<uint32_t> &tpos, std::vector<int> &task_of);
+// per task the contributions (element, local row node la, local column node lb) to its block, row by row in
+// incidence order: word = index of the element in el | la << la_shift | lb << lb_shift
+void chunk_block_lists(const HostPattern &hp, const int *conn, int npe, int r0, int r1, const std::vector<int> &el,
+                       const std::vector<int> &task_of, int ntask, int la_shift, int lb_shift,
+                       std::vector<std::vector<uint16_t>> &lists);
+// distinct elements touching the rows [r0, r1)
+long long count_distinct_elems(const HostPattern &hp, const int *conn, int npe, int r0, int r1);
+// what the gather maps of both families have in common
+struct HostChunkMaps {
+  std::vector<unsigned char> blob;   // nchunks records of lay.stride bytes
+  std::vector<int> first_row;        // [nchunks+1]
+  long long total_evals = 0, distinct_elems = 0;   // element evaluations of all chunks; elements touching the rows
+  int nchunks = 0;
+  bool ok = false;
+};
+
 // GATHER assembly (kernels_gather.hip, gather.cpp): a 256-thread workgroup owns a run of consecutive block rows.
 // Per chunk the host prepares one fixed-stride record: header, the chunk's nodes (owned rows first), its distinct
 // elements as 4 chunk-local node ids, and per off-diagonal block the list of (element, local row node, local
@@ -183,14 +256,9 @@ struct GatherLayout {                // the same for every chunk of a context
   int max_nodes, max_elems, max_tile;                        // LDS tiles: coordinates, element records, K blocks
   int max_tasks, max_depth, max_vthr, max_vdepth, max_ddepth;   // largest chunk: block threads, contribution words, residual threads, visits, diagonal words
 };
-struct HostGather {
+struct HostGather : HostChunkMaps {
   GatherLayout lay;
-  std::vector<unsigned char> blob;   // nchunks records of lay.stride bytes
-  std::vector<int> first_row;        // [nchunks+1]
-  long long total_evals = 0, distinct_elems = 0;   // element evaluations of all chunks; elements touching the rows
-  int nchunks = 0;
   int same_as_previous = 0;          // chunks whose map words equal their predecessor's (GatherHeader::flags)
-  bool ok = false;
 };
 // rows [row_lo, row_hi) only: a rank builds the maps of the rows it owns
 void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out);
@@ -237,15 +305,10 @@ enum Gather10Limit {                 // why build_host_gather10 gave up (feahip_
   G10_TASKS = FEAHIP_G10_LIMIT_TASKS, G10_RESIDUAL_LANES = FEAHIP_G10_LIMIT_RESIDUAL_LANES,
   G10_LIST_LENGTH = FEAHIP_G10_LIMIT_LIST_LENGTH, G10_PASSES = FEAHIP_G10_LIMIT_PASSES, G10_OTHER = FEAHIP_G10_LIMIT_OTHER
 };
-struct HostGather10 {
+struct HostGather10 : HostChunkMaps {
   Gather10Layout lay;
-  std::vector<unsigned char> blob;
-  std::vector<int> first_row;
   std::vector<int> elist;            // the rank's elements (touching its rows), ascending: order of the state records
   int npe = 10;
-  long long total_evals = 0, distinct_elems = 0;
-  int nchunks = 0;
-  bool ok = false;
   int limit = G10_FITS;              // when !ok: the limit the maps ran into first
   int limit_row = -1;                // ... at this row (the row that fits no chunk, or the first row of the chunk that failed)
   int tile_blocks = 0;               // blocks of the K tile the chunks are cut for (set also when the maps fail)

@@ -41,7 +41,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
   auto row_nodes = [&](int a, std::vector<int> &tmp) {
     tmp.clear();
     for (int p = hp.incptr[a]; p < hp.incptr[a + 1]; ++p) {
-      int e = (int)(hp.inc[p] & 0x0FFFFFFFu);
+      int e = inc_elem(hp.inc[p]);
       for (int k = 0; k < npe; ++k) tmp.push_back(conn[(size_t)e * npe + k]);
     }
     if (tmp.empty()) tmp.push_back(a);   // isolated node keeps its diagonal
@@ -104,11 +104,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
   // position of the diagonal block of every row
   hp.diag.resize((size_t)N);
   parallel_ranges(N, 65536, [&](int lo, int hi) {
-    for (int a = lo; a < hi; ++a) {
-      const int *cb = hp.colidx.data() + hp.rowptr[a];
-      const int *ce = hp.colidx.data() + hp.rowptr[a + 1];
-      hp.diag[a] = hp.rowptr[a] + (int)(std::lower_bound(cb, ce, a) - cb);
-    }
+    for (int a = lo; a < hi; ++a) hp.diag[a] = csr_pos(hp, a, a);
   });
 
   // Assembly partition of the staged kernel: finer chunks (visits, nodes and
@@ -133,7 +129,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
           int add = 0;
           std::vector<int> fresh;
           for (int q = hp.incptr[r]; q < hp.incptr[r + 1]; ++q) {
-            const int e = (int)(hp.inc_rows[q] & 0x0FFFFFFFu);
+            const int e = inc_elem(hp.inc_rows[q]);
             for (int k = 0; k < 4; ++k) {
               const int g = conn[(size_t)e * 4 + k];
               if (stamp[g] != serial) { stamp[g] = serial; fresh.push_back(g); ++add; }
@@ -171,7 +167,7 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
           const int len = hp.rowptr[r + 1] - hp.rowptr[r], vis = hp.incptr[r + 1] - hp.incptr[r];
           std::vector<int> fresh, nfresh;
           for (int q = hp.incptr[r]; q < hp.incptr[r + 1]; ++q) {
-            const int e = (int)(hp.inc_rows[q] & 0x0FFFFFFFu);
+            const int e = inc_elem(hp.inc_rows[q]);
             if (stamp[e] != serial) {
               stamp[e] = serial; fresh.push_back(e);
               for (int k = 0; k < npe; ++k) {
@@ -228,15 +224,13 @@ int build_host_pattern(int N, int E, int npe, const int *conn, HostPattern &hp,
     hp.incslot.resize((size_t)E * npe * npe);
     parallel_ranges((int)((long long)E * npe > 0x7FFFFFFF ? 0x7FFFFFFF : (long long)E * npe), 65536, [&](int lo, int hi) {
       for (int p = lo; p < hi; ++p) {
-        const int e = (int)(hp.inc[p] & 0x0FFFFFFFu), la = (int)(hp.inc[p] >> 28);
+        const int e = inc_elem(hp.inc[p]), la = inc_node(hp.inc[p]);
         const int a = conn[(size_t)e * npe + la];
-        const int *cb = hp.colidx.data() + hp.rowptr[a];
-        const int *ce = hp.colidx.data() + hp.rowptr[a + 1];
         for (int k = 0; k < npe; ++k) {
           // 4-node elements are visited with local node k XOR la in position k
           // (row node first, kernels_assemble.hip); slots are stored in that order
           int b = conn[(size_t)e * npe + (npe == 4 ? (k ^ la) : k)];
-          hp.incslot[(size_t)p * npe + k] = (uint8_t)(std::lower_bound(cb, ce, b) - cb);
+          hp.incslot[(size_t)p * npe + k] = (uint8_t)(csr_pos(hp, a, b) - hp.rowptr[a]);
         }
       }
     });
