@@ -331,6 +331,69 @@ extern "C" int feahip_create_rank(feahip_ctx **out, int device, int rank, int nr
   return FEAHIP_OK;
 }
 
+// The same context from the caller's own slab: local nodes, local elements, halo owners -- no whole mesh anywhere.  The
+// local order is the caller's (feahip_host_slab_order offers one that suits the kernels).
+extern "C" int feahip_create_rank_local(feahip_ctx **out, int device, int rank, int nranks, int n_global_nodes, int n_local,
+                                        int n_own, int n_elems, int npe, int gauss_count, const double *gauss_weights,
+                                        const double *dforms, const int *elements, const double *nodes0,
+                                        const int *node_global, const int *elem_global, const int *halo_owner, int model,
+                                        const double *model_params, int params_count, int n_presc, const int *presc_node,
+                                        const int *presc_type, const double *presc_values)
+{
+  if (!out) { g_create_error = "null output pointer"; return FEAHIP_EINVAL; }
+  *out = nullptr;
+  if (n_local <= 0 || n_elems <= 0 || !elements || !nodes0 || !node_global || (npe != 4 && npe != 8 && npe != 10) ||
+      n_presc < 0 || (n_presc > 0 && (!presc_node || !presc_type || !presc_values))) {
+    g_create_error = "feahip_create_rank_local: null or empty input"; return FEAHIP_EINVAL;
+  }
+  RankMesh rm;
+  int rc = build_rank_mesh_local(rank, nranks, n_global_nodes, n_local, n_own, n_elems, npe, elements, nodes0, node_global,
+                                 elem_global, halo_owner, n_presc, presc_node, presc_type, presc_values, rm, g_create_error);
+  if (rc) return rc;
+  feahip_ctx *c = new (std::nothrow) feahip_ctx();
+  if (!c) { g_create_error = "out of host memory"; return FEAHIP_ENOMEM; }
+  c->rank_own = rm.n_own; c->rank_local_ids = true;
+  rc = create_impl(c, device, n_local, n_elems, npe, gauss_count, gauss_weights, dforms, rm.elements.data(), rm.nodes0.data(),
+                   model, model_params, params_count, (int)rm.presc_node.size(), rm.presc_node.data(), rm.presc_type.data(),
+                   rm.presc_values.data());
+  if (rc == FEAHIP_OK) rc = install_plan(c, rm.plan);
+  if (rc != FEAHIP_OK) { g_create_error = c->err; feahip_destroy(c); return rc; }
+  c->rank_node_global.swap(rm.node_global); c->rank_elem_global.swap(rm.elem_global); c->rank_n_global = n_global_nodes;
+  *out = c;
+  return FEAHIP_OK;
+}
+
+// Host-only: the plan that call installs, in GLOBAL node ids (counts[3] by a first call with null lists).
+extern "C" int feahip_host_rank_local_plan(int rank, int nranks, int n_local, int n_own, int n_elems, int npe,
+                                           const int *elements, const int *node_global, const int *halo_owner, int *counts,
+                                           int *peers, int *send_off, int *recv_off, int *send_idx, int *recv_idx)
+{
+  if (!counts) return FEAHIP_EINVAL;
+  RankMesh rm;
+  int rc = build_rank_mesh_local(rank, nranks, -1, n_local, n_own, n_elems, npe, elements, nullptr, node_global, nullptr,
+                                 halo_owner, 0, nullptr, nullptr, nullptr, rm, g_create_error);
+  if (rc) return rc;
+  const ShardPlan &pl = rm.plan;
+  counts[0] = (int)pl.peer.size(); counts[1] = (int)pl.send_idx.size(); counts[2] = (int)pl.recv_idx.size();
+  if (peers) std::copy(pl.peer.begin(), pl.peer.end(), peers);
+  if (send_off) std::copy(pl.send_off.begin(), pl.send_off.end(), send_off);
+  if (recv_off) std::copy(pl.recv_off.begin(), pl.recv_off.end(), recv_off);
+  if (send_idx) for (size_t i = 0; i < pl.send_idx.size(); ++i) send_idx[i] = rm.node_global[pl.send_idx[i]];
+  if (recv_idx) for (size_t i = 0; i < pl.recv_idx.size(); ++i) recv_idx[i] = rm.node_global[pl.recv_idx[i]];
+  return FEAHIP_OK;
+}
+
+// Host-only: a local order for a slab (rankmesh.cpp slab_order); 1 when it reorders, 0 when the order given is kept.
+extern "C" int feahip_host_slab_order(int n_local, int n_own, int n_elems, int npe, const int *elements, const double *nodes0,
+                                      int *new_local_id)
+{
+  if (!elements || !nodes0 || !new_local_id || n_local <= 0 || n_elems <= 0 || n_own < 1 || n_own > n_local ||
+      (npe != 4 && npe != 8 && npe != 10)) return FEAHIP_EINVAL;
+  for (long long i = 0; i < (long long)n_elems * npe; ++i)
+    if (elements[i] < 0 || elements[i] >= n_local) return FEAHIP_EINVAL;
+  return slab_order(n_local, n_own, n_elems, npe, elements, nodes0, new_local_id);
+}
+
 extern "C" int feahip_rank_counts(feahip_ctx *c, long long *o)
 {
   if (!c || !o || c->rank_own < 0) return FEAHIP_EINVAL;

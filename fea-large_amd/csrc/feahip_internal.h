@@ -484,6 +484,7 @@ struct feahip_ctx {
   int rank_own = -1;                   // nodes it owns (local ids [0, rank_own)); -1: an ordinary context
   std::vector<int> rank_node_global, rank_elem_global;
   int rank_n_global = 0;
+  bool rank_local_ids = false;         // feahip_create_rank_local: the caller speaks local ids (surface faces included)
 
   // preconditioner of PCG_ILU / CHOLESKY solves: 0 = 3x3 block-Jacobi, 1 = aggregation multigrid (amg.h)
   // which matrix d_K holds: bumped by every stiffness assembly, copied by stash / restore; k_bc = prescribed-dof
@@ -567,6 +568,18 @@ void rank_row_range(int N, int npe, int rank, int nranks, int &g0, int &g1);
 int build_rank_mesh(int rank, int nranks, int N, int E, int npe, const int *elements, const double *nodes0,
                     int n_presc, const int *presc_node, const int *presc_type, const double *presc_values,
                     RankMesh &out, std::string &err);
+// the part behind "local nodes known", shared by both constructors: the halo plan from the rank's OWN elements
+// (out.elements, out.n_own filled) and the owner of every halo node.  key (may be null) = the order the rows to and from
+// a peer travel in: ascending key[local id]; null = ascending local id.
+void finish_rank_mesh(int rank, int nranks, int npe, const int *halo_owner, const int *key, RankMesh &out);
+// a rank's sub-mesh from the caller's own slab (feahip_create_rank_local): validated, copied, the plan in ascending
+// GLOBAL node id per peer.  nodes0 may be null (plan only); n_global < 0 skips the range check of node_global.
+int build_rank_mesh_local(int rank, int nranks, int n_global, int n_local, int n_own, int E, int npe, const int *elements,
+                          const double *nodes0, const int *node_global, const int *elem_global, const int *halo_owner,
+                          int n_presc, const int *presc_node, const int *presc_type, const double *presc_values,
+                          RankMesh &out, std::string &err);
+// the library's numbering of the LOCAL mesh, split stably into owned first, halo after; true when it reorders
+int slab_order(int n_local, int n_own, int E, int npe, const int *elements, const double *nodes0, int *new_local_id);
 int install_plan(feahip_ctx *c, const ShardPlan &plan);      // dist.hip: halo lists to the device, interior chunk range
 
 // multi-rank operations (kernels_solve.hip).  R = the ranks driven by this

@@ -298,6 +298,7 @@ int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes,
       c->err = "surface face " + std::to_string(f) + ": unknown load kind " + std::to_string(kind[f]); return FEAHIP_EINVAL;
     }
   // the faces in this context's node ids: library ids; on a rank context, the faces touching an owned node, in local ids
+  // (a feahip_create_rank_local context is handed local ids: nothing to look up, nothing sized by the whole mesh)
   std::vector<int> fn, fk, keep;
   std::vector<double> fv;
   if (nfaces > 0 && npf != nodes_per_face(c->npe)) {
@@ -305,9 +306,10 @@ int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes,
              "-node element has " + std::to_string(nodes_per_face(c->npe)) + " nodes, not " + std::to_string(npf);
     return FEAHIP_EINVAL;
   }
-  const int nglobal = c->rank_own >= 0 ? c->rank_n_global : c->N;
+  const bool global_faces = c->rank_own >= 0 && !c->rank_local_ids;
+  const int nglobal = global_faces ? c->rank_n_global : c->N;
   std::vector<int> local;
-  if (c->rank_own >= 0) {
+  if (global_faces) {
     local.assign((size_t)nglobal, -1);
     for (int a = 0; a < c->N; ++a) local[c->rank_node_global[a]] = a;
   }
@@ -318,7 +320,7 @@ int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes,
     for (int k = 0; k < npf; ++k) {
       if (ids[k] < 0 || ids[k] >= nglobal) { c->err = face_text(f, ids, npf) + ": node id outside [0, " + std::to_string(nglobal) + ")"; return FEAHIP_EINVAL; }
       if (c->rank_own >= 0) {
-        mapped[k] = local[ids[k]];
+        mapped[k] = global_faces ? local[ids[k]] : ids[k];
         present = present && mapped[k] >= 0;
         owned = owned || (mapped[k] >= 0 && mapped[k] < c->rank_own);
       } else mapped[k] = c->perm.empty() ? ids[k] : c->perm[ids[k]];

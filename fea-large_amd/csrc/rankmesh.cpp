@@ -12,6 +12,7 @@
 #include "feahip_internal.h"
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 // library ids [g0, g1) of rank `rank`: equal node counts, rounded to a multiple of the numbering's FULL cell (renumber.cpp:
 // 4 x 4 x 4 nodes, 48 half-grid nodes for 10-node elements).  The nodes of a cell are consecutive ids, so while the cells
@@ -90,19 +91,29 @@ int build_rank_mesh(int rank, int nranks, int N, int E, int npe, const int *elem
     out.presc_node.push_back(l); out.presc_type.push_back(presc_type[i]);
     for (int j = 0; j < 3; ++j) out.presc_values.push_back(presc_values[(size_t)i * 3 + j]);
   }
-  // halo plan in local ids.  recv: my halo nodes by owner (ascending library id inside a peer); send: my owned nodes that
-  // share an element with a node of that peer (the peer's halo nodes I own: the same set, seen from its elements)
+  std::vector<int> halo_owner((size_t)(nl - out.n_own));
+  for (int i = out.n_own; i < nl; ++i) halo_owner[(size_t)(i - out.n_own)] = owner_of(out.node_lib[i]);
+  finish_rank_mesh(rank, nranks, npe, halo_owner.data(), nullptr, out);   // rows travel in ascending library id (= local id)
+  return FEAHIP_OK;
+}
+
+// halo plan in local ids.  recv: my halo nodes by owner; send: my owned nodes that share an element with a node of
+// that peer (the peer's halo nodes I own: the same set, seen from its elements).  Inside a peer's segment the rows
+// ascend in key (the id both ends share); null: in local id, which feahip_create_rank's local order makes the library id.
+void finish_rank_mesh(int rank, int nranks, int npe, const int *halo_owner, const int *key, RankMesh &out)
+{
+  out.rank = rank; out.nranks = nranks; out.npe = npe;
+  const int nl = (int)out.node_global.size();
   std::vector<std::vector<int>> send((size_t)nranks), recv((size_t)nranks);
-  for (int i = out.n_own; i < nl; ++i) recv[(size_t)owner_of(out.node_lib[i])].push_back(i);
+  for (int i = out.n_own; i < nl; ++i) recv[(size_t)halo_owner[i - out.n_own]].push_back(i);
   {
-    std::vector<std::vector<int>> tmp((size_t)nranks);
-    const size_t ne = out.elem_global.size();
+    const size_t ne = out.elements.size() / (size_t)npe;
     for (size_t e = 0; e < ne; ++e) {
       const int *c = out.elements.data() + e * npe;
       int owners[16]; int no = 0;
       for (int k = 0; k < npe; ++k)
         if (c[k] >= out.n_own) {
-          const int r = owner_of(out.node_lib[c[k]]);
+          const int r = halo_owner[c[k] - out.n_own];
           bool seen = false;
           for (int q = 0; q < no; ++q) seen = seen || owners[q] == r;
           if (!seen && no < 16) owners[no++] = r;
@@ -110,12 +121,16 @@ int build_rank_mesh(int rank, int nranks, int N, int E, int npe, const int *elem
       if (!no) continue;
       for (int k = 0; k < npe; ++k)
         if (c[k] < out.n_own)
-          for (int q = 0; q < no; ++q) tmp[(size_t)owners[q]].push_back(c[k]);
+          for (int q = 0; q < no; ++q) send[(size_t)owners[q]].push_back(c[k]);
     }
     for (int r = 0; r < nranks; ++r) {
-      std::sort(tmp[r].begin(), tmp[r].end());
-      tmp[r].erase(std::unique(tmp[r].begin(), tmp[r].end()), tmp[r].end());
-      send[r] = tmp[r];                                         // local owned ids ascend with their library ids
+      std::sort(send[r].begin(), send[r].end());
+      send[r].erase(std::unique(send[r].begin(), send[r].end()), send[r].end());
+      if (key) {
+        auto by_key = [key](int a, int b) { return key[a] < key[b]; };
+        std::sort(send[r].begin(), send[r].end(), by_key);
+        std::sort(recv[r].begin(), recv[r].end(), by_key);
+      }
     }
   }
   ShardPlan &pl = out.plan;
@@ -129,5 +144,90 @@ int build_rank_mesh(int rank, int nranks, int N, int E, int npe, const int *elem
     pl.recv_idx.insert(pl.recv_idx.end(), recv[r].begin(), recv[r].end());
     pl.send_off.push_back((int)pl.send_idx.size()); pl.recv_off.push_back((int)pl.recv_idx.size());
   }
+}
+
+// One rank's sub-mesh as the caller cut it: local nodes [0, n_own) owned, the rest halo with their owners named.  Nothing
+// here is sized by the whole mesh: node_global is checked for repeats on a sorted copy, not through a table of n_global.
+int build_rank_mesh_local(int rank, int nranks, int n_global, int n_local, int n_own, int E, int npe, const int *elements,
+                          const double *nodes0, const int *node_global, const int *elem_global, const int *halo_owner,
+                          int n_presc, const int *presc_node, const int *presc_type, const double *presc_values,
+                          RankMesh &out, std::string &err)
+{
+  auto S = [](long long v) { return std::to_string(v); };
+  if (nranks < 1 || rank < 0 || rank >= nranks) { err = "bad (rank, nranks)"; return FEAHIP_EINVAL; }
+  if (npe != 4 && npe != 8 && npe != 10) { err = "nodes per element must be 4, 8 or 10"; return FEAHIP_EINVAL; }
+  if (n_local <= 0 || E <= 0 || !elements || !node_global) { err = "null or empty slab"; return FEAHIP_EINVAL; }
+  if (n_own < 1 || n_own > n_local) { err = "n_own = " + S(n_own) + " outside [1, n_local = " + S(n_local) + "]"; return FEAHIP_EINVAL; }
+  if (n_own < n_local && !halo_owner) { err = "halo nodes without halo_owner"; return FEAHIP_EINVAL; }
+  std::vector<char> touched((size_t)n_local, 0);
+  for (int e = 0; e < E; ++e) {
+    bool mine = false;
+    for (int k = 0; k < npe; ++k) {
+      const int a = elements[(size_t)e * npe + k];
+      if (a < 0 || a >= n_local) {
+        err = "element " + S(e) + " refers to local node " + S(a) + " outside [0," + S(n_local) + ")"; return FEAHIP_EINVAL;
+      }
+      touched[(size_t)a] = 1; mine = mine || a < n_own;
+    }
+    if (!mine) { err = "element " + S(e) + " has no owned node: it contributes to no row of this rank"; return FEAHIP_EINVAL; }
+  }
+  for (int i = n_own; i < n_local; ++i) {
+    if (!touched[(size_t)i]) { err = "halo node " + S(i) + " is touched by no element"; return FEAHIP_EINVAL; }
+    const int o = halo_owner[i - n_own];
+    if (o < 0 || o >= nranks || o == rank) {
+      err = "halo_owner[" + S(i - n_own) + "] = " + S(o) + (o == rank ? ": a halo node (local " + S(i) + ") cannot be owned by this rank"
+                                                                      : " outside [0," + S(nranks) + ")");
+      return FEAHIP_EINVAL;
+    }
+  }
+  {
+    std::vector<std::pair<int, int>> byid((size_t)n_local);
+    for (int i = 0; i < n_local; ++i) {
+      if (node_global[i] < 0 || (n_global >= 0 && node_global[i] >= n_global)) {
+        err = "node_global[" + S(i) + "] = " + S(node_global[i]) + " outside [0," + S(n_global) + ")"; return FEAHIP_EINVAL;
+      }
+      byid[(size_t)i] = {node_global[i], i};
+    }
+    std::sort(byid.begin(), byid.end());
+    for (int i = 1; i < n_local; ++i)
+      if (byid[(size_t)i].first == byid[(size_t)i - 1].first) {
+        err = "node_global[" + S(byid[(size_t)i].second) + "] repeats node_global[" + S(byid[(size_t)i - 1].second) + "] = " + S(byid[(size_t)i].first);
+        return FEAHIP_EINVAL;
+      }
+  }
+  out.n_global = n_global; out.n_own = n_own; out.lib0 = 0; out.lib1 = n_own;
+  out.node_global.assign(node_global, node_global + n_local);
+  out.node_lib.clear();                                         // no library numbering of the whole mesh exists here
+  out.elem_global.resize((size_t)E);
+  for (int e = 0; e < E; ++e) out.elem_global[(size_t)e] = elem_global ? elem_global[e] : e;
+  out.elements.assign(elements, elements + (size_t)E * npe);
+  if (nodes0) out.nodes0.assign(nodes0, nodes0 + (size_t)n_local * 3); else out.nodes0.clear();
+  out.presc_node.clear(); out.presc_type.clear(); out.presc_values.clear();
+  for (int i = 0; i < n_presc; ++i) {
+    if (presc_node[i] < 0 || presc_node[i] >= n_local) {
+      err = "prescribed entry " + S(i) + ": local node " + S(presc_node[i]) + " outside [0," + S(n_local) + ")"; return FEAHIP_EINVAL;
+    }
+    out.presc_node.push_back(presc_node[i]); out.presc_type.push_back(presc_type[i]);
+    for (int j = 0; j < 3; ++j) out.presc_values.push_back(presc_values[(size_t)i * 3 + j]);
+  }
+  // the two ends of an exchange are built in different processes and share only the global ids
+  finish_rank_mesh(rank, nranks, npe, halo_owner, out.node_global.data(), out);
   return FEAHIP_OK;
+}
+
+// A local order that suits the kernels: renumber.cpp's numbering of the local mesh (compact cells; bisection leaves off
+// a lattice), then the owned nodes first and the halo nodes after, each in that numbering's order.
+int slab_order(int n_local, int n_own, int E, int npe, const int *elements, const double *nodes0, int *new_local_id)
+{
+  std::vector<int> lib;
+  locality_numbering(n_local, E, npe, elements, nodes0, lib);
+  std::vector<std::pair<int, int>> own, halo;                  // (library id of the local mesh, incoming local id)
+  for (int a = 0; a < n_local; ++a) (a < n_own ? own : halo).emplace_back(lib[(size_t)a], a);
+  std::sort(own.begin(), own.end()); std::sort(halo.begin(), halo.end());
+  bool moved = false;
+  for (int i = 0; i < n_local; ++i) {
+    const int a = i < n_own ? own[(size_t)i].second : halo[(size_t)(i - n_own)].second;
+    new_local_id[a] = i; moved = moved || a != i;
+  }
+  return moved ? 1 : 0;
 }

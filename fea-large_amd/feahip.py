@@ -83,6 +83,11 @@ ABI = {
     "feahip_node_numbering": [C.c_void_p, _ip],
     "feahip_create_rank": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _dp,
                            C.c_int, _dp, C.c_int, C.c_int, _ip, _ip, _dp],
+    "feahip_create_rank_local": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, _dp, _dp, _ip, _dp, _ip, _ip, _ip, C.c_int, _dp, C.c_int, C.c_int, _ip, _ip, _dp],
+    "feahip_host_rank_local_plan": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip, _ip, _ip,
+                                    _ip, _ip],
+    "feahip_host_slab_order": [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _dp, _ip],
     "feahip_rank_counts": [C.c_void_p, C.POINTER(C.c_longlong)],
     "feahip_rank_maps": [C.c_void_p, _ip, _ip],
     "feahip_host_rank_plan": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _ip],
@@ -817,15 +822,170 @@ def host_rank_plan(deck, rank, nranks):
             "recv": [ridx[roff[k]:roff[k + 1]].copy() for k in range(npeer)]}
 
 
+class Slab:
+    """What ONE rank of a run holds when the caller partitions the mesh itself (feahip_create_rank_local): local nodes
+    -- [0, n_own) owned, then the halo nodes of the elements around them -- those elements in LOCAL node ids, the global
+    id of every local node and element, the owner of every halo node, the prescribed entries of every local node (halo
+    nodes included) and optional surface faces, both in local ids.  Material, element and solver fields as Deck."""
+
+    def __init__(self, **kw):
+        self.model = kw.get("model", MODEL_COMPRESSIBLE_NEOHOOKEAN)
+        self.parameters = np.array(kw.get("parameters", [100.0, 100.0]), dtype=np.float64)
+        self.solver_type = kw.get("solver_type", CG)
+        self.solver_tolerance = kw.get("solver_tolerance", 1e-14)
+        self.solver_max_iter = kw.get("solver_max_iter", 20000)
+        self.ele_type = kw.get("ele_type", TETRAHEDRA10)
+        self.load_increments_count = kw.get("load_increments_count", 1)
+        self.desired_tolerance = kw.get("desired_tolerance", 1e-8)
+        self.max_newton_count = kw.get("max_newton_count", 20)
+        self.modified_newton = kw.get("modified_newton", True)
+        self.gauss_nodes_count = kw.get("gauss_nodes_count", 5)
+        self.nodes = np.ascontiguousarray(kw["nodes"], dtype=np.float64).reshape(-1, 3)
+        self.elements = np.ascontiguousarray(kw["elements"], dtype=np.int32)
+        self.nodes_per_element = self.elements.shape[1]
+        self.node_global = np.ascontiguousarray(kw["node_global"], dtype=np.int32)
+        eg = kw.get("elem_global")
+        self.elem_global = np.arange(len(self.elements), dtype=np.int32) if eg is None else np.ascontiguousarray(eg, dtype=np.int32)
+        self.n_own = int(kw["n_own"])
+        self.n_global_nodes = int(kw["n_global_nodes"])
+        self.halo_owner = np.ascontiguousarray(kw.get("halo_owner", []), dtype=np.int32)
+        self.presc_node = np.ascontiguousarray(kw.get("presc_node", []), dtype=np.int32)
+        self.presc_type = np.ascontiguousarray(kw.get("presc_type", []), dtype=np.int32)
+        self.presc_values = np.ascontiguousarray(kw.get("presc_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+        faces = np.asarray(kw.get("surface_faces", np.zeros((0, 0))), dtype=np.int32)
+        self.surface_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
+        self.surface_kind = np.ascontiguousarray(kw.get("surface_kind", []), dtype=np.int32)
+        self.surface_values = np.ascontiguousarray(kw.get("surface_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+
+    def permuted(self, new_local_id):
+        """The same slab with local node a renamed new_local_id[a] (owned ids must stay in [0, n_own))."""
+        import copy
+        new = np.ascontiguousarray(new_local_id, dtype=np.int32)
+        n, no = len(self.nodes), self.n_own
+        if not (np.array_equal(np.sort(new), np.arange(n)) and np.all(new[:no] < no)):
+            raise ValueError("not a permutation of the local ids that keeps the owned nodes first")
+        out = copy.copy(self)
+        out.nodes = np.empty_like(self.nodes); out.nodes[new] = self.nodes
+        out.node_global = np.empty_like(self.node_global); out.node_global[new] = self.node_global
+        out.halo_owner = np.empty_like(self.halo_owner); out.halo_owner[new[no:] - no] = self.halo_owner
+        out.elements = np.ascontiguousarray(new[self.elements])
+        out.presc_node = np.ascontiguousarray(new[self.presc_node]) if len(self.presc_node) else self.presc_node
+        if len(self.surface_kind):
+            out.surface_faces = np.ascontiguousarray(new[self.surface_faces])
+        return out
+
+    def reordered(self):
+        """The slab in the local order feahip_host_slab_order proposes: the library's numbering of the local mesh,
+        owned nodes first."""
+        new = np.empty(len(self.nodes), dtype=np.int32)
+        rc = load_library().feahip_host_slab_order(len(self.nodes), self.n_own, len(self.elements), self.nodes_per_element,
+                                                   _i(self.elements), _d(self.nodes), _i(new))
+        if rc < 0:
+            raise FeaHipError(f"feahip_host_slab_order failed ({rc})")
+        return self.permuted(new) if rc else self
+
+
+class LocalRankSolver(FeaSolver):
+    """One rank's context from its own slab (feahip_create_rank_local): what RankSolver is, made without the whole mesh.
+    Every node- or element-indexed method speaks the slab's local indices; surface faces are local too."""
+
+    def __init__(self, slab, rank, nranks, device=0):            # noqa: super().__init__ not called: another constructor of the ABI
+        self._lib = load_library()
+        self._ctx = C.c_void_p()
+        self.deck = self.slab = slab
+        w, _, dforms = element_tables(slab.ele_type, slab.gauss_nodes_count)
+        self.npe, self.G = slab.nodes_per_element, slab.gauss_nodes_count
+        par = np.zeros(10)
+        par[:2] = slab.parameters[:2]
+        rc = self._lib.feahip_create_rank_local(
+            C.byref(self._ctx), device, rank, nranks, slab.n_global_nodes, len(slab.nodes), slab.n_own, len(slab.elements),
+            self.npe, self.G, _d(w), _d(dforms), _i(slab.elements), _d(slab.nodes), _i(slab.node_global), _i(slab.elem_global),
+            _i(slab.halo_owner), slab.model, _d(par), 2, len(slab.presc_node), _i(slab.presc_node), _i(slab.presc_type),
+            _d(slab.presc_values))
+        if rc != 0:
+            self._ctx = C.c_void_p()
+            raise FeaHipError(f"feahip_create_rank_local failed ({rc}): {self._lib.feahip_create_error().decode()}")
+        o = (C.c_longlong * 8)()
+        self._chk(self._lib.feahip_rank_counts(self._ctx, o))
+        self.N, self.n_own, self.E, self.N_global = int(o[0]), int(o[1]), int(o[2]), int(o[3])
+        self.nnzb_local, self.nnzb_owned, self.rows_sent, self.rows_received = int(o[4]), int(o[5]), int(o[6]), int(o[7])
+        self.ndof = 3 * self.N
+        self.node_global = np.empty(self.N, dtype=np.int32)
+        self.elem_global = np.empty(self.E, dtype=np.int32)
+        self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
+        self._deck_surface_loads()                              # local ids; faces of other ranks' nodes are dropped
+
+
+def host_rank_local_plan(slab, rank, nranks):
+    """Host only: the halo plan feahip_create_rank_local installs for this slab, in GLOBAL node ids:
+    dict(peers, send, recv), rows ascending in global id inside every peer."""
+    lib = load_library()
+    cnt = np.zeros(3, dtype=np.int32)
+    args = (rank, nranks, len(slab.nodes), slab.n_own, len(slab.elements), slab.nodes_per_element, _i(slab.elements),
+            _i(slab.node_global), _i(slab.halo_owner))
+    rc = lib.feahip_host_rank_local_plan(*args, _i(cnt), None, None, None, None, None)
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_rank_local_plan failed ({rc}): {lib.feahip_create_error().decode()}")
+    npeer, nsend, nrecv = (int(v) for v in cnt)
+    peers = np.zeros(max(npeer, 1), dtype=np.int32)
+    soff, roff = np.zeros(npeer + 1, dtype=np.int32), np.zeros(npeer + 1, dtype=np.int32)
+    sidx, ridx = np.zeros(max(nsend, 1), dtype=np.int32), np.zeros(max(nrecv, 1), dtype=np.int32)
+    rc = lib.feahip_host_rank_local_plan(*args, _i(cnt), _i(peers), _i(soff), _i(roff), _i(sidx), _i(ridx))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_rank_local_plan failed ({rc}): {lib.feahip_create_error().decode()}")
+    return {"peers": [int(p) for p in peers[:npeer]],
+            "send": [sidx[soff[k]:soff[k + 1]].copy() for k in range(npeer)],
+            "recv": [ridx[roff[k]:roff[k + 1]].copy() for k in range(npeer)]}
+
+
+def slab_of(deck, rank, nranks):
+    """Cuts a whole deck into the Slab of one rank, with the library's own cut and local order (host_rank_mesh): the
+    slab RankSolver(deck, rank, nranks) holds.  A bridge for callers that still have the whole deck, and for tests."""
+    N = len(deck.nodes)
+    meshes = [host_rank_mesh(deck, r, nranks, pattern=True) for r in range(nranks)]
+    owner = np.full(N, -1, dtype=np.int32)
+    for r, m in enumerate(meshes):
+        owner[m["node_global"][:m["owned_nodes"]]] = r
+    m = meshes[rank]
+    ng, eg, no = m["node_global"], m["elem_global"], m["owned_nodes"]
+    local_of = np.full(N, -1, dtype=np.int64)
+    local_of[ng] = np.arange(len(ng))
+    kw = {k: getattr(deck, k) for k in ("model", "parameters", "solver_type", "solver_tolerance", "solver_max_iter", "ele_type",
+                                         "load_increments_count", "desired_tolerance", "max_newton_count", "modified_newton",
+                                         "gauss_nodes_count")}
+    keep = local_of[deck.presc_node] >= 0 if len(deck.presc_node) else np.zeros(0, dtype=bool)
+    if len(getattr(deck, "surface_kind", [])):
+        fl = local_of[deck.surface_faces]
+        fk = np.all(fl >= 0, axis=1)                            # all of its nodes are local (the library drops other ranks')
+        kw.update(surface_faces=fl[fk], surface_kind=deck.surface_kind[fk], surface_values=deck.surface_values[fk])
+    slab = Slab(nodes=deck.nodes[ng], elements=local_of[deck.elements[eg]], node_global=ng, elem_global=eg, n_own=no,
+                n_global_nodes=N, halo_owner=owner[ng[no:]], presc_node=local_of[deck.presc_node[keep]] if keep.any() else [],
+                presc_type=deck.presc_type[keep] if keep.any() else [],
+                presc_values=deck.presc_values[keep] if keep.any() else np.zeros((0, 3)), **kw)
+    for k in ("linesearch_max", "arclength_max"):
+        if hasattr(deck, k):
+            setattr(slab, k, getattr(deck, k))
+    return slab
+
+
 class FeaGroup:
     """n contexts of one mesh sharded by rows and driven from this process
     (feahip_group_* entries)."""
 
-    def __init__(self, deck, n, device=0, rank_contexts=False):
-        """rank_contexts: every rank holds only its sub-mesh (RankSolver) instead of the whole mesh with a row shard."""
+    def __init__(self, deck, n=None, device=0, rank_contexts=False):
+        """rank_contexts: every rank holds only its sub-mesh (RankSolver) instead of the whole mesh with a row shard.
+        deck may be a list of Slabs, one per rank: every rank is made from its own slab (LocalRankSolver)."""
+        slabs = list(deck) if isinstance(deck, (list, tuple)) else None
+        if slabs is not None:
+            if n not in (None, len(slabs)):
+                raise ValueError("n slabs make n ranks")
+            n, rank_contexts = len(slabs), True
         self.deck, self.n = deck, n
+        self.n_global = slabs[0].n_global_nodes if slabs is not None else len(deck.nodes)
         self.rank_contexts = rank_contexts
-        if rank_contexts:
+        if slabs is not None:
+            self.ranks = [LocalRankSolver(s, r, n, device=device) for r, s in enumerate(slabs)]
+        elif rank_contexts:
             self.ranks = [RankSolver(deck, r, n, device=device) for r in range(n)]
         else:
             self.ranks = [FeaSolver(deck, device=device) for _ in range(n)]
@@ -895,7 +1055,7 @@ class FeaGroup:
         parts = self.each(name)
         if self.rank_contexts:                                  # local arrays: owned rows are the first n_own
             first = parts[0]
-            out = np.zeros((len(self.deck.nodes), 3)) if first.ndim == 2 else np.zeros(3 * len(self.deck.nodes))
+            out = np.zeros((self.n_global, 3)) if first.ndim == 2 else np.zeros(3 * self.n_global)
             for r, p in zip(self.ranks, parts):
                 nd = r.node_global[:r.n_own].astype(np.int64)
                 if out.ndim == 2:

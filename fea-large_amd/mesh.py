@@ -22,7 +22,7 @@ import math
 
 import numpy as np
 
-from feahip import (CG, HEXAHEDRA8, MODEL_COMPRESSIBLE_NEOHOOKEAN, TETRAHEDRA4, TETRAHEDRA10, Deck)
+from feahip import (CG, HEXAHEDRA8, MODEL_COMPRESSIBLE_NEOHOOKEAN, TETRAHEDRA4, TETRAHEDRA10, Deck, Slab)
 
 _EDGES = [(0, 1), (1, 2), (0, 2), (0, 3), (1, 3), (2, 3)]
 
@@ -186,6 +186,97 @@ def bar_deck(n=None, dims=None, quadratic=False, recipe="clamped", model=MODEL_C
     return Deck(model=model, parameters=[100.0, 100.0], ele_type=TETRAHEDRA10 if quadratic else TETRAHEDRA4,
                 gauss_nodes_count=gauss, nodes=nodes, elements=elements, presc_node=ids, presc_type=types,
                 presc_values=vals, **kw)
+
+
+def slab_planes(gy, rank, nranks):
+    """The node planes [p0, p1) across the long (y) axis that bar_slab gives rank `rank`: near-equal counts."""
+    return gy * rank // nranks, gy * (rank + 1) // nranks
+
+
+def bar_slab(rank, nranks, n=None, dims=None, quadratic=False, hexa=False, recipe="clamped",
+             model=MODEL_COMPRESSIBLE_NEOHOOKEAN, gauss=None, dy=None, **kw):
+    """ONE rank's Slab of the bar_deck block, generated directly: nothing here is sized by the whole block.
+
+    The cut is this generator's own (not the library's rank_cut): rank r owns the node planes slab_planes(gy, r, nranks)
+    of the grid across y.  Every element of a cube has a node on each of the cube's node planes (a Kuhn tetrahedron runs
+    from the cube's (0,0,0) to its (1,1,1) corner), so the elements around the owned planes are whole layers of cubes:
+    the layers the owned planes cut or bound.  Local nodes: the owned planes, then the halo planes below, then above,
+    each lexicographic (x fastest, then z, then y); global ids are kuhn_block / hex_block's lexicographic ids, element
+    ids their element order.  Prescribed entries as bar_boundary's, for every local node on an end face."""
+    nx, ny, nz = dims if dims is not None else block_dims(n)
+    m = 2 if (quadratic and not hexa) else 1
+    gx, gy, gz = m * nx + 1, m * ny + 1, m * nz + 1
+    if gy < nranks:
+        raise ValueError("fewer node planes than ranks")
+    cuts = np.array([slab_planes(gy, r, nranks)[0] for r in range(nranks)] + [gy])
+    p0, p1 = int(cuts[rank]), int(cuts[rank + 1])
+    c_lo, c_hi = max(0, -((m - p0) // m)), min(ny - 1, (p1 - 1) // m)     # cube layers with a node plane in [p0, p1)
+    j_lo, j_hi = m * c_lo, m * c_hi + m                                     # their node planes
+    planes = np.concatenate([np.arange(p0, p1), np.arange(j_lo, p0), np.arange(p1, j_hi + 1)])
+    pos = np.empty(j_hi - j_lo + 1, dtype=np.int32)                         # plane j -> its place in the local order
+    pos[planes - j_lo] = np.arange(len(planes), dtype=np.int32)
+    plane_nodes = gx * gz
+    n_own, n_local = (p1 - p0) * plane_nodes, len(planes) * plane_nodes
+
+    # local nodes
+    kk, ii = np.divmod(np.arange(plane_nodes, dtype=np.int32), gx)
+    jj = np.repeat(planes.astype(np.int32), plane_nodes)
+    origin, size = (0.0, 1.0, 0.0), (1.0, 6.0, 1.0)
+    nodes = np.empty((n_local, 3))
+    nodes[:, 0] = np.tile(origin[0] + size[0] * ii / (gx - 1), len(planes))
+    nodes[:, 1] = origin[1] + size[1] * jj / (gy - 1)
+    nodes[:, 2] = np.tile(origin[2] + size[2] * kk / (gz - 1), len(planes))
+    node_global = jj.astype(np.int64) * plane_nodes + np.tile(np.arange(plane_nodes, dtype=np.int64), len(planes))
+    owner = (np.searchsorted(cuts, planes[p1 - p0:], side="right") - 1).astype(np.int32)
+    halo_owner = np.repeat(owner, plane_nodes)
+
+    # local elements: the cube layers [c_lo, c_hi], cubes y slowest, then z, x fastest (kuhn_block's order)
+    layers = c_hi - c_lo + 1
+    cube = np.arange(layers * nz * nx, dtype=np.int32)
+    ci, ck, cj = cube % nx, (cube // nx) % nz, cube // (nx * nz) + c_lo
+
+    def lid(i, j, k):                                                       # grid coordinates -> local node id
+        return (pos[j - j_lo] * plane_nodes + k * gx + i).astype(np.int32)
+
+    if hexa:
+        corners = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)]
+        elements = np.empty((len(cube), 8), dtype=np.int32)
+        for a, (da, db, dc) in enumerate(corners):
+            elements[:, a] = lid(ci + da, cj + db, ck + dc)
+        elem_global = (cj.astype(np.int64) * nz + ck) * nx + ci
+        ele_type, gauss = HEXAHEDRA8, (8 if gauss is None else gauss)
+    else:
+        off = _kuhn_corner_offsets().astype(np.int32)                       # [6][4][3]
+        elements = np.empty((len(cube) * 6, 10 if quadratic else 4), dtype=np.int32)
+        verts = [(a, a) for a in range(4)] + (list(_EDGES) if quadratic else [])
+        for col, (a, b) in enumerate(verts):                                # a vertex, or the mid-point of edge (a, b)
+            d = (off[:, a, :] + off[:, b, :]) * m // 2                      # [6][3] grid offset inside the cube
+            elements[:, col] = lid(m * ci[:, None] + d[None, :, 0], m * cj[:, None] + d[None, :, 1],
+                                   m * ck[:, None] + d[None, :, 2]).ravel()
+        elem_global = (((cj.astype(np.int64) * nz + ck) * nx + ci)[:, None] * 6 + np.arange(6)[None, :]).ravel()
+        ele_type = TETRAHEDRA10 if quadratic else TETRAHEDRA4
+        if gauss is None:
+            gauss = 5 if quadratic else 1
+
+    # prescribed entries of the local nodes on the end faces (bar_boundary's recipe), halo nodes included
+    if dy is None:
+        dy = increment_for(max(nx, nz))
+    on = np.nonzero((jj == 0) | (jj == gy - 1))[0].astype(np.int32)
+    vals = np.zeros((len(on), 3))
+    vals[jj[on] == gy - 1, 1] = dy
+    if recipe == "clamped":
+        types = np.full(len(on), 7, dtype=np.int32)
+    elif recipe == "uniaxial":
+        types = np.full(len(on), 2, dtype=np.int32)
+        li = np.tile(ii, len(planes))[on]; lk = np.tile(kk, len(planes))[on]
+        types[(jj[on] == 0) & (li == 0) & (lk == 0)] = 7
+        types[(jj[on] == 0) & (li == gx - 1) & (lk == 0)] = 6
+    else:
+        raise ValueError(recipe)
+    kw.setdefault("solver_type", CG)
+    return Slab(model=model, parameters=[100.0, 100.0], ele_type=ele_type, gauss_nodes_count=gauss, nodes=nodes,
+                elements=elements, node_global=node_global, elem_global=elem_global, halo_owner=halo_owner, n_own=n_own,
+                n_global_nodes=gx * gy * gz, presc_node=on, presc_type=types, presc_values=vals, **kw)
 
 
 def cylinder_deck(nr, nt, nz, quadratic=False, ri=1.0, ro=2.0, zlo=-8.0, zhi=8.0, du=None,

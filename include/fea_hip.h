@@ -174,7 +174,7 @@ int feahip_solve(feahip_ctx *ctx, int load_increments, int max_newton,
  * no loaded faces nothing is launched and nothing changes.  Row shards and
  * in-process groups add the loads of the rows they own; a feahip_create_rank
  * context takes the whole face list and keeps the faces touching its owned
- * nodes.                                                                    */
+ * nodes; a feahip_create_rank_local context takes faces in LOCAL node ids.  */
 enum { FEAHIP_LOAD_PRESSURE = 0, FEAHIP_LOAD_TRACTION = 1 };
 /* replaces the set; n_faces = 0 clears it.  face_nodes[n_faces][nodes_per_face]
  * in the CALLER's node ids, kind[n_faces], values[n_faces][3] (pressure in [0];
@@ -241,6 +241,68 @@ int feahip_create_rank(feahip_ctx **out, int device, int rank, int nranks,
                        int model, const double *model_params, int params_count,
                        int n_presc, const int *presc_node, const int *presc_type,
                        const double *presc_values);
+/* The same rank context from the caller's OWN slab: a caller that partitions its
+ * mesh itself (every MPI code does) hands over its local nodes -- [0, n_own)
+ * the nodes it owns, then the halo nodes: every other node of an element that
+ * touches an owned node -- those elements in LOCAL node ids, and for every halo
+ * node the rank that owns it.  No argument is sized by the whole mesh and
+ * nothing of that size is allocated.  The context is a rank context in every
+ * respect (feahip_rank_counts / _maps, feahip_owned_rows, feahip_comm_init,
+ * feahip_group_*, multigrid, line search, surface loads).  It keeps the local
+ * order it is given; the order of the owned rows is what the assembly kernels
+ * see, and feahip_host_slab_order below offers a good one.
+ *   n_global_nodes  nodes of the whole mesh (reports and the range of
+ *                   node_global only)
+ *   elements        [n_elems][npe] LOCAL node ids; every element has an owned
+ *                   node, and the rank holds EVERY element touching its nodes
+ *   node_global     [n_local] the caller's global id, distinct
+ *   elem_global     [n_elems] or NULL (then 0..n_elems-1); reports only
+ *   halo_owner      [n_local - n_own] owning rank of local node n_own + i
+ * Halo plan: derived from the local elements and halo_owner.  The two ends of an
+ * exchange are built in different processes and share only node_global, so the
+ * rows to and from a peer travel in ascending GLOBAL node id on both sides
+ * (feahip_create_rank orders them by library id).
+ * Prescribed dofs: presc_node in LOCAL ids, and the caller passes the entries
+ * of EVERY local node, halo nodes included: an owned row's column at a
+ * prescribed halo dof is cancelled from it (feahip_apply_prescribed_bc), which
+ * the rank can only do if it knows the dof is prescribed.
+ * Surface loads on such a context (feahip_set_surface_loads) take faces in
+ * LOCAL node ids, all of whose nodes are local; a face that touches no owned
+ * node is dropped silently (another rank's), any other bad face is refused.
+ * Refused with FEAHIP_EINVAL, feahip_create_error naming the offending index:
+ * n_own outside [1, n_local]; an element id outside [0, n_local); an element
+ * with no owned node; a halo node no element touches; halo_owner outside
+ * [0, nranks) or equal to rank; node_global outside [0, n_global_nodes) or
+ * repeated; a prescribed id outside [0, n_local).                            */
+int feahip_create_rank_local(feahip_ctx **out, int device, int rank, int nranks,
+        int n_global_nodes,
+        int n_local, int n_own,
+        int n_elems, int npe, int gauss_count,
+        const double *gauss_weights, const double *dforms,
+        const int *elements,
+        const double *nodes0,          /* [n_local][3]                            */
+        const int *node_global,
+        const int *elem_global,
+        const int *halo_owner,
+        int model, const double *model_params, int params_count,
+        int n_presc, const int *presc_node /* LOCAL ids */, const int *presc_type,
+        const double *presc_values);
+/* Host-only (no device): the halo plan feahip_create_rank_local installs, in
+ * GLOBAL node ids -- counts3 = {peers, rows sent, rows received} by a sizing
+ * call with null lists, then the lists as feahip_host_rank_plan gives them.
+ * The same validation (without the range of node_global: no n_global_nodes
+ * here), the message through feahip_create_error.                            */
+int feahip_host_rank_local_plan(int rank, int nranks, int n_local, int n_own, int n_elems, int npe,
+        const int *elements, const int *node_global, const int *halo_owner,
+        int *counts3, int *peers, int *send_off, int *recv_off, int *send_idx, int *recv_idx);
+/* Host-only (no device): a local order that suits the kernels -- the library's
+ * numbering (csrc/renumber.cpp) of the LOCAL mesh, split stably into owned
+ * first, halo after.  new_local_id[n_local]: the new local id of local node a
+ * (owned ids stay in [0, n_own)); the caller permutes its arrays by it.
+ * Returns 1 when it reorders, 0 when the order given is kept, negative on
+ * error.                                                                     */
+int feahip_host_slab_order(int n_local, int n_own, int n_elems, int npe, const int *elements,
+        const double *nodes0, int *new_local_id);
 int feahip_rank_counts(feahip_ctx *ctx, long long *out8);
 int feahip_rank_maps(feahip_ctx *ctx, int *node_global, int *elem_global);
 /* Host-only (no device): the same sub-mesh without a context -- counts8 =
