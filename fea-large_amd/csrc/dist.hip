@@ -4,7 +4,8 @@
 // Production shape (bench.py, torch.distributed launch): one process per GPU,
 // one context per process, halo rows over ncclSend/ncclRecv (point-to-point
 // over xGMI; every rank talks to its slab neighbours only) and one to three
-// doubles per ncclAllReduce.  No vector all-reduce, no all-gather on the path.
+// doubles per ncclAllReduce.  No all-gather on the path; the only vector all-reduce is the coarse level's
+// (preconditioner kind 2, coarse.h: at most 768 doubles per CG iteration, on the communication stream).
 // The same loop also drives an in-process group of contexts (GroupTransport),
 // which is how the sharded path is exercised where one process sees the GPU.
 #include "feahip_internal.h"
@@ -150,6 +151,13 @@ struct RcclTransport : Transport {
     feahip_ctx *c = R[0];
     ncclResult_t r = ncclAllReduce(c->d_scal + 8 + slot, c->d_scal + 8 + slot, (size_t)n, ncclDouble, ncclSum, comm, c->stream);
     if (r != ncclSuccess) return fail(c, "ncclAllReduce", r);
+    return FEAHIP_OK;
+  }
+  int allreduce_vec(std::vector<feahip_ctx *> &R, size_t n, bool comm) override
+  {
+    feahip_ctx *c = R[0];
+    ncclResult_t r = ncclAllReduce(c->d_vred, c->d_vred, n, ncclDouble, ncclSum, this->comm, comm ? c->comm_stream : c->stream);
+    if (r != ncclSuccess) return fail(c, "ncclAllReduce (vector)", r);
     return FEAHIP_OK;
   }
 };

@@ -12,6 +12,7 @@ hipError_t feahip_device_malloc(void **p, size_t bytes)
 }
 #define hipMalloc(p, bytes) feahip_device_malloc((void **)(p), (bytes))
 #include "amg.h"
+#include "coarse.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -478,6 +479,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   if (c->tr && c->owns_tr) delete c->tr;
   amg_destroy(c);
+  coarse_destroy(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -508,8 +510,9 @@ extern "C" int feahip_set_assembly(feahip_ctx *c, int strategy)
 extern "C" int feahip_set_preconditioner(feahip_ctx *c, int kind)
 {
   CTX_GUARD(c);
-  if (kind != 0 && kind != 1) { c->err = "unknown preconditioner"; return FEAHIP_EINVAL; }
-  if (kind == 1) { int rc = amg_create(c); if (rc) return rc; }
+  if (kind < 0 || kind > 2) { c->err = "unknown preconditioner"; return FEAHIP_EINVAL; }
+  if (kind >= 1) { int rc = amg_create(c); if (rc) return rc; }
+  if (kind != 2) coarse_destroy(c);                    // nothing of the coarse level outlives kind 2
   c->precond = kind;
   return FEAHIP_OK;
 }
@@ -718,6 +721,7 @@ extern "C" int feahip_group_init(feahip_ctx **ctxs, int n)
     ctxs[r]->tr = t;
     ctxs[r]->owns_tr = (r == 0);
   }
+  t->set_members(std::vector<feahip_ctx *>(ctxs, ctxs + n));
   return FEAHIP_OK;
 }
 
@@ -1014,10 +1018,81 @@ extern "C" int feahip_apply_preconditioner(feahip_ctx *c, const double *r, doubl
   return FEAHIP_OK;
 }
 
+// z = M^-1 r on every rank of a group at once: what the group's PCG applies.  Under kind 2 the operator spans the
+// ranks, so this is the only way to apply it in-process; kinds 0 and 1 give what the per-context entry gives.
+int dist_precond_apply(std::vector<feahip_ctx *> &R, const double **z);      // kernels_solve.hip
+extern "C" int feahip_group_apply_preconditioner(feahip_ctx **ctxs, int n, const double *const *r, double *const *z)
+{
+  std::vector<feahip_ctx *> R;
+  int rc = group_vec(ctxs, n, R);
+  if (rc) return rc;
+  if (!r || !z) return FEAHIP_EINVAL;
+  for (int k = 0; k < n; ++k) {
+    feahip_ctx *c = R[k];
+    if (!r[k] || !z[k]) return FEAHIP_EINVAL;
+    CTX_GUARD(c);
+    if (!c->k_valid) { c->err = "apply_preconditioner: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+    if ((rc = set_node_vec(c, c->d_r, r[k]))) return rc;
+  }
+  std::vector<const double *> dz((size_t)n, nullptr);
+  if ((rc = dist_precond_apply(R, dz.data()))) return rc;
+  for (int k = 0; k < n; ++k) {
+    feahip_ctx *c = R[k];
+    FEA_HIP_CHECK(c, hipSetDevice(c->device));
+    std::vector<double> tmp((size_t)c->ndof, 0.0);               // rows of other ranks: 0
+    if ((rc = get_vec(c, dz[k] + (size_t)3 * c->row0, tmp.data() + (size_t)3 * c->row0, (size_t)3 * (c->row1 - c->row0)))) return rc;
+    for (int a = 0; a < c->N; ++a)
+      for (int j = 0; j < 3; ++j) z[k][(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+  }
+  return FEAHIP_OK;
+}
+
+// ---- the coarse level across the ranks (preconditioner 2, coarse.h) -----------
+// prepared for the current K as the next solve would prepare it; collective -- an in-process group is driven from
+// any of its contexts, the ranks of an RCCL run all make the call
+static int coarse_ready(feahip_ctx *c)
+{
+  if (c->precond != 2) { c->err = "coarse view: the preconditioner is not kind 2 (feahip_set_preconditioner(2))"; return FEAHIP_ESTATE; }
+  std::vector<feahip_ctx *> R(1, c);
+  if (c->tr && c->tr->members()) R = *c->tr->members();
+  for (feahip_ctx *m : R) {
+    if (m->precond != 2) { c->err = "coarse view: preconditioner 2 is not set on every rank of the group"; return FEAHIP_ESTATE; }
+    CTX_GUARD(m);
+  }
+  const int rc = coarse_prepare(R, c->tr);
+  if (rc && c->err.empty()) c->err = R[0]->err;
+  FEA_HIP_CHECK(c, hipSetDevice(c->device));
+  return rc;
+}
+
+extern "C" int feahip_coarse_info(feahip_ctx *c, long long *out8, int *agg_of_owned_row, double *centroids)
+{
+  CTX_GUARD(c);
+  if (!out8) return FEAHIP_EINVAL;
+  const int rc = coarse_ready(c);
+  if (rc) return rc;
+  return coarse_export_info(c, out8, agg_of_owned_row, centroids);
+}
+
+extern "C" int feahip_coarse_matrix(feahip_ctx *c, double *A)
+{
+  CTX_GUARD(c);
+  if (!A) return FEAHIP_EINVAL;
+  const int rc = coarse_ready(c);
+  if (rc) return rc;
+  return coarse_export_matrix(c, A);
+}
+
+extern "C" int feahip_host_coarse_aggregates(int n_owned, int m, int *first_row_of_aggregate)
+{
+  if (n_owned < 1 || m < 1) return FEAHIP_EINVAL;
+  return coarse_cuts(n_owned, m, first_row_of_aggregate);
+}
+
 // the hierarchy as the next PCG solve would use it (prepared here when K changed since)
 static int amg_ready(feahip_ctx *c)
 {
-  if (c->precond != 1) { c->err = "multigrid view: the preconditioner is not the multigrid (feahip_set_preconditioner(1))"; return FEAHIP_ESTATE; }
+  if (c->precond < 1) { c->err = "multigrid view: the preconditioner is not the multigrid (feahip_set_preconditioner(1))"; return FEAHIP_ESTATE; }
   if (!c->k_valid) { c->err = "multigrid view: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
   return amg_prepare(c);
 }

@@ -486,7 +486,8 @@ struct feahip_ctx {
   int rank_n_global = 0;
   bool rank_local_ids = false;         // feahip_create_rank_local: the caller speaks local ids (surface faces included)
 
-  // preconditioner of PCG_ILU / CHOLESKY solves: 0 = 3x3 block-Jacobi, 1 = aggregation multigrid (amg.h)
+  // preconditioner of PCG_ILU / CHOLESKY solves: 0 = 3x3 block-Jacobi, 1 = aggregation multigrid (amg.h), 2 = the
+  // multigrid plus a coarse level across the ranks (coarse.h)
   // which matrix d_K holds: bumped by every stiffness assembly, copied by stash / restore; k_bc = prescribed-dof
   // masking applied since.  Only used to skip numeric re-setup of the multigrid hierarchy for an unchanged K
   // (modified Newton restores the same matrix every iteration); a stale hierarchy would cost iterations, not accuracy.
@@ -497,6 +498,10 @@ struct feahip_ctx {
   int linesearch_max = 0;
   int precond = 0;
   void *amg = nullptr;         // AmgHierarchy, built on first use
+  // kind 2: the multigrid plus one coarse level across the ranks (coarse.h); nothing of it exists under kinds 0 and 1
+  void *coarse = nullptr;      // RankCoarse, built on first use
+  double *d_vred = nullptr;    // buffer of the vector all-reduce (Transport::allreduce_vec)
+  size_t vred_cap = 0;         // its length in doubles
   // surface loads: f = load_factor * F_ext(x) - T(x) in every residual assembly; feahip_update_nodes_with_bc adds its
   // lambda to load_factor (one increment of the loads per step, as of the prescribed displacements)
   SurfaceLoads surf;
@@ -595,6 +600,12 @@ struct Transport {
   virtual int exchange_end(std::vector<feahip_ctx *> &R) { (void)R; return FEAHIP_OK; }
   // d_scal[8+slot .. 8+slot+n) summed over all ranks, result on every rank
   virtual int allreduce(std::vector<feahip_ctx *> &R, int slot, int n) = 0;
+  // the contexts' d_vred[0 .. n) summed over all ranks, result on every rank.  comm: the buffer is produced and
+  // consumed on the contexts' communication streams (which exist), not on their own
+  virtual int allreduce_vec(std::vector<feahip_ctx *> &R, size_t n, bool comm) = 0;
+  // the contexts of an in-process group in rank order; null where every process drives one context
+  virtual const std::vector<feahip_ctx *> *members() const { return nullptr; }
+  virtual void set_members(const std::vector<feahip_ctx *> &) {}
 };
 Transport *make_group_transport();
 Transport *make_rccl_transport(feahip_ctx *c, int rank, int nranks, const void *unique_id, std::string &err);

@@ -11,6 +11,7 @@
 // order, so repeated runs give identical bits.
 #include <type_traits>
 #include "feahip_internal.h"
+#include "coarse.h"
 #include <map>
 
 // ------------------------------------------------------------------------
@@ -502,7 +503,18 @@ void k_reduce_final(int n, int nsums, int stride, const double *part, double *ou
 int amg_prepare(feahip_ctx *c);
 double *amg_apply(feahip_ctx *c, const double *r);
 double *amg_result(feahip_ctx *c);
-static inline bool use_amg(const feahip_ctx *c, int mode) { return mode != 0 && c->precond == 1; }
+static inline bool use_amg(const feahip_ctx *c, int mode) { return mode != 0 && c->precond >= 1; }
+// ... with the coarse level across the ranks on top (coarse.h): all contexts of a run are set alike
+static inline bool use_coarse(const std::vector<feahip_ctx *> &R, int mode) { return mode != 0 && R[0]->precond == 2; }
+static int check_same_kind(const std::vector<feahip_ctx *> &R)
+{
+  for (feahip_ctx *c : R)
+    if ((c->precond == 2) != (R[0]->precond == 2)) {
+      for (feahip_ctx *e : R) e->err = "preconditioner 2 (coarse level across the ranks) must be set on every rank or on none";
+      return FEAHIP_ESTATE;
+    }
+  return FEAHIP_OK;
+}
 
 // 3x3 inverse of the diagonal blocks (block-Jacobi); mode 0 = identity
 __global__ void k_precond_build(int a0, int a1, const int *diag, const double *K, int mode, double *minv)
@@ -787,9 +799,19 @@ __global__ void k_precond_apply(int a0, int a1, const double *minv, const double
   const double *m = minv + (size_t)a * 9, *v = r + (size_t)a * 3;
   for (int i = 0; i < 3; ++i) z[(size_t)a * 3 + i] = m[3 * i] * v[0] + m[3 * i + 1] * v[1] + m[3 * i + 2] * v[2];
 }
+int dist_precond_apply(std::vector<feahip_ctx *> &R, const double **z);
 int precond_apply(feahip_ctx *c, const double *r, const double **z)
 {
   int rc;
+  if (c->precond == 2) {                           // collective: the ranks of an RCCL run all call this
+    if (r != c->d_r) { c->err = "apply_preconditioner: kind 2 reads the context's residual vector"; return FEAHIP_EINVAL; }
+    if (c->tr && c->tr->members() && c->tr->members()->size() > 1) {
+      c->err = "apply_preconditioner: preconditioner 2 spans the ranks of the group (feahip_group_apply_preconditioner)";
+      return FEAHIP_ESTATE;
+    }
+    std::vector<feahip_ctx *> R(1, c);
+    return dist_precond_apply(R, z);
+  }
   if (c->precond == 1) {
     if ((rc = amg_prepare(c))) return rc;
     if (!(*z = amg_apply(c, r))) return FEAHIP_EHIP;
@@ -981,6 +1003,29 @@ struct GroupTransport : Transport {
     }
     return FEAHIP_OK;
   }
+  // the vector all-reduce: summed on the host in rank order, every rank receives the same bits
+  std::vector<feahip_ctx *> group;
+  std::vector<double> vsum, vtmp;
+  const std::vector<feahip_ctx *> *members() const override { return &group; }
+  void set_members(const std::vector<feahip_ctx *> &m) override { group = m; }
+  int allreduce_vec(std::vector<feahip_ctx *> &R, size_t n, bool comm) override
+  {
+    vsum.assign(n, 0.0); vtmp.resize(n);
+    for (auto *c : R) {
+      (void)hipSetDevice(c->device);
+      hipStream_t st = comm ? c->comm_stream : c->stream;
+      FEA_HIP_CHECK(c, hipMemcpyAsync(vtmp.data(), c->d_vred, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+      FEA_HIP_CHECK(c, hipStreamSynchronize(st));
+      for (size_t i = 0; i < n; ++i) vsum[i] += vtmp[i];
+    }
+    for (auto *c : R) {
+      (void)hipSetDevice(c->device);
+      hipStream_t st = comm ? c->comm_stream : c->stream;
+      FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_vred, vsum.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+      FEA_HIP_CHECK(c, hipStreamSynchronize(st));
+    }
+    return FEAHIP_OK;
+  }
 };
 Transport *make_group_transport() { return new GroupTransport(); }
 
@@ -998,19 +1043,32 @@ static int enq_cg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it, 
     if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, spmv_grid(c), 1, RB, c->d_part, c->d_scal + 8);
   }
   if (T && (rc = T->allreduce(R, 0, 1))) return rc;              // p.q
-  FOR_RANKS(c) {
-    const int gv = vgrid(c);
+  const bool coarse = use_coarse(R, mode);
+  auto update = [&](feahip_ctx *c) {
     const bool amg = use_amg(c, mode);
     // block-Jacobi: z = M r is formed here and left in q; multigrid: plain update, then the cycle
-    hipLaunchKernelGGL(k_cg_update, dim3(gv), dim3(256), 0, c->stream, own0(c), own1(c), it, spmv_grid(c), c->d_p,
+    hipLaunchKernelGGL(k_cg_update, dim3(vgrid(c)), dim3(256), 0, c->stream, own0(c), own1(c), it, spmv_grid(c), c->d_p,
                        c->d_q, amg ? (const double *)nullptr : c->d_minv, c->d_u, c->d_r, c->d_part,
                        T ? c->d_scal + 8 : (const double *)nullptr, c->d_scal, c->d_flag, amg ? (double *)nullptr : c->d_q);
-    if (amg) {
-      const double *z = amg_apply(c, c->d_r);                      // local: block-Jacobi over the ranks, a W-cycle inside
+  };
+  auto cycle = [&](feahip_ctx *c) -> int {
+    const int gv = vgrid(c);
+    if (use_amg(c, mode)) {
+      double *z = amg_apply(c, c->d_r);                            // local: block-Jacobi over the ranks, a W-cycle inside
       if (!z) return FEAHIP_EHIP;
+      if (coarse) { const int rk = coarse_enq_prolong_add(c, z); if (rk) return rk; }   // + Phi e_c, all-reduced meanwhile
       hipLaunchKernelGGL(k_dot_partial, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), c->d_r, z, c->d_part + RB);
     }
     if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, gv, 2, RB, c->d_part + RB, c->d_scal + 9);
+    return FEAHIP_OK;
+  };
+  if (!coarse) {
+    FOR_RANKS(c) { update(c); if ((rc = cycle(c))) return rc; }
+  } else {
+    // kind 2: r_c = Phi' r and its all-reduce run on the communication stream, under the cycle
+    FOR_RANKS(c) { update(c); if ((rc = coarse_enq_restrict(c, c->d_r))) return rc; }
+    if ((rc = coarse_allreduce_rc(R, T))) return rc;
+    FOR_RANKS(c) { if ((rc = coarse_enq_solve(c)) || (rc = cycle(c))) return rc; }
   }
   if (T && (rc = T->allreduce(R, 1, 2))) return rc;              // r.z, r.r
   FOR_RANKS(c) {
@@ -1026,26 +1084,42 @@ static int enq_cg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it, 
 static int enq_cg_start(std::vector<feahip_ctx *> &R, Transport *T, int mode, double tol)
 {
   int rc;
+  const bool coarse = use_coarse(R, mode);
+  if (mode != 0 && (rc = check_same_kind(R))) return rc;
   FOR_RANKS(c) {
     if (use_amg(c, mode)) { if ((rc = amg_prepare(c))) return rc; }
     else enq_precond(c, mode);
+  }
+  if (coarse && (rc = coarse_prepare(R, T))) return rc;          // (its topology borrows p: before anything of the solve)
+  FOR_RANKS(c) {
     FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_u, c->d_f, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToDevice, c->stream));
   }
   if (T && (rc = T->exchange(R, 1))) return rc;                  // halo rows of u0 = f
-  FOR_RANKS(c) {
-    const int gv = vgrid(c);
+  auto residual = [&](feahip_ctx *c) {
     const bool amg = use_amg(c, mode);
     enq_spmv_dot(c, c->d_u, c->d_q, nullptr, nullptr);
-    hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(256), 0, c->stream, own0(c), own1(c), c->d_f, c->d_q,
+    hipLaunchKernelGGL(k_cg_init, dim3(vgrid(c)), dim3(256), 0, c->stream, own0(c), own1(c), c->d_f, c->d_q,
                        amg ? (const double *)nullptr : c->d_minv, c->d_r, c->d_p, c->d_part);
-    if (amg) {                                                   // p = z = M^-1 r from the cycle, r.z from it
-      const double *z = amg_apply(c, c->d_r);
+  };
+  auto cycle = [&](feahip_ctx *c) -> int {
+    const int gv = vgrid(c);
+    if (use_amg(c, mode)) {                                      // p = z = M^-1 r from the cycle, r.z from it
+      double *z = amg_apply(c, c->d_r);
       if (!z) return FEAHIP_EHIP;
+      if (coarse) { const int rk = coarse_enq_prolong_add(c, z); if (rk) return rk; }
       hipLaunchKernelGGL(k_dot_partial, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), c->d_r, z, c->d_part + RB);
       FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_p + (size_t)3 * own0(c), z + (size_t)3 * own0(c),
                                       sizeof(double) * 3 * (size_t)(own1(c) - own0(c)), hipMemcpyDeviceToDevice, c->stream));
     }
     if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, gv, 3, RB, c->d_part + RB, c->d_scal + 8);
+    return FEAHIP_OK;
+  };
+  if (!coarse) {
+    FOR_RANKS(c) { residual(c); if ((rc = cycle(c))) return rc; }
+  } else {
+    FOR_RANKS(c) { residual(c); if ((rc = coarse_enq_restrict(c, c->d_r))) return rc; }
+    if ((rc = coarse_allreduce_rc(R, T))) return rc;
+    FOR_RANKS(c) { if ((rc = coarse_enq_solve(c)) || (rc = cycle(c))) return rc; }
   }
   if (T && (rc = T->allreduce(R, 0, 3))) return rc;              // r.z, r.r, b.b
   FOR_RANKS(c) {
@@ -1109,27 +1183,41 @@ static void enq_cgcg_reduce(feahip_ctx *c, int with_bb)
 static int enq_cgcg_start(std::vector<feahip_ctx *> &R, Transport *T, int mode, double tol)
 {
   int rc;
+  const bool coarse = use_coarse(R, mode);
+  if (mode != 0 && (rc = check_same_kind(R))) return rc;
   FOR_RANKS(c) {
     if ((rc = ensure_cgcg(c))) return rc;
     if (use_amg(c, mode)) { if ((rc = amg_prepare(c))) return rc; }
     else enq_precond(c, mode);
+  }
+  if (coarse && (rc = coarse_prepare(R, T))) return rc;          // (its topology borrows p: before anything of the solve)
+  FOR_RANKS(c) {
     FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_u, c->d_f, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToDevice, c->stream));
     FEA_HIP_CHECK(c, hipMemsetAsync(c->d_p, 0, sizeof(double) * (size_t)c->ndof, c->stream));     // p = s = 0: the first iteration has beta = 0
     FEA_HIP_CHECK(c, hipMemsetAsync(c->d_s, 0, sizeof(double) * (size_t)c->ndof, c->stream));
   }
   if (T && (rc = T->exchange(R, 1))) return rc;                  // halo rows of u0 = f
-  FOR_RANKS(c) {
-    const int gv = vgrid(c);
+  auto residual = [&](feahip_ctx *c) {
     const bool amg = use_amg(c, mode);
     enq_spmv_dot(c, c->d_u, c->d_w, nullptr, nullptr);           // K x0 (into w, overwritten below)
     // r = b - K x0, z = M r, partial sums r.z, r.r, b.b
-    hipLaunchKernelGGL(k_cg_init, dim3(gv), dim3(256), 0, c->stream, own0(c), own1(c), c->d_f, c->d_w,
+    hipLaunchKernelGGL(k_cg_init, dim3(vgrid(c)), dim3(256), 0, c->stream, own0(c), own1(c), c->d_f, c->d_w,
                        amg ? (const double *)nullptr : c->d_minv, c->d_r, c->d_z, c->d_part);
-    if (amg) {
-      const double *z = amg_apply(c, c->d_r);
-      if (!z) return FEAHIP_EHIP;
-      hipLaunchKernelGGL(k_copy_dot, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), z, c->d_r, c->d_z, c->d_part + RB, (const int *)nullptr);
-    }
+  };
+  auto cycle = [&](feahip_ctx *c) -> int {
+    if (!use_amg(c, mode)) return FEAHIP_OK;
+    const double *z = amg_apply(c, c->d_r);
+    if (!z) return FEAHIP_EHIP;
+    if (coarse) return coarse_enq_copy_dot(c, z, c->d_r, c->d_z, c->d_part + RB, (const int *)nullptr);
+    hipLaunchKernelGGL(k_copy_dot, dim3(vgrid(c)), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), z, c->d_r, c->d_z, c->d_part + RB, (const int *)nullptr);
+    return FEAHIP_OK;
+  };
+  if (!coarse) {
+    FOR_RANKS(c) { residual(c); if ((rc = cycle(c))) return rc; }
+  } else {
+    FOR_RANKS(c) { residual(c); if ((rc = coarse_enq_restrict(c, c->d_r))) return rc; }
+    if ((rc = coarse_allreduce_rc(R, T))) return rc;
+    FOR_RANKS(c) { if ((rc = coarse_enq_solve(c)) || (rc = cycle(c))) return rc; }
   }
   if (T && (rc = T->exchange_begin(R, 3))) return rc;            // halo rows of z
   FOR_RANKS(c) enq_spmv_interior(c, c->d_z, c->d_w);
@@ -1149,17 +1237,30 @@ static int enq_cgcg_start(std::vector<feahip_ctx *> &R, Transport *T, int mode, 
 static int enq_cgcg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it, int mode)
 {
   int rc;
-  FOR_RANKS(c) {
-    const int gv = vgrid(c);
+  const bool coarse = use_coarse(R, mode);
+  auto update = [&](feahip_ctx *c) {
     const bool amg = use_amg(c, mode);
-    hipLaunchKernelGGL(k_cgcg_update, dim3(gv), dim3(256), 0, c->stream, own0(c), own1(c), it, c->d_z, c->d_w,
+    hipLaunchKernelGGL(k_cgcg_update, dim3(vgrid(c)), dim3(256), 0, c->stream, own0(c), own1(c), it, c->d_z, c->d_w,
                        amg ? (const double *)nullptr : c->d_minv, c->d_p, c->d_s, c->d_u, c->d_r, c->d_z, c->d_part,
                        c->d_scal + 8, c->d_scal, c->d_flag);
-    if (amg) {
-      const double *z = amg_apply(c, c->d_r);                      // local: block-Jacobi over the ranks, a W-cycle inside
-      if (!z) return FEAHIP_EHIP;
-      hipLaunchKernelGGL(k_copy_dot, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), z, c->d_r, c->d_z, c->d_part + RB, (const int *)c->d_flag);
-    }
+  };
+  auto cycle = [&](feahip_ctx *c) -> int {
+    if (!use_amg(c, mode)) return FEAHIP_OK;
+    const double *z = amg_apply(c, c->d_r);                        // local: block-Jacobi over the ranks, a W-cycle inside
+    if (!z) return FEAHIP_EHIP;
+    // kind 2: the launch that follows the cycle adds Phi e_c on its way
+    if (coarse) return coarse_enq_copy_dot(c, z, c->d_r, c->d_z, c->d_part + RB, (const int *)c->d_flag);
+    hipLaunchKernelGGL(k_copy_dot, dim3(vgrid(c)), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), z, c->d_r, c->d_z, c->d_part + RB, (const int *)c->d_flag);
+    return FEAHIP_OK;
+  };
+  if (!coarse) {
+    FOR_RANKS(c) { update(c); if ((rc = cycle(c))) return rc; }
+  } else {
+    // kind 2: r_c = Phi' r, its all-reduce (the second of the iteration) and e_c = A_c^-1 r_c on the communication
+    // stream, under the cycle
+    FOR_RANKS(c) { update(c); if ((rc = coarse_enq_restrict(c, c->d_r))) return rc; }
+    if ((rc = coarse_allreduce_rc(R, T))) return rc;
+    FOR_RANKS(c) { if ((rc = coarse_enq_solve(c)) || (rc = cycle(c))) return rc; }
   }
   if (T && (rc = T->exchange_begin(R, 3))) return rc;            // halo rows of z on their way ...
   FOR_RANKS(c) enq_spmv_interior(c, c->d_z, c->d_w);             // ... under the rows that do not need them
@@ -1215,6 +1316,31 @@ int dist_solve_pcg(std::vector<feahip_ctx *> &R, int type, double tol, int max_i
   if (flag < 0 && flag != -1000000000) {
     c0->err = "CG breakdown (NaN or zero curvature) at iteration " + std::to_string(-flag);
     return FEAHIP_ENOTCONVERGED;
+  }
+  return FEAHIP_OK;
+}
+
+// the same for all ranks of a run, each context's r in its d_r; kind 2 is collective (coarse.h)
+int dist_precond_apply(std::vector<feahip_ctx *> &R, const double **z)
+{
+  Transport *T = R[0]->tr;
+  int rc;
+  size_t k = 0;
+  if ((rc = check_same_kind(R))) return rc;
+  if (R[0]->precond != 2) {
+    FOR_RANKS(c) { if ((rc = precond_apply(c, c->d_r, &z[k++]))) return rc; }
+    return FEAHIP_OK;
+  }
+  FOR_RANKS(c) { if ((rc = amg_prepare(c))) return rc; }
+  if ((rc = coarse_prepare(R, T))) return rc;
+  FOR_RANKS(c) { if ((rc = coarse_enq_restrict(c, c->d_r))) return rc; }
+  if ((rc = coarse_allreduce_rc(R, T))) return rc;
+  FOR_RANKS(c) {
+    if ((rc = coarse_enq_solve(c))) return rc;
+    double *zz = amg_apply(c, c->d_r);
+    if (!zz) return FEAHIP_EHIP;
+    if ((rc = coarse_enq_prolong_add(c, zz))) return rc;
+    z[k++] = zz;
   }
   return FEAHIP_OK;
 }

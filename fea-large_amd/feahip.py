@@ -106,7 +106,12 @@ ABI = {
     "feahip_apply_preconditioner": [C.c_void_p, _dp, _dp],
     "feahip_amg_info": [C.c_void_p, C.POINTER(C.c_longlong), _dp],
     "feahip_amg_level": [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), _dp, _ip, _ip, _dp, _ip, _dp, _ip],
+    "feahip_group_apply_preconditioner": [C.POINTER(C.c_void_p), C.c_int, C.POINTER(_dp), C.POINTER(_dp)],
+    "feahip_coarse_info": [C.c_void_p, C.POINTER(C.c_longlong), _ip, _dp],
+    "feahip_coarse_matrix": [C.c_void_p, _dp],
+    "feahip_host_coarse_aggregates": [C.c_int, C.c_int, _ip],
 }
+COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
 AMG_INFO_KEYS = ("levels", "gamma", "gamma_from", "gamma_until", "coarse_sweeps", "fine_bits", "coarse_f32", "fused_post",
                  "tail_from", "tail_entry", "tail_cop", "tail_lds_levels", "row0", "row1", "tail_blob")
 TAIL_ENTRY = {0: None, 1: "lds", 2: "ell", 3: "l2"}
@@ -511,7 +516,30 @@ class FeaSolver:
 
     # ---- tuning / measurement ------------------------------------------
     def set_preconditioner(self, kind):
+        """0 block-Jacobi, 1 multigrid, 2 multigrid plus a coarse level across the ranks (feahip_set_preconditioner)."""
         self._chk(self._lib.feahip_set_preconditioner(self._ctx, kind))
+        self.preconditioner = kind
+
+    def coarse_info(self):
+        """The coarse level of preconditioner 2 for the current K (feahip_coarse_info): dict of COARSE_INFO_KEYS plus
+        agg [owned rows] (global aggregate of every owned row, in the context's row order) and centroids
+        [aggregates][3] of all aggregates."""
+        o = (C.c_longlong * 8)()
+        self._chk(self._lib.feahip_coarse_info(self._ctx, o, None, None))
+        d = dict(zip(COARSE_INFO_KEYS, [int(v) for v in o]))
+        agg = np.zeros(max(d["owned_rows"], 1), dtype=np.int32)
+        cent = np.zeros((max(d["aggregates"], 1), 3))
+        self._chk(self._lib.feahip_coarse_info(self._ctx, o, _i(agg), _d(cent)))
+        d.update(zip(COARSE_INFO_KEYS, [int(v) for v in o]))
+        d["agg"], d["centroids"] = agg[:d["owned_rows"]], cent[:d["aggregates"]]
+        return d
+
+    def coarse_matrix(self):
+        """The all-reduced Phi' K Phi of preconditioner 2 for the current K, [unknowns][unknowns]."""
+        n = self.coarse_info()["unknowns"]
+        A = np.zeros((n, n))
+        self._chk(self._lib.feahip_coarse_matrix(self._ctx, _d(A)))
+        return A
 
     def apply_preconditioner(self, r):
         """z = M^-1 r with the preconditioner the next PCG solve would use (set_preconditioner), for the current K."""
@@ -716,6 +744,18 @@ def host_assembly_digest(elements, n_nodes, rank=0, nranks=1):
     if rc:
         raise FeaHipError(f"feahip_host_assembly_digest failed ({rc})")
     return h, (int(rows[0]), int(rows[1]))
+
+
+def host_coarse_aggregates(n_owned, m):
+    """Host only: the cuts of preconditioner 2's aggregates over n_owned rows under the cap m
+    (feahip_host_coarse_aggregates): first rows [m_r + 1], counted from the rank's first owned row."""
+    lib = load_library()
+    mr = lib.feahip_host_coarse_aggregates(n_owned, m, None)
+    if mr < 1:
+        raise FeaHipError(f"feahip_host_coarse_aggregates failed ({mr})")
+    first = np.zeros(mr + 1, dtype=np.int32)
+    lib.feahip_host_coarse_aggregates(n_owned, m, _i(first))
+    return first
 
 
 def comm_unique_id():
@@ -1007,10 +1047,19 @@ class FeaGroup:
         return [getattr(r, name)(*args) for r in self.ranks]
 
     def apply_preconditioner(self, r):
-        """Every rank's z = M^-1 r on its own rows, stitched together: the block-diagonal preconditioner the group's PCG
-        uses.  r in the deck's node ids."""
+        """Every rank's z = M^-1 r on its own rows, stitched together: the preconditioner the group's PCG uses
+        (block-diagonal over the ranks for kinds 0 and 1).  r in the deck's node ids."""
         r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 3)
         z = np.zeros_like(r)
+        if all(getattr(rk, "preconditioner", 0) == 2 for rk in self.ranks):
+            # the coarse level spans the ranks: one collective application (feahip_group_apply_preconditioner)
+            rs = [np.ascontiguousarray(r[rk.node_global] if self.rank_contexts else r).ravel() for rk in self.ranks]
+            zs = [np.zeros(rk.ndof) for rk in self.ranks]
+            rp, zp = (_dp * self.n)(*[_d(v) for v in rs]), (_dp * self.n)(*[_d(v) for v in zs])
+            self._chk(self._lib.feahip_group_apply_preconditioner(self._arr, self.n, rp, zp))
+            for rk, nd, zr in zip(self.ranks, self.nodes, zs):
+                z[nd] += zr.reshape(-1, 3)[:rk.n_own] if self.rank_contexts else zr.reshape(-1, 3)[nd]
+            return z.ravel()
         for rk, nd in zip(self.ranks, self.nodes):
             if self.rank_contexts:
                 zr = rk.apply_preconditioner(r[rk.node_global]).reshape(-1, 3)

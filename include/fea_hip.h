@@ -335,6 +335,13 @@ int feahip_group_solve(feahip_ctx **ctxs, int n, int load_increments, int max_ne
                        int modified_newton, double desired_tolerance, int solver_type,
                        double solver_tolerance, int solver_max_iter, double *tol_log,
                        int tol_log_cap, int *its_log, int *steps_done);
+/* z = M^-1 r on every rank of the group at once, with the preconditioner the
+ * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
+ * feahip_apply_preconditioner takes them (the caller's node ids of context k;
+ * z[k] covers rank k's rows, 0 elsewhere).  Under preconditioner 2 the operator
+ * spans the ranks and this is how it is applied without a solve.             */
+int feahip_group_apply_preconditioner(feahip_ctx **ctxs, int n, const double *const *r,
+                                      double *const *z);
 
 /* Host-only (no device): the halo plan of one rank from the element->node
  * map, in the numbering it is given (a context plans in library ids: pass
@@ -456,9 +463,26 @@ int feahip_set_assembly(feahip_ctx *ctx, int strategy);
  * blocks (default), 1 = aggregation multigrid (rigid-body modes of every
  * aggregate, W-cycle).  In a sharded solve every rank builds the hierarchy of
  * its own diagonal block and the preconditioner is block-Jacobi over the ranks
- * with a W-cycle inside each: no communication beyond the CG's own.  Either
- * way the solve runs to the requested residual, so the solution is the same
- * to that tolerance.                                                          */
+ * with a W-cycle inside each: no communication beyond the CG's own.
+ * 2 = kind 1 plus one coarse level ACROSS the ranks, added to it:
+ *     M2^-1 r = M1^-1 r + Phi (Phi' K Phi)^-1 Phi' r
+ * with K the matrix the PCG sees.  Every rank cuts its owned rows, in its own
+ * row order, into m_r = min(m, max(1, n_r / 64)) contiguous runs (aggregates;
+ * m = clamp(128 / nranks, 1, 16), or the environment's FEAHIP_COARSE_AGGS, a
+ * measurement knob); Phi holds the six rigid-body modes of every aggregate
+ * about the mean X0 of its nodes, prescribed dofs included.  At most 128
+ * aggregates, 768 coarse unknowns.  Phi' K Phi is formed and inverted in double
+ * whenever K changed.  This kind DOES communicate inside the preconditioner:
+ * one vector all-reduce of the coarse matrix per numeric setup, and one of at
+ * most 768 doubles per CG iteration (on the communication stream, beside the
+ * cycle) -- the single-reduction loop then carries two all-reduces per
+ * iteration.  A solve returns FEAHIP_ESTATE, feahip_last_error naming the
+ * aggregate, when Phi' K Phi has a pivot that is not positive (below 1e-12 of
+ * its diagonal entry): an unconstrained body, a degenerate aggregate.  On a
+ * context without a transport kind 2 is the same formula with one rank.  Set
+ * the same kind on every rank.
+ * Whatever the kind, the solve runs to the requested residual, so the solution
+ * is the same to that tolerance.                                              */
 int feahip_set_preconditioner(feahip_ctx *ctx, int kind);
 /* z = M^-1 r with the preconditioner a PCG solve (feahip_solve_slae with
  * PCG_ILU) would use now, for the current K: kind 0 the 3x3 block-Jacobi,
@@ -467,9 +491,34 @@ int feahip_set_preconditioner(feahip_ctx *ctx, int kind);
  * rank's rows and is 0 elsewhere.  FEAHIP_ESTATE before the first stiffness
  * assembly.  Touches only scratch that a solve overwrites at its start.  A
  * solve's multigrid cycles (and this) return FEAHIP_EHIP if the tail kernel
- * of the small levels fails to launch.                                       */
+ * of the small levels fails to launch.
+ * Under kind 2 on a context with an RCCL transport (feahip_comm_init) this
+ * call is COLLECTIVE: every rank makes it, each with its own r.  A member of
+ * an in-process group is refused (FEAHIP_ESTATE): one call cannot stand for
+ * all ranks there, feahip_group_apply_preconditioner does.                   */
 int feahip_apply_preconditioner(feahip_ctx *ctx, const double *r, double *z);
-/* Read-only view of the multigrid hierarchy (preconditioner 1) for the
+/* The coarse level of preconditioner 2 as the next solve would use it, prepared
+ * here for the current K (collective like a solve: all ranks of an RCCL run
+ * call it; an in-process group is prepared as a whole from any member).
+ * out8: 0 aggregates over all ranks, 1 this rank's first global aggregate id,
+ * 2 its aggregates, 3 coarse unknowns (6 per aggregate), 4 numeric epoch (the
+ * number of numeric setups so far: it advances only when K changed), 5 owned
+ * rows, 6 the cap m, 7 (row aggregate, column aggregate) pairs of its rows.
+ * With non-null arrays (sized by a first call): agg_of_owned_row[owned rows]
+ * the global aggregate of every owned row in the context's row order (library
+ * ids [row0, row1); local ids [0, n_own) of a rank context), and
+ * centroids[aggregates][3] of ALL aggregates.  FEAHIP_ESTATE unless kind 2 is
+ * set (on every rank) and K was assembled.                                   */
+int feahip_coarse_info(feahip_ctx *ctx, long long *out8, int *agg_of_owned_row, double *centroids);
+/* A[n][n], n = out8[3]: the all-reduced Phi' K Phi, row-major, unknown 6 A + k
+ * = mode k of aggregate A (k < 3 translation, else rotation about axis k - 3). */
+int feahip_coarse_matrix(feahip_ctx *ctx, double *A);
+/* Host-only (no device): the cut rule.  Returns m_r = min(m, max(1, n_owned / 64))
+ * (negative on a bad argument) and, when non-null, first_row_of_aggregate[m_r + 1]
+ * = floor(j n_owned / m_r): aggregate j is the owned rows [first[j], first[j + 1]),
+ * counted from the rank's first owned row.                                    */
+int feahip_host_coarse_aggregates(int n_owned, int m, int *first_row_of_aggregate);
+/* Read-only view of the multigrid hierarchy (preconditioner 1 or 2) for the
  * current K; prepared here if K changed since the last solve.
  * out16: 0 levels, 1 gamma, 2 gamma_from, 3 gamma_until, 4 coarse_sweeps,
  * 5 fine_bits (level-0 smoother matrix: 16 bfloat16, 32 float, 64 K),
@@ -479,7 +528,7 @@ int feahip_apply_preconditioner(feahip_ctx *ctx, const double *r, double *z);
  * 10 the coarsest level as one dense operator, 11 bit l set: level l's
  * matrix sits in the tail's LDS, 12/13 the rank's rows [row0, row1) in
  * library ids, 14 the tail's packed blob in use.  *over: the over-correction.
- * FEAHIP_ESTATE unless preconditioner 1 is set and K was assembled.          */
+ * FEAHIP_ESTATE unless preconditioner 1 or 2 is set and K was assembled.     */
 int feahip_amg_info(feahip_ctx *ctx, long long *out16, double *over);
 /* One level.  counts[4]: N block rows, nnzb blocks, Nc block rows of the
  * next level (0 on the coarsest), bits of the stored matrix (level 0: the
