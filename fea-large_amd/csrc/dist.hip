@@ -248,3 +248,197 @@ int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newto
   for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
   return FEAHIP_OK;
 }
+
+// ---- arc-length continuation on the surface loads (feahip_solve_arclength) -------
+// Crisfield's cylindrical arc length, one unsharded context.  The linear algebra of a corrector iteration is ONE
+// two-column solve K [du_R, du_F] = [R, F] (kernels_solve2.hip) and one fused reduction over Du, du_R, du_F, R.
+#define ARC_SUMS 7
+// partial sums, block b: part[s * FEA_RED_BLOCKS + b] of
+//   0 du_F.du_F   1 Du.du_F   2 du_R.du_F   3 |Du + du_R|^2   4 Du.(Du + du_R)   5 du_R.R   6 du_F.R
+// (a, the two parts of b, c + dl^2, the root choice, and the two parts of the energy <du, R>)
+__global__ __launch_bounds__(256)
+void k_arc_dots_partial(int n, const double *Du, const double *dR, const double *dF, const double *R, double *part)
+{
+  __shared__ double sh[ARC_SUMS][4];
+  double s[ARC_SUMS] = {0, 0, 0, 0, 0, 0, 0};
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double u = Du[i], r = dR[i], f = dF[i], g = R[i], w = u + r;
+    s[0] += f * f; s[1] += u * f; s[2] += r * f; s[3] += w * w; s[4] += u * w; s[5] += r * g; s[6] += f * g;
+  }
+#pragma unroll
+  for (int k = 0; k < ARC_SUMS; ++k) {
+    double v = s[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < ARC_SUMS) {
+    const double *q = sh[threadIdx.x];
+    part[(size_t)threadIdx.x * FEA_RED_BLOCKS + blockIdx.x] = q[0] + q[1] + q[2] + q[3];
+  }
+}
+// out[s] = sum of part[s * FEA_RED_BLOCKS .. + nparts) for s < nsums: one block, fixed order
+__global__ __launch_bounds__(256)
+void k_arc_dots_final(int nparts, int nsums, const double *part, double *out)
+{
+  __shared__ double sh[4];
+  for (int s = 0; s < nsums; ++s) {
+    double v = 0;
+    for (int i = threadIdx.x; i < nparts; i += 256) v += part[(size_t)s * FEA_RED_BLOCKS + i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) out[s] = sh[0] + sh[1] + sh[2] + sh[3];
+    __syncthreads();
+  }
+}
+__global__ void k_arc_scale(int n, double s, const double *v, double *Du)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) Du[i] = s * v[i];
+}
+__global__ void k_arc_update(int n, double dlam, const double *dR, const double *dF, double *Du)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) Du[i] += dR[i] + dlam * dF[i];
+}
+// x = x_n + Du; x and x_n are [N][4]
+__global__ void k_arc_nodes(int n, const double *xn, const double *Du, double *x)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[(size_t)(i / 3) * 4 + i % 3] = xn[(size_t)(i / 3) * 4 + i % 3] + Du[i];
+}
+__global__ void k_arc_mask(int n, const uint8_t *mask, double *f)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && mask[i]) f[i] = 0.0;
+}
+
+namespace {
+struct ArcBuffers {
+  double *xn = nullptr, *Du = nullptr, *Dprev = nullptr, *v = nullptr, *F = nullptr;
+  ~ArcBuffers() { dev_free({xn, Du, Dprev, v, F}); }
+};
+}
+
+// F(x) at load factor 1 into d_F, zero at the prescribed dofs: the surface kernels with another destination and factor
+static int arc_external_forces(feahip_ctx *c, double *d_F)
+{
+  const double lf = c->load_factor;
+  FEA_HIP_CHECK(c, hipMemsetAsync(d_F, 0, sizeof(double) * (size_t)c->ndof, c->stream));
+  c->load_factor = 1.0;
+  const int rc = launch_surface_loads(c, d_F);
+  c->load_factor = lf;
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_arc_mask, dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof, c->d_dofmask, d_F);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+// the seven sums of a corrector iteration (or, with R = dR = dF = v and Du = Dprev, v.v in [0] and Dprev.v in [1])
+static int arc_dots(feahip_ctx *c, const double *Du, const double *dR, const double *dF, const double *R, double *out)
+{
+  int g = (c->ndof + 255) / 256;
+  g = g < FEA_RED_BLOCKS ? g : FEA_RED_BLOCKS;
+  hipLaunchKernelGGL(k_arc_dots_partial, dim3(g), dim3(256), 0, c->stream, c->ndof, Du, dR, dF, R, c->d2_part);
+  hipLaunchKernelGGL(k_arc_dots_final, dim3(1), dim3(256), 0, c->stream, g, ARC_SUMS, c->d2_part, c->d2_scal);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  FEA_HIP_CHECK(c, hipMemcpyAsync(out, c->d2_scal, sizeof(double) * ARC_SUMS, hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+int arclength_solve(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
+                    int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log, double *tol_log,
+                    int log_cap, int *its_log, int *steps_done)
+{
+  int rc, nlog = 0, step = 0, n_bad = 0;
+  const int n = c->ndof;
+  const size_t vb = sizeof(double) * (size_t)n, xb = sizeof(double) * 4 * (size_t)c->N;
+  const dim3 gn((n + 255) / 256), b256(256);
+  ArcBuffers B;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&B.xn, xb));
+  for (double **p : {&B.Du, &B.Dprev, &B.v, &B.F}) {
+    FEA_HIP_CHECK(c, hipMalloc((void **)p, vb));
+    FEA_HIP_CHECK(c, hipMemsetAsync(*p, 0, vb, c->stream));
+  }
+  double lambda_n = c->load_factor, dl = 0.0, s[ARC_SUMS];
+  FEA_HIP_CHECK(c, hipMemcpyAsync(B.xn, c->d_x, xb, hipMemcpyDeviceToDevice, c->stream));
+  auto restore = [&]() -> int {
+    c->state_valid = false;
+    c->load_factor = lambda_n;
+    FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_x, B.xn, xb, hipMemcpyDeviceToDevice, c->stream));
+    FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return FEAHIP_OK;
+  };
+  int result = FEAHIP_OK;
+  for (; step < max_steps && lambda_n < lambda_max; ++step) {
+    // predictor: K v = F at the converged point
+    if ((rc = feahip_create_stiffness(c)) || (rc = feahip_update_state(c, &n_bad))) return rc;
+    if (n_bad) { c->err = "solve_arclength: bad Jacobians at a converged point"; result = FEAHIP_ENOTCONVERGED; break; }
+    if ((rc = feahip_apply_prescribed_bc(c, 0.0)) || (rc = arc_external_forces(c, B.F))) return rc;
+    FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_f, B.F, vb, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = solve_pcg(c, solver_type, solver_tolerance, solver_max_iter, nullptr, nullptr))) return rc;
+    FEA_HIP_CHECK(c, hipMemcpyAsync(B.v, c->d_u, vb, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = arc_dots(c, B.Dprev, B.v, B.v, B.v, s))) return rc;
+    const double vnorm = sqrt(s[0]);
+    if (!(vnorm > 0.0)) { c->err = "solve_arclength: the loads move nothing (K v = F gave v = 0)"; result = FEAHIP_ENOTCONVERGED; break; }
+    const double sgn = (step > 0 && s[1] < 0.0) ? -1.0 : 1.0;
+    if (step == 0) dl = vnorm;
+    bool converged = false;
+    int it = 0;
+    for (int cut = 0; cut <= 8 && !converged; ++cut) {
+      if (cut > 0) dl *= 0.5;
+      double Dlambda = sgn * dl / vnorm;
+      hipLaunchKernelGGL(k_arc_scale, gn, b256, 0, c->stream, n, Dlambda, B.v, B.Du);
+      bool failed = false;
+      for (it = 1; it <= max_newton && !failed; ++it) {
+        c->state_valid = false;
+        c->load_factor = lambda_n + Dlambda;
+        hipLaunchKernelGGL(k_arc_nodes, gn, b256, 0, c->stream, n, B.xn, B.Du, c->d_x);
+        if ((rc = feahip_create_stiffness_and_residual(c)) || (rc = feahip_update_state(c, &n_bad))) return rc;
+        if (n_bad) { failed = true; break; }
+        if ((rc = feahip_apply_prescribed_bc(c, 0.0)) || (rc = arc_external_forces(c, B.F))) return rc;
+        if ((rc = launch_interleave(c, c->d_f, B.F, c->d2_f))) return rc;
+        rc = solve_pcg2(c, solver_type, solver_tolerance, solver_max_iter, nullptr, nullptr);
+        if (rc == FEAHIP_ENOTCONVERGED) { failed = true; break; }
+        if (rc) return rc;
+        if ((rc = arc_dots(c, B.Du, c->d_u, c->d_u2, c->d_f, s))) return rc;
+        const double qa = s[0], qb = 2.0 * (s[1] + s[2]), qc = s[3] - dl * dl;
+        const double disc = qb * qb - 4.0 * qa * qc;
+        if (!(qa > 0.0) || !(disc >= 0.0)) { failed = true; break; }
+        // both roots without cancellation; the one that keeps Du pointing forward: larger Du.(Du + du_R + dlam du_F)
+        const double q = -0.5 * (qb + (qb >= 0.0 ? 1.0 : -1.0) * sqrt(disc));
+        const double r1 = q / qa, r2 = q != 0.0 ? qc / q : r1;
+        const double dlam = (s[4] + r1 * s[1] >= s[4] + r2 * s[1]) ? r1 : r2;
+        const double tolerance = s[5] + dlam * s[6];
+        if (tol_log && nlog < log_cap) tol_log[nlog] = tolerance;
+        nlog++;
+        hipLaunchKernelGGL(k_arc_update, gn, b256, 0, c->stream, n, dlam, c->d_u, c->d_u2, B.Du);
+        Dlambda += dlam;
+        if (!(tolerance == tolerance)) { failed = true; break; }
+        if (fabs(tolerance) <= desired_tolerance) { converged = true; break; }
+      }
+      if (converged) {
+        hipLaunchKernelGGL(k_arc_nodes, gn, b256, 0, c->stream, n, B.xn, B.Du, c->d_x);
+        FEA_HIP_CHECK(c, hipMemcpyAsync(B.xn, c->d_x, xb, hipMemcpyDeviceToDevice, c->stream));
+        FEA_HIP_CHECK(c, hipMemcpyAsync(B.Dprev, B.Du, vb, hipMemcpyDeviceToDevice, c->stream));
+        lambda_n += Dlambda;
+      } else if ((rc = restore())) return rc;
+    }
+    if (!converged) {
+      c->err = "solve_arclength: step " + std::to_string(step) + " did not converge after 8 halvings of the arc length";
+      result = FEAHIP_ENOTCONVERGED;
+      break;
+    }
+    if (lambda_log) lambda_log[step] = lambda_n;
+    if (its_log) its_log[step] = it;
+  }
+  if (steps_done) *steps_done = step;
+  const std::string why = c->err;
+  if ((rc = restore())) return rc;
+  if (result != FEAHIP_OK) c->err = why;
+  return result;
+}

@@ -478,6 +478,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   if (c->ev_unpacked) (void)hipEventDestroy(c->ev_unpacked);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   if (c->tr && c->owns_tr) delete c->tr;
+  release_solve2(c);
   amg_destroy(c);
   coarse_destroy(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -882,6 +883,65 @@ extern "C" int feahip_get_forces(feahip_ctx *c, double *f) { CTX_GUARD(c); retur
 extern "C" int feahip_get_solution(feahip_ctx *c, double *u) { CTX_GUARD(c); return get_node_vec(c, c->d_u, u); }
 extern "C" int feahip_set_forces(feahip_ctx *c, const double *f) { CTX_GUARD(c); return set_node_vec(c, c->d_f, f); }
 
+// ---- two-column solve (kernels_solve2.hip) ---------------------------------
+static int solve2_ready(feahip_ctx *c, const char *who)
+{
+  int rc;
+  if ((rc = solve2_refused(c, who))) return rc;
+  if (!c->k_valid) { c->err = std::string(who) + ": no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+  return ensure_solve2(c);
+}
+
+extern "C" int feahip_solve_slae2(feahip_ctx *c, int type, double tol, int max_iter, const double *f2, int iters[2], double resid[2])
+{
+  CTX_GUARD(c);
+  if (type < FEAHIP_CG || type > FEAHIP_CHOLESKY) { c->err = "unknown solver type"; return FEAHIP_EINVAL; }
+  if (max_iter <= 0) { c->err = "max_iterations must be positive"; return FEAHIP_EINVAL; }
+  if (!f2) { c->err = "solve_slae2: null second right-hand side"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = solve2_ready(c, "solve_slae2"))) return rc;
+  if ((rc = set_node_vec(c, c->d_q, f2))) return rc;             // (q is scratch of any solve)
+  if ((rc = launch_interleave(c, c->d_f, c->d_q, c->d2_f))) return rc;
+  return solve_pcg2(c, type, tol, max_iter, iters, resid);
+}
+
+extern "C" int feahip_get_solution2(feahip_ctx *c, double *u2)
+{
+  CTX_GUARD(c);
+  if (!c->d_u2) { c->err = "get_solution2 before solve_slae2"; return FEAHIP_ESTATE; }
+  return get_node_vec(c, c->d_u2, u2);
+}
+
+extern "C" int feahip_spmv2(feahip_ctx *c, const double *x2, double *y2)
+{
+  CTX_GUARD(c);
+  if (!x2 || !y2) return FEAHIP_EINVAL;
+  int rc;
+  if ((rc = solve2_ready(c, "spmv2"))) return rc;
+  if ((rc = set_node_vec(c, c->d_p, x2)) || (rc = set_node_vec(c, c->d_q, x2 + (size_t)c->ndof))) return rc;
+  if ((rc = launch_interleave(c, c->d_p, c->d_q, c->d2_p))) return rc;
+  if ((rc = launch_spmv2(c, c->d2_p, c->d2_q))) return rc;
+  if ((rc = launch_deinterleave(c, c->d2_q, c->d_p, c->d_q))) return rc;
+  if ((rc = get_node_vec(c, c->d_p, y2))) return rc;
+  return get_node_vec(c, c->d_q, y2 + (size_t)c->ndof);
+}
+
+extern "C" int feahip_solve_arclength(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
+                                      int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log,
+                                      double *tol_log, int log_cap, int *its_log, int *steps_done)
+{
+  CTX_GUARD(c);
+  if (steps_done) *steps_done = 0;
+  if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "unknown solver type"; return FEAHIP_EINVAL; }
+  if (max_steps <= 0 || max_newton <= 0 || solver_max_iter <= 0) { c->err = "solve_arclength: max_steps, max_newton and solver_max_iter must be positive"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = solve2_refused(c, "solve_arclength"))) return rc;
+  if (c->surf.nfaces == 0) { c->err = "solve_arclength: no surface loads on this context"; return FEAHIP_ESTATE; }
+  if ((rc = ensure_solve2(c))) return rc;
+  return arclength_solve(c, lambda_max, max_steps, max_newton, desired_tolerance, solver_type, solver_tolerance,
+                         solver_max_iter, lambda_log, tol_log, log_cap, its_log, steps_done);
+}
+
 extern "C" int feahip_node_numbering(feahip_ctx *c, int *library_id_of_node)
 {
   if (!c || !library_id_of_node) return FEAHIP_EINVAL;
@@ -1153,6 +1213,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
   CTX_GUARD(c);
   if (!avg_ms || iters <= 0 || warmup < 0) return FEAHIP_EINVAL;
   if (what == 4) return time_pcg_iteration(c, warmup, iters, avg_ms);
+  if (what == 6 || what == 7) {
+    const int rk = solve2_ready(c, what == 6 ? "time_kernel(6)" : "time_kernel(7)");
+    if (rk) return rk;
+    if (what == 7) return time_pcg2_iteration(c, warmup, iters, avg_ms);
+  }
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   auto one = [&]() -> int {
     switch (what) {
@@ -1161,6 +1226,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 2: return launch_assemble(c, false, true);
     case 3: return launch_spmv(c, c->d_p, c->d_q);
     case 5: return launch_surface_loads(c, c->d_f);
+    case 6: return launch_spmv2(c, c->d2_p, c->d2_q);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   };

@@ -506,6 +506,13 @@ struct feahip_ctx {
   // lambda to load_factor (one increment of the loads per step, as of the prescribed displacements)
   SurfaceLoads surf;
   double load_factor = 0;
+  // two-column solve (kernels_solve2.hip), allocated on first use: paired vectors [3N][2] (the two columns interleaved
+  // per dof), the second column's solution as a plain vector, and the columns' partial sums, scalars and flags
+  double *d2_f = nullptr, *d2_u = nullptr, *d2_r = nullptr, *d2_p = nullptr, *d2_q = nullptr;
+  double *d_u2 = nullptr;      // [3N]
+  double *d2_part = nullptr;   // 8 x FEA_RED_BLOCKS
+  double *d2_scal = nullptr;   // 2 x 8
+  int *d2_flag = nullptr;      // [2]
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -541,6 +548,20 @@ int precond_apply(feahip_ctx *c, const double *r, const double **z);   // kernel
 int solve_pcg(feahip_ctx *c, int type, double tol, int max_iter, int *iters,
               double *resid);
 int time_pcg_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);
+void enq_precond_blockjacobi(feahip_ctx *c);                            // kernels_solve.hip
+// kernels_solve2.hip -- K [u, u2] = [f, f2] over one read of K per iteration; paired vectors are [3N][2]
+int ensure_solve2(feahip_ctx *c);
+void release_solve2(feahip_ctx *c);
+int solve2_refused(feahip_ctx *c, const char *who);                     // FEAHIP_EINVAL and the reason in c->err, or OK
+int launch_spmv2(feahip_ctx *c, const double *d_x2, double *d_y2);
+int launch_interleave(feahip_ctx *c, const double *a, const double *b, double *out2);
+int launch_deinterleave(feahip_ctx *c, const double *in2, double *a, double *b);
+int solve_pcg2(feahip_ctx *c, int type, double tol, int max_iter, int *iters, double *resid);   // d2_f -> d_u, d_u2
+int time_pcg2_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);
+// dist.hip -- Crisfield's cylindrical arc length on the surface loads (one unsharded context)
+int arclength_solve(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
+                    int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log, double *tol_log,
+                    int log_cap, int *its_log, int *steps_done);
 
 // renumber.cpp -- locality numbering of the nodes; false = no basis for one (identity returned)
 bool locality_numbering(int N, int E, int npe, const int *conn, const double *X, std::vector<int> &new_of_old);

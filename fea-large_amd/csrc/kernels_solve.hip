@@ -789,6 +789,9 @@ static void enq_precond(feahip_ctx *c, int mode)
                      own0(c), own1(c), c->d_diag, c->d_K, mode, c->d_minv);
 }
 
+// the inverse diagonal blocks of the current K into d_minv (the two-column solve, kernels_solve2.hip)
+void enq_precond_blockjacobi(feahip_ctx *c) { enq_precond(c, 1); }
+
 // z = M^-1 r on the rank's rows with the preconditioner a PCG solve would use now (feahip_apply_preconditioner); r, z
 // device vectors in library ids.  Block-Jacobi leaves z in q, the multigrid where its cycle ends.  Either way only the
 // scratch a solve overwrites at its start is touched, and the multigrid is prepared exactly as enq_cg_start does.

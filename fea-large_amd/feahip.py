@@ -18,6 +18,7 @@ HOST_LIB_PATH = os.path.join(_HERE, "libfeahost.so")
 
 MODEL_A5, MODEL_COMPRESSIBLE_NEOHOOKEAN = 0, 1
 CG, PCG_ILU, CHOLESKY = 0, 1, 2
+EINVAL, ESTATE, ENOTCONVERGED = -1, -5, -6              # FEAHIP_E* of include/fea_hip.h
 ASM_AUTO, ASM_ROWOWNER, ASM_ATOMIC, ASM_PATCH, ASM_STAGED, ASM_PAIRED, ASM_PIPELINED, ASM_SHARED, ASM_GATHER = 0, 1, 2, 3, 4, 5, 6, 7, 8
 TETRAHEDRA10, TETRAHEDRA4, HEXAHEDRA8 = 0, 1, 2
 LOAD_PRESSURE, LOAD_TRACTION = 0, 1
@@ -41,6 +42,11 @@ ABI = {
     "feahip_restore_stiffness": [C.c_void_p],
     "feahip_apply_prescribed_bc": [C.c_void_p, C.c_double],
     "feahip_solve_slae": [C.c_void_p, C.c_int, C.c_double, C.c_int, _ip, _dp],
+    "feahip_solve_slae2": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp],
+    "feahip_get_solution2": [C.c_void_p, _dp],
+    "feahip_spmv2": [C.c_void_p, _dp, _dp],
+    "feahip_solve_arclength": [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _dp, _dp,
+                               C.c_int, _ip, _ip],
     "feahip_energy": [C.c_void_p, _dp],
     "feahip_update_nodes_with_solution": [C.c_void_p, _dp],
     "feahip_solve": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _dp,
@@ -239,6 +245,8 @@ class Deck:
         self.max_newton_count = kw.get("max_newton_count", 20)
         self.modified_newton = kw.get("modified_newton", True)
         self.gauss_nodes_count = kw.get("gauss_nodes_count", 5)
+        self.linesearch_max = kw.get("linesearch_max", 0)
+        self.arclength_max = kw.get("arclength_max", 0)       # > 0 with surface loads: feasolver_hip follows the path
         self.nodes = np.ascontiguousarray(kw["nodes"], dtype=np.float64)
         self.elements = np.ascontiguousarray(kw["elements"], dtype=np.int32)
         self.nodes_per_element = self.elements.shape[1]
@@ -292,6 +300,7 @@ class Deck:
         fd.load_increments_count, fd.desired_tolerance = self.load_increments_count, self.desired_tolerance
         fd.max_newton_count, fd.modified_newton = self.max_newton_count, int(self.modified_newton)
         fd.nodes_per_element, fd.gauss_nodes_count = self.nodes_per_element, self.gauss_nodes_count
+        fd.linesearch_max, fd.arclength_max = int(self.linesearch_max), int(self.arclength_max)
         fd.nodes_count, fd.nodes = len(self.nodes), _d(self.nodes)
         fd.elements_count, fd.elements = len(self.elements), _i(self.elements)
         fd.prescribed_nodes_count = len(self.presc_node)
@@ -389,6 +398,26 @@ class FeaSolver:
             d.solver_max_iter if max_iterations is None else max_iterations, C.byref(it), C.byref(res)))
         return it.value, res.value
 
+    def solve_slae2(self, f2, solver_type=None, tolerance=None, max_iterations=None):
+        """K [u, u2] = [f, f2] over one read of K per iteration (feahip_solve_slae2): (iters[2], resid[2]); the
+        columns are read with solution() and solution2()."""
+        f2 = np.ascontiguousarray(f2, dtype=np.float64)
+        assert f2.shape == (self.ndof,)
+        it, res = np.zeros(2, dtype=np.int32), np.zeros(2)
+        d = self.deck
+        self._chk(self._lib.feahip_solve_slae2(
+            self._ctx, d.solver_type if solver_type is None else solver_type,
+            d.solver_tolerance if tolerance is None else tolerance,
+            d.solver_max_iter if max_iterations is None else max_iterations, _d(f2), _i(it), _d(res)))
+        return it, res
+
+    def get_solution2(self):
+        u = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_get_solution2(self._ctx, _d(u)))
+        return u
+
+    solution2 = get_solution2
+
     def energy(self):
         t = C.c_double(0)
         self._chk(self._lib.feahip_energy(self._ctx, C.byref(t)))
@@ -421,6 +450,28 @@ class FeaSolver:
             _d(tol_log), cap, _i(its), C.byref(done)))
         n = int(its[:max(done.value, 0) + (1 if done.value < li else 0)].sum())
         return done.value, its, tol_log[:n]
+
+    def solve_arclength(self, lambda_max=None, max_steps=None, max_newton=None, desired_tolerance=None,
+                        solver_type=None, solver_tolerance=None, solver_max_iter=None, check=True):
+        """Arc-length continuation on the surface loads (feahip_solve_arclength).  Returns (steps done, lambda_log,
+        its_log, tol_log, rc); with check=False a FEAHIP_ENOTCONVERGED comes back as rc instead of raising."""
+        d = self.deck
+        lmax = float(d.load_increments_count if lambda_max is None else lambda_max)
+        ms = int(getattr(d, "arclength_max", 0) if max_steps is None else max_steps)
+        mn = d.max_newton_count if max_newton is None else max_newton
+        cap = ms * mn * 9
+        lam, its, tol = np.zeros(max(ms, 1)), np.zeros(max(ms, 1), dtype=np.int32), np.zeros(max(cap, 1))
+        done = C.c_int(0)
+        rc = self._lib.feahip_solve_arclength(
+            self._ctx, lmax, ms, mn, d.desired_tolerance if desired_tolerance is None else desired_tolerance,
+            d.solver_type if solver_type is None else solver_type,
+            d.solver_tolerance if solver_tolerance is None else solver_tolerance,
+            d.solver_max_iter if solver_max_iter is None else solver_max_iter,
+            _d(lam), _d(tol), cap, _i(its), C.byref(done))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        n = max(done.value, 0)
+        return n, lam[:n], its[:n], tol, rc
 
     # ---- surface loads ---------------------------------------------------
     def set_surface_loads(self, faces, kind, values):
@@ -513,6 +564,14 @@ class FeaSolver:
         y = np.zeros(self.ndof)
         self._chk(self._lib.feahip_spmv(self._ctx, _d(x), _d(y)))
         return y
+
+    def spmv2(self, x2):
+        """[y, y2] = K [x, x2] in one pass over K; x2 and the result are [2][3N]."""
+        x2 = np.ascontiguousarray(x2, dtype=np.float64)
+        assert x2.shape == (2, self.ndof)
+        y2 = np.zeros((2, self.ndof))
+        self._chk(self._lib.feahip_spmv2(self._ctx, _d(x2), _d(y2)))
+        return y2
 
     # ---- tuning / measurement ------------------------------------------
     def set_preconditioner(self, kind):

@@ -57,6 +57,31 @@ int fea_solve_with_snapshots(const fea_deck *d, feahip_ctx *ctx, void *logp, fea
   return done;
 }
 
+/* (arc-length :max N) with N > 0 on a deck with surface loads: the path is followed by feahip_solve_arclength,
+ * max_steps = N, lambda_max = load-increments; the final state is the one snapshot */
+int fea_solve_arclength_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *logp, fea_step_snapshot *last)
+{
+  FILE *log = (FILE *)logp;
+  struct snap_sink k;
+  const int n = d->arclength_max;
+  double *lam = (double *)calloc((size_t)n, sizeof *lam);
+  int *its = (int *)calloc((size_t)n, sizeof *its);
+  int done = 0, rc, i;
+  if (!lam || !its) { free(lam); free(its); return FEAHIP_ENOMEM; }
+  rc = feahip_solve_arclength(ctx, (double)d->load_increments_count, n, d->max_newton_count, d->desired_tolerance,
+                              d->solver_type, d->solver_tolerance, d->solver_max_iter, lam, NULL, 0, its, &done);
+  if (log)
+    for (i = 0; i < done; ++i)
+      fprintf(log, "Arc-length step %d finished: load factor %.17g, %d iterations\n", i + 1, lam[i], its[i]);
+  free(lam); free(its);
+  if (rc == FEAHIP_ENOTCONVERGED && log) fprintf(log, "Unable to finish arc-length step %d, exit\n", done + 1);
+  if (rc && rc != FEAHIP_ENOTCONVERGED) return rc;
+  k.steps = last; k.cap = 1; k.S = NULL;
+  rc = keep_snapshot(d, ctx, 0, &k);
+  free(k.S);
+  return rc ? rc : done;
+}
+
 int fea_export_gmsh(const char *filename, const fea_deck *d, const fea_step_snapshot *steps, int nsteps)
 {
   FILE *f = fopen(filename, "w+");

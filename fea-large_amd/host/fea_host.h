@@ -36,7 +36,8 @@ typedef struct fea_deck {
   int load_increments_count;
   double desired_tolerance;
   int max_newton_count;
-  int linesearch_max, arclength_max;   /* parsed, unused (as the reference)  */
+  int linesearch_max, arclength_max;   /* line search: parsed, unused (as the reference); arc length: steps of
+                                        * feahip_solve_arclength when > 0 and the deck has surface loads     */
   int modified_newton;
   /* solution params */
   int nodes_per_element, gauss_nodes_count;
@@ -103,6 +104,13 @@ typedef struct fea_step_snapshot {
 int fea_solve_with_snapshots(const fea_deck *deck, feahip_ctx *ctx, void *log,
                              fea_step_snapshot *steps, int cap);
 void fea_snapshots_free(fea_step_snapshot *steps, int n);
+/* The path-following run of a deck with (arc-length :max N), N > 0, and surface
+ * loads: feahip_solve_arclength with max_steps = N and lambda_max =
+ * load-increments; one log line per converged step ("Arc-length step k
+ * finished: load factor l, n iterations"); *last receives the final state.
+ * Returns the completed steps or a negative FEAHIP_E* code.                  */
+int fea_solve_arclength_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void *log,
+                                      fea_step_snapshot *last);
 
 /* solver_export_tetrahedra10_gmsh (fea_solver.c:1375-1488): Gmsh 2.0 ASCII,
  * nodes with %f, TET10 elements with local nodes 8 and 9 swapped, and per

@@ -4,6 +4,11 @@
  * runs the load-increment / Newton loop through the C ABI, writes
  * "<base>.msh" like initial_data_load + solve() do.
  *
+ * A deck with (arc-length :max N), N > 0, and a (surface-loads ...) section is
+ * followed along its equilibrium path by feahip_solve_arclength (N steps at
+ * most, up to the load factor load-increments); the file then holds the final
+ * state as its one step.  Every other deck takes the reference's loop.
+ *
  * One option the reference does not have, after the deck name:
  *   --multigrid   PCG_ILU / CHOLESKY solves use the aggregation-multigrid
  *                 preconditioner (feahip_set_preconditioner); an error, not a
@@ -21,7 +26,7 @@ int main(int argc, char **argv)
   feahip_ctx *ctx = NULL;
   char err[512], *msh;
   fea_step_snapshot *steps;
-  int done, rc, cap, status = 0;
+  int done, rc, cap, arc, status = 0;
   if (argc < 2) {
     printf("Usage: fea_solve input_data.sexp\n");            /* fea_solver.c:328 */
     return 1;
@@ -45,7 +50,10 @@ int main(int argc, char **argv)
   }
   cap = deck.load_increments_count > 0 ? deck.load_increments_count : 1;
   steps = (fea_step_snapshot *)calloc((size_t)cap, sizeof *steps);
-  done = fea_solve_with_snapshots(&deck, ctx, stdout, steps, deck.load_increments_count);
+  /* (arc-length :max N) with N > 0 and surface loads: path following instead of load control */
+  arc = deck.arclength_max > 0 && deck.surface_faces_count > 0;
+  if (arc) done = fea_solve_arclength_with_snapshot(&deck, ctx, stdout, steps);
+  else done = fea_solve_with_snapshots(&deck, ctx, stdout, steps, deck.load_increments_count);
   if (done < 0) {
     /* a HIP failure or a broken-down linear solve: the reference's error() exits with EXIT_FAILURE
      * (fea_solver.c:57-61); nothing is exported */
@@ -57,7 +65,7 @@ int main(int argc, char **argv)
     fea_export_name(argv[1], msh);
     /* a failed increment leaves current_load_step one lower (fea_solver.c:227), so the
      * reference then drops the last completed step from the file: same here */
-    if (fea_export_gmsh(msh, &deck, steps, done == deck.load_increments_count ? done : done - 1)) {
+    if (fea_export_gmsh(msh, &deck, steps, arc ? 1 : (done == deck.load_increments_count ? done : done - 1))) {
       fprintf(stderr, "could not write %s\n", msh);
       status = 1;
     }

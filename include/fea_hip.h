@@ -133,6 +133,28 @@ int feahip_apply_prescribed_bc(feahip_ctx *ctx, double lambda);
 int feahip_solve_slae(feahip_ctx *ctx, int solver_type, double tolerance,
                       int max_iterations, int *iters, double *resid);
 
+/* K [u, u2] = [f, f2]: two CG / PCG recurrences run in lockstep over ONE read
+ * of the matrix per iteration.  Column 0 is exactly the system
+ * feahip_solve_slae solves (the context's f, start vector u0 = f); column 1 is
+ * f2, [3N] in the caller's dof order, used as given (the caller zeroes the
+ * prescribed dofs), start vector f2.  Each column has its own scalars and its
+ * own stop test; a column that has converged is frozen -- none of its vectors
+ * is written again -- and the solve ends when both have stopped or at
+ * max_iterations.  iters[2] / resid[2] per column (either may be NULL).  The
+ * loop is the two-reduction textbook loop; feahip_set_pcg_variant does not
+ * apply to it.  Preconditioner kind 0 and 1 as feahip_solve_slae (kind 1: one
+ * W-cycle per live column and iteration); CHOLESKY means "to stagnation".
+ * Returns FEAHIP_ESTATE before the first stiffness assembly, FEAHIP_EINVAL
+ * under preconditioner kind 2 and on a context that has a transport, a row
+ * shard, or was created by feahip_create_rank* (feahip_last_error says which),
+ * FEAHIP_ENOTCONVERGED on a breakdown in either column (feahip_last_error
+ * names the column).  Column 0 is read with feahip_get_solution, column 1
+ * with feahip_get_solution2.                                                 */
+int feahip_solve_slae2(feahip_ctx *ctx, int solver_type, double tolerance,
+                       int max_iterations, const double *f2, int iters[2], double resid[2]);
+/* u2 of the last feahip_solve_slae2, [3N] in the caller's dof order.         */
+int feahip_get_solution2(feahip_ctx *ctx, double *u2);
+
 /* cdot(global_forces_vct, global_solution_vct) (fea_solver.c:208-210).     */
 int feahip_energy(feahip_ctx *ctx, double *tolerance);
 
@@ -149,6 +171,36 @@ int feahip_solve(feahip_ctx *ctx, int load_increments, int max_newton,
                  int solver_type, double solver_tolerance, int solver_max_iter,
                  double *tol_log, int tol_log_cap, int *its_log,
                  int *steps_done);
+
+/* Crisfield's cylindrical arc length on the surface loads: follows the
+ * equilibrium path T(x) = lambda F(x) through limit points, where the load
+ * control of feahip_solve stops converging.  F is the surface-load vector at
+ * load factor 1 (constant for dead tractions, evaluated at the current nodes
+ * for follower pressure); prescribed dofs stay where they are.  Every step
+ * starts from a converged (x_n, lambda_n) with radius dl:
+ *   predictor  K v = F; first step dl = |v| (so dlambda = 1: load control's
+ *              first increment), later dlambda = s dl / |v| with
+ *              s = sign(Du_prev . v); Du = dlambda v;
+ *   corrector  (at most max_newton) at x_n + Du, lambda_n + Dlambda: K, R =
+ *              lambda F - T and F; K [du_R, du_F] = [R, F] with the two-column
+ *              solve; dlam from a dlam^2 + b dlam + c = 0, a = du_F.du_F,
+ *              b = 2 (Du + du_R).du_F, c = |Du + du_R|^2 - dl^2, the root with
+ *              the larger Du . (Du + du_R + dlam du_F); du = du_R + dlam du_F,
+ *              Du += du, Dlambda += dlam; converged when |<du, R>| <=
+ *              desired_tolerance (the energy test of fea_solver.c:208-221).
+ * A negative discriminant, max_newton iterations without convergence or an
+ * assembly with bad Jacobians restore (x_n, lambda_n), halve dl and retry, at
+ * most 8 times per step; then FEAHIP_ENOTCONVERGED with *steps_done completed
+ * steps.  dl is never grown.  Stops when lambda >= lambda_max or after
+ * max_steps steps.  lambda_log[max_steps] receives the converged factor of
+ * every step, its_log[max_steps] its corrector iterations, tol_log[log_cap]
+ * <du, R> of every corrector iteration (any may be NULL).  The context's load
+ * factor and nodes are left at the last converged point.  FEAHIP_ESTATE
+ * without loaded faces; refused like feahip_solve_slae2 on sharded contexts.  */
+int feahip_solve_arclength(feahip_ctx *ctx, double lambda_max, int max_steps, int max_newton,
+                           double desired_tolerance, int solver_type, double solver_tolerance,
+                           int solver_max_iter, double *lambda_log, double *tol_log, int log_cap,
+                           int *its_log, int *steps_done);
 
 /* ---- surface loads ------------------------------------------------------ */
 /* What the reference leaves unwritten (solver_create_forces_bc, fea_solver.c:
@@ -455,6 +507,9 @@ int feahip_get_matrix_yale64(feahip_ctx *ctx, long long *offsets, int *indexes,
                              double *values);
 /* y = K x with host vectors (test hook for the SpMV kernel)                 */
 int feahip_spmv(feahip_ctx *ctx, const double *x, double *y);
+/* [y, y2] = K [x, x2] in one pass over K, host vectors [2][3N] (test hook for
+ * the two-vector product of feahip_solve_slae2; refused as that solve is)    */
+int feahip_spmv2(feahip_ctx *ctx, const double *x2, double *y2);
 
 /* ---- tuning and measurement -------------------------------------------- */
 
@@ -573,7 +628,9 @@ int feahip_sync(feahip_ctx *ctx);
  * ones, bracketed by HIP events on the context's own stream; *avg_ms is the
  * mean device time of one launch.  what: 0 stiffness+residual assembly,
  * 1 stiffness only, 2 residual only, 3 SpMV, 4 one PCG iteration, 5 the
- * surface-load kernels alone (refused on a context without loaded faces).   */
+ * surface-load kernels alone (refused on a context without loaded faces),
+ * 6 the two-vector SpMV, 7 one two-column PCG iteration (feahip_solve_slae2;
+ * both refused where that solve is).                                        */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
