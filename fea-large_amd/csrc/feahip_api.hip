@@ -327,7 +327,7 @@ extern "C" int feahip_create_rank(feahip_ctx **out, int device, int rank, int nr
     rc = install_plan(c, rm.plan);                         // rows [0, n_own), peers, halo lists, interior chunk range
   }
   if (rc != FEAHIP_OK) { g_create_error = c->err; feahip_destroy(c); return rc; }
-  c->rank_node_global = rm.node_global; c->rank_elem_global = rm.elem_global; c->rank_n_global = n_nodes;
+  c->rank_node_global = rm.node_global; c->rank_elem_global = rm.elem_global; c->rank_n_global = n_nodes; c->rank_e_global = n_elems;
   *out = c;
   return FEAHIP_OK;
 }
@@ -469,7 +469,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
-                  c->d_dofmask, c->d_F, c->d_S};
+                  c->d_dofmask, c->d_F, c->d_S, c->d_mat, c->d_elem_mat, c->d_f_discard};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (void *p : {(void *)c->d_send_idx, (void *)c->d_recv_idx, (void *)c->d_send_buf, (void *)c->d_recv_buf, (void *)c->d_z, (void *)c->d_w, (void *)c->d_s})
@@ -666,6 +666,61 @@ extern "C" int feahip_get_load_factor(feahip_ctx *c, double *lambda)
 {
   if (!c || !lambda) return FEAHIP_EINVAL;
   *lambda = c->load_factor;
+  return FEAHIP_OK;
+}
+
+// ---- material table (include/fea_hip.h).  Validated in full before anything of the context changes.
+extern "C" int feahip_set_materials(feahip_ctx *c, int n_materials, const double *params, const int *elem_material)
+{
+  CTX_GUARD_NOK(c);
+  auto refuse = [c](std::string why) { c->err = "feahip_set_materials: " + std::move(why); return FEAHIP_EINVAL; };
+  if (n_materials < 0) return refuse("negative material count");
+  if (n_materials > FEAHIP_MAX_MATERIALS)
+    return refuse(std::to_string(n_materials) + " materials, at most " + std::to_string(FEAHIP_MAX_MATERIALS));
+  std::vector<uint8_t> ids;
+  if (n_materials > 0) {
+    if (!params || !elem_material) return refuse("null array with " + std::to_string(n_materials) + " materials");
+    for (int i = 0; i < 2 * n_materials; ++i)
+      if (!std::isfinite(params[i]))
+        return refuse(std::string(i & 1 ? "mu" : "lambda") + " of material " + std::to_string(i / 2) + " is not finite");
+    // the caller's element order: the whole mesh's on a feahip_create_rank context (its own entries are kept)
+    const bool whole = c->rank_own >= 0 && !c->rank_local_ids;
+    const int ne = whole ? c->rank_e_global : c->E;
+    for (int e = 0; e < ne; ++e)
+      if (elem_material[e] < 0 || elem_material[e] >= n_materials)
+        return refuse("element " + std::to_string(e) + " has material " + std::to_string(elem_material[e]) + " outside [0," +
+                      std::to_string(n_materials) + ")");
+    ids.resize((size_t)c->E);
+    for (int e = 0; e < c->E; ++e) ids[e] = (uint8_t)elem_material[whole ? c->rank_elem_global[e] : e];
+  }
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));   // no assembly in flight reads the old table
+  // the new table goes to the device first: a failed allocation or copy leaves the context with the old one
+  double2 *d_mat = nullptr;
+  uint8_t *d_elem_mat = nullptr;
+  if (n_materials > 0) {
+    int rc = dev_upload(c, &d_mat, reinterpret_cast<const double2 *>(params), (size_t)n_materials);
+    if (!rc) rc = dev_upload(c, &d_elem_mat, ids.data(), ids.size());
+    if (rc) { dev_free({d_mat, d_elem_mat}); return rc; }
+  }
+  dev_free({c->d_mat, c->d_elem_mat});
+  c->d_mat = d_mat; c->d_elem_mat = d_elem_mat;
+  c->n_materials = n_materials;
+  c->h_mat_params.assign(params, params + (n_materials ? 2 * (size_t)n_materials : 0));
+  c->h_elem_mat.swap(ids);
+  c->state_valid = false;
+  // the 4-node gather maps carry the ids (GatherLayout::o_emat): whatever was built or declined for this shard is built
+  // again by the next assembly that asks.  No other maps know the materials.
+  c->gather.release();
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_materials(feahip_ctx *c, int *n_materials, double *params, int *elem_material)
+{
+  CTX_GUARD_NOK(c);
+  if (!n_materials) { c->err = "feahip_get_materials: null count"; return FEAHIP_EINVAL; }
+  *n_materials = c->n_materials;
+  if (params) std::copy(c->h_mat_params.begin(), c->h_mat_params.end(), params);
+  if (elem_material) std::copy(c->h_elem_mat.begin(), c->h_elem_mat.end(), elem_material);
   return FEAHIP_OK;
 }
 

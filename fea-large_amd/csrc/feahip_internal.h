@@ -255,13 +255,16 @@ struct GatherLayout {                // the same for every chunk of a context
   int o_nodes, o_elems, o_bpos, o_rows, o_vlist, o_dlist, o_clist;   // byte offsets of the sections
   int max_nodes, max_elems, max_tile;                        // LDS tiles: coordinates, element records, K blocks
   int max_tasks, max_depth, max_vthr, max_vdepth, max_ddepth;   // largest chunk: block threads, contribution words, residual threads, visits, diagonal words
+  int o_emat;                        // byte offset of the material ids (one byte per element slot, the last section); 0: no material table
 };
 struct HostGather : HostChunkMaps {
   GatherLayout lay;
   int same_as_previous = 0;          // chunks whose map words equal their predecessor's (GatherHeader::flags)
 };
 // rows [row_lo, row_hi) only: a rank builds the maps of the rows it owns
-void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out);
+// elem_mat (may be null): material id of every element; the records then carry the optional section o_emat
+void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out,
+                       const uint8_t *elem_mat = nullptr);
 int ensure_gather(feahip_ctx *c);
 int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF);
 
@@ -410,6 +413,14 @@ struct feahip_ctx {
   bool linear_tet = false;    // npe == 4 and dN is the constant-strain table
   int model = 0;
   double lambda = 0, mu = 0;
+  // material table (feahip_set_materials): n_materials = 0 is the single pair above.  h_elem_mat is in the order of
+  // the context's own elements (a rank context: its local elements)
+  int n_materials = 0;
+  std::vector<double> h_mat_params;    // [n_materials][2] lambda, mu
+  std::vector<uint8_t> h_elem_mat;     // [E]
+  double2 *d_mat = nullptr;            // [n_materials] (lambda, mu)
+  uint8_t *d_elem_mat = nullptr;       // [E]
+  double *d_f_discard = nullptr;       // [3N] where the residual of a K-only gather assembly with a table goes (kernels_gather.hip)
   int strategy = FEAHIP_ASM_AUTO;
   int last_strategy = FEAHIP_ASM_AUTO;   // what the most recent assembly launch ran
 
@@ -484,6 +495,7 @@ struct feahip_ctx {
   int rank_own = -1;                   // nodes it owns (local ids [0, rank_own)); -1: an ordinary context
   std::vector<int> rank_node_global, rank_elem_global;
   int rank_n_global = 0;
+  int rank_e_global = 0;               // elements of the whole mesh (feahip_create_rank; 0 where the context never saw it)
   bool rank_local_ids = false;         // feahip_create_rank_local: the caller speaks local ids (surface faces included)
 
   // preconditioner of PCG_ILU / CHOLESKY solves: 0 = 3x3 block-Jacobi, 1 = aggregation multigrid (amg.h), 2 = the

@@ -37,7 +37,17 @@ struct AsmArgs {
   int *bad;                      // counter of Gauss points with det J <= 0
   double *Fout, *Sout;           // state export
   double *Gout, *Dout;           // shape gradients [E][G][3][npe] and det J [E][G] (null: not exported)
+  const double2 *mat;            // a context with a material table (the HET kernels): [n_materials] (lambda, mu) ...
+  const uint8_t *emat;           // ... and the material id of every element [E]
 };
+
+// (lambda, mu) of element e: its own pair of the material table (HET), the context's single pair otherwise
+template <bool HET, class Args>
+__device__ __forceinline__ double2 elem_material(const Args &A, int e)
+{
+  if constexpr (HET) return A.mat[A.emat[e]];
+  else return make_double2(A.lambda, A.mu);
+}
 
 template <int NPE>
 struct GPState {

@@ -210,12 +210,14 @@ struct Local {                                      // a chunk's record, before 
   std::vector<int> nodes;
   std::vector<uint32_t> elems, tpos;
   std::vector<uint16_t> rows, vlist, clist, dlist;
+  std::vector<uint8_t> emat;                        // material id per element slot (a context with a material table only)
 };
 
 // ---- pass B: one chunk's record, stage by stage; one per parallel_ranges worker, its vectors reused chunk after chunk
 struct ChunkBuilder {
   const int *conn;
   const HostPattern &hp;
+  const uint8_t *elem_mat;                          // [E] material ids, null without a material table
   int r0 = 0, r1 = 0, nrows = 0, b0 = 0, nb = 0, nelem = 0, nnode = 0, nslots = 0, nnslots = 0;
   int ntask = 0, wdepth[G_TASK_THREADS / 64] = {0}, dwords = 0, ddwords = 0, zslot = 0;
   std::vector<int> el, nd, task_of, thr_blk, order, res, eslot, nslot;
@@ -224,7 +226,7 @@ struct ChunkBuilder {
   std::vector<std::vector<Read>> reads;
   std::vector<uint8_t> occ;
 
-  ChunkBuilder(const int *c, const HostPattern &p) : conn(c), hp(p) {}
+  ChunkBuilder(const int *c, const HostPattern &p, const uint8_t *em) : conn(c), hp(p), elem_mat(em) {}
   int lnode(int g) const { return (int)(std::lower_bound(nd.begin(), nd.end(), g) - nd.begin()); }
   int lelem(int e) const { return (int)(std::lower_bound(el.begin(), el.end(), e) - el.begin()); }
 
@@ -404,6 +406,11 @@ struct ChunkBuilder {
       for (int k = 0; k < 4; ++k) w |= (uint32_t)nslot[lnode(conn[(size_t)el[i] * 4 + k])] << (8 * k);
       L.elems[eslot[i]] = w;
     }
+    L.emat.clear();
+    if (elem_mat) {                               // unused slots: material 0 (loaded, never used)
+      L.emat.assign((size_t)nslots, 0);
+      for (int i = 0; i < nelem; ++i) L.emat[eslot[i]] = elem_mat[el[i]];
+    }
     L.tpos.assign((size_t)ntask, 0xFFFFFFFFu);    // a thread without a block: no tile position
     for (int t = 0; t < ntask; ++t)
       if (thr_blk[t] >= 0) L.tpos[t] = btpos[thr_blk[t]];
@@ -444,7 +451,7 @@ struct ChunkBuilder {
 };
 
 // ---- layout: fixed section offsets, sized by the largest chunk
-bool lay_out(const std::vector<Local> &loc, HostGather &out)
+bool lay_out(const std::vector<Local> &loc, bool materials, HostGather &out)
 {
   const int nch = (int)loc.size();
   int m_v = 0, m_c = 0, m_d = 0, g_nodes = 0, g_elems = 0, g_tile = 0;
@@ -466,6 +473,9 @@ bool lay_out(const std::vector<Local> &loc, HostGather &out)
   lay.o_dlist = lay.o_vlist + round_up(m_v, 64);
   lay.o_clist = lay.o_dlist + round_up(m_d, 64);
   lay.stride = round_up(lay.o_clist + m_c, 128);
+  // the optional last section, one material id per element slot: behind everything else, so that the offsets (and,
+  // without a material table, the stride and the bytes) of the other sections are what they are without it
+  if (materials) { lay.o_emat = lay.stride; lay.stride += round_up(FEA_G_THREADS, 128); }   // (a byte per thread: the kernel indexes it by its thread id)
   if ((long long)nch * lay.stride > 0x7FFFFFFF00LL) return false;
   out.blob.assign((size_t)nch * lay.stride, 0);
   parallel_ranges(nch, 512, [&](int lo, int hi) {
@@ -480,6 +490,7 @@ bool lay_out(const std::vector<Local> &loc, HostGather &out)
       memcpy(rec + lay.o_vlist, L.vlist.data(), L.vlist.size() * 2);
       memcpy(rec + lay.o_dlist, L.dlist.data(), L.dlist.size() * 2);
       memcpy(rec + lay.o_clist, L.clist.data(), L.clist.size() * 2);
+      if (lay.o_emat) memcpy(rec + lay.o_emat, L.emat.data(), L.emat.size());
     }
   });
   return true;
@@ -496,13 +507,14 @@ void mark_repeats(HostGather &out, int nch)
     const GatherHeader &h0 = *reinterpret_cast<const GatherHeader *>(r0), &h1 = *reinterpret_cast<const GatherHeader *>(r1);
     const bool same = h0.nelem == h1.nelem && h0.noffd == h1.noffd && h0.depth == h1.depth && h0.nvthr == h1.nvthr &&
                       h0.vdepth == h1.vdepth && h0.ddepth == h1.ddepth && h0.r1 - h0.r0 == h1.r1 - h1.r0 &&
-                      memcmp(r0 + lay.o_elems, r1 + lay.o_elems, (size_t)(lay.stride - lay.o_elems)) == 0;
+                      memcmp(r0 + lay.o_elems, r1 + lay.o_elems, (size_t)((lay.o_emat ? lay.o_emat : lay.stride) - lay.o_elems)) == 0;   // (the material ids are no map words: the kernel loads them for every chunk)
     if (same) { reinterpret_cast<GatherHeader *>(out.blob.data() + (size_t)p * lay.stride)->flags |= 1; ++out.same_as_previous; }
   }
 }
 }  // namespace
 
-void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out)
+void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out,
+                       const uint8_t *elem_mat)
 {
   (void)E;
   out.ok = false; out.nchunks = 0; out.blob.clear(); out.first_row.clear();
@@ -512,12 +524,12 @@ void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int
   std::vector<Local> loc((size_t)nch);
   std::vector<char> bad((size_t)nch, 0);
   parallel_ranges(nch, 512, [&](int lo, int hi) {
-    ChunkBuilder cb(conn, hp);
+    ChunkBuilder cb(conn, hp, elem_mat);
     for (int p = lo; p < hi; ++p) bad[p] = !cb.build(out.first_row[p], out.first_row[p + 1], loc[p]);
   });
   for (int p = 0; p < nch; ++p)
     if (bad[p]) return;
-  if (!lay_out(loc, out)) return;
+  if (!lay_out(loc, elem_mat != nullptr, out)) return;
   mark_repeats(out, nch);
   out.nchunks = nch;
   out.total_evals = 0;

@@ -25,6 +25,7 @@ struct GatherArgs {
   int *bad;
   unsigned long long *stamps;    // diagnostic build only: [chunk][8] s_memtime deltas
   int ablate;                    // diagnostic build only: timing experiments (results meaningless)
+  const double2 *mat;            // [n_materials] (lambda, mu): a context with a material table (HET kernels) only
 };
 #if defined(FEAHIP_DEBUG) && !defined(FEAHIP_NOABL)       // FEAHIP_NOABL: stamps only, the code of the shipped kernel otherwise
 #define G_ABL(bit) (A.ablate & (bit))

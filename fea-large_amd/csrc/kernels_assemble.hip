@@ -27,7 +27,8 @@
 // row-owner
 // ------------------------------------------------------------------------
 // 4 waves per SIMD (<= 128 VGPRs) for 4-node elements; 10-node elements need the whole file
-template <int NPE, bool LINTET, bool DOK, bool DOF>
+// HET: the context has a material table; every visit reads the (lambda, mu) pair of its element (elem_material)
+template <int NPE, bool LINTET, bool DOK, bool DOF, bool HET>
 __global__ __launch_bounds__(64 * FEA_WAVES_PER_WG)
 void k_assemble_rowowner(AsmArgs A)
 {
@@ -80,11 +81,12 @@ void k_assemble_rowowner(AsmArgs A)
       }
     }
     const int rowoff = (A.rowptr[a] - b0) * 9;
+    const double2 lm = elem_material<HET>(A, e);
     double fa[3] = {0, 0, 0};
     for (int gp = 0; gp < A.G; ++gp) {
       GPState<NPE> s;
-      if constexpr (NPE == 4) gp_state<4, LINTET, false>(xe, Xe, A.tab, gp, A.model, A.lambda, A.mu, s);
-      else gp_state_stream<NPE>(A.x, A.X0, nd, A.tab, gp, A.model, A.lambda, A.mu, s);
+      if constexpr (NPE == 4) gp_state<4, LINTET, false>(xe, Xe, A.tab, gp, A.model, lm.x, lm.y, s);
+      else gp_state_stream<NPE>(A.x, A.X0, nd, A.tab, gp, A.model, lm.x, lm.y, s);
       if (!(s.detJ > 0.0) && DOK && la == 0) atomicAdd(A.bad, 1);
       if (s.detJ == 0.0) continue;      // reference keeps no gradient then (fea_solver.c:697)
       double ga[3] = {s.g[0][0], s.g[0][1], s.g[0][2]};
@@ -171,7 +173,7 @@ __device__ __forceinline__ int find_block(const AsmArgs &A, int row, int col)
   return lo;
 }
 
-template <int NPE, bool LINTET, bool DOK, bool DOF>
+template <int NPE, bool LINTET, bool DOK, bool DOF, bool HET>
 __global__ __launch_bounds__(256)
 void k_assemble_atomic(AsmArgs A)
 {
@@ -183,9 +185,10 @@ void k_assemble_atomic(AsmArgs A)
   int nd[NPE];
   double xe[NPE][3], Xe[NPE][3];
   load_element<NPE>(A, e, nd, xe, Xe);
+  const double2 lm = elem_material<HET>(A, e);
   for (int gp = 0; gp < A.G; ++gp) {
     GPState<NPE> s;
-    gp_state<NPE, LINTET>(xe, Xe, A.tab, gp, A.model, A.lambda, A.mu, s);
+    gp_state<NPE, LINTET>(xe, Xe, A.tab, gp, A.model, lm.x, lm.y, s);
     if (!(s.detJ > 0.0) && DOK) atomicAdd(A.bad, 1);
     if (s.detJ == 0.0) continue;
 #pragma unroll
@@ -231,7 +234,7 @@ void k_assemble_atomic(AsmArgs A)
 // per-Gauss-point F and sigma in the reference's shapes
 // (graddefs[e][g], stresses[e][g]: fea_solver.h:262-269)
 // ------------------------------------------------------------------------
-template <int NPE, bool LINTET>
+template <int NPE, bool LINTET, bool HET>
 __global__ __launch_bounds__(256)
 void k_state_export(AsmArgs A)
 {
@@ -240,9 +243,10 @@ void k_state_export(AsmArgs A)
   int nd[NPE];
   double xe[NPE][3], Xe[NPE][3];
   load_element<NPE>(A, e, nd, xe, Xe);
+  const double2 lm = elem_material<HET>(A, e);
   for (int gp = 0; gp < A.G; ++gp) {
     GPState<NPE> s;
-    gp_state<NPE, LINTET>(xe, Xe, A.tab, gp, A.model, A.lambda, A.mu, s);
+    gp_state<NPE, LINTET>(xe, Xe, A.tab, gp, A.model, lm.x, lm.y, s);
     double *Fo = A.Fout + ((size_t)e * A.G + gp) * 9;
     double *So = A.Sout + ((size_t)e * A.G + gp) * 9;
 #pragma unroll
@@ -271,7 +275,7 @@ static AsmArgs make_args(feahip_ctx *c)
   AsmArgs A;
   A.N = c->N; A.E = c->E; A.G = c->G; A.nchunks = c->nchunks_local; A.chunk0 = c->chunk0; A.model = c->model;
   A.row0 = c->row0; A.row1 = c->row1;
-  A.lambda = c->lambda; A.mu = c->mu;
+  A.lambda = c->lambda; A.mu = c->mu; A.mat = c->d_mat; A.emat = c->d_elem_mat;
   A.tab = c->d_table; A.conn = c->d_conn; A.X0 = c->d_X0; A.x = c->d_x;
   A.rowptr = c->d_rowptr; A.colidx = c->d_colidx; A.K = c->d_K; A.f = c->d_f;
   A.incptr = c->generic.d_incptr; A.inc = c->generic.d_inc; A.incslot = c->generic.d_incslot;
@@ -285,7 +289,8 @@ static void launch_rowowner_t(feahip_ctx *c, const AsmArgs &A, bool doK, bool do
 {
   const int grid = (c->nchunks_local + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
   with_kf(doK, doF, [&](auto K, auto F) {
-    hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, K, F>), dim3(grid), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, A);
+    if (c->n_materials) hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, K, F, true>), dim3(grid), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, A);
+    else hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, K, F, false>), dim3(grid), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, A);
   });
 }
 
@@ -294,7 +299,8 @@ static void launch_atomic_t(feahip_ctx *c, const AsmArgs &A, bool doK, bool doF)
 {
   const int grid = (c->E + 255) / 256;
   with_kf(doK, doF, [&](auto K, auto F) {
-    hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, K, F>), dim3(grid), dim3(256), 0, c->stream, A);
+    if (c->n_materials) hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, K, F, true>), dim3(grid), dim3(256), 0, c->stream, A);
+    else hipLaunchKernelGGL((k_assemble_atomic<NPE, LINTET, K, F, false>), dim3(grid), dim3(256), 0, c->stream, A);
   });
 }
 
@@ -305,6 +311,9 @@ static bool rowowner_fits(const feahip_ctx *c) { return c->incslot_ok && c->max_
 static int resolve_assembly(feahip_ctx *c, bool doK)
 {
   int strat = c->strategy, rc;
+  // a material table: the staged visits and the shared-state kernel evaluate one (lambda, mu) pair and are refused
+  // with one (dispatch_assembly), so AUTO goes from the gather kernels straight to the generic ones
+  const bool het = c->n_materials > 0;
   // AUTO: the gather kernels where their maps build and their chunks are compact, the staged visits / the
   // shared-state kernel behind them, the generic row-owner visits or the atomic scatter behind those
   if (strat == FEAHIP_ASM_AUTO) {
@@ -315,7 +324,9 @@ static int resolve_assembly(feahip_ctx *c, bool doK)
       GatherMaps &g = c->gather;
       if (!g.is(MapOutcome::declined, c->row0, c->row1) && (rc = ensure_gather(c))) return rc;
       if (g.built() && g.evals_per_element <= 2.5) strat = FEAHIP_ASM_GATHER;
-      else {
+      else if (het) {                                  // (the staged visits know one material)
+        if (g.built()) { g.release(); g.record(MapOutcome::declined, c->row0, c->row1); }
+      } else {
         if (g.built()) {
           // the maps were built to learn what the chunks cost; AUTO does not run them: they do not stay resident
           // (84 B per element), and the sizes reported are those of the kernel that runs
@@ -333,9 +344,9 @@ static int resolve_assembly(feahip_ctx *c, bool doK)
       if ((rc = ensure_gather10(c))) return rc;
       if (c->gather10.built() && c->gather10.evals_per_element <= 12.0) strat = FEAHIP_ASM_GATHER;
     }
-    if (strat == FEAHIP_ASM_AUTO && c->npe == 10 && (rc = ensure_quad(c))) return rc;
+    if (strat == FEAHIP_ASM_AUTO && c->npe == 10 && !het && (rc = ensure_quad(c))) return rc;
     if (strat == FEAHIP_ASM_AUTO)
-      strat = (c->quad.built() && doK) ? FEAHIP_ASM_SHARED : (rowowner_fits(c) ? FEAHIP_ASM_ROWOWNER : FEAHIP_ASM_ATOMIC);
+      strat = (c->quad.built() && doK && !het) ? FEAHIP_ASM_SHARED : (rowowner_fits(c) ? FEAHIP_ASM_ROWOWNER : FEAHIP_ASM_ATOMIC);
   }
   if (strat == FEAHIP_ASM_SHARED && (rc = ensure_quad(c))) return rc;
   if (strat == FEAHIP_ASM_SHARED && !doK && c->quad.built())     // residual alone: visit kernel
@@ -349,6 +360,8 @@ static int dispatch_assembly(feahip_ctx *c, int strat, bool doK, bool doF)
   const bool gather10 = c->npe == 10 || c->npe == 8;
   auto refuse = [c](std::string why) { c->err = std::move(why); return FEAHIP_EINVAL; };
   int rc;
+  if (c->n_materials && (strat == FEAHIP_ASM_SHARED || strat == FEAHIP_ASM_STAGED))
+    return refuse("the staged and shared-state assemblies take one (lambda, mu) pair: with a material table use GATHER or ROWOWNER");
   switch (strat) {
   case FEAHIP_ASM_SHARED:
     if (!c->quad.built()) return refuse("shared-state assembly needs 10-node elements whose chunks fit the LDS tiles");
@@ -413,13 +426,16 @@ int launch_state_export(feahip_ctx *c, double *d_grads, double *d_detj)
   AsmArgs A = make_args(c);
   A.Gout = d_grads; A.Dout = d_detj;
   const int grid = (c->E + 255) / 256;
-  if (c->npe == 4) {
-    if (c->linear_tet) hipLaunchKernelGGL((k_state_export<4, true>), dim3(grid), dim3(256), 0, c->stream, A);
-    else hipLaunchKernelGGL((k_state_export<4, false>), dim3(grid), dim3(256), 0, c->stream, A);
-  } else if (c->npe == 8)
-    hipLaunchKernelGGL((k_state_export<8, false>), dim3(grid), dim3(256), 0, c->stream, A);
-  else
-    hipLaunchKernelGGL((k_state_export<10, false>), dim3(grid), dim3(256), 0, c->stream, A);
+  auto launch = [&](auto H) {
+    if (c->npe == 4) {
+      if (c->linear_tet) hipLaunchKernelGGL((k_state_export<4, true, H>), dim3(grid), dim3(256), 0, c->stream, A);
+      else hipLaunchKernelGGL((k_state_export<4, false, H>), dim3(grid), dim3(256), 0, c->stream, A);
+    } else if (c->npe == 8)
+      hipLaunchKernelGGL((k_state_export<8, false, H>), dim3(grid), dim3(256), 0, c->stream, A);
+    else
+      hipLaunchKernelGGL((k_state_export<10, false, H>), dim3(grid), dim3(256), 0, c->stream, A);
+  };
+  if (c->n_materials) launch(std::true_type()); else launch(std::false_type());
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }

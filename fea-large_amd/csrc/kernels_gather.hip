@@ -38,7 +38,14 @@
 //     state phase of chunk i and sit in registers; the coordinates move into the LDS tile after chunk i's gather
 //     phase (the tile is dead from the end of the state phase), a whole state + gather phase after their request;
 //   * the finished rows of chunk i are stored last and nobody waits for them.
-template <bool DOK, bool DOF, bool NH>
+//
+// HET (a context with a material table, feahip_set_materials): lane t also holds the (lambda, mu) pair of the element
+// in slot t.  The slot's material id is one byte of the record's last section; the pair is read from the table in
+// global memory (4 KB at most, L2-resident: the LDS has 1.8 KB to spare next to the records, less than the table).  Both
+// follow the node ids and coordinates through the pipeline -- the id is requested two chunks ahead, the pair one chunk
+// ahead by the id that has arrived by then -- so the state phase waits for neither.  HET = false is the kernel as it
+// was: no further load, register or LDS byte.
+template <bool DOK, bool DOF, bool NH, bool HET>
 __global__ __launch_bounds__(FEA_G_THREADS, FEA_G_BIG ? 4 : 3)
 void k_assemble_gather(GatherArgs A, int run_len)
 {
@@ -82,6 +89,17 @@ void k_assemble_gather(GatherArgs A, int run_len)
     const int cn = min(chunk + 1, cend - 1);
     node1 = reinterpret_cast<const int *>(A.maps + (size_t)(A.chunk0 + cn) * stride + A.lay.o_nodes)[t & (FEA_G_MAX_NODES - 1)];
   }
+  // HET: the pair of the first chunk's element slot t (two dependent loads, nothing to hide behind) and the material id
+  // of the next chunk's (the section has a byte per THREAD: no clamp, no register for a clamped index).  pn holds this
+  // chunk's pair through its state phase and is overwritten with the next chunk's behind it.
+  int mid1 = 0;
+  double2 pn = make_double2(A.lambda, A.mu);
+  if constexpr (HET) {
+    pn = A.mat[rec[A.lay.o_emat + t]];
+    const int cn = min(chunk + 1, cend - 1);
+    mid1 = (A.maps + (size_t)(A.chunk0 + cn) * stride + A.lay.o_emat)[t];
+    asm volatile("" : : "v"(mid1), "v"(pn.x), "v"(pn.y));
+  }
   // nothing is pending when the loop is entered: otherwise the loop header inherits "node1 may still be in
   // flight" and the compiler waits for everything (s_waitcnt vmcnt(0)) at the top of EVERY iteration
   asm volatile("" : : "v"(mn.eids), "v"(mn.tpos), "v"(mn.cw[0]), "v"(mn.cw[1]), "v"(mn.cw[2]), "v"(mn.cw[3]), "v"(mn.cw[4]), "v"(mn.cw[5]),
@@ -118,8 +136,8 @@ void k_assemble_gather(GatherArgs A, int run_len)
       double R[REC];
       double detJ;
       if (G_ABL(8)) { detJ = 1.0; for (int q = 0; q < REC; ++q) R[q] = xe[q & 3][q % 3] + Xe[(q >> 2) & 3][q % 3]; }
-      else detJ = NH ? lintet_record_nh<DOK>(xe, Xe, gauss_w, A.lambda, A.mu, R)
-                     : lintet_record_a5<DOK>(xe, Xe, gauss_w, A.lambda, A.mu, R);
+      else detJ = NH ? lintet_record_nh<DOK>(xe, Xe, gauss_w, HET ? pn.x : A.lambda, HET ? pn.y : A.mu, R)
+                     : lintet_record_a5<DOK>(xe, Xe, gauss_w, HET ? pn.x : A.lambda, HET ? pn.y : A.mu, R);
       if (!(detJ > 0.0)) {                             // rare, kept off the fast path
         if (DOK) {                                     // counted by the chunk that owns its lowest-numbered node
           const int *gn = reinterpret_cast<const int *>(rec + A.lay.o_nodes);
@@ -164,6 +182,15 @@ void k_assemble_gather(GatherArgs A, int run_len)
         ca0 = *reinterpret_cast<const double2 *>(A.x + n1 * 4); ca1.x = A.x[n1 * 4 + 2];
         cc0 = *reinterpret_cast<const double2 *>(A.X0 + n1 * 4); cc1.x = A.X0[n1 * 4 + 2];
         node1 = reinterpret_cast<const int *>(A.maps + (size_t)(A.chunk0 + c2) * stride + A.lay.o_nodes)[t & (FEA_G_MAX_NODES - 1)];
+      }
+      // HET: the next chunk's pair by the material id requested a chunk ago (it has arrived: it was waited for with
+      // the other prefetched words before the previous chunk's rows), and the id of the chunk after it -- the waves
+      // that hold element slots only
+      if constexpr (HET) {
+        if (wslot * 64 < A.lay.max_elems) {
+          pn = A.mat[mid1];
+          mid1 = (A.maps + (size_t)(A.chunk0 + c2) * stride + A.lay.o_emat)[t];
+        }
       }
     }
 
@@ -250,6 +277,7 @@ void k_assemble_gather(GatherArgs A, int run_len)
     G_STAMP(4);
     asm volatile("" : : "v"(mn.eids), "v"(mn.tpos), "v"(mn.cw[0]), "v"(mn.cw[1]), "v"(mn.cw[2]), "v"(mn.cw[3]), "v"(mn.cw[4]), "v"(mn.cw[5]),
                  "v"(mn.vw[0]), "v"(mn.vw[1]), "v"(mn.kd), "v"(mn.vb), "v"(mn.ve), "v"(node1), "v"(hword));
+    if constexpr (HET) asm volatile("" : : "v"(mid1), "v"(pn.x), "v"(pn.y));
     if (more && node_lane) {                           // next chunk's coordinates: the tile has been dead since the state phase
       sC[t * 3] = ca0; sC[t * 3 + 1] = make_double2(ca1.x, cc0.x); sC[t * 3 + 2] = make_double2(cc0.y, cc1.x);
     }
@@ -321,7 +349,9 @@ int ensure_gather(feahip_ctx *c)
   // they go before anything else can launch them -- also when the new range turns out not to fit
   g.release();
   HostGather hg;
-  build_host_gather(c->N, c->E, c->h_conn.data(), *c->h_pat, c->row0, c->row1, hg);
+  // a context with a material table: the records carry the material id of every element slot (feahip_set_materials
+  // releases the maps, so that they are built again with the ids it was given)
+  build_host_gather(c->N, c->E, c->h_conn.data(), *c->h_pat, c->row0, c->row1, hg, c->n_materials ? c->h_elem_mat.data() : nullptr);
   if (!hg.ok) { g.record(MapOutcome::failed, c->row0, c->row1); return FEAHIP_OK; }   // this row range only: another shard of the same context may fit
   FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_maps, hg.blob.size() ? hg.blob.size() : 1));
   FEA_HIP_CHECK(c, hipMemcpy(g.d_maps, hg.blob.data(), hg.blob.size(), hipMemcpyHostToDevice));
@@ -354,7 +384,7 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
   GatherArgs A;
   A.chunk0 = 0; A.nchunks = g.nchunks; A.model = c->model; A.lambda = c->lambda; A.mu = c->mu;
   A.tab = c->d_table; A.maps = g.d_maps; A.lay = g.lay; A.X0 = c->d_X0; A.x = c->d_x;
-  A.K = c->d_K; A.f = c->d_f; A.bad = c->d_flag + 1; A.stamps = nullptr; A.ablate = 0;
+  A.K = c->d_K; A.f = c->d_f; A.bad = c->d_flag + 1; A.stamps = nullptr; A.ablate = 0; A.mat = c->d_mat;
   if (g.nchunks <= 0) return FEAHIP_OK;
 #ifdef FEAHIP_DEBUG
   static unsigned long long *d_stamps = nullptr;
@@ -398,14 +428,31 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
   const int regF = std::max(A.lay.max_elems * GREC_F, 3 * FEA_G_THREADS);
   const int ldsK = A.lay.max_nodes * 48 + ((regK + 1) & ~1) * 8, ldsF = A.lay.max_nodes * 48 + ((regF + 1) & ~1) * 8;
   const bool nh = c->model == FEAHIP_MODEL_COMPRESSIBLE_NEOHOOKEAN;
-  auto launch = [&](auto K, auto F, auto M) -> int {
+  const bool het = c->n_materials > 0;
+  if (het != (g.lay.o_emat != 0)) { c->err = "gather maps and material table disagree"; return FEAHIP_ESTATE; }
+  // The pair and the material id cost a HET kernel eight vector registers.  The A5 kernel that assembles K alone is the
+  // one closest to the 128 a 1024-thread workgroup has (121) and would spill two of them: with a table that assembly
+  // runs the K-and-f kernel (119 registers, no scratch) with the residual going to a vector nobody reads.  K is the same
+  // to the bit: the residual is summed beside the diagonal blocks, out of the same records.
+  if (het && !nh && doK && !doF) {
+    if (!c->d_f_discard) FEA_HIP_CHECK(c, hipMalloc((void **)&c->d_f_discard, sizeof(double) * (size_t)c->ndof));
+    A.f = c->d_f_discard;
+    doF = true;
+  }
+  auto launch = [&](auto K, auto F, auto M, auto H) -> int {
+    if constexpr (H && K && !F && !M) { c->err = "gather assembly: no K-only A5 kernel with a material table"; return FEAHIP_ESTATE; }
+    else {
     const int lds = K ? ldsK : ldsF;
-    FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((k_assemble_gather<K, F, M>), grid, blk, lds, c->stream, A, run_len);
+    FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M, H>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((k_assemble_gather<K, F, M, H>), grid, blk, lds, c->stream, A, run_len);
     return FEAHIP_OK;
+    }
   };
   int rc;
-  with_kf(doK, doF, [&](auto K, auto F) { rc = nh ? launch(K, F, std::true_type()) : launch(K, F, std::false_type()); });
+  with_kf(doK, doF, [&](auto K, auto F) {
+    auto model = [&](auto H) { return nh ? launch(K, F, std::true_type(), H) : launch(K, F, std::false_type(), H); };
+    rc = het ? model(std::true_type()) : model(std::false_type());
+  });
   if (rc) return rc;
   FEA_HIP_CHECK(c, hipGetLastError());
 #ifdef FEAHIP_DEBUG

@@ -47,11 +47,13 @@ struct S10Args {
   const double *X0, *x;
   double *state;
   int *bad;
+  const double2 *mat;            // material table and per-element ids (HET: a context with a table)
+  const uint8_t *emat;
 };
 
 // thread <-> element, its Gauss points one after the other with the twenty coordinate triples held in registers (one
 // thread per (element, Gauss point) gathered them G times: 0.18 ms of the 1.11 ms assembly at G = 5)
-template <int NPE>
+template <int NPE, bool HET>
 __global__ __launch_bounds__(256)
 void k_state10(S10Args A)
 {
@@ -76,6 +78,7 @@ void k_state10(S10Args A)
     xc[k][0] = a0.x; xc[k][1] = a0.y; xc[k][2] = A.x[n * 4 + 2];
     Xc[k][0] = c0.x; Xc[k][1] = c0.y; Xc[k][2] = A.X0[n * 4 + 2];
   }
+  const double2 lm = elem_material<HET>(A, e);             // HET: the pair of the rank's local element e
   const bool mine = n0 >= A.row0 && n0 < A.row1;           // inverted points are counted once per mesh: by the rank that owns the first node
   int nbad = 0;
   for (int g = 0; g < A.G; ++g) {
@@ -99,7 +102,7 @@ void k_state10(S10Args A)
       for (int j = 0; j < 3; ++j) Fi[i][j] = M[0][i] * Ji[j][0] + M[1][i] * Ji[j][1] + M[2][i] * Ji[j][2];
     fd_inv3(Fi, F, detFi);
     double sig[3][3], l1, m1;
-    fd_constitutive(F, A.model, A.lambda, A.mu, sig, l1, m1);
+    fd_constitutive(F, A.model, lm.x, lm.y, sig, l1, m1);
     nbad += act && !(detJ > 0.0);
     double st[T_HDR];
 #pragma unroll
@@ -515,9 +518,14 @@ int launch_assemble_gather10(feahip_ctx *c, bool doK, bool doF)
     S.nloc = g.nloc; S.G = c->G; S.model = c->model; S.row0 = c->row0; S.row1 = c->row1; S.lambda = c->lambda; S.mu = c->mu;
     S.tab = c->d_table; S.elist = g.d_elist; S.conn = c->d_conn; S.X0 = c->d_X0; S.x = c->d_x;
     S.state = g.d_state; S.bad = doK ? c->d_flag + 1 : nullptr;      // the counter is reset by stiffness assemblies only
+    S.mat = c->d_mat; S.emat = c->d_elem_mat;
     if (g.nloc > 0) {
-      if (c->npe == 10) hipLaunchKernelGGL(k_state10<10>, dim3((unsigned)((g.nloc + 255) / 256)), dim3(256), 0, c->stream, S);
-      else              hipLaunchKernelGGL(k_state10<8>, dim3((unsigned)((g.nloc + 255) / 256)), dim3(256), 0, c->stream, S);
+      const dim3 grid((unsigned)((g.nloc + 255) / 256));
+      auto launch = [&](auto H) {
+        if (c->npe == 10) hipLaunchKernelGGL((k_state10<10, H>), grid, dim3(256), 0, c->stream, S);
+        else              hipLaunchKernelGGL((k_state10<8, H>), grid, dim3(256), 0, c->stream, S);
+      };
+      if (c->n_materials) launch(std::true_type()); else launch(std::false_type());
     }
   }
   G10Args A;

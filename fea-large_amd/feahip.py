@@ -108,6 +108,8 @@ ABI = {
     "feahip_get_surface_forces": [C.c_void_p, _dp],
     "feahip_set_load_factor": [C.c_void_p, C.c_double],
     "feahip_get_load_factor": [C.c_void_p, _dp],
+    "feahip_set_materials": [C.c_void_p, C.c_int, _dp, _ip],
+    "feahip_get_materials": [C.c_void_p, _ip, _dp, _ip],
     "feahip_host_surface_faces": [C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip, _ip, _ip],
     "feahip_apply_preconditioner": [C.c_void_p, _dp, _dp],
     "feahip_amg_info": [C.c_void_p, C.POINTER(C.c_longlong), _dp],
@@ -160,6 +162,7 @@ class FeaDeck(C.Structure):
         ("prescribed_nodes_count", C.c_int), ("presc_node", _ip), ("presc_type", _ip), ("presc_values", _dp),
         ("surface_faces_count", C.c_int), ("surface_nodes_per_face", C.c_int), ("surface_nodes", _ip),
         ("surface_kind", _ip), ("surface_values", _dp),
+        ("materials_count", C.c_int), ("material_params", _dp), ("element_material", _ip),
     ]
 
 
@@ -259,6 +262,12 @@ class Deck:
         self.surface_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
         self.surface_kind = np.ascontiguousarray(kw.get("surface_kind", []), dtype=np.int32)
         self.surface_values = np.ascontiguousarray(kw.get("surface_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+        # material table (feahip_set_materials): materials[n][2] = lambda, mu and one id per element; none = the single
+        # pair `parameters`
+        self.materials = np.ascontiguousarray(kw.get("materials", np.zeros((0, 2))), dtype=np.float64).reshape(-1, 2)
+        self.element_material = np.ascontiguousarray(kw.get("element_material", []), dtype=np.int32)
+        if len(self.element_material) != (len(self.elements) if len(self.materials) else 0):
+            raise ValueError("materials and element_material come together, one id per element")
 
     @staticmethod
     def load(path):
@@ -270,7 +279,7 @@ class Deck:
             raise FeaHipError(f"{path}: {err.value.decode()}")
         try:
             n, e, npe, nb = fd.nodes_count, fd.elements_count, fd.nodes_per_element, fd.prescribed_nodes_count
-            ns, npf = fd.surface_faces_count, fd.surface_nodes_per_face
+            ns, npf, nm = fd.surface_faces_count, fd.surface_nodes_per_face, fd.materials_count
             deck = Deck(
                 model=fd.model, parameters=[fd.parameters[0], fd.parameters[1]], solver_type=fd.solver_type,
                 solver_tolerance=fd.solver_tolerance, solver_max_iter=fd.solver_max_iter, ele_type=fd.ele_type,
@@ -284,7 +293,9 @@ class Deck:
                 presc_values=np.ctypeslib.as_array(fd.presc_values, (nb, 3)).copy() if nb else np.zeros((0, 3)),
                 surface_faces=np.ctypeslib.as_array(fd.surface_nodes, (ns, npf)).copy() if ns else np.zeros((0, 0)),
                 surface_kind=np.ctypeslib.as_array(fd.surface_kind, (ns,)).copy() if ns else [],
-                surface_values=np.ctypeslib.as_array(fd.surface_values, (ns, 3)).copy() if ns else np.zeros((0, 3)))
+                surface_values=np.ctypeslib.as_array(fd.surface_values, (ns, 3)).copy() if ns else np.zeros((0, 3)),
+                materials=np.ctypeslib.as_array(fd.material_params, (nm, 2)).copy() if nm else np.zeros((0, 2)),
+                element_material=np.ctypeslib.as_array(fd.element_material, (e,)).copy() if nm else [])
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -308,6 +319,11 @@ class Deck:
         fd.surface_faces_count = len(self.surface_kind)
         fd.surface_nodes_per_face = self.surface_faces.shape[1] if len(self.surface_kind) else 0
         fd.surface_nodes, fd.surface_kind, fd.surface_values = _i(self.surface_faces), _i(self.surface_kind), _d(self.surface_values)
+        # (the arrays are the deck's own, contiguous and of the struct's types: the struct borrows them)
+        self.materials = np.ascontiguousarray(self.materials, dtype=np.float64).reshape(-1, 2)
+        self.element_material = np.ascontiguousarray(self.element_material, dtype=np.int32)
+        fd.materials_count = len(self.materials)
+        fd.material_params, fd.element_material = _d(self.materials), _i(self.element_material)
         return fd
 
     def save(self, path):
@@ -341,6 +357,33 @@ class FeaSolver:
             self._ctx = C.c_void_p()
             raise FeaHipError(f"feahip_create failed ({rc}): {self._lib.feahip_create_error().decode()}")
         self._deck_surface_loads()
+        self._deck_materials()
+
+    def _deck_materials(self):
+        """Installs the deck's (or the slab's) material table, where it has one."""
+        if len(getattr(self.deck, "materials", [])):
+            self.set_materials(self.deck.materials, self.deck.element_material)
+
+    def set_materials(self, materials, element_material=None):
+        """feahip_set_materials: materials[n][2] = (lambda, mu), element_material[E] in [0, n) in the order of the
+        elements this solver was made from (the whole deck's for a RankSolver, the slab's for a LocalRankSolver).
+        set_materials(None) (or an empty table) returns to the single pair of the deck."""
+        par = np.ascontiguousarray(np.zeros((0, 2)) if materials is None else materials, dtype=np.float64).reshape(-1, 2)
+        ids = np.ascontiguousarray([] if element_material is None else element_material, dtype=np.int32).ravel()
+        n = len(par)
+        ne = len(self.deck.elements)
+        if n and len(ids) != ne:
+            raise ValueError(f"element_material has {len(ids)} entries for {ne} elements")
+        self._chk(self._lib.feahip_set_materials(self._ctx, n, _d(par) if n else None, _i(ids) if n else None))
+
+    def materials(self):
+        """(materials[n][2], element_material[this context's elements]) in force; ([0][2], []) without a table."""
+        n = C.c_int(0)
+        self._chk(self._lib.feahip_get_materials(self._ctx, C.byref(n), None, None))
+        par, ids = np.zeros((n.value, 2)), np.zeros(self.E if n.value else 0, dtype=np.int32)
+        if n.value:
+            self._chk(self._lib.feahip_get_materials(self._ctx, C.byref(n), _d(par), _i(ids)))
+        return par, ids
 
     def _deck_surface_loads(self):
         if len(getattr(self.deck, "surface_kind", [])):
@@ -876,6 +919,7 @@ class RankSolver(FeaSolver):
         self.elem_global = np.empty(self.E, dtype=np.int32)
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
         self._deck_surface_loads()                              # the whole face list: the rank keeps what touches its nodes
+        self._deck_materials()                                  # the whole mesh's ids: the rank keeps its own elements'
 
 
 def host_rank_mesh(deck, rank, nranks, pattern=False):
@@ -955,6 +999,12 @@ class Slab:
         self.surface_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
         self.surface_kind = np.ascontiguousarray(kw.get("surface_kind", []), dtype=np.int32)
         self.surface_values = np.ascontiguousarray(kw.get("surface_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+        # material table (feahip_set_materials): materials[n][2] = lambda, mu and one id per element; none = the single
+        # pair `parameters`
+        self.materials = np.ascontiguousarray(kw.get("materials", np.zeros((0, 2))), dtype=np.float64).reshape(-1, 2)
+        self.element_material = np.ascontiguousarray(kw.get("element_material", []), dtype=np.int32)
+        if len(self.element_material) != (len(self.elements) if len(self.materials) else 0):
+            raise ValueError("materials and element_material come together, one id per element")
 
     def permuted(self, new_local_id):
         """The same slab with local node a renamed new_local_id[a] (owned ids must stay in [0, n_own))."""
@@ -1013,6 +1063,7 @@ class LocalRankSolver(FeaSolver):
         self.elem_global = np.empty(self.E, dtype=np.int32)
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
         self._deck_surface_loads()                              # local ids; faces of other ranks' nodes are dropped
+        self._deck_materials()                                  # the slab's own ids, in its element order
 
 
 def host_rank_local_plan(slab, rank, nranks):
@@ -1057,6 +1108,8 @@ def slab_of(deck, rank, nranks):
         fl = local_of[deck.surface_faces]
         fk = np.all(fl >= 0, axis=1)                            # all of its nodes are local (the library drops other ranks')
         kw.update(surface_faces=fl[fk], surface_kind=deck.surface_kind[fk], surface_values=deck.surface_values[fk])
+    if len(getattr(deck, "materials", [])):
+        kw.update(materials=deck.materials, element_material=deck.element_material[eg])
     slab = Slab(nodes=deck.nodes[ng], elements=local_of[deck.elements[eg]], node_global=ng, elem_global=eg, n_own=no,
                 n_global_nodes=N, halo_owner=owner[ng[no:]], presc_node=local_of[deck.presc_node[keep]] if keep.any() else [],
                 presc_type=deck.presc_type[keep] if keep.any() else [],

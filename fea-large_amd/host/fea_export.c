@@ -95,16 +95,17 @@ int fea_export_gmsh(const char *filename, const fea_deck *d, const fea_step_snap
   fprintf(f, "$EndNodes\n$Elements\n%d\n", d->elements_count);
   for (i = 0; i < d->elements_count; ++i) {
     const int *c = d->elements + (size_t)i * npe;
+    const int tag = d->materials_count > 0 ? d->element_material[i] + 1 : 1;   /* physical entity: the material, from 1 */
     if (npe == 10) {                       /* our 8 <-> Gmsh 9 (fea_solver.c:1430-1434) */
-      fprintf(f, "%d 11 3 1 1 1 ", i + 1);
+      fprintf(f, "%d 11 3 %d 1 1 ", i + 1, tag);
       for (j = 0; j < 8; ++j) fprintf(f, "%d ", c[j] + 1);
       fprintf(f, "%d %d \n", c[9] + 1, c[8] + 1);
     } else if (npe == 8) {                 /* Gmsh type 5, 8-node hexahedron: the same corner order */
-      fprintf(f, "%d 5 3 1 1 1 ", i + 1);
+      fprintf(f, "%d 5 3 %d 1 1 ", i + 1, tag);
       for (j = 0; j < 8; ++j) fprintf(f, "%d ", c[j] + 1);
       fprintf(f, "\n");
     } else {
-      fprintf(f, "%d 4 3 1 1 1 ", i + 1);
+      fprintf(f, "%d 4 3 %d 1 1 ", i + 1, tag);
       for (j = 0; j < 4; ++j) fprintf(f, "%d ", c[j] + 1);
       fprintf(f, "\n");
     }

@@ -59,6 +59,13 @@ typedef struct fea_deck {
   int *surface_nodes;           /* [count][nodes_per_face]                   */
   int *surface_kind;            /* [count] FEAHIP_LOAD_*                     */
   double *surface_values;       /* [count][3]: pressure in [0], or t0        */
+  /* material table (feahip_set_materials), optional: (materials (material
+   * :lambda l :mu m) ...) inside (model ...) and (element-materials i0 i1 ...)
+   * inside (geometry ...), one id per element in deck order.  Both or neither;
+   * materials_count = 0: the single pair `parameters`                         */
+  int materials_count;
+  double *material_params;      /* [materials_count][2] = lambda, mu         */
+  int *element_material;        /* [elements_count], values in [0, count)    */
 } fea_deck;
 
 /* sexp_data_load (sexp_loader.c:275-327).  Returns 0, or -1 with a message
@@ -75,7 +82,7 @@ int fea_deck_save(const char *path, const fea_deck *deck);
 int fea_element_tables(int ele_type, int gauss_count, double *weights,
                        double *forms, double *dforms);
 
-/* creates the device context for a deck, its surface loads installed */
+/* creates the device context for a deck, its surface loads and its material table installed */
 int fea_deck_create_solver(const fea_deck *deck, int device, feahip_ctx **ctx,
                            char *errbuf, int errlen);
 
@@ -116,7 +123,9 @@ int fea_solve_arclength_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, voi
  * nodes with %f, TET10 elements with local nodes 8 and 9 swapped, and per
  * load step (step 0 = zeros) NodeData "Displacements" and ElementData
  * "Stress tensor" (Gauss point 0) tagged load*0.83333333.  4-node elements
- * are written as Gmsh type 4.                                                */
+ * are written as Gmsh type 4.  A deck with a material table writes the
+ * element's material as its first tag, the physical entity, numbered from 1
+ * as everything in the file (material id + 1); other decks write 1.          */
 int fea_export_gmsh(const char *filename, const fea_deck *deck,
                     const fea_step_snapshot *steps, int nsteps);
 

@@ -36,6 +36,13 @@ int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
     feahip_destroy(*ctx);
     *ctx = NULL;
+    return rc;
+  }
+  if (d->materials_count > 0 &&
+      (rc = feahip_set_materials(*ctx, d->materials_count, d->material_params, d->element_material))) {
+    if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
+    feahip_destroy(*ctx);
+    *ctx = NULL;
   }
   return rc;
 }

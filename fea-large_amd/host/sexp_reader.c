@@ -28,6 +28,7 @@ typedef struct {
   FILE *f;
   int line;
   char err[256];
+  int n_element_material;        /* ids read by (element-materials ...), -1: no such section */
 } reader;
 
 enum { T_EOF, T_OPEN, T_CLOSE, T_ATOM };
@@ -311,6 +312,57 @@ static int read_surface(reader *r, fea_deck *d)
   return 0;
 }
 
+/* (materials (material :lambda l :mu m) ...) inside (model ...): the table of feahip_set_materials */
+static int read_materials(reader *r, fea_deck *d)
+{
+  char buf[TOK_MAX];
+  size_t n = 0;
+  double *p = (double *)malloc(FEAHIP_MAX_MATERIALS * 2 * sizeof(double));   /* the largest table there is */
+  int rc = 0;
+  if (!p) return fail(r, "out of memory reading (materials ...)");
+  for (;;) {
+    attr a[ATTR_MAX];
+    int na, t = next_token(r, buf);
+    if (t == T_CLOSE) break;
+    if (t != T_OPEN || next_token(r, buf) != T_ATOM || !ieq(buf, "material")) { rc = fail(r, "expected (material :lambda l :mu m)"); break; }
+    if (n == FEAHIP_MAX_MATERIALS) { rc = fail(r, "more than 256 materials"); break; }   /* the 257th: read no further */
+    if ((rc = read_attrs(r, d, a, &na, 0))) break;
+    if ((rc = need_num(r, a, na, "lambda", &p[2 * n]))) break;
+    if ((rc = need_num(r, a, na, "mu", &p[2 * n + 1]))) break;
+    n++;
+  }
+  if (!rc && n == 0) rc = fail(r, "(materials ...) without a (material ...)");
+  if (rc) { free(p); return rc; }
+  free(d->material_params);
+  d->material_params = p; d->materials_count = (int)n;
+  return 0;
+}
+
+/* (element-materials i0 i1 ...) inside (geometry ...): one material id per element, deck order.  Count and range
+ * are checked when the whole deck is read (the sections come in any order). */
+static int read_element_materials(reader *r, fea_deck *d, int *count)
+{
+  char buf[TOK_MAX];
+  size_t cap = 1024, n = 0;
+  int *p = (int *)malloc(cap * sizeof(int)), t;
+  if (!p) return fail(r, "out of memory reading (element-materials ...)");
+  while ((t = next_token(r, buf)) == T_ATOM) {
+    char *end;
+    if (n == cap) {
+      int *q = (int *)realloc(p, 2 * cap * sizeof(int));
+      if (!q) { free(p); return fail(r, "out of memory reading (element-materials ...)"); }
+      p = q; cap *= 2;
+    }
+    p[n] = (int)strtol(buf, &end, 10);
+    if (end == buf || *end) { free(p); return fail(r, "bad material id in element-materials"); }
+    n++;
+  }
+  if (t != T_CLOSE) { free(p); return fail(r, "element-materials must be a flat list of material ids"); }
+  free(d->element_material);
+  d->element_material = p; *count = (int)n;
+  return 0;
+}
+
 /* one list, '(' consumed: dispatch on the head like traverse_function
  * (sexp_loader.c:249-272) */
 static int read_list(reader *r, fea_deck *d)
@@ -331,6 +383,8 @@ static int read_list(reader *r, fea_deck *d)
   if (ieq(head, "elements")) return read_elements(r, d);
   if (ieq(head, "prescribed-displacements")) return read_prescribed(r, d);
   if (ieq(head, "surface-loads")) return read_surface(r, d);
+  if (ieq(head, "materials")) return read_materials(r, d);
+  if (ieq(head, "element-materials")) return read_element_materials(r, d, &r->n_element_material);
 
   if (read_attrs(r, d, a, &na, 1)) return -1;
 
@@ -407,7 +461,7 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
   char buf[TOK_MAX];
   int t, rc;
   deck_defaults(deck);
-  r.line = 1; r.err[0] = 0;
+  r.line = 1; r.err[0] = 0; r.n_element_material = -1;
   r.f = fopen(path, "rt");
   if (!r.f) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "could not open file %s", path);
@@ -432,6 +486,19 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
       if (deck->elements[i] < 0 || deck->elements[i] >= deck->nodes_count) {
         rc = -1; snprintf(r.err, sizeof r.err, "element %d refers to node %d outside the node list", i / deck->nodes_per_element, deck->elements[i]);
       }
+    /* the material table: both sections or neither, one id per element, every id a row of the table */
+    if (rc == 0 && (deck->materials_count > 0) != (r.n_element_material >= 0)) {
+      rc = -1;
+      snprintf(r.err, sizeof r.err, deck->materials_count > 0 ? "deck has (materials ...) but no (element-materials ...)"
+                                                               : "deck has (element-materials ...) but no (materials ...)");
+    }
+    if (rc == 0 && deck->materials_count > 0 && r.n_element_material != deck->elements_count) {
+      rc = -1; snprintf(r.err, sizeof r.err, "element-materials has %d ids for %d elements", r.n_element_material, deck->elements_count);
+    }
+    for (i = 0; rc == 0 && deck->materials_count > 0 && i < deck->elements_count; ++i)
+      if (deck->element_material[i] < 0 || deck->element_material[i] >= deck->materials_count) {
+        rc = -1; snprintf(r.err, sizeof r.err, "element %d has material %d outside [0,%d)", i, deck->element_material[i], deck->materials_count);
+      }
   }
   if (rc) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", r.err);
@@ -447,6 +514,8 @@ void fea_deck_free(fea_deck *d)
   free(d->nodes); free(d->elements);
   free(d->presc_node); free(d->presc_type); free(d->presc_values);
   free(d->surface_nodes); free(d->surface_kind); free(d->surface_values);
+  free(d->material_params); free(d->element_material);
+  d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
   d->presc_node = d->presc_type = NULL; d->presc_values = NULL;
   d->surface_nodes = d->surface_kind = NULL; d->surface_values = NULL;
@@ -460,8 +529,15 @@ int fea_deck_save(const char *path, const fea_deck *d)
   int i, k;
   if (!f) return -1;
   fprintf(f, ";; -*- Mode: lisp; -*-\n(task\n");
-  fprintf(f, " (model :name %s\n        (model-parameters :mu %.17g :lambda %.17g))\n",
+  fprintf(f, " (model :name %s\n        (model-parameters :mu %.17g :lambda %.17g)",
           d->model == FEAHIP_MODEL_A5 ? "A5" : "COMPRESSIBLE_NEOHOOKEAN", d->parameters[1], d->parameters[0]);
+  if (d->materials_count > 0) {                      /* written only when there is a table: other decks save as before */
+    fprintf(f, "\n        (materials");
+    for (i = 0; i < d->materials_count; ++i)
+      fprintf(f, "\n         (material :lambda %.17g :mu %.17g)", d->material_params[2 * i], d->material_params[2 * i + 1]);
+    fprintf(f, ")");
+  }
+  fprintf(f, ")\n");
   fprintf(f, " (solution :desired-tolerance %.17g :task-type CARTESIAN3D :load-increments-count %d"
              " :modified-newton %s :max-newton-count %d\n",
           d->desired_tolerance, d->load_increments_count, d->modified_newton ? "yes" : "no", d->max_newton_count);
@@ -480,7 +556,13 @@ int fea_deck_save(const char *path, const fea_deck *d)
       fprintf(f, k ? " %d" : "%d", d->elements[(size_t)i * d->nodes_per_element + k]);
     fprintf(f, ")");
   }
-  fprintf(f, "))\n  (boundary-conditions\n   (prescribed-displacements");
+  fprintf(f, ")");
+  if (d->materials_count > 0) {
+    fprintf(f, "\n   (element-materials");
+    for (i = 0; i < d->elements_count; ++i) fprintf(f, i % 32 ? " %d" : "\n    %d", d->element_material[i]);
+    fprintf(f, ")");
+  }
+  fprintf(f, ")\n  (boundary-conditions\n   (prescribed-displacements");
   for (i = 0; i < d->prescribed_nodes_count; ++i)
     fprintf(f, "\n    (presc-node :y %.17g :x %.17g :z %.17g :type %d :node-id %d)", d->presc_values[3 * i + 1],
             d->presc_values[3 * i], d->presc_values[3 * i + 2], d->presc_type[i], d->presc_node[i]);

@@ -240,6 +240,38 @@ int feahip_set_surface_loads(feahip_ctx *ctx, int n_faces, int nodes_per_face, c
 int feahip_get_surface_forces(feahip_ctx *ctx, double *f);
 int feahip_set_load_factor(feahip_ctx *ctx, double lambda);
 int feahip_get_load_factor(feahip_ctx *ctx, double *lambda);
+
+/* ---- heterogeneous bodies: a table of (lambda, mu) pairs and one material id
+ * per element.  feahip_set_materials replaces the context's single pair by the
+ * table; n_materials = 0 returns to the pair given at creation.  At most
+ * FEAHIP_MAX_MATERIALS pairs.  The MODEL stays one per context (FEAHIP_MODEL_*
+ * is a compile-time parameter of the kernels): the table varies its two
+ * parameters, not the law.
+ * params[n_materials][2] = lambda, mu; elem_material[E] has values in
+ * [0, n_materials), in the CALLER's element order: the whole mesh's on a
+ * feahip_create / feahip_create_rank context (a rank context keeps the entries
+ * of its own elements), the LOCAL order on a feahip_create_rank_local context.
+ * On row shards and in-process groups every context gets the same call.
+ * FEAHIP_EINVAL (feahip_last_error names the offending index): null arrays with
+ * n_materials > 0, n_materials > FEAHIP_MAX_MATERIALS, an id outside
+ * [0, n_materials), a non-finite parameter; the context is left as it was.
+ * May be called at any time: the cached F and sigma are dropped, K and f are
+ * what the next assembly makes them, a stashed K is left alone, and gather maps
+ * built before are built again with the ids.  Strategies: GATHER, ROWOWNER and
+ * ATOMIC (and AUTO, which chooses among them) assemble with a table; STAGED
+ * and SHARED are refused with FEAHIP_EINVAL at the assembly.                  */
+#define FEAHIP_MAX_MATERIALS 256
+int feahip_set_materials(feahip_ctx *ctx, int n_materials, const double *params, const int *elem_material);
+/* the table in force: *n_materials (0: the single pair), and where non-null
+ * params[n][2] and elem_material (a first call with nulls sizes them).
+ * elem_material always has one entry per element of THIS context, in the
+ * context's own element order.  On a feahip_create_rank context that is the
+ * LOCAL order of the rank's elements (feahip_rank_maps: elem_global), NOT the
+ * whole-mesh order feahip_set_materials takes there: what this call returns
+ * cannot be passed back to feahip_set_materials on such a context without
+ * scattering it through elem_global first.  On every other context get and
+ * set use the same order.                                                     */
+int feahip_get_materials(feahip_ctx *ctx, int *n_materials, double *params, int *elem_material);
 /* Host-only (no device): resolve faces to (owning element, local face) exactly
  * as feahip_set_surface_loads does; returns FEAHIP_EINVAL with the index of
  * the first bad face in *bad (-1 when all resolve).  Local faces: TET4 / TET10
