@@ -249,6 +249,97 @@ int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newto
   return FEAHIP_OK;
 }
 
+// ---- implicit dynamics: Newmark steps in displacement form, full Newton (feahip_solve_dynamic) ----------------
+// Per step, a0 = 1 / (beta dt^2): predictor xt = x + dt v + dt^2 (1/2 - beta) a, vt = v + dt (1 - gamma) a on all nodes
+// of every context; one increment of the prescribed dofs and the load factor; Newton on K + a0 M with the residual
+// f = lambda F_ext - T - a0 M (x - xt); corrector a = a0 (x - xt), v = vt + gamma dt a.  Acceleration and velocity are
+// pointwise functions of x, which every rank holds at its halo nodes after dist_update_nodes_with_solution: no
+// exchange beyond the static loop's.
+namespace {
+struct NodeCopies {
+  std::vector<double *> p;
+  ~NodeCopies() { for (double *q : p) if (q) (void)hipFree(q); }
+};
+}
+
+int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double beta, double gamma, double dlambda,
+                 int max_newton, double desired_tolerance, int solver_type, double solver_tolerance, int solver_max_iter,
+                 double *tol_log, int tol_log_cap, int *its_log, int *steps_done)
+{
+  int rc, nlog = 0, step = 0;
+  const double a0 = 1.0 / (beta * dt * dt);
+  NodeCopies xn;                                                      // x at the start of the step in hand
+#define EACH(call) for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); if ((rc = (call))) return rc; }
+  EACH(mass_ensure(c, "feahip_solve_dynamic"));
+  for (feahip_ctx *c : R) {
+    (void)hipSetDevice(c->device);
+    double *q = nullptr;
+    FEA_HIP_CHECK(c, hipMalloc((void **)&q, sizeof(double) * 4 * (size_t)c->N));
+    xn.p.push_back(q);
+  }
+  // (full Newton only: the context's line search and modified Newton are not consulted)
+  for (; step < n_steps; ++step) {
+    int it = 0, k = 0;
+    double tolerance = 0;
+    for (feahip_ctx *c : R) {
+      (void)hipSetDevice(c->device);
+      FEA_HIP_CHECK(c, hipMemcpyAsync(xn.p[k++], c->d_x, sizeof(double) * 4 * (size_t)c->N, hipMemcpyDeviceToDevice, c->stream));
+    }
+    EACH(launch_newmark_predict(c, dt, beta, gamma));
+    EACH(feahip_update_nodes_with_bc(c, dlambda));
+    do {
+      it++;
+      EACH(feahip_create_stiffness_and_residual(c));
+      EACH(launch_mass_residual(c, a0));
+      EACH(launch_mass_add(c, a0));
+      EACH(feahip_apply_prescribed_bc(c, 0.0));
+      if ((rc = dist_solve_pcg(R, solver_type, solver_tolerance, solver_max_iter, nullptr, nullptr))) return rc;
+      if ((rc = dist_energy(R, &tolerance))) return rc;
+      if (tol_log && nlog < tol_log_cap) tol_log[nlog] = tolerance;
+      nlog++;
+      if ((rc = dist_update_nodes_with_solution(R, nullptr))) return rc;
+      EACH(feahip_update_state(c, nullptr));
+    } while (fabs(tolerance) > desired_tolerance && it < max_newton);
+    if (its_log) its_log[step] = it;
+    if (it == max_newton) {                                           // as feahip_solve: the step is not counted ...
+      k = 0;
+      for (feahip_ctx *c : R) {                                       // ... and the state stays that of the last completed one
+        (void)hipSetDevice(c->device);
+        FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_x, xn.p[k++], sizeof(double) * 4 * (size_t)c->N, hipMemcpyDeviceToDevice, c->stream));
+        c->load_factor -= dlambda;
+        c->state_valid = false;
+      }
+      break;
+    }
+    EACH(launch_newmark_correct(c, dt, beta, gamma));
+    for (feahip_ctx *c : R) c->mass.time += dt;
+  }
+  if (steps_done) *steps_done = step;
+  for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
+  return FEAHIP_OK;
+}
+
+// M a = lambda F_ext(x) - T(x), a = 0 on the prescribed dofs: the ordinary solve with K := M
+int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, double tol, int max_iter)
+{
+  int rc;
+  EACH(mass_ensure(c, "feahip_consistent_acceleration"));
+  for (feahip_ctx *c : R) {
+    (void)hipSetDevice(c->device);
+    FEA_HIP_CHECK(c, hipMemsetAsync(c->d_K_base, 0, sizeof(double) * 9 * (size_t)(c->kb1 - c->kb0), c->stream));
+    c->k_bc = false; c->k_valid = true;
+  }
+  EACH(launch_mass_add(c, 1.0));
+  EACH(feahip_create_residual_forces(c));
+  EACH(feahip_apply_prescribed_bc(c, 0.0));
+  if ((rc = dist_solve_pcg(R, solver_type, tol, max_iter, nullptr, nullptr))) return rc;
+  if (R[0]->tr && (rc = R[0]->tr->exchange(R, 1))) return rc;        // the owners' rows of u to the halo copies
+  EACH(launch_vec3_to_nodes(c, c->d_u, c->mass.d_acc));
+  for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); ++c->k_epoch; FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
+  return FEAHIP_OK;
+}
+#undef EACH
+
 // ---- arc-length continuation on the surface loads (feahip_solve_arclength) -------
 // Crisfield's cylindrical arc length, one unsharded context.  The linear algebra of a corrector iteration is ONE
 // two-column solve K [du_R, du_F] = [R, F] (kernels_solve2.hip) and one fused reduction over Du, du_R, du_F, R.

@@ -466,6 +466,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   delete c->h_pat; c->h_pat = nullptr;
   c->generic.release(); c->visits.release(); c->quad.release(); c->gather.release(); c->gather10.release();
   c->surf.release();
+  c->mass.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -704,6 +705,12 @@ extern "C" int feahip_set_materials(feahip_ctx *c, int n_materials, const double
   }
   dev_free({c->d_mat, c->d_elem_mat});
   c->d_mat = d_mat; c->d_elem_mat = d_elem_mat;
+  // a mass with one density per material: a table of another size drops it (the next call that needs the mass says
+  // so); the same size keeps the densities and m is assembled again with the new ids on next use
+  if (c->mass.set && c->mass.n_rho > 1) {
+    if (n_materials != c->mass.n_mat) c->mass.stale = true;
+    c->mass.release_m();
+  }
   c->n_materials = n_materials;
   c->h_mat_params.assign(params, params + (n_materials ? 2 * (size_t)n_materials : 0));
   c->h_elem_mat.swap(ids);
@@ -938,6 +945,136 @@ extern "C" int feahip_get_forces(feahip_ctx *c, double *f) { CTX_GUARD(c); retur
 extern "C" int feahip_get_solution(feahip_ctx *c, double *u) { CTX_GUARD(c); return get_node_vec(c, c->d_u, u); }
 extern "C" int feahip_set_forces(feahip_ctx *c, const double *f) { CTX_GUARD(c); return set_node_vec(c, c->d_f, f); }
 
+// ---- consistent mass, body force and implicit dynamics (kernels_mass.hip, dist.hip) -------------------------------
+extern "C" int feahip_set_mass(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights,
+                               const double *forms, const double *dforms)
+{
+  CTX_GUARD_NOK(c);
+  if (n_rho < 0) { c->err = "feahip_set_mass: negative density count"; return FEAHIP_EINVAL; }
+  return mass_set(c, n_rho, rho, mass_points, weights, forms, dforms);
+}
+
+extern "C" int feahip_set_body_force(feahip_ctx *c, const double *b)
+{
+  CTX_GUARD_NOK(c);
+  return mass_set_body_force(c, b);
+}
+
+// node records ([N][4], library ids) to and from [N][3] in the caller's ids
+static int get_node4(feahip_ctx *c, const double *d, double *h)
+{
+  if (!h) return FEAHIP_EINVAL;
+  std::vector<double> pad((size_t)c->N * 4);
+  FEA_HIP_CHECK(c, hipMemcpyAsync(pad.data(), d, sizeof(double) * pad.size(), hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  for (int a = 0; a < c->N; ++a)
+    for (int j = 0; j < 3; ++j) h[(size_t)a * 3 + j] = pad[(size_t)lib_id(c, a) * 4 + j];
+  return FEAHIP_OK;
+}
+
+static int set_node4(feahip_ctx *c, double *d, const double *h)
+{
+  if (!h) return FEAHIP_EINVAL;
+  std::vector<double> pad((size_t)c->N * 4, 0.0);
+  for (int a = 0; a < c->N; ++a)
+    for (int j = 0; j < 3; ++j) pad[(size_t)lib_id(c, a) * 4 + j] = h[(size_t)a * 3 + j];
+  FEA_HIP_CHECK(c, hipMemcpyAsync(d, pad.data(), sizeof(double) * pad.size(), hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+#define MASS_GUARD(c, who)                                         \
+  CTX_GUARD_NOK(c);                                                \
+  { const int _rm = mass_ensure(c, who); if (_rm) return _rm; }
+
+extern "C" int feahip_set_velocities(feahip_ctx *c, const double *v) { MASS_GUARD(c, "feahip_set_velocities"); return set_node4(c, c->mass.d_vel, v); }
+extern "C" int feahip_get_velocities(feahip_ctx *c, double *v) { MASS_GUARD(c, "feahip_get_velocities"); return get_node4(c, c->mass.d_vel, v); }
+extern "C" int feahip_set_accelerations(feahip_ctx *c, const double *a) { MASS_GUARD(c, "feahip_set_accelerations"); return set_node4(c, c->mass.d_acc, a); }
+extern "C" int feahip_get_accelerations(feahip_ctx *c, double *a) { MASS_GUARD(c, "feahip_get_accelerations"); return get_node4(c, c->mass.d_acc, a); }
+
+extern "C" int feahip_get_time(feahip_ctx *c, double *t)
+{
+  if (!c || !t) return FEAHIP_EINVAL;
+  *t = c->mass.time;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_set_time(feahip_ctx *c, double t)
+{
+  if (!c) return FEAHIP_EINVAL;
+  c->mass.time = t;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_mass_spmv(feahip_ctx *c, const double *x, double *y)
+{
+  MASS_GUARD(c, "feahip_mass_spmv");
+  if (!x || !y) return FEAHIP_EINVAL;
+  int rc;
+  if ((rc = set_node4(c, c->mass.d_xt, x))) return rc;             // (xt is free outside a step)
+  FEA_HIP_CHECK(c, hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream));   // rows of other ranks: 0
+  if ((rc = launch_mass_product(c, c->mass.d_xt, c->d_q))) return rc;
+  return get_node_vec(c, c->d_q, y);
+}
+
+// the ranks a collective call made on one context drives: the members of its in-process group, or the context alone
+static std::vector<feahip_ctx *> ranks_of(feahip_ctx *c)
+{
+  if (c->tr && c->tr->members()) return *c->tr->members();
+  return std::vector<feahip_ctx *>(1, c);
+}
+
+extern "C" int feahip_consistent_acceleration(feahip_ctx *c, int solver_type, double tol, int max_iter)
+{
+  CTX_GUARD(c);
+  if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "unknown solver type"; return FEAHIP_EINVAL; }
+  if (max_iter <= 0) { c->err = "max_iterations must be positive"; return FEAHIP_EINVAL; }
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  const int rc = dist_consistent_acceleration(R, solver_type, tol, max_iter);
+  if (rc && c->err.empty()) c->err = R[0]->err;
+  return rc;
+}
+
+static int dynamic_args(feahip_ctx *c, int n_steps, double dt, double beta, double gamma, int max_newton, int solver_type,
+                        int solver_max_iter, int *steps_done)
+{
+  if (steps_done) *steps_done = 0;
+  if (!(dt > 0.0) || !std::isfinite(dt)) { c->err = "solve_dynamic: dt must be positive"; return FEAHIP_EINVAL; }
+  if (!(beta > 0.0) || !std::isfinite(beta)) { c->err = "solve_dynamic: beta must be positive"; return FEAHIP_EINVAL; }
+  if (!(gamma >= 0.0) || !std::isfinite(gamma)) { c->err = "solve_dynamic: gamma must not be negative"; return FEAHIP_EINVAL; }
+  if (n_steps < 0 || max_newton <= 0 || solver_max_iter <= 0) { c->err = "solve_dynamic: n_steps >= 0, max_newton and solver_max_iter positive"; return FEAHIP_EINVAL; }
+  if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "unknown solver type"; return FEAHIP_EINVAL; }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_solve_dynamic(feahip_ctx *c, int n_steps, double dt, double beta, double gamma, double dlambda,
+                                    int max_newton, double desired_tolerance, int solver_type, double solver_tolerance,
+                                    int solver_max_iter, double *tol_log, int tol_log_cap, int *its_log, int *steps_done)
+{
+  CTX_GUARD(c);
+  int rc;
+  if ((rc = dynamic_args(c, n_steps, dt, beta, gamma, max_newton, solver_type, solver_max_iter, steps_done))) return rc;
+  std::vector<feahip_ctx *> R(1, c);
+  return dist_dynamic(R, n_steps, dt, beta, gamma, dlambda, max_newton, desired_tolerance, solver_type, solver_tolerance,
+                      solver_max_iter, tol_log, tol_log_cap, its_log, steps_done);
+}
+
+extern "C" int feahip_group_solve_dynamic(feahip_ctx **ctxs, int n, int n_steps, double dt, double beta, double gamma,
+                                          double dlambda, int max_newton, double desired_tolerance, int solver_type,
+                                          double solver_tolerance, int solver_max_iter, double *tol_log, int tol_log_cap,
+                                          int *its_log, int *steps_done)
+{
+  std::vector<feahip_ctx *> R;
+  int rc = group_vec(ctxs, n, R);
+  if (rc) return rc;
+  if ((rc = dynamic_args(R[0], n_steps, dt, beta, gamma, max_newton, solver_type, solver_max_iter, steps_done))) return rc;
+  for (feahip_ctx *c : R) { CTX_GUARD(c); }
+  rc = dist_dynamic(R, n_steps, dt, beta, gamma, dlambda, max_newton, desired_tolerance, solver_type, solver_tolerance,
+                    solver_max_iter, tol_log, tol_log_cap, its_log, steps_done);
+  if (rc && R[0]->err.empty()) for (feahip_ctx *c : R) if (!c->err.empty()) { R[0]->err = c->err; break; }
+  return rc;
+}
+
 // ---- two-column solve (kernels_solve2.hip) ---------------------------------
 static int solve2_ready(feahip_ctx *c, const char *who)
 {
@@ -991,6 +1128,7 @@ extern "C" int feahip_solve_arclength(feahip_ctx *c, double lambda_max, int max_
   if (max_steps <= 0 || max_newton <= 0 || solver_max_iter <= 0) { c->err = "solve_arclength: max_steps, max_newton and solver_max_iter must be positive"; return FEAHIP_EINVAL; }
   int rc;
   if ((rc = solve2_refused(c, "solve_arclength"))) return rc;
+  if (c->mass.body[0] != 0.0 || c->mass.body[1] != 0.0 || c->mass.body[2] != 0.0) { c->err = "solve_arclength: a body force is set on this context (not followed by the arc length)"; return FEAHIP_EINVAL; }
   if (c->surf.nfaces == 0) { c->err = "solve_arclength: no surface loads on this context"; return FEAHIP_ESTATE; }
   if ((rc = ensure_solve2(c))) return rc;
   return arclength_solve(c, lambda_max, max_steps, max_newton, desired_tolerance, solver_type, solver_tolerance,
@@ -1273,6 +1411,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (rk) return rk;
     if (what == 7) return time_pcg2_iteration(c, warmup, iters, avg_ms);
   }
+  if (what == 8 || what == 9) {
+    if (!c->mass.set || c->mass.stale) { c->err = std::string(what == 8 ? "time_kernel(8)" : "time_kernel(9)") + ": no mass on this context (feahip_set_mass)"; return FEAHIP_EINVAL; }
+    const int rk = mass_ensure(c, "time_kernel");
+    if (rk) return rk;
+  }
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   auto one = [&]() -> int {
     switch (what) {
@@ -1282,6 +1425,8 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 3: return launch_spmv(c, c->d_p, c->d_q);
     case 5: return launch_surface_loads(c, c->d_f);
     case 6: return launch_spmv2(c, c->d2_p, c->d2_q);
+    case 8: return launch_mass_add(c, 1.0);
+    case 9: return launch_mass_residual(c, 1.0);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   };

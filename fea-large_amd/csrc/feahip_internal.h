@@ -389,6 +389,26 @@ struct SurfaceLoads {
   void release() { dev_free({d_fnode, d_kind, d_val, d_fc, d_lnode, d_lptr, d_lslot}); *this = SurfaceLoads(); }
 };
 
+// consistent mass and the kinematic state of the Newmark steps (kernels_mass.hip).  The parameters of the last
+// feahip_set_mass call stay on the host: m holds the block rows of the shard installed when it was assembled and is
+// assembled again (mass_ensure) when the shard has changed since.
+struct MassState {
+  bool set = false;                    // feahip_set_mass was called with n_rho > 0 and not cleared since
+  bool stale = false;                  // a per-material mass whose material count changed: every use is FEAHIP_ESTATE
+  int n_rho = 0, n_mat = 0, Gm = 0;    // n_mat: the material count the densities were given for
+  std::vector<double> rho, w, N, dN;   // [n_rho], [Gm], [Gm][npe], [Gm][3][npe]
+  double *d_m_base = nullptr;          // [kb1 - kb0] one double per owned block of K's pattern
+  double *d_m = nullptr;               // d_m_base - kb0: indexed by GLOBAL block number, as d_K
+  long long kb0 = -1, kb1 = -1;        // the window m was assembled for
+  // node vectors in the 32-byte layout of d_x ([N][4], the fourth double stays 0), all nodes of the context
+  double *d_vel = nullptr, *d_acc = nullptr, *d_xt = nullptr, *d_vt = nullptr;
+  double *d_body = nullptr;            // [3N] F_body = M (1 (x) b) on the owned rows, at load factor 1; null: none
+  double body[3] = {0, 0, 0};
+  double time = 0;
+  void release_m() { dev_free({d_m_base}); d_m_base = d_m = nullptr; kb0 = kb1 = -1; }
+  void release() { dev_free({d_m_base, d_vel, d_acc, d_xt, d_vt, d_body}); *this = MassState(); }
+};
+
 struct feahip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -525,6 +545,8 @@ struct feahip_ctx {
   double *d2_part = nullptr;   // 8 x FEA_RED_BLOCKS
   double *d2_scal = nullptr;   // 2 x 8
   int *d2_flag = nullptr;      // [2]
+  // consistent mass (kernels_mass.hip): nothing of it exists, and nothing below is launched, until feahip_set_mass
+  MassState mass;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -570,6 +592,23 @@ int launch_interleave(feahip_ctx *c, const double *a, const double *b, double *o
 int launch_deinterleave(feahip_ctx *c, const double *in2, double *a, double *b);
 int solve_pcg2(feahip_ctx *c, int type, double tol, int max_iter, int *iters, double *resid);   // d2_f -> d_u, d_u2
 int time_pcg2_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);
+// kernels_mass.hip -- consistent mass, body force and the vector kernels of the Newmark steps
+int mass_set(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights, const double *forms,
+             const double *dforms);
+int mass_ensure(feahip_ctx *c, const char *who);               // FEAHIP_ESTATE without a (valid) mass; m for the shard installed now
+int mass_set_body_force(feahip_ctx *c, const double *b);
+int launch_body_force(feahip_ctx *c, double *d_fv);            // d_fv += load_factor * F_body on the owned rows (nothing without one)
+int launch_mass_add(feahip_ctx *c, double coef);               // K += coef M on the diagonal entries of every owned block
+int launch_mass_residual(feahip_ctx *c, double a0);            // f -= a0 M (x - xt) on the owned rows
+int launch_mass_product(feahip_ctx *c, const double *d_v4, double *d_y);   // y = M v on the owned rows, v in the node layout
+int launch_newmark_predict(feahip_ctx *c, double dt, double beta, double gamma);
+int launch_newmark_correct(feahip_ctx *c, double dt, double beta, double gamma);
+int launch_vec3_to_nodes(feahip_ctx *c, const double *d_v3, double *d_v4);
+// dist.hip -- Newmark steps and the consistent acceleration over one or more ranks
+int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double beta, double gamma, double dlambda,
+                 int max_newton, double desired_tolerance, int solver_type, double solver_tolerance, int solver_max_iter,
+                 double *tol_log, int tol_log_cap, int *its_log, int *steps_done);
+int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, double tol, int max_iter);
 // dist.hip -- Crisfield's cylindrical arc length on the surface loads (one unsharded context)
 int arclength_solve(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
                     int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log, double *tol_log,

@@ -415,10 +415,11 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF)
   const int strat = resolve_assembly(c, doK);
   if (strat < 0) return strat;
   c->last_strategy = strat;                          // the kernel that runs, after the residual-only fallbacks
-  const int rc = dispatch_assembly(c, strat, doK, doF);
+  int rc = dispatch_assembly(c, strat, doK, doF);
   if (!rc && doK) c->k_valid = true;
   if (rc || !doF) return rc;
-  return launch_surface_loads(c, c->d_f);            // f = lambda F_ext - T (nothing to launch without loads)
+  if ((rc = launch_surface_loads(c, c->d_f))) return rc;   // f = lambda F_ext - T (nothing to launch without loads)
+  return launch_body_force(c, c->d_f);               // ... + lambda F_body (nothing to launch without a body force)
 }
 
 int launch_state_export(feahip_ctx *c, double *d_grads, double *d_detj)

@@ -118,7 +118,23 @@ ABI = {
     "feahip_coarse_info": [C.c_void_p, C.POINTER(C.c_longlong), _ip, _dp],
     "feahip_coarse_matrix": [C.c_void_p, _dp],
     "feahip_host_coarse_aggregates": [C.c_int, C.c_int, _ip],
+    "feahip_set_mass": [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
+    "feahip_mass_spmv": [C.c_void_p, _dp, _dp],
+    "feahip_set_body_force": [C.c_void_p, _dp],
+    "feahip_set_velocities": [C.c_void_p, _dp],
+    "feahip_get_velocities": [C.c_void_p, _dp],
+    "feahip_set_accelerations": [C.c_void_p, _dp],
+    "feahip_get_accelerations": [C.c_void_p, _dp],
+    "feahip_get_time": [C.c_void_p, _dp],
+    "feahip_set_time": [C.c_void_p, C.c_double],
+    "feahip_consistent_acceleration": [C.c_void_p, C.c_int, C.c_double, C.c_int],
+    "feahip_solve_dynamic": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int,
+                             C.c_double, C.c_int, _dp, C.c_int, _ip, _ip],
+    "feahip_group_solve_dynamic": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _dp, C.c_int, _ip, _ip],
 }
+# the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
+MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
 COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
 AMG_INFO_KEYS = ("levels", "gamma", "gamma_from", "gamma_until", "coarse_sweeps", "fine_bits", "coarse_f32", "fused_post",
                  "tail_from", "tail_entry", "tail_cop", "tail_lds_levels", "row0", "row1", "tail_blob")
@@ -163,6 +179,9 @@ class FeaDeck(C.Structure):
         ("surface_faces_count", C.c_int), ("surface_nodes_per_face", C.c_int), ("surface_nodes", _ip),
         ("surface_kind", _ip), ("surface_values", _dp),
         ("materials_count", C.c_int), ("material_params", _dp), ("element_material", _ip),
+        ("has_dynamics", C.c_int), ("dynamics_steps", C.c_int), ("dynamics_dt", C.c_double), ("dynamics_beta", C.c_double),
+        ("dynamics_gamma", C.c_double), ("dynamics_dlambda", C.c_double), ("density", C.c_double),
+        ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
     ]
 
 
@@ -233,6 +252,21 @@ def element_tables(ele_type, gauss_count):
     return w, forms, dforms
 
 
+def _take_dynamics(obj, kw):
+    """The implicit-dynamics fields of a Deck or a Slab: density (a number, or one per material for FeaSolver.set_mass; the
+    .sexp grammar holds one number), body_force[3] (an acceleration per unit mass) and dynamics = dict(steps, dt, beta,
+    gamma, dlambda)."""
+    obj.density = kw.get("density")
+    bf = kw.get("body_force")
+    obj.body_force = None if bf is None else np.ascontiguousarray(bf, dtype=np.float64).reshape(3)
+    dyn = kw.get("dynamics")
+    obj.dynamics = None if dyn is None else {"steps": int(dyn.get("steps", 0)), "dt": float(dyn["dt"]),
+                                             "beta": float(dyn.get("beta", 0.25)), "gamma": float(dyn.get("gamma", 0.5)),
+                                             "dlambda": float(dyn.get("dlambda", 0.0))}
+    if (obj.dynamics is not None or obj.body_force is not None) and obj.density is None:
+        raise ValueError("dynamics and body_force need a density")
+
+
 class Deck:
     """A task deck as numpy arrays (fields named as the reference's structs)."""
 
@@ -268,6 +302,7 @@ class Deck:
         self.element_material = np.ascontiguousarray(kw.get("element_material", []), dtype=np.int32)
         if len(self.element_material) != (len(self.elements) if len(self.materials) else 0):
             raise ValueError("materials and element_material come together, one id per element")
+        _take_dynamics(self, kw)
 
     @staticmethod
     def load(path):
@@ -295,7 +330,11 @@ class Deck:
                 surface_kind=np.ctypeslib.as_array(fd.surface_kind, (ns,)).copy() if ns else [],
                 surface_values=np.ctypeslib.as_array(fd.surface_values, (ns, 3)).copy() if ns else np.zeros((0, 3)),
                 materials=np.ctypeslib.as_array(fd.material_params, (nm, 2)).copy() if nm else np.zeros((0, 2)),
-                element_material=np.ctypeslib.as_array(fd.element_material, (e,)).copy() if nm else [])
+                element_material=np.ctypeslib.as_array(fd.element_material, (e,)).copy() if nm else [],
+                density=fd.density if fd.has_dynamics else None,
+                body_force=[fd.body_force[k] for k in range(3)] if fd.has_body_force else None,
+                dynamics=dict(steps=fd.dynamics_steps, dt=fd.dynamics_dt, beta=fd.dynamics_beta, gamma=fd.dynamics_gamma,
+                              dlambda=fd.dynamics_dlambda) if fd.has_dynamics else None)
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -324,6 +363,18 @@ class Deck:
         self.element_material = np.ascontiguousarray(self.element_material, dtype=np.int32)
         fd.materials_count = len(self.materials)
         fd.material_params, fd.element_material = _d(self.materials), _i(self.element_material)
+        if getattr(self, "density", None) is not None:
+            rho = np.atleast_1d(np.asarray(self.density, dtype=np.float64))
+            if len(rho) != 1:
+                raise ValueError("the deck grammar holds one density; per-material densities go through set_mass")
+            dyn = getattr(self, "dynamics", None) or {"steps": 0, "dt": 1.0, "beta": 0.25, "gamma": 0.5, "dlambda": 0.0}
+            fd.has_dynamics, fd.density = 1, float(rho[0])
+            fd.dynamics_steps, fd.dynamics_dt = dyn["steps"], dyn["dt"]
+            fd.dynamics_beta, fd.dynamics_gamma, fd.dynamics_dlambda = dyn["beta"], dyn["gamma"], dyn["dlambda"]
+            if getattr(self, "body_force", None) is not None:
+                fd.has_body_force = 1
+                for k in range(3):
+                    fd.body_force[k] = float(self.body_force[k])
         return fd
 
     def save(self, path):
@@ -358,6 +409,14 @@ class FeaSolver:
             raise FeaHipError(f"feahip_create failed ({rc}): {self._lib.feahip_create_error().decode()}")
         self._deck_surface_loads()
         self._deck_materials()
+        self._deck_mass()
+
+    def _deck_mass(self):
+        """Installs the deck's (or the slab's) density and body force, where it has them."""
+        if getattr(self.deck, "density", None) is not None:
+            self.set_mass(self.deck.density)
+            if getattr(self.deck, "body_force", None) is not None:
+                self.set_body_force(self.deck.body_force)
 
     def _deck_materials(self):
         """Installs the deck's (or the slab's) material table, where it has one."""
@@ -515,6 +574,87 @@ class FeaSolver:
             self._chk(rc)
         n = max(done.value, 0)
         return n, lam[:n], its[:n], tol, rc
+
+    # ---- consistent mass, body force, Newmark steps ------------------------
+    def set_mass(self, rho):
+        """feahip_set_mass with the mass rule of the element type (MASS_POINTS).  rho: one density, or one per material
+        of the table in force; None (or an empty list) clears the mass, the body force, velocities and accelerations."""
+        rho = np.zeros(0) if rho is None else np.ascontiguousarray(np.atleast_1d(rho), dtype=np.float64).ravel()
+        if len(rho) == 0:
+            self._chk(self._lib.feahip_set_mass(self._ctx, 0, None, 0, None, None, None))
+            return
+        gm = MASS_POINTS[self.deck.ele_type]
+        w, forms, dforms = element_tables(self.deck.ele_type, gm)
+        self._chk(self._lib.feahip_set_mass(self._ctx, len(rho), _d(rho), gm, _d(w), _d(forms), _d(dforms)))
+
+    def mass_spmv(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        assert len(x) == self.ndof
+        y = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_mass_spmv(self._ctx, _d(x), _d(y)))
+        return y
+
+    def set_body_force(self, b):
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(3)
+        self._chk(self._lib.feahip_set_body_force(self._ctx, None if b is None else _d(b)))
+
+    def _node_get(self, fn):
+        v = np.zeros((self.N, 3))
+        self._chk(fn(self._ctx, _d(v)))
+        return v
+
+    def _node_set(self, fn, v):
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert v.shape == (self.N, 3)
+        self._chk(fn(self._ctx, _d(v)))
+
+    def velocities(self):
+        return self._node_get(self._lib.feahip_get_velocities)
+
+    def set_velocities(self, v):
+        self._node_set(self._lib.feahip_set_velocities, v)
+
+    def accelerations(self):
+        return self._node_get(self._lib.feahip_get_accelerations)
+
+    def set_accelerations(self, a):
+        self._node_set(self._lib.feahip_set_accelerations, a)
+
+    def time(self):
+        t = C.c_double(0)
+        self._chk(self._lib.feahip_get_time(self._ctx, C.byref(t)))
+        return t.value
+
+    def set_time(self, t):
+        self._chk(self._lib.feahip_set_time(self._ctx, float(t)))
+
+    def consistent_acceleration(self, solver_type=None, tolerance=None, max_iterations=None):
+        """Solves M a = lambda F_ext(x) - T(x) into the accelerations (collective on a group: one call drives it)."""
+        d = self.deck
+        self._chk(self._lib.feahip_consistent_acceleration(
+            self._ctx, d.solver_type if solver_type is None else solver_type,
+            d.solver_tolerance if tolerance is None else tolerance,
+            d.solver_max_iter if max_iterations is None else max_iterations))
+
+    def solve_dynamic(self, n_steps=None, dt=None, beta=None, gamma=None, dlambda=None, max_newton=None,
+                      desired_tolerance=None, solver_type=None, solver_tolerance=None, solver_max_iter=None):
+        """feahip_solve_dynamic; arguments left out come from the deck (its `dynamics`).  Returns (steps done, its_log,
+        tol_log)."""
+        d = self.deck
+        dyn = getattr(d, "dynamics", None) or {}
+        ns = int(dyn.get("steps", 0) if n_steps is None else n_steps)
+        mn = d.max_newton_count if max_newton is None else max_newton
+        cap = max(ns * mn, 1)
+        tol_log, its, done = np.zeros(cap), np.zeros(max(ns, 1), dtype=np.int32), C.c_int(0)
+        self._chk(self._lib.feahip_solve_dynamic(
+            self._ctx, ns, float(dyn.get("dt", 0.0) if dt is None else dt), float(dyn.get("beta", 0.25) if beta is None else beta),
+            float(dyn.get("gamma", 0.5) if gamma is None else gamma), float(dyn.get("dlambda", 0.0) if dlambda is None else dlambda),
+            mn, d.desired_tolerance if desired_tolerance is None else desired_tolerance,
+            d.solver_type if solver_type is None else solver_type,
+            d.solver_tolerance if solver_tolerance is None else solver_tolerance,
+            d.solver_max_iter if solver_max_iter is None else solver_max_iter, _d(tol_log), cap, _i(its), C.byref(done)))
+        n = int(its[:min(done.value + 1, ns)].sum())
+        return done.value, its[:ns], tol_log[:n]
 
     # ---- surface loads ---------------------------------------------------
     def set_surface_loads(self, faces, kind, values):
@@ -920,6 +1060,7 @@ class RankSolver(FeaSolver):
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
         self._deck_surface_loads()                              # the whole face list: the rank keeps what touches its nodes
         self._deck_materials()                                  # the whole mesh's ids: the rank keeps its own elements'
+        self._deck_mass()
 
 
 def host_rank_mesh(deck, rank, nranks, pattern=False):
@@ -1005,6 +1146,7 @@ class Slab:
         self.element_material = np.ascontiguousarray(kw.get("element_material", []), dtype=np.int32)
         if len(self.element_material) != (len(self.elements) if len(self.materials) else 0):
             raise ValueError("materials and element_material come together, one id per element")
+        _take_dynamics(self, kw)
 
     def permuted(self, new_local_id):
         """The same slab with local node a renamed new_local_id[a] (owned ids must stay in [0, n_own))."""
@@ -1064,6 +1206,7 @@ class LocalRankSolver(FeaSolver):
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
         self._deck_surface_loads()                              # local ids; faces of other ranks' nodes are dropped
         self._deck_materials()                                  # the slab's own ids, in its element order
+        self._deck_mass()
 
 
 def host_rank_local_plan(slab, rank, nranks):
@@ -1114,7 +1257,7 @@ def slab_of(deck, rank, nranks):
                 n_global_nodes=N, halo_owner=owner[ng[no:]], presc_node=local_of[deck.presc_node[keep]] if keep.any() else [],
                 presc_type=deck.presc_type[keep] if keep.any() else [],
                 presc_values=deck.presc_values[keep] if keep.any() else np.zeros((0, 3)), **kw)
-    for k in ("linesearch_max", "arclength_max"):
+    for k in ("linesearch_max", "arclength_max", "density", "body_force", "dynamics"):
         if hasattr(deck, k):
             setattr(slab, k, getattr(deck, k))
     return slab
@@ -1210,6 +1353,25 @@ class FeaGroup:
                                                desired_tolerance, solver_type, solver_tolerance, solver_max_iter,
                                                _d(tol_log), cap, _i(its), C.byref(done)))
         return done.value, its, tol_log[:int(its.sum())]
+
+    def set_mass(self, rho):
+        self.each("set_mass", rho)
+
+    def set_body_force(self, b):
+        self.each("set_body_force", b)
+
+    def consistent_acceleration(self, solver_type, tolerance=1e-14, max_iterations=20000):
+        self.ranks[0].consistent_acceleration(solver_type, tolerance, max_iterations)   # one call drives the group
+
+    def solve_dynamic(self, n_steps, dt, beta, gamma, dlambda, max_newton, desired_tolerance, solver_type,
+                      solver_tolerance=1e-14, solver_max_iter=20000):
+        cap = max(n_steps * max_newton, 1)
+        tol_log, its, done = np.zeros(cap), np.zeros(max(n_steps, 1), dtype=np.int32), C.c_int(0)
+        self._chk(self._lib.feahip_group_solve_dynamic(self._arr, self.n, n_steps, dt, beta, gamma, dlambda, max_newton,
+                                                       desired_tolerance, solver_type, solver_tolerance, solver_max_iter,
+                                                       _d(tol_log), cap, _i(its), C.byref(done)))
+        n = int(its[:min(done.value + 1, n_steps)].sum())
+        return done.value, its[:n_steps], tol_log[:n]
 
     def gather(self, name):
         """Owned rows of a per-node ([N][3]) or per-dof ([3N]) getter, stitched together."""

@@ -82,6 +82,30 @@ int fea_solve_arclength_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *
   return rc ? rc : done;
 }
 
+/* (dynamics :steps N ...) with N > 0: the Newmark steps of feahip_solve_dynamic; the final state is the one snapshot */
+int fea_solve_dynamic_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *logp, fea_step_snapshot *last)
+{
+  FILE *log = (FILE *)logp;
+  struct snap_sink k;
+  const int n = d->dynamics_steps;
+  int *its = (int *)calloc((size_t)(n > 0 ? n : 1), sizeof *its);
+  int done = 0, rc, i;
+  if (!its) return FEAHIP_ENOMEM;
+  rc = feahip_solve_dynamic(ctx, n, d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda,
+                            d->max_newton_count, d->desired_tolerance, d->solver_type, d->solver_tolerance,
+                            d->solver_max_iter, NULL, 0, its, &done);
+  if (log)
+    for (i = 0; i < done; ++i)
+      fprintf(log, "Dynamic step %d finished: time %.17g, %d iterations\n", i + 1, (i + 1) * d->dynamics_dt, its[i]);
+  free(its);
+  if (rc) return rc;
+  if (done < n && log) fprintf(log, "Unable to finish dynamic step %d in %d Newton iterations,exit\n", done + 1, d->max_newton_count);
+  k.steps = last; k.cap = 1; k.S = NULL;
+  rc = keep_snapshot(d, ctx, 0, &k);
+  free(k.S);
+  return rc ? rc : done;
+}
+
 int fea_export_gmsh(const char *filename, const fea_deck *d, const fea_step_snapshot *steps, int nsteps)
 {
   FILE *f = fopen(filename, "w+");

@@ -66,6 +66,18 @@ typedef struct fea_deck {
   int materials_count;
   double *material_params;      /* [materials_count][2] = lambda, mu         */
   int *element_material;        /* [elements_count], values in [0, count)    */
+  /* implicit dynamics, optional: (dynamics :steps N :dt x :beta b :gamma g
+   * :dlambda l :density rho) inside (solution ...) -- :beta 0.25, :gamma 0.5 and
+   * :dlambda 0 where absent -- installs a uniform consistent mass
+   * (feahip_set_mass); :steps > 0 runs feahip_solve_dynamic instead of the load
+   * increments.  (body-force :x :y :z) inside (boundary-conditions ...) needs
+   * the density (feahip_set_body_force).  Written by fea_deck_save only when
+   * present                                                                   */
+  int has_dynamics;
+  int dynamics_steps;
+  double dynamics_dt, dynamics_beta, dynamics_gamma, dynamics_dlambda, density;
+  int has_body_force;
+  double body_force[3];
 } fea_deck;
 
 /* sexp_data_load (sexp_loader.c:275-327).  Returns 0, or -1 with a message
@@ -82,7 +94,10 @@ int fea_deck_save(const char *path, const fea_deck *deck);
 int fea_element_tables(int ele_type, int gauss_count, double *weights,
                        double *forms, double *dforms);
 
-/* creates the device context for a deck, its surface loads and its material table installed */
+/* the mass rule of an element type (exact for straight-sided elements): 4 points for TET4, 27 for TET10, 8 for
+ * HEXAHEDRA8; 0 for an unknown type                                          */
+int fea_mass_points(int ele_type);
+/* creates the device context for a deck, its surface loads, its material table, its mass and its body force installed */
 int fea_deck_create_solver(const fea_deck *deck, int device, feahip_ctx **ctx,
                            char *errbuf, int errlen);
 
@@ -118,6 +133,11 @@ void fea_snapshots_free(fea_step_snapshot *steps, int n);
  * Returns the completed steps or a negative FEAHIP_E* code.                  */
 int fea_solve_arclength_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void *log,
                                       fea_step_snapshot *last);
+
+/* The run of a deck with (dynamics :steps N ...), N > 0: feahip_solve_dynamic; one log line per completed step
+ * ("Dynamic step k finished: time t, n iterations"); *last receives the final state.  Returns the completed steps
+ * or a negative FEAHIP_E* code.                                               */
+int fea_solve_dynamic_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void *log, fea_step_snapshot *last);
 
 /* solver_export_tetrahedra10_gmsh (fea_solver.c:1375-1488): Gmsh 2.0 ASCII,
  * nodes with %f, TET10 elements with local nodes 8 and 9 swapped, and per

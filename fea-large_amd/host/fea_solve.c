@@ -13,6 +13,22 @@
 #include <string.h>
 #include "fea_host.h"
 
+int fea_mass_points(int ele_type)
+{
+  return ele_type == FEA_TETRAHEDRA4 ? 4 : ele_type == FEA_TETRAHEDRA10 ? 27 : ele_type == FEA_HEXAHEDRA8 ? 8 : 0;
+}
+
+/* the deck's uniform mass and its body force */
+static int install_mass(const fea_deck *d, feahip_ctx *ctx)
+{
+  double w[32], forms[32 * 10], dforms[32 * 3 * 10];
+  const int gm = fea_mass_points(d->ele_type);
+  int rc;
+  if (gm <= 0 || fea_element_tables(d->ele_type, gm, w, forms, dforms) != d->nodes_per_element) return FEAHIP_EINVAL;
+  if ((rc = feahip_set_mass(ctx, 1, &d->density, gm, w, forms, dforms))) return rc;
+  return d->has_body_force ? feahip_set_body_force(ctx, d->body_force) : 0;
+}
+
 int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char *errbuf, int errlen)
 {
   double w[32], dforms[32 * 3 * 10];
@@ -40,6 +56,12 @@ int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char
   }
   if (d->materials_count > 0 &&
       (rc = feahip_set_materials(*ctx, d->materials_count, d->material_params, d->element_material))) {
+    if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
+    feahip_destroy(*ctx);
+    *ctx = NULL;
+    return rc;
+  }
+  if (d->has_dynamics && (rc = install_mass(d, *ctx))) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
     feahip_destroy(*ctx);
     *ctx = NULL;

@@ -7,7 +7,9 @@
  * A deck with (arc-length :max N), N > 0, and a (surface-loads ...) section is
  * followed along its equilibrium path by feahip_solve_arclength (N steps at
  * most, up to the load factor load-increments); the file then holds the final
- * state as its one step.  Every other deck takes the reference's loop.
+ * state as its one step.  A deck with (dynamics :steps N ...), N > 0, takes N
+ * Newmark steps (feahip_solve_dynamic) and likewise writes the final state.
+ * Every other deck takes the reference's loop.
  *
  * One option the reference does not have, after the deck name:
  *   --multigrid   PCG_ILU / CHOLESKY solves use the aggregation-multigrid
@@ -26,7 +28,7 @@ int main(int argc, char **argv)
   feahip_ctx *ctx = NULL;
   char err[512], *msh;
   fea_step_snapshot *steps;
-  int done, rc, cap, arc, status = 0;
+  int done, rc, cap, arc, dyn, status = 0;
   if (argc < 2) {
     printf("Usage: fea_solve input_data.sexp\n");            /* fea_solver.c:328 */
     return 1;
@@ -52,7 +54,9 @@ int main(int argc, char **argv)
   steps = (fea_step_snapshot *)calloc((size_t)cap, sizeof *steps);
   /* (arc-length :max N) with N > 0 and surface loads: path following instead of load control */
   arc = deck.arclength_max > 0 && deck.surface_faces_count > 0;
-  if (arc) done = fea_solve_arclength_with_snapshot(&deck, ctx, stdout, steps);
+  dyn = deck.has_dynamics && deck.dynamics_steps > 0;
+  if (dyn) done = fea_solve_dynamic_with_snapshot(&deck, ctx, stdout, steps);
+  else if (arc) done = fea_solve_arclength_with_snapshot(&deck, ctx, stdout, steps);
   else done = fea_solve_with_snapshots(&deck, ctx, stdout, steps, deck.load_increments_count);
   if (done < 0) {
     /* a HIP failure or a broken-down linear solve: the reference's error() exits with EXIT_FAILURE
@@ -65,7 +69,7 @@ int main(int argc, char **argv)
     fea_export_name(argv[1], msh);
     /* a failed increment leaves current_load_step one lower (fea_solver.c:227), so the
      * reference then drops the last completed step from the file: same here */
-    if (fea_export_gmsh(msh, &deck, steps, arc ? 1 : (done == deck.load_increments_count ? done : done - 1))) {
+    if (fea_export_gmsh(msh, &deck, steps, (arc || dyn) ? 1 : (done == deck.load_increments_count ? done : done - 1))) {
       fprintf(stderr, "could not write %s\n", msh);
       status = 1;
     }

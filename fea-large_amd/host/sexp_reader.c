@@ -435,6 +435,26 @@ static int read_list(reader *r, fea_deck *d)
   } else if (ieq(head, "arc-length")) {                       /* :165-171 */
     if (need_num(r, a, na, "max", &v)) return -1;
     d->arclength_max = (int)v;
+  } else if (ieq(head, "dynamics")) {                         /* no counterpart in the reference */
+    if (need_num(r, a, na, "steps", &v)) return -1;
+    if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "dynamics :steps must be a non-negative integer");
+    d->dynamics_steps = (int)v;
+    if (need_num(r, a, na, "dt", &d->dynamics_dt)) return -1;
+    if (!(d->dynamics_dt > 0)) return fail(r, "dynamics :dt must be positive");
+    d->dynamics_beta = 0.25; d->dynamics_gamma = 0.5; d->dynamics_dlambda = 0;
+    if (attr_get(a, na, "beta") && need_num(r, a, na, "beta", &d->dynamics_beta)) return -1;
+    if (attr_get(a, na, "gamma") && need_num(r, a, na, "gamma", &d->dynamics_gamma)) return -1;
+    if (attr_get(a, na, "dlambda") && need_num(r, a, na, "dlambda", &d->dynamics_dlambda)) return -1;
+    if (!(d->dynamics_beta > 0)) return fail(r, "dynamics :beta must be positive");
+    if (!(d->dynamics_gamma >= 0)) return fail(r, "dynamics :gamma must not be negative");
+    if (need_num(r, a, na, "density", &d->density)) return -1;
+    if (!(d->density > 0)) return fail(r, "dynamics :density must be positive");
+    d->has_dynamics = 1;
+  } else if (ieq(head, "body-force")) {
+    if (need_num(r, a, na, "x", &d->body_force[0])) return -1;
+    if (need_num(r, a, na, "y", &d->body_force[1])) return -1;
+    if (need_num(r, a, na, "z", &d->body_force[2])) return -1;
+    d->has_body_force = 1;
   }
   return 0;
 }
@@ -499,6 +519,9 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
       if (deck->element_material[i] < 0 || deck->element_material[i] >= deck->materials_count) {
         rc = -1; snprintf(r.err, sizeof r.err, "element %d has material %d outside [0,%d)", i, deck->element_material[i], deck->materials_count);
       }
+    if (rc == 0 && deck->has_body_force && !deck->has_dynamics) {
+      rc = -1; snprintf(r.err, sizeof r.err, "deck has (body-force ...) but no (dynamics ... :density rho)");
+    }
   }
   if (rc) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", r.err);
@@ -545,7 +568,11 @@ int fea_deck_save(const char *path, const fea_deck *d)
           d->ele_type == FEA_TETRAHEDRA4 ? "TETRAHEDRA4" : d->ele_type == FEA_HEXAHEDRA8 ? "HEXAHEDRA8" : "TETRAHEDRA10", d->nodes_per_element);
   fprintf(f, "   (slae-solver :type %s :tolerance %.17g :max-iterations %d)\n", solver[d->solver_type],
           d->solver_tolerance, d->solver_max_iter);
-  fprintf(f, "   (line-search :max %d)\n   (arc-length :max %d))\n", d->linesearch_max, d->arclength_max);
+  fprintf(f, "   (line-search :max %d)\n   (arc-length :max %d)", d->linesearch_max, d->arclength_max);
+  if (d->has_dynamics)                               /* written only when present: other decks save as before */
+    fprintf(f, "\n   (dynamics :steps %d :dt %.17g :beta %.17g :gamma %.17g :dlambda %.17g :density %.17g)", d->dynamics_steps,
+            d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda, d->density);
+  fprintf(f, ")\n");
   fprintf(f, " (input-data\n  (geometry\n   (nodes");
   for (i = 0; i < d->nodes_count; ++i)
     fprintf(f, "\n    (%.17g %.17g %.17g)", d->nodes[3 * i], d->nodes[3 * i + 1], d->nodes[3 * i + 2]);
@@ -579,6 +606,8 @@ int fea_deck_save(const char *path, const fea_deck *d)
     }
     fprintf(f, ")");
   }
+  if (d->has_body_force)
+    fprintf(f, "\n   (body-force :x %.17g :y %.17g :z %.17g)", d->body_force[0], d->body_force[1], d->body_force[2]);
   fprintf(f, ")))\n");
   return fclose(f);
 }

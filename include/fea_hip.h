@@ -272,6 +272,71 @@ int feahip_set_materials(feahip_ctx *ctx, int n_materials, const double *params,
  * scattering it through elem_global first.  On every other context get and
  * set use the same order.                                                     */
 int feahip_get_materials(feahip_ctx *ctx, int *n_materials, double *params, int *elem_material);
+/* ---- implicit dynamics: consistent mass, body force, Newmark steps ---------
+ * Nothing below changes a bit of K, f, u or any launch on a context that never
+ * had a mass set, or whose mass was cleared again.
+ *
+ * feahip_set_mass: M_ab = sum_e rho_e sum_g w_g det J0_g N_a(g) N_b(g), times
+ * the 3x3 identity, kept as one double per block of K's pattern (owned rows).
+ * The mass rule is the caller's and separate from the stiffness rule (a
+ * 1-point TET4 rule gives a rank-1 element mass): weights[mass_points] with
+ * the divisor inside as gauss_weights, forms[mass_points][npe] = N_a at the
+ * points, dforms[mass_points][3][npe] for det J0 (reference configuration).
+ * n_rho = 1: a uniform density; n_rho = the material count in force
+ * (feahip_set_materials): one density per material id, the ids in the
+ * context's own element order as feahip_set_materials documents; n_rho = 0
+ * clears the mass and with it the body force, velocities and accelerations.
+ * A later feahip_set_materials with another count drops a per-material mass:
+ * the next call that needs the mass returns FEAHIP_ESTATE.  FEAHIP_EINVAL
+ * (feahip_last_error names the index or element; the context is left as it
+ * was): a density that is not finite and positive, n_rho neither 1 nor the
+ * table size, null arrays, det J0 <= 0 at a mass point.  Assembled on the GPU,
+ * once per call, no atomics, fixed summation order.  Row shards, in-process
+ * groups and rank contexts each get the same call.  Velocities, accelerations
+ * are zero afterwards.                                                        */
+int feahip_set_mass(feahip_ctx *ctx, int n_rho, const double *rho, int mass_points, const double *weights,
+                    const double *forms, const double *dforms);
+/* y = M x, host vectors [3N] in the caller's dof order (test hook;
+ * authoritative on the owned rows like feahip_spmv, zero on the others)       */
+int feahip_mass_spmv(feahip_ctx *ctx, const double *x, double *y);
+/* An acceleration b per unit mass as the dead load F_body = M (1 (x) b),
+ * computed once on the owned rows.  It is scaled by the load factor like the
+ * surface loads: every assembly that writes the residual gives
+ * f = lambda (F_surf(x) + F_body) - T(x), so feahip_solve ramps gravity.  NULL
+ * or zeros clear it; FEAHIP_ESTATE without a mass.  feahip_solve_arclength
+ * with a body force set is refused with FEAHIP_EINVAL.                       */
+int feahip_set_body_force(feahip_ctx *ctx, const double b[3]);
+/* Velocity and acceleration of ALL nodes of the context (halo nodes
+ * included), [N][3] in the caller's node ids; the time.  FEAHIP_ESTATE without
+ * a mass (the time excepted).                                                */
+int feahip_set_velocities(feahip_ctx *ctx, const double *v);
+int feahip_get_velocities(feahip_ctx *ctx, double *v);
+int feahip_set_accelerations(feahip_ctx *ctx, const double *a);
+int feahip_get_accelerations(feahip_ctx *ctx, double *a);
+int feahip_get_time(feahip_ctx *ctx, double *t);
+int feahip_set_time(feahip_ctx *ctx, double t);
+/* Solves M a = lambda F_ext(x) - T(x) with a = 0 on the prescribed dofs into
+ * the accelerations, by the ordinary solve on K := M (K is marked changed
+ * afterwards).  Collective: an in-process group is driven from any of its
+ * contexts, the ranks of an RCCL run all make the call.                      */
+int feahip_consistent_acceleration(feahip_ctx *ctx, int solver_type, double tolerance, int max_iterations);
+/* n_steps Newmark steps (displacement form, full Newton; line search and
+ * modified Newton do not apply).  Per step, a0 = 1 / (beta dt^2):
+ *   xt = x + dt v + dt^2 (1/2 - beta) a,  vt = v + dt (1 - gamma) a;
+ *   feahip_update_nodes_with_bc(ctx, dlambda) (dlambda = 0 holds loads and
+ *   supports fixed);
+ *   Newton from x_n until |<u,f>| <= desired_tolerance or max_newton
+ *   iterations, on K + a0 M and f = lambda F_ext - T - a0 M (x - xt);
+ *   a = a0 (x - xt), v = vt + gamma dt a, t += dt on all nodes (at prescribed
+ *   nodes they describe the prescribed motion).
+ * A step that uses up max_newton iterations stops the loop as in feahip_solve;
+ * *steps_done counts the completed steps and the state is that of the last
+ * completed one.  tol_log / its_log as feahip_solve.  FEAHIP_EINVAL for
+ * dt <= 0, beta <= 0 or gamma < 0; FEAHIP_ESTATE without a mass.             */
+int feahip_solve_dynamic(feahip_ctx *ctx, int n_steps, double dt, double beta, double gamma, double dlambda,
+                         int max_newton, double desired_tolerance, int solver_type, double solver_tolerance,
+                         int solver_max_iter, double *tol_log, int tol_log_cap, int *its_log, int *steps_done);
+
 /* Host-only (no device): resolve faces to (owning element, local face) exactly
  * as feahip_set_surface_loads does; returns FEAHIP_EINVAL with the index of
  * the first bad face in *bad (-1 when all resolve).  Local faces: TET4 / TET10
@@ -419,6 +484,10 @@ int feahip_group_solve(feahip_ctx **ctxs, int n, int load_increments, int max_ne
                        int modified_newton, double desired_tolerance, int solver_type,
                        double solver_tolerance, int solver_max_iter, double *tol_log,
                        int tol_log_cap, int *its_log, int *steps_done);
+int feahip_group_solve_dynamic(feahip_ctx **ctxs, int n, int n_steps, double dt, double beta, double gamma,
+                               double dlambda, int max_newton, double desired_tolerance, int solver_type,
+                               double solver_tolerance, int solver_max_iter, double *tol_log, int tol_log_cap,
+                               int *its_log, int *steps_done);
 /* z = M^-1 r on every rank of the group at once, with the preconditioner the
  * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
  * feahip_apply_preconditioner takes them (the caller's node ids of context k;
@@ -662,7 +731,8 @@ int feahip_sync(feahip_ctx *ctx);
  * 1 stiffness only, 2 residual only, 3 SpMV, 4 one PCG iteration, 5 the
  * surface-load kernels alone (refused on a context without loaded faces),
  * 6 the two-vector SpMV, 7 one two-column PCG iteration (feahip_solve_slae2;
- * both refused where that solve is).                                        */
+ * both refused where that solve is), 8 K += M (k_mass_add), 9 the inertia
+ * term of the residual (k_mass_residual; 8 and 9 refused without a mass).   */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
