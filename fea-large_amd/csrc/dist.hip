@@ -153,6 +153,13 @@ struct RcclTransport : Transport {
     if (r != ncclSuccess) return fail(c, "ncclAllReduce", r);
     return FEAHIP_OK;
   }
+  int allreduce_max(std::vector<feahip_ctx *> &R, int slot, int n) override
+  {
+    feahip_ctx *c = R[0];
+    ncclResult_t r = ncclAllReduce(c->d_scal + 8 + slot, c->d_scal + 8 + slot, (size_t)n, ncclDouble, ncclMax, comm, c->stream);
+    if (r != ncclSuccess) return fail(c, "ncclAllReduce (max)", r);
+    return FEAHIP_OK;
+  }
   int allreduce_vec(std::vector<feahip_ctx *> &R, size_t n, bool comm) override
   {
     feahip_ctx *c = R[0];
@@ -273,6 +280,7 @@ int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double be
   EACH(mass_ensure(c, "feahip_solve_dynamic"));
   for (feahip_ctx *c : R) {
     (void)hipSetDevice(c->device);
+    c->mass.ke_parts = 0;                                             // (host only: the velocities are about to change)
     double *q = nullptr;
     FEA_HIP_CHECK(c, hipMalloc((void **)&q, sizeof(double) * 4 * (size_t)c->N));
     xn.p.push_back(q);
@@ -337,6 +345,122 @@ int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, 
   EACH(launch_vec3_to_nodes(c, c->d_u, c->mass.d_acc));
   for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); ++c->k_epoch; FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
   return FEAHIP_OK;
+}
+
+// ---- explicit dynamics: central differences in the velocity-Verlet form on the HRZ-lumped mass (feahip_solve_explicit) ----
+// State (x, v, a) at t_n, the Newmark state.  Per step: kick and drift (vh = v + dt/2 a, u = dt vh on the owned rows, 0 on
+// prescribed dofs); the static loop's exchange of u and x += u; one increment of the prescribed dofs and the load factor;
+// ONE residual assembly f = lambda (F_surf + F_body) - T(x); finish (a = f / ml, v = vh + dt/2 a).  No K is assembled, no
+// system solved; with a fixed dt nothing is read back between the first and the last step.  v and a are authoritative on
+// owned nodes only: a halo node gets v = u / dt and a = 0, which needs no second exchange.
+
+// Gershgorin: omega_max^2 <= max_i (sum_j |K_ij|) / ml(i), K the unmasked tangent at x; dt_crit = 2 / sqrt(bound)
+int dist_stable_step(std::vector<feahip_ctx *> &R, double *dt_crit)
+{
+  int rc;
+  EACH(lump_ensure(c, "feahip_stable_step"));
+  EACH(feahip_create_stiffness(c));                                   // (K is another matrix from here on: k_epoch)
+  EACH(launch_gershgorin(c));
+  if (R[0]->tr && (rc = R[0]->tr->allreduce_max(R, 0, 1))) return rc;
+  feahip_ctx *c0 = R[0];
+  (void)hipSetDevice(c0->device);
+  double bound = 0;
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(&bound, c0->d_scal + 8, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  // (a NaN or an infinity in K reaches here: the reductions propagate it.  Every rank reads the same all-reduced number,
+  // so every rank takes this branch or none does)
+  if (!(bound > 0.0) || !std::isfinite(bound)) {
+    for (feahip_ctx *c : R) c->err = "feahip_stable_step: the stiffness has no positive finite row sum";
+    return FEAHIP_ESTATE;
+  }
+  *dt_crit = 2.0 / sqrt(bound);
+  return FEAHIP_OK;
+}
+
+// 1/2 sum ml |v|^2 over all ranks
+int dist_kinetic_energy(std::vector<feahip_ctx *> &R, double *e)
+{
+  int rc;
+  EACH(lump_ensure(c, "feahip_kinetic_energy"));
+  EACH(launch_kinetic_energy(c, c->d_scal + 8));
+  if (R[0]->tr && (rc = R[0]->tr->allreduce(R, 0, 1))) return rc;
+  feahip_ctx *c0 = R[0];
+  (void)hipSetDevice(c0->device);
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(e, c0->d_scal + 8, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  return FEAHIP_OK;
+}
+
+int dist_explicit(std::vector<feahip_ctx *> &R, int n_steps, double dt_fixed, double safety, int restep, double dlambda,
+                  double *dt_log, int dt_log_cap, int *steps_done)
+{
+  int rc, step = 0, checked = 0, result = FEAHIP_OK;
+  double dt = dt_fixed;
+  EACH(lump_ensure(c, "feahip_solve_explicit"));
+  for (feahip_ctx *c : R) {
+    (void)hipSetDevice(c->device);
+    // u is zero outside the owned and the halo rows (dist_update_nodes_with_solution adds all of it)
+    FEA_HIP_CHECK(c, hipMemsetAsync(c->d_u, 0, sizeof(double) * (size_t)c->ndof, c->stream));
+  }
+  // Elements with det J <= 0 (or NaN) at a Gauss point of the current x, on ANY rank.  Every rank counts its own and its
+  // ghost elements (launch_count_inverted, read through feahip_update_state); the counts meet in a max all-reduce BEFORE
+  // anything branches on them, so all ranks of an RCCL run leave the loop together, with the same code and the same
+  // steps_done, and none is left waiting in a collective its peers never enter.
+  auto inverted = [&](bool &bad) -> int {
+    double most = 0.0;
+    for (feahip_ctx *c : R) {
+      (void)hipSetDevice(c->device);
+      int n = 0;
+      if ((rc = launch_count_inverted(c)) || (rc = feahip_update_state(c, &n))) return rc;
+      most = n != 0 ? 1.0 : most;
+    }
+    if (Transport *T = R[0]->tr) {
+      for (feahip_ctx *c : R) {
+        (void)hipSetDevice(c->device);
+        FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_scal + 8, &most, sizeof(double), hipMemcpyHostToDevice, c->stream));
+        FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+      }
+      if ((rc = T->allreduce_max(R, 0, 1))) return rc;
+      feahip_ctx *c0 = R[0];
+      (void)hipSetDevice(c0->device);
+      FEA_HIP_CHECK(c0, hipMemcpyAsync(&most, c0->d_scal + 8, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
+      FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+    }
+    bad = bad || most != 0.0;
+    return FEAHIP_OK;
+  };
+  auto refuse = [&](int at) {
+    for (feahip_ctx *c : R) c->err = "solve_explicit: inverted elements (det J <= 0) found at the check of step " + std::to_string(at) +
+                "; the state is left as it is (explicit steps are not rolled back)";
+    result = FEAHIP_ENOTCONVERGED;
+  };
+  for (; step < n_steps; ++step) {
+    if (dt_fixed == 0.0 && (step == 0 || (restep > 0 && step % restep == 0))) {
+      bool bad = false;
+      double dtc = 0;
+      if ((rc = inverted(bad))) return rc;
+      if (bad) { refuse(step); break; }
+      if ((rc = dist_stable_step(R, &dtc))) return rc;
+      checked = step;
+      dt = safety * dtc;
+    }
+    EACH(launch_explicit_kick(c, dt));
+    if ((rc = dist_update_nodes_with_solution(R, nullptr))) return rc;
+    EACH(feahip_update_nodes_with_bc(c, dlambda));
+    EACH(launch_explicit_presc(c, dlambda, dt));
+    EACH(feahip_create_residual_forces(c));
+    EACH(launch_explicit_finish(c, dt));
+    for (feahip_ctx *c : R) c->mass.time += dt;
+    if (dt_log && step < dt_log_cap) dt_log[step] = dt;
+  }
+  if (result == FEAHIP_OK && n_steps > 0) {
+    bool bad = false;
+    if ((rc = inverted(bad))) return rc;
+    if (bad) refuse(n_steps); else checked = n_steps;
+  }
+  if (steps_done) *steps_done = result == FEAHIP_OK ? step : checked;
+  for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
+  return result;
 }
 #undef EACH
 

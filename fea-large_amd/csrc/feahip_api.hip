@@ -710,6 +710,7 @@ extern "C" int feahip_set_materials(feahip_ctx *c, int n_materials, const double
   if (c->mass.set && c->mass.n_rho > 1) {
     if (n_materials != c->mass.n_mat) c->mass.stale = true;
     c->mass.release_m();
+    c->mass.release_lump();
   }
   c->n_materials = n_materials;
   c->h_mat_params.assign(params, params + (n_materials ? 2 * (size_t)n_materials : 0));
@@ -987,7 +988,7 @@ static int set_node4(feahip_ctx *c, double *d, const double *h)
   CTX_GUARD_NOK(c);                                                \
   { const int _rm = mass_ensure(c, who); if (_rm) return _rm; }
 
-extern "C" int feahip_set_velocities(feahip_ctx *c, const double *v) { MASS_GUARD(c, "feahip_set_velocities"); return set_node4(c, c->mass.d_vel, v); }
+extern "C" int feahip_set_velocities(feahip_ctx *c, const double *v) { MASS_GUARD(c, "feahip_set_velocities"); c->mass.ke_parts = 0; return set_node4(c, c->mass.d_vel, v); }
 extern "C" int feahip_get_velocities(feahip_ctx *c, double *v) { MASS_GUARD(c, "feahip_get_velocities"); return get_node4(c, c->mass.d_vel, v); }
 extern "C" int feahip_set_accelerations(feahip_ctx *c, const double *a) { MASS_GUARD(c, "feahip_set_accelerations"); return set_node4(c, c->mass.d_acc, a); }
 extern "C" int feahip_get_accelerations(feahip_ctx *c, double *a) { MASS_GUARD(c, "feahip_get_accelerations"); return get_node4(c, c->mass.d_acc, a); }
@@ -1071,6 +1072,71 @@ extern "C" int feahip_group_solve_dynamic(feahip_ctx **ctxs, int n, int n_steps,
   for (feahip_ctx *c : R) { CTX_GUARD(c); }
   rc = dist_dynamic(R, n_steps, dt, beta, gamma, dlambda, max_newton, desired_tolerance, solver_type, solver_tolerance,
                     solver_max_iter, tol_log, tol_log_cap, its_log, steps_done);
+  if (rc && R[0]->err.empty()) for (feahip_ctx *c : R) if (!c->err.empty()) { R[0]->err = c->err; break; }
+  return rc;
+}
+
+// ---- explicit dynamics on the lumped mass (kernels_mass.hip, kernels_solve.hip, dist.hip) ---------------------------
+extern "C" int feahip_get_lumped_mass(feahip_ctx *c, double *ml)
+{
+  CTX_GUARD_NOK(c);
+  if (!ml) return FEAHIP_EINVAL;
+  int rc;
+  if ((rc = lump_ensure(c, "feahip_get_lumped_mass"))) return rc;
+  std::vector<double> tmp((size_t)c->N);
+  if ((rc = get_vec(c, c->mass.d_ml, tmp.data(), tmp.size()))) return rc;
+  for (int a = 0; a < c->N; ++a) ml[a] = tmp[(size_t)lib_id(c, a)];
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_stable_step(feahip_ctx *c, double *dt_crit)
+{
+  CTX_GUARD(c);
+  if (!dt_crit) return FEAHIP_EINVAL;
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  const int rc = dist_stable_step(R, dt_crit);
+  if (rc && c->err.empty()) for (feahip_ctx *r : R) if (!r->err.empty()) { c->err = r->err; break; }
+  return rc;
+}
+
+extern "C" int feahip_kinetic_energy(feahip_ctx *c, double *e)
+{
+  CTX_GUARD_NOK(c);
+  if (!e) return FEAHIP_EINVAL;
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  const int rc = dist_kinetic_energy(R, e);
+  if (rc && c->err.empty()) for (feahip_ctx *r : R) if (!r->err.empty()) { c->err = r->err; break; }
+  return rc;
+}
+
+static int explicit_args(feahip_ctx *c, int n_steps, double dt, double safety, int *steps_done)
+{
+  if (steps_done) *steps_done = 0;
+  if (!(dt >= 0.0) || !std::isfinite(dt)) { c->err = "solve_explicit: dt must not be negative (0 asks for the stable-step estimate)"; return FEAHIP_EINVAL; }
+  if (n_steps < 0) { c->err = "solve_explicit: n_steps must not be negative"; return FEAHIP_EINVAL; }
+  if (dt == 0.0 && !(safety > 0.0 && safety <= 1.0)) { c->err = "solve_explicit: safety must be in (0, 1]"; return FEAHIP_EINVAL; }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_solve_explicit(feahip_ctx *c, int n_steps, double dt, double safety, int restep, double dlambda,
+                                     double *dt_log, int dt_log_cap, int *steps_done)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = explicit_args(c, n_steps, dt, safety, steps_done))) return rc;
+  std::vector<feahip_ctx *> R(1, c);
+  return dist_explicit(R, n_steps, dt, safety, restep, dlambda, dt_log, dt_log_cap, steps_done);
+}
+
+extern "C" int feahip_group_solve_explicit(feahip_ctx **ctxs, int n, int n_steps, double dt, double safety, int restep,
+                                           double dlambda, double *dt_log, int dt_log_cap, int *steps_done)
+{
+  std::vector<feahip_ctx *> R;
+  int rc = group_vec(ctxs, n, R);
+  if (rc) return rc;
+  if ((rc = explicit_args(R[0], n_steps, dt, safety, steps_done))) return rc;
+  for (feahip_ctx *c : R) { CTX_GUARD_NOK(c); }
+  rc = dist_explicit(R, n_steps, dt, safety, restep, dlambda, dt_log, dt_log_cap, steps_done);
   if (rc && R[0]->err.empty()) for (feahip_ctx *c : R) if (!c->err.empty()) { R[0]->err = c->err; break; }
   return rc;
 }
@@ -1416,6 +1482,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     const int rk = mass_ensure(c, "time_kernel");
     if (rk) return rk;
   }
+  if (what == 10 || what == 11) {
+    if (!c->mass.set || c->mass.stale) { c->err = std::string(what == 10 ? "time_kernel(10)" : "time_kernel(11)") + ": no mass on this context (feahip_set_mass)"; return FEAHIP_EINVAL; }
+    const int rk = lump_ensure(c, "time_kernel");
+    if (rk) return rk;
+  }
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   auto one = [&]() -> int {
     switch (what) {
@@ -1427,6 +1498,8 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 6: return launch_spmv2(c, c->d2_p, c->d2_q);
     case 8: return launch_mass_add(c, 1.0);
     case 9: return launch_mass_residual(c, 1.0);
+    case 10: { const int rk = launch_explicit_kick(c, 1.0); return rk ? rk : launch_explicit_finish(c, 1.0); }
+    case 11: return launch_gershgorin(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   };

@@ -405,8 +405,14 @@ struct MassState {
   double *d_body = nullptr;            // [3N] F_body = M (1 (x) b) on the owned rows, at load factor 1; null: none
   double body[3] = {0, 0, 0};
   double time = 0;
+  // explicit steps (lump_ensure): nothing below exists until an explicit entry asks for it
+  double *d_ml = nullptr;              // [N] HRZ lumped mass of the owned rows [ml_row0, ml_row1), zero elsewhere
+  int ml_row0 = -1, ml_row1 = -1;      // the rows ml was built for
+  double *d_ke_part = nullptr;         // [4 FEA_RED_BLOCKS] per-workgroup partial sums of 1/2 ml |v|^2
+  int ke_parts = 0;                    // partial sums the last explicit step left for the velocities in force (0: none)
   void release_m() { dev_free({d_m_base}); d_m_base = d_m = nullptr; kb0 = kb1 = -1; }
-  void release() { dev_free({d_m_base, d_vel, d_acc, d_xt, d_vt, d_body}); *this = MassState(); }
+  void release_lump() { dev_free({d_ml, d_ke_part}); d_ml = d_ke_part = nullptr; ml_row0 = ml_row1 = -1; ke_parts = 0; }
+  void release() { dev_free({d_m_base, d_vel, d_acc, d_xt, d_vt, d_body, d_ml, d_ke_part}); *this = MassState(); }
 };
 
 struct feahip_ctx {
@@ -604,11 +610,25 @@ int launch_mass_product(feahip_ctx *c, const double *d_v4, double *d_y);   // y 
 int launch_newmark_predict(feahip_ctx *c, double dt, double beta, double gamma);
 int launch_newmark_correct(feahip_ctx *c, double dt, double beta, double gamma);
 int launch_vec3_to_nodes(feahip_ctx *c, const double *d_v3, double *d_v4);
+// kernels_mass.hip -- HRZ lumped mass and the pointwise kernels of an explicit (central-difference) step
+int lump_ensure(feahip_ctx *c, const char *who);               // mass_ensure, then ml for the rows installed now
+int launch_explicit_kick(feahip_ctx *c, double dt);            // vh = v + dt/2 a (d_vt), u = dt vh; 0 on prescribed dofs
+int launch_explicit_presc(feahip_ctx *c, double dlambda, double dt);   // vh = prescribed increment / dt on the prescribed dofs
+int launch_explicit_finish(feahip_ctx *c, double dt);          // a = f / ml, v = vh + dt/2 a; partial sums of the kinetic energy
+int launch_kinetic_energy(feahip_ctx *c, double *d_out);       // *d_out = 1/2 sum ml |v|^2 over the owned rows
+int launch_count_inverted(feahip_ctx *c);                      // d_flag[1] = elements with det J <= 0 (or NaN) at a Gauss point of x
+// kernels_solve.hip -- Gershgorin bound max_i sum_j |K_ij| / ml(i) over the owned rows into d_scal[8]
+int launch_gershgorin(feahip_ctx *c);
 // dist.hip -- Newmark steps and the consistent acceleration over one or more ranks
 int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double beta, double gamma, double dlambda,
                  int max_newton, double desired_tolerance, int solver_type, double solver_tolerance, int solver_max_iter,
                  double *tol_log, int tol_log_cap, int *its_log, int *steps_done);
 int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, double tol, int max_iter);
+// dist.hip -- explicit steps, the stable step and the kinetic energy over one or more ranks
+int dist_explicit(std::vector<feahip_ctx *> &R, int n_steps, double dt, double safety, int restep, double dlambda,
+                  double *dt_log, int dt_log_cap, int *steps_done);
+int dist_stable_step(std::vector<feahip_ctx *> &R, double *dt_crit);
+int dist_kinetic_energy(std::vector<feahip_ctx *> &R, double *e);
 // dist.hip -- Crisfield's cylindrical arc length on the surface loads (one unsharded context)
 int arclength_solve(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
                     int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log, double *tol_log,
@@ -672,6 +692,8 @@ struct Transport {
   virtual int exchange_end(std::vector<feahip_ctx *> &R) { (void)R; return FEAHIP_OK; }
   // d_scal[8+slot .. 8+slot+n) summed over all ranks, result on every rank
   virtual int allreduce(std::vector<feahip_ctx *> &R, int slot, int n) = 0;
+  // the same with the maximum over all ranks (order-independent: reproducible on any transport)
+  virtual int allreduce_max(std::vector<feahip_ctx *> &R, int slot, int n) = 0;
   // the contexts' d_vred[0 .. n) summed over all ranks, result on every rank.  comm: the buffer is produced and
   // consumed on the contexts' communication streams (which exist), not on their own
   virtual int allreduce_vec(std::vector<feahip_ctx *> &R, size_t n, bool comm) = 0;

@@ -13,6 +13,12 @@
 //                    y = M v: feahip_mass_spmv, the body force)
 // and two pointwise kernels frame a step (k_newmark_predict, k_newmark_correct: 16-byte pieces of the 32-byte node
 // records).  Nothing here is launched on a context without a mass.
+//
+// Explicit (central-difference) steps use a DIAGONAL mass instead: ml[N], one double per node, HRZ-lumped per element
+// (k_mass_lump: m_e d_a / sum_b d_b with d_a = sum_g rho w det J0 N_a^2 -- positive on every element type and the
+// element's mass exactly; the row sum of a 10-node tetrahedron is <= 0 at its corners).  It is built on first use by
+// lump_ensure and framed by two pointwise kernels per step, k_explicit_kick and k_explicit_finish.  A context that
+// never makes an explicit call allocates and launches none of it.
 #include "feahip_internal.h"
 #include <cmath>
 #include <cstring>
@@ -237,6 +243,161 @@ void k_newmark_correct(size_t n, double a0, double gdt, const mass_v2d *__restri
   }
 }
 
+// HRZ lumped mass.  A wave per chunk, one lane per row: the lane walks the chunk's (element, local node) visits in stored
+// order, keeps those of its row and adds m_e d_la / sum_k d_k -- no atomics, a fixed order, the same bits on every call.
+__global__ __launch_bounds__(64 * FEA_WAVES_PER_WG)
+void k_mass_lump(int chunk0, int nchunks, const int *__restrict__ chunk, const int *__restrict__ incptr,
+                 const uint32_t *__restrict__ inc, const int *__restrict__ conn, int npe, int Gm,
+                 const MassTable *__restrict__ tab, const double *__restrict__ wdet, double *__restrict__ ml)
+{
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int ch = chunk0 + blockIdx.x * FEA_WAVES_PER_WG + wave; ch < chunk0 + nchunks; ch += gridDim.x * FEA_WAVES_PER_WG) {
+    const int r0 = chunk[ch], r1 = chunk[ch + 1];
+    const int p0 = incptr[r0], p1 = incptr[r1];
+    for (int a = r0 + lane; a < r1; a += 64) {
+      double acc = 0.0;
+      for (int p = p0; p < p1; ++p) {
+        const uint32_t w = inc[p];
+        const int e = (int)(w & 0x0FFFFFFFu), la = (int)(w >> 28);
+        if (conn[(size_t)e * npe + la] != a) continue;
+        const double *wd = wdet + (size_t)e * Gm;
+        double me = 0.0, dsum = 0.0, da = 0.0;
+        for (int g = 0; g < Gm; ++g) me += wd[g];
+        for (int k = 0; k < npe; ++k) {
+          double d = 0.0;
+          for (int g = 0; g < Gm; ++g) d += wd[g] * tab->N[g][k] * tab->N[g][k];
+          dsum += d;
+          da = (k == la) ? d : da;
+        }
+        acc += me * da / dsum;
+      }
+      ml[a] = acc;
+    }
+  }
+}
+
+// *bad = elements of the context (its own and its ghosts) with det J <= 0, or NaN, at a Gauss point of the stiffness
+// rule in the CURRENT configuration x.  The check of the explicit loop: the same count on every element type and
+// assembly strategy, without an assembly (the residual-only kernels do not all count) and without touching K.
+__global__ __launch_bounds__(256)
+void k_count_inverted(int E, int npe, int G, const int *__restrict__ conn, const double *__restrict__ x,
+                      const ElemTable *__restrict__ tab, int *bad)
+{
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  bool inv = false;
+  for (int g = 0; g < G; ++g) {
+    double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    for (int k = 0; k < npe; ++k) {
+      const double *X = x + (size_t)conn[(size_t)e * npe + k] * 4;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double d = tab->dN[g][i][k];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) J[i][j] += d * X[j];
+      }
+    }
+    const double det = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+                       J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+    inv = inv || !(det > 0.0);
+  }
+  if (inv) atomicAdd(bad, 1);
+}
+
+// sum over the 256 threads of a block in a fixed order; valid in thread 0
+__device__ __forceinline__ double mass_block_sum(double v, double *sh /*[4]*/)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return threadIdx.x == 0 ? sh[0] + sh[1] + sh[2] + sh[3] : 0.0;
+}
+
+// Kick and drift over the 16-byte pieces of the owned node records [a0, a1): vh = v + dt/2 a, u = dt vh; both 0 on the
+// prescribed dofs (k_explicit_presc then gives vh its prescribed value there)
+__global__ __launch_bounds__(256)
+void k_explicit_kick(int a0, int a1, double dt, const mass_v2d *__restrict__ v, const mass_v2d *__restrict__ a,
+                     const uint8_t *__restrict__ mask, mass_v2d *__restrict__ vh, double *__restrict__ u)
+{
+  const size_t p1 = (size_t)a1 * 2, stride = (size_t)gridDim.x * 256;
+  const double hdt = 0.5 * dt;
+  for (size_t p = (size_t)a0 * 2 + (size_t)blockIdx.x * 256 + threadIdx.x; p < p1; p += stride) {
+    const size_t d = (p >> 1) * 3 + 2 * (p & 1);               // first dof of the piece
+    mass_v2d w = v[p] + hdt * a[p];
+    if (mask[d]) w.x = 0.0;
+    if (p & 1) w.y = 0.0;                                      // (the pad)
+    else if (mask[d + 1]) w.y = 0.0;
+    vh[p] = w;
+    u[d] = dt * w.x;
+    if (!(p & 1)) u[d + 1] = dt * w.y;
+  }
+}
+
+// vh += value dlambda / dt on the prescribed dofs of the owned nodes (the kick left 0 there; a dof named twice adds up,
+// as in k_nodes_bc)
+__global__ __launch_bounds__(256)
+void k_explicit_presc(int n_cdof, const int *__restrict__ cdof, const double *__restrict__ cval, double rate, int a0, int a1,
+                      double *__restrict__ vh)
+{
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_cdof) return;
+  const int c = cdof[t], node = c / 3;
+  if (node < a0 || node >= a1) return;
+  atomicAdd(vh + (size_t)node * 4 + c % 3, cval[t] * rate);
+}
+
+// Finish over the pieces of ALL node records.  Owned nodes: a = f / ml (0 on prescribed dofs), v = vh + dt/2 a, and the
+// piece's share of 1/2 ml |v|^2 into the workgroup's partial sum.  Other nodes: v = u / dt, a = 0 -- u is what the
+// exchange brought (0 on nodes that are not in the halo), so no second exchange is needed; v and a are authoritative on
+// owned nodes only.  KE_ONLY: nothing is written but the partial sums of the velocities in force.
+template <bool KE_ONLY>
+__global__ __launch_bounds__(256)
+void k_explicit_finish(int N, int a0, int a1, double dt, const double *__restrict__ f, const double *__restrict__ ml,
+                       const uint8_t *__restrict__ mask, const double *__restrict__ u, const mass_v2d *__restrict__ vh,
+                       mass_v2d *__restrict__ v, mass_v2d *__restrict__ a, double *__restrict__ part)
+{
+  __shared__ double sh[4];
+  const size_t n = (size_t)N * 2, stride = (size_t)gridDim.x * 256;
+  const double hdt = 0.5 * dt;
+  double ke = 0.0;
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += stride) {
+    const int node = (int)(p >> 1);
+    const bool lo = !(p & 1);
+    const size_t d = (size_t)node * 3 + (lo ? 0 : 2);
+    const bool own = node >= a0 && node < a1;
+    if constexpr (KE_ONLY) {
+      if (own) { const mass_v2d w = v[p]; ke += 0.5 * ml[node] * (w.x * w.x + w.y * w.y); }
+    } else {
+      mass_v2d vv, aa;
+      if (own) {
+        const double m = ml[node];
+        aa.x = mask[d] ? 0.0 : f[d] / m;
+        aa.y = lo ? (mask[d + 1] ? 0.0 : f[d + 1] / m) : 0.0;
+        vv = vh[p] + hdt * aa;
+        ke += 0.5 * m * (vv.x * vv.x + vv.y * vv.y);
+      } else {
+        aa.x = 0.0; aa.y = 0.0;
+        vv.x = u[d] / dt; vv.y = lo ? u[d + 1] / dt : 0.0;
+      }
+      v[p] = vv; a[p] = aa;
+    }
+  }
+  ke = mass_block_sum(ke, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = ke;
+}
+
+// *out = part[0] + ... + part[n - 1]: one block, fixed order (the pattern of k_reduce_final)
+__global__ __launch_bounds__(256)
+void k_mass_sum_final(int n, const double *__restrict__ part, double *__restrict__ out)
+{
+  __shared__ double sh[4];
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) v += part[i];
+  v = mass_block_sum(v, sh);
+  if (threadIdx.x == 0) *out = v;
+}
+
 // [N][3] -> [N][4] (the pad is written 0)
 __global__ __launch_bounds__(256)
 void k_vec3_to_nodes(int N, const double *__restrict__ v3, double *__restrict__ v4)
@@ -320,6 +481,61 @@ int launch_newmark_correct(feahip_ctx *c, double dt, double beta, double gamma)
   hipLaunchKernelGGL(k_newmark_correct, dim3(piece_grid(n)), dim3(256), 0, c->stream, n, 1.0 / (beta * dt * dt), gamma * dt,
                      (const mass_v2d *)c->d_x, (const mass_v2d *)M.d_xt, (const mass_v2d *)M.d_vt, (mass_v2d *)M.d_vel,
                      (mass_v2d *)M.d_acc);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+int launch_explicit_kick(feahip_ctx *c, double dt)
+{
+  MassState &M = c->mass;
+  M.ke_parts = 0;
+  if (c->row1 <= c->row0) return FEAHIP_OK;
+  hipLaunchKernelGGL(k_explicit_kick, dim3(piece_grid((size_t)(c->row1 - c->row0) * 2)), dim3(256), 0, c->stream, c->row0, c->row1,
+                     dt, (const mass_v2d *)M.d_vel, (const mass_v2d *)M.d_acc, (const uint8_t *)c->d_dofmask, (mass_v2d *)M.d_vt, c->d_u);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+int launch_explicit_presc(feahip_ctx *c, double dlambda, double dt)
+{
+  if (c->n_cdof == 0 || dlambda == 0.0) return FEAHIP_OK;
+  hipLaunchKernelGGL(k_explicit_presc, dim3((c->n_cdof + 255) / 256), dim3(256), 0, c->stream, c->n_cdof, c->d_cdof, c->d_cval,
+                     dlambda / dt, c->row0, c->row1, c->mass.d_vt);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+int launch_explicit_finish(feahip_ctx *c, double dt)
+{
+  MassState &M = c->mass;
+  const int g = piece_grid((size_t)c->N * 2);
+  hipLaunchKernelGGL(k_explicit_finish<false>, dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, dt, c->d_f, M.d_ml,
+                     (const uint8_t *)c->d_dofmask, c->d_u, (const mass_v2d *)M.d_vt, (mass_v2d *)M.d_vel, (mass_v2d *)M.d_acc, M.d_ke_part);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  M.ke_parts = g;
+  return FEAHIP_OK;
+}
+
+int launch_kinetic_energy(feahip_ctx *c, double *d_out)
+{
+  MassState &M = c->mass;
+  if (M.ke_parts == 0) {                                   // no explicit step left the sums of these velocities
+    const int g = piece_grid((size_t)c->N * 2);
+    hipLaunchKernelGGL(k_explicit_finish<true>, dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, 0.0, (const double *)nullptr,
+                       M.d_ml, (const uint8_t *)nullptr, (const double *)nullptr, (const mass_v2d *)nullptr, (mass_v2d *)M.d_vel,
+                       (mass_v2d *)nullptr, M.d_ke_part);
+    M.ke_parts = g;
+  }
+  hipLaunchKernelGGL(k_mass_sum_final, dim3(1), dim3(256), 0, c->stream, M.ke_parts, M.d_ke_part, d_out);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+int launch_count_inverted(feahip_ctx *c)
+{
+  FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag + 1, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_count_inverted, dim3((c->E + 255) / 256), dim3(256), 0, c->stream, c->E, c->npe, c->G, c->d_conn, c->d_x,
+                     (const ElemTable *)c->d_table, c->d_flag + 1);
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }
@@ -423,6 +639,47 @@ int mass_ensure(feahip_ctx *c, const char *who)
   return body_assemble(c);
 }
 
+// The lumped mass of the rows installed now, from the rule and the densities of the last feahip_set_mass: built on the
+// first explicit call and again when the shard has changed (feahip_set_materials and feahip_set_mass drop it).
+int lump_ensure(feahip_ctx *c, const char *who)
+{
+  int rc;
+  if ((rc = mass_ensure(c, who))) return rc;
+  MassState &M = c->mass;
+  if (M.d_ml && M.ml_row0 == c->row0 && M.ml_row1 == c->row1) return FEAHIP_OK;
+  if ((rc = ensure_generic_maps(c))) return rc;
+  MassScratch S;
+  MassTable T;
+  memset(&T, 0, sizeof(T));
+  for (int g = 0; g < M.Gm; ++g) {
+    T.w[g] = M.w[g];
+    for (int k = 0; k < c->npe; ++k) {
+      T.N[g][k] = M.N[(size_t)g * c->npe + k];
+      for (int i = 0; i < 3; ++i) T.dN[g][i][k] = M.dN[((size_t)g * 3 + i) * c->npe + k];
+    }
+  }
+  const int none = 0x7FFFFFFF;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.tab, sizeof(T)));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.rho, sizeof(double) * M.rho.size()));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.wdet, sizeof(double) * (size_t)c->E * M.Gm));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.bad, sizeof(int)));
+  if (!M.d_ml) FEA_HIP_CHECK(c, hipMalloc((void **)&M.d_ml, sizeof(double) * (size_t)c->N));
+  if (!M.d_ke_part) FEA_HIP_CHECK(c, hipMalloc((void **)&M.d_ke_part, sizeof(double) * 4 * FEA_RED_BLOCKS));
+  M.ml_row0 = M.ml_row1 = -1; M.ke_parts = 0;
+  FEA_HIP_CHECK(c, hipMemsetAsync(M.d_ml, 0, sizeof(double) * (size_t)c->N, c->stream));
+  FEA_HIP_CHECK(c, hipMemcpyAsync(S.tab, &T, sizeof(T), hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipMemcpyAsync(S.rho, M.rho.data(), sizeof(double) * M.rho.size(), hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipMemcpyAsync(S.bad, &none, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_mass_elements, dim3((c->E + 255) / 256), dim3(256), 0, c->stream, c->E, c->npe, M.Gm, c->d_conn,
+                     c->d_X0, S.tab, S.rho, M.n_rho, c->d_elem_mat, S.wdet, S.bad);
+  hipLaunchKernelGGL(k_mass_lump, dim3(chunk_grid(c)), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, c->chunk0, c->nchunks_local,
+                     c->d_chunk, c->generic.d_incptr, c->generic.d_inc, c->d_conn, c->npe, M.Gm, S.tab, S.wdet, M.d_ml);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));          // (the scratch is freed on return)
+  M.ml_row0 = c->row0; M.ml_row1 = c->row1;
+  return FEAHIP_OK;
+}
+
 int mass_set(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights, const double *forms,
              const double *dforms)
 {
@@ -459,6 +716,7 @@ int mass_set(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const
     FEA_HIP_CHECK(c, hipMemsetAsync(*p, 0, nb4, c->stream));
   }
   M.release_m();
+  M.release_lump();                                          // of the mass before: built again by the next explicit call
   M.set = true; M.stale = false;
   M.n_rho = P.n_rho; M.n_mat = P.n_mat; M.Gm = P.Gm;
   M.rho.swap(P.rho); M.w.swap(P.w); M.N.swap(P.N); M.dN.swap(P.dN);

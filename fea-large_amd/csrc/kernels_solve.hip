@@ -461,6 +461,106 @@ int launch_spmv(feahip_ctx *c, const double *d_xv, double *d_yv)
 }
 
 // ------------------------------------------------------------------------
+// Gershgorin bound of M_L^-1 K over the owned rows: max_i (sum_j |K_ij|) / ml(node of i), the row loop of k_spmv without
+// x and without the column index.  A wave owns a chunk, lane k takes its blocks k and k + 64 and leaves the three
+// absolute row sums of each in LDS; lane (row, i) adds its row's partial sums in block order and divides by ml[row].
+// Rows longer than the tile stride over their blocks.  The wave's, the workgroup's and (k_max_final) the grid's results
+// meet by max, which no order changes (nan_max: a NaN in K reaches the host, which refuses it).  72 bytes per block are
+// read and nothing else of size.
+// ------------------------------------------------------------------------
+// the larger of two, NaN if either is: fmax alone would drop a NaN row of K and take the bound from the others
+__device__ __forceinline__ double nan_max(double a, double b) { return a != a ? a : (b != b ? b : fmax(a, b)); }
+__device__ __forceinline__ double wave_max_all(double v)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = nan_max(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+__global__ __launch_bounds__(64 * FEA_WAVES_PER_WG)
+void k_gershgorin(int chunk0, int nchunks, const int *__restrict__ chunk, const int *__restrict__ rowptr,
+                  const double *__restrict__ K, const double *__restrict__ ml, double *__restrict__ part)
+{
+  static_assert(FEA_CHUNK_ROWS * 3 <= 64, "one lane per (row, component) of a chunk");
+  static_assert(FEA_CHUNK_BLOCKS <= 128, "a lane takes the blocks k and k + 64 of a chunk");
+  __shared__ double sP[FEA_WAVES_PER_WG][FEA_CHUNK_BLOCKS * 3];
+  __shared__ double sM[FEA_WAVES_PER_WG];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double *tP = sP[wave];
+  double best = 0.0;
+  auto row_sums = [&](int q, double (&d)[3]) {
+    const double *vp = K + (size_t)q * 9;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d[i] = fabs(vp[3 * i]) + fabs(vp[3 * i + 1]) + fabs(vp[3 * i + 2]);
+  };
+  for (int ch = chunk0 + blockIdx.x * FEA_WAVES_PER_WG + wave; ch < chunk0 + nchunks; ch += gridDim.x * FEA_WAVES_PER_WG) {
+    const int r0 = chunk[ch], r1 = chunk[ch + 1];
+    const int b0 = rowptr[r0], nb = rowptr[r1] - b0;
+    if (nb > FEA_CHUNK_BLOCKS) {                               // one long row (pattern.cpp gives it a chunk of its own)
+      double s[3] = {0, 0, 0};
+      for (int k = lane; k < nb; k += 64) {
+        double d[3];
+        row_sums(b0 + k, d);
+        s[0] += d[0]; s[1] += d[1]; s[2] += d[2];
+      }
+      s[0] = wave_sum_all(s[0]); s[1] = wave_sum_all(s[1]); s[2] = wave_sum_all(s[2]);
+      best = nan_max(best, nan_max(s[0], nan_max(s[1], s[2])) / ml[r0]);
+      continue;
+    }
+    int kb = 0, ke = 0;
+    if (lane < (r1 - r0) * 3) { kb = rowptr[r0 + lane / 3] - b0; ke = rowptr[r0 + lane / 3 + 1] - b0; }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k < nb) {
+        double d[3];
+        row_sums(b0 + k, d);
+        tP[k * 3 + 0] = d[0]; tP[k * 3 + 1] = d[1]; tP[k * 3 + 2] = d[2];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    if (lane < (r1 - r0) * 3) {
+      const int i = lane % 3;
+      double acc = 0;
+      for (int k = kb; k < ke; ++k) acc += tP[k * 3 + i];
+      best = nan_max(best, acc / ml[r0 + lane / 3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  }
+  best = wave_max_all(best);
+  if (lane == 0) sM[wave] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double m = sM[0];
+    for (int w = 1; w < FEA_WAVES_PER_WG; ++w) m = nan_max(m, sM[w]);
+    part[blockIdx.x] = m;
+  }
+}
+
+// *out = max of part[0 .. n): one block
+__global__ __launch_bounds__(256)
+void k_max_final(int n, const double *__restrict__ part, double *__restrict__ out)
+{
+  __shared__ double sh[4];
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) v = nan_max(v, part[i]);
+  v = wave_max_all(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = nan_max(nan_max(sh[0], sh[1]), nan_max(sh[2], sh[3]));
+}
+
+int launch_gershgorin(feahip_ctx *c)
+{
+  const int g = spmv_grid(c);
+  hipLaunchKernelGGL(k_gershgorin, dim3(g), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, c->chunk0, c->nchunks_local, c->d_chunk,
+                     c->d_rowptr, (const double *)c->d_K, (const double *)c->mass.d_ml, c->d_part);
+  hipLaunchKernelGGL(k_max_final, dim3(1), dim3(256), 0, c->stream, g, (const double *)c->d_part, c->d_scal + 8);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+// ------------------------------------------------------------------------
 // dot product over the owned rows (two-stage, fixed order)
 // ------------------------------------------------------------------------
 __global__ __launch_bounds__(256)
@@ -1002,6 +1102,24 @@ struct GroupTransport : Transport {
     for (auto *c : R) {
       (void)hipSetDevice(c->device);
       FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_scal + 8 + slot, sum, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+      FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    }
+    return FEAHIP_OK;
+  }
+  int allreduce_max(std::vector<feahip_ctx *> &R, int slot, int n) override
+  {
+    double best[8], tmp[8];
+    bool first = true;
+    for (auto *c : R) {
+      (void)hipSetDevice(c->device);
+      FEA_HIP_CHECK(c, hipMemcpyAsync(tmp, c->d_scal + 8 + slot, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+      FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+      for (int i = 0; i < n; ++i) best[i] = first || tmp[i] != tmp[i] || tmp[i] > best[i] ? tmp[i] : best[i];   // (a NaN stays)
+      first = false;
+    }
+    for (auto *c : R) {
+      (void)hipSetDevice(c->device);
+      FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_scal + 8 + slot, best, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
       FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     }
     return FEAHIP_OK;

@@ -132,6 +132,12 @@ ABI = {
                              C.c_double, C.c_int, _dp, C.c_int, _ip, _ip],
     "feahip_group_solve_dynamic": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, _dp, C.c_int, _ip, _ip],
+    "feahip_get_lumped_mass": [C.c_void_p, _dp],
+    "feahip_stable_step": [C.c_void_p, _dp],
+    "feahip_kinetic_energy": [C.c_void_p, _dp],
+    "feahip_solve_explicit": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _dp, C.c_int, _ip],
+    "feahip_group_solve_explicit": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _dp,
+                                    C.c_int, _ip],
 }
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
@@ -182,6 +188,7 @@ class FeaDeck(C.Structure):
         ("has_dynamics", C.c_int), ("dynamics_steps", C.c_int), ("dynamics_dt", C.c_double), ("dynamics_beta", C.c_double),
         ("dynamics_gamma", C.c_double), ("dynamics_dlambda", C.c_double), ("density", C.c_double),
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
+        ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
     ]
 
 
@@ -255,7 +262,8 @@ def element_tables(ele_type, gauss_count):
 def _take_dynamics(obj, kw):
     """The implicit-dynamics fields of a Deck or a Slab: density (a number, or one per material for FeaSolver.set_mass; the
     .sexp grammar holds one number), body_force[3] (an acceleration per unit mass) and dynamics = dict(steps, dt, beta,
-    gamma, dlambda)."""
+    gamma, dlambda) -- or, for the explicit scheme, dict(steps, dt, dlambda, scheme="explicit", safety, restep), where
+    dt = 0 asks for safety times the stable-step estimate, made again every restep steps."""
     obj.density = kw.get("density")
     bf = kw.get("body_force")
     obj.body_force = None if bf is None else np.ascontiguousarray(bf, dtype=np.float64).reshape(3)
@@ -263,6 +271,12 @@ def _take_dynamics(obj, kw):
     obj.dynamics = None if dyn is None else {"steps": int(dyn.get("steps", 0)), "dt": float(dyn["dt"]),
                                              "beta": float(dyn.get("beta", 0.25)), "gamma": float(dyn.get("gamma", 0.5)),
                                              "dlambda": float(dyn.get("dlambda", 0.0))}
+    if dyn is not None and dyn.get("scheme", "newmark") != "newmark":
+        if dyn["scheme"] != "explicit":
+            raise ValueError("dynamics scheme: newmark or explicit")
+        obj.dynamics.update(scheme="explicit", safety=float(dyn.get("safety", 0.9)), restep=int(dyn.get("restep", 0)))
+    elif dyn is not None and ("safety" in dyn or "restep" in dyn):
+        raise ValueError("safety and restep belong to the explicit scheme")
     if (obj.dynamics is not None or obj.body_force is not None) and obj.density is None:
         raise ValueError("dynamics and body_force need a density")
 
@@ -334,7 +348,9 @@ class Deck:
                 density=fd.density if fd.has_dynamics else None,
                 body_force=[fd.body_force[k] for k in range(3)] if fd.has_body_force else None,
                 dynamics=dict(steps=fd.dynamics_steps, dt=fd.dynamics_dt, beta=fd.dynamics_beta, gamma=fd.dynamics_gamma,
-                              dlambda=fd.dynamics_dlambda) if fd.has_dynamics else None)
+                              dlambda=fd.dynamics_dlambda,
+                              **(dict(scheme="explicit", safety=fd.dynamics_safety, restep=fd.dynamics_restep)
+                                 if fd.dynamics_explicit else {})) if fd.has_dynamics else None)
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -371,6 +387,8 @@ class Deck:
             fd.has_dynamics, fd.density = 1, float(rho[0])
             fd.dynamics_steps, fd.dynamics_dt = dyn["steps"], dyn["dt"]
             fd.dynamics_beta, fd.dynamics_gamma, fd.dynamics_dlambda = dyn["beta"], dyn["gamma"], dyn["dlambda"]
+            if dyn.get("scheme") == "explicit":
+                fd.dynamics_explicit, fd.dynamics_safety, fd.dynamics_restep = 1, dyn["safety"], dyn["restep"]
             if getattr(self, "body_force", None) is not None:
                 fd.has_body_force = 1
                 for k in range(3):
@@ -655,6 +673,39 @@ class FeaSolver:
             d.solver_max_iter if solver_max_iter is None else solver_max_iter, _d(tol_log), cap, _i(its), C.byref(done)))
         n = int(its[:min(done.value + 1, ns)].sum())
         return done.value, its[:ns], tol_log[:n]
+
+    # ---- explicit steps on the lumped mass ---------------------------------
+    def lumped_mass(self):
+        """feahip_get_lumped_mass: ml[N], authoritative on the owned rows, zero elsewhere."""
+        ml = np.zeros(self.N)
+        self._chk(self._lib.feahip_get_lumped_mass(self._ctx, _d(ml)))
+        return ml
+
+    def stable_step(self):
+        """feahip_stable_step: 2 / sqrt(Gershgorin bound) at the current nodes (collective on a group)."""
+        dt = C.c_double(0)
+        self._chk(self._lib.feahip_stable_step(self._ctx, C.byref(dt)))
+        return dt.value
+
+    def kinetic_energy(self):
+        e = C.c_double(0)
+        self._chk(self._lib.feahip_kinetic_energy(self._ctx, C.byref(e)))
+        return e.value
+
+    def solve_explicit(self, n_steps=None, dt=None, safety=None, restep=None, dlambda=None, check=True):
+        """feahip_solve_explicit; arguments left out come from the deck (its `dynamics`).  Returns (steps done, dt_log
+        of the steps taken) and, with check=False, the return code as a third item instead of raising on an inversion."""
+        dyn = getattr(self.deck, "dynamics", None) or {}
+        ns = int(dyn.get("steps", 0) if n_steps is None else n_steps)
+        log, done = np.zeros(max(ns, 1)), C.c_int(0)
+        rc = self._lib.feahip_solve_explicit(
+            self._ctx, ns, float(dyn.get("dt", 0.0) if dt is None else dt),
+            float(dyn.get("safety", 0.9) if safety is None else safety), int(dyn.get("restep", 0) if restep is None else restep),
+            float(dyn.get("dlambda", 0.0) if dlambda is None else dlambda), _d(log), len(log), C.byref(done))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        taken = log[:ns][log[:ns] > 0]
+        return (done.value, taken) if check else (done.value, taken, rc)
 
     # ---- surface loads ---------------------------------------------------
     def set_surface_loads(self, faces, kind, values):
@@ -1372,6 +1423,26 @@ class FeaGroup:
                                                        _d(tol_log), cap, _i(its), C.byref(done)))
         n = int(its[:min(done.value + 1, n_steps)].sum())
         return done.value, its[:n_steps], tol_log[:n]
+
+    def stable_step(self):
+        return self.ranks[0].stable_step()                      # one call drives the group
+
+    def kinetic_energy(self):
+        return self.ranks[0].kinetic_energy()
+
+    def lumped_mass(self):
+        """The owned rows of every rank's lumped mass, stitched together ([N] of the whole mesh)."""
+        out = np.zeros(self.n_global)
+        for r, nd in zip(self.ranks, self.nodes):
+            ml = r.lumped_mass()
+            out[nd] = ml[:r.n_own] if self.rank_contexts else ml[nd]
+        return out
+
+    def solve_explicit(self, n_steps, dt, safety=0.9, restep=0, dlambda=0.0):
+        log, done = np.zeros(max(n_steps, 1)), C.c_int(0)
+        self._chk(self._lib.feahip_group_solve_explicit(self._arr, self.n, n_steps, float(dt), float(safety), int(restep),
+                                                        float(dlambda), _d(log), len(log), C.byref(done)))
+        return done.value, log[:done.value]
 
     def gather(self, name):
         """Owned rows of a per-node ([N][3]) or per-dof ([3N]) getter, stitched together."""

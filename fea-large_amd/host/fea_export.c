@@ -82,7 +82,8 @@ int fea_solve_arclength_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *
   return rc ? rc : done;
 }
 
-/* (dynamics :steps N ...) with N > 0: the Newmark steps of feahip_solve_dynamic; the final state is the one snapshot */
+/* (dynamics :steps N ...) with N > 0: the Newmark steps of feahip_solve_dynamic, or the explicit steps of
+ * feahip_solve_explicit; the final state is the one snapshot */
 int fea_solve_dynamic_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *logp, fea_step_snapshot *last)
 {
   FILE *log = (FILE *)logp;
@@ -91,6 +92,24 @@ int fea_solve_dynamic_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *lo
   int *its = (int *)calloc((size_t)(n > 0 ? n : 1), sizeof *its);
   int done = 0, rc, i;
   if (!its) return FEAHIP_ENOMEM;
+  if (d->dynamics_explicit) {                         /* :scheme explicit: central differences on the lumped mass */
+    double *dts = (double *)calloc((size_t)(n > 0 ? n : 1), sizeof *dts), t = 0;
+    free(its);
+    if (!dts) return FEAHIP_ENOMEM;
+    rc = feahip_solve_explicit(ctx, n, d->dynamics_dt, d->dynamics_safety, d->dynamics_restep, d->dynamics_dlambda, dts, n, &done);
+    if (log)
+      for (i = 0; i < done; ++i) {
+        t += dts[i];
+        fprintf(log, "Explicit step %d finished: time %.17g, dt %.17g\n", i + 1, t, dts[i]);
+      }
+    free(dts);
+    if (rc == FEAHIP_ENOTCONVERGED && log) fprintf(log, "Inverted elements after explicit step %d, exit\n", done);
+    if (rc && rc != FEAHIP_ENOTCONVERGED) return rc;
+    k.steps = last; k.cap = 1; k.S = NULL;
+    rc = keep_snapshot(d, ctx, 0, &k);
+    free(k.S);
+    return rc ? rc : done;
+  }
   rc = feahip_solve_dynamic(ctx, n, d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda,
                             d->max_newton_count, d->desired_tolerance, d->solver_type, d->solver_tolerance,
                             d->solver_max_iter, NULL, 0, its, &done);

@@ -78,6 +78,14 @@ typedef struct fea_deck {
   double dynamics_dt, dynamics_beta, dynamics_gamma, dynamics_dlambda, density;
   int has_body_force;
   double body_force[3];
+  /* explicit dynamics: (dynamics ... :scheme explicit :safety s :restep n) runs feahip_solve_explicit on the lumped mass
+   * instead of the Newmark steps.  :dt 0 (legal with this scheme only) asks for dt = :safety times the stable-step
+   * estimate, made again every :restep steps (:safety 0.9 and :restep 0, once, where absent); :beta and :gamma are
+   * ignored.  :safety and :restep without :scheme explicit, a :scheme other than newmark / explicit and :dt 0 with
+   * Newmark are load errors.  The three attributes are written only for the explicit scheme                    */
+  int dynamics_explicit;
+  double dynamics_safety;
+  int dynamics_restep;
 } fea_deck;
 
 /* sexp_data_load (sexp_loader.c:275-327).  Returns 0, or -1 with a message
@@ -135,7 +143,8 @@ int fea_solve_arclength_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, voi
                                       fea_step_snapshot *last);
 
 /* The run of a deck with (dynamics :steps N ...), N > 0: feahip_solve_dynamic; one log line per completed step
- * ("Dynamic step k finished: time t, n iterations"); *last receives the final state.  Returns the completed steps
+ * ("Dynamic step k finished: time t, n iterations"; the explicit scheme: feahip_solve_explicit and
+ * "Explicit step k finished: time t, dt h"); *last receives the final state.  Returns the completed steps
  * or a negative FEAHIP_E* code.                                               */
 int fea_solve_dynamic_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void *log, fea_step_snapshot *last);
 

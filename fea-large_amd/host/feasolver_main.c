@@ -8,7 +8,8 @@
  * followed along its equilibrium path by feahip_solve_arclength (N steps at
  * most, up to the load factor load-increments); the file then holds the final
  * state as its one step.  A deck with (dynamics :steps N ...), N > 0, takes N
- * Newmark steps (feahip_solve_dynamic) and likewise writes the final state.
+ * Newmark steps (feahip_solve_dynamic), or with :scheme explicit N explicit
+ * steps (feahip_solve_explicit), and likewise writes the final state.
  * Every other deck takes the reference's loop.
  *
  * One option the reference does not have, after the deck name:

@@ -440,7 +440,24 @@ static int read_list(reader *r, fea_deck *d)
     if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "dynamics :steps must be a non-negative integer");
     d->dynamics_steps = (int)v;
     if (need_num(r, a, na, "dt", &d->dynamics_dt)) return -1;
-    if (!(d->dynamics_dt > 0)) return fail(r, "dynamics :dt must be positive");
+    d->dynamics_explicit = 0; d->dynamics_safety = 0.9; d->dynamics_restep = 0;
+    if (attr_get(a, na, "scheme")) {
+      const char *sc = attr_get(a, na, "scheme");
+      if (ieq(sc, "explicit")) d->dynamics_explicit = 1;
+      else if (!ieq(sc, "newmark")) return fail(r, "dynamics :scheme must be newmark or explicit");
+    }
+    if (!d->dynamics_explicit && (attr_get(a, na, "safety") || attr_get(a, na, "restep")))
+      return fail(r, "dynamics :safety and :restep need :scheme explicit");
+    if (d->dynamics_explicit) {
+      if (attr_get(a, na, "safety") && need_num(r, a, na, "safety", &d->dynamics_safety)) return -1;
+      if (!(d->dynamics_safety > 0 && d->dynamics_safety <= 1)) return fail(r, "dynamics :safety must be in (0, 1]");
+      if (attr_get(a, na, "restep")) {
+        if (need_num(r, a, na, "restep", &v)) return -1;
+        if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "dynamics :restep must be a non-negative integer");
+        d->dynamics_restep = (int)v;
+      }
+      if (!(d->dynamics_dt >= 0)) return fail(r, "dynamics :dt must not be negative");
+    } else if (!(d->dynamics_dt > 0)) return fail(r, "dynamics :dt must be positive");
     d->dynamics_beta = 0.25; d->dynamics_gamma = 0.5; d->dynamics_dlambda = 0;
     if (attr_get(a, na, "beta") && need_num(r, a, na, "beta", &d->dynamics_beta)) return -1;
     if (attr_get(a, na, "gamma") && need_num(r, a, na, "gamma", &d->dynamics_gamma)) return -1;
@@ -570,8 +587,11 @@ int fea_deck_save(const char *path, const fea_deck *d)
           d->solver_tolerance, d->solver_max_iter);
   fprintf(f, "   (line-search :max %d)\n   (arc-length :max %d)", d->linesearch_max, d->arclength_max);
   if (d->has_dynamics)                               /* written only when present: other decks save as before */
-    fprintf(f, "\n   (dynamics :steps %d :dt %.17g :beta %.17g :gamma %.17g :dlambda %.17g :density %.17g)", d->dynamics_steps,
+    fprintf(f, "\n   (dynamics :steps %d :dt %.17g :beta %.17g :gamma %.17g :dlambda %.17g :density %.17g", d->dynamics_steps,
             d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda, d->density);
+  if (d->has_dynamics && d->dynamics_explicit)
+    fprintf(f, " :scheme explicit :safety %.17g :restep %d", d->dynamics_safety, d->dynamics_restep);
+  if (d->has_dynamics) fprintf(f, ")");
   fprintf(f, ")\n");
   fprintf(f, " (input-data\n  (geometry\n   (nodes");
   for (i = 0; i < d->nodes_count; ++i)

@@ -488,6 +488,55 @@ int feahip_group_solve_dynamic(feahip_ctx **ctxs, int n, int n_steps, double dt,
                                double dlambda, int max_newton, double desired_tolerance, int solver_type,
                                double solver_tolerance, int solver_max_iter, double *tol_log, int tol_log_cap,
                                int *its_log, int *steps_done);
+/* ---- explicit dynamics: central differences on a lumped mass --------------
+ * The state (x, v, a, time, load factor) is the Newmark state, with the same
+ * getters and setters: a caller may switch between feahip_solve_dynamic and
+ * feahip_solve_explicit on one context.  All entries below return
+ * FEAHIP_ESTATE without a mass (feahip_set_mass); the lumped mass is built on
+ * the first of them, from the rule and the densities of the last
+ * feahip_set_mass, and again when the shard or the material ids change.
+ *
+ * feahip_get_lumped_mass: ml[N] in the caller's node ids, HRZ-lumped per
+ * element (ml_a = sum_e m_e d_a / sum_b d_b, d_a = sum_g rho w det J0 N_a^2):
+ * positive on every element type, each element's mass kept.  Authoritative on
+ * the owned rows of a sharded context, zero elsewhere.
+ *
+ * feahip_stable_step (collective like feahip_consistent_acceleration):
+ * *dt_crit = 2 / sqrt(max_i sum_j |K_ij| / ml(i)), Gershgorin's bound on the
+ * largest frequency of M_L^-1 K with K the tangent at the current x (assembled
+ * here, not masked: K holds another matrix afterwards, as after an assembly).
+ *
+ * feahip_kinetic_energy (collective): 1/2 sum ml |v|^2 over the owned nodes.
+ *
+ * feahip_solve_explicit: n_steps of
+ *   vh = v + dt/2 a;  x += dt vh  (prescribed dofs: x += dlambda * value);
+ *   load factor += dlambda;  f = lambda (F_surf + F_body) - T(x);
+ *   a = f / ml;  v = vh + dt/2 a;  time += dt
+ * with a = 0 and v = dlambda * value / dt on the prescribed dofs.  One residual
+ * assembly and two pointwise kernels per step; no stiffness assembly, no solve.
+ * dt > 0: a fixed step (safety, restep ignored).  dt == 0: dt = safety *
+ * feahip_stable_step, estimated before the first step and again every restep
+ * steps (restep <= 0: once); 0 < safety <= 1.  dt_log (may be NULL) receives
+ * the step used in each step, up to dt_log_cap entries.  Elements with
+ * det J <= 0 (or NaN) at a Gauss point are counted by a pass of their own over
+ * the current nodes, on every element type alike, before every estimate and
+ * once after the last step; nothing is read back anywhere else.  The counts
+ * of all ranks meet in a max all-reduce before anything depends on them: an
+ * inversion on any rank ends the loop on every rank with
+ * FEAHIP_ENOTCONVERGED, *steps_done = the steps done at the previous check,
+ * and the state is left as it is -- explicit steps cannot be rolled back.
+ * feahip_update_state reports that count afterwards.
+ * v and a are authoritative on owned nodes only: a halo node holds
+ * v = (its displacement of the step) / dt and a = 0.
+ * FEAHIP_EINVAL: dt < 0, n_steps < 0, safety outside (0, 1] with dt == 0.   */
+int feahip_get_lumped_mass(feahip_ctx *ctx, double *ml);
+int feahip_stable_step(feahip_ctx *ctx, double *dt_crit);
+int feahip_kinetic_energy(feahip_ctx *ctx, double *e);
+int feahip_solve_explicit(feahip_ctx *ctx, int n_steps, double dt, double safety, int restep,
+                          double dlambda, double *dt_log, int dt_log_cap, int *steps_done);
+int feahip_group_solve_explicit(feahip_ctx **ctxs, int n, int n_steps, double dt, double safety,
+                                int restep, double dlambda, double *dt_log, int dt_log_cap,
+                                int *steps_done);
 /* z = M^-1 r on every rank of the group at once, with the preconditioner the
  * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
  * feahip_apply_preconditioner takes them (the caller's node ids of context k;
@@ -732,7 +781,10 @@ int feahip_sync(feahip_ctx *ctx);
  * surface-load kernels alone (refused on a context without loaded faces),
  * 6 the two-vector SpMV, 7 one two-column PCG iteration (feahip_solve_slae2;
  * both refused where that solve is), 8 K += M (k_mass_add), 9 the inertia
- * term of the residual (k_mass_residual; 8 and 9 refused without a mass).   */
+ * term of the residual (k_mass_residual; 8 and 9 refused without a mass),
+ * 10 the two pointwise kernels of an explicit step together (they advance v
+ * and a by a step of dt = 1 on the f in force), 11 k_gershgorin on the K in
+ * force (10 and 11 refused without a mass).                                 */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
