@@ -5,12 +5,12 @@
 // wave shuffles, then the four waves in order), a second pass adds the slices in order.  No atomics anywhere, so a
 // repeated setup or application gives identical bits.
 #include "coarse.h"
+#include "reduce_device.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
 static inline RankCoarse *RC(const feahip_ctx *c) { return static_cast<RankCoarse *>(c->coarse); }
-#define FOR_RANKS(c) for (feahip_ctx *c : R) if (hipSetDevice(c->device) == hipSuccess)
 
 // ------------------------------------------------------------------------
 // the cut rule
@@ -36,34 +36,6 @@ int coarse_default_m(int nranks)
 // ------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------
-__device__ __forceinline__ double cwave_sum(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double cwave_sum_all(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// NV sums over the 256 threads of a block, each in the same fixed order; out[k] valid in thread k < NV afterwards
-template <int NV>
-__device__ __forceinline__ double cblock_sums(double (&v)[NV], double (*scratch)[NV] /*[4][NV]*/)
-{
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const double s = cwave_sum(v[k]);
-    if (lane == 0) scratch[wave][k] = s;
-  }
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x < NV) r = ((scratch[0][threadIdx.x] + scratch[1][threadIdx.x]) + scratch[2][threadIdx.x]) + scratch[3][threadIdx.x];
-  __syncthreads();
-  return r;
-}
 // rows [lo, hi) of slice s of ns of the rows [r0, r1)
 __device__ __forceinline__ void slice_rows(int r0, int r1, int s, int ns, int &lo, int &hi)
 {
@@ -132,7 +104,7 @@ void k_coarse_setup(int ns, const int *__restrict__ first, const int *__restrict
       acc[30 + j] += d0 * Y[1][j] - d1 * Y[0][j];
     }
   }
-  const double r = cblock_sums<36>(acc, scratch);
+  const double r = block_sums<36>(acc, scratch);
   if (threadIdx.x < 36) apart[((size_t)p * ns + s) * 36 + threadIdx.x] = r;
 }
 
@@ -169,7 +141,7 @@ void k_coarse_restrict(int ns, const int *__restrict__ first, const int *__restr
     acc[0] += v0; acc[1] += v1; acc[2] += v2;
     acc[3] += d1 * v2 - d2 * v1; acc[4] += d2 * v0 - d0 * v2; acc[5] += d0 * v1 - d1 * v0;
   }
-  const double t = cblock_sums<6>(acc, scratch);
+  const double t = block_sums<6>(acc, scratch);
   if (threadIdx.x < 6) rpart[((size_t)A * ns + s) * 6 + threadIdx.x] = t;
 }
 
@@ -194,7 +166,7 @@ void k_coarse_solve(int nc, const double *__restrict__ Ainv, const double *__res
   const double *m = Ainv + (size_t)row * nc;
   double v = 0;
   for (int j = lane; j < nc; j += 64) v += m[j] * rc[j];
-  v = cwave_sum_all(v);
+  v = wave_sum_all(v);
   if (lane == 0) ec[row] = v;
 }
 
@@ -219,7 +191,7 @@ void k_coarse_copy_dot(int i0, int i1, const double *__restrict__ z, const doubl
     const double zi = z[i] + phi_e(i / 3, i % 3, agg, cent, X0, ec);
     znew[i] = zi; v[0] += r[i] * zi;
   }
-  const double s = cblock_sums<1>(v, scratch);
+  const double s = block_sums<1>(v, scratch);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 

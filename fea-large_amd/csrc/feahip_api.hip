@@ -801,12 +801,21 @@ static int group_vec(feahip_ctx **ctxs, int n, std::vector<feahip_ctx *> &R)
   return FEAHIP_OK;
 }
 
+// The one way the error text of a collective call reaches the caller: a failed call (rc != 0) whose handle `to` holds
+// no message gets the first one any of the ranks R holds.  Returns rc.
+static int surface_error(feahip_ctx *to, const std::vector<feahip_ctx *> &R, int rc)
+{
+  if (rc && to->err.empty())
+    for (feahip_ctx *r : R) if (!r->err.empty()) { to->err = r->err; break; }
+  return rc;
+}
+
 extern "C" int feahip_group_solve_slae(feahip_ctx **ctxs, int n, int type, double tol, int max_iter, int *iters, double *resid)
 {
   std::vector<feahip_ctx *> R;
   int rc = group_vec(ctxs, n, R);
   if (rc) return rc;
-  return dist_solve_pcg(R, type, tol, max_iter, iters, resid);
+  return surface_error(R[0], R, dist_solve_pcg(R, type, tol, max_iter, iters, resid));
 }
 
 extern "C" int feahip_group_energy(feahip_ctx **ctxs, int n, double *tolerance)
@@ -814,7 +823,7 @@ extern "C" int feahip_group_energy(feahip_ctx **ctxs, int n, double *tolerance)
   std::vector<feahip_ctx *> R;
   int rc = group_vec(ctxs, n, R);
   if (rc) return rc;
-  return dist_energy(R, tolerance);
+  return surface_error(R[0], R, dist_energy(R, tolerance));
 }
 
 extern "C" int feahip_group_update_nodes_with_solution(feahip_ctx **ctxs, int n)
@@ -822,7 +831,7 @@ extern "C" int feahip_group_update_nodes_with_solution(feahip_ctx **ctxs, int n)
   std::vector<feahip_ctx *> R;
   int rc = group_vec(ctxs, n, R);
   if (rc) return rc;
-  return dist_update_nodes_with_solution(R, nullptr);
+  return surface_error(R[0], R, dist_update_nodes_with_solution(R, nullptr));
 }
 
 extern "C" int feahip_group_solve(feahip_ctx **ctxs, int n, int load_increments, int max_newton, int modified_newton,
@@ -832,8 +841,8 @@ extern "C" int feahip_group_solve(feahip_ctx **ctxs, int n, int load_increments,
   std::vector<feahip_ctx *> R;
   int rc = group_vec(ctxs, n, R);
   if (rc) return rc;
-  return dist_newton(R, load_increments, max_newton, modified_newton, desired_tolerance, solver_type,
-                     solver_tolerance, solver_max_iter, tol_log, tol_log_cap, its_log, steps_done);
+  return surface_error(R[0], R, dist_newton(R, load_increments, max_newton, modified_newton, desired_tolerance, solver_type,
+                                            solver_tolerance, solver_max_iter, tol_log, tol_log_cap, its_log, steps_done));
 }
 
 extern "C" int feahip_owned_rows(feahip_ctx *c, int *row0, int *row1)
@@ -946,7 +955,7 @@ extern "C" int feahip_get_forces(feahip_ctx *c, double *f) { CTX_GUARD(c); retur
 extern "C" int feahip_get_solution(feahip_ctx *c, double *u) { CTX_GUARD(c); return get_node_vec(c, c->d_u, u); }
 extern "C" int feahip_set_forces(feahip_ctx *c, const double *f) { CTX_GUARD(c); return set_node_vec(c, c->d_f, f); }
 
-// ---- consistent mass, body force and implicit dynamics (kernels_mass.hip, dist.hip) -------------------------------
+// ---- consistent mass, body force and implicit dynamics (kernels_mass.hip, drivers.hip) ----------------------------
 extern "C" int feahip_set_mass(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights,
                                const double *forms, const double *dforms)
 {
@@ -1031,9 +1040,7 @@ extern "C" int feahip_consistent_acceleration(feahip_ctx *c, int solver_type, do
   if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "unknown solver type"; return FEAHIP_EINVAL; }
   if (max_iter <= 0) { c->err = "max_iterations must be positive"; return FEAHIP_EINVAL; }
   std::vector<feahip_ctx *> R = ranks_of(c);
-  const int rc = dist_consistent_acceleration(R, solver_type, tol, max_iter);
-  if (rc && c->err.empty()) c->err = R[0]->err;
-  return rc;
+  return surface_error(c, R, dist_consistent_acceleration(R, solver_type, tol, max_iter));
 }
 
 static int dynamic_args(feahip_ctx *c, int n_steps, double dt, double beta, double gamma, int max_newton, int solver_type,
@@ -1072,11 +1079,10 @@ extern "C" int feahip_group_solve_dynamic(feahip_ctx **ctxs, int n, int n_steps,
   for (feahip_ctx *c : R) { CTX_GUARD(c); }
   rc = dist_dynamic(R, n_steps, dt, beta, gamma, dlambda, max_newton, desired_tolerance, solver_type, solver_tolerance,
                     solver_max_iter, tol_log, tol_log_cap, its_log, steps_done);
-  if (rc && R[0]->err.empty()) for (feahip_ctx *c : R) if (!c->err.empty()) { R[0]->err = c->err; break; }
-  return rc;
+  return surface_error(R[0], R, rc);
 }
 
-// ---- explicit dynamics on the lumped mass (kernels_mass.hip, kernels_solve.hip, dist.hip) ---------------------------
+// ---- explicit dynamics on the lumped mass (kernels_mass.hip, kernels_solve.hip, drivers.hip) ------------------------
 extern "C" int feahip_get_lumped_mass(feahip_ctx *c, double *ml)
 {
   CTX_GUARD_NOK(c);
@@ -1094,9 +1100,7 @@ extern "C" int feahip_stable_step(feahip_ctx *c, double *dt_crit)
   CTX_GUARD(c);
   if (!dt_crit) return FEAHIP_EINVAL;
   std::vector<feahip_ctx *> R = ranks_of(c);
-  const int rc = dist_stable_step(R, dt_crit);
-  if (rc && c->err.empty()) for (feahip_ctx *r : R) if (!r->err.empty()) { c->err = r->err; break; }
-  return rc;
+  return surface_error(c, R, dist_stable_step(R, dt_crit));
 }
 
 extern "C" int feahip_kinetic_energy(feahip_ctx *c, double *e)
@@ -1104,9 +1108,7 @@ extern "C" int feahip_kinetic_energy(feahip_ctx *c, double *e)
   CTX_GUARD_NOK(c);
   if (!e) return FEAHIP_EINVAL;
   std::vector<feahip_ctx *> R = ranks_of(c);
-  const int rc = dist_kinetic_energy(R, e);
-  if (rc && c->err.empty()) for (feahip_ctx *r : R) if (!r->err.empty()) { c->err = r->err; break; }
-  return rc;
+  return surface_error(c, R, dist_kinetic_energy(R, e));
 }
 
 static int explicit_args(feahip_ctx *c, int n_steps, double dt, double safety, int *steps_done)
@@ -1137,8 +1139,7 @@ extern "C" int feahip_group_solve_explicit(feahip_ctx **ctxs, int n, int n_steps
   if ((rc = explicit_args(R[0], n_steps, dt, safety, steps_done))) return rc;
   for (feahip_ctx *c : R) { CTX_GUARD_NOK(c); }
   rc = dist_explicit(R, n_steps, dt, safety, restep, dlambda, dt_log, dt_log_cap, steps_done);
-  if (rc && R[0]->err.empty()) for (feahip_ctx *c : R) if (!c->err.empty()) { R[0]->err = c->err; break; }
-  return rc;
+  return surface_error(R[0], R, rc);
 }
 
 // ---- two-column solve (kernels_solve2.hip) ---------------------------------
@@ -1354,7 +1355,7 @@ extern "C" int feahip_group_apply_preconditioner(feahip_ctx **ctxs, int n, const
     if ((rc = set_node_vec(c, c->d_r, r[k]))) return rc;
   }
   std::vector<const double *> dz((size_t)n, nullptr);
-  if ((rc = dist_precond_apply(R, dz.data()))) return rc;
+  if ((rc = surface_error(R[0], R, dist_precond_apply(R, dz.data())))) return rc;
   for (int k = 0; k < n; ++k) {
     feahip_ctx *c = R[k];
     FEA_HIP_CHECK(c, hipSetDevice(c->device));
@@ -1488,7 +1489,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (rk) return rk;
   }
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
-  auto one = [&]() -> int {
+  return time_enqueued(c, warmup, iters, avg_ms, [&](int) -> int {
     switch (what) {
     case 0: return launch_assemble(c, true, true);
     case 1: return launch_assemble(c, true, false);
@@ -1502,21 +1503,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 11: return launch_gershgorin(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
-  };
-  int rc;
-  for (int k = 0; k < warmup; ++k) if ((rc = one())) return rc;
-  hipEvent_t e0, e1;
-  FEA_HIP_CHECK(c, hipEventCreate(&e0));
-  FEA_HIP_CHECK(c, hipEventCreate(&e1));
-  FEA_HIP_CHECK(c, hipEventRecord(e0, c->stream));
-  for (int k = 0; k < iters; ++k) if ((rc = one())) return rc;
-  FEA_HIP_CHECK(c, hipEventRecord(e1, c->stream));
-  FEA_HIP_CHECK(c, hipEventSynchronize(e1));
-  float ms = 0;
-  FEA_HIP_CHECK(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *avg_ms = (double)ms / iters;
-  return FEAHIP_OK;
+  });
 }
 
 // Streaming copies: the copy bandwidth of THIS box, the figure the roofline fractions can be quoted against next to the

@@ -588,6 +588,10 @@ int precond_apply(feahip_ctx *c, const double *r, const double **z);   // kernel
 int solve_pcg(feahip_ctx *c, int type, double tol, int max_iter, int *iters,
               double *resid);
 int time_pcg_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);
+// host half shared by the PCG loops (kernels_solve.hip): iterations and residual from a stop flag and its scalars
+bool pcg_outcome(int flag, int it, const double *scal, int *iters, double *resid);
+// out[k] = sum of part[k*stride .. k*stride+n) for k < nsums, on the context's stream (k_reduce_final, reduce_device.h)
+void enq_reduce_final(feahip_ctx *c, int n, int nsums, int stride, const double *part, double *out);
 void enq_precond_blockjacobi(feahip_ctx *c);                            // kernels_solve.hip
 // kernels_solve2.hip -- K [u, u2] = [f, f2] over one read of K per iteration; paired vectors are [3N][2]
 int ensure_solve2(feahip_ctx *c);
@@ -619,17 +623,17 @@ int launch_kinetic_energy(feahip_ctx *c, double *d_out);       // *d_out = 1/2 s
 int launch_count_inverted(feahip_ctx *c);                      // d_flag[1] = elements with det J <= 0 (or NaN) at a Gauss point of x
 // kernels_solve.hip -- Gershgorin bound max_i sum_j |K_ij| / ml(i) over the owned rows into d_scal[8]
 int launch_gershgorin(feahip_ctx *c);
-// dist.hip -- Newmark steps and the consistent acceleration over one or more ranks
+// drivers.hip -- Newmark steps and the consistent acceleration over one or more ranks
 int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double beta, double gamma, double dlambda,
                  int max_newton, double desired_tolerance, int solver_type, double solver_tolerance, int solver_max_iter,
                  double *tol_log, int tol_log_cap, int *its_log, int *steps_done);
 int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, double tol, int max_iter);
-// dist.hip -- explicit steps, the stable step and the kinetic energy over one or more ranks
+// drivers.hip -- explicit steps, the stable step and the kinetic energy over one or more ranks
 int dist_explicit(std::vector<feahip_ctx *> &R, int n_steps, double dt, double safety, int restep, double dlambda,
                   double *dt_log, int dt_log_cap, int *steps_done);
 int dist_stable_step(std::vector<feahip_ctx *> &R, double *dt_crit);
 int dist_kinetic_energy(std::vector<feahip_ctx *> &R, double *e);
-// dist.hip -- Crisfield's cylindrical arc length on the surface loads (one unsharded context)
+// drivers.hip -- Crisfield's cylindrical arc length on the surface loads (one unsharded context)
 int arclength_solve(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
                     int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log, double *tol_log,
                     int log_cap, int *its_log, int *steps_done);
@@ -679,9 +683,10 @@ int build_rank_mesh_local(int rank, int nranks, int n_global, int n_local, int n
 int slab_order(int n_local, int n_own, int E, int npe, const int *elements, const double *nodes0, int *new_local_id);
 int install_plan(feahip_ctx *c, const ShardPlan &plan);      // dist.hip: halo lists to the device, interior chunk range
 
-// multi-rank operations (kernels_solve.hip).  R = the ranks driven by this
+// multi-rank operations (kernels_solve.hip; the step loops in drivers.hip).  R = the ranks driven by this
 // process: one context with the RCCL transport, or all contexts of an
 // in-process group.
+#define FOR_RANKS(c) for (feahip_ctx *c : R) if (hipSetDevice(c->device) == hipSuccess)
 struct Transport {
   virtual ~Transport() {}
   // halo rows of vector `which` (0 = p, 1 = u, 2 = x, 3 = z) from their owners
@@ -707,7 +712,36 @@ int rccl_unique_id(void *out, int cap);
 int install_shard(feahip_ctx *c, int rank, int nranks);
 int dist_solve_pcg(std::vector<feahip_ctx *> &R, int type, double tol, int max_iter, int *iters, double *resid);
 int dist_energy(std::vector<feahip_ctx *> &R, double *out);
+// d_scal[8 .. 8+n) reduced over the ranks (over the transport, where there is one) and read from R[0] into out
+enum class RankReduce { sum, max };
+int dist_read_scalars(std::vector<feahip_ctx *> &R, RankReduce how, int n, double *out);
 int dist_update_nodes_with_solution(std::vector<feahip_ctx *> &R, const double *u_host);
 int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newton, int modified_newton,
                 double desired_tolerance, int solver_type, double solver_tolerance, int solver_max_iter,
                 double *tol_log, int tol_log_cap, int *its_log, int *steps_done);
+
+// avg_ms = the mean time of one(k) for k in [warmup, warmup + iters) on the context's stream, after one(0 .. warmup);
+// one(k) enqueues and returns a status.  The events are destroyed on every path.
+template <class F>
+int time_enqueued(feahip_ctx *c, int warmup, int iters, double *avg_ms, F one)
+{
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto run = [&]() -> int {
+    int rc;
+    FEA_HIP_CHECK(c, hipEventCreate(&e0));
+    FEA_HIP_CHECK(c, hipEventCreate(&e1));
+    for (int k = 0; k < warmup; ++k) if ((rc = one(k))) return rc;
+    FEA_HIP_CHECK(c, hipEventRecord(e0, c->stream));
+    for (int k = 0; k < iters; ++k) if ((rc = one(warmup + k))) return rc;
+    FEA_HIP_CHECK(c, hipEventRecord(e1, c->stream));
+    FEA_HIP_CHECK(c, hipEventSynchronize(e1));
+    float ms = 0;
+    FEA_HIP_CHECK(c, hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = iters > 0 ? (double)ms / iters : 0.0;
+    return FEAHIP_OK;
+  };
+  const int rc = run();
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}

@@ -20,6 +20,7 @@
 // lump_ensure and framed by two pointwise kernels per step, k_explicit_kick and k_explicit_finish.  A context that
 // never makes an explicit call allocates and launches none of it.
 #include "feahip_internal.h"
+#include "reduce_device.h"
 #include <cmath>
 #include <cstring>
 
@@ -304,16 +305,6 @@ void k_count_inverted(int E, int npe, int G, const int *__restrict__ conn, const
   if (inv) atomicAdd(bad, 1);
 }
 
-// sum over the 256 threads of a block in a fixed order; valid in thread 0
-__device__ __forceinline__ double mass_block_sum(double v, double *sh /*[4]*/)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return threadIdx.x == 0 ? sh[0] + sh[1] + sh[2] + sh[3] : 0.0;
-}
-
 // Kick and drift over the 16-byte pieces of the owned node records [a0, a1): vh = v + dt/2 a, u = dt vh; both 0 on the
 // prescribed dofs (k_explicit_presc then gives vh its prescribed value there)
 __global__ __launch_bounds__(256)
@@ -383,19 +374,8 @@ void k_explicit_finish(int N, int a0, int a1, double dt, const double *__restric
       v[p] = vv; a[p] = aa;
     }
   }
-  ke = mass_block_sum(ke, sh);
+  ke = block_sum(ke, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = ke;
-}
-
-// *out = part[0] + ... + part[n - 1]: one block, fixed order (the pattern of k_reduce_final)
-__global__ __launch_bounds__(256)
-void k_mass_sum_final(int n, const double *__restrict__ part, double *__restrict__ out)
-{
-  __shared__ double sh[4];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-  v = mass_block_sum(v, sh);
-  if (threadIdx.x == 0) *out = v;
 }
 
 // [N][3] -> [N][4] (the pad is written 0)
@@ -526,7 +506,7 @@ int launch_kinetic_energy(feahip_ctx *c, double *d_out)
                        (mass_v2d *)nullptr, M.d_ke_part);
     M.ke_parts = g;
   }
-  hipLaunchKernelGGL(k_mass_sum_final, dim3(1), dim3(256), 0, c->stream, M.ke_parts, M.d_ke_part, d_out);
+  enq_reduce_final(c, M.ke_parts, 1, 0, M.d_ke_part, d_out);
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }

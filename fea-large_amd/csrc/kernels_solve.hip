@@ -12,51 +12,8 @@
 #include <type_traits>
 #include "feahip_internal.h"
 #include "coarse.h"
+#include "reduce_device.h"
 #include <map>
-
-// ------------------------------------------------------------------------
-// small device helpers
-// ------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// the same sum in every lane (butterfly: a fixed order as well)
-__device__ __forceinline__ double wave_sum_all(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// sum over the 256 threads of a block; result valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *scratch /*[4]*/)
-{
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x == 0) r = scratch[0] + scratch[1] + scratch[2] + scratch[3];
-  __syncthreads();
-  return r;
-}
-
-// every block re-reduces the producer kernel's partial sums, in fixed order;
-// result broadcast to all threads
-__device__ __forceinline__ double reduce_partials(const double *part, int n, double *scratch /*[5]*/)
-{
-  double v = 0;
-  for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-  v = block_sum(v, scratch);
-  if (threadIdx.x == 0) scratch[4] = v;
-  __syncthreads();
-  v = scratch[4];
-  __syncthreads();
-  return v;
-}
 
 // ------------------------------------------------------------------------
 // prescribed displacements
@@ -584,11 +541,16 @@ void k_reduce_final(int n, int nsums, int stride, const double *part, double *ou
   }
 }
 
+void enq_reduce_final(feahip_ctx *c, int n, int nsums, int stride, const double *part, double *out)
+{
+  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, n, nsums, stride, part, out);
+}
+
 // ------------------------------------------------------------------------
 // preconditioned conjugate gradients
 //
 // Device scalars (d_scal): [0],[1] r.z ping-pong, [2] b.b, [3] last r.r,
-// [4] tolerance^2, [8..11] reduction results / all-reduce buffer.
+// [4] tolerance^2, [8..15] reduction results / all-reduce buffer (dist_read_scalars).
 // d_flag[0] = iteration at which the stop test fired (0 = still running,
 // <0 = breakdown).  Partial-sum arrays in d_part: [0..RB) p.q, [RB..2RB) r.z,
 // [2RB..3RB) r.r, [3RB..4RB) b.b.
@@ -1153,15 +1115,13 @@ Transport *make_group_transport() { return new GroupTransport(); }
 // ------------------------------------------------------------------------
 // multi-rank PCG.  With one rank and no transport this is the plain solver.
 // ------------------------------------------------------------------------
-#define FOR_RANKS(c) for (feahip_ctx *c : R) if (hipSetDevice(c->device) == hipSuccess)
-
 static int enq_cg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it, int mode)
 {
   int rc;
   if (T && (rc = T->exchange(R, 0))) return rc;                  // halo rows of p
   FOR_RANKS(c) {
     enq_spmv_dot(c, c->d_p, c->d_q, c->d_p, c->d_part);
-    if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, spmv_grid(c), 1, RB, c->d_part, c->d_scal + 8);
+    if (T) enq_reduce_final(c, spmv_grid(c), 1, RB, c->d_part, c->d_scal + 8);
   }
   if (T && (rc = T->allreduce(R, 0, 1))) return rc;              // p.q
   const bool coarse = use_coarse(R, mode);
@@ -1180,7 +1140,7 @@ static int enq_cg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it, 
       if (coarse) { const int rk = coarse_enq_prolong_add(c, z); if (rk) return rk; }   // + Phi e_c, all-reduced meanwhile
       hipLaunchKernelGGL(k_dot_partial, dim3(gv), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), c->d_r, z, c->d_part + RB);
     }
-    if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, gv, 2, RB, c->d_part + RB, c->d_scal + 9);
+    if (T) enq_reduce_final(c, gv, 2, RB, c->d_part + RB, c->d_scal + 9);
     return FEAHIP_OK;
   };
   if (!coarse) {
@@ -1232,7 +1192,7 @@ static int enq_cg_start(std::vector<feahip_ctx *> &R, Transport *T, int mode, do
       FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_p + (size_t)3 * own0(c), z + (size_t)3 * own0(c),
                                       sizeof(double) * 3 * (size_t)(own1(c) - own0(c)), hipMemcpyDeviceToDevice, c->stream));
     }
-    if (T) hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, gv, 3, RB, c->d_part + RB, c->d_scal + 8);
+    if (T) enq_reduce_final(c, gv, 3, RB, c->d_part + RB, c->d_scal + 8);
     return FEAHIP_OK;
   };
   if (!coarse) {
@@ -1396,6 +1356,18 @@ static int enq_cgcg_iteration(std::vector<feahip_ctx *> &R, Transport *T, int it
 
 static inline bool use_cgcg(const feahip_ctx *c, Transport *T) { return c->pcg_variant == 1 || (c->pcg_variant < 0 && T != nullptr); }
 
+// What a solve's stop flag and scalars say on the host (scal: [2] b.b, [3] last r.r): the iterations done -- `it` were
+// enqueued, the flag holds the one the stop test fired at -- and the relative residual.  True on a breakdown.
+bool pcg_outcome(int flag, int it, const double *scal, int *iters, double *resid)
+{
+  if (flag == -1000000000) it = 0;                // solved before the first iteration
+  else if (flag > 0) it = flag;
+  else if (flag < 0) it = -flag;
+  if (iters) *iters = it;
+  if (resid) *resid = (scal[2] > 0) ? sqrt(scal[3] / scal[2]) : sqrt(scal[3]);
+  return flag < 0 && flag != -1000000000;
+}
+
 // Solves K u = f by (preconditioned) CG started from u0 = f, the start vector
 // the reference hands to sp_matrix_yale_solve_cg (fea_solver.c:251-256).
 int dist_solve_pcg(std::vector<feahip_ctx *> &R, int type, double tol, int max_iter, int *iters, double *resid)
@@ -1423,18 +1395,13 @@ int dist_solve_pcg(std::vector<feahip_ctx *> &R, int type, double tol, int max_i
   double sc[5];
   FEA_HIP_CHECK(c0, hipMemcpyAsync(sc, c0->d_scal, sizeof(sc), hipMemcpyDeviceToHost, c0->stream));
   FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
-  int done_it = it;
-  if (flag == -1000000000) done_it = 0;
-  else if (flag > 0) done_it = flag;
-  else if (flag < 0) done_it = -flag;
-  if (iters) *iters = done_it;
-  if (resid) *resid = (sc[2] > 0) ? sqrt(sc[3] / sc[2]) : sqrt(sc[3]);
+  const bool broke = pcg_outcome(flag, it, sc, iters, resid);
   // leave the flag clear so stand-alone SpMV launches are not skipped
   FOR_RANKS(c) {
     FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
   }
-  if (flag < 0 && flag != -1000000000) {
+  if (broke) {
     c0->err = "CG breakdown (NaN or zero curvature) at iteration " + std::to_string(-flag);
     return FEAHIP_ENOTCONVERGED;
   }
@@ -1472,23 +1439,30 @@ int solve_pcg(feahip_ctx *c, int type, double tol, int max_iter, int *iters, dou
   return dist_solve_pcg(R, type, tol, max_iter, iters, resid);
 }
 
+// d_scal[8 .. 8+n) of every context reduced over the ranks (where there is a transport), then read from R[0]: every
+// rank holds, and every caller reads, the same bits
+int dist_read_scalars(std::vector<feahip_ctx *> &R, RankReduce how, int n, double *out)
+{
+  int rc;
+  if (Transport *T = R[0]->tr)
+    if ((rc = how == RankReduce::sum ? T->allreduce(R, 0, n) : T->allreduce_max(R, 0, n))) return rc;
+  feahip_ctx *c0 = R[0];
+  (void)hipSetDevice(c0->device);
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(out, c0->d_scal + 8, sizeof(double) * n, hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  return FEAHIP_OK;
+}
+
 // cdot(f, u) over all ranks (fea_solver.c:208-210)
 int dist_energy(std::vector<feahip_ctx *> &R, double *out)
 {
-  Transport *T = R[0]->tr;
-  int rc;
   FOR_RANKS(c) {
     const int g = vec_grid_range(3 * (own1(c) - own0(c)));
     hipLaunchKernelGGL(k_dot_partial, dim3(g), dim3(256), 0, c->stream, 3 * own0(c), 3 * own1(c), c->d_f, c->d_u, c->d_part);
-    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, g, 1, RB, c->d_part, c->d_scal + 8);
+    enq_reduce_final(c, g, 1, RB, c->d_part, c->d_scal + 8);
     FEA_HIP_CHECK(c, hipGetLastError());
   }
-  if (T && (rc = T->allreduce(R, 0, 1))) return rc;
-  feahip_ctx *c0 = R[0];
-  (void)hipSetDevice(c0->device);
-  FEA_HIP_CHECK(c0, hipMemcpyAsync(out, c0->d_scal + 8, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
-  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
-  return FEAHIP_OK;
+  return dist_read_scalars(R, RankReduce::sum, 1, out);
 }
 
 // solver_update_nodes_with_solution (fea_solver.c:1270-1279) on every rank:
@@ -1541,19 +1515,9 @@ int time_pcg_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms)
   rc = cgcg ? enq_cgcg_start(R, T, 1, 0.0) : enq_cg_start(R, T, 1, 0.0);
   if (rc) return rc;
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-  hipEvent_t e0, e1;
-  FEA_HIP_CHECK(c, hipEventCreate(&e0));
-  FEA_HIP_CHECK(c, hipEventCreate(&e1));
-  for (int k = 0; k < warmup; ++k) if ((rc = cgcg ? enq_cgcg_iteration(R, T, k, 1) : enq_cg_iteration(R, T, k, 1))) return rc;
-  FEA_HIP_CHECK(c, hipEventRecord(e0, c->stream));
-  for (int k = 0; k < iters; ++k) if ((rc = cgcg ? enq_cgcg_iteration(R, T, warmup + k, 1) : enq_cg_iteration(R, T, warmup + k, 1))) return rc;
-  FEA_HIP_CHECK(c, hipEventRecord(e1, c->stream));
-  FEA_HIP_CHECK(c, hipEventSynchronize(e1));
-  float ms = 0;
-  FEA_HIP_CHECK(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  if ((rc = time_enqueued(c, warmup, iters, avg_ms, [&](int k) { return cgcg ? enq_cgcg_iteration(R, T, k, 1) : enq_cg_iteration(R, T, k, 1); })))
+    return rc;
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d_flag, 0, sizeof(int), c->stream));
-  *avg_ms = iters > 0 ? (double)ms / iters : 0.0;
   return FEAHIP_OK;
 }
 

@@ -11,6 +11,7 @@
 // (enq_cg_start / enq_cg_iteration); all reductions are two-stage with a fixed grid and a fixed order, no atomics.
 // The single-column kernels of kernels_solve.hip are not touched.
 #include "feahip_internal.h"
+#include "reduce_device.h"
 #include <cmath>
 
 #ifndef FEA_SPMV_STAGED
@@ -23,42 +24,6 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 int amg_prepare(feahip_ctx *c);
 double *amg_apply(feahip_ctx *c, const double *r);
 
-// ------------------------------------------------------------------------
-// device helpers (the ones of kernels_solve.hip, per translation unit)
-// ------------------------------------------------------------------------
-static __device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-static __device__ __forceinline__ double wave_sum_all(double v)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-static __device__ __forceinline__ double block_sum(double v, double *scratch /*[4]*/)
-{
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0;
-  if (threadIdx.x == 0) r = scratch[0] + scratch[1] + scratch[2] + scratch[3];
-  __syncthreads();
-  return r;
-}
-static __device__ __forceinline__ double reduce_partials(const double *part, int n, double *scratch /*[5]*/)
-{
-  double v = 0;
-  for (int i = threadIdx.x; i < n; i += 256) v += part[i];
-  v = block_sum(v, scratch);
-  if (threadIdx.x == 0) scratch[4] = v;
-  __syncthreads();
-  v = scratch[4];
-  __syncthreads();
-  return v;
-}
 // the pair, or the component of the live column alone: a frozen column's half of the 16 bytes is not written
 static __device__ __forceinline__ void store_live(v2d *p, v2d v, bool l0, bool l1)
 {
@@ -534,17 +499,11 @@ int solve_pcg2(feahip_ctx *c, int type, double tol, int max_iter, int *iters, do
   if ((rc = launch_deinterleave(c, c->d2_u, c->d_u, c->d_u2))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d2_flag, 0, sizeof(int) * 2, c->stream));
-  for (int col = 0; col < 2; ++col) {
-    const double *s = sc + 8 * col;
-    int done = it;
-    if (flag[col] == -1000000000) done = 0;
-    else if (flag[col] > 0) done = flag[col];
-    else if (flag[col] < 0) done = -flag[col];
-    if (iters) iters[col] = done;
-    if (resid) resid[col] = (s[2] > 0) ? sqrt(s[3] / s[2]) : sqrt(s[3]);
-  }
+  bool broke[2];
   for (int col = 0; col < 2; ++col)
-    if (flag[col] < 0 && flag[col] != -1000000000) {
+    broke[col] = pcg_outcome(flag[col], it, sc + 8 * col, iters ? iters + col : nullptr, resid ? resid + col : nullptr);
+  for (int col = 0; col < 2; ++col)
+    if (broke[col]) {
       c->err = "CG breakdown (NaN or zero curvature) in column " + std::to_string(col) + " at iteration " + std::to_string(-flag[col]);
       return FEAHIP_ENOTCONVERGED;
     }
@@ -560,18 +519,7 @@ int time_pcg2_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms)
   if ((rc = enq_cg2_start(c, 1, 0.0))) return rc;
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d2_flag, 0, sizeof(int) * 2, c->stream));
   const bool live[2] = {true, true};
-  hipEvent_t e0, e1;
-  FEA_HIP_CHECK(c, hipEventCreate(&e0));
-  FEA_HIP_CHECK(c, hipEventCreate(&e1));
-  for (int k = 0; k < warmup; ++k) if ((rc = enq_cg2_iteration(c, k, 1, live))) return rc;
-  FEA_HIP_CHECK(c, hipEventRecord(e0, c->stream));
-  for (int k = 0; k < iters; ++k) if ((rc = enq_cg2_iteration(c, warmup + k, 1, live))) return rc;
-  FEA_HIP_CHECK(c, hipEventRecord(e1, c->stream));
-  FEA_HIP_CHECK(c, hipEventSynchronize(e1));
-  float ms = 0;
-  FEA_HIP_CHECK(c, hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  if ((rc = time_enqueued(c, warmup, iters, avg_ms, [&](int k) { return enq_cg2_iteration(c, k, 1, live); }))) return rc;
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d2_flag, 0, sizeof(int) * 2, c->stream));
-  *avg_ms = iters > 0 ? (double)ms / iters : 0.0;
   return FEAHIP_OK;
 }

@@ -276,6 +276,20 @@ def test_sharded_trajectory_is_the_unsharded_one(form):
     g.close()
 
 
+def test_a_collective_error_on_another_rank_reaches_the_callers_handle():
+    """feahip_consistent_acceleration is made on ONE handle and drives the group: when a rank other than that handle's
+    refuses (here rank 1 has no mass), the code is that rank's and the handle the caller holds names the reason."""
+    g = feahip.FeaGroup(mesh.bar_deck(dims=(2, 2, 2)), 2)
+    r0 = g.ranks[0]
+    r0.set_mass(1.5)                                                   # rank 0 only
+    rc = r0._lib.feahip_consistent_acceleration(r0._ctx, feahip.PCG_ILU, 1e-14, 100)
+    msg = r0._lib.feahip_last_error(r0._ctx).decode()
+    print("rc", rc, "last_error of the caller's handle:", repr(msg))
+    assert rc == feahip.ESTATE
+    assert msg and "feahip_consistent_acceleration" in msg
+    g.close()
+
+
 def one_newton_iteration(s):
     s.update_nodes_with_bc(1.0)
     s.create_stiffness_and_residual()
