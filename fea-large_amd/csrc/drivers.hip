@@ -200,6 +200,15 @@ int dist_kinetic_energy(std::vector<feahip_ctx *> &R, double *e)
   return dist_read_scalars(R, RankReduce::sum, 1, e);
 }
 
+// sum_e W_e over all ranks: every rank sums the shares W_e / npe of the nodes it owns, so that an element a rank holds as
+// a ghost is counted once
+int dist_strain_energy(std::vector<feahip_ctx *> &R, double *W)
+{
+  int rc;
+  FOR_RANKS(c) { if ((rc = launch_results(c, -1, c->d_scal + 8))) return rc; }
+  return dist_read_scalars(R, RankReduce::sum, 1, W);
+}
+
 int dist_explicit(std::vector<feahip_ctx *> &R, int n_steps, double dt_fixed, double safety, int restep, double dlambda,
                   double *dt_log, int dt_log_cap, int *steps_done)
 {

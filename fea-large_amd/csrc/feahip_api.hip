@@ -467,6 +467,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->generic.release(); c->visits.release(); c->quad.release(); c->gather.release(); c->gather10.release();
   c->surf.release();
   c->mass.release();
+  c->results.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -1142,6 +1143,75 @@ extern "C" int feahip_group_solve_explicit(feahip_ctx **ctxs, int n, int n_steps
   return surface_error(R[0], R, rc);
 }
 
+// ---- results: nodal stress, strain energy, reactions (kernels_results.hip) ------------------------------------------
+static int results_material(feahip_ctx *c, int material, const char *who)
+{
+  if (material == -1) return FEAHIP_OK;
+  if (material < -1 || material >= c->n_materials) {
+    c->err = std::string(who) + ": material " + std::to_string(material) +
+             (c->n_materials ? " outside the table of " + std::to_string(c->n_materials) : " on a context without a material table");
+    return FEAHIP_EINVAL;
+  }
+  return FEAHIP_OK;
+}
+
+// a node scalar [N] from the library's ids to the caller's
+static int get_node_scalar(feahip_ctx *c, const double *d, double *h)
+{
+  std::vector<double> tmp((size_t)c->N);
+  const int rc = get_vec(c, d, tmp.data(), tmp.size());
+  if (rc) return rc;
+  for (int a = 0; a < c->N; ++a) h[a] = tmp[(size_t)lib_id(c, a)];
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_nodal_stresses(feahip_ctx *c, int material, double *sig6, double *von_mises, double *weight)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = results_material(c, material, "feahip_get_nodal_stresses"))) return rc;
+  if ((rc = launch_results(c, material, nullptr))) return rc;
+  if (sig6) {
+    std::vector<double> tmp((size_t)c->N * 6);
+    if ((rc = get_vec(c, c->results.d_sig6, tmp.data(), tmp.size()))) return rc;
+    for (int a = 0; a < c->N; ++a)
+      for (int j = 0; j < 6; ++j) sig6[(size_t)a * 6 + j] = tmp[(size_t)lib_id(c, a) * 6 + j];
+  }
+  if (von_mises && (rc = get_node_scalar(c, c->results.d_vm, von_mises))) return rc;
+  if (weight && (rc = get_node_scalar(c, c->results.d_wt, weight))) return rc;
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_nodal_energy(feahip_ctx *c, double *w_node)
+{
+  CTX_GUARD_NOK(c);
+  if (!w_node) return FEAHIP_EINVAL;
+  int rc;
+  if ((rc = launch_results(c, -1, nullptr))) return rc;
+  return get_node_scalar(c, c->results.d_wn, w_node);
+}
+
+extern "C" int feahip_strain_energy(feahip_ctx *c, double *W)
+{
+  CTX_GUARD_NOK(c);
+  if (!W) return FEAHIP_EINVAL;
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  return surface_error(c, R, dist_strain_energy(R, W));
+}
+
+extern "C" int feahip_get_reactions(feahip_ctx *c, double *r)
+{
+  CTX_GUARD(c);
+  if (!r) return FEAHIP_EINVAL;
+  double *d = nullptr;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * 2 * (size_t)c->ndof));
+  int rc = launch_reactions(c, d, d + c->ndof);
+  if (rc == FEAHIP_OK) rc = get_node_vec(c, d, r);
+  (void)hipFree(d);
+  return rc;
+}
+
 // ---- two-column solve (kernels_solve2.hip) ---------------------------------
 static int solve2_ready(feahip_ctx *c, const char *who)
 {
@@ -1488,6 +1558,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     const int rk = lump_ensure(c, "time_kernel");
     if (rk) return rk;
   }
+  if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   return time_enqueued(c, warmup, iters, avg_ms, [&](int) -> int {
     switch (what) {
@@ -1501,6 +1572,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 9: return launch_mass_residual(c, 1.0);
     case 10: { const int rk = launch_explicit_kick(c, 1.0); return rk ? rk : launch_explicit_finish(c, 1.0); }
     case 11: return launch_gershgorin(c);
+    case 12: return launch_results(c, -1, c->d_scal + 8);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

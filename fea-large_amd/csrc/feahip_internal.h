@@ -415,6 +415,15 @@ struct MassState {
   void release() { dev_free({d_m_base, d_vel, d_acc, d_xt, d_vt, d_body, d_ml, d_ke_part}); *this = MassState(); }
 };
 
+// result recovery (kernels_results.hip): nothing of it exists until a results entry is called
+struct ResultState {
+  double *d_rec = nullptr;             // [E][8] element records: sum vol sigma (6), sum vol, W_e
+  double *d_sig6 = nullptr;            // [N][6] nodal stress xx yy zz xy yz xz of the owned rows, zero elsewhere (library ids)
+  double *d_vm = nullptr, *d_wt = nullptr, *d_wn = nullptr;   // [N] von Mises, weight, nodal energy share
+  double *d_part = nullptr;            // [FEA_RED_BLOCKS] per-workgroup partial sums of the nodal energy shares
+  void release() { dev_free({d_rec, d_sig6, d_vm, d_wt, d_wn, d_part}); *this = ResultState(); }
+};
+
 struct feahip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -553,6 +562,7 @@ struct feahip_ctx {
   int *d2_flag = nullptr;      // [2]
   // consistent mass (kernels_mass.hip): nothing of it exists, and nothing below is launched, until feahip_set_mass
   MassState mass;
+  ResultState results;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -633,6 +643,11 @@ int dist_explicit(std::vector<feahip_ctx *> &R, int n_steps, double dt, double s
                   double *dt_log, int dt_log_cap, int *steps_done);
 int dist_stable_step(std::vector<feahip_ctx *> &R, double *dt_crit);
 int dist_kinetic_energy(std::vector<feahip_ctx *> &R, double *e);
+// kernels_results.hip -- nodal stress, strain energy and reactions
+int launch_results(feahip_ctx *c, int material, double *d_energy);   // both passes; *d_energy (may be null) = sum of the owned nodal energy shares
+int launch_reactions(feahip_ctx *c, double *d_r, double *d_save);    // d_r = -residual on the owned prescribed dofs; d_f saved in d_save and restored
+// drivers.hip -- the strain energy over one or more ranks
+int dist_strain_energy(std::vector<feahip_ctx *> &R, double *W);
 // drivers.hip -- Crisfield's cylindrical arc length on the surface loads (one unsharded context)
 int arclength_solve(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
                     int solver_type, double solver_tolerance, int solver_max_iter, double *lambda_log, double *tol_log,

@@ -138,6 +138,10 @@ ABI = {
     "feahip_solve_explicit": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _dp, C.c_int, _ip],
     "feahip_group_solve_explicit": [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, _dp,
                                     C.c_int, _ip],
+    "feahip_get_nodal_stresses": [C.c_void_p, C.c_int, _dp, _dp, _dp],
+    "feahip_strain_energy": [C.c_void_p, _dp],
+    "feahip_get_nodal_energy": [C.c_void_p, _dp],
+    "feahip_get_reactions": [C.c_void_p, _dp],
 }
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
@@ -189,23 +193,29 @@ class FeaDeck(C.Structure):
         ("dynamics_gamma", C.c_double), ("dynamics_dlambda", C.c_double), ("density", C.c_double),
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
+        ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
     ]
 
 
 class StepSnapshot(C.Structure):
     """struct fea_step_snapshot of host/fea_host.h."""
-    _fields_ = [("nodes", _dp), ("stress0", _dp)]
+    _fields_ = [("nodes", _dp), ("stress0", _dp), ("nodal_stress", _dp), ("von_mises", _dp)]
 
 
-def export_gmsh(path, deck, nodes_steps, stress0_steps):
-    """fea_export_gmsh: nodes_steps[k] is [N][3], stress0_steps[k] is [E][3][3] after load step k+1."""
+def export_gmsh(path, deck, nodes_steps, stress0_steps, nodal_stress_steps=None, von_mises_steps=None):
+    """fea_export_gmsh: nodes_steps[k] is [N][3], stress0_steps[k] is [E][3][3] after load step k+1; with
+    nodal_stress_steps[k] ([N][6]) and von_mises_steps[k] ([N]) every step also gets its two nodal-stress sections."""
     h = load_host_library()
     n = len(nodes_steps)
     keep = [(np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64))
             for a, b in zip(nodes_steps, stress0_steps)]
+    nodal = [(np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64))
+             for a, b in zip(nodal_stress_steps or [], von_mises_steps or [])]
     arr = (StepSnapshot * max(n, 1))()
     for k, (a, b) in enumerate(keep):
         arr[k].nodes, arr[k].stress0 = _d(a), _d(b)
+    for k, (a, b) in enumerate(nodal[:n]):
+        arr[k].nodal_stress, arr[k].von_mises = _d(a), _d(b)
     fd = deck.to_struct()
     if h.fea_export_gmsh(os.fsencode(path), C.byref(fd), arr, n) != 0:
         raise FeaHipError(f"could not write {path}")
@@ -317,6 +327,11 @@ class Deck:
         if len(self.element_material) != (len(self.elements) if len(self.materials) else 0):
             raise ValueError("materials and element_material come together, one id per element")
         _take_dynamics(self, kw)
+        # (results :nodal-stress t :energy t :reactions t): what feasolver_hip adds to its .msh file and its log
+        res = kw.get("results") or {}
+        if set(res) - {"nodal_stress", "energy", "reactions"}:
+            raise ValueError("results: nodal_stress, energy, reactions")
+        self.results = {k: bool(res.get(k, False)) for k in ("nodal_stress", "energy", "reactions")}
 
     @staticmethod
     def load(path):
@@ -350,7 +365,9 @@ class Deck:
                 dynamics=dict(steps=fd.dynamics_steps, dt=fd.dynamics_dt, beta=fd.dynamics_beta, gamma=fd.dynamics_gamma,
                               dlambda=fd.dynamics_dlambda,
                               **(dict(scheme="explicit", safety=fd.dynamics_safety, restep=fd.dynamics_restep)
-                                 if fd.dynamics_explicit else {})) if fd.has_dynamics else None)
+                                 if fd.dynamics_explicit else {})) if fd.has_dynamics else None,
+                results=dict(nodal_stress=bool(fd.results_nodal_stress), energy=bool(fd.results_energy),
+                             reactions=bool(fd.results_reactions)))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -393,6 +410,9 @@ class Deck:
                 fd.has_body_force = 1
                 for k in range(3):
                     fd.body_force[k] = float(self.body_force[k])
+        res = getattr(self, "results", None) or {}
+        fd.results_nodal_stress, fd.results_energy = int(res.get("nodal_stress", False)), int(res.get("energy", False))
+        fd.results_reactions = int(res.get("reactions", False))
         return fd
 
     def save(self, path):
@@ -691,6 +711,32 @@ class FeaSolver:
         e = C.c_double(0)
         self._chk(self._lib.feahip_kinetic_energy(self._ctx, C.byref(e)))
         return e.value
+
+    # ---- results ------------------------------------------------------------
+    def nodal_stresses(self, material=-1):
+        """feahip_get_nodal_stresses: (sig6[N][6] as xx yy zz xy yz xz, von_mises[N], weight[N]), the volume-weighted
+        average over all elements (material = -1) or over those of one material; owned rows, zero elsewhere."""
+        sig6, vm, wt = np.zeros((self.N, 6)), np.zeros(self.N), np.zeros(self.N)
+        self._chk(self._lib.feahip_get_nodal_stresses(self._ctx, int(material), _d(sig6), _d(vm), _d(wt)))
+        return sig6, vm, wt
+
+    def strain_energy(self):
+        """feahip_strain_energy (collective on a group)."""
+        w = C.c_double(0)
+        self._chk(self._lib.feahip_strain_energy(self._ctx, C.byref(w)))
+        return w.value
+
+    def nodal_energy(self):
+        """feahip_get_nodal_energy: w_node[N], the shares W_e / npe of the owned rows."""
+        wn = np.zeros(self.N)
+        self._chk(self._lib.feahip_get_nodal_energy(self._ctx, _d(wn)))
+        return wn
+
+    def reactions(self):
+        """feahip_get_reactions: r[3N], minus the unmasked residual on the prescribed dofs, zero elsewhere."""
+        r = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_get_reactions(self._ctx, _d(r)))
+        return r
 
     def solve_explicit(self, n_steps=None, dt=None, safety=None, restep=None, dlambda=None, check=True):
         """feahip_solve_explicit; arguments left out come from the deck (its `dynamics`).  Returns (steps done, dt_log
@@ -1430,6 +1476,16 @@ class FeaGroup:
     def kinetic_energy(self):
         return self.ranks[0].kinetic_energy()
 
+    def strain_energy(self):
+        return self.ranks[0].strain_energy()                    # one call drives the group
+
+    def _stitch_rows(self, parts):
+        """Owned rows of per-node arrays ([N] or [N][k]), stitched together."""
+        out = np.zeros((self.n_global,) + parts[0].shape[1:])
+        for r, nd, p in zip(self.ranks, self.nodes, parts):
+            out[nd] = p[:r.n_own] if self.rank_contexts else p[nd]
+        return out
+
     def lumped_mass(self):
         """The owned rows of every rank's lumped mass, stitched together ([N] of the whole mesh)."""
         out = np.zeros(self.n_global)
@@ -1447,6 +1503,10 @@ class FeaGroup:
     def gather(self, name):
         """Owned rows of a per-node ([N][3]) or per-dof ([3N]) getter, stitched together."""
         parts = self.each(name)
+        if name == "nodal_stresses":                            # (sig6, von_mises, weight): one row per node each
+            return tuple(self._stitch_rows([p[k] for p in parts]) for k in range(3))
+        if name == "nodal_energy":
+            return self._stitch_rows(parts)
         if self.rank_contexts:                                  # local arrays: owned rows are the first n_own
             first = parts[0]
             out = np.zeros((self.n_global, 3)) if first.ndim == 2 else np.zeros(3 * self.n_global)

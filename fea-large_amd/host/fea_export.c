@@ -23,18 +23,22 @@ void fea_snapshots_free(fea_step_snapshot *steps, int n)
 {
   int i;
   if (!steps) return;
-  for (i = 0; i < n; ++i) { free(steps[i].nodes); free(steps[i].stress0); steps[i].nodes = steps[i].stress0 = NULL; }
+  for (i = 0; i < n; ++i) {
+    free(steps[i].nodes); free(steps[i].stress0); free(steps[i].nodal_stress); free(steps[i].von_mises);
+    steps[i].nodes = steps[i].stress0 = steps[i].nodal_stress = steps[i].von_mises = NULL;
+  }
 }
 
 /* what solver_load_step_init keeps of a finished increment (fea_solver.c:605-636): the nodes and, for the
  * export, the stress of Gauss point 0 of every element (:1480) */
-struct snap_sink { fea_step_snapshot *steps; int cap; double *S; };
+struct snap_sink { fea_step_snapshot *steps; int cap; double *S; FILE *log; int explicit_run; };
 
 static int keep_snapshot(const fea_deck *d, feahip_ctx *ctx, int step, void *user)
 {
   struct snap_sink *k = (struct snap_sink *)user;
   const int G = d->gauss_nodes_count;
   int e, rc;
+  if ((rc = fea_log_results(d, ctx, k->log, k->explicit_run))) return rc;
   if (!k->steps || step >= k->cap) return 0;
   k->steps[step].nodes = (double *)malloc(sizeof(double) * 3 * (size_t)d->nodes_count);
   k->steps[step].stress0 = (double *)malloc(sizeof(double) * 9 * (size_t)d->elements_count);
@@ -44,6 +48,12 @@ static int keep_snapshot(const fea_deck *d, feahip_ctx *ctx, int step, void *use
   if ((rc = feahip_get_stresses(ctx, k->S))) return rc;
   for (e = 0; e < d->elements_count; ++e)
     memcpy(k->steps[step].stress0 + (size_t)e * 9, k->S + (size_t)e * G * 9, sizeof(double) * 9);
+  if (d->results_nodal_stress) {
+    k->steps[step].nodal_stress = (double *)malloc(sizeof(double) * 6 * (size_t)d->nodes_count);
+    k->steps[step].von_mises = (double *)malloc(sizeof(double) * (size_t)d->nodes_count);
+    if (!k->steps[step].nodal_stress || !k->steps[step].von_mises) return FEAHIP_ENOMEM;
+    if ((rc = feahip_get_nodal_stresses(ctx, -1, k->steps[step].nodal_stress, k->steps[step].von_mises, NULL))) return rc;
+  }
   return 0;
 }
 
@@ -51,7 +61,7 @@ int fea_solve_with_snapshots(const fea_deck *d, feahip_ctx *ctx, void *logp, fea
 {
   struct snap_sink k;
   int done;
-  k.steps = steps; k.cap = cap; k.S = NULL;
+  k.steps = steps; k.cap = cap; k.S = NULL; k.log = NULL; k.explicit_run = 0;   /* (fea_solve_steps writes the result lines) */
   done = fea_solve_steps(d, ctx, logp, keep_snapshot, &k);     /* the one Newton loop of the host side (fea_solve.c) */
   free(k.S);
   return done;
@@ -76,7 +86,7 @@ int fea_solve_arclength_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *
   free(lam); free(its);
   if (rc == FEAHIP_ENOTCONVERGED && log) fprintf(log, "Unable to finish arc-length step %d, exit\n", done + 1);
   if (rc && rc != FEAHIP_ENOTCONVERGED) return rc;
-  k.steps = last; k.cap = 1; k.S = NULL;
+  k.steps = last; k.cap = 1; k.S = NULL; k.log = log; k.explicit_run = 0;
   rc = keep_snapshot(d, ctx, 0, &k);
   free(k.S);
   return rc ? rc : done;
@@ -91,35 +101,62 @@ int fea_solve_dynamic_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *lo
   const int n = d->dynamics_steps;
   int *its = (int *)calloc((size_t)(n > 0 ? n : 1), sizeof *its);
   int done = 0, rc, i;
+  const int per_step = d->results_energy || d->results_reactions;
   if (!its) return FEAHIP_ENOMEM;
   if (d->dynamics_explicit) {                         /* :scheme explicit: central differences on the lumped mass */
     double *dts = (double *)calloc((size_t)(n > 0 ? n : 1), sizeof *dts), t = 0;
     free(its);
     if (!dts) return FEAHIP_ENOMEM;
-    rc = feahip_solve_explicit(ctx, n, d->dynamics_dt, d->dynamics_safety, d->dynamics_restep, d->dynamics_dlambda, dts, n, &done);
-    if (log)
-      for (i = 0; i < done; ++i) {
+    k.steps = NULL; k.cap = 0; k.S = NULL; k.log = log; k.explicit_run = 1;
+    if (per_step && d->dynamics_dt > 0) {             /* a fixed step: one call per step, the result lines after each */
+      for (rc = 0, i = 0; i < n && !rc; ++i) {
+        int one = 0;
+        rc = feahip_solve_explicit(ctx, 1, d->dynamics_dt, d->dynamics_safety, d->dynamics_restep, d->dynamics_dlambda, dts + i, 1, &one);
+        done += one;
+        if (!one) break;
         t += dts[i];
-        fprintf(log, "Explicit step %d finished: time %.17g, dt %.17g\n", i + 1, t, dts[i]);
+        if (log) fprintf(log, "Explicit step %d finished: time %.17g, dt %.17g\n", i + 1, t, dts[i]);
+        if (!rc && i + 1 < n) rc = fea_log_results(d, ctx, log, 1);   /* (the last step's lines come with its snapshot) */
       }
+    } else {
+      rc = feahip_solve_explicit(ctx, n, d->dynamics_dt, d->dynamics_safety, d->dynamics_restep, d->dynamics_dlambda, dts, n, &done);
+      if (log)
+        for (i = 0; i < done; ++i) {
+          t += dts[i];
+          fprintf(log, "Explicit step %d finished: time %.17g, dt %.17g\n", i + 1, t, dts[i]);
+        }
+    }
     free(dts);
     if (rc == FEAHIP_ENOTCONVERGED && log) fprintf(log, "Inverted elements after explicit step %d, exit\n", done);
     if (rc && rc != FEAHIP_ENOTCONVERGED) return rc;
-    k.steps = last; k.cap = 1; k.S = NULL;
+    k.steps = last; k.cap = 1;
     rc = keep_snapshot(d, ctx, 0, &k);
     free(k.S);
     return rc ? rc : done;
   }
-  rc = feahip_solve_dynamic(ctx, n, d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda,
-                            d->max_newton_count, d->desired_tolerance, d->solver_type, d->solver_tolerance,
-                            d->solver_max_iter, NULL, 0, its, &done);
-  if (log)
-    for (i = 0; i < done; ++i)
-      fprintf(log, "Dynamic step %d finished: time %.17g, %d iterations\n", i + 1, (i + 1) * d->dynamics_dt, its[i]);
+  if (per_step) {                                     /* one call per step, the result lines after each */
+    for (rc = 0, i = 0; i < n && !rc; ++i) {
+      int one = 0;
+      rc = feahip_solve_dynamic(ctx, 1, d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda,
+                                d->max_newton_count, d->desired_tolerance, d->solver_type, d->solver_tolerance,
+                                d->solver_max_iter, NULL, 0, its + i, &one);
+      if (rc || !one) break;
+      done += one;
+      if (log) fprintf(log, "Dynamic step %d finished: time %.17g, %d iterations\n", i + 1, (i + 1) * d->dynamics_dt, its[i]);
+      if (i + 1 < n) rc = fea_log_results(d, ctx, log, 0);            /* (the last step's lines come with its snapshot) */
+    }
+  } else {
+    rc = feahip_solve_dynamic(ctx, n, d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda,
+                              d->max_newton_count, d->desired_tolerance, d->solver_type, d->solver_tolerance,
+                              d->solver_max_iter, NULL, 0, its, &done);
+    if (log)
+      for (i = 0; i < done; ++i)
+        fprintf(log, "Dynamic step %d finished: time %.17g, %d iterations\n", i + 1, (i + 1) * d->dynamics_dt, its[i]);
+  }
   free(its);
   if (rc) return rc;
   if (done < n && log) fprintf(log, "Unable to finish dynamic step %d in %d Newton iterations,exit\n", done + 1, d->max_newton_count);
-  k.steps = last; k.cap = 1; k.S = NULL;
+  k.steps = last; k.cap = 1; k.S = NULL; k.log = log; k.explicit_run = 0;
   rc = keep_snapshot(d, ctx, 0, &k);
   free(k.S);
   return rc ? rc : done;
@@ -172,6 +209,20 @@ int fea_export_gmsh(const char *filename, const fea_deck *d, const fea_step_snap
       fprintf(f, "\n");
     }
     fprintf(f, "$EndElementData\n");
+    if (load && steps[load - 1].nodal_stress && steps[load - 1].von_mises) {   /* (results :nodal-stress t) */
+      static const int at[9] = {0, 3, 5, 3, 1, 4, 5, 4, 2};                    /* xx xy xz / xy yy yz / xz yz zz */
+      const double *s6 = steps[load - 1].nodal_stress, *vm = steps[load - 1].von_mises;
+      fprintf(f, "$NodeData\n1\n\"Nodal stress\"\n1\n%f\n3\n%d\n9\n%d\n", load * 0.83333333, load, d->nodes_count);
+      for (i = 0; i < d->nodes_count; ++i) {
+        fprintf(f, "%d ", i + 1);
+        for (j = 0; j < 9; ++j) fprintf(f, "%f ", s6[(size_t)i * 6 + at[j]]);
+        fprintf(f, "\n");
+      }
+      fprintf(f, "$EndNodeData\n");
+      fprintf(f, "$NodeData\n1\n\"Von Mises\"\n1\n%f\n3\n%d\n1\n%d\n", load * 0.83333333, load, d->nodes_count);
+      for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %f\n", i + 1, vm[i]);
+      fprintf(f, "$EndNodeData\n");
+    }
   }
   fclose(f);
   return 0;

@@ -86,6 +86,11 @@ typedef struct fea_deck {
   int dynamics_explicit;
   double dynamics_safety;
   int dynamics_restep;
+  /* results, optional: (results :nodal-stress t :energy t :reactions t) inside (solution ...), each attribute t or nil
+   * (absent: nil).  :nodal-stress keeps the nodal stress with every snapshot and adds two $NodeData sections per step
+   * to the .msh file; :energy and :reactions add one log line each per finished step.  Written by fea_deck_save only
+   * when one of them is set; without the section the file and the log are what they were                        */
+  int results_nodal_stress, results_energy, results_reactions;
 } fea_deck;
 
 /* sexp_data_load (sexp_loader.c:275-327).  Returns 0, or -1 with a message
@@ -122,11 +127,19 @@ int fea_solve_steps(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */
 int fea_solve(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */,
               double *x_steps, int x_steps_cap);
 
+/* The log lines of (results :energy t) and (results :reactions t) for the state in force: "Strain energy W" (with
+ * explicit_run: "Strain energy W, kinetic energy T, total W + T") and "Reactions sum rx ry rz".  Nothing is written,
+ * and nothing computed, without the attributes or with a NULL log.                                              */
+int fea_log_results(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, int explicit_run);
+
 /* Per-load-step snapshot (load_step of the reference, fea_solver.h:212-224):
  * node coordinates and the stress of Gauss point 0 of every element.         */
 typedef struct fea_step_snapshot {
   double *nodes;      /* [nodes_count][3] */
   double *stress0;    /* [elements_count][9], stresses[e][0] */
+  /* (results :nodal-stress t) only, NULL otherwise: feahip_get_nodal_stresses of all elements */
+  double *nodal_stress;   /* [nodes_count][6] xx yy zz xy yz xz */
+  double *von_mises;      /* [nodes_count] */
 } fea_step_snapshot;
 
 /* fea_solve with snapshots for the exporter: steps[cap] are allocated by the
@@ -145,7 +158,12 @@ int fea_solve_arclength_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, voi
 /* The run of a deck with (dynamics :steps N ...), N > 0: feahip_solve_dynamic; one log line per completed step
  * ("Dynamic step k finished: time t, n iterations"; the explicit scheme: feahip_solve_explicit and
  * "Explicit step k finished: time t, dt h"); *last receives the final state.  Returns the completed steps
- * or a negative FEAHIP_E* code.                                               */
+ * or a negative FEAHIP_E* code.
+ * With (results :energy t) or (results :reactions t) the steps are made one call each (one call for all of them where
+ * the explicit scheme estimates its own step, :dt 0: the lines then follow the last step only) and every step is
+ * followed by "Strain energy W" -- on the explicit scheme "Strain energy W, kinetic energy T, total W + T" -- and
+ * "Reactions sum rx ry rz", the sum of feahip_get_reactions per axis.  The static and the arc-length runs write the
+ * same lines after every finished increment / at the end of the path.                                          */
 int fea_solve_dynamic_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void *log, fea_step_snapshot *last);
 
 /* solver_export_tetrahedra10_gmsh (fea_solver.c:1375-1488): Gmsh 2.0 ASCII,
@@ -154,7 +172,9 @@ int fea_solve_dynamic_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void 
  * "Stress tensor" (Gauss point 0) tagged load*0.83333333.  4-node elements
  * are written as Gmsh type 4.  A deck with a material table writes the
  * element's material as its first tag, the physical entity, numbered from 1
- * as everything in the file (material id + 1); other decks write 1.          */
+ * as everything in the file (material id + 1); other decks write 1.  Steps
+ * whose snapshot holds a nodal stress are followed by NodeData "Nodal stress"
+ * (9 components, the symmetric tensor in full) and NodeData "Von Mises".     */
 int fea_export_gmsh(const char *filename, const fea_deck *deck,
                     const fea_step_snapshot *steps, int nsteps);
 

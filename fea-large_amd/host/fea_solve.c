@@ -69,6 +69,32 @@ int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char
   return rc;
 }
 
+/* the log lines of (results :energy t :reactions t) after a finished step */
+int fea_log_results(const fea_deck *d, feahip_ctx *ctx, void *logp, int explicit_run)
+{
+  FILE *log = (FILE *)logp;
+  int rc, i;
+  if (!log) return 0;
+  if (d->results_energy) {
+    double W = 0, T = 0;
+    if ((rc = feahip_strain_energy(ctx, &W))) return rc;
+    if (explicit_run) {
+      if ((rc = feahip_kinetic_energy(ctx, &T))) return rc;
+      fprintf(log, "Strain energy %.17g, kinetic energy %.17g, total %.17g\n", W, T, W + T);
+    } else
+      fprintf(log, "Strain energy %.17g\n", W);
+  }
+  if (d->results_reactions) {
+    double *r = (double *)malloc(sizeof(double) * 3 * (size_t)d->nodes_count), sum[3] = {0, 0, 0};
+    if (!r) return FEAHIP_ENOMEM;
+    if ((rc = feahip_get_reactions(ctx, r))) { free(r); return rc; }
+    for (i = 0; i < 3 * d->nodes_count; ++i) sum[i % 3] += r[i];
+    free(r);
+    fprintf(log, "Reactions sum %.17g %.17g %.17g\n", sum[0], sum[1], sum[2]);
+  }
+  return 0;
+}
+
 #define CALL(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
 /* solve() of fea_solver.c:163-236: THE load-increment / Newton loop of the host side (fea_solve and
@@ -106,6 +132,7 @@ int fea_solve_steps(const fea_deck *d, feahip_ctx *ctx, void *logp, fea_step_fn 
       if (log) fprintf(log, "Unable to finish load step in %d Newton iterations,exit\n", d->max_newton_count);
       break;
     }
+    CALL(fea_log_results(d, ctx, log, 0));                                   /* (results ...): nothing without the section */
     if (after_step) CALL(after_step(d, ctx, step, user));                    /* :233-235 */
   }
   return step;

@@ -10,7 +10,9 @@
  * state as its one step.  A deck with (dynamics :steps N ...), N > 0, takes N
  * Newmark steps (feahip_solve_dynamic), or with :scheme explicit N explicit
  * steps (feahip_solve_explicit), and likewise writes the final state.
- * Every other deck takes the reference's loop.
+ * Every other deck takes the reference's loop.  A deck with a (results ...)
+ * section gets the nodal stress in the file and the strain energy and the
+ * reaction sums in the log (fea_host.h).
  *
  * One option the reference does not have, after the deck name:
  *   --multigrid   PCG_ILU / CHOLESKY solves use the aggregation-multigrid

@@ -467,6 +467,17 @@ static int read_list(reader *r, fea_deck *d)
     if (need_num(r, a, na, "density", &d->density)) return -1;
     if (!(d->density > 0)) return fail(r, "dynamics :density must be positive");
     d->has_dynamics = 1;
+  } else if (ieq(head, "results")) {                          /* no counterpart in the reference */
+    static const char *key[3] = {"nodal-stress", "energy", "reactions"};
+    int *flag[3], i;
+    flag[0] = &d->results_nodal_stress; flag[1] = &d->results_energy; flag[2] = &d->results_reactions;
+    for (i = 0; i < 3; ++i) {
+      *flag[i] = 0;
+      if ((s = attr_get(a, na, key[i]))) {
+        if (ieq(s, "t") || ieq(s, "yes") || ieq(s, "true")) *flag[i] = 1;
+        else if (!(ieq(s, "nil") || ieq(s, "no") || ieq(s, "false"))) return fail(r, "results attributes take t or nil");
+      }
+    }
   } else if (ieq(head, "body-force")) {
     if (need_num(r, a, na, "x", &d->body_force[0])) return -1;
     if (need_num(r, a, na, "y", &d->body_force[1])) return -1;
@@ -592,6 +603,9 @@ int fea_deck_save(const char *path, const fea_deck *d)
   if (d->has_dynamics && d->dynamics_explicit)
     fprintf(f, " :scheme explicit :safety %.17g :restep %d", d->dynamics_safety, d->dynamics_restep);
   if (d->has_dynamics) fprintf(f, ")");
+  if (d->results_nodal_stress || d->results_energy || d->results_reactions)   /* written only when asked for */
+    fprintf(f, "\n   (results :nodal-stress %s :energy %s :reactions %s)", d->results_nodal_stress ? "t" : "nil",
+            d->results_energy ? "t" : "nil", d->results_reactions ? "t" : "nil");
   fprintf(f, ")\n");
   fprintf(f, " (input-data\n  (geometry\n   (nodes");
   for (i = 0; i < d->nodes_count; ++i)

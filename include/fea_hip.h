@@ -537,6 +537,60 @@ int feahip_solve_explicit(feahip_ctx *ctx, int n_steps, double dt, double safety
 int feahip_group_solve_explicit(feahip_ctx **ctxs, int n, int n_steps, double dt, double safety,
                                 int restep, double dlambda, double *dt_log, int dt_log_cap,
                                 int *steps_done);
+/* ---- results: nodal stress, strain energy, reactions -----------------------
+ * What a load case is read by, recovered on the device from the current nodes
+ * and the material table in force (nothing is cached between calls).  A context
+ * that never calls these allocates and launches nothing for them.  The
+ * reference has no counterpart: it exports the Gauss-point tensors only.
+ *
+ * feahip_get_nodal_stresses: the volume-weighted average of the Cauchy stress
+ * over the selected elements at node a,
+ *   sigma_a = (sum_{e at a} sum_g vol_eg sigma_eg) / (sum_{e at a} sum_g vol_eg),
+ * sigma_eg and vol_eg = w_g |det J_g| those of the current configuration on the
+ * stiffness rule, with the element's own (lambda, mu) under a material table.
+ * sig6[N][6] in the order xx, yy, zz, xy, yz, xz (the upper entries of the
+ * averaged tensor); von_mises[N] = sqrt(3/2 s:s) with s the deviator of
+ * sigma_a -- the von Mises stress of the average, not the average of the von
+ * Mises stresses; weight[N] = the denominator.  Any of the three may be NULL.
+ * All are indexed by the caller's node ids (local ids on a rank context).
+ * material = -1 selects all elements, material = m in [0, n_materials) those
+ * with that id: stress is discontinuous across a material interface and an
+ * average across one means nothing.  A node no selected element touches gets
+ * stress 0 and weight 0.  FEAHIP_EINVAL for an id outside the table, and for
+ * m >= 0 on a context without one.  On a sharded context the result is
+ * authoritative on the owned rows and zero elsewhere, like
+ * feahip_get_lumped_mass; no exchange is needed.
+ *
+ * feahip_strain_energy: W = sum_e sum_g w_g det J0_g Psi(F_eg) over the
+ * stiffness rule, det J0 = det J / det F, with the potential of the model's
+ * stress:  COMPRESSIBLE_NEOHOOKEAN  Psi = mu/2 (tr b - 3) - mu ln J
+ *                                         + lambda/2 (ln J)^2
+ *          A5                       Psi = lambda/2 (tr E)^2 + mu E:E,
+ *                                   E = (F'F - I)/2.
+ * Collective like feahip_kinetic_energy: an in-process group is driven from
+ * any of its members, the ranks of an RCCL run all make the call.  Every node
+ * of an element takes the share W_e / npe and a rank sums the shares of the
+ * nodes it owns, so a ghost element is counted once.  feahip_get_nodal_energy
+ * returns those shares, w_node[N] in the caller's ids, owned rows only.  No
+ * inversion check is made: with det F <= 0 the NaN propagates, and
+ * feahip_update_state still reports the inversions.
+ *
+ * feahip_get_reactions: r[3N] in the caller's dof order.  On every prescribed
+ * dof c, r_c = T_c(x) - lambda (F_surf(x) + F_body)_c, minus the unmasked
+ * residual at that dof (feahip_apply_prescribed_bc overwrites f there, so the
+ * residual is assembled again here); zero on every other dof; authoritative on
+ * the owned rows.  The inertia term of a dynamic context is NOT included: on a
+ * moving body this is the internal force minus the applied loads at the
+ * support, not the force the support exerts.  K, f, u, x, the cached F / sigma
+ * and the count feahip_update_state reports are left exactly as they were.
+ *
+ * All four return FEAHIP_EINVAL on a null context or a null required output. */
+int feahip_get_nodal_stresses(feahip_ctx *ctx, int material,
+                              double *sig6, double *von_mises, double *weight);
+int feahip_strain_energy(feahip_ctx *ctx, double *W);
+int feahip_get_nodal_energy(feahip_ctx *ctx, double *w_node);
+int feahip_get_reactions(feahip_ctx *ctx, double *r);
+
 /* z = M^-1 r on every rank of the group at once, with the preconditioner the
  * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
  * feahip_apply_preconditioner takes them (the caller's node ids of context k;
@@ -784,7 +838,8 @@ int feahip_sync(feahip_ctx *ctx);
  * term of the residual (k_mass_residual; 8 and 9 refused without a mass),
  * 10 the two pointwise kernels of an explicit step together (they advance v
  * and a by a step of dt = 1 on the f in force), 11 k_gershgorin on the K in
- * force (10 and 11 refused without a mass).                                 */
+ * force (10 and 11 refused without a mass), 12 the two result passes together
+ * (k_result_elements, k_result_nodes) with all outputs and material = -1.    */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
