@@ -468,6 +468,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->surf.release();
   c->mass.release();
   c->results.release();
+  c->modal.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -1212,6 +1213,73 @@ extern "C" int feahip_get_reactions(feahip_ctx *c, double *r)
   return rc;
 }
 
+// ---- modal analysis (kernels_modal.hip) --------------------------------------
+static int modal_ready(feahip_ctx *c, const char *who)
+{
+  int rc;
+  if ((rc = solve2_refused(c, who))) return rc;
+  return mass_ensure(c, who);
+}
+
+extern "C" int feahip_solve_modes(feahip_ctx *c, int n_modes, double tol, int max_iter, int warm, double *lambda,
+                                  double *resid, int *iters)
+{
+  CTX_GUARD(c);
+  if (iters) *iters = 0;
+  if (n_modes < 1 || n_modes > FEA_MODAL_COLS) { c->err = "solve_modes: n_modes must be in [1, 8]"; return FEAHIP_EINVAL; }
+  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_modes: tolerance must be positive"; return FEAHIP_EINVAL; }
+  if (max_iter < 0) { c->err = "solve_modes: max_iterations must not be negative"; return FEAHIP_EINVAL; }
+  if (!lambda) { c->err = "solve_modes: null lambda"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = modal_ready(c, "solve_modes"))) return rc;
+  return modal_solve(c, n_modes, tol, max_iter, warm, lambda, resid, iters);
+}
+
+extern "C" int feahip_get_modes(feahip_ctx *c, int first, int count, double *phi)
+{
+  CTX_GUARD_NOK(c);
+  if (!c->modal.have) { c->err = "get_modes: no modes held (feahip_solve_modes first)"; return FEAHIP_ESTATE; }
+  if (first < 0 || count < 0 || first + count > FEA_MODAL_COLS) { c->err = "get_modes: modes [first, first + count) outside the eight held"; return FEAHIP_EINVAL; }
+  if (!phi) { c->err = "get_modes: null phi"; return FEAHIP_EINVAL; }
+  std::vector<double> tmp((size_t)c->ndof);
+  for (int k = 0; k < count; ++k) {
+    const int rc = modal_get(c, first + k, tmp.data());
+    if (rc) return rc;
+    double *out = phi + (size_t)k * c->ndof;
+    for (int a = 0; a < c->N; ++a)
+      for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_spmm_km(feahip_ctx *c, const double *x8, double *y8, double *z8)
+{
+  CTX_GUARD(c);
+  if (!x8 || !y8 || !z8) return FEAHIP_EINVAL;
+  int rc;
+  if ((rc = modal_ready(c, "spmm_km"))) return rc;
+  if (!c->k_valid) { c->err = "spmm_km: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+  if ((rc = ensure_modal(c))) return rc;
+  c->modal.have = false;                                             // the block vectors are scratch here
+  const size_t n = (size_t)c->ndof, n8 = n * FEA_MODAL_COLS;
+  double *v = c->modal.d_v;                                          // X, W <- the host layout, KX, MX <- the products
+  for (int k = 0; k < FEA_MODAL_COLS; ++k)
+    if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, x8 + (size_t)k * n))) return rc;
+  if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, v, v + 3 * n8, v + 6 * n8))) return rc;
+  for (int which = 0; which < 2; ++which) {
+    if ((rc = launch_modal_pack(c, v + (which ? 6 : 3) * n8, v + n8, 1))) return rc;
+    for (int k = 0; k < FEA_MODAL_COLS; ++k)
+      if ((rc = get_node_vec(c, v + n8 + (size_t)k * n, (which ? z8 : y8) + (size_t)k * n))) return rc;
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const double *gram_k, double *theta, double *coef)
+{
+  if (!gram_m || !gram_k || !theta || !coef || (n_dirs != 8 && n_dirs != 16 && n_dirs != 24)) return FEAHIP_EINVAL;
+  return modal_ritz(n_dirs, gram_m, gram_k, FEA_MODAL_COLS, theta, coef);
+}
+
 // ---- two-column solve (kernels_solve2.hip) ---------------------------------
 static int solve2_ready(feahip_ctx *c, const char *who)
 {
@@ -1558,6 +1626,12 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     const int rk = lump_ensure(c, "time_kernel");
     if (rk) return rk;
   }
+  if (what >= 13 && what <= 15) {
+    const std::string who = "time_kernel(" + std::to_string(what) + ")";
+    if (!c->mass.set || c->mass.stale) { c->err = who + ": no mass on this context (feahip_set_mass)"; return FEAHIP_EINVAL; }
+    int rk;
+    if ((rk = solve2_refused(c, who.c_str())) || (rk = mass_ensure(c, "time_kernel")) || (rk = time_modal_prepare(c))) return rk;
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   return time_enqueued(c, warmup, iters, avg_ms, [&](int) -> int {
@@ -1573,6 +1647,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 10: { const int rk = launch_explicit_kick(c, 1.0); return rk ? rk : launch_explicit_finish(c, 1.0); }
     case 11: return launch_gershgorin(c);
     case 12: return launch_results(c, -1, c->d_scal + 8);
+    case 13: case 14: case 15: return time_modal_kernel(c, what);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

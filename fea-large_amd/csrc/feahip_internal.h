@@ -424,6 +424,20 @@ struct ResultState {
   void release() { dev_free({d_rec, d_sig6, d_vm, d_wt, d_wn, d_part}); *this = ResultState(); }
 };
 
+// modal analysis (kernels_modal.hip): nothing of it exists until feahip_solve_modes (or one of its hooks) is called.
+// Block vectors are [3N][FEA_MODAL_COLS] doubles, the columns of a dof contiguous.
+#define MODAL_SMALL (24 + 12 * 64 + 24 * 16 + FEA_MODAL_COLS)
+struct ModalState {
+  double *d_v = nullptr;               // [9][3N][8]: X W P, KX KW KP, MX MW MP
+  double *d_part = nullptr;            // [24 + 768][FEA_RED_BLOCKS] per-workgroup partial sums: column norms, Gram entries
+  double *d_small = nullptr;           // [MODAL_SMALL]: the reduced sums, then C[24][16] and theta[8] of the step
+  std::vector<double> h_C;             // host copy of C and theta while their upload is in flight
+  double theta[FEA_MODAL_COLS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int n_free = 0;                      // dofs that are not prescribed
+  bool have = false;                   // X holds the modes of a finished solve (feahip_get_modes, warm restarts)
+  void release() { dev_free({d_v, d_part, d_small}); *this = ModalState(); }
+};
+
 struct feahip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -563,6 +577,7 @@ struct feahip_ctx {
   // consistent mass (kernels_mass.hip): nothing of it exists, and nothing below is launched, until feahip_set_mass
   MassState mass;
   ResultState results;
+  ModalState modal;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -612,6 +627,15 @@ int launch_interleave(feahip_ctx *c, const double *a, const double *b, double *o
 int launch_deinterleave(feahip_ctx *c, const double *in2, double *a, double *b);
 int solve_pcg2(feahip_ctx *c, int type, double tol, int max_iter, int *iters, double *resid);   // d2_f -> d_u, d_u2
 int time_pcg2_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);
+// kernels_modal.hip -- the lowest eigenpairs of K phi = lambda M phi by a blocked LOBPCG on eight columns
+int ensure_modal(feahip_ctx *c);
+int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, double *lambda, double *resid, int *iters);
+int modal_get(feahip_ctx *c, int col, double *h_lib);                   // column col of X, [3N] in library ids
+int launch_spmm_km(feahip_ctx *c, const double *d_x8, double *d_y8, double *d_z8);   // Y = K X, Z = mask(M X)
+int launch_modal_pack(feahip_ctx *c, const double *d_in, double *d_out, int unpack); // [8][3N] <-> [3N][8]
+int time_modal_prepare(feahip_ctx *c);                                  // the nine vectors filled for feahip_time_kernel 13-15
+int time_modal_kernel(feahip_ctx *c, int what);
+int modal_ritz(int ns, const double *GM, const double *GK, int m, double *theta, double *C);   // host only
 // kernels_mass.hip -- consistent mass, body force and the vector kernels of the Newmark steps
 int mass_set(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights, const double *forms,
              const double *dforms);

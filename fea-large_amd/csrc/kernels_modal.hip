@@ -1,0 +1,656 @@
+// kernels_modal.hip -- the lowest eigenpairs of K(x) phi = lambda M phi on the free dofs (feahip_solve_modes): a blocked
+// LOBPCG whose basis is M-orthonormalised at every step, on block vectors of FEA_MODAL_COLS = 8 columns.
+//
+// Layout of a block vector: [3N][8] doubles, the eight columns of a scalar dof contiguous (64 bytes, half a cache
+// line) -- the layout of kernels_solve2.hip carried from two columns to eight.  Nine of them live in one allocation
+// (ModalState::d_v): S = [X, W, P], KS = [KX, KW, KP], MS = [MX, MW, MP].
+//
+// Per Rayleigh-Ritz step (modal_solve below):
+//   k_modal_residual  R = KX - MX diag(theta), the three column norms |r|^2, |Kx|^2, |Mx|^2 of every column, and (kind
+//                     0) W = D^-1 R with the 3x3 block-Jacobi inverse, zero on the prescribed dofs -- one pass
+//   k_spmm_km         KW = K W and MW = mask(M W) over ONE read of rowptr / colidx / K / m
+//   k_modal_gram      G_M = S' MS and G_K = S' KS (24 x 24 each, the block-upper triangle) from the nine arrays in one
+//                     pass, fixed grid, two-stage reduction in a fixed order, no atomics
+//   (one read-back: 24 norms + 768 Gram sums; the host scales, eigendecomposes G_M by cyclic Jacobi, drops directions
+//   below 1e-12 of the largest, forms the M-orthonormal basis, eigendecomposes the projected K and sends back two
+//   24 x 8 coefficient matrices: modal_ritz)
+//   k_modal_combine   [X, P] <- S [C_x, C_p] and the same for KS and MS, in place: only W is ever multiplied by the
+//                     matrices; every 20 steps and at return KX and MX are recomputed from X.
+// Nothing here exists, and nothing is launched, on a context that never calls feahip_solve_modes (or the hooks
+// feahip_spmm_km, feahip_time_kernel 13-15).
+#include "feahip_internal.h"
+#include "reduce_device.h"
+#include <cmath>
+
+#define RB FEA_RED_BLOCKS
+#define MC FEA_MODAL_COLS
+static_assert(MC == 8, "the kernels below are written for eight columns (four 16-byte pairs per dof)");
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+// multigrid preconditioner (amg.hip)
+int amg_prepare(feahip_ctx *c);
+double *amg_apply(feahip_ctx *c, const double *r);
+
+// partial sums in ModalState::d_part: sum e of workgroup b at [e RB + b]; e < 24: the column norms (s 8 + column,
+// s = 0 |r|^2, 1 |Kx|^2, 2 |Mx|^2), then 12 x 64 Gram sums: block pair q (M: 0..5, K: 6..11, the pairs (X,X) (X,W)
+// (X,P) (W,W) (W,P) (P,P)) entry (a, b) at 24 + q 64 + a 8 + b
+#define MODAL_NORMS 24
+#define MODAL_GRAM (12 * 64)
+#define MODAL_SUMS (MODAL_NORMS + MODAL_GRAM)
+
+// ------------------------------------------------------------------------
+// Y = K X, Z = mask(M X) for eight columns in one pass over the pattern.  k_spmv2's chunking: a wave owns a chunk of up
+// to 16 rows and 128 blocks, lane k takes the blocks k and k + 64, loads their nine K doubles, their m and the 3 x 8
+// x entries of their column ONCE into registers, and then walks the columns in four pairs: per pair it leaves 3 rows x
+// (K pair, M pair) = 96 bytes per block in LDS (12 KB per wave; all eight columns at once would take 48 KB per wave),
+// and lane (row, i) adds its row's partial products in block order into register accumulators that are stored once,
+// 64 bytes per dof and matrix.  A row longer than the tile has a chunk of its own: the lanes stride over its blocks,
+// a butterfly per sum, pair by pair.  mask: 1 = prescribed dof (Z is zero there).
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void k_spmm_km(int chunk0, int nchunks, const int *__restrict__ chunk, const int *__restrict__ rowptr,
+               const int *__restrict__ colidx, const double *__restrict__ K, const double *__restrict__ m,
+               const uint8_t *__restrict__ mask, const v2d *__restrict__ x, v2d *__restrict__ y, v2d *__restrict__ z)
+{
+  static_assert(FEA_CHUNK_ROWS * 3 <= 64, "one lane per (row, component) of a chunk");
+  static_assert(FEA_CHUNK_BLOCKS <= 128, "a lane takes the blocks k and k + 64 of a chunk");
+  __shared__ __attribute__((aligned(16))) double sP[FEA_WAVES_PER_WG][FEA_CHUNK_BLOCKS * 12];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  v2d *tP2 = reinterpret_cast<v2d *>(sP[wave]);      // block k, row i: K pair at [6 k + 2 i], M pair at [6 k + 2 i + 1]
+  for (int ch = chunk0 + blockIdx.x * FEA_WAVES_PER_WG + wave; ch < chunk0 + nchunks; ch += gridDim.x * FEA_WAVES_PER_WG) {
+    const int r0 = chunk[ch], r1 = chunk[ch + 1];
+    const int b0 = rowptr[r0], nb = rowptr[r1] - b0;
+    if (nb > FEA_CHUNK_BLOCKS) {
+      for (int p = 0; p < 4; ++p) {
+        v2d aK[3] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}}, aM[3] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+        for (int k = lane; k < nb; k += 64) {
+          const double *vp = K + (size_t)(b0 + k) * 9;
+          const double mm = m[b0 + k];
+          const size_t col = (size_t)colidx[b0 + k];
+          const v2d x0 = x[(col * 3) * 4 + p], x1 = x[(col * 3 + 1) * 4 + p], x2 = x[(col * 3 + 2) * 4 + p];
+          aK[0] += vp[0] * x0 + vp[1] * x1 + vp[2] * x2;
+          aK[1] += vp[3] * x0 + vp[4] * x1 + vp[5] * x2;
+          aK[2] += vp[6] * x0 + vp[7] * x1 + vp[8] * x2;
+          aM[0] += mm * x0; aM[1] += mm * x1; aM[2] += mm * x2;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          aK[i].x = wave_sum_all(aK[i].x); aK[i].y = wave_sum_all(aK[i].y);
+          aM[i].x = wave_sum_all(aM[i].x); aM[i].y = wave_sum_all(aM[i].y);
+        }
+        if (lane < 3) {
+          const size_t d = (size_t)r0 * 3 + lane;
+          const v2d zero = {0.0, 0.0};
+          y[d * 4 + p] = lane == 0 ? aK[0] : lane == 1 ? aK[1] : aK[2];
+          z[d * 4 + p] = mask[d] ? zero : (lane == 0 ? aM[0] : lane == 1 ? aM[1] : aM[2]);
+        }
+      }
+      continue;
+    }
+    double v[2][9], mm[2];
+    v2d xv[2][3][4];
+    int kb = 0, ke = 0;
+    if (lane < (r1 - r0) * 3) { kb = rowptr[r0 + lane / 3] - b0; ke = rowptr[r0 + lane / 3 + 1] - b0; }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      const int kk = k < nb ? b0 + k : b0;
+      const double *vp = K + (size_t)kk * 9;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) v[h][q] = vp[q];
+      mm[h] = m[kk];
+      const size_t col = (size_t)colidx[kk];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) xv[h][i][p] = x[(col * 3 + i) * 4 + p];
+    }
+    v2d accK[4], accM[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      accK[p] = v2d{0.0, 0.0}; accM[p] = v2d{0.0, 0.0};
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int k = lane + 64 * h;
+        if (k < nb) {
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            tP2[k * 6 + 2 * i] = v[h][3 * i] * xv[h][0][p] + v[h][3 * i + 1] * xv[h][1][p] + v[h][3 * i + 2] * xv[h][2][p];
+            tP2[k * 6 + 2 * i + 1] = mm[h] * xv[h][i][p];
+          }
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      if (lane < (r1 - r0) * 3) {
+        const int i = lane % 3;
+        for (int k = kb; k < ke; ++k) { accK[p] += tP2[k * 6 + 2 * i]; accM[p] += tP2[k * 6 + 2 * i + 1]; }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    }
+    if (lane < (r1 - r0) * 3) {
+      const size_t d = (size_t)r0 * 3 + lane;
+      const bool fixed = mask[d] != 0;
+      const v2d zero = {0.0, 0.0};
+#pragma unroll
+      for (int p = 0; p < 4; ++p) { y[d * 4 + p] = accK[p]; z[d * 4 + p] = fixed ? zero : accM[p]; }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------
+// G_M = S' MS and G_K = S' KS from the nine arrays in one pass.  base + j stride is array j of X W P KX KW KP MX MW MP;
+// np = the column blocks of S in use (1: X alone, 2: X and W, 3: all; the others count as zero and are not read).
+// A workgroup stages 32 dofs x 9 arrays in LDS with coalesced loads; wave w takes eight of them, lane (a, b) keeps the
+// twelve sums s_A[a] ms_B[b], s_A[a] ks_B[b] of the six block pairs A <= B.  The four waves' sums meet in LDS in wave
+// order, and the 768 sums of the workgroup go to part[(24 + e) RB + block].
+// ------------------------------------------------------------------------
+#define GRAM_DOFS 32
+__global__ __launch_bounds__(256)
+void k_modal_gram(int ndof, int np, const double *__restrict__ base, size_t stride, double *__restrict__ part)
+{
+  __shared__ double sh[4 * 12 * 64];                   // the tile [9][32][8] first (2304 doubles), the waves' sums after
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, a = lane >> 3, b = lane & 7;
+  double acc[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) acc[q] = 0.0;
+  for (int j = 0; j < 9; ++j) sh[j * 256 + threadIdx.x] = 0.0;        // arrays not in use stay zero
+  const int ntiles = (ndof + GRAM_DOFS - 1) / GRAM_DOFS;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t e = (size_t)tile * (GRAM_DOFS * 8) + threadIdx.x;      // element of a block vector
+    const bool in = e < (size_t)ndof * 8;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+      if (j % 3 < np) sh[j * 256 + threadIdx.x] = in ? base[(size_t)j * stride + e] : 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      const int row = (wave * 8 + d) * 8;
+      const double s0 = sh[row + a], s1 = sh[256 + row + a], s2 = sh[512 + row + a];
+      const double k0 = sh[768 + row + b], k1 = sh[1024 + row + b], k2 = sh[1280 + row + b];
+      const double m0 = sh[1536 + row + b], m1 = sh[1792 + row + b], m2 = sh[2048 + row + b];
+      acc[0] += s0 * m0; acc[1] += s0 * m1; acc[2] += s0 * m2; acc[3] += s1 * m1; acc[4] += s1 * m2; acc[5] += s2 * m2;
+      acc[6] += s0 * k0; acc[7] += s0 * k1; acc[8] += s0 * k2; acc[9] += s1 * k1; acc[10] += s1 * k2; acc[11] += s2 * k2;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 12; ++q) sh[(wave * 12 + q) * 64 + lane] = acc[q];
+  __syncthreads();
+  for (int e = threadIdx.x; e < MODAL_GRAM; e += 256)
+    part[(size_t)(MODAL_NORMS + e) * RB + blockIdx.x] = ((sh[e] + sh[768 + e]) + sh[1536 + e]) + sh[2304 + e];
+}
+
+// out[e] = the sum of part[e RB .. e RB + n): n = n_norms for e < 24, n_gram after; one workgroup per sum
+__global__ __launch_bounds__(256)
+void k_modal_reduce(int e0, int n_norms, int n_gram, const double *__restrict__ part, double *__restrict__ out)
+{
+  __shared__ double scratch[5];
+  const int e = e0 + blockIdx.x;
+  const double v = reduce_partials(part + (size_t)e * RB, e < MODAL_NORMS ? n_norms : n_gram, scratch);
+  if (threadIdx.x == 0) out[e] = v;
+}
+
+// ------------------------------------------------------------------------
+// [X, P] <- S C for the three triples (blockIdx.y = 0: S, 1: KS, 2: MS), in place: a lane owns one dof, reads its np x 8
+// entries, and writes the eight of X and (write_p) the eight of P.  C[24][16]: row k = direction k of S, columns 0-7
+// the coefficients of X_new, 8-15 those of P_new; it is read with uniform addresses (scalar loads), the same for
+// every lane.
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void k_modal_combine(int ndof, int np, int write_p, double *__restrict__ base, size_t stride, const double *__restrict__ C)
+{
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndof) return;
+  v2d *X = reinterpret_cast<v2d *>(base + (size_t)(3 * blockIdx.y) * stride) + (size_t)d * 4;
+  v2d *W = reinterpret_cast<v2d *>(base + (size_t)(3 * blockIdx.y + 1) * stride) + (size_t)d * 4;
+  v2d *P = reinterpret_cast<v2d *>(base + (size_t)(3 * blockIdx.y + 2) * stride) + (size_t)d * 4;
+  double xo[8], po[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) { xo[q] = 0.0; po[q] = 0.0; }
+  auto add = [&](const v2d *src, int row0) {
+    double s[8];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) { const v2d t = src[p]; s[2 * p] = t.x; s[2 * p + 1] = t.y; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        xo[q] += s[k] * C[(row0 + k) * 16 + q];
+        po[q] += s[k] * C[(row0 + k) * 16 + 8 + q];
+      }
+  };
+  add(X, 0);
+  if (np > 1) add(W, 8);
+  if (np > 2) add(P, 16);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) X[p] = v2d{xo[2 * p], xo[2 * p + 1]};
+  if (write_p) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) P[p] = v2d{po[2 * p], po[2 * p + 1]};
+  }
+}
+
+// ------------------------------------------------------------------------
+// R = KX - MX diag(theta) and the sums |r|^2, |Kx|^2, |Mx|^2 of every column; W = D^-1 R (minv: the 3x3 block-Jacobi
+// inverse, row i of node a at 9 a + 3 i) or, with minv null, W = R (the multigrid cycles follow); W is zero on the
+// prescribed dofs.  A lane owns (node, column): eight lanes share a node and read its D^-1 block together.
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void k_modal_residual(int N, const double *__restrict__ KX, const double *__restrict__ MX, const double *__restrict__ theta,
+                      const double *__restrict__ minv, const uint8_t *__restrict__ mask, double *__restrict__ W,
+                      double *__restrict__ part)
+{
+  __shared__ double sh[4][MODAL_NORMS];
+  const int col = threadIdx.x & 7, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double th = theta[col];
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int a = blockIdx.x * 32 + (threadIdx.x >> 3); a < N; a += gridDim.x * 32) {
+    double r[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const size_t e = ((size_t)a * 3 + j) * 8 + col;
+      const double kx = KX[e], mx = MX[e];
+      r[j] = kx - th * mx;
+      s[0] += r[j] * r[j]; s[1] += kx * kx; s[2] += mx * mx;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double w = r[i];
+      if (minv) { const double *mi = minv + (size_t)a * 9 + 3 * i; w = mi[0] * r[0] + mi[1] * r[1] + mi[2] * r[2]; }
+      W[((size_t)a * 3 + i) * 8 + col] = mask[(size_t)a * 3 + i] ? 0.0 : w;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int off = 32; off >= 8; off >>= 1) s[k] += __shfl_xor(s[k], off, 64);     // the lanes of one column
+    if (lane < 8) sh[wave][k * 8 + lane] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < MODAL_NORMS)
+    part[(size_t)threadIdx.x * RB + blockIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+
+// the start block: a fixed integer hash of (library dof index, column) mapped to [-1, 1), zero on the prescribed dofs
+__global__ __launch_bounds__(256)
+void k_modal_hash(size_t n8, const uint8_t *__restrict__ mask, double *__restrict__ X)
+{
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n8) return;
+  uint32_t h = (uint32_t)(e >> 3) * 0x9E3779B1u ^ ((uint32_t)(e & 7) + 1u) * 0x85EBCA77u;
+  h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+  X[e] = mask[e >> 3] ? 0.0 : (double)h * (1.0 / 2147483648.0) - 1.0;
+}
+
+// a column out of a block vector, and a vector (a multigrid cycle's result) into one, zero on the prescribed dofs
+__global__ void k_modal_extract(size_t n, const double *__restrict__ in8, int col, double *__restrict__ out)
+{
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) out[k] = in8[k * 8 + col];
+}
+__global__ void k_modal_insert(size_t n, const double *__restrict__ zv, const uint8_t *__restrict__ mask, int col, double *__restrict__ dst8)
+{
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) dst8[k * 8 + col] = mask[k] ? 0.0 : zv[k];
+}
+// eight plain vectors [8][n] (the hooks' host layout) into a block vector, or (unpack) back
+__global__ void k_modal_pack(size_t n, const double *__restrict__ in, double *__restrict__ out8, int unpack)
+{
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * 8) return;
+  const size_t k = e >> 3, col = e & 7;
+  if (unpack) out8[col * n + k] = in[e]; else out8[e] = in[col * n + k];
+}
+
+// ------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------
+static inline dim3 g256(size_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
+static int spmm_grid(const feahip_ctx *c)
+{
+  const int g = (c->nchunks_local + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
+  return g < RB ? (g > 0 ? g : 1) : RB;
+}
+static int gram_grid(const feahip_ctx *c)
+{
+  const int g = (c->ndof + GRAM_DOFS - 1) / GRAM_DOFS;
+  return g < RB ? (g > 0 ? g : 1) : RB;
+}
+static int resid_grid(const feahip_ctx *c)
+{
+  const int g = (c->N + 31) / 32;
+  return g < RB ? (g > 0 ? g : 1) : RB;
+}
+
+int ensure_modal(feahip_ctx *c)
+{
+  ModalState &S = c->modal;
+  if (S.d_v) return FEAHIP_OK;
+  const size_t n8 = (size_t)c->ndof * MC;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_v, sizeof(double) * 9 * n8));
+  FEA_HIP_CHECK(c, hipMemsetAsync(S.d_v, 0, sizeof(double) * 9 * n8, c->stream));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_part, sizeof(double) * (size_t)MODAL_SUMS * RB));
+  FEA_HIP_CHECK(c, hipMemsetAsync(S.d_part, 0, sizeof(double) * (size_t)MODAL_SUMS * RB, c->stream));
+  FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_small, sizeof(double) * MODAL_SMALL));
+  FEA_HIP_CHECK(c, hipMemsetAsync(S.d_small, 0, sizeof(double) * MODAL_SMALL, c->stream));
+  // the prescribed-dof mask is the context's own byte array (d_dofmask, built once from d_cdof); its free dofs
+  std::vector<uint8_t> hm((size_t)c->ndof);
+  FEA_HIP_CHECK(c, hipMemcpyAsync(hm.data(), c->d_dofmask, hm.size(), hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  S.n_free = 0;
+  for (uint8_t b : hm) S.n_free += b ? 0 : 1;
+  S.have = false;
+  return FEAHIP_OK;
+}
+
+static inline double *mv(feahip_ctx *c, int j) { return c->modal.d_v + (size_t)j * c->ndof * MC; }
+enum { V_X = 0, V_W = 1, V_P = 2, V_KX = 3, V_KW = 4, V_KP = 5, V_MX = 6, V_MW = 7, V_MP = 8 };
+
+// Y = K X, Z = mask(M X) for device block vectors
+int launch_spmm_km(feahip_ctx *c, const double *d_x8, double *d_y8, double *d_z8)
+{
+  hipLaunchKernelGGL(k_spmm_km, dim3(spmm_grid(c)), dim3(256), 0, c->stream, c->chunk0, c->nchunks_local, c->d_chunk,
+                     c->d_rowptr, c->d_colidx, (const double *)c->d_K, (const double *)c->mass.d_m,
+                     (const uint8_t *)c->d_dofmask, (const v2d *)d_x8, (v2d *)d_y8, (v2d *)d_z8);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+static void enq_gram(feahip_ctx *c, int np)
+{
+  hipLaunchKernelGGL(k_modal_gram, dim3(gram_grid(c)), dim3(256), 0, c->stream, c->ndof, np, (const double *)c->modal.d_v,
+                     (size_t)c->ndof * MC, c->modal.d_part);
+}
+static void enq_combine(feahip_ctx *c, int np, int write_p)
+{
+  hipLaunchKernelGGL(k_modal_combine, dim3((c->ndof + 255) / 256, 3), dim3(256), 0, c->stream, c->ndof, np, write_p,
+                     c->modal.d_v, (size_t)c->ndof * MC, (const double *)(c->modal.d_small + MODAL_SUMS));
+}
+// sums [e0, e0 + n) of d_part reduced into d_small and read into h (one synchronisation)
+static int read_sums(feahip_ctx *c, int e0, int n, double *h)
+{
+  hipLaunchKernelGGL(k_modal_reduce, dim3(n), dim3(256), 0, c->stream, e0, resid_grid(c), gram_grid(c),
+                     (const double *)c->modal.d_part, c->modal.d_small);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  FEA_HIP_CHECK(c, hipMemcpyAsync(h + e0, c->modal.d_small + e0, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+// hooks of feahip_time_kernel 13, 14, 15: the product on X, the Gram pass and the combination (with the identity: the
+// vectors stay as they are) on all nine arrays
+int time_modal_kernel(feahip_ctx *c, int what)
+{
+  if (what == 13) return launch_spmm_km(c, mv(c, V_X), mv(c, V_KX), mv(c, V_MX));
+  if (what == 14) enq_gram(c, 3);
+  else enq_combine(c, 3, 1);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+int time_modal_prepare(feahip_ctx *c)
+{
+  int rc;
+  if ((rc = ensure_modal(c))) return rc;
+  ModalState &S = c->modal;
+  S.have = false;                                                     // the vectors are scratch from here on
+  const size_t n8 = (size_t)c->ndof * MC;
+  for (int j : {V_X, V_W, V_P})
+    hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, j));
+  S.h_C.assign(24 * 16, 0.0);
+  for (int k = 0; k < 8; ++k) { S.h_C[(size_t)k * 16 + k] = 1.0; S.h_C[(size_t)(16 + k) * 16 + 8 + k] = 1.0; }   // X <- X, P <- P
+  FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + MODAL_SUMS, S.h_C.data(), sizeof(double) * 24 * 16, hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+// [8][3N] host-ordered device vectors (library ids) to a block vector and back
+int launch_modal_pack(feahip_ctx *c, const double *d_in, double *d_out, int unpack)
+{
+  hipLaunchKernelGGL(k_modal_pack, g256((size_t)c->ndof * MC), dim3(256), 0, c->stream, (size_t)c->ndof, d_in, d_out, unpack);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+// ---- the Rayleigh-Ritz step on the host ---------------------------------------------------------------------------
+// cyclic Jacobi: A (n x n, symmetric, row-major, destroyed) = V diag(w) V'; a fixed sweep order, so the same input gives
+// the same bits
+static void jacobi_eig(int n, double *A, double *V, double *w)
+{
+  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, dia = 0.0;
+    for (int i = 0; i < n; ++i) { dia += A[i * n + i] * A[i * n + i]; for (int j = i + 1; j < n; ++j) off += A[i * n + j] * A[i * n + j]; }
+    if (!(off > 1e-36 * dia)) break;
+    for (int p = 0; p < n - 1; ++p)
+      for (int q = p + 1; q < n; ++q) {
+        const double apq = A[p * n + q];
+        if (apq == 0.0) continue;
+        const double tau = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
+        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+        const double cs = 1.0 / sqrt(1.0 + t * t), sn = t * cs;
+        for (int k = 0; k < n; ++k) {
+          const double akp = A[k * n + p], akq = A[k * n + q];
+          A[k * n + p] = cs * akp - sn * akq; A[k * n + q] = sn * akp + cs * akq;
+        }
+        for (int k = 0; k < n; ++k) {
+          const double apk = A[p * n + k], aqk = A[q * n + k];
+          A[p * n + k] = cs * apk - sn * aqk; A[q * n + k] = sn * apk + cs * aqk;
+        }
+        A[p * n + q] = A[q * n + p] = 0.0;
+        for (int k = 0; k < n; ++k) {
+          const double vkp = V[k * n + p], vkq = V[k * n + q];
+          V[k * n + p] = cs * vkp - sn * vkq; V[k * n + q] = sn * vkp + cs * vkq;
+        }
+      }
+  }
+  for (int i = 0; i < n; ++i) w[i] = A[i * n + i];
+}
+
+// GM, GK: ns x ns (ns = 8, 16 or 24), symmetric, row-major, of S = [X, W, P].  theta[m] ascending, C[ns][2 m]: columns
+// 0..m-1 the coefficients of X_new = S C_x, m..2m-1 those of P_new = X_new - X C_x[X rows].  Returns the rank of the
+// basis kept, or -1 when fewer than m directions are left or a sum is not finite.
+int modal_ritz(int ns, const double *GM, const double *GK, int m, double *theta, double *C)
+{
+  if (ns < m || ns > 24 || m > MC) return -1;
+  double A[24 * 24], V[24 * 24], w[24], d[24], Q[24 * 24], T[24 * 24], Z[24 * 24], t[24], GQ[24 * 24];
+  for (int i = 0; i < ns * ns; ++i) if (!std::isfinite(GM[i]) || !std::isfinite(GK[i])) return -1;
+  for (int i = 0; i < ns; ++i) d[i] = GM[i * ns + i] > 0.0 ? 1.0 / sqrt(GM[i * ns + i]) : 0.0;
+  for (int i = 0; i < ns; ++i) for (int j = 0; j < ns; ++j) A[i * ns + j] = d[i] * GM[i * ns + j] * d[j];
+  jacobi_eig(ns, A, V, w);
+  double wmax = 0.0;
+  for (int i = 0; i < ns; ++i) wmax = w[i] > wmax ? w[i] : wmax;
+  int r = 0;
+  for (int k = 0; k < ns; ++k)
+    if (w[k] > 1e-12 * wmax) {
+      const double s = 1.0 / sqrt(w[k]);
+      for (int i = 0; i < ns; ++i) Q[i * ns + r] = d[i] * V[i * ns + k] * s;
+      ++r;
+    }
+  if (r < m) return -1;
+  for (int i = 0; i < ns; ++i)
+    for (int k = 0; k < r; ++k) { double s = 0.0; for (int j = 0; j < ns; ++j) s += GK[i * ns + j] * Q[j * ns + k]; GQ[i * ns + k] = s; }
+  for (int a = 0; a < r; ++a)
+    for (int b = a; b < r; ++b) {
+      double s1 = 0.0, s2 = 0.0;
+      for (int i = 0; i < ns; ++i) { s1 += Q[i * ns + a] * GQ[i * ns + b]; s2 += Q[i * ns + b] * GQ[i * ns + a]; }
+      T[a * r + b] = T[b * r + a] = 0.5 * (s1 + s2);
+    }
+  jacobi_eig(r, T, Z, t);
+  int order[24];
+  for (int k = 0; k < r; ++k) order[k] = k;
+  std::stable_sort(order, order + r, [&](int x, int y) { return t[x] < t[y]; });
+  for (int j = 0; j < m; ++j) {
+    theta[j] = t[order[j]];
+    for (int i = 0; i < ns; ++i) {
+      double s = 0.0;
+      for (int k = 0; k < r; ++k) s += Q[i * ns + k] * Z[k * r + order[j]];
+      C[i * 2 * m + j] = s;
+    }
+  }
+  // P_new = X_new - X C_x[X rows] = [W, P] C_x[W, P rows]: the part of the new Ritz vectors that is not X.  It spans,
+  // with X_new, the same space as X_new - X (X' M X_new) does, and is formed from the small directions alone -- the
+  // other form subtracts two O(1) coefficients to get one of the size of P, and the recurrences for K P and M P then
+  // carry that cancellation: with all eight columns wanted it stalled at 1e-5 on a 108-dof bar and then diverged
+  for (int j = 0; j < m; ++j)
+    for (int i = 0; i < ns; ++i) C[i * 2 * m + m + j] = i < m ? 0.0 : C[i * 2 * m + j];
+  return r;
+}
+
+namespace {
+// the Gram matrices of np column blocks out of the 768 reduced sums
+void unpack_gram(const double *sums, int np, double *GM, double *GK)
+{
+  static const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {0, 1, 2, 1, 2, 2};
+  const int ns = 8 * np;
+  for (int q = 0; q < 6; ++q) {
+    if (pb[q] >= np) continue;
+    for (int a = 0; a < 8; ++a)
+      for (int b = 0; b < 8; ++b) {
+        if (pa[q] == pb[q] && b < a) continue;                          // the upper triangle of a diagonal block
+        const int i = pa[q] * 8 + a, j = pb[q] * 8 + b;
+        GM[i * ns + j] = GM[j * ns + i] = sums[q * 64 + a * 8 + b];
+        GK[i * ns + j] = GK[j * ns + i] = sums[(6 + q) * 64 + a * 8 + b];
+      }
+  }
+}
+}
+
+// R (and W) of the current X, KX, MX and theta; precond: W = M^-1 R with the context's preconditioner
+static int enq_residual(feahip_ctx *c, bool precond)
+{
+  ModalState &S = c->modal;
+  const bool amg = c->precond == 1;
+  hipLaunchKernelGGL(k_modal_residual, dim3(resid_grid(c)), dim3(256), 0, c->stream, c->N, (const double *)mv(c, V_KX),
+                     (const double *)mv(c, V_MX), (const double *)(S.d_small + MODAL_SUMS + 24 * 16),
+                     (precond && !amg) ? (const double *)c->d_minv : (const double *)nullptr, (const uint8_t *)c->d_dofmask,
+                     mv(c, V_W), S.d_part);
+  if (precond && amg) {
+    // one W-cycle per column: its residual out of the block, the cycle, its result into the block (enq_cycle2)
+    const size_t n = (size_t)c->ndof;
+    for (int col = 0; col < MC; ++col) {
+      hipLaunchKernelGGL(k_modal_extract, g256(n), dim3(256), 0, c->stream, n, (const double *)mv(c, V_W), col, c->d_r);
+      const double *zv = amg_apply(c, c->d_r);
+      if (!zv) return FEAHIP_EHIP;
+      hipLaunchKernelGGL(k_modal_insert, g256(n), dim3(256), 0, c->stream, n, zv, (const uint8_t *)c->d_dofmask, col, mv(c, V_W));
+    }
+  }
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, double *lambda, double *resid, int *iters)
+{
+  int rc;
+  if ((rc = ensure_modal(c))) return rc;
+  ModalState &S = c->modal;
+  if (S.n_free < 3 * MC) {
+    c->err = "solve_modes: " + std::to_string(S.n_free) + " free dofs, fewer than the 24 the block of eight columns needs";
+    return FEAHIP_EINVAL;
+  }
+  // K(x), masked as the PCG sees it (K and f are another matrix from here on: k_epoch)
+  if ((rc = feahip_create_stiffness(c)) || (rc = feahip_apply_prescribed_bc(c, 0.0))) return rc;
+  if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
+  else enq_precond_blockjacobi(c);
+  const size_t n8 = (size_t)c->ndof * MC;
+  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
+  double *theta = S.theta;
+  S.h_C.assign(24 * 16 + MC, 0.0);
+  auto products_x = [&]() { return launch_spmm_km(c, mv(c, V_X), mv(c, V_KX), mv(c, V_MX)); };
+  auto upload = [&]() -> int {                        // C and theta (h_C is not touched again before the next read-back)
+    for (int j = 0; j < MC; ++j) S.h_C[24 * 16 + j] = theta[j];
+    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + MODAL_SUMS, S.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
+    return FEAHIP_OK;
+  };
+  auto converged = [&]() {                            // the stop test on the norms in sums[0 .. 24)
+    bool ok = true;
+    for (int j = 0; j < MC; ++j) {
+      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
+      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
+      if (j < n_modes && !(ratio[j] <= tol)) ok = false;
+    }
+    return ok;
+  };
+  // Rayleigh-Ritz on np column blocks from the sums read back: theta and the coefficients; false when the basis breaks
+  auto ritz = [&](int np, int *rank) -> bool {
+    unpack_gram(sums + MODAL_NORMS, np, GM, GK);
+    double Cs[24 * 16];
+    const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
+    if (r < 0) return false;
+    std::fill(S.h_C.begin(), S.h_C.begin() + 24 * 16, 0.0);
+    std::copy(Cs, Cs + 8 * np * 16, S.h_C.begin());
+    *rank = r;
+    return true;
+  };
+  auto broke = [&]() {
+    S.have = false;
+    c->err = "solve_modes: the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes is not supported)";
+    return FEAHIP_ENOTCONVERGED;
+  };
+  // X alone: fresh products, the Gram sums of X, theta ascending and X M-orthonormal again, fresh products, the norms
+  auto ritz_on_x = [&]() -> int {
+    int rank = 0;
+    if ((rc = products_x())) return rc;
+    enq_gram(c, 1);
+    if ((rc = read_sums(c, MODAL_NORMS, MODAL_GRAM, sums))) return rc;
+    if (!ritz(1, &rank)) return broke();
+    if ((rc = upload())) return rc;
+    enq_combine(c, 1, 0);
+    return products_x();
+  };
+  auto fresh_norms = [&]() -> int {
+    if ((rc = enq_residual(c, false))) return rc;
+    return read_sums(c, 0, MODAL_NORMS, sums);
+  };
+  auto finish = [&](int it, int code) {
+    S.have = true;
+    for (int j = 0; j < n_modes; ++j) { lambda[j] = theta[j]; if (resid) resid[j] = ratio[j]; }
+    if (iters) *iters = it;
+    if (code == FEAHIP_ENOTCONVERGED) c->err = "solve_modes: not converged after " + std::to_string(it) + " Rayleigh-Ritz steps";
+    return code;
+  };
+
+  if (warm && S.have) {
+    // the modes held, their theta, against the K of now: converged already means nothing is touched
+    if ((rc = upload()) || (rc = products_x()) || (rc = fresh_norms())) return rc;
+    if (converged()) return finish(0, FEAHIP_OK);
+  } else {
+    hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, V_X));
+  }
+  S.have = false;
+  if ((rc = ritz_on_x())) return rc;
+  bool hasP = false, must_step = false;
+  for (int it = 0;;) {
+    if (it > 0 && it % 20 == 0 && !must_step) { if ((rc = products_x())) return rc; }   // the recurrences cannot drift
+    const int np = hasP ? 3 : 2;
+    if ((rc = upload()) || (rc = enq_residual(c, true))) return rc;
+    if ((rc = launch_spmm_km(c, mv(c, V_W), mv(c, V_KW), mv(c, V_MW)))) return rc;
+    enq_gram(c, np);
+    if ((rc = read_sums(c, 0, MODAL_SUMS, sums))) return rc;            // the one synchronisation of a step
+    const bool stop = converged() && !must_step;
+    must_step = false;
+    if (stop || it >= max_it) {
+      // at return: X orthonormalised on its own, fresh products, and the test made on them
+      if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
+      if (converged()) return finish(it, FEAHIP_OK);
+      if (it >= max_it) return finish(it, FEAHIP_ENOTCONVERGED);
+      must_step = true;                                                 // the recurrences had drifted: go on from the fresh products
+      continue;
+    }
+    int rank = 0;
+    if (!ritz(np, &rank)) return broke();
+    if ((rc = upload())) return rc;
+    enq_combine(c, np, 1);
+    hasP = rank == 8 * np;                                              // a rank drop restarts the recurrence without P
+    ++it;
+  }
+}
+
+int modal_get(feahip_ctx *c, int col, double *h_lib /*[3N], library ids*/)
+{
+  hipLaunchKernelGGL(k_modal_extract, g256((size_t)c->ndof), dim3(256), 0, c->stream, (size_t)c->ndof, (const double *)mv(c, V_X), col, c->d_q);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  FEA_HIP_CHECK(c, hipMemcpyAsync(h_lib, c->d_q, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}

@@ -142,7 +142,12 @@ ABI = {
     "feahip_strain_energy": [C.c_void_p, _dp],
     "feahip_get_nodal_energy": [C.c_void_p, _dp],
     "feahip_get_reactions": [C.c_void_p, _dp],
+    "feahip_solve_modes": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip],
+    "feahip_get_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
+    "feahip_spmm_km": [C.c_void_p, _dp, _dp, _dp],
+    "feahip_host_modal_ritz": [C.c_int, _dp, _dp, _dp, _dp],
 }
+MODAL_COLS = 8                                          # FEA_MODAL_COLS of include/fea_hip.h
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
 COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
@@ -194,6 +199,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("modal_modes", C.c_int), ("modal_tolerance", C.c_double), ("modal_max", C.c_int),
     ]
 
 
@@ -254,6 +260,17 @@ def _d(a):
 
 def _i(a):
     return a.ctypes.data_as(_ip)
+
+
+def host_modal_ritz(gram_m, gram_k):
+    """feahip_host_modal_ritz (no device): (rank kept, theta[8], coef[n_dirs][16]) of one Rayleigh-Ritz step."""
+    lib = load_library()
+    gm, gk = np.ascontiguousarray(gram_m, dtype=np.float64), np.ascontiguousarray(gram_k, dtype=np.float64)
+    n = len(gm)
+    assert gm.shape == (n, n) and gk.shape == (n, n)
+    theta, coef = np.zeros(MODAL_COLS), np.zeros((n, 2 * MODAL_COLS))
+    rank = lib.feahip_host_modal_ritz(n, _d(gm), _d(gk), _d(theta), _d(coef))
+    return rank, theta, coef
 
 
 def element_tables(ele_type, gauss_count):
@@ -332,6 +349,14 @@ class Deck:
         if set(res) - {"nodal_stress", "energy", "reactions"}:
             raise ValueError("results: nodal_stress, energy, reactions")
         self.results = {k: bool(res.get(k, False)) for k in ("nodal_stress", "energy", "reactions")}
+        # (modal :modes N :tolerance t :max M): the natural frequencies feasolver_hip computes after its last step
+        self.modal_modes = int(kw.get("modal_modes", 0))
+        self.modal_tolerance = float(kw.get("modal_tolerance", 1e-8))
+        self.modal_max = int(kw.get("modal_max", 1000))
+        if not 0 <= self.modal_modes <= MODAL_COLS:
+            raise ValueError("modal_modes: 0 to 8")
+        if self.modal_modes and self.density is None:
+            raise ValueError("modal_modes needs a density")
 
     @staticmethod
     def load(path):
@@ -367,7 +392,9 @@ class Deck:
                               **(dict(scheme="explicit", safety=fd.dynamics_safety, restep=fd.dynamics_restep)
                                  if fd.dynamics_explicit else {})) if fd.has_dynamics else None,
                 results=dict(nodal_stress=bool(fd.results_nodal_stress), energy=bool(fd.results_energy),
-                             reactions=bool(fd.results_reactions)))
+                             reactions=bool(fd.results_reactions)),
+                **(dict(modal_modes=fd.modal_modes, modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
+                   if fd.modal_modes else {}))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -413,6 +440,8 @@ class Deck:
         res = getattr(self, "results", None) or {}
         fd.results_nodal_stress, fd.results_energy = int(res.get("nodal_stress", False)), int(res.get("energy", False))
         fd.results_reactions = int(res.get("reactions", False))
+        fd.modal_modes = int(getattr(self, "modal_modes", 0))
+        fd.modal_tolerance, fd.modal_max = float(getattr(self, "modal_tolerance", 1e-8)), int(getattr(self, "modal_max", 1000))
         return fd
 
     def save(self, path):
@@ -752,6 +781,34 @@ class FeaSolver:
             self._chk(rc)
         taken = log[:ns][log[:ns] > 0]
         return (done.value, taken) if check else (done.value, taken, rc)
+
+    # ---- modal analysis ---------------------------------------------------
+    def solve_modes(self, n_modes, tolerance=1e-8, max_iterations=1000, warm=False, check=True):
+        """feahip_solve_modes: the n_modes lowest eigenpairs of K(x) phi = lambda M phi on the free dofs.  Returns
+        (lam[n_modes] ascending = omega^2, resid[n_modes], Rayleigh-Ritz steps) and, with check=False, the return code
+        as a fourth item instead of raising when the steps run out."""
+        lam, res, it = np.zeros(max(int(n_modes), 1)), np.zeros(max(int(n_modes), 1)), C.c_int(0)
+        rc = self._lib.feahip_solve_modes(self._ctx, int(n_modes), float(tolerance), int(max_iterations), int(bool(warm)),
+                                          _d(lam), _d(res), C.byref(it))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        return (lam, res, it.value) if check else (lam, res, it.value, rc)
+
+    def modes(self, first=0, count=None):
+        """feahip_get_modes: phi[count][3N] of the last solve_modes, M-orthonormal, zero on the prescribed dofs; all
+        eight columns of the block are held (count=None: from `first` to the last)."""
+        count = MODAL_COLS - first if count is None else count
+        phi = np.zeros((max(int(count), 0), self.ndof))
+        self._chk(self._lib.feahip_get_modes(self._ctx, int(first), int(count), _d(phi)))
+        return phi
+
+    def spmm_km(self, x8):
+        """[K X, mask(M X)] of eight columns in one pass over K's pattern; x8 and both results are [8][3N]."""
+        x8 = np.ascontiguousarray(x8, dtype=np.float64)
+        assert x8.shape == (MODAL_COLS, self.ndof)
+        y8, z8 = np.zeros_like(x8), np.zeros_like(x8)
+        self._chk(self._lib.feahip_spmm_km(self._ctx, _d(x8), _d(y8), _d(z8)))
+        return y8, z8
 
     # ---- surface loads ---------------------------------------------------
     def set_surface_loads(self, faces, kind, values):

@@ -91,6 +91,14 @@ typedef struct fea_deck {
    * to the .msh file; :energy and :reactions add one log line each per finished step.  Written by fea_deck_save only
    * when one of them is set; without the section the file and the log are what they were                        */
   int results_nodal_stress, results_energy, results_reactions;
+  /* modal analysis, optional: (modal :modes N :tolerance t :max M) inside (solution ...), N in [1, 8] (:tolerance 1e-8
+   * and :max 1000 where absent).  After its last step feasolver_hip calls feahip_solve_modes at the state reached, logs
+   * one line per mode and appends one $NodeData section per mode shape to the .msh file (fea_modal_run).  It needs the
+   * density of (dynamics ... :density rho) -- :steps 0 there leaves the run static --: a deck without one is refused at
+   * load.  Written by fea_deck_save only when N > 0                                                             */
+  int modal_modes;
+  double modal_tolerance;
+  int modal_max;
 } fea_deck;
 
 /* sexp_data_load (sexp_loader.c:275-327).  Returns 0, or -1 with a message
@@ -177,6 +185,12 @@ int fea_solve_dynamic_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void 
  * (9 components, the symmetric tensor in full) and NodeData "Von Mises".     */
 int fea_export_gmsh(const char *filename, const fea_deck *deck,
                     const fea_step_snapshot *steps, int nsteps);
+
+/* The modal analysis of a deck with (modal :modes N ...), N > 0, at the state the context is in: feahip_solve_modes,
+ * one log line per mode ("Mode k: omega^2 = l, f = x Hz", f = sqrt(max(l, 0)) / 2 pi) and, with msh_path not NULL, one
+ * $NodeData section "Mode k" per mode shape appended to that file, tagged with the frequency.  A solve that runs out
+ * of steps is logged and its modes are written as they stand.  Returns 0, or a negative FEAHIP_E* code.        */
+int fea_modal_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 
 /* "<base>.msh" next to the deck, as initial_data_load builds it
  * (fea_solver.c:1681-1687); out must hold strlen(deck_path)+5 bytes.        */

@@ -12,7 +12,9 @@
  * steps (feahip_solve_explicit), and likewise writes the final state.
  * Every other deck takes the reference's loop.  A deck with a (results ...)
  * section gets the nodal stress in the file and the strain energy and the
- * reaction sums in the log (fea_host.h).
+ * reaction sums in the log (fea_host.h).  A deck with (modal :modes N ...)
+ * then gets its N lowest natural frequencies at the final state in the log
+ * and the mode shapes in the file (feahip_solve_modes).
  *
  * One option the reference does not have, after the deck name:
  *   --multigrid   PCG_ILU / CHOLESKY solves use the aggregation-multigrid
@@ -74,6 +76,10 @@ int main(int argc, char **argv)
      * reference then drops the last completed step from the file: same here */
     if (fea_export_gmsh(msh, &deck, steps, (arc || dyn) ? 1 : (done == deck.load_increments_count ? done : done - 1))) {
       fprintf(stderr, "could not write %s\n", msh);
+      status = 1;
+    } else if (deck.modal_modes > 0 && (rc = fea_modal_run(&deck, ctx, stdout, msh))) {
+      /* (modal :modes N ...): the natural frequencies at the state reached, the mode shapes behind the steps */
+      fprintf(stderr, "feasolve error encountered: %s\n", feahip_last_error(ctx));
       status = 1;
     }
     free(msh);

@@ -478,6 +478,18 @@ static int read_list(reader *r, fea_deck *d)
         else if (!(ieq(s, "nil") || ieq(s, "no") || ieq(s, "false"))) return fail(r, "results attributes take t or nil");
       }
     }
+  } else if (ieq(head, "modal")) {                            /* no counterpart in the reference */
+    if (need_num(r, a, na, "modes", &v)) return -1;
+    if (!(v >= 0 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "modal :modes must be an integer in [0, 8]");
+    d->modal_modes = (int)v;
+    d->modal_tolerance = 1e-8; d->modal_max = 1000;
+    if (attr_get(a, na, "tolerance") && need_num(r, a, na, "tolerance", &d->modal_tolerance)) return -1;
+    if (!(d->modal_tolerance > 0)) return fail(r, "modal :tolerance must be positive");
+    if (attr_get(a, na, "max")) {
+      if (need_num(r, a, na, "max", &v)) return -1;
+      if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "modal :max must be a non-negative integer");
+      d->modal_max = (int)v;
+    }
   } else if (ieq(head, "body-force")) {
     if (need_num(r, a, na, "x", &d->body_force[0])) return -1;
     if (need_num(r, a, na, "y", &d->body_force[1])) return -1;
@@ -550,6 +562,9 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
     if (rc == 0 && deck->has_body_force && !deck->has_dynamics) {
       rc = -1; snprintf(r.err, sizeof r.err, "deck has (body-force ...) but no (dynamics ... :density rho)");
     }
+    if (rc == 0 && deck->modal_modes > 0 && !deck->has_dynamics) {
+      rc = -1; snprintf(r.err, sizeof r.err, "deck has (modal ...) but no density: add (dynamics :steps 0 :dt 1 :density rho)");
+    }
   }
   if (rc) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", r.err);
@@ -606,6 +621,8 @@ int fea_deck_save(const char *path, const fea_deck *d)
   if (d->results_nodal_stress || d->results_energy || d->results_reactions)   /* written only when asked for */
     fprintf(f, "\n   (results :nodal-stress %s :energy %s :reactions %s)", d->results_nodal_stress ? "t" : "nil",
             d->results_energy ? "t" : "nil", d->results_reactions ? "t" : "nil");
+  if (d->modal_modes > 0)                                                      /* written only when asked for */
+    fprintf(f, "\n   (modal :modes %d :tolerance %.17g :max %d)", d->modal_modes, d->modal_tolerance, d->modal_max);
   fprintf(f, ")\n");
   fprintf(f, " (input-data\n  (geometry\n   (nodes");
   for (i = 0; i < d->nodes_count; ++i)

@@ -591,6 +591,70 @@ int feahip_strain_energy(feahip_ctx *ctx, double *W);
 int feahip_get_nodal_energy(feahip_ctx *ctx, double *w_node);
 int feahip_get_reactions(feahip_ctx *ctx, double *r);
 
+/* ---- modal analysis: the lowest natural frequencies and mode shapes ---------
+ * feahip_solve_modes: the n_modes lowest eigenpairs of K(x) phi = lambda M phi
+ * on the free dofs, by a blocked LOBPCG whose basis is M-orthonormalised at
+ * every step.  A context that never calls the entries below allocates and
+ * launches nothing for them.  The reference has no counterpart.
+ *   K  the tangent at the current nodes, assembled here (feahip_create_stiffness)
+ *      and masked with feahip_apply_prescribed_bc(ctx, 0.0): what the PCG and
+ *      the multigrid see.  K and f hold another matrix afterwards, as after
+ *      feahip_stable_step and feahip_consistent_acceleration.
+ *   M  the consistent mass of feahip_set_mass, per-material densities included,
+ *      used unmasked: the iteration lives in the subspace of vectors that vanish
+ *      on the prescribed dofs -- every vector it builds is zero there and the
+ *      M-products are zeroed there.
+ * lambda[n_modes] is ascending and holds omega^2 (not its root).  The modes are
+ * M-orthonormal and exactly 0 on the prescribed dofs.  The sign of a mode is
+ * arbitrary but the same bits on every call: the start block is a fixed integer
+ * hash of (library dof index, column) mapped to [-1, 1), no random state and no
+ * clock.  The block width is FEA_MODAL_COLS = 8 and 1 <= n_modes <= 8; all eight
+ * columns iterate (the surplus are guard vectors), no locking, no deflation.
+ * Converged: for every M-normalised column j < n_modes, r_j = K x_j - theta_j M x_j
+ * has ||r_j|| <= tolerance (||K x_j|| + |theta_j| ||M x_j||) in the 2-norm.
+ * resid[n_modes] (may be NULL) receives that ratio from FRESH products K X, M X
+ * at return, *iters (may be NULL) the Rayleigh-Ritz steps taken.  After
+ * max_iterations steps without convergence: FEAHIP_ENOTCONVERGED, with lambda,
+ * resid and the modes left as they stand.
+ * Preconditioner: the context's own (feahip_set_preconditioner) -- kind 0 the
+ * 3x3 block-Jacobi inverse, kind 1 one W-cycle per column and step; kind 2 is
+ * refused.  warm != 0 with modes held from an earlier call on this context:
+ * the solve starts from them (all eight columns, the guard columns included),
+ * and a converged restart at an unchanged state returns with *iters == 0 and
+ * nothing touched; warm == 0 starts from the hash.
+ * FEAHIP_ESTATE: no mass, or a stale one.  FEAHIP_EINVAL: n_modes outside
+ * [1, 8], tolerance <= 0, max_iterations < 0, null lambda, fewer than 24 free
+ * dofs; a context with a transport, a row shard or made by feahip_create_rank*
+ * (refused like feahip_solve_slae2, feahip_last_error says which).
+ * A body with zero-energy modes (no or too few supports) is NOT refused and
+ * nothing is promised for it: the relative test cannot be met at lambda = 0,
+ * and no shift is offered.
+ * Memory: nine block vectors, 9 x 192 bytes per node, plus 13 MB of partial
+ * sums, allocated on the first call and kept until feahip_destroy.
+ *
+ * feahip_get_modes: modes [first, first + count) of the last solve (all eight
+ * columns are held), phi[count][3N] in the caller's dof order.  FEAHIP_ESTATE
+ * before any solve, FEAHIP_EINVAL for a range outside [0, 8] or null phi.     */
+#define FEA_MODAL_COLS 8
+int feahip_solve_modes(feahip_ctx *ctx, int n_modes, double tolerance, int max_iterations, int warm,
+                       double *lambda /*[n_modes]*/, double *resid /*[n_modes], may be NULL*/, int *iters /*may be NULL*/);
+int feahip_get_modes(feahip_ctx *ctx, int first, int count, double *phi);
+/* [Y, Z] = [K X, mask(M X)] for eight columns in one pass over K's pattern,
+ * host vectors [8][3N] in the caller's dof order; Z is zero on the prescribed
+ * dofs (test hook for the block product of feahip_solve_modes, refused as that
+ * solve is; FEAHIP_ESTATE before the first stiffness assembly; modes held from
+ * a solve are dropped)                                                        */
+int feahip_spmm_km(feahip_ctx *ctx, const double *x8, double *y8, double *z8);
+/* Host-only (no device): the Rayleigh-Ritz step of feahip_solve_modes.  gram_m,
+ * gram_k: S' M S and S' K S, n_dirs x n_dirs (8, 16 or 24), row-major, S = [X, W,
+ * P] in blocks of eight.  Scales by diag(gram_m)^-1/2, eigendecomposes by cyclic
+ * Jacobi, drops directions with eigenvalue <= 1e-12 x the largest, and returns
+ * theta[8] ascending and coef[n_dirs][16]: columns 0-7 give X_new = S C_x,
+ * columns 8-15 P_new = X_new - X C_x[X rows] (the part of X_new that lies in
+ * [W, P]: its X rows are zero).  Returns the rank kept, or -1
+ * when fewer than eight directions are left or an entry is not finite.        */
+int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const double *gram_k, double *theta, double *coef);
+
 /* z = M^-1 r on every rank of the group at once, with the preconditioner the
  * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
  * feahip_apply_preconditioner takes them (the caller's node ids of context k;
@@ -839,7 +903,11 @@ int feahip_sync(feahip_ctx *ctx);
  * 10 the two pointwise kernels of an explicit step together (they advance v
  * and a by a step of dt = 1 on the f in force), 11 k_gershgorin on the K in
  * force (10 and 11 refused without a mass), 12 the two result passes together
- * (k_result_elements, k_result_nodes) with all outputs and material = -1.    */
+ * (k_result_elements, k_result_nodes) with all outputs and material = -1,
+ * 13 k_spmm_km (K X and M X of eight columns in one pass), 14 k_modal_gram (both
+ * 24 x 24 Gram matrices from the nine block vectors), 15 k_modal_combine (the
+ * nine block vectors recombined in place); 13-15 refused without a mass and
+ * where feahip_solve_modes is.                                               */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
