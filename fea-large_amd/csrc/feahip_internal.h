@@ -259,12 +259,23 @@ struct GatherLayout {                // the same for every chunk of a context
 };
 struct HostGather : HostChunkMaps {
   GatherLayout lay;
-  int same_as_previous = 0;          // chunks whose map words equal their predecessor's (GatherHeader::flags)
+  int same_as_previous = 0;          // chunks whose map words equal their predecessor's in walk order (GatherHeader::flags)
+  // the walk (gather.cpp): the blob holds the records in walk order; first_row stays in row order
+  std::vector<int> walk;             // [nchunks] the chunk, in row order, whose record is the i-th of the blob
+  std::vector<int> run_start;        // [nruns+1] a workgroup walks the records [run_start[r], run_start[r+1]); no run is empty
+  std::vector<int> cost;             // [nchunks] modelled cycles of the i-th record where it stands (gather_chunk_cost)
 };
 // rows [row_lo, row_hi) only: a rank builds the maps of the rows it owns
 // elem_mat (may be null): material id of every element; the records then carry the optional section o_emat
+// ncu: the compute units the runs are cut for (0: 256).  FEAHIP_GATHER_ORDER=0: the records in row order;
+// FEAHIP_GATHER_BALANCE=0: runs of equal chunk counts; FEAHIP_GATHER_RUN=n: runs of n chunks (tuning; no result changes)
 void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out,
-                       const uint8_t *elem_mat = nullptr);
+                       const uint8_t *elem_mat = nullptr, int ncu = 0);
+// modelled shader cycles of one chunk (K-and-f kernel) from its header; loads_words: its predecessor in the run cannot
+// hand it its map words.  Pure host arithmetic.
+int gather_chunk_cost(const GatherHeader &h, bool loads_words);
+// modelled cycles of a launch of runs of these costs on ncu compute units
+long long gather_launch_cost(const std::vector<long long> &run_cost, int ncu);
 int ensure_gather(feahip_ctx *c);
 int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF);
 
@@ -366,7 +377,10 @@ struct GatherCache : MapCache {        // either gather kernel: one map record p
 };
 struct GatherMaps : GatherCache {
   GatherLayout lay{};
-  void release() { dev_free({d_maps}); *this = GatherMaps(); }
+  int *d_run_start = nullptr;          // [nruns+1] records of the runs, in walk order (HostGather::run_start)
+  int nruns = 0;
+  std::vector<int> record_of;          // [nchunks] where in d_maps the record of a chunk (in row order) sits
+  void release() { dev_free({d_maps, d_run_start}); *this = GatherMaps(); }
 };
 struct Gather10Maps : GatherCache {
   Gather10Layout lay{};

@@ -450,8 +450,9 @@ struct ChunkBuilder {
   }
 };
 
-// ---- layout: fixed section offsets, sized by the largest chunk
-bool lay_out(const std::vector<Local> &loc, bool materials, HostGather &out)
+// ---- layout: fixed section offsets, sized by the largest chunk; the records in walk order (walk[i]: the chunk, in row
+// order, whose record is the i-th of the blob)
+bool lay_out(const std::vector<Local> &loc, const std::vector<int> &walk, bool materials, HostGather &out)
 {
   const int nch = (int)loc.size();
   int m_v = 0, m_c = 0, m_d = 0, g_nodes = 0, g_elems = 0, g_tile = 0;
@@ -480,7 +481,7 @@ bool lay_out(const std::vector<Local> &loc, bool materials, HostGather &out)
   out.blob.assign((size_t)nch * lay.stride, 0);
   parallel_ranges(nch, 512, [&](int lo, int hi) {
     for (int p = lo; p < hi; ++p) {
-      const Local &L = loc[p];
+      const Local &L = loc[walk[p]];
       unsigned char *rec = out.blob.data() + (size_t)p * lay.stride;
       memcpy(rec, &L.h, sizeof(GatherHeader));
       memcpy(rec + lay.o_nodes, L.nodes.data(), L.nodes.size() * 4);
@@ -496,8 +497,8 @@ bool lay_out(const std::vector<Local> &loc, bool materials, HostGather &out)
   return true;
 }
 
-// a chunk whose successor has the same map words (chunk-local indices only: the interior bricks of a structured
-// block are all alike) says so in its header: the kernel then keeps the words in registers instead of loading them
+// a chunk whose successor IN WALK ORDER has the same map words (chunk-local indices only: the interior bricks of a
+// structured block are all alike) says so in its header: the kernel then keeps the words in registers instead of loading them
 void mark_repeats(HostGather &out, int nch)
 {
   const GatherLayout &lay = out.lay;
@@ -513,11 +514,266 @@ void mark_repeats(HostGather &out, int nch)
 }
 }  // namespace
 
+// ---------------------------------------------------------------------------
+// The walk: which chunks a workgroup works on, and in what order.  A workgroup walks one RUN, a contiguous range of
+// the blob's records; the records are self-describing (rows, CSR range), so their place in the blob is free.
+//   * runs cut by cost: the launch lasts as long as its most expensive run, and chunks are not equally expensive (the
+//     face and partial bricks of a block evaluate fewer elements and write fewer blocks than an interior brick);
+//   * equal chunks adjacent: inside a run the chunks with byte-identical map words follow one another, so that all
+//     but the first of them run with the words their predecessor left in registers.
+// Both are decided here, once; neither changes a sum (every chunk computes what it computed, whoever walks it).
+// ---------------------------------------------------------------------------
+// Modelled cost of one chunk in shader cycles of the K-and-f kernel, from what the builder knows: a regression of the
+// in-kernel stamps' per-run totals (diagnostic build, 66 x 396 x 66 block on an MI355X; 254 equal-count runs in row order
+// and 256 cost-cut grouped runs fitted together, rms residual 5 000 cycles = 0.35 % of a run; tools/gather_run_costs.py,
+// DESIGN.md section 4) on the runs' sums of
+//   element waves   the state phase: waves of 64 element slots
+//   list words      the gather phase: the contribution words walked by the busiest SIMD's block waves (wave slots s, s + 4,
+//                   s + 8 share a SIMD, GatherHeader::wdepth) and by a diagonal wave (ddepth)
+//   blocks          tile writes and row write-out
+//   words           a chunk whose successor cannot keep its map words requests them behind its state phase
+// Rows, elements and blocks of a brick shrink together, so the coefficients predict a chunk (interior brick 13 250, face
+// brick 12 500, 48-row partial brick 10 570 cycles measured; 13 210 / 12 590 / 10 640 modelled) and are NOT phase times.
+// Not measured: G_COST_LONG (a list word beyond the registers is fetched inside the gather phase: DESIGN.md's "one exposed
+// HBM round trip per word"), G_COST_RUN (the prologue: two dependent latencies with nothing to hide behind), and the
+// diagonal words apart from the block words (every chunk of the block has three).
+#ifndef G_WALK_ORDER
+#define G_WALK_ORDER 1                // defaults of FEAHIP_GATHER_ORDER / FEAHIP_GATHER_BALANCE
+#endif
+#ifndef G_WALK_BALANCE
+#define G_WALK_BALANCE 1
+#endif
+#define G_COST_CHUNK 4930
+#define G_COST_ELEM_WAVE 103
+#define G_COST_LIST_WORD 92
+#define G_COST_2_BLOCKS 13
+#define G_COST_WORDS 1123
+#define G_COST_LONG 2000
+#define G_COST_RUN 4000
+int gather_chunk_cost(const GatherHeader &h, bool loads_words)
+{
+  int simd[4] = {0, 0, 0, 0};
+  for (int w = 0; w < G_TASK_THREADS / 64; ++w) simd[w & 3] += (int)((h.wdepth[w >> 2] >> (8 * (w & 3))) & 255u);
+  const int gwords = std::max(std::max(simd[0], simd[1]), std::max(simd[2], simd[3]));
+  const int over = std::max(0, h.depth - FEA_G_REGW) + std::max(0, h.ddepth - FEA_G_REGW);
+  return G_COST_CHUNK + G_COST_ELEM_WAVE * ((h.nelem + 63) / 64) + G_COST_LIST_WORD * (gwords + h.ddepth) + G_COST_2_BLOCKS * h.nb / 2 +
+         G_COST_LONG * over + (loads_words ? G_COST_WORDS : 0);
+}
+
+namespace {
+inline unsigned long long hash_words(unsigned long long h, const void *p, size_t bytes)
+{
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  size_t i = 0;
+  for (; i + 8 <= bytes; i += 8) { unsigned long long v; memcpy(&v, b + i, 8); h = (h ^ v) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
+  for (; i < bytes; ++i) h = (h ^ b[i]) * 0x100000001B3ull;
+  return h;
+}
+// what mark_repeats compares, before the layout: the header's shape and every word section
+bool same_words(const Local &a, const Local &b)
+{
+  return a.h.nelem == b.h.nelem && a.h.noffd == b.h.noffd && a.h.depth == b.h.depth && a.h.nvthr == b.h.nvthr && a.h.vdepth == b.h.vdepth &&
+         a.h.ddepth == b.h.ddepth && a.h.r1 - a.h.r0 == b.h.r1 - b.h.r0 && a.elems == b.elems && a.tpos == b.tpos && a.rows == b.rows &&
+         a.vlist == b.vlist && a.dlist == b.dlist && a.clist == b.clist;
+}
+// kind[p]: chunks with byte-identical map words share a number (a hash finds the candidates, the bytes decide)
+void word_kinds(const std::vector<Local> &loc, std::vector<int> &kind)
+{
+  const int nch = (int)loc.size();
+  std::vector<unsigned long long> hs((size_t)nch);
+  parallel_ranges(nch, 512, [&](int lo, int hi) {
+    for (int p = lo; p < hi; ++p) {
+      const Local &L = loc[p];
+      const int shape[7] = {L.h.nelem, L.h.noffd, L.h.depth, L.h.nvthr, L.h.vdepth, L.h.ddepth, L.h.r1 - L.h.r0};
+      unsigned long long h = hash_words(0xCBF29CE484222325ull, shape, sizeof(shape));
+      h = hash_words(h, L.elems.data(), L.elems.size() * 4); h = hash_words(h, L.tpos.data(), L.tpos.size() * 4);
+      h = hash_words(h, L.rows.data(), L.rows.size() * 2); h = hash_words(h, L.vlist.data(), L.vlist.size() * 2);
+      h = hash_words(h, L.dlist.data(), L.dlist.size() * 2); h = hash_words(h, L.clist.data(), L.clist.size() * 2);
+      hs[p] = h;
+    }
+  });
+  std::vector<int> idx((size_t)nch);
+  for (int p = 0; p < nch; ++p) idx[p] = p;
+  std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return hs[a] < hs[b]; });
+  kind.assign((size_t)nch, -1);
+  int nkinds = 0;
+  for (int i = 0; i < nch;) {
+    int j = i;
+    while (j < nch && hs[idx[j]] == hs[idx[i]]) ++j;
+    std::vector<int> reps;                            // one representative per kind among the chunks of this hash
+    for (int q = i; q < j; ++q) {
+      const int p = idx[q];
+      for (int r : reps)
+        if (same_words(loc[r], loc[p])) { kind[p] = kind[r]; break; }
+      if (kind[p] < 0) { kind[p] = nkinds++; reps.push_back(p); }
+    }
+    i = j;
+  }
+}
+
+struct WalkCost {                                    // the cost of a chunk where it stands in a run
+  const std::vector<int> &base, &kind;
+  bool grouped;                                      // the run's chunks will be grouped by kind (else: row order)
+  std::vector<int> seen;                             // kind -> the last run it was met in
+  WalkCost(const std::vector<int> &b, const std::vector<int> &k, bool g) : base(b), kind(k), grouped(g), seen(b.size(), -1) {}
+  // chunk p joining run `run` that began at chunk s: its predecessor there requests p's words unless it holds them
+  int add(int p, int s, int run)
+  {
+    int c = base[p];
+    if (p > s && (grouped ? seen[kind[p]] != run : kind[p] != kind[p - 1])) c += G_COST_WORDS;
+    seen[kind[p]] = run;
+    return c;
+  }
+};
+
+// runs of at most `cap` modelled cycles, greedily; returns their number
+int fill_runs(const std::vector<int> &base, const std::vector<int> &kind, bool grouped, long long cap, std::vector<int> *start)
+{
+  const int nch = (int)base.size();
+  WalkCost wc(base, kind, grouped);
+  if (start) start->assign(1, 0);
+  int runs = 1, s = 0;
+  long long cur = 0;
+  for (int p = 0; p < nch; ++p) {
+    int c = wc.add(p, s, runs);
+    if (p > s && cur + c > cap) {
+      s = p; ++runs; cur = 0;
+      c = wc.add(p, s, runs);
+      if (start) start->push_back(p);
+    }
+    cur += c;
+  }
+  if (start) start->push_back(nch);
+  return runs;
+}
+
+// the cost of every run of a cut, and of every chunk in it
+long long run_costs(const std::vector<int> &base, const std::vector<int> &kind, bool grouped, const std::vector<int> &start,
+                    std::vector<long long> &rc)
+{
+  WalkCost wc(base, kind, grouped);
+  const int nruns = (int)start.size() - 1;
+  rc.assign((size_t)nruns, 0);
+  long long mx = 0;
+  for (int r = 0; r < nruns; ++r) {
+    for (int p = start[r]; p < start[r + 1]; ++p) rc[r] += wc.add(p, start[r], r);
+    mx = std::max(mx, rc[r]);
+  }
+  return mx;
+}
+
+// at most nruns runs with the smallest largest cost the greedy fill finds (bisection on the cap), then the heaviest
+// runs halved until there are nruns of them: no CU is left without a run while another has two chunks
+void cut_by_cost(const std::vector<int> &base, const std::vector<int> &kind, bool grouped, int nruns, std::vector<int> &start)
+{
+  const int nch = (int)base.size();
+  long long lo = 0, hi = 0;
+  for (int p = 0; p < nch; ++p) { lo = std::max(lo, (long long)base[p] + G_COST_WORDS); hi += base[p] + G_COST_WORDS; }
+  while (lo < hi) {
+    const long long mid = lo + (hi - lo) / 2;
+    if (fill_runs(base, kind, grouped, mid, nullptr) <= nruns) hi = mid; else lo = mid + 1;
+  }
+  fill_runs(base, kind, grouped, hi, &start);
+  std::vector<long long> rc;
+  while ((int)start.size() - 1 < nruns) {
+    run_costs(base, kind, grouped, start, rc);
+    int best = -1;
+    for (int r = 0; r + 1 < (int)start.size(); ++r)
+      if (start[r + 1] - start[r] >= 2 && (best < 0 || rc[r] > rc[best])) best = r;
+    if (best < 0) break;
+    long long half = 0;
+    int m = start[best];
+    while (m < start[best + 1] - 1 && 2 * (half + base[m]) <= rc[best]) half += base[m++];
+    start.insert(start.begin() + best + 1, std::max(m, start[best] + 1));
+  }
+}
+}  // namespace
+
+// how long a launch of these runs lasts, in modelled cycles: one workgroup is resident per CU, workgroup b goes to
+// XCD b mod 8 and walks run (b mod 8) * per + b / 8 (kernels_gather.hip); a CU that finishes a run takes its XCD's next
+long long gather_launch_cost(const std::vector<long long> &run_cost, int ncu)
+{
+  const int nruns = (int)run_cost.size(), per = (((nruns + 7) & ~7) + 7) >> 3, cus = std::max(1, ncu / 8);
+  long long span = 0;
+  for (int x = 0; x < 8; ++x) {
+    std::vector<long long> busy((size_t)cus, 0);
+    for (int j = 0; j < per && x * per + j < nruns; ++j) {
+      auto cu = std::min_element(busy.begin(), busy.end());
+      *cu += G_COST_RUN + run_cost[(size_t)x * per + j];
+    }
+    span = std::max(span, *std::max_element(busy.begin(), busy.end()));
+  }
+  return span;
+}
+
+namespace {
+int env_int(const char *name, int dflt) { const char *e = getenv(name); return e && *e ? atoi(e) : dflt; }
+
+// out.walk, out.run_start and out.cost from the chunks' records (before the layout)
+void plan_walk(const std::vector<Local> &loc, int ncu, HostGather &out)
+{
+  const int nch = (int)loc.size();
+  const bool grouped = env_int("FEAHIP_GATHER_ORDER", G_WALK_ORDER) != 0, balanced = env_int("FEAHIP_GATHER_BALANCE", G_WALK_BALANCE) != 0;
+  const int run_fixed = std::max(0, env_int("FEAHIP_GATHER_RUN", 0));        // a fixed run length (tuning, tests)
+  const int runs_fixed = std::max(0, env_int("FEAHIP_GATHER_NRUNS", 0));     // a fixed number of cost-balanced runs (tests)
+  if (ncu <= 0) ncu = 256;
+  std::vector<int> base((size_t)nch), kind;
+  for (int p = 0; p < nch; ++p) base[p] = gather_chunk_cost(loc[p].h, false);
+  word_kinds(loc, kind);
+  std::vector<int> &start = out.run_start;
+  auto equal_runs = [&](int rl, std::vector<int> &st) {
+    st.clear();
+    for (int c = 0; c < nch; c += rl) st.push_back(c);
+    st.push_back(nch);
+  };
+  std::vector<long long> rc;
+  if (run_fixed) equal_runs(run_fixed, start);
+  else if (runs_fixed) cut_by_cost(base, kind, grouped, std::min(runs_fixed, nch), start);
+  else if (FEA_G_BIG != 1) equal_runs(16, start);
+  else {
+    // One workgroup is resident per CU: with k runs per CU a launch lasts as long as the CU with the most work.  Two runs
+    // per CU leave the scheduler something to even out, one run per CU saves a round where the chunks are few (a rank
+    // of eight: 14.0 chunks per CU): whichever of k = 1, 2 predicts the shorter launch is taken.  Without balancing
+    // the runs are cut by count, ceil(chunks / (k CUs)) each, and the launch is counted in chunks.
+    long long best = -1;
+    std::vector<int> st;
+    for (int k = 2; k >= 1; --k) {
+      long long cost;
+      if (balanced) {
+        cut_by_cost(base, kind, grouped, std::min(k * ncu, nch), st);
+        run_costs(base, kind, grouped, st, rc);
+        cost = gather_launch_cost(rc, ncu);
+      } else {
+        const int rl = std::max(1, (nch + k * ncu - 1) / (k * ncu)), nr = (nch + rl - 1) / rl;
+        cost = (long long)((nr + ncu - 1) / ncu) * rl;
+        equal_runs(rl, st);
+      }
+      if (best < 0 || cost < best) { best = cost; start = st; }
+    }
+  }
+  // inside a run: the kinds in order of first appearance, row order inside a kind
+  out.walk.resize((size_t)nch);
+  for (int p = 0; p < nch; ++p) out.walk[p] = p;
+  if (grouped) {
+    std::vector<int> first((size_t)nch, -1);          // kind -> where it first appeared in the current run
+    for (size_t r = 0; r + 1 < start.size(); ++r) {
+      for (int p = start[r]; p < start[r + 1]; ++p)
+        if (first[kind[p]] < start[r]) first[kind[p]] = p;
+      std::stable_sort(out.walk.begin() + start[r], out.walk.begin() + start[r + 1], [&](int a, int b) { return first[kind[a]] < first[kind[b]]; });
+    }
+  }
+  out.cost.resize((size_t)nch);
+  for (size_t r = 0; r + 1 < start.size(); ++r)
+    for (int i = start[r]; i < start[r + 1]; ++i)
+      out.cost[i] = gather_chunk_cost(loc[out.walk[i]].h, i > start[r] && kind[out.walk[i]] != kind[out.walk[i - 1]]);
+}
+}  // namespace
+
 void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int row_lo, int row_hi, HostGather &out,
-                       const uint8_t *elem_mat)
+                       const uint8_t *elem_mat, int ncu)
 {
   (void)E;
-  out.ok = false; out.nchunks = 0; out.blob.clear(); out.first_row.clear();
+  out.ok = false; out.nchunks = 0; out.blob.clear(); out.first_row.clear(); out.walk.clear(); out.run_start.clear(); out.cost.clear();
   if (row_lo < 0 || row_hi > N || row_lo >= row_hi) return;
   if (!partition(N, conn, hp, row_lo, row_hi, out.first_row)) return;
   const int nch = (int)out.first_row.size() - 1;
@@ -529,7 +785,8 @@ void build_host_gather(int N, int E, const int *conn, const HostPattern &hp, int
   });
   for (int p = 0; p < nch; ++p)
     if (bad[p]) return;
-  if (!lay_out(loc, elem_mat != nullptr, out)) return;
+  plan_walk(loc, ncu, out);
+  if (!lay_out(loc, out.walk, elem_mat != nullptr, out)) return;
   mark_repeats(out, nch);
   out.nchunks = nch;
   out.total_evals = 0;
@@ -760,6 +1017,35 @@ extern "C" int feahip_host_gather_chunks(int n_nodes, int n_elems, const int *el
   return hg.nchunks;
 }
 
+// Host-only (no device): the walk of the 4-node gather maps (include/fea_hip.h)
+extern "C" int feahip_host_gather_walk(int n_nodes, int n_elems, const int *elements, int row_lo, int row_hi, int ncu, long long *info,
+                                       int capacity, int *walk, int *run_start, int *cost, long long blob_capacity, unsigned char *blob)
+{
+  if (!elements || !info || n_nodes <= 0 || n_elems <= 0 || capacity < 0 || blob_capacity < 0) return FEAHIP_EINVAL;
+  HostPattern hp;
+  std::string err;
+  int rc = build_host_pattern(n_nodes, n_elems, 4, elements, hp, err);
+  if (rc) return rc;
+  if (row_hi <= 0) { row_lo = 0; row_hi = n_nodes; }
+  HostGather hg;
+  build_host_gather(n_nodes, n_elems, elements, hp, row_lo, row_hi, hg, nullptr, ncu);
+  if (!hg.ok) return FEAHIP_EINVAL;
+  const int nruns = (int)hg.run_start.size() - 1;
+  std::vector<long long> rcost((size_t)nruns, 0);
+  for (int r = 0; r < nruns; ++r)
+    for (int i = hg.run_start[r]; i < hg.run_start[r + 1]; ++i) rcost[r] += hg.cost[i];
+  info[0] = hg.nchunks; info[1] = nruns; info[2] = hg.lay.stride; info[3] = hg.lay.o_elems;
+  info[4] = hg.lay.o_emat ? hg.lay.o_emat : hg.lay.stride; info[5] = (long long)hg.blob.size(); info[6] = hg.same_as_previous;
+  info[7] = gather_launch_cost(rcost, ncu > 0 ? ncu : 256);
+  if (capacity >= hg.nchunks && walk && run_start && cost) {
+    std::copy(hg.walk.begin(), hg.walk.end(), walk);
+    std::copy(hg.run_start.begin(), hg.run_start.end(), run_start);
+    std::copy(hg.cost.begin(), hg.cost.end(), cost);
+  }
+  if (blob && blob_capacity >= (long long)hg.blob.size()) memcpy(blob, hg.blob.data(), hg.blob.size());
+  return hg.nchunks;
+}
+
 #ifdef FEAHIP_DEBUG
 // diagnostic build only, host only: one chunk's map record and the layout, for the LDS bank model (dbg/lds_model.py)
 extern "C" int feahip_debug_gather_record_host(int n_nodes, int n_elems, const int *elements, int chunk, int *layout_ints,
@@ -778,7 +1064,9 @@ extern "C" int feahip_debug_gather_record_host(int n_nodes, int n_elems, const i
   if (chunk < 0) chunk = hg.nchunks / 2;
   memcpy(layout_ints, &hg.lay, sizeof(GatherLayout));
   if (nchunks) *nchunks = hg.nchunks;
-  if (record) memcpy(record, hg.blob.data() + (size_t)chunk * hg.lay.stride, hg.lay.stride);
+  if (chunk >= hg.nchunks) return FEAHIP_EINVAL;
+  const size_t at = (size_t)(std::find(hg.walk.begin(), hg.walk.end(), chunk) - hg.walk.begin());   // chunk: in row order
+  if (record) memcpy(record, hg.blob.data() + at * hg.lay.stride, hg.lay.stride);
   return (int)(sizeof(GatherLayout) / sizeof(int));
 }
 #endif

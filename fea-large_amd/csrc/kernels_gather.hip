@@ -47,7 +47,7 @@
 // was: no further load, register or LDS byte.
 template <bool DOK, bool DOF, bool NH, bool HET>
 __global__ __launch_bounds__(FEA_G_THREADS, FEA_G_BIG ? 4 : 3)
-void k_assemble_gather(GatherArgs A, int run_len)
+void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nruns)
 {
   extern __shared__ double2 g_smem[];
   double2 *sC = g_smem;                                       // per node slot 3 x 16 bytes: (x0,x1) (x2,X0) (X1,X2)
@@ -58,13 +58,15 @@ void k_assemble_gather(GatherArgs A, int run_len)
   const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), real0 = __builtin_amdgcn_s_memrealtime();
 #endif
   // XCD-aware order: workgroups b and b+8 share an L2; each XCD gets a contiguous eighth of the runs so that
-  // neighbouring chunks re-read each other's halo coordinates from the same L2 (speed only)
-  const int nruns = (A.nchunks + run_len - 1) / run_len;
+  // neighbouring chunks re-read each other's halo coordinates from the same L2 (speed only).  The records of a run are
+  // consecutive in the maps; where the runs start is the host's table (gather.cpp cuts them by cost), read once, here,
+  // before the first prefetch: nothing in the loop waits for it
   const int per = ((int)gridDim.x + 7) >> 3;
   const int ridx = ((int)blockIdx.x & 7) * per + ((int)blockIdx.x >> 3);
   if (ridx >= nruns) return;
-  int chunk = ridx * run_len;
-  const int cend = min(A.nchunks, chunk + run_len);
+  int chunk = run_start[ridx];
+  const int cend = run_start[ridx + 1];
+  if (chunk >= cend) return;                                  // (the host cuts no empty run)
   constexpr int REC = DOK ? GREC : GREC_F;
   const size_t stride = (size_t)A.lay.stride;
   const unsigned char *rec = A.maps + (size_t)(A.chunk0 + chunk) * stride;
@@ -340,6 +342,15 @@ void k_assemble_gather(GatherArgs A, int run_len)
 #endif
 }
 
+// compute units of a device: one workgroup of the gather kernel is resident on each
+static int device_cus(int device)
+{
+  static int ncu_of[64];
+  int &ncu = ncu_of[device & 63];
+  if (ncu <= 0) { hipDeviceProp_t p; ncu = (hipGetDeviceProperties(&p, device) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
+  return ncu;
+}
+
 int ensure_gather(feahip_ctx *c)
 {
   GatherMaps &g = c->gather;
@@ -351,10 +362,17 @@ int ensure_gather(feahip_ctx *c)
   HostGather hg;
   // a context with a material table: the records carry the material id of every element slot (feahip_set_materials
   // releases the maps, so that they are built again with the ids it was given)
-  build_host_gather(c->N, c->E, c->h_conn.data(), *c->h_pat, c->row0, c->row1, hg, c->n_materials ? c->h_elem_mat.data() : nullptr);
+  build_host_gather(c->N, c->E, c->h_conn.data(), *c->h_pat, c->row0, c->row1, hg, c->n_materials ? c->h_elem_mat.data() : nullptr,
+                    device_cus(c->device));
   if (!hg.ok) { g.record(MapOutcome::failed, c->row0, c->row1); return FEAHIP_OK; }   // this row range only: another shard of the same context may fit
   FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_maps, hg.blob.size() ? hg.blob.size() : 1));
   FEA_HIP_CHECK(c, hipMemcpy(g.d_maps, hg.blob.data(), hg.blob.size(), hipMemcpyHostToDevice));
+  // the runs of the walk: the records are in walk order already, the kernel needs where the runs start
+  g.nruns = (int)hg.run_start.size() - 1;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&g.d_run_start, sizeof(int) * hg.run_start.size()));
+  FEA_HIP_CHECK(c, hipMemcpy(g.d_run_start, hg.run_start.data(), sizeof(int) * hg.run_start.size(), hipMemcpyHostToDevice));
+  g.record_of.assign((size_t)hg.nchunks, 0);
+  for (int i = 0; i < hg.nchunks; ++i) g.record_of[hg.walk[i]] = i;
   g.lay = hg.lay;
   g.nchunks = hg.nchunks;
   g.bytes = (long long)hg.blob.size();
@@ -372,8 +390,9 @@ extern "C" int feahip_debug_gather_record(feahip_ctx *c, int chunk, int *layout_
   const GatherMaps &g = c->gather;
   if (rc || !g.built()) return FEAHIP_ESTATE;
   if (chunk < 0) chunk = g.nchunks / 2;
+  if (chunk >= g.nchunks) return FEAHIP_EINVAL;
   memcpy(layout_ints, &g.lay, sizeof(GatherLayout));
-  if (record) (void)hipMemcpy(record, g.d_maps + (size_t)chunk * g.lay.stride, g.lay.stride, hipMemcpyDeviceToHost);
+  if (record) (void)hipMemcpy(record, g.d_maps + (size_t)g.record_of[chunk] * g.lay.stride, g.lay.stride, hipMemcpyDeviceToHost);
   return (int)(sizeof(GatherLayout) / sizeof(int));
 }
 #endif
@@ -401,27 +420,8 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
     A.stamps = d_stamps;
   }
 #endif
-  // chunks per workgroup run: one workgroup is resident per CU, so the runs are cut to give every CU the same number of
-  // them, two per CU (FEAHIP_GATHER_RUN: a fixed run length instead; tuning only, results unchanged)
-  static int run_env = -1;
-  if (run_env < 0) { const char *e = getenv("FEAHIP_GATHER_RUN"); run_env = e && atoi(e) > 0 ? atoi(e) : 0; }
-  static int ncu_of[64];
-  int &ncu = ncu_of[c->device & 63];
-  if (ncu <= 0) { hipDeviceProp_t p; ncu = (hipGetDeviceProperties(&p, c->device) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
-  // One workgroup is resident per CU: with k runs per CU a launch lasts ceil(runs / CUs) rounds of run_len chunks.  Two runs
-  // per CU even out the lighter boundary chunks on a whole mesh (28 682 chunks: 2 x 57); a rank of eight has 3 585 chunks
-  // and 2 x 8 = 16 chunk times where one run of 15 does -- whichever of k = 1, 2 gives the shorter launch is taken.
-  int run_len = 16;
-  if (run_env) run_len = run_env;
-  else if (FEA_G_BIG == 1) {
-    long best = -1;
-    for (int k = 2; k >= 1; --k) {
-      const int rl = std::max(1, (g.nchunks + k * ncu - 1) / (k * ncu)), nr = (g.nchunks + rl - 1) / rl;
-      const long cost = (long)((nr + ncu - 1) / ncu) * rl;
-      if (best < 0 || cost < best) { best = cost; run_len = rl; }
-    }
-  }
-  const int nruns = (g.nchunks + run_len - 1) / run_len;
+  // the runs were cut when the maps were built (gather.cpp: by cost, or by count, or FEAHIP_GATHER_RUN chunks each)
+  const int nruns = g.nruns;
   const dim3 grid((nruns + 7) & ~7), blk(FEA_G_THREADS);
   // LDS: coordinates (48 bytes per node slot) | element records, later the K tile (+1 double of alignment slack) and the residual partials
   const int regK = std::max(A.lay.max_elems * GREC, ((A.lay.max_tile * 9 + 3) & ~1) + 3 * FEA_G_THREADS);
@@ -444,7 +444,7 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
     else {
     const int lds = K ? ldsK : ldsF;
     FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M, H>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((k_assemble_gather<K, F, M, H>), grid, blk, lds, c->stream, A, run_len);
+    hipLaunchKernelGGL((k_assemble_gather<K, F, M, H>), grid, blk, lds, c->stream, A, g.d_run_start, nruns);
     return FEAHIP_OK;
     }
   };
@@ -467,8 +467,16 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
       for (int i = 0; i < nruns; ++i)
         for (int w = 0; w < NW; ++w)
           for (int q = 0; q < 8; ++q) sum[w][q] += (double)hst[((size_t)i * NW + w) * 8 + q];
-      fprintf(stderr, "[gather stamps] in-kernel clock %.0f MHz (s_memtime / s_memrealtime x 100 MHz over a run), run = %.0f shader cycles for %d chunks\n",
-              sum[0][7] > 0 ? 100.0 * sum[0][6] / sum[0][7] : 0.0, sum[0][6] / nruns, run_len);
+      fprintf(stderr, "[gather stamps] in-kernel clock %.0f MHz (s_memtime / s_memrealtime x 100 MHz over a run), run = %.0f shader cycles, %d runs of %d chunks\n",
+              sum[0][7] > 0 ? 100.0 * sum[0][6] / sum[0][7] : 0.0, sum[0][6] / nruns, nruns, g.nchunks);
+      if (const char *path = getenv("FEAHIP_GATHER_STAMPS_FILE")) {       // the lines of all runs, [run][wave][8] (tools/gather_run_costs.py)
+        if (FILE *fo = fopen(path, "wb")) {
+          const long long head[2] = {nruns, NW};
+          fwrite(head, sizeof(head), 1, fo);
+          fwrite(hst.data(), sizeof(unsigned long long), (size_t)nruns * NW * 8, fo);
+          fclose(fo);
+        }
+      }
       for (int w = 0; w < NW; w += (NW > 4 ? 5 : 1))
         fprintf(stderr, "[gather stamps K=%d F=%d wave %d, per chunk] state %.0f  gather %.0f  barrier B %.0f  tile writes %.0f  wait for the prefetched words + coordinates + barrier C %.0f  rows out (+ barrier D) %.0f cycles\n",
                 (int)doK, (int)doF, w, sum[w][0] / g.nchunks, sum[w][1] / g.nchunks, sum[w][2] / g.nchunks, sum[w][3] / g.nchunks,

@@ -84,6 +84,8 @@ ABI = {
     "feahip_host_gather_stats": [C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong), _ip],
     "feahip_host_gather10_shape": [C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong)],
     "feahip_host_gather_chunks": [C.c_int, C.c_int, _ip, C.c_int, _ip],
+    "feahip_host_gather_walk": [C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, _ip, _ip, _ip,
+                                C.c_longlong, C.c_void_p],
     "feahip_host_assembly_digest": [C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), _ip],
     "feahip_assembly_in_use": [C.c_void_p, _ip],
     "feahip_node_numbering": [C.c_void_p, _ip],
@@ -1096,8 +1098,32 @@ def host_gather_stats(elements, n_nodes):
             "chunks_with_long_block_lists": int(st[6]), "chunks_with_long_diagonal_lists": int(st[7])}, hist
 
 
+def host_gather_walk(elements, n_nodes, rows=None, ncu=0):
+    """The walk of the 4-node GATHER maps of a mesh in the numbering given (host only), under the FEAHIP_GATHER_ORDER /
+    _BALANCE / _RUN / _NRUNS settings of the environment; rows = (first, end) for a rank's rows; ncu: the compute units
+    the runs are cut for (0: 256).  dict: walk[i] = the chunk (in row order) whose record is the i-th of the maps,
+    run_start[nruns + 1], cost[i] = modelled cycles of record i, blob = the map records (uint8, `stride` bytes each; the
+    map words of a record are its bytes [words_begin, words_end)), launch_cost = modelled cycles of a launch."""
+    el = np.ascontiguousarray(elements, dtype=np.int32)
+    lib = load_library()
+    r0, r1 = rows if rows is not None else (0, 0)
+    info = np.zeros(8, dtype=np.int64)
+    ip = info.ctypes.data_as(C.POINTER(C.c_longlong))
+    n = lib.feahip_host_gather_walk(n_nodes, el.shape[0], _i(el), r0, r1, ncu, ip, 0, None, None, None, 0, None)
+    if n < 0:
+        raise FeaHipError(f"feahip_host_gather_walk failed ({n})")
+    walk, start, cost = np.zeros(n, dtype=np.int32), np.zeros(n + 1, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    blob = np.zeros(int(info[5]), dtype=np.uint8)
+    if lib.feahip_host_gather_walk(n_nodes, el.shape[0], _i(el), r0, r1, ncu, ip, n, _i(walk), _i(start), _i(cost), len(blob),
+                                   blob.ctypes.data_as(C.c_void_p)) != n:
+        raise FeaHipError("feahip_host_gather_walk: chunk count changed")
+    return {"chunks": n, "runs": int(info[1]), "stride": int(info[2]), "words_begin": int(info[3]), "words_end": int(info[4]),
+            "chunks_with_predecessors_words": int(info[6]), "launch_cost": int(info[7]), "walk": walk,
+            "run_start": start[:int(info[1]) + 1].copy(), "cost": cost, "blob": blob}
+
+
 def host_gather_chunks(elements, n_nodes):
-    """Per chunk of the 4-node GATHER maps, in chunk order (host only): int array of flags -- bit 0 the next chunk
+    """Per chunk of the 4-node GATHER maps, in walk order (host only): int array of flags -- bit 0 the next chunk
     repeats this chunk's map words, bit 1 a block list, bit 2 a diagonal list longer than the registers hold."""
     el = np.ascontiguousarray(elements, dtype=np.int32)
     lib = load_library()

@@ -693,12 +693,31 @@ int feahip_host_gather_stats(int n_nodes, int n_elems, int npe, const int *eleme
                              long long *stats, int *rows_hist);
 
 /* Host-only (no device): the chunks of the 4-node GATHER maps of a mesh of
- * linear tetrahedra, in chunk order, in the numbering given (as
+ * linear tetrahedra, in walk order, in the numbering given (as
  * feahip_host_gather_stats).  flags[capacity] (may be null when capacity is
  * 0): bit 0 the next chunk's map words equal this chunk's (the kernel keeps
  * them in registers), bit 1 a block list, bit 2 a diagonal list longer than
  * a thread keeps in registers.  Returns the number of chunks, or negative.   */
 int feahip_host_gather_chunks(int n_nodes, int n_elems, const int *elements, int capacity, int *flags);
+
+/* Host-only (no device): the WALK of the 4-node GATHER maps of the rows
+ * [row_lo, row_hi) (row_hi <= 0: all rows) of a mesh of linear tetrahedra in
+ * the numbering given -- the order of the chunk records in the maps and the
+ * runs of consecutive records one workgroup walks, cut for ncu compute units
+ * (0: 256).  Inside a run the chunks with byte-identical map words follow one
+ * another (FEAHIP_GATHER_ORDER=0: row order); the runs are cut to near-equal
+ * modelled cost (FEAHIP_GATHER_BALANCE=0: to equal chunk counts;
+ * FEAHIP_GATHER_RUN=n: n chunks each; FEAHIP_GATHER_NRUNS=n: n runs by cost).
+ * info[8] = {chunks, runs, bytes per record, first and end byte of a record's
+ * map words, bytes of all records, chunks whose predecessor holds their map
+ * words, modelled cycles of a launch}.  With capacity >= chunks: walk[i] =
+ * the chunk (in row order) whose record is the i-th, run_start[runs + 1],
+ * cost[i] = modelled cycles of record i where it stands.  With blob_capacity
+ * >= info[5]: the records.  Any of the arrays may be null.  Returns the number
+ * of chunks, or negative.                                                    */
+int feahip_host_gather_walk(int n_nodes, int n_elems, const int *elements, int row_lo, int row_hi, int ncu,
+                            long long *info, int capacity, int *walk, int *run_start, int *cost,
+                            long long blob_capacity, unsigned char *blob);
 
 /* Host-only (no device): the edges the GATHER maps of 10-node tetrahedra or
  * 8-node bricks reach, for a mesh in the numbering it is given (library ids:
