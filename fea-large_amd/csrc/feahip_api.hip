@@ -1274,6 +1274,80 @@ extern "C" int feahip_spmm_km(feahip_ctx *c, const double *x8, double *y8, doubl
   return FEAHIP_OK;
 }
 
+extern "C" int feahip_solve_modes_locked(feahip_ctx *c, int n_modes, double shift, double tol, int max_iter, double *lambda,
+                                         double *resid, int *iters, int *sweeps)
+{
+  CTX_GUARD(c);
+  if (iters) *iters = 0;
+  if (sweeps) *sweeps = 0;
+  if (n_modes < 1 || n_modes > FEA_MODAL_MAX_LOCKED) { c->err = "solve_modes_locked: n_modes must be in [1, 64]"; return FEAHIP_EINVAL; }
+  if (!(shift >= 0.0) || !std::isfinite(shift)) { c->err = "solve_modes_locked: shift must be finite and not negative"; return FEAHIP_EINVAL; }
+  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_modes_locked: tolerance must be positive"; return FEAHIP_EINVAL; }
+  if (max_iter < 0) { c->err = "solve_modes_locked: max_iterations must not be negative"; return FEAHIP_EINVAL; }
+  if (!lambda) { c->err = "solve_modes_locked: null lambda"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = modal_ready(c, "solve_modes_locked"))) return rc;
+  return modal_solve_locked(c, n_modes, shift, tol, max_iter, lambda, resid, iters, sweeps);
+}
+
+extern "C" int feahip_get_locked_count(feahip_ctx *c, int *count)
+{
+  CTX_GUARD_NOK(c);
+  if (!count) return FEAHIP_EINVAL;
+  if (!c->modal.have_locked) { c->err = "get_locked_count: no locked modes held (feahip_solve_modes_locked first)"; return FEAHIP_ESTATE; }
+  *count = c->modal.n_locked;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_locked_modes(feahip_ctx *c, int first, int count, double *phi)
+{
+  CTX_GUARD_NOK(c);
+  if (!c->modal.have_locked) { c->err = "get_locked_modes: no locked modes held (feahip_solve_modes_locked first)"; return FEAHIP_ESTATE; }
+  if (first < 0 || count < 0 || first + count > c->modal.n_locked) {
+    c->err = "get_locked_modes: modes [first, first + count) outside the " + std::to_string(c->modal.n_locked) + " locked";
+    return FEAHIP_EINVAL;
+  }
+  if (!phi) { c->err = "get_locked_modes: null phi"; return FEAHIP_EINVAL; }
+  std::vector<double> tmp((size_t)c->ndof);
+  for (int k = 0; k < count; ++k) {
+    const int rc = modal_get_locked(c, first + k, tmp.data());
+    if (rc) return rc;
+    double *out = phi + (size_t)k * c->ndof;
+    for (int a = 0; a < c->N; ++a)
+      for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_modal_deflate(feahip_ctx *c, int n_locked, const double *q, const double *x8, double *out8)
+{
+  CTX_GUARD(c);
+  if (!q || !x8 || !out8) return FEAHIP_EINVAL;
+  if (n_locked < 1 || n_locked > FEA_MODAL_MAX_LOCKED) { c->err = "modal_deflate: n_locked must be in [1, 64]"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = modal_ready(c, "modal_deflate"))) return rc;
+  if (!c->k_valid) { c->err = "modal_deflate: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+  if ((rc = ensure_modal(c)) || (rc = ensure_locked(c, n_locked))) return rc;
+  c->modal.have = false;                                             // the block vectors and the store are scratch here
+  const size_t n = (size_t)c->ndof, n8 = n * FEA_MODAL_COLS;
+  double *v = c->modal.d_v;                                          // W <- the host layout, X <- a panel of q, MX <- mask(M X)
+  for (int p = 0; p * FEA_MODAL_COLS < n_locked; ++p) {
+    FEA_HIP_CHECK(c, hipMemsetAsync(v + n8, 0, sizeof(double) * n8, c->stream));
+    for (int k = 0; k < FEA_MODAL_COLS && p * FEA_MODAL_COLS + k < n_locked; ++k)
+      if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, q + ((size_t)p * FEA_MODAL_COLS + k) * n))) return rc;
+    if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, v, v + 3 * n8, v + 6 * n8))) return rc;
+    FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
+    FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 1, p), v + 6 * n8, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
+  }
+  for (int k = 0; k < FEA_MODAL_COLS; ++k)
+    if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, x8 + (size_t)k * n))) return rc;
+  if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_deflate(c, v, n_locked))) return rc;
+  if ((rc = launch_modal_pack(c, v, v + n8, 1))) return rc;
+  for (int k = 0; k < FEA_MODAL_COLS; ++k)
+    if ((rc = get_node_vec(c, v + n8 + (size_t)k * n, out8 + (size_t)k * n))) return rc;
+  return FEAHIP_OK;
+}
+
 extern "C" int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const double *gram_k, double *theta, double *coef)
 {
   if (!gram_m || !gram_k || !theta || !coef || (n_dirs != 8 && n_dirs != 16 && n_dirs != 24)) return FEAHIP_EINVAL;
@@ -1632,6 +1706,12 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     int rk;
     if ((rk = solve2_refused(c, who.c_str())) || (rk = mass_ensure(c, "time_kernel")) || (rk = time_modal_prepare(c))) return rk;
   }
+  if (what == 16 || what == 17) {
+    const std::string who = "time_kernel(" + std::to_string(what) + ")";
+    if (!c->mass.set || c->mass.stale) { c->err = who + ": no mass on this context (feahip_set_mass)"; return FEAHIP_EINVAL; }
+    int rk;
+    if ((rk = solve2_refused(c, who.c_str())) || (rk = mass_ensure(c, "time_kernel")) || (rk = time_deflate_prepare(c))) return rk;
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   return time_enqueued(c, warmup, iters, avg_ms, [&](int) -> int {
@@ -1648,6 +1728,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 11: return launch_gershgorin(c);
     case 12: return launch_results(c, -1, c->d_scal + 8);
     case 13: case 14: case 15: return time_modal_kernel(c, what);
+    case 16: case 17: return time_deflate_kernel(c, what);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

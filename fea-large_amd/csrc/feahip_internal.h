@@ -449,7 +449,15 @@ struct ModalState {
   double theta[FEA_MODAL_COLS] = {0, 0, 0, 0, 0, 0, 0, 0};
   int n_free = 0;                      // dofs that are not prescribed
   bool have = false;                   // X holds the modes of a finished solve (feahip_get_modes, warm restarts)
-  void release() { dev_free({d_v, d_part, d_small}); *this = ModalState(); }
+  // the locked store of feahip_solve_modes_locked: nothing of it exists until that entry (or one of its hooks) is called
+  double *d_lock = nullptr;            // [2][lock_panels][3N][8]: the panels of Q, then those of MQ = mask(M Q)
+  double *d_lpart = nullptr;           // [lock_panels * 64][FEA_RED_BLOCKS] per-workgroup partial sums of MQ' W
+  double *d_lcoef = nullptr;           // [lock_panels * 64] the coefficients MQ' W (they never visit the host)
+  int lock_panels = 0;                 // panels allocated (once, for the n_modes asked; a larger request reallocates)
+  int n_locked = 0;                    // modes in the store
+  int lock_order[64] = {0};            // mode j of the ascending lambda is column lock_order[j] of the store
+  bool have_locked = false;            // the store holds the modes of a locked solve (feahip_get_locked_modes)
+  void release() { dev_free({d_v, d_part, d_small, d_lock, d_lpart, d_lcoef}); *this = ModalState(); }
 };
 
 struct feahip_ctx {
@@ -650,6 +658,15 @@ int launch_modal_pack(feahip_ctx *c, const double *d_in, double *d_out, int unpa
 int time_modal_prepare(feahip_ctx *c);                                  // the nine vectors filled for feahip_time_kernel 13-15
 int time_modal_kernel(feahip_ctx *c, int what);
 int modal_ritz(int ns, const double *GM, const double *GK, int m, double *theta, double *C);   // host only
+// the same pencil with a shift, in sweeps of the eight-column block with hard locking: up to FEA_MODAL_MAX_LOCKED modes
+int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int max_it, double *lambda, double *resid,
+                       int *iters, int *sweeps);
+int modal_get_locked(feahip_ctx *c, int mode, double *h_lib);           // mode of the locked store, [3N] in library ids
+int ensure_locked(feahip_ctx *c, int n_modes);                          // the store for n_modes, zeroed and empty
+double *locked_panel(feahip_ctx *c, int mq, int panel);                 // panel of Q (mq = 0) or of MQ (1), [3N][8]
+int launch_deflate(feahip_ctx *c, double *d_w8, int n_locked);          // W -= Q (MQ' W) against the first n_locked modes
+int time_deflate_prepare(feahip_ctx *c);                                // eight panels of hash for feahip_time_kernel 16-17
+int time_deflate_kernel(feahip_ctx *c, int what);
 // kernels_mass.hip -- consistent mass, body force and the vector kernels of the Newmark steps
 int mass_set(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights, const double *forms,
              const double *dforms);

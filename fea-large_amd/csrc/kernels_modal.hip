@@ -18,6 +18,16 @@
 //                     matrices; every 20 steps and at return KX and MX are recomputed from X.
 // Nothing here exists, and nothing is launched, on a context that never calls feahip_solve_modes (or the hooks
 // feahip_spmm_km, feahip_time_kernel 13-15).
+//
+// More than eight modes, and bodies with zero-energy modes (feahip_solve_modes_locked, modal_solve_locked below): the
+// same step in sweeps of the eight-column block on the pencil (K + shift M, M).  Converged leading columns are locked
+// into a store of up to 64 modes Q with their products MQ = mask(M Q), panels of eight columns in the block-vector
+// layout; the block is kept in the M-complement of the store by  W <- W - Q (MQ' W):
+//   k_modal_deflate_gram    the L x 8 coefficients MQ' W: one read of W and of every MQ panel in use, fixed grid
+//   k_modal_deflate_reduce  their per-workgroup partial sums in a fixed order; the coefficients stay on the device
+//   k_modal_deflate_apply   W -= Q C: one read of W and of every Q panel in use, one write of W
+// The store exists on a context that called feahip_solve_modes_locked (or feahip_modal_deflate, feahip_time_kernel
+// 16-17) and on no other.
 #include "feahip_internal.h"
 #include "reduce_device.h"
 #include <cmath>
@@ -301,6 +311,129 @@ __global__ void k_modal_pack(size_t n, const double *__restrict__ in, double *__
   if (e >= n * 8) return;
   const size_t k = e >> 3, col = e & 7;
   if (unpack) out8[col * n + k] = in[e]; else out8[e] = in[col * n + k];
+}
+
+// ------------------------------------------------------------------------
+// The locked store (feahip_solve_modes_locked).  Q and MQ: npanels panels [3N][8] each, pstride doubles apart; the
+// columns of the last panel that hold no mode are zero.
+//
+// C_p = MQ_p' W for every panel p < npanels in one pass: k_modal_gram's staging -- a workgroup stages 32 dofs of W and
+// of every panel in LDS with coalesced loads (W's tile once, not once per panel); wave w takes eight of the dofs, lane
+// (a, b) keeps mq_p[a] w[b] for each panel.  The four waves' sums meet in LDS in wave order and go to
+// part[(p 64 + a 8 + b) RB + block].  The reads of a wave are eight consecutive doubles (broadcast over the other
+// index): conflict-free.
+// ------------------------------------------------------------------------
+#define MODAL_PANELS (FEA_MODAL_MAX_LOCKED / MC)
+static_assert(MODAL_PANELS == 8, "the panel loops below are unrolled eight times");
+__global__ __launch_bounds__(256)
+void k_modal_deflate_gram(int ndof, int npanels, const double *__restrict__ W, const double *__restrict__ MQ, size_t pstride,
+                          double *__restrict__ part)
+{
+  __shared__ double sh[(1 + MODAL_PANELS) * 256];      // the tile [1 + 8][32][8] first, the waves' sums [4][8][64] after
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, a = lane >> 3, b = lane & 7;
+  double acc[MODAL_PANELS];
+#pragma unroll
+  for (int p = 0; p < MODAL_PANELS; ++p) acc[p] = 0.0;
+  const int ntiles = (ndof + GRAM_DOFS - 1) / GRAM_DOFS;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const size_t e = (size_t)tile * (GRAM_DOFS * 8) + threadIdx.x;      // element of a block vector
+    const bool in = e < (size_t)ndof * 8;
+    __syncthreads();
+    sh[threadIdx.x] = in ? W[e] : 0.0;
+#pragma unroll
+    for (int p = 0; p < MODAL_PANELS; ++p)
+      if (p < npanels) sh[(1 + p) * 256 + threadIdx.x] = in ? MQ[(size_t)p * pstride + e] : 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      const int row = (wave * 8 + d) * 8;
+      const double w = sh[row + b];
+#pragma unroll
+      for (int p = 0; p < MODAL_PANELS; ++p)
+        if (p < npanels) acc[p] += sh[(1 + p) * 256 + row + a] * w;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < MODAL_PANELS; ++p) sh[(wave * MODAL_PANELS + p) * 64 + lane] = acc[p];
+  __syncthreads();
+  for (int e = threadIdx.x; e < npanels * 64; e += 256)
+    part[(size_t)e * RB + blockIdx.x] = ((sh[e] + sh[512 + e]) + sh[1024 + e]) + sh[1536 + e];
+}
+
+// out[e] = the sum of part[e RB .. e RB + n), one workgroup per coefficient (k_modal_reduce's order)
+__global__ __launch_bounds__(256)
+void k_modal_deflate_reduce(int n, const double *__restrict__ part, double *__restrict__ out)
+{
+  __shared__ double scratch[5];
+  const double v = reduce_partials(part + (size_t)blockIdx.x * RB, n, scratch);
+  if (threadIdx.x == 0) out[blockIdx.x] = v;
+}
+
+// W -= sum_p Q_p C_p: a lane owns one dof, reads its 64 bytes of W once and 64 bytes of every panel in use, and
+// writes W once.  C[p][a][b] (mode a of panel p, column b) is read with uniform addresses, as k_modal_combine reads
+// its coefficients.  Q is zero on the prescribed dofs, so W stays zero there.
+__global__ __launch_bounds__(256)
+void k_modal_deflate_apply(int ndof, int npanels, double *__restrict__ W, const double *__restrict__ Q, size_t pstride,
+                           const double *__restrict__ C)
+{
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndof) return;
+  v2d *Wd = reinterpret_cast<v2d *>(W) + (size_t)d * 4;
+  double w[8];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) { const v2d t = Wd[p]; w[2 * p] = t.x; w[2 * p + 1] = t.y; }
+  for (int p = 0; p < npanels; ++p) {
+    const v2d *Qd = reinterpret_cast<const v2d *>(Q + (size_t)p * pstride) + (size_t)d * 4;
+    double q[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const v2d t = Qd[k]; q[2 * k] = t.x; q[2 * k + 1] = t.y; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w[j] -= q[k] * C[p * 64 + k * 8 + j];
+  }
+#pragma unroll
+  for (int p = 0; p < 4; ++p) Wd[p] = v2d{w[2 * p], w[2 * p + 1]};
+}
+
+// columns [0, count) of X and of MX into the modes [at, at + count) of the store
+__global__ __launch_bounds__(256)
+void k_modal_lock(int ndof, int at, int count, const double *__restrict__ X, const double *__restrict__ MX,
+                  double *__restrict__ Q, double *__restrict__ MQ, size_t pstride)
+{
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndof) return;
+  for (int j = 0; j < count; ++j) {
+    const size_t to = (size_t)((at + j) >> 3) * pstride + (size_t)d * 8 + ((at + j) & 7);
+    Q[to] = X[(size_t)d * 8 + j];
+    MQ[to] = MX[(size_t)d * 8 + j];
+  }
+}
+
+// the next block of a sweep: the columns [drop, 8) of X move to the front; the columns freed are k_modal_hash's values
+// for the column indices id0, id0 + 1, ... (indices no block has used before)
+__global__ __launch_bounds__(256)
+void k_modal_advance(int ndof, int drop, int id0, const uint8_t *__restrict__ mask, double *__restrict__ X)
+{
+  const int d = blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndof) return;
+  double x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = X[(size_t)d * 8 + j];
+  const bool fixed = mask[d] != 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (k == j + drop) v = x[k];
+    if (j + drop >= 8) {
+      uint32_t h = (uint32_t)d * 0x9E3779B1u ^ ((uint32_t)(id0 + j + drop - 8) + 1u) * 0x85EBCA77u;
+      h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+      v = fixed ? 0.0 : (double)h * (1.0 / 2147483648.0) - 1.0;
+    }
+    X[(size_t)d * 8 + j] = v;
+  }
 }
 
 // ------------------------------------------------------------------------
@@ -649,6 +782,226 @@ int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, do
 int modal_get(feahip_ctx *c, int col, double *h_lib /*[3N], library ids*/)
 {
   hipLaunchKernelGGL(k_modal_extract, g256((size_t)c->ndof), dim3(256), 0, c->stream, (size_t)c->ndof, (const double *)mv(c, V_X), col, c->d_q);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  FEA_HIP_CHECK(c, hipMemcpyAsync(h_lib, c->d_q, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+// ---- more than eight modes, and a shift: sweeps of the block with hard locking ------------------------------------------
+int ensure_locked(feahip_ctx *c, int n_modes)
+{
+  ModalState &S = c->modal;
+  const int panels = (n_modes + MC - 1) / MC;
+  const size_t n8 = (size_t)c->ndof * MC;
+  if (panels > S.lock_panels) {
+    FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    dev_free({S.d_lock, S.d_lpart, S.d_lcoef});
+    S.d_lock = S.d_lpart = S.d_lcoef = nullptr; S.lock_panels = 0;
+    FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_lock, sizeof(double) * 2 * panels * n8));
+    FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_lpart, sizeof(double) * (size_t)panels * 64 * RB));
+    FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_lcoef, sizeof(double) * (size_t)panels * 64));
+    S.lock_panels = panels;
+    FEA_HIP_CHECK(c, hipMemsetAsync(S.d_lpart, 0, sizeof(double) * (size_t)panels * 64 * RB, c->stream));
+  }
+  FEA_HIP_CHECK(c, hipMemsetAsync(S.d_lock, 0, sizeof(double) * 2 * S.lock_panels * n8, c->stream));
+  FEA_HIP_CHECK(c, hipMemsetAsync(S.d_lcoef, 0, sizeof(double) * (size_t)S.lock_panels * 64, c->stream));
+  S.n_locked = 0;
+  S.have_locked = false;
+  return FEAHIP_OK;
+}
+
+double *locked_panel(feahip_ctx *c, int mq, int panel)
+{
+  return c->modal.d_lock + ((size_t)(mq ? c->modal.lock_panels : 0) + panel) * c->ndof * MC;
+}
+
+static void enq_deflate_gram(feahip_ctx *c, const double *d_w8, int panels)
+{
+  hipLaunchKernelGGL(k_modal_deflate_gram, dim3(gram_grid(c)), dim3(256), 0, c->stream, c->ndof, panels, d_w8,
+                     (const double *)locked_panel(c, 1, 0), (size_t)c->ndof * MC, c->modal.d_lpart);
+}
+static void enq_deflate_apply(feahip_ctx *c, double *d_w8, int panels)
+{
+  hipLaunchKernelGGL(k_modal_deflate_apply, dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof, panels, d_w8,
+                     (const double *)locked_panel(c, 0, 0), (size_t)c->ndof * MC, (const double *)c->modal.d_lcoef);
+}
+
+// W <- W - Q (MQ' W) against the panels that hold the first n_locked modes: three launches, nothing read back
+int launch_deflate(feahip_ctx *c, double *d_w8, int n_locked)
+{
+  const int panels = (n_locked + MC - 1) / MC;
+  if (panels == 0) return FEAHIP_OK;
+  enq_deflate_gram(c, d_w8, panels);
+  hipLaunchKernelGGL(k_modal_deflate_reduce, dim3(panels * 64), dim3(256), 0, c->stream, gram_grid(c),
+                     (const double *)c->modal.d_lpart, c->modal.d_lcoef);
+  enq_deflate_apply(c, d_w8, panels);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+// hooks of feahip_time_kernel 16 and 17 on W against eight panels of hash; the coefficients are zero, so W stays as it is
+int time_deflate_prepare(feahip_ctx *c)
+{
+  int rc;
+  if ((rc = time_modal_prepare(c)) || (rc = ensure_locked(c, FEA_MODAL_MAX_LOCKED))) return rc;
+  const size_t n8 = (size_t)c->ndof * MC;
+  for (int mq = 0; mq < 2; ++mq)
+    for (int p = 0; p < MODAL_PANELS; ++p)
+      hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, locked_panel(c, mq, p));
+  FEA_HIP_CHECK(c, hipGetLastError());
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+int time_deflate_kernel(feahip_ctx *c, int what)
+{
+  if (what == 16) enq_deflate_gram(c, mv(c, V_W), MODAL_PANELS);
+  else enq_deflate_apply(c, mv(c, V_W), MODAL_PANELS);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
+// The driver.  K_s = K + shift M (masked) is in K's store; the iteration is modal_solve's on the pencil (K_s, M), theta_s
+// = lambda + shift, with W deflated against the store before its products.  A sweep: deflate X, orthonormalise it on its
+// own, iterate until the leading min(6, n_modes - locked) columns pass the stop test on fresh products, lock the leading
+// converged columns, move the others to the front and refill from the hash.  (The small host helpers are modal_solve's,
+// restated: that function is not to change a bit, and is left as it is.)
+int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int max_it, double *lambda, double *resid,
+                       int *iters, int *sweeps)
+{
+  int rc;
+  if ((rc = ensure_modal(c))) return rc;
+  ModalState &S = c->modal;
+  S.have = false;                                                     // the block is scratch here
+  S.have_locked = false;
+  if (S.n_free < n_modes + 3 * MC) {
+    c->err = "solve_modes_locked: " + std::to_string(S.n_free) + " free dofs, fewer than n_modes + 24";
+    return FEAHIP_EINVAL;
+  }
+  if ((rc = ensure_locked(c, n_modes))) return rc;
+  // K(x) + shift M in the order of a Newmark iteration: assemble, add, mask (K and f are another matrix from here on)
+  if ((rc = feahip_create_stiffness(c))) return rc;
+  if (shift > 0.0 && (rc = launch_mass_add(c, shift))) return rc;
+  if ((rc = feahip_apply_prescribed_bc(c, 0.0))) return rc;
+  if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
+  else enq_precond_blockjacobi(c);
+  const size_t n8 = (size_t)c->ndof * MC;
+  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
+  double *theta = S.theta;
+  S.h_C.assign(24 * 16 + MC, 0.0);
+  int locked = 0, it = 0, sweep = 0, next_id = MC;
+  for (int j = 0; j < n_modes; ++j) { lambda[j] = NAN; if (resid) resid[j] = NAN; }
+  auto products_x = [&]() { return launch_spmm_km(c, mv(c, V_X), mv(c, V_KX), mv(c, V_MX)); };
+  auto upload = [&]() -> int {
+    for (int j = 0; j < MC; ++j) S.h_C[24 * 16 + j] = theta[j];
+    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + MODAL_SUMS, S.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
+    return FEAHIP_OK;
+  };
+  auto converged = [&](int want) {                    // the stop test of the leading want columns, in the shifted quantities
+    bool ok = true;
+    for (int j = 0; j < MC; ++j) {
+      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
+      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
+      if (j < want && !(ratio[j] <= tol)) ok = false;
+    }
+    return ok;
+  };
+  auto ritz = [&](int np, int *rank) -> bool {
+    unpack_gram(sums + MODAL_NORMS, np, GM, GK);
+    double Cs[24 * 16];
+    const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
+    if (r < 0) return false;
+    std::fill(S.h_C.begin(), S.h_C.begin() + 24 * 16, 0.0);
+    std::copy(Cs, Cs + 8 * np * 16, S.h_C.begin());
+    *rank = r;
+    return true;
+  };
+  auto done = [&](int code, const std::string &why) {
+    // The store is in the order of locking.  Two eigenvalues that are equal to rounding (a degenerate pair split by the
+    // end of a sweep) can come out of two sweeps in either order, so lambda is sorted once more, stably, and the modes
+    // are read through the same permutation
+    static_assert(sizeof(S.lock_order) / sizeof(int) == FEA_MODAL_MAX_LOCKED, "one entry per mode of the store");
+    double lam[FEA_MODAL_MAX_LOCKED], res[FEA_MODAL_MAX_LOCKED];
+    for (int j = 0; j < locked; ++j) { S.lock_order[j] = j; lam[j] = lambda[j]; res[j] = resid ? resid[j] : 0.0; }
+    std::stable_sort(S.lock_order, S.lock_order + locked, [&](int x, int y) { return lam[x] < lam[y]; });
+    for (int j = 0; j < locked; ++j) { lambda[j] = lam[S.lock_order[j]]; if (resid) resid[j] = res[S.lock_order[j]]; }
+    S.n_locked = locked;
+    S.have_locked = true;                                               // the pairs locked so far stay readable
+    if (iters) *iters = it;
+    if (sweeps) *sweeps = sweep;
+    if (code) c->err = "solve_modes_locked: " + why + " (" + std::to_string(locked) + " of " + std::to_string(n_modes) + " modes locked)";
+    return code;
+  };
+  auto broke = [&]() {
+    return done(FEAHIP_ENOTCONVERGED, "the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes needs a shift)");
+  };
+  auto ritz_on_x = [&]() -> int {
+    int rank = 0;
+    if ((rc = products_x())) return rc;
+    enq_gram(c, 1);
+    if ((rc = read_sums(c, MODAL_NORMS, MODAL_GRAM, sums))) return rc;
+    if (!ritz(1, &rank)) return broke();
+    if ((rc = upload())) return rc;
+    enq_combine(c, 1, 0);
+    return products_x();
+  };
+  auto fresh_norms = [&]() -> int {
+    if ((rc = enq_residual(c, false))) return rc;
+    return read_sums(c, 0, MODAL_NORMS, sums);
+  };
+
+  hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, V_X));
+  while (locked < n_modes) {
+    ++sweep;
+    const int want = n_modes - locked < MC - 2 ? n_modes - locked : MC - 2;   // two guard columns
+    if ((rc = launch_deflate(c, mv(c, V_X), locked)) || (rc = ritz_on_x())) return rc;
+    bool hasP = false, must_step = false;
+    for (int its = 0;;) {
+      if (its > 0 && its % 20 == 0 && !must_step) { if ((rc = products_x())) return rc; }
+      const int np = hasP ? 3 : 2;
+      if ((rc = upload()) || (rc = enq_residual(c, true)) || (rc = launch_deflate(c, mv(c, V_W), locked))) return rc;
+      if ((rc = launch_spmm_km(c, mv(c, V_W), mv(c, V_KW), mv(c, V_MW)))) return rc;
+      enq_gram(c, np);
+      if ((rc = read_sums(c, 0, MODAL_SUMS, sums))) return rc;          // the one synchronisation of a step
+      const bool stop = converged(want) && !must_step;
+      must_step = false;
+      if (stop || it >= max_it) {
+        if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
+        if (converged(want)) break;
+        if (it >= max_it) return done(FEAHIP_ENOTCONVERGED, "not converged after " + std::to_string(it) + " Rayleigh-Ritz steps");
+        must_step = true;
+        continue;
+      }
+      int rank = 0;
+      if (!ritz(np, &rank)) return broke();
+      if ((rc = upload())) return rc;
+      enq_combine(c, np, 1);
+      hasP = rank == 8 * np;
+      ++its; ++it;
+    }
+    // lock the leading converged columns, contiguous from column 0, within n_modes
+    int k = 0;
+    while (k < MC && locked + k < n_modes && ratio[k] <= tol) ++k;
+    hipLaunchKernelGGL(k_modal_lock, dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof, locked, k,
+                       (const double *)mv(c, V_X), (const double *)mv(c, V_MX), locked_panel(c, 0, 0), locked_panel(c, 1, 0), n8);
+    for (int j = 0; j < k; ++j) { lambda[locked + j] = theta[j] - shift; if (resid) resid[locked + j] = ratio[j]; }
+    locked += k;
+    if (locked < n_modes) {
+      hipLaunchKernelGGL(k_modal_advance, dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof, k, next_id,
+                         (const uint8_t *)c->d_dofmask, mv(c, V_X));
+      next_id += k;
+    }
+    FEA_HIP_CHECK(c, hipGetLastError());
+  }
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return done(FEAHIP_OK, "");
+}
+
+int modal_get_locked(feahip_ctx *c, int mode, double *h_lib /*[3N], library ids*/)   // mode of the ascending lambda
+{
+  hipLaunchKernelGGL(k_modal_extract, g256((size_t)c->ndof), dim3(256), 0, c->stream, (size_t)c->ndof,
+                     (const double *)locked_panel(c, 0, c->modal.lock_order[mode] / MC), c->modal.lock_order[mode] % MC, c->d_q);
   FEA_HIP_CHECK(c, hipGetLastError());
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_lib, c->d_q, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));

@@ -148,8 +148,13 @@ ABI = {
     "feahip_get_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_spmm_km": [C.c_void_p, _dp, _dp, _dp],
     "feahip_host_modal_ritz": [C.c_int, _dp, _dp, _dp, _dp],
+    "feahip_solve_modes_locked": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _ip, _ip],
+    "feahip_get_locked_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
+    "feahip_get_locked_count": [C.c_void_p, _ip],
+    "feahip_modal_deflate": [C.c_void_p, C.c_int, _dp, _dp, _dp],
 }
 MODAL_COLS = 8                                          # FEA_MODAL_COLS of include/fea_hip.h
+MODAL_MAX_LOCKED = 64                                   # FEA_MODAL_MAX_LOCKED
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
 COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
@@ -201,6 +206,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("modal_count", C.c_int), ("modal_shift", C.c_double),
         ("modal_modes", C.c_int), ("modal_tolerance", C.c_double), ("modal_max", C.c_int),
     ]
 
@@ -357,7 +363,18 @@ class Deck:
         self.modal_max = int(kw.get("modal_max", 1000))
         if not 0 <= self.modal_modes <= MODAL_COLS:
             raise ValueError("modal_modes: 0 to 8")
-        if self.modal_modes and self.density is None:
+        # :count N (up to 64 modes, instead of :modes) and :shift s: the locked solve (solve_modes_locked)
+        self.modal_count = int(kw.get("modal_count", 0))
+        self.modal_shift = float(kw.get("modal_shift", 0.0))
+        if not 0 <= self.modal_count <= MODAL_MAX_LOCKED:
+            raise ValueError("modal_count: 1 to 64")
+        if self.modal_count and self.modal_modes:
+            raise ValueError("modal_modes or modal_count, not both")
+        if not (0.0 <= self.modal_shift < np.inf):
+            raise ValueError("modal_shift: finite and not negative")
+        if self.modal_shift and not (self.modal_modes or self.modal_count):
+            raise ValueError("modal_shift needs modal_modes or modal_count")
+        if (self.modal_modes or self.modal_count) and self.density is None:
             raise ValueError("modal_modes needs a density")
 
     @staticmethod
@@ -395,8 +412,9 @@ class Deck:
                                  if fd.dynamics_explicit else {})) if fd.has_dynamics else None,
                 results=dict(nodal_stress=bool(fd.results_nodal_stress), energy=bool(fd.results_energy),
                              reactions=bool(fd.results_reactions)),
-                **(dict(modal_modes=fd.modal_modes, modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
-                   if fd.modal_modes else {}))
+                **(dict(modal_modes=fd.modal_modes, modal_count=fd.modal_count, modal_shift=fd.modal_shift,
+                        modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
+                   if fd.modal_modes or fd.modal_count else {}))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -443,6 +461,7 @@ class Deck:
         fd.results_nodal_stress, fd.results_energy = int(res.get("nodal_stress", False)), int(res.get("energy", False))
         fd.results_reactions = int(res.get("reactions", False))
         fd.modal_modes = int(getattr(self, "modal_modes", 0))
+        fd.modal_count, fd.modal_shift = int(getattr(self, "modal_count", 0)), float(getattr(self, "modal_shift", 0.0))
         fd.modal_tolerance, fd.modal_max = float(getattr(self, "modal_tolerance", 1e-8)), int(getattr(self, "modal_max", 1000))
         return fd
 
@@ -803,6 +822,42 @@ class FeaSolver:
         phi = np.zeros((max(int(count), 0), self.ndof))
         self._chk(self._lib.feahip_get_modes(self._ctx, int(first), int(count), _d(phi)))
         return phi
+
+    def solve_modes_locked(self, n_modes, shift=0.0, tolerance=1e-8, max_iterations=4000, check=True):
+        """feahip_solve_modes_locked: the n_modes <= 64 lowest eigenpairs of K(x) phi = lambda M phi by sweeps of the
+        eight-column block with hard locking, on the pencil (K + shift M, M); lam is unshifted.  Returns (lam[n_modes]
+        ascending, resid[n_modes], Rayleigh-Ritz steps over all sweeps, sweeps) and, with check=False, the return code as
+        a fifth item instead of raising when the steps run out (lam and resid are NaN past the pairs locked by then:
+        locked_count)."""
+        lam, res = np.zeros(max(int(n_modes), 1)), np.zeros(max(int(n_modes), 1))
+        it, sw = C.c_int(0), C.c_int(0)
+        rc = self._lib.feahip_solve_modes_locked(self._ctx, int(n_modes), float(shift), float(tolerance), int(max_iterations),
+                                                 _d(lam), _d(res), C.byref(it), C.byref(sw))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        return (lam, res, it.value, sw.value) if check else (lam, res, it.value, sw.value, rc)
+
+    def locked_count(self):
+        """The modes in the locked store of the last solve_modes_locked (fewer than asked when its steps ran out)."""
+        n = C.c_int(0)
+        self._chk(self._lib.feahip_get_locked_count(self._ctx, C.byref(n)))
+        return n.value
+
+    def locked_modes(self, first=0, count=None):
+        """feahip_get_locked_modes: phi[count][3N] of the last solve_modes_locked, M-orthonormal, zero on the prescribed
+        dofs (count=None: from `first` to the last one locked)."""
+        count = self.locked_count() - first if count is None else count
+        phi = np.zeros((max(int(count), 0), self.ndof))
+        self._chk(self._lib.feahip_get_locked_modes(self._ctx, int(first), int(count), _d(phi)))
+        return phi
+
+    def modal_deflate(self, q, x8):
+        """x8 - Q (MQ' x8) by the two deflation kernels, MQ = mask(M Q) by the block product: q[n_locked][3N], x8[8][3N]."""
+        q, x8 = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(x8, dtype=np.float64)
+        assert q.ndim == 2 and q.shape[1] == self.ndof and x8.shape == (MODAL_COLS, self.ndof)
+        out = np.zeros_like(x8)
+        self._chk(self._lib.feahip_modal_deflate(self._ctx, len(q), _d(q), _d(x8), _d(out)))
+        return out
 
     def spmm_km(self, x8):
         """[K X, mask(M X)] of eight columns in one pass over K's pattern; x8 and both results are [8][3N]."""

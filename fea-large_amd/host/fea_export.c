@@ -165,22 +165,27 @@ int fea_solve_dynamic_with_snapshot(const fea_deck *d, feahip_ctx *ctx, void *lo
 int fea_modal_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   FILE *log = (FILE *)log_, *f;
-  const int n = d->modal_modes;
-  double lam[FEA_MODAL_COLS], res[FEA_MODAL_COLS], *phi;
+  const int locked = d->modal_count > 0 || d->modal_shift != 0.0;       /* :count or :shift: the locked solve */
+  int n = d->modal_count > 0 ? d->modal_count : d->modal_modes;
+  double lam[FEA_MODAL_MAX_LOCKED], res[FEA_MODAL_MAX_LOCKED], *phi;
   int k, i, its = 0, rc, solved;
   if (n <= 0) return 0;
-  solved = feahip_solve_modes(ctx, n, d->modal_tolerance, d->modal_max, 0, lam, res, &its);
+  solved = locked ? feahip_solve_modes_locked(ctx, n, d->modal_shift, d->modal_tolerance, d->modal_max, lam, res, &its, NULL)
+                  : feahip_solve_modes(ctx, n, d->modal_tolerance, d->modal_max, 0, lam, res, &its);
   if (solved && solved != FEAHIP_ENOTCONVERGED) return solved;
   if (log) {
     if (solved) fprintf(log, "Modal analysis not converged in %d steps\n", its);
     else fprintf(log, "Modal analysis finished: %d modes, %d steps\n", n, its);
+  }
+  if (locked && solved && (rc = feahip_get_locked_count(ctx, &n))) return rc;   /* the steps ran out: the modes locked so far */
+  if (log) {
     for (k = 0; k < n; ++k)
       fprintf(log, "Mode %d: omega^2 = %.17g, f = %.17g Hz\n", k + 1, lam[k], sqrt(lam[k] > 0 ? lam[k] : 0.0) / 6.283185307179586);
   }
-  if (!msh_path) return 0;
+  if (!msh_path || n == 0) return 0;
   phi = (double *)malloc(sizeof(double) * 3 * (size_t)d->nodes_count * (size_t)n);
   if (!phi) return FEAHIP_ENOMEM;
-  if ((rc = feahip_get_modes(ctx, 0, n, phi))) { free(phi); return rc; }
+  if ((rc = locked ? feahip_get_locked_modes(ctx, 0, n, phi) : feahip_get_modes(ctx, 0, n, phi))) { free(phi); return rc; }
   if (!(f = fopen(msh_path, "a"))) { free(phi); return FEAHIP_EINVAL; }
   for (k = 0; k < n; ++k) {
     const double *p = phi + (size_t)k * 3 * d->nodes_count;

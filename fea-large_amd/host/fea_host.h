@@ -95,7 +95,13 @@ typedef struct fea_deck {
    * and :max 1000 where absent).  After its last step feasolver_hip calls feahip_solve_modes at the state reached, logs
    * one line per mode and appends one $NodeData section per mode shape to the .msh file (fea_modal_run).  It needs the
    * density of (dynamics ... :density rho) -- :steps 0 there leaves the run static --: a deck without one is refused at
-   * load.  Written by fea_deck_save only when N > 0                                                             */
+   * load.  Written by fea_deck_save only when N > 0.
+   * :count N, N in [1, 64], instead of :modes (both together are refused), and :shift s, s >= 0 (written only when not
+   * zero): with either key fea_modal_run calls feahip_solve_modes_locked(N, s) -- more than eight modes, and with s of
+   * the order of the first elastic eigenvalue a body with rigid-body modes.  A deck without them is read, run and
+   * written as before                                                                                           */
+  int modal_count;
+  double modal_shift;
   int modal_modes;
   double modal_tolerance;
   int modal_max;
@@ -186,7 +192,8 @@ int fea_solve_dynamic_with_snapshot(const fea_deck *deck, feahip_ctx *ctx, void 
 int fea_export_gmsh(const char *filename, const fea_deck *deck,
                     const fea_step_snapshot *steps, int nsteps);
 
-/* The modal analysis of a deck with (modal :modes N ...), N > 0, at the state the context is in: feahip_solve_modes,
+/* The modal analysis of a deck with (modal :modes N ...), N > 0, at the state the context is in: feahip_solve_modes
+ * (feahip_solve_modes_locked and the locked store for a deck with :count or :shift),
  * one log line per mode ("Mode k: omega^2 = l, f = x Hz", f = sqrt(max(l, 0)) / 2 pi) and, with msh_path not NULL, one
  * $NodeData section "Mode k" per mode shape appended to that file, tagged with the frequency.  A solve that runs out
  * of steps is logged and its modes are written as they stand.  Returns 0, or a negative FEAHIP_E* code.        */

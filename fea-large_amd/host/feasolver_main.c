@@ -77,7 +77,7 @@ int main(int argc, char **argv)
     if (fea_export_gmsh(msh, &deck, steps, (arc || dyn) ? 1 : (done == deck.load_increments_count ? done : done - 1))) {
       fprintf(stderr, "could not write %s\n", msh);
       status = 1;
-    } else if (deck.modal_modes > 0 && (rc = fea_modal_run(&deck, ctx, stdout, msh))) {
+    } else if ((deck.modal_modes > 0 || deck.modal_count > 0) && (rc = fea_modal_run(&deck, ctx, stdout, msh))) {
       /* (modal :modes N ...): the natural frequencies at the state reached, the mode shapes behind the steps */
       fprintf(stderr, "feasolve error encountered: %s\n", feahip_last_error(ctx));
       status = 1;

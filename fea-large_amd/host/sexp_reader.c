@@ -479,9 +479,21 @@ static int read_list(reader *r, fea_deck *d)
       }
     }
   } else if (ieq(head, "modal")) {                            /* no counterpart in the reference */
-    if (need_num(r, a, na, "modes", &v)) return -1;
-    if (!(v >= 0 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "modal :modes must be an integer in [0, 8]");
-    d->modal_modes = (int)v;
+    d->modal_modes = d->modal_count = 0; d->modal_shift = 0.0;
+    if (attr_get(a, na, "count")) {                           /* :count N, up to 64 modes by the locked solve, instead of :modes */
+      if (attr_get(a, na, "modes")) return fail(r, "modal takes :modes or :count, not both");
+      if (need_num(r, a, na, "count", &v)) return -1;
+      if (!(v >= 1 && v <= FEA_MODAL_MAX_LOCKED) || v != (double)(int)v) return fail(r, "modal :count must be an integer in [1, 64]");
+      d->modal_count = (int)v;
+    } else {
+      if (need_num(r, a, na, "modes", &v)) return -1;
+      if (!(v >= 0 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "modal :modes must be an integer in [0, 8]");
+      d->modal_modes = (int)v;
+    }
+    if (attr_get(a, na, "shift")) {
+      if (need_num(r, a, na, "shift", &d->modal_shift)) return -1;
+      if (!(d->modal_shift >= 0 && d->modal_shift <= 1.7976931348623157e308)) return fail(r, "modal :shift must be finite and not negative");
+    }
     d->modal_tolerance = 1e-8; d->modal_max = 1000;
     if (attr_get(a, na, "tolerance") && need_num(r, a, na, "tolerance", &d->modal_tolerance)) return -1;
     if (!(d->modal_tolerance > 0)) return fail(r, "modal :tolerance must be positive");
@@ -562,7 +574,7 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
     if (rc == 0 && deck->has_body_force && !deck->has_dynamics) {
       rc = -1; snprintf(r.err, sizeof r.err, "deck has (body-force ...) but no (dynamics ... :density rho)");
     }
-    if (rc == 0 && deck->modal_modes > 0 && !deck->has_dynamics) {
+    if (rc == 0 && (deck->modal_modes > 0 || deck->modal_count > 0) && !deck->has_dynamics) {
       rc = -1; snprintf(r.err, sizeof r.err, "deck has (modal ...) but no density: add (dynamics :steps 0 :dt 1 :density rho)");
     }
   }
@@ -621,8 +633,12 @@ int fea_deck_save(const char *path, const fea_deck *d)
   if (d->results_nodal_stress || d->results_energy || d->results_reactions)   /* written only when asked for */
     fprintf(f, "\n   (results :nodal-stress %s :energy %s :reactions %s)", d->results_nodal_stress ? "t" : "nil",
             d->results_energy ? "t" : "nil", d->results_reactions ? "t" : "nil");
-  if (d->modal_modes > 0)                                                      /* written only when asked for */
-    fprintf(f, "\n   (modal :modes %d :tolerance %.17g :max %d)", d->modal_modes, d->modal_tolerance, d->modal_max);
+  if (d->modal_modes > 0 || d->modal_count > 0) {                              /* written only when asked for */
+    fprintf(f, "\n   (modal :%s %d :tolerance %.17g :max %d", d->modal_count > 0 ? "count" : "modes",
+            d->modal_count > 0 ? d->modal_count : d->modal_modes, d->modal_tolerance, d->modal_max);
+    if (d->modal_shift != 0.0) fprintf(f, " :shift %.17g", d->modal_shift);    /* (the old text without the new keys) */
+    fprintf(f, ")");
+  }
   fprintf(f, ")\n");
   fprintf(f, " (input-data\n  (geometry\n   (nodes");
   for (i = 0; i < d->nodes_count; ++i)

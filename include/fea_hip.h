@@ -655,6 +655,61 @@ int feahip_spmm_km(feahip_ctx *ctx, const double *x8, double *y8, double *z8);
  * when fewer than eight directions are left or an entry is not finite.        */
 int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const double *gram_k, double *theta, double *coef);
 
+/* ---- modal analysis, more than eight modes and free bodies --------------------
+ * feahip_solve_modes_locked: the n_modes lowest eigenpairs of the same pencil,
+ * 1 <= n_modes <= FEA_MODAL_MAX_LOCKED, in sweeps of the eight-column block with
+ * hard locking, on the shifted pencil (K + shift M, M), shift >= 0.
+ *   shift  K's store holds K_s = K + shift M on the free dofs (assembled, the
+ *      mass added, masked: the order of a Newmark iteration), so the products
+ *      and both preconditioners see K_s.  The iteration finds theta_s = lambda +
+ *      shift; lambda[] is UNSHIFTED, near 0 for the rigid-body modes of a free
+ *      body.  With shift > 0 K_s is positive definite and the stop test is well
+ *      posed at lambda = 0: give a shift of the order of the first elastic
+ *      eigenvalue expected (no automatic choice is made).  shift == 0 is the
+ *      supported body; a free body with shift == 0 behaves as under
+ *      feahip_solve_modes: not refused, nothing promised.
+ *   sweep  the block is deflated against the locked modes and orthonormalised
+ *      on its own; it iterates as feahip_solve_modes does, with the
+ *      preconditioned residuals deflated against the locked modes
+ *      (W <- W - Q (MQ' W), on the device, nothing read back) before they are
+ *      multiplied; it stops when its leading min(6, n_modes - locked) columns
+ *      (two guard columns) pass the stop test on fresh products.  The leading
+ *      converged columns, contiguous from column 0 and within n_modes, are
+ *      locked; the others move to the front and the freed columns are filled
+ *      from the hash with column indices not used before.  lambda[] is
+ *      ascending: the pairs are sorted once more at return, because two
+ *      eigenvalues equal to rounding (a degenerate pair split by the end of
+ *      a sweep) can come out of two sweeps in either order.
+ * Converged: ||K_s x - theta_s M x|| <= tolerance (||K_s x|| + |theta_s| ||M x||),
+ * the ratio resid[] reports.  *iters: the Rayleigh-Ritz steps summed over all
+ * sweeps, capped by max_iterations; *sweeps: the sweeps.  When the steps run
+ * out: FEAHIP_ENOTCONVERGED, the pairs locked so far in lambda / resid (NaN
+ * after them), their count in feahip_get_locked_count, their modes readable.
+ * The same input gives the same bits.  Refused: what feahip_solve_modes refuses,
+ * n_modes outside [1, 64], a negative or non-finite shift, fewer than
+ * n_modes + 24 free dofs.  K and f hold another matrix afterwards, the block
+ * of feahip_solve_modes is scratch (feahip_get_modes and warm restarts behave
+ * as before any solve), and there is no warm restart of this solve.
+ * Memory: 2 x ceil(n_modes / 8) block vectors and up to 8 MB of partial sums on
+ * top of feahip_solve_modes', allocated on the first call for the n_modes
+ * asked (a larger request later reallocates).
+ * feahip_get_locked_modes: modes [first, first + count) of the locked store,
+ * phi[count][3N] in the caller's dof order, M-orthonormal, 0 on the prescribed
+ * dofs.  FEAHIP_ESTATE before a locked solve, FEAHIP_EINVAL outside those
+ * locked.                                                                      */
+#define FEA_MODAL_MAX_LOCKED 64
+int feahip_solve_modes_locked(feahip_ctx *ctx, int n_modes, double shift, double tolerance, int max_iterations,
+                              double *lambda /*[n_modes]*/, double *resid /*[n_modes], may be NULL*/,
+                              int *iters /*may be NULL: Rayleigh-Ritz steps over all sweeps*/,
+                              int *sweeps /*may be NULL*/);
+int feahip_get_locked_modes(feahip_ctx *ctx, int first, int count, double *phi /*[count][3N], caller's dof order*/);
+int feahip_get_locked_count(feahip_ctx *ctx, int *count);
+/* Test hook for the deflation kernels: out8 = x8 - Q (MQ' x8) with MQ = mask(M Q)
+ * from the block product, q[n_locked][3N], x8 and out8 [8][3N] host vectors in
+ * the caller's dof order, 1 <= n_locked <= 64.  Refused where feahip_spmm_km is;
+ * modes held from either solve are dropped.                                   */
+int feahip_modal_deflate(feahip_ctx *ctx, int n_locked, const double *q, const double *x8, double *out8);
+
 /* z = M^-1 r on every rank of the group at once, with the preconditioner the
  * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
  * feahip_apply_preconditioner takes them (the caller's node ids of context k;
@@ -925,8 +980,10 @@ int feahip_sync(feahip_ctx *ctx);
  * (k_result_elements, k_result_nodes) with all outputs and material = -1,
  * 13 k_spmm_km (K X and M X of eight columns in one pass), 14 k_modal_gram (both
  * 24 x 24 Gram matrices from the nine block vectors), 15 k_modal_combine (the
- * nine block vectors recombined in place); 13-15 refused without a mass and
- * where feahip_solve_modes is.                                               */
+ * nine block vectors recombined in place), 16 k_modal_deflate_gram and 17
+ * k_modal_deflate_apply (one block vector against eight panels of the locked
+ * store filled with the hash; with zero coefficients, so nothing moves); 13-17
+ * refused without a mass and where feahip_solve_modes is.                     */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
