@@ -469,6 +469,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->mass.release();
   c->results.release();
   c->modal.release();
+  c->buckling.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -1354,6 +1355,65 @@ extern "C" int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const do
   return modal_ritz(n_dirs, gram_m, gram_k, FEA_MODAL_COLS, theta, coef);
 }
 
+// ---- linear buckling (kernels_buckling.hip) -----------------------------------
+extern "C" int feahip_host_buckling_factor(int n, const double *nu, double *factor)
+{
+  if (n < 0 || (n > 0 && (!nu || !factor))) return FEAHIP_EINVAL;
+  for (int i = 0; i < n; ++i) factor[i] = nu[i] < 0.0 ? 1.0 - 1.0 / nu[i] : INFINITY;   // (-0.0 and NaN: no buckling found)
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_solve_buckling(feahip_ctx *c, int n_modes, double tol, int max_iter, double *factor, double *nu,
+                                     double *resid, int *iters)
+{
+  CTX_GUARD(c);
+  if (iters) *iters = 0;
+  if (n_modes < 1 || n_modes > FEA_MODAL_COLS) { c->err = "solve_buckling: n_modes must be in [1, 8]"; return FEAHIP_EINVAL; }
+  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_buckling: tolerance must be positive"; return FEAHIP_EINVAL; }
+  if (max_iter < 0) { c->err = "solve_buckling: max_iterations must not be negative"; return FEAHIP_EINVAL; }
+  if (!factor) { c->err = "solve_buckling: null factor"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = solve2_refused(c, "solve_buckling"))) return rc;
+  double v[FEA_MODAL_COLS];
+  for (int j = 0; j < n_modes; ++j) { v[j] = NAN; factor[j] = NAN; if (nu) nu[j] = NAN; if (resid) resid[j] = NAN; }
+  rc = buckling_solve(c, n_modes, tol, max_iter, v, resid, iters);
+  if (c->modal.have_buckling) {                                       // converged, or the steps ran out: the pairs as they stand
+    (void)feahip_host_buckling_factor(n_modes, v, factor);
+    if (nu) for (int j = 0; j < n_modes; ++j) nu[j] = v[j];
+  }
+  return rc;
+}
+
+extern "C" int feahip_get_buckling_modes(feahip_ctx *c, int first, int count, double *phi)
+{
+  CTX_GUARD_NOK(c);
+  if (!c->modal.have_buckling) { c->err = "get_buckling_modes: no buckling modes held (feahip_solve_buckling first)"; return FEAHIP_ESTATE; }
+  if (first < 0 || count < 0 || first + count > FEA_MODAL_COLS) { c->err = "get_buckling_modes: modes [first, first + count) outside the eight held"; return FEAHIP_EINVAL; }
+  if (!phi) { c->err = "get_buckling_modes: null phi"; return FEAHIP_EINVAL; }
+  std::vector<double> tmp((size_t)c->ndof);
+  for (int k = 0; k < count; ++k) {
+    const int rc = modal_get(c, first + k, tmp.data());
+    if (rc) return rc;
+    double *out = phi + (size_t)k * c->ndof;
+    for (int a = 0; a < c->N; ++a)
+      for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_geometric_spmv(feahip_ctx *c, const double *x, double *y)
+{
+  CTX_GUARD(c);
+  if (!x || !y) return FEAHIP_EINVAL;
+  int rc;
+  if ((rc = solve2_refused(c, "geometric_spmv")) || (rc = geom_assemble(c))) return rc;
+  BucklingState &B = c->buckling;
+  if (!B.d_x4) FEA_HIP_CHECK(c, hipMalloc((void **)&B.d_x4, sizeof(double) * 4 * (size_t)c->N));
+  if ((rc = set_node4(c, B.d_x4, x))) return rc;
+  if ((rc = launch_block_product(c, B.d_kg, B.d_x4, c->d_q))) return rc;
+  return get_node_vec(c, c->d_q, y);
+}
+
 // ---- two-column solve (kernels_solve2.hip) ---------------------------------
 static int solve2_ready(feahip_ctx *c, const char *who)
 {
@@ -1712,6 +1772,10 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     int rk;
     if ((rk = solve2_refused(c, who.c_str())) || (rk = mass_ensure(c, "time_kernel")) || (rk = time_deflate_prepare(c))) return rk;
   }
+  if (what == 18 || what == 19) {                      // one assembly first: the buffers, and the records the block pass reads
+    int rk;
+    if ((rk = solve2_refused(c, what == 18 ? "time_kernel(18)" : "time_kernel(19)")) || (rk = geom_assemble(c))) return rk;
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   return time_enqueued(c, warmup, iters, avg_ms, [&](int) -> int {
@@ -1729,6 +1793,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 12: return launch_results(c, -1, c->d_scal + 8);
     case 13: case 14: case 15: return time_modal_kernel(c, what);
     case 16: case 17: return time_deflate_kernel(c, what);
+    case 18: case 19: return time_geom_kernel(c, what);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

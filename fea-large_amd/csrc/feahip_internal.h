@@ -457,7 +457,19 @@ struct ModalState {
   int n_locked = 0;                    // modes in the store
   int lock_order[64] = {0};            // mode j of the ascending lambda is column lock_order[j] of the store
   bool have_locked = false;            // the store holds the modes of a locked solve (feahip_get_locked_modes)
+  bool have_buckling = false;          // X holds the buckling modes of feahip_solve_buckling (feahip_get_buckling_modes)
   void release() { dev_free({d_v, d_part, d_small, d_lock, d_lpart, d_lcoef}); *this = ModalState(); }
+};
+
+// linear buckling (kernels_buckling.hip): nothing of it exists until feahip_solve_buckling (or one of its hooks,
+// feahip_geometric_spmv and feahip_time_kernel 18-19) is called.  kg is stored like MassState::d_m.
+struct BucklingState {
+  double *d_rec = nullptr;             // [E][npe (npe + 1) / 2] the upper triangle of every element's scalar matrix G_e
+  double *d_kg_base = nullptr;         // [kb1 - kb0] one double per owned block of K's pattern
+  double *d_kg = nullptr;              // d_kg_base - kb0: indexed by GLOBAL block number, as d_K
+  long long kb0 = -1, kb1 = -1;        // the window kg is allocated for
+  double *d_x4 = nullptr;              // [N][4] the vector of feahip_geometric_spmv in the node layout
+  void release() { dev_free({d_rec, d_kg_base, d_x4}); *this = BucklingState(); }
 };
 
 struct feahip_ctx {
@@ -600,6 +612,7 @@ struct feahip_ctx {
   MassState mass;
   ResultState results;
   ModalState modal;
+  BucklingState buckling;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -667,6 +680,20 @@ double *locked_panel(feahip_ctx *c, int mq, int panel);                 // panel
 int launch_deflate(feahip_ctx *c, double *d_w8, int n_locked);          // W -= Q (MQ' W) against the first n_locked modes
 int time_deflate_prepare(feahip_ctx *c);                                // eight panels of hash for feahip_time_kernel 16-17
 int time_deflate_kernel(feahip_ctx *c, int what);
+// the pieces of a Rayleigh-Ritz step for a driver in another file (kernels_buckling.hip): the block vector j of
+// ModalState::d_v (0 X, 1 W, 2 P, 3 KX, 4 KW, 5 KP, 6 MX, 7 MW, 8 MP) and the launches modal_solve makes, unchanged
+double *modal_vec(feahip_ctx *c, int j);
+int launch_spmm_pencil(feahip_ctx *c, const double *d_m, const double *d_x8, double *d_y8, double *d_z8);   // Y = K X, Z = mask(m X), m one double per block
+int modal_enq_hash(feahip_ctx *c, int j);                               // the start block into vector j
+int modal_enq_gram(feahip_ctx *c, int np);
+int modal_enq_combine(feahip_ctx *c, int np, int write_p);
+int modal_enq_residual(feahip_ctx *c, bool precond);
+int modal_read_sums(feahip_ctx *c, int e0, int n, double *h);           // sums [e0, e0 + n) reduced and read into h + e0
+void modal_unpack_gram(const double *gram_sums, int np, double *GM, double *GK);
+// kernels_buckling.hip -- K_sigma as one double per block, and the lowest eigenpairs of K_sigma phi = nu K phi
+int geom_assemble(feahip_ctx *c);                                       // buckling.d_kg at the current nodes
+int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters);
+int time_geom_kernel(feahip_ctx *c, int what);                          // feahip_time_kernel 18 (elements), 19 (blocks)
 // kernels_mass.hip -- consistent mass, body force and the vector kernels of the Newmark steps
 int mass_set(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights, const double *forms,
              const double *dforms);
@@ -676,6 +703,7 @@ int launch_body_force(feahip_ctx *c, double *d_fv);            // d_fv += load_f
 int launch_mass_add(feahip_ctx *c, double coef);               // K += coef M on the diagonal entries of every owned block
 int launch_mass_residual(feahip_ctx *c, double a0);            // f -= a0 M (x - xt) on the owned rows
 int launch_mass_product(feahip_ctx *c, const double *d_v4, double *d_y);   // y = M v on the owned rows, v in the node layout
+int launch_block_product(feahip_ctx *c, const double *d_m, const double *d_v4, double *d_y);   // the same with m given (one double per block, global index)
 int launch_newmark_predict(feahip_ctx *c, double dt, double beta, double gamma);
 int launch_newmark_correct(feahip_ctx *c, double dt, double beta, double gamma);
 int launch_vec3_to_nodes(feahip_ctx *c, const double *d_v3, double *d_v4);

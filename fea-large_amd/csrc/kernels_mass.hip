@@ -429,6 +429,14 @@ int launch_mass_product(feahip_ctx *c, const double *d_v4, double *d_y)
   return FEAHIP_OK;
 }
 
+int launch_block_product(feahip_ctx *c, const double *d_m, const double *d_v4, double *d_y)
+{
+  hipLaunchKernelGGL(k_mass_product, dim3(chunk_grid(c)), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, c->chunk0,
+                     c->nchunks_local, c->d_chunk, c->d_rowptr, c->d_colidx, d_m, d_v4, d_y);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+
 int launch_body_force(feahip_ctx *c, double *d_fv)
 {
   MassState &M = c->mass;

@@ -17,7 +17,8 @@
 //   k_modal_combine   [X, P] <- S [C_x, C_p] and the same for KS and MS, in place: only W is ever multiplied by the
 //                     matrices; every 20 steps and at return KX and MX are recomputed from X.
 // Nothing here exists, and nothing is launched, on a context that never calls feahip_solve_modes (or the hooks
-// feahip_spmm_km, feahip_time_kernel 13-15).
+// feahip_spmm_km, feahip_time_kernel 13-15) -- or feahip_solve_buckling, whose driver (kernels_buckling.hip) runs the same
+// step on the pencil (K_sigma, K) through the launchers exported below modal_ritz' helpers.
 //
 // More than eight modes, and bodies with zero-energy modes (feahip_solve_modes_locked, modal_solve_locked below): the
 // same step in sweeps of the eight-column block on the pencil (K + shift M, M).  Converged leading columns are locked
@@ -459,6 +460,7 @@ static int resid_grid(const feahip_ctx *c)
 int ensure_modal(feahip_ctx *c)
 {
   ModalState &S = c->modal;
+  S.have_buckling = false;                                            // every caller makes the block its own
   if (S.d_v) return FEAHIP_OK;
   const size_t n8 = (size_t)c->ndof * MC;
   FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_v, sizeof(double) * 9 * n8));
@@ -671,6 +673,29 @@ static int enq_residual(feahip_ctx *c, bool precond)
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }
+
+// ---- the same launches for the buckling driver (kernels_buckling.hip): the kernels live in this file -------------------
+double *modal_vec(feahip_ctx *c, int j) { return mv(c, j); }
+int launch_spmm_pencil(feahip_ctx *c, const double *d_m, const double *d_x8, double *d_y8, double *d_z8)
+{
+  hipLaunchKernelGGL(k_spmm_km, dim3(spmm_grid(c)), dim3(256), 0, c->stream, c->chunk0, c->nchunks_local, c->d_chunk,
+                     c->d_rowptr, c->d_colidx, (const double *)c->d_K, d_m, (const uint8_t *)c->d_dofmask, (const v2d *)d_x8,
+                     (v2d *)d_y8, (v2d *)d_z8);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+int modal_enq_hash(feahip_ctx *c, int j)
+{
+  const size_t n8 = (size_t)c->ndof * MC;
+  hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, j));
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+int modal_enq_gram(feahip_ctx *c, int np) { enq_gram(c, np); FEA_HIP_CHECK(c, hipGetLastError()); return FEAHIP_OK; }
+int modal_enq_combine(feahip_ctx *c, int np, int write_p) { enq_combine(c, np, write_p); FEA_HIP_CHECK(c, hipGetLastError()); return FEAHIP_OK; }
+int modal_enq_residual(feahip_ctx *c, bool precond) { return enq_residual(c, precond); }
+int modal_read_sums(feahip_ctx *c, int e0, int n, double *h) { return read_sums(c, e0, n, h); }
+void modal_unpack_gram(const double *gram_sums, int np, double *GM, double *GK) { unpack_gram(gram_sums, np, GM, GK); }
 
 int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, double *lambda, double *resid, int *iters)
 {

@@ -152,6 +152,10 @@ ABI = {
     "feahip_get_locked_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_get_locked_count": [C.c_void_p, _ip],
     "feahip_modal_deflate": [C.c_void_p, C.c_int, _dp, _dp, _dp],
+    "feahip_solve_buckling": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
+    "feahip_get_buckling_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
+    "feahip_geometric_spmv": [C.c_void_p, _dp, _dp],
+    "feahip_host_buckling_factor": [C.c_int, _dp, _dp],
 }
 MODAL_COLS = 8                                          # FEA_MODAL_COLS of include/fea_hip.h
 MODAL_MAX_LOCKED = 64                                   # FEA_MODAL_MAX_LOCKED
@@ -206,6 +210,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("buckling_modes", C.c_int), ("buckling_tolerance", C.c_double), ("buckling_max", C.c_int),
         ("modal_count", C.c_int), ("modal_shift", C.c_double),
         ("modal_modes", C.c_int), ("modal_tolerance", C.c_double), ("modal_max", C.c_int),
     ]
@@ -279,6 +284,16 @@ def host_modal_ritz(gram_m, gram_k):
     theta, coef = np.zeros(MODAL_COLS), np.zeros((n, 2 * MODAL_COLS))
     rank = lib.feahip_host_modal_ritz(n, _d(gm), _d(gk), _d(theta), _d(coef))
     return rank, theta, coef
+
+
+def host_buckling_factor(nu):
+    """feahip_host_buckling_factor (no device): 1 - 1/nu where nu < 0, +infinity elsewhere."""
+    lib = load_library()
+    nu = np.ascontiguousarray(np.atleast_1d(nu), dtype=np.float64)
+    factor = np.zeros(len(nu))
+    if lib.feahip_host_buckling_factor(len(nu), _d(nu), _d(factor)) != 0:
+        raise FeaHipError("feahip_host_buckling_factor failed")
+    return factor
 
 
 def element_tables(ele_type, gauss_count):
@@ -376,6 +391,16 @@ class Deck:
             raise ValueError("modal_shift needs modal_modes or modal_count")
         if (self.modal_modes or self.modal_count) and self.density is None:
             raise ValueError("modal_modes needs a density")
+        # (buckling :modes N :tolerance t :max M): the load factors feasolver_hip computes after its last step
+        self.buckling_modes = int(kw.get("buckling_modes", 0))
+        self.buckling_tolerance = float(kw.get("buckling_tolerance", 1e-8))
+        self.buckling_max = int(kw.get("buckling_max", 2000))
+        if not 0 <= self.buckling_modes <= MODAL_COLS:
+            raise ValueError("buckling_modes: 0 to 8")
+        if not self.buckling_tolerance > 0:
+            raise ValueError("buckling_tolerance: positive")
+        if self.buckling_max < 0:
+            raise ValueError("buckling_max: not negative")
 
     @staticmethod
     def load(path):
@@ -414,7 +439,9 @@ class Deck:
                              reactions=bool(fd.results_reactions)),
                 **(dict(modal_modes=fd.modal_modes, modal_count=fd.modal_count, modal_shift=fd.modal_shift,
                         modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
-                   if fd.modal_modes or fd.modal_count else {}))
+                   if fd.modal_modes or fd.modal_count else {}),
+                **(dict(buckling_modes=fd.buckling_modes, buckling_tolerance=fd.buckling_tolerance,
+                        buckling_max=fd.buckling_max) if fd.buckling_modes else {}))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
             return deck
         finally:
@@ -463,6 +490,9 @@ class Deck:
         fd.modal_modes = int(getattr(self, "modal_modes", 0))
         fd.modal_count, fd.modal_shift = int(getattr(self, "modal_count", 0)), float(getattr(self, "modal_shift", 0.0))
         fd.modal_tolerance, fd.modal_max = float(getattr(self, "modal_tolerance", 1e-8)), int(getattr(self, "modal_max", 1000))
+        fd.buckling_modes = int(getattr(self, "buckling_modes", 0))
+        fd.buckling_tolerance = float(getattr(self, "buckling_tolerance", 1e-8))
+        fd.buckling_max = int(getattr(self, "buckling_max", 2000))
         return fd
 
     def save(self, path):
@@ -858,6 +888,36 @@ class FeaSolver:
         out = np.zeros_like(x8)
         self._chk(self._lib.feahip_modal_deflate(self._ctx, len(q), _d(q), _d(x8), _d(out)))
         return out
+
+    # ---- linear buckling ---------------------------------------------------
+    def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):
+        """feahip_solve_buckling: the n_modes lowest eigenpairs of K_sigma(x) phi = nu K(x) phi on the free dofs.  Returns
+        (factor[n_modes] = 1 - 1/nu where nu < 0 and +infinity elsewhere, nu[n_modes] ascending, resid[n_modes],
+        Rayleigh-Ritz steps) and, with check=False, the return code as a fifth item instead of raising when the steps
+        run out or K is not positive definite."""
+        n = max(int(n_modes), 1)
+        fac, nu, res, it = np.zeros(n), np.zeros(n), np.zeros(n), C.c_int(0)
+        rc = self._lib.feahip_solve_buckling(self._ctx, int(n_modes), float(tolerance), int(max_iterations), _d(fac), _d(nu),
+                                             _d(res), C.byref(it))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        return (fac, nu, res, it.value) if check else (fac, nu, res, it.value, rc)
+
+    def buckling_modes(self, first=0, count=None):
+        """feahip_get_buckling_modes: phi[count][3N] of the last solve_buckling, K-orthonormal, zero on the prescribed
+        dofs; all eight columns of the block are held (count=None: from `first` to the last)."""
+        count = MODAL_COLS - first if count is None else count
+        phi = np.zeros((max(int(count), 0), self.ndof))
+        self._chk(self._lib.feahip_get_buckling_modes(self._ctx, int(first), int(count), _d(phi)))
+        return phi
+
+    def geometric_spmv(self, x):
+        """y = K_sigma(current nodes) x, unmasked (feahip_geometric_spmv; K_sigma is assembled on each call)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        assert x.size == self.ndof
+        y = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_geometric_spmv(self._ctx, _d(x), _d(y)))
+        return y
 
     def spmm_km(self, x8):
         """[K X, mask(M X)] of eight columns in one pass over K's pattern; x8 and both results are [8][3N]."""

@@ -199,6 +199,37 @@ int fea_modal_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *ms
   return 0;
 }
 
+int fea_buckling_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
+{
+  FILE *log = (FILE *)log_, *f;
+  const int n = d->buckling_modes;
+  double fac[FEA_MODAL_COLS], nu[FEA_MODAL_COLS], *phi;
+  int k, i, its = 0, rc, solved;
+  if (n <= 0) return 0;
+  solved = feahip_solve_buckling(ctx, n, d->buckling_tolerance, d->buckling_max, fac, nu, NULL, &its);
+  if (solved == FEAHIP_ENOTCONVERGED && nu[0] != nu[0]) return solved;  /* K not positive definite: nothing to report */
+  if (solved && solved != FEAHIP_ENOTCONVERGED) return solved;
+  if (log) {
+    if (solved) fprintf(log, "Buckling analysis not converged in %d steps\n", its);
+    else fprintf(log, "Buckling analysis finished: %d modes, %d steps\n", n, its);
+    for (k = 0; k < n; ++k) fprintf(log, "Buckling mode %d: factor = %.17g, nu = %.17g\n", k + 1, fac[k], nu[k]);
+  }
+  if (!msh_path) return 0;
+  phi = (double *)malloc(sizeof(double) * 3 * (size_t)d->nodes_count * (size_t)n);
+  if (!phi) return FEAHIP_ENOMEM;
+  if ((rc = feahip_get_buckling_modes(ctx, 0, n, phi))) { free(phi); return rc; }
+  if (!(f = fopen(msh_path, "a"))) { free(phi); return FEAHIP_EINVAL; }
+  for (k = 0; k < n; ++k) {
+    const double *p = phi + (size_t)k * 3 * d->nodes_count;
+    fprintf(f, "$NodeData\n1\n\"Buckling mode %d\"\n1\n%f\n3\n%d\n3\n%d\n", k + 1, fac[k], k, d->nodes_count);
+    for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %f %f %f\n", i + 1, p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+    fprintf(f, "$EndNodeData\n");
+  }
+  fclose(f);
+  free(phi);
+  return 0;
+}
+
 int fea_export_gmsh(const char *filename, const fea_deck *d, const fea_step_snapshot *steps, int nsteps)
 {
   FILE *f = fopen(filename, "w+");

@@ -91,6 +91,15 @@ typedef struct fea_deck {
    * to the .msh file; :energy and :reactions add one log line each per finished step.  Written by fea_deck_save only
    * when one of them is set; without the section the file and the log are what they were                        */
   int results_nodal_stress, results_energy, results_reactions;
+  /* linear buckling, optional: (buckling :modes N :tolerance t :max M) inside (solution ...), N in [1, 8] (:tolerance
+   * 1e-8 and :max 2000 where absent).  After its last step -- and after the modal run of a deck that has both --
+   * feasolver_hip calls feahip_solve_buckling at the state reached, logs one line per mode and appends one $NodeData
+   * section per mode shape to the .msh file (fea_buckling_run).  It needs no density.  Written by fea_deck_save only
+   * when N > 0: a deck without the section is read, run and written as before.  The three fields are the newest of the
+   * struct and stand in front of the five modal ones, whose place at its end is pinned by the modal tests       */
+  int buckling_modes;
+  double buckling_tolerance;
+  int buckling_max;
   /* modal analysis, optional: (modal :modes N :tolerance t :max M) inside (solution ...), N in [1, 8] (:tolerance 1e-8
    * and :max 1000 where absent).  After its last step feasolver_hip calls feahip_solve_modes at the state reached, logs
    * one line per mode and appends one $NodeData section per mode shape to the .msh file (fea_modal_run).  It needs the
@@ -198,6 +207,12 @@ int fea_export_gmsh(const char *filename, const fea_deck *deck,
  * $NodeData section "Mode k" per mode shape appended to that file, tagged with the frequency.  A solve that runs out
  * of steps is logged and its modes are written as they stand.  Returns 0, or a negative FEAHIP_E* code.        */
 int fea_modal_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
+
+/* The buckling analysis of a deck with (buckling :modes N ...), N > 0, at the state the context is in:
+ * feahip_solve_buckling, one log line per mode ("Buckling mode k: factor = f, nu = v") and, with msh_path not NULL, one
+ * $NodeData section "Buckling mode k" per mode shape appended to that file, tagged with the factor.  A solve that runs
+ * out of steps is logged and its modes are written as they stand.  Returns 0, or a negative FEAHIP_E* code.       */
+int fea_buckling_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 
 /* "<base>.msh" next to the deck, as initial_data_load builds it
  * (fea_solver.c:1681-1687); out must hold strlen(deck_path)+5 bytes.        */

@@ -14,7 +14,9 @@
  * section gets the nodal stress in the file and the strain energy and the
  * reaction sums in the log (fea_host.h).  A deck with (modal :modes N ...)
  * then gets its N lowest natural frequencies at the final state in the log
- * and the mode shapes in the file (feahip_solve_modes).
+ * and the mode shapes in the file (feahip_solve_modes).  A deck with
+ * (buckling :modes N ...) then gets its N lowest buckling load factors in the
+ * log and their mode shapes in the file (feahip_solve_buckling).
  *
  * One option the reference does not have, after the deck name:
  *   --multigrid   PCG_ILU / CHOLESKY solves use the aggregation-multigrid
@@ -79,6 +81,10 @@ int main(int argc, char **argv)
       status = 1;
     } else if ((deck.modal_modes > 0 || deck.modal_count > 0) && (rc = fea_modal_run(&deck, ctx, stdout, msh))) {
       /* (modal :modes N ...): the natural frequencies at the state reached, the mode shapes behind the steps */
+      fprintf(stderr, "feasolve error encountered: %s\n", feahip_last_error(ctx));
+      status = 1;
+    } else if (deck.buckling_modes > 0 && (rc = fea_buckling_run(&deck, ctx, stdout, msh))) {
+      /* (buckling :modes N ...): the load factors at the state reached, the mode shapes behind everything else */
       fprintf(stderr, "feasolve error encountered: %s\n", feahip_last_error(ctx));
       status = 1;
     }

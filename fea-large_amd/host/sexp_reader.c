@@ -502,6 +502,18 @@ static int read_list(reader *r, fea_deck *d)
       if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "modal :max must be a non-negative integer");
       d->modal_max = (int)v;
     }
+  } else if (ieq(head, "buckling")) {                         /* no counterpart in the reference */
+    if (need_num(r, a, na, "modes", &v)) return -1;
+    if (!(v >= 1 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "buckling :modes must be an integer in [1, 8]");
+    d->buckling_modes = (int)v;
+    d->buckling_tolerance = 1e-8; d->buckling_max = 2000;
+    if (attr_get(a, na, "tolerance") && need_num(r, a, na, "tolerance", &d->buckling_tolerance)) return -1;
+    if (!(d->buckling_tolerance > 0 && d->buckling_tolerance <= 1.7976931348623157e308)) return fail(r, "buckling :tolerance must be positive");
+    if (attr_get(a, na, "max")) {
+      if (need_num(r, a, na, "max", &v)) return -1;
+      if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "buckling :max must be a non-negative integer");
+      d->buckling_max = (int)v;
+    }
   } else if (ieq(head, "body-force")) {
     if (need_num(r, a, na, "x", &d->body_force[0])) return -1;
     if (need_num(r, a, na, "y", &d->body_force[1])) return -1;
@@ -639,6 +651,8 @@ int fea_deck_save(const char *path, const fea_deck *d)
     if (d->modal_shift != 0.0) fprintf(f, " :shift %.17g", d->modal_shift);    /* (the old text without the new keys) */
     fprintf(f, ")");
   }
+  if (d->buckling_modes > 0)                                                   /* written only when asked for */
+    fprintf(f, "\n   (buckling :modes %d :tolerance %.17g :max %d)", d->buckling_modes, d->buckling_tolerance, d->buckling_max);
   fprintf(f, ")\n");
   fprintf(f, " (input-data\n  (geometry\n   (nodes");
   for (i = 0; i < d->nodes_count; ++i)

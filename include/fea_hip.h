@@ -710,6 +710,67 @@ int feahip_get_locked_count(feahip_ctx *ctx, int *count);
  * modes held from either solve are dropped.                                   */
 int feahip_modal_deflate(feahip_ctx *ctx, int n_locked, const double *q, const double *x8, double *out8);
 
+/* ---- linear buckling: load factors and modes from K and its geometric part ----
+ * feahip_solve_buckling: the n_modes lowest eigenpairs of
+ *     K_sigma(x) phi = nu K(x) phi          on the free dofs,
+ * by the blocked LOBPCG of feahip_solve_modes on another pencil.  A context that
+ * never calls the entries below allocates and launches nothing for them.
+ *   K        the tangent at the current nodes, assembled and masked as
+ *            feahip_solve_modes does it; positive definite at a stable
+ *            equilibrium.  K and f hold another matrix afterwards.
+ *   K_sigma  the geometric (initial-stress) part of that tangent as a matrix of
+ *            its own: the block of a node pair is sum_g vol_g (g_a . sigma_g g_b)
+ *            times the 3x3 identity, so ONE double per block of K's pattern,
+ *            assembled on the GPU at every call from the current nodes and the
+ *            material table in force (both models, all three element types).
+ * Model: along the load path K(gamma) ~ (K - K_sigma) + gamma K_sigma with
+ * gamma = 1 now; it is singular at
+ *     factor = 1 - 1/nu     for nu < 0,
+ *     factor = +infinity    for nu >= 0 (no buckling in this load direction),
+ * and the estimated critical load is `factor` times the load applied so far.
+ * At a small preload this is classical linear buckling.  The follower-pressure
+ * load stiffness is not part of the pencil (the library assembles none).
+ * nu[n_modes] (may be NULL) is ascending, so the finite factors come first and
+ * ascend; factor[n_modes] as above.  The modes are K-orthonormal
+ * (phi_i' K phi_j = delta_ij) and exactly 0 on the prescribed dofs.  The same
+ * input gives the same bits (the start block is feahip_solve_modes' hash).
+ * Converged: for every column j < n_modes, on fresh products at return,
+ *   ||K_sigma x_j - nu_j K x_j|| <= tolerance (||K_sigma x_j|| + |nu_j| ||K x_j||),
+ * the ratio resid[] (may be NULL) reports; *iters (may be NULL): the
+ * Rayleigh-Ritz steps.  After max_iterations steps: FEAHIP_ENOTCONVERGED with
+ * the pairs as they stand.  Preconditioner: the context's own, kind 0 or 1,
+ * which approximates K^-1 -- the natural one for this pencil.
+ * If x_j' K x_j of a column of the block is not positive, K is not positive
+ * definite at this state: FEAHIP_ENOTCONVERGED, and feahip_last_error says so
+ * and names a passed critical point as the likely reason (factor, nu, resid
+ * are NaN then).
+ * It needs NO mass, and a context that has one keeps it untouched.  Refused
+ * (FEAHIP_EINVAL) as feahip_solve_modes refuses: a transport, a row shard, a
+ * feahip_create_rank* context, preconditioner 2, fewer than 24 free dofs,
+ * n_modes outside [1, 8]; also tolerance <= 0, max_iterations < 0, null factor.
+ * Modes held by feahip_solve_modes / feahip_solve_modes_locked are dropped (and
+ * either of those solves drops the buckling modes).  Nothing is promised for
+ * an unstressed body, where all nu are of rounding size.  Not offered: more
+ * than eight modes, a sharded solve, a shift, a reference state other than the
+ * current one.
+ * Memory: feahip_solve_modes' nine block vectors, one double per block of K,
+ * and npe (npe + 1) / 2 doubles per element.
+ *
+ * feahip_get_buckling_modes: modes [first, first + count) of the last buckling
+ * solve (all eight columns are held), phi[count][3N] in the caller's dof order.
+ * FEAHIP_ESTATE before any solve, FEAHIP_EINVAL for a range outside [0, 8].    */
+int feahip_solve_buckling(feahip_ctx *ctx, int n_modes, double tolerance, int max_iterations,
+                          double *factor /*[n_modes]*/, double *nu /*[n_modes], may be NULL*/,
+                          double *resid /*[n_modes], may be NULL*/, int *iters /*may be NULL*/);
+int feahip_get_buckling_modes(feahip_ctx *ctx, int first, int count, double *phi /*[count][3N]*/);
+/* Test hook: y = K_sigma(current nodes) x, unmasked, host vectors [3N] in the
+ * caller's dof order.  K_sigma is assembled on each call; refused on sharded or
+ * rank contexts, as feahip_spmm_km is.                                         */
+int feahip_geometric_spmv(feahip_ctx *ctx, const double *x, double *y);
+/* Host-only (no device): factor[i] = 1 - 1/nu[i] for nu[i] < 0, +infinity
+ * otherwise (nu = 0, -0.0 and positive nu: no buckling in this direction).     */
+int feahip_host_buckling_factor(int n, const double *nu, double *factor);
+
 /* z = M^-1 r on every rank of the group at once, with the preconditioner the
  * group's PCG applies: r[k] and z[k] are rank k's [N_k][3] vectors as
  * feahip_apply_preconditioner takes them (the caller's node ids of context k;
@@ -983,7 +1044,9 @@ int feahip_sync(feahip_ctx *ctx);
  * nine block vectors recombined in place), 16 k_modal_deflate_gram and 17
  * k_modal_deflate_apply (one block vector against eight panels of the locked
  * store filled with the hash; with zero coefficients, so nothing moves); 13-17
- * refused without a mass and where feahip_solve_modes is.                     */
+ * refused without a mass and where feahip_solve_modes is; 18 k_geom_elements
+ * and 19 k_geom_blocks, the two passes of the geometric stiffness at the
+ * current nodes (refused where feahip_solve_buckling is; no mass needed).     */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
