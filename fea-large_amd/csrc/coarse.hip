@@ -208,7 +208,7 @@ int ensure_comm_stream(feahip_ctx *c)
   return FEAHIP_OK;
 }
 
-static int ensure_vred(feahip_ctx *c, size_t n)
+int ensure_vred(feahip_ctx *c, size_t n)
 {
   if (c->vred_cap >= n) return FEAHIP_OK;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));

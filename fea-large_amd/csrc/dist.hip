@@ -145,6 +145,36 @@ struct RcclTransport : Transport {
     FEA_HIP_CHECK(c, hipStreamWaitEvent(c->stream, c->ev_unpacked, 0));
     return FEAHIP_OK;
   }
+  // the halo rows of a block vector [3N][8] (the sharded modal solve, kernels_modal.hip): the same two halves with 24
+  // doubles per row through ModalState::d_bsend / d_brecv
+  int exchange_block_begin(std::vector<feahip_ctx *> &R, const std::vector<double *> &d_v8) override
+  {
+    feahip_ctx *c = R[0];
+    if (d_v8.size() != 1) { c->err = "block exchange: one block vector per context"; return FEAHIP_EINVAL; }
+    if (!c->comm_stream) {
+      FEA_HIP_CHECK(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
+      FEA_HIP_CHECK(c, hipEventCreateWithFlags(&c->ev_packed, hipEventDisableTiming));
+      FEA_HIP_CHECK(c, hipEventCreateWithFlags(&c->ev_unpacked, hipEventDisableTiming));
+    }
+    double *sb = c->modal.d_bsend, *rb = c->modal.d_brecv;
+    modal_enq_block_pack(c, d_v8[0]);
+    FEA_HIP_CHECK(c, hipEventRecord(c->ev_packed, c->stream));
+    FEA_HIP_CHECK(c, hipStreamWaitEvent(c->comm_stream, c->ev_packed, 0));
+    ncclResult_t r = ncclGroupStart();
+    if (r != ncclSuccess) return fail(c, "ncclGroupStart", r);
+    for (size_t k = 0; k < c->peer.size(); ++k) {
+      const size_t ns = (size_t)24 * (c->send_off[k + 1] - c->send_off[k]), nr = (size_t)24 * (c->recv_off[k + 1] - c->recv_off[k]);
+      if (ns && (r = ncclSend(sb + (size_t)24 * c->send_off[k], ns, ncclDouble, c->peer[k], comm, c->comm_stream)) != ncclSuccess)
+        return fail(c, "ncclSend", r);
+      if (nr && (r = ncclRecv(rb + (size_t)24 * c->recv_off[k], nr, ncclDouble, c->peer[k], comm, c->comm_stream)) != ncclSuccess)
+        return fail(c, "ncclRecv", r);
+    }
+    if ((r = ncclGroupEnd()) != ncclSuccess) return fail(c, "ncclGroupEnd", r);
+    modal_enq_block_unpack_on(c, d_v8[0], c->comm_stream);
+    FEA_HIP_CHECK(c, hipEventRecord(c->ev_unpacked, c->comm_stream));
+    return FEAHIP_OK;
+  }
+  int exchange_block_end(std::vector<feahip_ctx *> &R) override { return exchange_end(R); }
   int allreduce(std::vector<feahip_ctx *> &R, int slot, int n) override
   {
     feahip_ctx *c = R[0];

@@ -1239,13 +1239,17 @@ extern "C" int feahip_solve_modes(feahip_ctx *c, int n_modes, double tol, int ma
 extern "C" int feahip_get_modes(feahip_ctx *c, int first, int count, double *phi)
 {
   CTX_GUARD_NOK(c);
-  if (!c->modal.have) { c->err = "get_modes: no modes held (feahip_solve_modes first)"; return FEAHIP_ESTATE; }
+  if (!c->modal.have && !c->modal.have_sharded) { c->err = "get_modes: no modes held (feahip_solve_modes first)"; return FEAHIP_ESTATE; }
   if (first < 0 || count < 0 || first + count > FEA_MODAL_COLS) { c->err = "get_modes: modes [first, first + count) outside the eight held"; return FEAHIP_EINVAL; }
   if (!phi) { c->err = "get_modes: null phi"; return FEAHIP_EINVAL; }
   std::vector<double> tmp((size_t)c->ndof);
   for (int k = 0; k < count; ++k) {
     const int rc = modal_get(c, first + k, tmp.data());
     if (rc) return rc;
+    if (c->modal.have_sharded) {                                       // a sharded solve: the rank's own rows, zero elsewhere
+      std::fill(tmp.begin(), tmp.begin() + (size_t)3 * c->row0, 0.0);
+      std::fill(tmp.begin() + (size_t)3 * c->row1, tmp.end(), 0.0);
+    }
     double *out = phi + (size_t)k * c->ndof;
     for (int a = 0; a < c->N; ++a)
       for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
@@ -1271,6 +1275,72 @@ extern "C" int feahip_spmm_km(feahip_ctx *c, const double *x8, double *y8, doubl
     if ((rc = launch_modal_pack(c, v + (which ? 6 : 3) * n8, v + n8, 1))) return rc;
     for (int k = 0; k < FEA_MODAL_COLS; ++k)
       if ((rc = get_node_vec(c, v + n8 + (size_t)k * n, (which ? z8 : y8) + (size_t)k * n))) return rc;
+  }
+  return FEAHIP_OK;
+}
+
+// ---- the same solve over the ranks of a sharded run (modal_solve_dist, kernels_modal.hip) ------------------------------
+extern "C" int feahip_solve_modes_sharded(feahip_ctx *c, int n_modes, double tol, int max_iter, int warm, double *lambda,
+                                          double *resid, int *iters)
+{
+  CTX_GUARD(c);
+  if (iters) *iters = 0;
+  if (n_modes < 1 || n_modes > FEA_MODAL_COLS) { c->err = "solve_modes_sharded: n_modes must be in [1, 8]"; return FEAHIP_EINVAL; }
+  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_modes_sharded: tolerance must be positive"; return FEAHIP_EINVAL; }
+  if (max_iter < 0) { c->err = "solve_modes_sharded: max_iterations must not be negative"; return FEAHIP_EINVAL; }
+  if (!lambda) { c->err = "solve_modes_sharded: null lambda"; return FEAHIP_EINVAL; }
+  if (!c->tr) {
+    c->err = "solve_modes_sharded: the context has no transport (feahip_group_init, feahip_comm_init); feahip_solve_modes solves on one context";
+    return FEAHIP_EINVAL;
+  }
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  for (feahip_ctx *r : R) { CTX_GUARD(r); }
+  return surface_error(c, R, modal_solve_dist(R, n_modes, tol, max_iter, warm, lambda, resid, iters));
+}
+
+// the rows a sharded context owns of a device vector in library ids, into the caller's dof order; zero elsewhere
+static int get_owned_node_vec(feahip_ctx *c, const double *d, double *h)
+{
+  std::vector<double> tmp((size_t)c->ndof, 0.0);
+  int rc;
+  if (c->row1 > c->row0 &&
+      (rc = get_vec(c, d + (size_t)3 * c->row0, tmp.data() + (size_t)3 * c->row0, (size_t)3 * (c->row1 - c->row0)))) return rc;
+  for (int a = 0; a < c->N; ++a)
+    for (int j = 0; j < 3; ++j) h[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_group_spmm_km(feahip_ctx **ctxs, int n, const double *const *x8, double *const *y8, double *const *z8)
+{
+  std::vector<feahip_ctx *> R;
+  int rc = group_vec(ctxs, n, R);
+  if (rc) return rc;
+  if (!x8 || !y8 || !z8) return FEAHIP_EINVAL;
+  for (int k = 0; k < n; ++k) {
+    feahip_ctx *c = R[k];
+    if (!x8[k] || !y8[k] || !z8[k]) return FEAHIP_EINVAL;
+    CTX_GUARD(c);
+    if ((rc = surface_error(R[0], R, mass_ensure(c, "group_spmm_km")))) return rc;
+    if (!c->k_valid) { R[0]->err = c->err = "group_spmm_km: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
+    if ((rc = surface_error(R[0], R, ensure_modal_dist(c)))) return rc;
+    c->modal.have = c->modal.have_sharded = false;                     // the block vectors are scratch here
+    const size_t nd = (size_t)c->ndof, n8 = nd * FEA_MODAL_COLS;
+    double *v = c->modal.d_v;                                          // X, W <- the host layout, KX, MX <- the products
+    for (int q = 0; q < FEA_MODAL_COLS; ++q)
+      if ((rc = set_node_vec(c, v + n8 + (size_t)q * nd, x8[k] + (size_t)q * nd))) return rc;
+    if ((rc = launch_modal_pack(c, v + n8, v, 0))) return rc;
+  }
+  if ((rc = surface_error(R[0], R, modal_spmm_km_dist(R)))) return rc;
+  for (int k = 0; k < n; ++k) {
+    feahip_ctx *c = R[k];
+    FEA_HIP_CHECK(c, hipSetDevice(c->device));
+    const size_t nd = (size_t)c->ndof, n8 = nd * FEA_MODAL_COLS;
+    double *v = c->modal.d_v;
+    for (int which = 0; which < 2; ++which) {
+      if ((rc = launch_modal_pack(c, v + (which ? 6 : 3) * n8, v + n8, 1))) return rc;
+      for (int q = 0; q < FEA_MODAL_COLS; ++q)
+        if ((rc = get_owned_node_vec(c, v + n8 + (size_t)q * nd, (which ? z8[k] : y8[k]) + (size_t)q * nd))) return rc;
+    }
   }
   return FEAHIP_OK;
 }

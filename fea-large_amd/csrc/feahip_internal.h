@@ -458,7 +458,15 @@ struct ModalState {
   int lock_order[64] = {0};            // mode j of the ascending lambda is column lock_order[j] of the store
   bool have_locked = false;            // the store holds the modes of a locked solve (feahip_get_locked_modes)
   bool have_buckling = false;          // X holds the buckling modes of feahip_solve_buckling (feahip_get_buckling_modes)
-  void release() { dev_free({d_v, d_part, d_small, d_lock, d_lpart, d_lcoef}); *this = ModalState(); }
+  // the sharded solve (feahip_solve_modes_sharded, feahip_group_spmm_km): nothing of it exists until one of them is called
+  double *d_bsend = nullptr, *d_brecv = nullptr;   // [24 nsend], [24 nrecv]: halo rows of a block vector, 192 bytes each
+  int *d_key = nullptr;                // [row1 - row0] the whole-mesh node of every owned row (rank contexts; null: row0 + a)
+  int blk_nsend = -1, blk_nrecv = -1;  // the halo plan the buffers were allocated for
+  int key_row0 = -1, key_row1 = -1;    // the rows d_key and n_free_own were built for
+  int n_free_own = 0;                  // free dofs among the owned rows
+  bool have_sharded = false;           // X holds, on the rows [sh_row0, sh_row1), the modes of a finished sharded solve
+  int sh_row0 = -1, sh_row1 = -1;
+  void release() { dev_free({d_v, d_part, d_small, d_lock, d_lpart, d_lcoef, d_bsend, d_brecv, d_key}); *this = ModalState(); }
 };
 
 // linear buckling (kernels_buckling.hip): nothing of it exists until feahip_solve_buckling (or one of its hooks,
@@ -671,6 +679,16 @@ int launch_modal_pack(feahip_ctx *c, const double *d_in, double *d_out, int unpa
 int time_modal_prepare(feahip_ctx *c);                                  // the nine vectors filled for feahip_time_kernel 13-15
 int time_modal_kernel(feahip_ctx *c, int what);
 int modal_ritz(int ns, const double *GM, const double *GK, int m, double *theta, double *C);   // host only
+// the same solve over the ranks R of a sharded run (collective); the block product over the ranks for the test hook
+int modal_solve_dist(std::vector<feahip_ctx *> &R, int n_modes, double tol, int max_it, int warm, double *lambda,
+                     double *resid, int *iters);
+int modal_spmm_km_dist(std::vector<feahip_ctx *> &R);                   // [KX, MX] <- [K X, mask(M X)] on the owned rows, X's halo rows exchanged
+int ensure_modal_dist(feahip_ctx *c);                                   // ensure_modal, the block halo buffers and the row keys
+// the halo rows of a block vector [3N][8], twelve 16-byte lanes per row: into ModalState::d_bsend on the context's
+// stream, out of d_brecv on `stream`, and (test knob) NaN into the halo rows on the context's stream
+void modal_enq_block_pack(feahip_ctx *c, const double *d_v8);
+void modal_enq_block_unpack_on(feahip_ctx *c, double *d_v8, hipStream_t stream);
+void modal_enq_block_poison(feahip_ctx *c, double *d_v8);
 // the same pencil with a shift, in sweeps of the eight-column block with hard locking: up to FEA_MODAL_MAX_LOCKED modes
 int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int max_it, double *lambda, double *resid,
                        int *iters, int *sweeps);
@@ -780,6 +798,7 @@ int build_rank_mesh_local(int rank, int nranks, int n_global, int n_local, int n
 // the library's numbering of the LOCAL mesh, split stably into owned first, halo after; true when it reorders
 int slab_order(int n_local, int n_own, int E, int npe, const int *elements, const double *nodes0, int *new_local_id);
 int install_plan(feahip_ctx *c, const ShardPlan &plan);      // dist.hip: halo lists to the device, interior chunk range
+int ensure_vred(feahip_ctx *c, size_t n);                    // coarse.hip: d_vred holds at least n doubles
 
 // multi-rank operations (kernels_solve.hip; the step loops in drivers.hip).  R = the ranks driven by this
 // process: one context with the RCCL transport, or all contexts of an
@@ -793,6 +812,10 @@ struct Transport {
   // one), end() makes the context's stream wait for the halo rows.  Work enqueued between the two must not read them.
   virtual int exchange_begin(std::vector<feahip_ctx *> &R, int which) { return exchange(R, which); }
   virtual int exchange_end(std::vector<feahip_ctx *> &R) { (void)R; return FEAHIP_OK; }
+  // the halo rows of a block vector [3N][8] per context of R (d_v8[k] belongs to R[k]) from their owners, through
+  // ModalState::d_bsend / d_brecv (ensure_modal_dist): the two halves of exchange_begin / exchange_end, same events
+  virtual int exchange_block_begin(std::vector<feahip_ctx *> &R, const std::vector<double *> &d_v8) = 0;
+  virtual int exchange_block_end(std::vector<feahip_ctx *> &R) = 0;
   // d_scal[8+slot .. 8+slot+n) summed over all ranks, result on every rank
   virtual int allreduce(std::vector<feahip_ctx *> &R, int slot, int n) = 0;
   // the same with the maximum over all ranks (order-independent: reproducible on any transport)

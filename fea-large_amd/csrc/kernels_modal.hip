@@ -29,6 +29,13 @@
 //   k_modal_deflate_apply   W -= Q C: one read of W and of every Q panel in use, one write of W
 // The store exists on a context that called feahip_solve_modes_locked (or feahip_modal_deflate, feahip_time_kernel
 // 16-17) and on no other.
+//
+// Over the ranks of a sharded run (feahip_solve_modes_sharded, modal_solve_dist at the end of this file): the same step
+// with every rank on the rows it owns.  The sums, the combination and the residual take the owned range [row0, row1);
+// the halo rows of X and W travel as rows of 192 bytes (k_block_halo_pack / k_block_halo_unpack, Transport::
+// exchange_block_begin / _end) under the product of the chunks that read no halo column; the 24 + 768 sums are
+// all-reduced (Transport::allreduce_vec) before the one Rayleigh-Ritz step.  The block halo buffers and the row keys
+// of the start block exist on a context that called the sharded solve (or feahip_group_spmm_km) and on no other.
 #include "feahip_internal.h"
 #include "reduce_device.h"
 #include <cmath>
@@ -284,14 +291,58 @@ void k_modal_residual(int N, const double *__restrict__ KX, const double *__rest
 }
 
 // the start block: a fixed integer hash of (library dof index, column) mapped to [-1, 1), zero on the prescribed dofs
+__device__ __forceinline__ double modal_hash_value(uint32_t dof, uint32_t col)
+{
+  uint32_t h = dof * 0x9E3779B1u ^ (col + 1u) * 0x85EBCA77u;
+  h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+  return (double)h * (1.0 / 2147483648.0) - 1.0;
+}
 __global__ __launch_bounds__(256)
 void k_modal_hash(size_t n8, const uint8_t *__restrict__ mask, double *__restrict__ X)
 {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= n8) return;
-  uint32_t h = (uint32_t)(e >> 3) * 0x9E3779B1u ^ ((uint32_t)(e & 7) + 1u) * 0x85EBCA77u;
-  h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
-  X[e] = mask[e >> 3] ? 0.0 : (double)h * (1.0 / 2147483648.0) - 1.0;
+  X[e] = mask[e >> 3] ? 0.0 : modal_hash_value((uint32_t)(e >> 3), (uint32_t)(e & 7));
+}
+// the same on the owned rows of a sharded context, keyed by the node's identity in the whole mesh (key[a] for the a-th
+// owned row; null: row0 + a, the library id of a row shard), so that the start block does not depend on the cut.
+// mask and X point at the first owned row.
+__global__ __launch_bounds__(256)
+void k_modal_hash_rows(int nrows, int row0, const int *__restrict__ key, const uint8_t *__restrict__ mask, double *__restrict__ X)
+{
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)nrows * 24) return;
+  const int a = (int)(e / 24), j = (int)((e >> 3) % 3);
+  const uint32_t node = (uint32_t)(key ? key[a] : row0 + a);
+  X[e] = mask[e >> 3] ? 0.0 : modal_hash_value(node * 3u + (uint32_t)j, (uint32_t)(e & 7));
+}
+
+// ------------------------------------------------------------------------
+// Halo rows of a block vector (the sharded solve).  A node's three dofs are 24 contiguous doubles of the [3N][8]
+// layout: a row travels as twelve 16-byte lanes, lane t of the launch moves lane t % 12 of row t / 12, so a wave reads
+// and writes runs of 192 contiguous bytes.  buf: [n][24].
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void k_block_halo_pack(int n, const int *__restrict__ idx, const v2d *__restrict__ v, v2d *__restrict__ buf)
+{
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * 12) return;
+  buf[t] = v[(size_t)idx[t / 12] * 12 + t % 12];
+}
+__global__ __launch_bounds__(256)
+void k_block_halo_unpack(int n, const int *__restrict__ idx, const v2d *__restrict__ buf, v2d *__restrict__ v)
+{
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * 12) return;
+  v[(size_t)idx[t / 12] * 12 + t % 12] = buf[t];
+}
+// test knob of the in-process transport (FEAHIP_TEST_POISON_HALO): the halo rows become NaN
+__global__ __launch_bounds__(256)
+void k_block_halo_poison(int n, const int *__restrict__ idx, v2d *__restrict__ v)
+{
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)n * 12) return;
+  v[(size_t)idx[t / 12] * 12 + t % 12] = v2d{__builtin_nan(""), __builtin_nan("")};
 }
 
 // a column out of a block vector, and a vector (a multigrid cycle's result) into one, zero on the prescribed dofs
@@ -428,11 +479,7 @@ void k_modal_advance(int ndof, int drop, int id0, const uint8_t *__restrict__ ma
     double v = 0.0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) if (k == j + drop) v = x[k];
-    if (j + drop >= 8) {
-      uint32_t h = (uint32_t)d * 0x9E3779B1u ^ ((uint32_t)(id0 + j + drop - 8) + 1u) * 0x85EBCA77u;
-      h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
-      v = fixed ? 0.0 : (double)h * (1.0 / 2147483648.0) - 1.0;
-    }
+    if (j + drop >= 8) v = fixed ? 0.0 : modal_hash_value((uint32_t)d, (uint32_t)(id0 + j + drop - 8));
     X[(size_t)d * 8 + j] = v;
   }
 }
@@ -446,14 +493,19 @@ static int spmm_grid(const feahip_ctx *c)
   const int g = (c->nchunks_local + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
   return g < RB ? (g > 0 ? g : 1) : RB;
 }
+// The sums, the combination and the residual run on the rows the context owns, [row0, row1): all of them on an
+// unsharded context, where these are the launches they always were (base pointers + 0, the same counts and grids).
+static inline int own_nodes(const feahip_ctx *c) { return c->row1 - c->row0; }
+static inline int own_dofs(const feahip_ctx *c) { return 3 * (c->row1 - c->row0); }
+static inline size_t own_off8(const feahip_ctx *c) { return (size_t)3 * c->row0 * MC; }   // of row0 in a block vector
 static int gram_grid(const feahip_ctx *c)
 {
-  const int g = (c->ndof + GRAM_DOFS - 1) / GRAM_DOFS;
+  const int g = (own_dofs(c) + GRAM_DOFS - 1) / GRAM_DOFS;
   return g < RB ? (g > 0 ? g : 1) : RB;
 }
 static int resid_grid(const feahip_ctx *c)
 {
-  const int g = (c->N + 31) / 32;
+  const int g = (own_nodes(c) + 31) / 32;
   return g < RB ? (g > 0 ? g : 1) : RB;
 }
 
@@ -461,6 +513,7 @@ int ensure_modal(feahip_ctx *c)
 {
   ModalState &S = c->modal;
   S.have_buckling = false;                                            // every caller makes the block its own
+  S.have_sharded = false;                                             // (ensure_modal_dist keeps it for the sharded solve)
   if (S.d_v) return FEAHIP_OK;
   const size_t n8 = (size_t)c->ndof * MC;
   FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_v, sizeof(double) * 9 * n8));
@@ -494,13 +547,14 @@ int launch_spmm_km(feahip_ctx *c, const double *d_x8, double *d_y8, double *d_z8
 
 static void enq_gram(feahip_ctx *c, int np)
 {
-  hipLaunchKernelGGL(k_modal_gram, dim3(gram_grid(c)), dim3(256), 0, c->stream, c->ndof, np, (const double *)c->modal.d_v,
-                     (size_t)c->ndof * MC, c->modal.d_part);
+  hipLaunchKernelGGL(k_modal_gram, dim3(gram_grid(c)), dim3(256), 0, c->stream, own_dofs(c), np,
+                     (const double *)(c->modal.d_v + own_off8(c)), (size_t)c->ndof * MC, c->modal.d_part);
 }
 static void enq_combine(feahip_ctx *c, int np, int write_p)
 {
-  hipLaunchKernelGGL(k_modal_combine, dim3((c->ndof + 255) / 256, 3), dim3(256), 0, c->stream, c->ndof, np, write_p,
-                     c->modal.d_v, (size_t)c->ndof * MC, (const double *)(c->modal.d_small + MODAL_SUMS));
+  if (own_dofs(c) <= 0) return;                                       // (a rank without rows)
+  hipLaunchKernelGGL(k_modal_combine, dim3((own_dofs(c) + 255) / 256, 3), dim3(256), 0, c->stream, own_dofs(c), np, write_p,
+                     c->modal.d_v + own_off8(c), (size_t)c->ndof * MC, (const double *)(c->modal.d_small + MODAL_SUMS));
 }
 // sums [e0, e0 + n) of d_part reduced into d_small and read into h (one synchronisation)
 static int read_sums(feahip_ctx *c, int e0, int n, double *h)
@@ -656,18 +710,22 @@ static int enq_residual(feahip_ctx *c, bool precond)
 {
   ModalState &S = c->modal;
   const bool amg = c->precond == 1;
-  hipLaunchKernelGGL(k_modal_residual, dim3(resid_grid(c)), dim3(256), 0, c->stream, c->N, (const double *)mv(c, V_KX),
-                     (const double *)mv(c, V_MX), (const double *)(S.d_small + MODAL_SUMS + 24 * 16),
-                     (precond && !amg) ? (const double *)c->d_minv : (const double *)nullptr, (const uint8_t *)c->d_dofmask,
-                     mv(c, V_W), S.d_part);
+  const size_t o8 = own_off8(c), o = (size_t)3 * c->row0;
+  hipLaunchKernelGGL(k_modal_residual, dim3(resid_grid(c)), dim3(256), 0, c->stream, own_nodes(c),
+                     (const double *)(mv(c, V_KX) + o8), (const double *)(mv(c, V_MX) + o8),
+                     (const double *)(S.d_small + MODAL_SUMS + 24 * 16),
+                     (precond && !amg) ? (const double *)(c->d_minv + 3 * o) : (const double *)nullptr,
+                     (const uint8_t *)(c->d_dofmask + o), mv(c, V_W) + o8, S.d_part);
   if (precond && amg) {
-    // one W-cycle per column: its residual out of the block, the cycle, its result into the block (enq_cycle2)
-    const size_t n = (size_t)c->ndof;
+    // one W-cycle per column: its residual out of the block, the cycle, its result into the block (enq_cycle2); on
+    // a sharded context the cycle is the rank's own (its diagonal block of K), as in the sharded PCG
+    const size_t n = (size_t)own_dofs(c);
     for (int col = 0; col < MC; ++col) {
-      hipLaunchKernelGGL(k_modal_extract, g256(n), dim3(256), 0, c->stream, n, (const double *)mv(c, V_W), col, c->d_r);
+      hipLaunchKernelGGL(k_modal_extract, g256(n), dim3(256), 0, c->stream, n, (const double *)(mv(c, V_W) + o8), col, c->d_r + o);
       const double *zv = amg_apply(c, c->d_r);
       if (!zv) return FEAHIP_EHIP;
-      hipLaunchKernelGGL(k_modal_insert, g256(n), dim3(256), 0, c->stream, n, zv, (const uint8_t *)c->d_dofmask, col, mv(c, V_W));
+      hipLaunchKernelGGL(k_modal_insert, g256(n), dim3(256), 0, c->stream, n, zv + o, (const uint8_t *)(c->d_dofmask + o), col,
+                         mv(c, V_W) + o8);
     }
   }
   FEA_HIP_CHECK(c, hipGetLastError());
@@ -1031,4 +1089,298 @@ int modal_get_locked(feahip_ctx *c, int mode, double *h_lib /*[3N], library ids*
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_lib, c->d_q, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return FEAHIP_OK;
+}
+
+// ---- the base solve over the ranks of a sharded run (feahip_solve_modes_sharded) ----------------------------------------
+// modal_solve step for step on R = the ranks this process drives (all members of an in-process group, or the one
+// context of an RCCL rank).  Every rank keeps the nine block vectors of its own context; a vector is authoritative on
+// the owned rows [row0, row1), and the halo rows of X and W hold what the block exchange last brought.  Per step:
+//   residual, preconditioner          owned rows; kind 1: one W-cycle per column on the rank's own diagonal block
+//   exchange_block_begin(W)           pack on the context's stream, copies and unpack on the communication stream
+//   k_spmm_km on the interior chunks  they read no halo column (install_plan), so they run under the exchange
+//   exchange_block_end, k_spmm_km on the chunks before and after the interior range
+//   k_modal_gram, k_modal_reduce      owned rows; 24 + 768 sums into d_small, copied into d_vred
+//   Transport::allreduce_vec          792 doubles; in a group the sums meet on the host in rank order
+//   (one read-back; modal_ritz once on the all-reduced sums; C and theta uploaded to every rank of R)
+//   k_modal_combine                   owned rows
+// Every branch below depends on the all-reduced sums alone, so all ranks take it together.
+int ensure_modal_dist(feahip_ctx *c)
+{
+  int rc;
+  ModalState &S = c->modal;
+  const bool held = S.have_sharded;
+  if ((rc = ensure_modal(c))) return rc;
+  S.have_sharded = held;
+  if (!S.d_bsend || S.blk_nsend != c->nsend || S.blk_nrecv != c->nrecv) {
+    FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    if (c->comm_stream) FEA_HIP_CHECK(c, hipStreamSynchronize(c->comm_stream));
+    dev_free({S.d_bsend, S.d_brecv});
+    S.d_bsend = S.d_brecv = nullptr; S.blk_nsend = S.blk_nrecv = -1;
+    FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_bsend, sizeof(double) * 24 * (size_t)(c->nsend ? c->nsend : 1)));
+    FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_brecv, sizeof(double) * 24 * (size_t)(c->nrecv ? c->nrecv : 1)));
+    S.blk_nsend = c->nsend; S.blk_nrecv = c->nrecv;
+  }
+  if (S.key_row0 != c->row0 || S.key_row1 != c->row1) {
+    FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    dev_free({S.d_key});
+    S.d_key = nullptr; S.key_row0 = S.key_row1 = -1;
+    S.have_sharded = false;                                             // whatever X holds, it was for other rows
+    const int n = own_nodes(c);
+    if (c->rank_own >= 0 && n > 0) {                                    // a rank context: the caller's id in the whole mesh
+      std::vector<int> key((size_t)n);
+      for (int a = 0; a < n; ++a) {
+        const int lib = c->row0 + a;
+        key[(size_t)a] = c->rank_node_global[(size_t)(c->iperm.empty() ? lib : c->iperm[(size_t)lib])];
+      }
+      FEA_HIP_CHECK(c, hipMalloc((void **)&S.d_key, sizeof(int) * (size_t)n));
+      FEA_HIP_CHECK(c, hipMemcpy(S.d_key, key.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    std::vector<uint8_t> hm((size_t)3 * (n > 0 ? n : 0));
+    if (!hm.empty()) {
+      FEA_HIP_CHECK(c, hipMemcpyAsync(hm.data(), c->d_dofmask + (size_t)3 * c->row0, hm.size(), hipMemcpyDeviceToHost, c->stream));
+      FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    }
+    S.n_free_own = 0;
+    for (uint8_t b : hm) S.n_free_own += b ? 0 : 1;
+    S.key_row0 = c->row0; S.key_row1 = c->row1;
+  }
+  return FEAHIP_OK;
+}
+
+void modal_enq_block_pack(feahip_ctx *c, const double *d_v8)
+{
+  if (c->nsend <= 0) return;
+  hipLaunchKernelGGL(k_block_halo_pack, g256((size_t)c->nsend * 12), dim3(256), 0, c->stream, c->nsend,
+                     (const int *)c->d_send_idx, (const v2d *)d_v8, (v2d *)c->modal.d_bsend);
+}
+void modal_enq_block_unpack_on(feahip_ctx *c, double *d_v8, hipStream_t stream)
+{
+  if (c->nrecv <= 0) return;
+  hipLaunchKernelGGL(k_block_halo_unpack, g256((size_t)c->nrecv * 12), dim3(256), 0, stream, c->nrecv,
+                     (const int *)c->d_recv_idx, (const v2d *)c->modal.d_brecv, (v2d *)d_v8);
+}
+void modal_enq_block_poison(feahip_ctx *c, double *d_v8)
+{
+  if (c->nrecv <= 0) return;
+  hipLaunchKernelGGL(k_block_halo_poison, g256((size_t)c->nrecv * 12), dim3(256), 0, c->stream, c->nrecv,
+                     (const int *)c->d_recv_idx, (v2d *)d_v8);
+}
+
+// k_spmm_km on the chunks [first, first + n) of the rank: a row's sums are formed by one wave in block order, so the
+// cut of the launches changes no bit
+static void enq_spmm_chunks(feahip_ctx *c, int first, int n, const double *d_x8, double *d_y8, double *d_z8)
+{
+  if (n <= 0) return;
+  const int g = (n + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
+  hipLaunchKernelGGL(k_spmm_km, dim3(g < RB ? g : RB), dim3(256), 0, c->stream, c->chunk0 + first, n, c->d_chunk, c->d_rowptr,
+                     c->d_colidx, (const double *)c->d_K, (const double *)c->mass.d_m, (const uint8_t *)c->d_dofmask,
+                     (const v2d *)d_x8, (v2d *)d_y8, (v2d *)d_z8);
+}
+
+// [vector jy, vector jz] <- [K, mask(M)] vector jx on the owned rows of every rank, the halo rows of jx by exchange
+static int products_dist(std::vector<feahip_ctx *> &R, Transport *T, int jx, int jy, int jz)
+{
+  int rc;
+  std::vector<double *> xs;
+  for (feahip_ctx *c : R) xs.push_back(mv(c, jx));
+  if ((rc = T->exchange_block_begin(R, xs))) return rc;
+  FOR_RANKS(c) enq_spmm_chunks(c, c->ichunk_lo, c->ichunk_hi - c->ichunk_lo, mv(c, jx), mv(c, jy), mv(c, jz));
+  if ((rc = T->exchange_block_end(R))) return rc;
+  FOR_RANKS(c) {
+    enq_spmm_chunks(c, 0, c->ichunk_lo, mv(c, jx), mv(c, jy), mv(c, jz));
+    enq_spmm_chunks(c, c->ichunk_hi, c->nchunks_local - c->ichunk_hi, mv(c, jx), mv(c, jy), mv(c, jz));
+    FEA_HIP_CHECK(c, hipGetLastError());
+  }
+  return FEAHIP_OK;
+}
+
+int modal_spmm_km_dist(std::vector<feahip_ctx *> &R) { return products_dist(R, R[0]->tr, V_X, V_KX, V_MX); }
+
+// n doubles per rank (host, rank k's at h[k n]) summed over all ranks into out: through d_vred and the transport
+static int allreduce_host(std::vector<feahip_ctx *> &R, Transport *T, int n, const double *h, double *out)
+{
+  int rc;
+  size_t k = 0;
+  FOR_RANKS(c) {
+    FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_vred, h + (k++) * n, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  }
+  if ((rc = T->allreduce_vec(R, (size_t)n, false))) return rc;
+  feahip_ctx *c0 = R[0];
+  (void)hipSetDevice(c0->device);
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(out, c0->d_vred, sizeof(double) * n, hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  return FEAHIP_OK;
+}
+
+// the sums [e0, e0 + n) of every rank reduced into its d_small, copied into d_vred, summed over the ranks and read
+// into h + e0 (one synchronisation): every rank holds, and this process reads, the same bits
+static int read_sums_dist(std::vector<feahip_ctx *> &R, Transport *T, int e0, int n, double *h)
+{
+  int rc;
+  FOR_RANKS(c) {
+    hipLaunchKernelGGL(k_modal_reduce, dim3(n), dim3(256), 0, c->stream, e0, resid_grid(c), gram_grid(c),
+                       (const double *)c->modal.d_part, c->modal.d_small);
+    FEA_HIP_CHECK(c, hipGetLastError());
+    FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_vred, c->modal.d_small + e0, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if ((rc = T->allreduce_vec(R, (size_t)n, false))) return rc;
+  feahip_ctx *c0 = R[0];
+  (void)hipSetDevice(c0->device);
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(h + e0, c0->d_vred, sizeof(double) * n, hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  return FEAHIP_OK;
+}
+
+int modal_solve_dist(std::vector<feahip_ctx *> &R, int n_modes, double tol, int max_it, int warm, double *lambda,
+                     double *resid, int *iters)
+{
+  int rc;
+  Transport *T = R[0]->tr;
+  feahip_ctx *c0 = R[0];
+  auto refuse = [&](int code, const std::string &why) { for (feahip_ctx *c : R) c->err = "solve_modes_sharded: " + why; return code; };
+  // What decides a refusal is all-reduced, so that every rank of the run returns the same code: the free dofs, the
+  // ranks that hold modes of a sharded solve on their current rows, the preconditioner kinds, a missing mass
+  enum { Q_FREE, Q_HAVE, Q_KIND1, Q_KIND2, Q_NOMASS, Q_RANKS, Q_N };
+  std::vector<double> q((size_t)Q_N * R.size(), 0.0);
+  double tot[Q_N];
+  std::string mass_err;
+  {
+    size_t k = 0;
+    FOR_RANKS(c) {
+      double *qk = q.data() + (k++) * Q_N;
+      if ((rc = ensure_vred(c, MODAL_SUMS))) return rc;
+      const int rm = mass_ensure(c, "solve_modes_sharded");
+      if (rm && rm != FEAHIP_ESTATE) return rm;
+      if (rm) { qk[Q_NOMASS] = 1.0; if (mass_err.empty()) mass_err = c->err; }
+      else if ((rc = ensure_modal_dist(c))) return rc;
+      ModalState &S = c->modal;
+      qk[Q_FREE] = rm ? 0.0 : (double)S.n_free_own;
+      qk[Q_HAVE] = (!rm && S.have_sharded && S.sh_row0 == c->row0 && S.sh_row1 == c->row1) ? 1.0 : 0.0;
+      qk[Q_KIND1] = c->precond == 1 ? 1.0 : 0.0;
+      qk[Q_KIND2] = c->precond == 2 ? 1.0 : 0.0;
+      qk[Q_RANKS] = 1.0;
+    }
+  }
+  if ((rc = allreduce_host(R, T, Q_N, q.data(), tot))) return rc;
+  if (tot[Q_NOMASS] > 0.0) {
+    for (feahip_ctx *c : R) c->err = !mass_err.empty() ? mass_err : "solve_modes_sharded: no mass, or a stale one, on another rank of the run (feahip_set_mass)";
+    return FEAHIP_ESTATE;
+  }
+  if (tot[Q_KIND2] > 0.0) return refuse(FEAHIP_EINVAL, "preconditioner 2 (coarse level across the ranks) is not supported");
+  if (tot[Q_KIND1] != 0.0 && tot[Q_KIND1] != tot[Q_RANKS]) return refuse(FEAHIP_EINVAL, "the ranks' preconditioner kinds differ (feahip_set_preconditioner: the same kind on every rank)");
+  if (tot[Q_FREE] < 3 * MC)
+    return refuse(FEAHIP_EINVAL, std::to_string((long long)tot[Q_FREE]) + " free dofs, fewer than the 24 the block of eight columns needs");
+  const bool have = tot[Q_HAVE] == tot[Q_RANKS];
+  for (feahip_ctx *c : R) { c->modal.have = false; c->modal.have_sharded = false; }   // the block is this solve's from here on
+
+  // K(x), masked as the PCG sees it (K and f are another matrix from here on: k_epoch)
+  FOR_RANKS(c) { if ((rc = feahip_create_stiffness(c)) || (rc = feahip_apply_prescribed_bc(c, 0.0))) return rc; }
+  FOR_RANKS(c) {
+    if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
+    else enq_precond_blockjacobi(c);
+  }
+  ModalState &S0 = c0->modal;                           // the host side of the step lives on the first rank driven here
+  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
+  double *theta = S0.theta;
+  S0.h_C.assign(24 * 16 + MC, 0.0);
+  auto products_x = [&]() { return products_dist(R, T, V_X, V_KX, V_MX); };
+  auto upload = [&]() -> int {                        // C and theta to every rank (h_C is not touched again before the next read-back)
+    for (int j = 0; j < MC; ++j) S0.h_C[24 * 16 + j] = theta[j];
+    FOR_RANKS(c) {
+      FEA_HIP_CHECK(c, hipMemcpyAsync(c->modal.d_small + MODAL_SUMS, S0.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
+    }
+    return FEAHIP_OK;
+  };
+  auto converged = [&]() {                            // modal_solve's stop test on the all-reduced norms
+    bool ok = true;
+    for (int j = 0; j < MC; ++j) {
+      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
+      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
+      if (j < n_modes && !(ratio[j] <= tol)) ok = false;
+    }
+    return ok;
+  };
+  auto ritz = [&](int np, int *rank) -> bool {        // once for all ranks of R
+    unpack_gram(sums + MODAL_NORMS, np, GM, GK);
+    double Cs[24 * 16];
+    const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
+    if (r < 0) return false;
+    std::fill(S0.h_C.begin(), S0.h_C.begin() + 24 * 16, 0.0);
+    std::copy(Cs, Cs + 8 * np * 16, S0.h_C.begin());
+    *rank = r;
+    return true;
+  };
+  auto broke = [&]() {
+    return refuse(FEAHIP_ENOTCONVERGED, "the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes is not supported)");
+  };
+  auto gram = [&](int np) { FOR_RANKS(c) enq_gram(c, np); };
+  auto combine = [&](int np, int write_p) { FOR_RANKS(c) enq_combine(c, np, write_p); };
+  auto residual = [&](bool precond) -> int {
+    FOR_RANKS(c) { if ((rc = enq_residual(c, precond))) return rc; }
+    return FEAHIP_OK;
+  };
+  auto ritz_on_x = [&]() -> int {
+    int rank = 0;
+    if ((rc = products_x())) return rc;
+    gram(1);
+    if ((rc = read_sums_dist(R, T, MODAL_NORMS, MODAL_GRAM, sums))) return rc;
+    if (!ritz(1, &rank)) return broke();
+    if ((rc = upload())) return rc;
+    combine(1, 0);
+    return products_x();
+  };
+  auto fresh_norms = [&]() -> int {
+    if ((rc = residual(false))) return rc;
+    return read_sums_dist(R, T, 0, MODAL_NORMS, sums);
+  };
+  auto finish = [&](int it, int code) {
+    for (feahip_ctx *c : R) {
+      ModalState &S = c->modal;
+      S.have_sharded = true; S.sh_row0 = c->row0; S.sh_row1 = c->row1;
+      for (int j = 0; j < MC; ++j) S.theta[j] = theta[j];
+      if (code == FEAHIP_ENOTCONVERGED) c->err = "solve_modes_sharded: not converged after " + std::to_string(it) + " Rayleigh-Ritz steps";
+    }
+    for (int j = 0; j < n_modes; ++j) { lambda[j] = theta[j]; if (resid) resid[j] = ratio[j]; }
+    if (iters) *iters = it;
+    return code;
+  };
+
+  if (warm && have) {
+    // the modes held, their theta, against the K of now: converged already means nothing is touched
+    if ((rc = upload()) || (rc = products_x()) || (rc = fresh_norms())) return rc;
+    if (converged()) return finish(0, FEAHIP_OK);
+  } else {
+    FOR_RANKS(c) {
+      if (own_nodes(c) > 0)
+        hipLaunchKernelGGL(k_modal_hash_rows, g256((size_t)own_nodes(c) * 24), dim3(256), 0, c->stream, own_nodes(c), c->row0,
+                           (const int *)c->modal.d_key, (const uint8_t *)(c->d_dofmask + (size_t)3 * c->row0), mv(c, V_X) + own_off8(c));
+    }
+  }
+  if ((rc = ritz_on_x())) return rc;
+  bool hasP = false, must_step = false;
+  for (int it = 0;;) {
+    if (it > 0 && it % 20 == 0 && !must_step) { if ((rc = products_x())) return rc; }   // the recurrences cannot drift
+    const int np = hasP ? 3 : 2;
+    if ((rc = upload()) || (rc = residual(true))) return rc;
+    if ((rc = products_dist(R, T, V_W, V_KW, V_MW))) return rc;
+    gram(np);
+    if ((rc = read_sums_dist(R, T, 0, MODAL_SUMS, sums))) return rc;    // the one synchronisation of a step
+    const bool stop = converged() && !must_step;
+    must_step = false;
+    if (stop || it >= max_it) {
+      // at return: X orthonormalised on its own, fresh products, and the test made on them
+      if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
+      if (converged()) return finish(it, FEAHIP_OK);
+      if (it >= max_it) return finish(it, FEAHIP_ENOTCONVERGED);
+      must_step = true;                                                 // the recurrences had drifted: go on from the fresh products
+      continue;
+    }
+    int rank = 0;
+    if (!ritz(np, &rank)) return broke();
+    if ((rc = upload())) return rc;
+    combine(np, 1);
+    hasP = rank == 8 * np;                                              // a rank drop restarts the recurrence without P
+    ++it;
+  }
 }

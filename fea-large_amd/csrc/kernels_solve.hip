@@ -1051,6 +1051,65 @@ struct GroupTransport : Transport {
     for (auto *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamWaitEvent(c->stream, c->ev_unpacked, 0)); }
     return FEAHIP_OK;
   }
+  // The block exchange of the sharded modal solve (kernels_modal.hip): the same two halves for the halo rows of one
+  // block vector [3N][8] per context, 24 doubles per row through ModalState::d_bsend / d_brecv, on the same streams
+  // and events -- an exchange of either kind waits for the receivers of the one before it, whichever kind that was.
+  std::vector<double *> block_pending;
+  int copies_and_unpack_block(std::vector<feahip_ctx *> &R)
+  {
+    for (size_t ib = 0; ib < R.size(); ++ib) {       // receiver by receiver, on ITS communication stream
+      feahip_ctx *b = R[ib];
+      (void)hipSetDevice(b->device);
+      for (size_t kb = 0; kb < b->peer.size(); ++kb) {
+        feahip_ctx *a = R[(size_t)b->peer[kb]];
+        size_t k = 0;
+        while (k < a->peer.size() && a->peer[k] != b->rank) ++k;
+        const int n = b->recv_off[kb + 1] - b->recv_off[kb];
+        if (k == a->peer.size() || a->send_off[k + 1] - a->send_off[k] != n) { b->err = "halo plans of two ranks disagree"; return FEAHIP_ECOMM; }
+        FEA_HIP_CHECK(b, hipStreamWaitEvent(b->comm_stream, a->ev_packed, 0));
+        if (poison) FEA_HIP_CHECK(b, hipStreamWaitEvent(b->comm_stream, ev_interior[a], 0));
+        if (n > 0)
+          FEA_HIP_CHECK(b, hipMemcpyAsync(b->modal.d_brecv + (size_t)24 * b->recv_off[kb], a->modal.d_bsend + (size_t)24 * a->send_off[k],
+                                          sizeof(double) * 24 * (size_t)n, hipMemcpyDeviceToDevice, b->comm_stream));
+      }
+      FEA_HIP_CHECK(b, hipStreamWaitEvent(b->comm_stream, poison ? ev_interior[b] : b->ev_packed, 0));
+      modal_enq_block_unpack_on(b, block_pending[ib], b->comm_stream);
+      FEA_HIP_CHECK(b, hipEventRecord(b->ev_unpacked, b->comm_stream));
+    }
+    return FEAHIP_OK;
+  }
+  int exchange_block_begin(std::vector<feahip_ctx *> &R, const std::vector<double *> &d_v8) override
+  {
+    if (!poison_read) { const char *e = getenv("FEAHIP_TEST_POISON_HALO"); poison = e && atoi(e) > 0; poison_read = true; }
+    if (d_v8.size() != R.size() || R.size() != group.size()) { R[0]->err = "block exchange: one block vector per member of the group"; return FEAHIP_EINVAL; }
+    int rc;
+    for (auto *c : R) {
+      (void)hipSetDevice(c->device);
+      if ((rc = ensure_streams(c))) return rc;
+      if (poison && !ev_interior.count(c)) { hipEvent_t e; FEA_HIP_CHECK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_interior[c] = e; }
+    }
+    for (size_t i = 0; i < R.size(); ++i) {
+      feahip_ctx *c = R[i];
+      (void)hipSetDevice(c->device);
+      // the send buffer is free once every receiver of the previous exchange has copied it out
+      for (int pk : c->peer) FEA_HIP_CHECK(c, hipStreamWaitEvent(c->stream, R[(size_t)pk]->ev_unpacked, 0));
+      modal_enq_block_pack(c, d_v8[i]);
+      if (poison) modal_enq_block_poison(c, d_v8[i]);
+      FEA_HIP_CHECK(c, hipEventRecord(c->ev_packed, c->stream));
+    }
+    block_pending = d_v8;
+    return poison ? FEAHIP_OK : copies_and_unpack_block(R);
+  }
+  int exchange_block_end(std::vector<feahip_ctx *> &R) override
+  {
+    if (poison) {                                  // the copies start only now: behind everything enqueued since begin()
+      for (auto *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipEventRecord(ev_interior[c], c->stream)); }
+      const int rc = copies_and_unpack_block(R);
+      if (rc) return rc;
+    }
+    for (auto *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamWaitEvent(c->stream, c->ev_unpacked, 0)); }
+    return FEAHIP_OK;
+  }
   int allreduce(std::vector<feahip_ctx *> &R, int slot, int n) override
   {
     double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tmp[8];

@@ -147,6 +147,8 @@ ABI = {
     "feahip_solve_modes": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip],
     "feahip_get_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_spmm_km": [C.c_void_p, _dp, _dp, _dp],
+    "feahip_solve_modes_sharded": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip],
+    "feahip_group_spmm_km": [C.POINTER(C.c_void_p), C.c_int, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)],
     "feahip_host_modal_ritz": [C.c_int, _dp, _dp, _dp, _dp],
     "feahip_solve_modes_locked": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _ip, _ip],
     "feahip_get_locked_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
@@ -845,9 +847,21 @@ class FeaSolver:
             self._chk(rc)
         return (lam, res, it.value) if check else (lam, res, it.value, rc)
 
+    def solve_modes_sharded(self, n_modes, tolerance=1e-8, max_iterations=1000, warm=False, check=True):
+        """feahip_solve_modes_sharded: solve_modes over the ranks of a sharded run.  Collective: every rank of an RCCL
+        run (comm_init) makes the call; a member of an in-process group drives the whole group (FeaGroup.solve_modes).
+        Returns what solve_modes returns, the same on every rank; modes() then gives this rank's rows, zero elsewhere."""
+        lam, res, it = np.zeros(max(int(n_modes), 1)), np.zeros(max(int(n_modes), 1)), C.c_int(0)
+        rc = self._lib.feahip_solve_modes_sharded(self._ctx, int(n_modes), float(tolerance), int(max_iterations),
+                                                  int(bool(warm)), _d(lam), _d(res), C.byref(it))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        return (lam, res, it.value) if check else (lam, res, it.value, rc)
+
     def modes(self, first=0, count=None):
         """feahip_get_modes: phi[count][3N] of the last solve_modes, M-orthonormal, zero on the prescribed dofs; all
-        eight columns of the block are held (count=None: from `first` to the last)."""
+        eight columns of the block are held (count=None: from `first` to the last).  After solve_modes_sharded: the
+        rows this rank owns, zero on all others."""
         count = MODAL_COLS - first if count is None else count
         phi = np.zeros((max(int(count), 0), self.ndof))
         self._chk(self._lib.feahip_get_modes(self._ctx, int(first), int(count), _d(phi)))
@@ -1676,6 +1690,42 @@ class FeaGroup:
 
     def strain_energy(self):
         return self.ranks[0].strain_energy()                    # one call drives the group
+
+    # ---- modal analysis over the ranks -------------------------------------
+    def solve_modes(self, n_modes, tolerance=1e-8, max_iterations=1000, warm=False, check=True):
+        """feahip_solve_modes_sharded on the group (one call drives it): (lam[n_modes], resid[n_modes], steps) and, with
+        check=False, the return code as a fourth item instead of raising when the steps run out."""
+        lam, res, it = np.zeros(max(int(n_modes), 1)), np.zeros(max(int(n_modes), 1)), C.c_int(0)
+        rc = self._lib.feahip_solve_modes_sharded(self.ranks[0]._ctx, int(n_modes), float(tolerance), int(max_iterations),
+                                                  int(bool(warm)), _d(lam), _d(res), C.byref(it))
+        if check or rc != ENOTCONVERGED:
+            self._chk(rc)
+        return (lam, res, it.value) if check else (lam, res, it.value, rc)
+
+    def _stitch_dofs(self, parts):
+        """Owned rows of per-rank block arrays [k][3 N_rank], stitched into [k][3 N_global] in the deck's dof order."""
+        out = np.zeros((parts[0].shape[0], self.n_global, 3))
+        for r, nd, p in zip(self.ranks, self.nodes, parts):
+            p = p.reshape(len(p), -1, 3)
+            out[:, nd] = p[:, :r.n_own] if self.rank_contexts else p[:, nd]
+        return out.reshape(len(out), -1)
+
+    def modes(self, first=0, count=None):
+        """The modes of the last solve_modes: every rank's own rows stitched into phi[count][3 N_global] in the deck's
+        dof order."""
+        return self._stitch_dofs([r.modes(first, count) for r in self.ranks])
+
+    def spmm_km(self, x8, per_rank=False):
+        """[K X, mask(M X)] of eight whole-mesh columns x8[8][3 N_global] by the sharded block product
+        (feahip_group_spmm_km): every rank multiplies its own rows, the halo rows of X travel by the block exchange.
+        per_rank: also every rank's own [8][3 N_rank] results as the library returned them (zero off its rows)."""
+        x8 = np.ascontiguousarray(x8, dtype=np.float64).reshape(MODAL_COLS, self.n_global, 3)
+        xs = [np.ascontiguousarray(x8[:, r.node_global] if self.rank_contexts else x8).reshape(MODAL_COLS, -1) for r in self.ranks]
+        ys, zs = [np.zeros_like(x) for x in xs], [np.zeros_like(x) for x in xs]
+        xp, yp, zp = ((_dp * self.n)(*[_d(v) for v in vs]) for vs in (xs, ys, zs))
+        self._chk(self._lib.feahip_group_spmm_km(self._arr, self.n, xp, yp, zp))
+        out = (self._stitch_dofs(ys), self._stitch_dofs(zs))
+        return out + (ys, zs) if per_rank else out
 
     def _stitch_rows(self, parts):
         """Owned rows of per-node arrays ([N] or [N][k]), stitched together."""

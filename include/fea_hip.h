@@ -645,6 +645,48 @@ int feahip_get_modes(feahip_ctx *ctx, int first, int count, double *phi);
  * solve is; FEAHIP_ESTATE before the first stiffness assembly; modes held from
  * a solve are dropped)                                                        */
 int feahip_spmm_km(feahip_ctx *ctx, const double *x8, double *y8, double *z8);
+/* feahip_solve_modes over the ranks of a sharded run: the same pencil, stop
+ * test, block of eight columns and outputs, on row shards and on
+ * feahip_create_rank / feahip_create_rank_local contexts that have a transport.
+ * COLLECTIVE like feahip_consistent_acceleration: an in-process group
+ * (feahip_group_init) is driven from any one member, the ranks of an RCCL run
+ * (feahip_comm_init) all make the call.  Every rank works on the rows it owns:
+ * the halo rows of a block vector travel before its product (192 bytes per
+ * row, under the product of the rows that read no halo column), and the 24
+ * norms and 768 Gram sums of a step are all-reduced (792 doubles) before the
+ * one Rayleigh-Ritz step every rank then takes on identical numbers.  The
+ * preconditioner is the rank's own: kind 0 its 3x3 block-Jacobi inverses,
+ * kind 1 one W-cycle per column on its diagonal block of K.
+ * lambda, resid and *iters are the same on every rank.  Afterwards
+ * feahip_get_modes on each context gives the rank's own rows and zero on all
+ * others (as feahip_get_lumped_mass does); the rows of all ranks together are
+ * M-orthonormal over the whole mesh and 0 on the prescribed dofs.
+ * The start block is the hash of feahip_solve_modes keyed by the node's
+ * identity in the whole mesh (the library id on a row shard, node_global on a
+ * rank context), so it does not depend on the cut; the same input on the same
+ * number of ranks gives the same bits (a group sums in rank order).
+ * warm: as in feahip_solve_modes, when every rank holds modes of a sharded
+ * solve on its current rows.  Modes of this solve are not a start for
+ * feahip_solve_modes on the same context, nor the reverse: either solve
+ * drops the other's.
+ * FEAHIP_EINVAL: n_modes outside [1, 8], tolerance <= 0, max_iterations < 0,
+ * null lambda; a context without a transport (feahip_solve_modes is the solve
+ * for it); preconditioner 2; ranks whose preconditioner kinds differ; fewer
+ * than 24 free dofs over all ranks (one rank may own fewer, or none).
+ * FEAHIP_ESTATE: no mass, or a stale one, on any rank.  Refusals that depend
+ * on other ranks are all-reduced: every rank returns the same code.
+ * Memory per rank: feahip_solve_modes' nine block vectors over the rank's
+ * local nodes (owned and halo), plus 192 bytes per row sent and per row
+ * received, allocated on the first call.                                     */
+int feahip_solve_modes_sharded(feahip_ctx *ctx, int n_modes, double tolerance, int max_iterations, int warm,
+                               double *lambda /*[n_modes]*/, double *resid /*[n_modes], may be NULL*/, int *iters /*may be NULL*/);
+/* Test hook for the sharded block product, shaped like
+ * feahip_group_apply_preconditioner: x8[k], y8[k], z8[k] are [8][3 N_k] in
+ * context k's own dof order.  Only the owned rows of x8[k] matter: the halo
+ * rows of X come by the block exchange.  y8[k] = K X and z8[k] = mask(M X) on
+ * rank k's rows, zero elsewhere.  FEAHIP_ESTATE before the first stiffness
+ * assembly or without a mass; modes held are dropped.                        */
+int feahip_group_spmm_km(feahip_ctx **ctxs, int n, const double *const *x8, double *const *y8, double *const *z8);
 /* Host-only (no device): the Rayleigh-Ritz step of feahip_solve_modes.  gram_m,
  * gram_k: S' M S and S' K S, n_dirs x n_dirs (8, 16 or 24), row-major, S = [X, W,
  * P] in blocks of eight.  Scales by diag(gram_m)^-1/2, eigendecomposes by cyclic
