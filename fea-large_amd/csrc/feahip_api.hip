@@ -1270,7 +1270,7 @@ extern "C" int feahip_spmm_km(feahip_ctx *c, const double *x8, double *y8, doubl
   double *v = c->modal.d_v;                                          // X, W <- the host layout, KX, MX <- the products
   for (int k = 0; k < FEA_MODAL_COLS; ++k)
     if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, x8 + (size_t)k * n))) return rc;
-  if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, v, v + 3 * n8, v + 6 * n8))) return rc;
+  if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, v, v + 3 * n8, v + 6 * n8))) return rc;
   for (int which = 0; which < 2; ++which) {
     if ((rc = launch_modal_pack(c, v + (which ? 6 : 3) * n8, v + n8, 1))) return rc;
     for (int k = 0; k < FEA_MODAL_COLS; ++k)
@@ -1406,7 +1406,7 @@ extern "C" int feahip_modal_deflate(feahip_ctx *c, int n_locked, const double *q
     FEA_HIP_CHECK(c, hipMemsetAsync(v + n8, 0, sizeof(double) * n8, c->stream));
     for (int k = 0; k < FEA_MODAL_COLS && p * FEA_MODAL_COLS + k < n_locked; ++k)
       if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, q + ((size_t)p * FEA_MODAL_COLS + k) * n))) return rc;
-    if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, v, v + 3 * n8, v + 6 * n8))) return rc;
+    if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, v, v + 3 * n8, v + 6 * n8))) return rc;
     FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
     FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 1, p), v + 6 * n8, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
   }

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <initializer_list>
 #include <string>
 #include <thread>
@@ -440,7 +441,15 @@ struct ResultState {
 
 // modal analysis (kernels_modal.hip): nothing of it exists until feahip_solve_modes (or one of its hooks) is called.
 // Block vectors are [3N][FEA_MODAL_COLS] doubles, the columns of a dof contiguous.
+// The nine block vectors of ModalState::d_v, and the sums of a step: 24 column norms (s 8 + column, s = 0 |r|^2, 1 |Kx|^2,
+// 2 |Mx|^2), then 12 x 64 Gram sums (block pair q, M: 0..5, K: 6..11, the pairs (X,X) (X,W) (X,P) (W,W) (W,P) (P,P), entry
+// (a, b) at 24 + q 64 + a 8 + b).  Sum e of workgroup b is at d_part[e FEA_RED_BLOCKS + b]; reduced, at d_small[e].
+enum { V_X = 0, V_W = 1, V_P = 2, V_KX = 3, V_KW = 4, V_KP = 5, V_MX = 6, V_MW = 7, V_MP = 8 };
+#define MODAL_NORMS 24
+#define MODAL_GRAM (12 * 64)
+#define MODAL_SUMS (MODAL_NORMS + MODAL_GRAM)
 #define MODAL_SMALL (24 + 12 * 64 + 24 * 16 + FEA_MODAL_COLS)
+static_assert(MODAL_SMALL == MODAL_SUMS + 24 * 16 + FEA_MODAL_COLS, "the layout of ModalState::d_small: sums, C[24][16], theta[8]");
 struct ModalState {
   double *d_v = nullptr;               // [9][3N][8]: X W P, KX KW KP, MX MW MP
   double *d_part = nullptr;            // [24 + 768][FEA_RED_BLOCKS] per-workgroup partial sums: column norms, Gram entries
@@ -674,7 +683,10 @@ int time_pcg2_iteration(feahip_ctx *c, int warmup, int iters, double *avg_ms);
 int ensure_modal(feahip_ctx *c);
 int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, double *lambda, double *resid, int *iters);
 int modal_get(feahip_ctx *c, int col, double *h_lib);                   // column col of X, [3N] in library ids
-int launch_spmm_km(feahip_ctx *c, const double *d_x8, double *d_y8, double *d_z8);   // Y = K X, Z = mask(M X)
+// Y = K X, Z = mask(m X) on the chunks [first, first + n) of the context's own (all of them: 0, nchunks_local), m one
+// double per block of K's pattern (mass.d_m, buckling.d_kg); an empty range launches one idle workgroup
+int launch_spmm_km(feahip_ctx *c, int first, int n, const double *d_m, const double *d_x8, double *d_y8, double *d_z8);
+int launch_modal_hash(feahip_ctx *c, double *d_v8);                     // the start block into a whole block vector
 int launch_modal_pack(feahip_ctx *c, const double *d_in, double *d_out, int unpack); // [8][3N] <-> [3N][8]
 int time_modal_prepare(feahip_ctx *c);                                  // the nine vectors filled for feahip_time_kernel 13-15
 int time_modal_kernel(feahip_ctx *c, int what);
@@ -698,16 +710,36 @@ double *locked_panel(feahip_ctx *c, int mq, int panel);                 // panel
 int launch_deflate(feahip_ctx *c, double *d_w8, int n_locked);          // W -= Q (MQ' W) against the first n_locked modes
 int time_deflate_prepare(feahip_ctx *c);                                // eight panels of hash for feahip_time_kernel 16-17
 int time_deflate_kernel(feahip_ctx *c, int what);
-// the pieces of a Rayleigh-Ritz step for a driver in another file (kernels_buckling.hip): the block vector j of
-// ModalState::d_v (0 X, 1 W, 2 P, 3 KX, 4 KW, 5 KP, 6 MX, 7 MW, 8 MP) and the launches modal_solve makes, unchanged
-double *modal_vec(feahip_ctx *c, int j);
-int launch_spmm_pencil(feahip_ctx *c, const double *d_m, const double *d_x8, double *d_y8, double *d_z8);   // Y = K X, Z = mask(m X), m one double per block
-int modal_enq_hash(feahip_ctx *c, int j);                               // the start block into vector j
-int modal_enq_gram(feahip_ctx *c, int np);
-int modal_enq_combine(feahip_ctx *c, int np, int write_p);
-int modal_enq_residual(feahip_ctx *c, bool precond);
-int modal_read_sums(feahip_ctx *c, int e0, int n, double *h);           // sums [e0, e0 + n) reduced and read into h + e0
-void modal_unpack_gram(const double *gram_sums, int np, double *GM, double *GK);
+// The iteration the four eigenvalue drivers share (modal_solve, modal_solve_locked, modal_solve_dist, buckling_solve).
+// A driver assembles its matrix and its preconditioner, makes its start block in X, says below what differs and calls
+// run() once, or once per sweep; the ending -- error text, flags, locking, lambda and resid -- is the driver's again.
+enum { LOBPCG_CONVERGED = 0, LOBPCG_OUT_OF_STEPS = 1, LOBPCG_BROKE = 2 };   // run() < 0: the code of a HIP or transport error
+struct Lobpcg {
+  std::vector<feahip_ctx *> R;         // the contexts driven here; the host side of a step (theta, h_C) lives on R[0]
+  struct Transport *T;                 // null: R is one unsharded context -- one full-range product, the sums read straight
+                                       // out of d_small.  Else every rank works on its owned rows: the halo rows of a block
+                                       // exchanged under the interior product, the sums all-reduced through d_vred
+  double tol;                          // of the stop test ||r_j|| <= tol (||K x_j|| + |theta_j| ||M x_j||)
+  bool geometric = false;              // the pencil (K_sigma, K): buckling.d_kg stands beside K in place of mass.d_m, and the
+                                       // two products swap slots (K S into the "M" slots, mask(K_sigma S) into the "K" slots)
+  bool renew_p = false;                // the renewal of every 20 steps makes the products of P again as well as those of X
+  std::function<int()> after_residual; // between the preconditioned residual and W's products (the locked solve deflates W)
+  std::function<bool(int ns, const double *GM)> veto;   // true refuses the Gram matrix of a Rayleigh-Ritz step: the basis "broke"
+  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[FEA_MODAL_COLS];
+  double *theta;                       // R[0]->modal.theta
+
+  Lobpcg(const std::vector<feahip_ctx *> &ranks, struct Transport *transport, double tolerance);
+  int products(int jx, int jk, int jm);   // block vectors [jk, jm] <- [K, mask(M)] jx (the slots swapped when geometric)
+  int upload();                        // C and theta of the host to every rank
+  int enq_residual(bool precond);      // R, its norms and W from X's products and theta, on every rank
+  int read_sums(int e0, int n);        // the sums [e0, e0 + n) of all ranks into sums (one synchronisation)
+  int fresh_norms();                   // the norms of X's products as they stand, into sums
+  bool converged(int want);            // the stop test of the leading want columns on sums[0 .. 24); fills ratio
+  bool ritz(int np, int *rank);        // theta and C from the Gram sums of np column blocks; false: the basis broke
+  // X orthonormalised on its own, then steps until the leading want columns pass the stop test on fresh products or *it,
+  // which counts the steps over all calls, reaches max_it.  One of LOBPCG_*, or an error code
+  int run(int want, int max_it, int *it);
+};
 // kernels_buckling.hip -- K_sigma as one double per block, and the lowest eigenpairs of K_sigma phi = nu K phi
 int geom_assemble(feahip_ctx *c);                                       // buckling.d_kg at the current nodes
 int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters);

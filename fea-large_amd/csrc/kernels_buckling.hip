@@ -174,16 +174,11 @@ int geom_assemble(feahip_ctx *c)
 int time_geom_kernel(feahip_ctx *c, int what) { return what == 18 ? enq_geom_elements(c) : enq_geom_blocks(c); }
 
 // ---- the driver ------------------------------------------------------------------------------------------------------
-// modal_solve's iteration on the pencil (K_sigma, K); the slots of ModalState::d_v keep their names, and hold
+// The shared iteration (struct Lobpcg) on the pencil (K_sigma, K): kg stands beside K in the product and the two results
+// swap slots (Lobpcg::geometric).  The slots of ModalState::d_v keep their names, and hold
 //   V_KX, V_KW, V_KP: mask(K_sigma S)        V_MX, V_MW, V_MP: K S
-// (K is masked and S is zero on the prescribed dofs, so K S is zero there too).  The small host helpers are modal_solve's,
-// restated: that function is not to change a bit.
-enum { V_X = 0, V_W = 1, V_P = 2, V_KX = 3, V_KW = 4, V_KP = 5, V_MX = 6, V_MW = 7, V_MP = 8 };
-#define BK_NORMS 24
-#define BK_GRAM (12 * 64)
-#define BK_SUMS (BK_NORMS + BK_GRAM)
-static_assert(MODAL_SMALL == BK_SUMS + 24 * 16 + MC, "the layout of ModalState::d_small: sums, C[24][16], theta[8]");
-
+// (K is masked and S is zero on the prescribed dofs, so K S is zero there too), so the stop test is
+// ||K_sigma x - nu K x|| <= tol (||K_sigma x|| + |nu| ||K x||).
 int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters)
 {
   int rc;
@@ -199,100 +194,36 @@ int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *n
   if ((rc = feahip_create_stiffness(c)) || (rc = feahip_apply_prescribed_bc(c, 0.0)) || (rc = geom_assemble(c))) return rc;
   if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
   else enq_precond_blockjacobi(c);
-  const double *kg = c->buckling.d_kg;
-  double sums[BK_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
-  double *theta = S.theta;
-  bool not_pd = false;
-  S.h_C.assign(24 * 16 + MC, 0.0);
-  // y = K S into the "M" slot, z = mask(K_sigma S) into the "K" slot
-  auto products = [&](int s, int ks, int ms) { return launch_spmm_pencil(c, kg, modal_vec(c, s), modal_vec(c, ms), modal_vec(c, ks)); };
-  auto products_x = [&]() { return products(V_X, V_KX, V_MX); };
-  auto upload = [&]() -> int {                        // C and theta (h_C is not touched again before the next read-back)
-    for (int j = 0; j < MC; ++j) S.h_C[24 * 16 + j] = theta[j];
-    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + BK_SUMS, S.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
-    return FEAHIP_OK;
-  };
-  auto converged = [&]() {                            // ||K_sigma x - nu K x|| <= tol (||K_sigma x|| + |nu| ||K x||)
-    bool ok = true;
-    for (int j = 0; j < MC; ++j) {
-      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
-      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
-      if (j < n_modes && !(ratio[j] <= tol)) ok = false;
-    }
-    return ok;
-  };
-  // Rayleigh-Ritz on np column blocks from the sums read back; false when the basis breaks or K is not positive definite
-  auto ritz = [&](int np, int *rank) -> bool {
-    modal_unpack_gram(sums + BK_NORMS, np, GM, GK);
-    const int ns = 8 * np;
+  Lobpcg L({c}, nullptr, tol);
+  L.geometric = true;
+  // every 20 steps the products of X AND of P are made again.  modal_solve renews X's alone; on this pencil the products
+  // of P, carried by recurrence from the first step on, made the step count erratic (a float64 emulation of the
+  // clamped-free column: 322 to 1326 steps over four start blocks without the second product, 324 to 349 with it;
+  // tests/buckling_reference.py emulates this step)
+  L.renew_p = true;
+  bool not_pd = false;                                // x_j' K x_j <= 0 for a column of the block: K is not positive definite
+  L.veto = [&](int ns, const double *GM) {
     bool finite = true;
     for (int j = 0; j < MC; ++j) finite = finite && std::isfinite(GM[j * ns + j]);
-    for (int j = 0; finite && j < MC; ++j) if (!(GM[j * ns + j] > 0.0)) not_pd = true;     // x_j' K x_j of the block
-    if (not_pd) return false;
-    double Cs[24 * 16];
-    const int r = modal_ritz(ns, GM, GK, MC, theta, Cs);
-    if (r < 0) return false;
-    std::fill(S.h_C.begin(), S.h_C.begin() + 24 * 16, 0.0);
-    std::copy(Cs, Cs + ns * 16, S.h_C.begin());
-    *rank = r;
-    return true;
+    for (int j = 0; finite && j < MC; ++j) if (!(GM[j * ns + j] > 0.0)) not_pd = true;
+    return not_pd;
   };
-  auto broke = [&]() {
+  int it = 0;
+  if ((rc = launch_modal_hash(c, c->modal.d_v))) return rc;             // X, the first of the nine block vectors
+  const int end = L.run(n_modes, max_it, &it);
+  if (end < 0) return end;
+  if (end == LOBPCG_BROKE) {
     c->err = not_pd ? "solve_buckling: K is not positive definite at this state (x' K x <= 0 for a column of the block): "
                       "most likely a critical point has been passed"
                     : "solve_buckling: the Rayleigh-Ritz basis lost its rank or a sum is not finite";
     return FEAHIP_ENOTCONVERGED;
-  };
-  // X alone: fresh products, the Gram sums of X, nu ascending and X K-orthonormal again, fresh products
-  auto ritz_on_x = [&]() -> int {
-    int rank = 0;
-    if ((rc = products_x()) || (rc = modal_enq_gram(c, 1))) return rc;
-    if ((rc = modal_read_sums(c, BK_NORMS, BK_GRAM, sums))) return rc;
-    if (!ritz(1, &rank)) return broke();
-    if ((rc = upload()) || (rc = modal_enq_combine(c, 1, 0))) return rc;
-    return products_x();
-  };
-  auto fresh_norms = [&]() -> int {
-    if ((rc = modal_enq_residual(c, false))) return rc;
-    return modal_read_sums(c, 0, BK_NORMS, sums);
-  };
-  auto finish = [&](int it, int code) {
-    S.have_buckling = true;
-    for (int j = 0; j < n_modes; ++j) { nu[j] = theta[j]; if (resid) resid[j] = ratio[j]; }
-    if (iters) *iters = it;
-    if (code == FEAHIP_ENOTCONVERGED) c->err = "solve_buckling: not converged after " + std::to_string(it) + " Rayleigh-Ritz steps";
-    return code;
-  };
-
-  if ((rc = modal_enq_hash(c, V_X)) || (rc = ritz_on_x())) return rc;
-  bool hasP = false, must_step = false;
-  for (int it = 0;;) {
-    // the recurrences cannot drift: every 20 steps the products of X AND of P are made again.  modal_solve renews X's
-    // alone; on this pencil the products of P, carried by recurrence from the first step on, made the step count
-    // erratic (a float64 emulation of the clamped-free column: 322 to 1326 steps over four start blocks without the
-    // second product, 324 to 349 with it; tests/buckling_reference.py emulates this step)
-    if (it > 0 && it % 20 == 0 && !must_step) {
-      if ((rc = products_x())) return rc;
-      if (hasP && (rc = products(V_P, V_KP, V_MP))) return rc;
-    }
-    const int np = hasP ? 3 : 2;
-    if ((rc = upload()) || (rc = modal_enq_residual(c, true))) return rc;
-    if ((rc = products(V_W, V_KW, V_MW)) || (rc = modal_enq_gram(c, np))) return rc;
-    if ((rc = modal_read_sums(c, 0, BK_SUMS, sums))) return rc;         // the one synchronisation of a step
-    const bool stop = converged() && !must_step;
-    must_step = false;
-    if (stop || it >= max_it) {
-      // at return: X orthonormalised on its own, fresh products, and the test made on them
-      if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
-      if (converged()) return finish(it, FEAHIP_OK);
-      if (it >= max_it) return finish(it, FEAHIP_ENOTCONVERGED);
-      must_step = true;                                                 // the recurrences had drifted: go on from the fresh products
-      continue;
-    }
-    int rank = 0;
-    if (!ritz(np, &rank)) return broke();
-    if ((rc = upload()) || (rc = modal_enq_combine(c, np, 1))) return rc;
-    hasP = rank == 8 * np;                                              // a rank drop restarts the recurrence without P
-    ++it;
   }
+  S.have_buckling = true;
+  for (int j = 0; j < n_modes; ++j) { nu[j] = L.theta[j]; if (resid) resid[j] = L.ratio[j]; }
+  if (iters) *iters = it;
+  if (end == LOBPCG_OUT_OF_STEPS) {
+    c->err = "solve_buckling: not converged after " + std::to_string(it) + " Rayleigh-Ritz steps";
+    return FEAHIP_ENOTCONVERGED;
+  }
+  return FEAHIP_OK;
 }

@@ -5,7 +5,7 @@
 // line) -- the layout of kernels_solve2.hip carried from two columns to eight.  Nine of them live in one allocation
 // (ModalState::d_v): S = [X, W, P], KS = [KX, KW, KP], MS = [MX, MW, MP].
 //
-// Per Rayleigh-Ritz step (modal_solve below):
+// Per Rayleigh-Ritz step (struct Lobpcg, below enq_residual: the one iteration of all four drivers):
 //   k_modal_residual  R = KX - MX diag(theta), the three column norms |r|^2, |Kx|^2, |Mx|^2 of every column, and (kind
 //                     0) W = D^-1 R with the 3x3 block-Jacobi inverse, zero on the prescribed dofs -- one pass
 //   k_spmm_km         KW = K W and MW = mask(M W) over ONE read of rowptr / colidx / K / m
@@ -18,7 +18,7 @@
 //                     matrices; every 20 steps and at return KX and MX are recomputed from X.
 // Nothing here exists, and nothing is launched, on a context that never calls feahip_solve_modes (or the hooks
 // feahip_spmm_km, feahip_time_kernel 13-15) -- or feahip_solve_buckling, whose driver (kernels_buckling.hip) runs the same
-// step on the pencil (K_sigma, K) through the launchers exported below modal_ritz' helpers.
+// iteration on the pencil (K_sigma, K).
 //
 // More than eight modes, and bodies with zero-energy modes (feahip_solve_modes_locked, modal_solve_locked below): the
 // same step in sweeps of the eight-column block on the pencil (K + shift M, M).  Converged leading columns are locked
@@ -30,8 +30,8 @@
 // The store exists on a context that called feahip_solve_modes_locked (or feahip_modal_deflate, feahip_time_kernel
 // 16-17) and on no other.
 //
-// Over the ranks of a sharded run (feahip_solve_modes_sharded, modal_solve_dist at the end of this file): the same step
-// with every rank on the rows it owns.  The sums, the combination and the residual take the owned range [row0, row1);
+// Over the ranks of a sharded run (feahip_solve_modes_sharded, modal_solve_dist at the end of this file): the same
+// iteration with a transport, every rank on the rows it owns.  The sums, the combination and the residual take the owned range [row0, row1);
 // the halo rows of X and W travel as rows of 192 bytes (k_block_halo_pack / k_block_halo_unpack, Transport::
 // exchange_block_begin / _end) under the product of the chunks that read no halo column; the 24 + 768 sums are
 // all-reduced (Transport::allreduce_vec) before the one Rayleigh-Ritz step.  The block halo buffers and the row keys
@@ -48,13 +48,6 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 // multigrid preconditioner (amg.hip)
 int amg_prepare(feahip_ctx *c);
 double *amg_apply(feahip_ctx *c, const double *r);
-
-// partial sums in ModalState::d_part: sum e of workgroup b at [e RB + b]; e < 24: the column norms (s 8 + column,
-// s = 0 |r|^2, 1 |Kx|^2, 2 |Mx|^2), then 12 x 64 Gram sums: block pair q (M: 0..5, K: 6..11, the pairs (X,X) (X,W)
-// (X,P) (W,W) (W,P) (P,P)) entry (a, b) at 24 + q 64 + a 8 + b
-#define MODAL_NORMS 24
-#define MODAL_GRAM (12 * 64)
-#define MODAL_SUMS (MODAL_NORMS + MODAL_GRAM)
 
 // ------------------------------------------------------------------------
 // Y = K X, Z = mask(M X) for eight columns in one pass over the pattern.  k_spmv2's chunking: a wave owns a chunk of up
@@ -488,11 +481,6 @@ void k_modal_advance(int ndof, int drop, int id0, const uint8_t *__restrict__ ma
 // host side
 // ------------------------------------------------------------------------
 static inline dim3 g256(size_t n) { return dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)); }
-static int spmm_grid(const feahip_ctx *c)
-{
-  const int g = (c->nchunks_local + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
-  return g < RB ? (g > 0 ? g : 1) : RB;
-}
 // The sums, the combination and the residual run on the rows the context owns, [row0, row1): all of them on an
 // unsharded context, where these are the launches they always were (base pointers + 0, the same counts and grids).
 static inline int own_nodes(const feahip_ctx *c) { return c->row1 - c->row0; }
@@ -533,14 +521,22 @@ int ensure_modal(feahip_ctx *c)
 }
 
 static inline double *mv(feahip_ctx *c, int j) { return c->modal.d_v + (size_t)j * c->ndof * MC; }
-enum { V_X = 0, V_W = 1, V_P = 2, V_KX = 3, V_KW = 4, V_KP = 5, V_MX = 6, V_MW = 7, V_MP = 8 };
 
-// Y = K X, Z = mask(M X) for device block vectors
-int launch_spmm_km(feahip_ctx *c, const double *d_x8, double *d_y8, double *d_z8)
+// the one launch of k_spmm_km: the full range, the interior and boundary ranges of a rank, either pencil.  A row's sums are
+// formed by one wave in block order, so the cut of the launches changes no bit
+int launch_spmm_km(feahip_ctx *c, int first, int n, const double *d_m, const double *d_x8, double *d_y8, double *d_z8)
 {
-  hipLaunchKernelGGL(k_spmm_km, dim3(spmm_grid(c)), dim3(256), 0, c->stream, c->chunk0, c->nchunks_local, c->d_chunk,
-                     c->d_rowptr, c->d_colidx, (const double *)c->d_K, (const double *)c->mass.d_m,
-                     (const uint8_t *)c->d_dofmask, (const v2d *)d_x8, (v2d *)d_y8, (v2d *)d_z8);
+  const int g = (n + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
+  hipLaunchKernelGGL(k_spmm_km, dim3(g < RB ? (g > 0 ? g : 1) : RB), dim3(256), 0, c->stream, c->chunk0 + first, n, c->d_chunk,
+                     c->d_rowptr, c->d_colidx, (const double *)c->d_K, d_m, (const uint8_t *)c->d_dofmask, (const v2d *)d_x8,
+                     (v2d *)d_y8, (v2d *)d_z8);
+  FEA_HIP_CHECK(c, hipGetLastError());
+  return FEAHIP_OK;
+}
+int launch_modal_hash(feahip_ctx *c, double *d_v8)
+{
+  const size_t n8 = (size_t)c->ndof * MC;
+  hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, d_v8);
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }
@@ -556,22 +552,11 @@ static void enq_combine(feahip_ctx *c, int np, int write_p)
   hipLaunchKernelGGL(k_modal_combine, dim3((own_dofs(c) + 255) / 256, 3), dim3(256), 0, c->stream, own_dofs(c), np, write_p,
                      c->modal.d_v + own_off8(c), (size_t)c->ndof * MC, (const double *)(c->modal.d_small + MODAL_SUMS));
 }
-// sums [e0, e0 + n) of d_part reduced into d_small and read into h (one synchronisation)
-static int read_sums(feahip_ctx *c, int e0, int n, double *h)
-{
-  hipLaunchKernelGGL(k_modal_reduce, dim3(n), dim3(256), 0, c->stream, e0, resid_grid(c), gram_grid(c),
-                     (const double *)c->modal.d_part, c->modal.d_small);
-  FEA_HIP_CHECK(c, hipGetLastError());
-  FEA_HIP_CHECK(c, hipMemcpyAsync(h + e0, c->modal.d_small + e0, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  return FEAHIP_OK;
-}
-
 // hooks of feahip_time_kernel 13, 14, 15: the product on X, the Gram pass and the combination (with the identity: the
 // vectors stay as they are) on all nine arrays
 int time_modal_kernel(feahip_ctx *c, int what)
 {
-  if (what == 13) return launch_spmm_km(c, mv(c, V_X), mv(c, V_KX), mv(c, V_MX));
+  if (what == 13) return launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, mv(c, V_X), mv(c, V_KX), mv(c, V_MX));
   if (what == 14) enq_gram(c, 3);
   else enq_combine(c, 3, 1);
   FEA_HIP_CHECK(c, hipGetLastError());
@@ -583,9 +568,7 @@ int time_modal_prepare(feahip_ctx *c)
   if ((rc = ensure_modal(c))) return rc;
   ModalState &S = c->modal;
   S.have = false;                                                     // the vectors are scratch from here on
-  const size_t n8 = (size_t)c->ndof * MC;
-  for (int j : {V_X, V_W, V_P})
-    hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, j));
+  for (int j : {V_X, V_W, V_P}) if ((rc = launch_modal_hash(c, mv(c, j)))) return rc;
   S.h_C.assign(24 * 16, 0.0);
   for (int k = 0; k < 8; ++k) { S.h_C[(size_t)k * 16 + k] = 1.0; S.h_C[(size_t)(16 + k) * 16 + 8 + k] = 1.0; }   // X <- X, P <- P
   FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + MODAL_SUMS, S.h_C.data(), sizeof(double) * 24 * 16, hipMemcpyHostToDevice, c->stream));
@@ -732,28 +715,166 @@ static int enq_residual(feahip_ctx *c, bool precond)
   return FEAHIP_OK;
 }
 
-// ---- the same launches for the buckling driver (kernels_buckling.hip): the kernels live in this file -------------------
-double *modal_vec(feahip_ctx *c, int j) { return mv(c, j); }
-int launch_spmm_pencil(feahip_ctx *c, const double *d_m, const double *d_x8, double *d_y8, double *d_z8)
+// ---- the iteration of all four drivers (struct Lobpcg, feahip_internal.h) ------------------------------------------------
+// Per step on R, the ranks this process drives (one unsharded context; all members of an in-process group; the one
+// context of an RCCL rank).  Every rank keeps the nine block vectors of its own context; a vector is authoritative on
+// the owned rows [row0, row1) -- all rows without a transport -- and the halo rows of X and W hold what the block
+// exchange last brought:
+//   residual, preconditioner          owned rows; kind 1: one W-cycle per column on the rank's own diagonal block
+//   (after_residual: the locked solve deflates W)
+//   products of W                     without a transport ONE launch of k_spmm_km over all chunks.  With one:
+//     exchange_block_begin(W)           pack on the context's stream, copies and unpack on the communication stream
+//     k_spmm_km on the interior chunks  they read no halo column (install_plan), so they run under the exchange
+//     exchange_block_end, k_spmm_km on the chunks before and after the interior range
+//   k_modal_gram, k_modal_reduce      owned rows; 24 + 768 sums into d_small; with a transport copied into d_vred and
+//   Transport::allreduce_vec          summed over the ranks (in a group the sums meet on the host in rank order)
+//   (one read-back; modal_ritz once on the sums; C and theta uploaded to every rank of R)
+//   k_modal_combine                   owned rows
+// Every branch depends on the (all-reduced) sums alone, so all ranks take it together.
+#define EACH_RANK(c) for (feahip_ctx *c : R) if (!T || hipSetDevice(c->device) == hipSuccess)   // (one context: its device is current)
+Lobpcg::Lobpcg(const std::vector<feahip_ctx *> &ranks, Transport *transport, double tolerance)
+  : R(ranks), T(transport), tol(tolerance), theta(ranks[0]->modal.theta)
 {
-  hipLaunchKernelGGL(k_spmm_km, dim3(spmm_grid(c)), dim3(256), 0, c->stream, c->chunk0, c->nchunks_local, c->d_chunk,
-                     c->d_rowptr, c->d_colidx, (const double *)c->d_K, d_m, (const uint8_t *)c->d_dofmask, (const v2d *)d_x8,
-                     (v2d *)d_y8, (v2d *)d_z8);
-  FEA_HIP_CHECK(c, hipGetLastError());
+  R[0]->modal.h_C.assign(24 * 16 + MC, 0.0);
+}
+
+// block vectors [jk, jm] <- [K, mask(M)] jx on the owned rows of every rank, the halo rows of jx by exchange; geometric:
+// [jm, jk] <- [K, mask(K_sigma)] jx
+static int block_products(std::vector<feahip_ctx *> &R, Transport *T, bool geometric, int jx, int jk, int jm)
+{
+  int rc;
+  auto spmm = [&](feahip_ctx *c, int first, int n) {
+    return launch_spmm_km(c, first, n, geometric ? c->buckling.d_kg : c->mass.d_m, mv(c, jx), mv(c, geometric ? jm : jk),
+                          mv(c, geometric ? jk : jm));
+  };
+  if (!T) return spmm(R[0], 0, R[0]->nchunks_local);
+  std::vector<double *> xs;
+  for (feahip_ctx *c : R) xs.push_back(mv(c, jx));
+  if ((rc = T->exchange_block_begin(R, xs))) return rc;
+  FOR_RANKS(c) { if (c->ichunk_hi > c->ichunk_lo && (rc = spmm(c, c->ichunk_lo, c->ichunk_hi - c->ichunk_lo))) return rc; }
+  if ((rc = T->exchange_block_end(R))) return rc;
+  FOR_RANKS(c) {                                                        // (an empty range of a rank is not launched)
+    if (c->ichunk_lo > 0 && (rc = spmm(c, 0, c->ichunk_lo))) return rc;
+    if (c->nchunks_local > c->ichunk_hi && (rc = spmm(c, c->ichunk_hi, c->nchunks_local - c->ichunk_hi))) return rc;
+  }
   return FEAHIP_OK;
 }
-int modal_enq_hash(feahip_ctx *c, int j)
+int Lobpcg::products(int jx, int jk, int jm) { return block_products(R, T, geometric, jx, jk, jm); }
+
+int Lobpcg::upload()                                  // (h_C is not touched again before the next read-back)
 {
-  const size_t n8 = (size_t)c->ndof * MC;
-  hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, j));
-  FEA_HIP_CHECK(c, hipGetLastError());
+  std::vector<double> &h_C = R[0]->modal.h_C;
+  for (int j = 0; j < MC; ++j) h_C[24 * 16 + j] = theta[j];
+  EACH_RANK(c) {
+    FEA_HIP_CHECK(c, hipMemcpyAsync(c->modal.d_small + MODAL_SUMS, h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
+  }
   return FEAHIP_OK;
 }
-int modal_enq_gram(feahip_ctx *c, int np) { enq_gram(c, np); FEA_HIP_CHECK(c, hipGetLastError()); return FEAHIP_OK; }
-int modal_enq_combine(feahip_ctx *c, int np, int write_p) { enq_combine(c, np, write_p); FEA_HIP_CHECK(c, hipGetLastError()); return FEAHIP_OK; }
-int modal_enq_residual(feahip_ctx *c, bool precond) { return enq_residual(c, precond); }
-int modal_read_sums(feahip_ctx *c, int e0, int n, double *h) { return read_sums(c, e0, n, h); }
-void modal_unpack_gram(const double *gram_sums, int np, double *GM, double *GK) { unpack_gram(gram_sums, np, GM, GK); }
+
+int Lobpcg::enq_residual(bool precond)
+{
+  int rc;
+  EACH_RANK(c) { if ((rc = ::enq_residual(c, precond))) return rc; }
+  return FEAHIP_OK;
+}
+
+// every rank's sums reduced into its d_small; with a transport copied into d_vred and summed over the ranks, so that every
+// rank holds, and this process reads, the same bits
+int Lobpcg::read_sums(int e0, int n)
+{
+  int rc;
+  EACH_RANK(c) {
+    hipLaunchKernelGGL(k_modal_reduce, dim3(n), dim3(256), 0, c->stream, e0, resid_grid(c), gram_grid(c),
+                       (const double *)c->modal.d_part, c->modal.d_small);
+    FEA_HIP_CHECK(c, hipGetLastError());
+    if (T) FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_vred, c->modal.d_small + e0, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (T && (rc = T->allreduce_vec(R, (size_t)n, false))) return rc;
+  feahip_ctx *c0 = R[0];
+  if (T) (void)hipSetDevice(c0->device);
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(sums + e0, T ? c0->d_vred : c0->modal.d_small + e0, sizeof(double) * n, hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  return FEAHIP_OK;
+}
+
+int Lobpcg::fresh_norms()
+{
+  int rc;
+  if ((rc = enq_residual(false))) return rc;
+  return read_sums(0, MODAL_NORMS);
+}
+
+bool Lobpcg::converged(int want)
+{
+  bool ok = true;
+  for (int j = 0; j < MC; ++j) {
+    const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
+    ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
+    if (j < want && !(ratio[j] <= tol)) ok = false;
+  }
+  return ok;
+}
+
+bool Lobpcg::ritz(int np, int *rank)                  // once for all ranks of R
+{
+  unpack_gram(sums + MODAL_NORMS, np, GM, GK);
+  if (veto && veto(8 * np, GM)) return false;
+  double Cs[24 * 16];
+  const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
+  if (r < 0) return false;
+  std::vector<double> &h_C = R[0]->modal.h_C;
+  std::fill(h_C.begin(), h_C.begin() + 24 * 16, 0.0);
+  std::copy(Cs, Cs + 8 * np * 16, h_C.begin());
+  *rank = r;
+  return true;
+}
+
+int Lobpcg::run(int want, int max_it, int *it)
+{
+  int rc;
+  // X alone: fresh products, the Gram sums of X, theta ascending and X M-orthonormal again, fresh products
+  auto ritz_on_x = [&]() -> int {
+    int rank = 0;
+    if ((rc = products(V_X, V_KX, V_MX))) return rc;
+    EACH_RANK(c) enq_gram(c, 1);
+    if ((rc = read_sums(MODAL_NORMS, MODAL_GRAM))) return rc;
+    if (!ritz(1, &rank)) return LOBPCG_BROKE;
+    if ((rc = upload())) return rc;
+    EACH_RANK(c) enq_combine(c, 1, 0);
+    return products(V_X, V_KX, V_MX);
+  };
+  if ((rc = ritz_on_x())) return rc;
+  bool hasP = false, must_step = false;
+  for (int its = 0;;) {                               // the renewal follows the steps of this call, max_it bounds *it
+    // the recurrences cannot drift: every 20 steps the products of X, and where the driver says so of P, are made again
+    if (its > 0 && its % 20 == 0 && !must_step) {
+      if ((rc = products(V_X, V_KX, V_MX))) return rc;
+      if (renew_p && hasP && (rc = products(V_P, V_KP, V_MP))) return rc;
+    }
+    const int np = hasP ? 3 : 2;
+    if ((rc = upload()) || (rc = enq_residual(true))) return rc;
+    if (after_residual && (rc = after_residual())) return rc;
+    if ((rc = products(V_W, V_KW, V_MW))) return rc;
+    EACH_RANK(c) enq_gram(c, np);
+    if ((rc = read_sums(0, MODAL_SUMS))) return rc;                     // the one synchronisation of a step
+    const bool stop = converged(want) && !must_step;
+    must_step = false;
+    if (stop || *it >= max_it) {
+      // at return: X orthonormalised on its own, fresh products, and the test made on them
+      if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
+      if (converged(want)) return LOBPCG_CONVERGED;
+      if (*it >= max_it) return LOBPCG_OUT_OF_STEPS;
+      must_step = true;                                                 // the recurrences had drifted: go on from the fresh products
+      continue;
+    }
+    int rank = 0;
+    if (!ritz(np, &rank)) return LOBPCG_BROKE;
+    if ((rc = upload())) return rc;
+    EACH_RANK(c) enq_combine(c, np, 1);
+    hasP = rank == 8 * np;                                              // a rank drop restarts the recurrence without P
+    ++its; ++*it;
+  }
+}
 
 int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, double *lambda, double *resid, int *iters)
 {
@@ -768,108 +889,40 @@ int modal_solve(feahip_ctx *c, int n_modes, double tol, int max_it, int warm, do
   if ((rc = feahip_create_stiffness(c)) || (rc = feahip_apply_prescribed_bc(c, 0.0))) return rc;
   if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
   else enq_precond_blockjacobi(c);
-  const size_t n8 = (size_t)c->ndof * MC;
-  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
-  double *theta = S.theta;
-  S.h_C.assign(24 * 16 + MC, 0.0);
-  auto products_x = [&]() { return launch_spmm_km(c, mv(c, V_X), mv(c, V_KX), mv(c, V_MX)); };
-  auto upload = [&]() -> int {                        // C and theta (h_C is not touched again before the next read-back)
-    for (int j = 0; j < MC; ++j) S.h_C[24 * 16 + j] = theta[j];
-    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + MODAL_SUMS, S.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
-    return FEAHIP_OK;
-  };
-  auto converged = [&]() {                            // the stop test on the norms in sums[0 .. 24)
-    bool ok = true;
-    for (int j = 0; j < MC; ++j) {
-      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
-      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
-      if (j < n_modes && !(ratio[j] <= tol)) ok = false;
-    }
-    return ok;
-  };
-  // Rayleigh-Ritz on np column blocks from the sums read back: theta and the coefficients; false when the basis breaks
-  auto ritz = [&](int np, int *rank) -> bool {
-    unpack_gram(sums + MODAL_NORMS, np, GM, GK);
-    double Cs[24 * 16];
-    const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
-    if (r < 0) return false;
-    std::fill(S.h_C.begin(), S.h_C.begin() + 24 * 16, 0.0);
-    std::copy(Cs, Cs + 8 * np * 16, S.h_C.begin());
-    *rank = r;
-    return true;
-  };
-  auto broke = [&]() {
-    S.have = false;
-    c->err = "solve_modes: the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes is not supported)";
-    return FEAHIP_ENOTCONVERGED;
-  };
-  // X alone: fresh products, the Gram sums of X, theta ascending and X M-orthonormal again, fresh products, the norms
-  auto ritz_on_x = [&]() -> int {
-    int rank = 0;
-    if ((rc = products_x())) return rc;
-    enq_gram(c, 1);
-    if ((rc = read_sums(c, MODAL_NORMS, MODAL_GRAM, sums))) return rc;
-    if (!ritz(1, &rank)) return broke();
-    if ((rc = upload())) return rc;
-    enq_combine(c, 1, 0);
-    return products_x();
-  };
-  auto fresh_norms = [&]() -> int {
-    if ((rc = enq_residual(c, false))) return rc;
-    return read_sums(c, 0, MODAL_NORMS, sums);
-  };
+  Lobpcg L({c}, nullptr, tol);
   auto finish = [&](int it, int code) {
     S.have = true;
-    for (int j = 0; j < n_modes; ++j) { lambda[j] = theta[j]; if (resid) resid[j] = ratio[j]; }
+    for (int j = 0; j < n_modes; ++j) { lambda[j] = L.theta[j]; if (resid) resid[j] = L.ratio[j]; }
     if (iters) *iters = it;
     if (code == FEAHIP_ENOTCONVERGED) c->err = "solve_modes: not converged after " + std::to_string(it) + " Rayleigh-Ritz steps";
     return code;
   };
-
   if (warm && S.have) {
     // the modes held, their theta, against the K of now: converged already means nothing is touched
-    if ((rc = upload()) || (rc = products_x()) || (rc = fresh_norms())) return rc;
-    if (converged()) return finish(0, FEAHIP_OK);
-  } else {
-    hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, V_X));
-  }
+    if ((rc = L.upload()) || (rc = L.products(V_X, V_KX, V_MX)) || (rc = L.fresh_norms())) return rc;
+    if (L.converged(n_modes)) return finish(0, FEAHIP_OK);
+  } else if ((rc = launch_modal_hash(c, mv(c, V_X)))) return rc;
   S.have = false;
-  if ((rc = ritz_on_x())) return rc;
-  bool hasP = false, must_step = false;
-  for (int it = 0;;) {
-    if (it > 0 && it % 20 == 0 && !must_step) { if ((rc = products_x())) return rc; }   // the recurrences cannot drift
-    const int np = hasP ? 3 : 2;
-    if ((rc = upload()) || (rc = enq_residual(c, true))) return rc;
-    if ((rc = launch_spmm_km(c, mv(c, V_W), mv(c, V_KW), mv(c, V_MW)))) return rc;
-    enq_gram(c, np);
-    if ((rc = read_sums(c, 0, MODAL_SUMS, sums))) return rc;            // the one synchronisation of a step
-    const bool stop = converged() && !must_step;
-    must_step = false;
-    if (stop || it >= max_it) {
-      // at return: X orthonormalised on its own, fresh products, and the test made on them
-      if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
-      if (converged()) return finish(it, FEAHIP_OK);
-      if (it >= max_it) return finish(it, FEAHIP_ENOTCONVERGED);
-      must_step = true;                                                 // the recurrences had drifted: go on from the fresh products
-      continue;
-    }
-    int rank = 0;
-    if (!ritz(np, &rank)) return broke();
-    if ((rc = upload())) return rc;
-    enq_combine(c, np, 1);
-    hasP = rank == 8 * np;                                              // a rank drop restarts the recurrence without P
-    ++it;
+  int it = 0;
+  const int end = L.run(n_modes, max_it, &it);
+  if (end < 0) return end;
+  if (end == LOBPCG_BROKE) {
+    c->err = "solve_modes: the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes is not supported)";
+    return FEAHIP_ENOTCONVERGED;
   }
+  return finish(it, end == LOBPCG_CONVERGED ? FEAHIP_OK : FEAHIP_ENOTCONVERGED);
 }
 
-int modal_get(feahip_ctx *c, int col, double *h_lib /*[3N], library ids*/)
+// column col of the block vector d_v8 to the host, [3N] in library ids
+static int get_column(feahip_ctx *c, const double *d_v8, int col, double *h_lib)
 {
-  hipLaunchKernelGGL(k_modal_extract, g256((size_t)c->ndof), dim3(256), 0, c->stream, (size_t)c->ndof, (const double *)mv(c, V_X), col, c->d_q);
+  hipLaunchKernelGGL(k_modal_extract, g256((size_t)c->ndof), dim3(256), 0, c->stream, (size_t)c->ndof, d_v8, col, c->d_q);
   FEA_HIP_CHECK(c, hipGetLastError());
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_lib, c->d_q, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return FEAHIP_OK;
 }
+int modal_get(feahip_ctx *c, int col, double *h_lib) { return get_column(c, mv(c, V_X), col, h_lib); }
 
 // ---- more than eight modes, and a shift: sweeps of the block with hard locking ------------------------------------------
 int ensure_locked(feahip_ctx *c, int n_modes)
@@ -928,11 +981,8 @@ int time_deflate_prepare(feahip_ctx *c)
 {
   int rc;
   if ((rc = time_modal_prepare(c)) || (rc = ensure_locked(c, FEA_MODAL_MAX_LOCKED))) return rc;
-  const size_t n8 = (size_t)c->ndof * MC;
   for (int mq = 0; mq < 2; ++mq)
-    for (int p = 0; p < MODAL_PANELS; ++p)
-      hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, locked_panel(c, mq, p));
-  FEA_HIP_CHECK(c, hipGetLastError());
+    for (int p = 0; p < MODAL_PANELS; ++p) if ((rc = launch_modal_hash(c, locked_panel(c, mq, p)))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return FEAHIP_OK;
 }
@@ -945,11 +995,10 @@ int time_deflate_kernel(feahip_ctx *c, int what)
   return FEAHIP_OK;
 }
 
-// The driver.  K_s = K + shift M (masked) is in K's store; the iteration is modal_solve's on the pencil (K_s, M), theta_s
-// = lambda + shift, with W deflated against the store before its products.  A sweep: deflate X, orthonormalise it on its
-// own, iterate until the leading min(6, n_modes - locked) columns pass the stop test on fresh products, lock the leading
-// converged columns, move the others to the front and refill from the hash.  (The small host helpers are modal_solve's,
-// restated: that function is not to change a bit, and is left as it is.)
+// The driver.  K_s = K + shift M (masked) is in K's store; the shared iteration runs on the pencil (K_s, M), theta_s =
+// lambda + shift, with W deflated against the store before its products (Lobpcg::after_residual).  A sweep: deflate X, one
+// Lobpcg::run until the leading min(6, n_modes - locked) columns pass the stop test on fresh products, lock the leading
+// converged columns, move the others to the front and refill from the hash.
 int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int max_it, double *lambda, double *resid,
                        int *iters, int *sweeps)
 {
@@ -970,36 +1019,10 @@ int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int
   if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
   else enq_precond_blockjacobi(c);
   const size_t n8 = (size_t)c->ndof * MC;
-  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
-  double *theta = S.theta;
-  S.h_C.assign(24 * 16 + MC, 0.0);
   int locked = 0, it = 0, sweep = 0, next_id = MC;
   for (int j = 0; j < n_modes; ++j) { lambda[j] = NAN; if (resid) resid[j] = NAN; }
-  auto products_x = [&]() { return launch_spmm_km(c, mv(c, V_X), mv(c, V_KX), mv(c, V_MX)); };
-  auto upload = [&]() -> int {
-    for (int j = 0; j < MC; ++j) S.h_C[24 * 16 + j] = theta[j];
-    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_small + MODAL_SUMS, S.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
-    return FEAHIP_OK;
-  };
-  auto converged = [&](int want) {                    // the stop test of the leading want columns, in the shifted quantities
-    bool ok = true;
-    for (int j = 0; j < MC; ++j) {
-      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
-      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
-      if (j < want && !(ratio[j] <= tol)) ok = false;
-    }
-    return ok;
-  };
-  auto ritz = [&](int np, int *rank) -> bool {
-    unpack_gram(sums + MODAL_NORMS, np, GM, GK);
-    double Cs[24 * 16];
-    const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
-    if (r < 0) return false;
-    std::fill(S.h_C.begin(), S.h_C.begin() + 24 * 16, 0.0);
-    std::copy(Cs, Cs + 8 * np * 16, S.h_C.begin());
-    *rank = r;
-    return true;
-  };
+  Lobpcg L({c}, nullptr, tol);
+  L.after_residual = [&]() { return launch_deflate(c, mv(c, V_W), locked); };
   auto done = [&](int code, const std::string &why) {
     // The store is in the order of locking.  Two eigenvalues that are equal to rounding (a degenerate pair split by the
     // end of a sweep) can come out of two sweeps in either order, so lambda is sorted once more, stably, and the modes
@@ -1016,59 +1039,23 @@ int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int
     if (code) c->err = "solve_modes_locked: " + why + " (" + std::to_string(locked) + " of " + std::to_string(n_modes) + " modes locked)";
     return code;
   };
-  auto broke = [&]() {
-    return done(FEAHIP_ENOTCONVERGED, "the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes needs a shift)");
-  };
-  auto ritz_on_x = [&]() -> int {
-    int rank = 0;
-    if ((rc = products_x())) return rc;
-    enq_gram(c, 1);
-    if ((rc = read_sums(c, MODAL_NORMS, MODAL_GRAM, sums))) return rc;
-    if (!ritz(1, &rank)) return broke();
-    if ((rc = upload())) return rc;
-    enq_combine(c, 1, 0);
-    return products_x();
-  };
-  auto fresh_norms = [&]() -> int {
-    if ((rc = enq_residual(c, false))) return rc;
-    return read_sums(c, 0, MODAL_NORMS, sums);
-  };
 
-  hipLaunchKernelGGL(k_modal_hash, g256(n8), dim3(256), 0, c->stream, n8, (const uint8_t *)c->d_dofmask, mv(c, V_X));
+  if ((rc = launch_modal_hash(c, mv(c, V_X)))) return rc;
   while (locked < n_modes) {
     ++sweep;
     const int want = n_modes - locked < MC - 2 ? n_modes - locked : MC - 2;   // two guard columns
-    if ((rc = launch_deflate(c, mv(c, V_X), locked)) || (rc = ritz_on_x())) return rc;
-    bool hasP = false, must_step = false;
-    for (int its = 0;;) {
-      if (its > 0 && its % 20 == 0 && !must_step) { if ((rc = products_x())) return rc; }
-      const int np = hasP ? 3 : 2;
-      if ((rc = upload()) || (rc = enq_residual(c, true)) || (rc = launch_deflate(c, mv(c, V_W), locked))) return rc;
-      if ((rc = launch_spmm_km(c, mv(c, V_W), mv(c, V_KW), mv(c, V_MW)))) return rc;
-      enq_gram(c, np);
-      if ((rc = read_sums(c, 0, MODAL_SUMS, sums))) return rc;          // the one synchronisation of a step
-      const bool stop = converged(want) && !must_step;
-      must_step = false;
-      if (stop || it >= max_it) {
-        if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
-        if (converged(want)) break;
-        if (it >= max_it) return done(FEAHIP_ENOTCONVERGED, "not converged after " + std::to_string(it) + " Rayleigh-Ritz steps");
-        must_step = true;
-        continue;
-      }
-      int rank = 0;
-      if (!ritz(np, &rank)) return broke();
-      if ((rc = upload())) return rc;
-      enq_combine(c, np, 1);
-      hasP = rank == 8 * np;
-      ++its; ++it;
-    }
+    if ((rc = launch_deflate(c, mv(c, V_X), locked))) return rc;
+    const int end = L.run(want, max_it, &it);         // (the renewal follows the sweep's own steps, max_it bounds their total)
+    if (end < 0) return end;
+    if (end == LOBPCG_BROKE)
+      return done(FEAHIP_ENOTCONVERGED, "the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes needs a shift)");
+    if (end == LOBPCG_OUT_OF_STEPS) return done(FEAHIP_ENOTCONVERGED, "not converged after " + std::to_string(it) + " Rayleigh-Ritz steps");
     // lock the leading converged columns, contiguous from column 0, within n_modes
     int k = 0;
-    while (k < MC && locked + k < n_modes && ratio[k] <= tol) ++k;
+    while (k < MC && locked + k < n_modes && L.ratio[k] <= tol) ++k;
     hipLaunchKernelGGL(k_modal_lock, dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof, locked, k,
                        (const double *)mv(c, V_X), (const double *)mv(c, V_MX), locked_panel(c, 0, 0), locked_panel(c, 1, 0), n8);
-    for (int j = 0; j < k; ++j) { lambda[locked + j] = theta[j] - shift; if (resid) resid[locked + j] = ratio[j]; }
+    for (int j = 0; j < k; ++j) { lambda[locked + j] = L.theta[j] - shift; if (resid) resid[locked + j] = L.ratio[j]; }
     locked += k;
     if (locked < n_modes) {
       hipLaunchKernelGGL(k_modal_advance, dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof, k, next_id,
@@ -1081,29 +1068,15 @@ int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int
   return done(FEAHIP_OK, "");
 }
 
-int modal_get_locked(feahip_ctx *c, int mode, double *h_lib /*[3N], library ids*/)   // mode of the ascending lambda
+int modal_get_locked(feahip_ctx *c, int mode, double *h_lib)           // mode of the ascending lambda
 {
-  hipLaunchKernelGGL(k_modal_extract, g256((size_t)c->ndof), dim3(256), 0, c->stream, (size_t)c->ndof,
-                     (const double *)locked_panel(c, 0, c->modal.lock_order[mode] / MC), c->modal.lock_order[mode] % MC, c->d_q);
-  FEA_HIP_CHECK(c, hipGetLastError());
-  FEA_HIP_CHECK(c, hipMemcpyAsync(h_lib, c->d_q, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  return FEAHIP_OK;
+  const int at = c->modal.lock_order[mode];
+  return get_column(c, locked_panel(c, 0, at / MC), at % MC, h_lib);
 }
 
 // ---- the base solve over the ranks of a sharded run (feahip_solve_modes_sharded) ----------------------------------------
-// modal_solve step for step on R = the ranks this process drives (all members of an in-process group, or the one
-// context of an RCCL rank).  Every rank keeps the nine block vectors of its own context; a vector is authoritative on
-// the owned rows [row0, row1), and the halo rows of X and W hold what the block exchange last brought.  Per step:
-//   residual, preconditioner          owned rows; kind 1: one W-cycle per column on the rank's own diagonal block
-//   exchange_block_begin(W)           pack on the context's stream, copies and unpack on the communication stream
-//   k_spmm_km on the interior chunks  they read no halo column (install_plan), so they run under the exchange
-//   exchange_block_end, k_spmm_km on the chunks before and after the interior range
-//   k_modal_gram, k_modal_reduce      owned rows; 24 + 768 sums into d_small, copied into d_vred
-//   Transport::allreduce_vec          792 doubles; in a group the sums meet on the host in rank order
-//   (one read-back; modal_ritz once on the all-reduced sums; C and theta uploaded to every rank of R)
-//   k_modal_combine                   owned rows
-// Every branch below depends on the all-reduced sums alone, so all ranks take it together.
+// modal_solve on R = the ranks this process drives (all members of an in-process group, or the one context of an RCCL
+// rank): the shared iteration with the run's transport, the start block keyed by the node's identity in the whole mesh.
 int ensure_modal_dist(feahip_ctx *c)
 {
   int rc;
@@ -1166,35 +1139,7 @@ void modal_enq_block_poison(feahip_ctx *c, double *d_v8)
                      (const int *)c->d_recv_idx, (v2d *)d_v8);
 }
 
-// k_spmm_km on the chunks [first, first + n) of the rank: a row's sums are formed by one wave in block order, so the
-// cut of the launches changes no bit
-static void enq_spmm_chunks(feahip_ctx *c, int first, int n, const double *d_x8, double *d_y8, double *d_z8)
-{
-  if (n <= 0) return;
-  const int g = (n + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
-  hipLaunchKernelGGL(k_spmm_km, dim3(g < RB ? g : RB), dim3(256), 0, c->stream, c->chunk0 + first, n, c->d_chunk, c->d_rowptr,
-                     c->d_colidx, (const double *)c->d_K, (const double *)c->mass.d_m, (const uint8_t *)c->d_dofmask,
-                     (const v2d *)d_x8, (v2d *)d_y8, (v2d *)d_z8);
-}
-
-// [vector jy, vector jz] <- [K, mask(M)] vector jx on the owned rows of every rank, the halo rows of jx by exchange
-static int products_dist(std::vector<feahip_ctx *> &R, Transport *T, int jx, int jy, int jz)
-{
-  int rc;
-  std::vector<double *> xs;
-  for (feahip_ctx *c : R) xs.push_back(mv(c, jx));
-  if ((rc = T->exchange_block_begin(R, xs))) return rc;
-  FOR_RANKS(c) enq_spmm_chunks(c, c->ichunk_lo, c->ichunk_hi - c->ichunk_lo, mv(c, jx), mv(c, jy), mv(c, jz));
-  if ((rc = T->exchange_block_end(R))) return rc;
-  FOR_RANKS(c) {
-    enq_spmm_chunks(c, 0, c->ichunk_lo, mv(c, jx), mv(c, jy), mv(c, jz));
-    enq_spmm_chunks(c, c->ichunk_hi, c->nchunks_local - c->ichunk_hi, mv(c, jx), mv(c, jy), mv(c, jz));
-    FEA_HIP_CHECK(c, hipGetLastError());
-  }
-  return FEAHIP_OK;
-}
-
-int modal_spmm_km_dist(std::vector<feahip_ctx *> &R) { return products_dist(R, R[0]->tr, V_X, V_KX, V_MX); }
+int modal_spmm_km_dist(std::vector<feahip_ctx *> &R) { return block_products(R, R[0]->tr, false, V_X, V_KX, V_MX); }
 
 // n doubles per rank (host, rank k's at h[k n]) summed over all ranks into out: through d_vred and the transport
 static int allreduce_host(std::vector<feahip_ctx *> &R, Transport *T, int n, const double *h, double *out)
@@ -1213,31 +1158,11 @@ static int allreduce_host(std::vector<feahip_ctx *> &R, Transport *T, int n, con
   return FEAHIP_OK;
 }
 
-// the sums [e0, e0 + n) of every rank reduced into its d_small, copied into d_vred, summed over the ranks and read
-// into h + e0 (one synchronisation): every rank holds, and this process reads, the same bits
-static int read_sums_dist(std::vector<feahip_ctx *> &R, Transport *T, int e0, int n, double *h)
-{
-  int rc;
-  FOR_RANKS(c) {
-    hipLaunchKernelGGL(k_modal_reduce, dim3(n), dim3(256), 0, c->stream, e0, resid_grid(c), gram_grid(c),
-                       (const double *)c->modal.d_part, c->modal.d_small);
-    FEA_HIP_CHECK(c, hipGetLastError());
-    FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_vred, c->modal.d_small + e0, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-  }
-  if ((rc = T->allreduce_vec(R, (size_t)n, false))) return rc;
-  feahip_ctx *c0 = R[0];
-  (void)hipSetDevice(c0->device);
-  FEA_HIP_CHECK(c0, hipMemcpyAsync(h + e0, c0->d_vred, sizeof(double) * n, hipMemcpyDeviceToHost, c0->stream));
-  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
-  return FEAHIP_OK;
-}
-
 int modal_solve_dist(std::vector<feahip_ctx *> &R, int n_modes, double tol, int max_it, int warm, double *lambda,
                      double *resid, int *iters)
 {
   int rc;
   Transport *T = R[0]->tr;
-  feahip_ctx *c0 = R[0];
   auto refuse = [&](int code, const std::string &why) { for (feahip_ctx *c : R) c->err = "solve_modes_sharded: " + why; return code; };
   // What decides a refusal is all-reduced, so that every rank of the run returns the same code: the free dofs, the
   // ranks that hold modes of a sharded solve on their current rows, the preconditioner kinds, a missing mass
@@ -1280,76 +1205,23 @@ int modal_solve_dist(std::vector<feahip_ctx *> &R, int n_modes, double tol, int 
     if (c->precond == 1) { if ((rc = amg_prepare(c))) return rc; }
     else enq_precond_blockjacobi(c);
   }
-  ModalState &S0 = c0->modal;                           // the host side of the step lives on the first rank driven here
-  double sums[MODAL_SUMS], GM[24 * 24], GK[24 * 24], ratio[MC];
-  double *theta = S0.theta;
-  S0.h_C.assign(24 * 16 + MC, 0.0);
-  auto products_x = [&]() { return products_dist(R, T, V_X, V_KX, V_MX); };
-  auto upload = [&]() -> int {                        // C and theta to every rank (h_C is not touched again before the next read-back)
-    for (int j = 0; j < MC; ++j) S0.h_C[24 * 16 + j] = theta[j];
-    FOR_RANKS(c) {
-      FEA_HIP_CHECK(c, hipMemcpyAsync(c->modal.d_small + MODAL_SUMS, S0.h_C.data(), sizeof(double) * (24 * 16 + MC), hipMemcpyHostToDevice, c->stream));
-    }
-    return FEAHIP_OK;
-  };
-  auto converged = [&]() {                            // modal_solve's stop test on the all-reduced norms
-    bool ok = true;
-    for (int j = 0; j < MC; ++j) {
-      const double den = sqrt(sums[8 + j]) + fabs(theta[j]) * sqrt(sums[16 + j]), num = sqrt(sums[j]);
-      ratio[j] = den > 0.0 ? num / den : (num == 0.0 ? 0.0 : INFINITY);
-      if (j < n_modes && !(ratio[j] <= tol)) ok = false;
-    }
-    return ok;
-  };
-  auto ritz = [&](int np, int *rank) -> bool {        // once for all ranks of R
-    unpack_gram(sums + MODAL_NORMS, np, GM, GK);
-    double Cs[24 * 16];
-    const int r = modal_ritz(8 * np, GM, GK, MC, theta, Cs);
-    if (r < 0) return false;
-    std::fill(S0.h_C.begin(), S0.h_C.begin() + 24 * 16, 0.0);
-    std::copy(Cs, Cs + 8 * np * 16, S0.h_C.begin());
-    *rank = r;
-    return true;
-  };
-  auto broke = [&]() {
-    return refuse(FEAHIP_ENOTCONVERGED, "the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes is not supported)");
-  };
-  auto gram = [&](int np) { FOR_RANKS(c) enq_gram(c, np); };
-  auto combine = [&](int np, int write_p) { FOR_RANKS(c) enq_combine(c, np, write_p); };
-  auto residual = [&](bool precond) -> int {
-    FOR_RANKS(c) { if ((rc = enq_residual(c, precond))) return rc; }
-    return FEAHIP_OK;
-  };
-  auto ritz_on_x = [&]() -> int {
-    int rank = 0;
-    if ((rc = products_x())) return rc;
-    gram(1);
-    if ((rc = read_sums_dist(R, T, MODAL_NORMS, MODAL_GRAM, sums))) return rc;
-    if (!ritz(1, &rank)) return broke();
-    if ((rc = upload())) return rc;
-    combine(1, 0);
-    return products_x();
-  };
-  auto fresh_norms = [&]() -> int {
-    if ((rc = residual(false))) return rc;
-    return read_sums_dist(R, T, 0, MODAL_NORMS, sums);
-  };
+  Lobpcg L(R, T, tol);
   auto finish = [&](int it, int code) {
     for (feahip_ctx *c : R) {
       ModalState &S = c->modal;
       S.have_sharded = true; S.sh_row0 = c->row0; S.sh_row1 = c->row1;
-      for (int j = 0; j < MC; ++j) S.theta[j] = theta[j];
+      for (int j = 0; j < MC; ++j) S.theta[j] = L.theta[j];
       if (code == FEAHIP_ENOTCONVERGED) c->err = "solve_modes_sharded: not converged after " + std::to_string(it) + " Rayleigh-Ritz steps";
     }
-    for (int j = 0; j < n_modes; ++j) { lambda[j] = theta[j]; if (resid) resid[j] = ratio[j]; }
+    for (int j = 0; j < n_modes; ++j) { lambda[j] = L.theta[j]; if (resid) resid[j] = L.ratio[j]; }
     if (iters) *iters = it;
     return code;
   };
 
   if (warm && have) {
     // the modes held, their theta, against the K of now: converged already means nothing is touched
-    if ((rc = upload()) || (rc = products_x()) || (rc = fresh_norms())) return rc;
-    if (converged()) return finish(0, FEAHIP_OK);
+    if ((rc = L.upload()) || (rc = L.products(V_X, V_KX, V_MX)) || (rc = L.fresh_norms())) return rc;
+    if (L.converged(n_modes)) return finish(0, FEAHIP_OK);
   } else {
     FOR_RANKS(c) {
       if (own_nodes(c) > 0)
@@ -1357,30 +1229,10 @@ int modal_solve_dist(std::vector<feahip_ctx *> &R, int n_modes, double tol, int 
                            (const int *)c->modal.d_key, (const uint8_t *)(c->d_dofmask + (size_t)3 * c->row0), mv(c, V_X) + own_off8(c));
     }
   }
-  if ((rc = ritz_on_x())) return rc;
-  bool hasP = false, must_step = false;
-  for (int it = 0;;) {
-    if (it > 0 && it % 20 == 0 && !must_step) { if ((rc = products_x())) return rc; }   // the recurrences cannot drift
-    const int np = hasP ? 3 : 2;
-    if ((rc = upload()) || (rc = residual(true))) return rc;
-    if ((rc = products_dist(R, T, V_W, V_KW, V_MW))) return rc;
-    gram(np);
-    if ((rc = read_sums_dist(R, T, 0, MODAL_SUMS, sums))) return rc;    // the one synchronisation of a step
-    const bool stop = converged() && !must_step;
-    must_step = false;
-    if (stop || it >= max_it) {
-      // at return: X orthonormalised on its own, fresh products, and the test made on them
-      if ((rc = ritz_on_x()) || (rc = upload()) || (rc = fresh_norms())) return rc;
-      if (converged()) return finish(it, FEAHIP_OK);
-      if (it >= max_it) return finish(it, FEAHIP_ENOTCONVERGED);
-      must_step = true;                                                 // the recurrences had drifted: go on from the fresh products
-      continue;
-    }
-    int rank = 0;
-    if (!ritz(np, &rank)) return broke();
-    if ((rc = upload())) return rc;
-    combine(np, 1);
-    hasP = rank == 8 * np;                                              // a rank drop restarts the recurrence without P
-    ++it;
-  }
+  int it = 0;
+  const int end = L.run(n_modes, max_it, &it);
+  if (end < 0) return end;
+  if (end == LOBPCG_BROKE)
+    return refuse(FEAHIP_ENOTCONVERGED, "the Rayleigh-Ritz basis lost its rank or a sum is not finite (a body with zero-energy modes is not supported)");
+  return finish(it, end == LOBPCG_CONVERGED ? FEAHIP_OK : FEAHIP_ENOTCONVERGED);
 }

@@ -226,6 +226,24 @@ def test_two_cold_solves_give_the_same_bits():
     s.close()
 
 
+@pytest.mark.parametrize("kind", ["tet4", "hex8"])
+def test_six_modes_without_a_shift_are_the_bits_of_solve_modes(kind):
+    """One sweep of the locked solve with nothing locked and no shift is the base solve: the deflation returns before any
+    launch, the stop test is on the same six leading columns, the start block, the iteration and the final Ritz step on
+    X are the same, the lock copies the columns verbatim, theta - 0.0 is theta and the stable sort of an ascending list
+    is the identity.  Two fresh contexts under block-Jacobi: equal, not close."""
+    a, b = solver(DECKS[kind]()), solver(DECKS[kind]())
+    lam_l, res_l, steps_l, sweeps = a.solve_modes_locked(6, 0.0, TOL, MAX_IT)
+    lam, res, steps = b.solve_modes(6, TOL, MAX_IT)
+    phi_l, phi, ndof = a.locked_modes(), b.modes(0, 6), a.ndof
+    a.close()
+    b.close()
+    print(kind, "steps", steps_l, steps, "sweeps", sweeps)
+    assert sweeps == 1 and steps_l == steps > 0
+    assert np.array_equal(lam_l, lam) and np.array_equal(res_l, res)
+    assert phi_l.shape == phi.shape == (6, ndof) and np.array_equal(phi_l, phi)
+
+
 def test_multigrid_preconditioner():
     """Preconditioner 1 (one W-cycle per column and step, the deflation after the cycles): twelve modes without a shift and
     with one of the order of the first eigenvalue, the criterion of the supported bodies.  The steps are printed."""
