@@ -16,19 +16,20 @@ int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newto
 {
   int rc, nlog = 0, step = 0;
   // (the feahip_* entry points set the device in their guard; that FOR_RANKS sets it as well is harmless)
-  for (; step < load_increments; ++step) {                           // fea_solver.c:163
-    int it = 0;
+  // One pass of Newton iterations at the nodes and the load in force: K, then iterations until the energy passes or
+  // max_newton of them are spent (failed).  A load increment is one pass; with contact multipliers to update, one more
+  // per augmentation.  it counts the iterations of all passes of the step.
+  auto newton_pass = [&](int &it, bool &failed) -> int {
+    int k = 0;
     double tolerance = 0;
-    FOR_RANKS(c) { if ((rc = feahip_update_nodes_with_bc(c, 1.0))) return rc; }   // :168 (prescribed values are replicated)
-    FOR_RANKS(c) { if ((rc = feahip_update_state(c, nullptr))) return rc; }   // :171-174
     FOR_RANKS(c) { if ((rc = feahip_create_stiffness(c))) return rc; }   // :177 (owned rows, ghost elements recomputed)
     if (modified_newton) { FOR_RANKS(c) { if ((rc = feahip_stash_stiffness(c))) return rc; } }   // :179
     do {
-      it++;
+      it++; k++;
       if (modified_newton) {
         FOR_RANKS(c) { if ((rc = feahip_create_residual_forces(c))) return rc; }   // :185
         FOR_RANKS(c) { if ((rc = feahip_restore_stiffness(c))) return rc; }   // :194-195
-      } else if (it == 1) {
+      } else if (k == 1) {
         FOR_RANKS(c) { if ((rc = feahip_create_residual_forces(c))) return rc; }   // K of :177 is current
       } else {
         FOR_RANKS(c) { if ((rc = feahip_create_stiffness_and_residual(c))) return rc; }   // :185 + :200
@@ -50,14 +51,14 @@ int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newto
         for (int ls = 0; ls < ls_max; ++ls) {
           const double x1 = b - tau * (b - a), x2 = a + tau * (b - a);
           double f[2];
-          for (int k = 0; k < 2; ++k) {
-            const double xk = k == 0 ? x1 : x2;
+          for (int j = 0; j < 2; ++j) {
+            const double xk = j == 0 ? x1 : x2;
             if ((rc = dist_nodes_add_scaled(R, xk - at, at == 0.0))) return rc;
             at = xk;
             FOR_RANKS(c) { if ((rc = feahip_create_residual_forces(c))) return rc; }
             double uf = 0;
             if ((rc = dist_energy(R, &uf))) return rc;                // <u, -R> with the sign of the residual vector f
-            f[k] = fabs(xk * uf);
+            f[j] = fabs(xk * uf);
           }
           if (f[0] > f[1]) a = x1; else b = x2;
           if (fabs(tolerance) < f[0] && fabs(tolerance) < f[1]) { eta = 1.0; break; }
@@ -66,9 +67,31 @@ int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newto
         if ((rc = dist_nodes_add_scaled(R, eta - at, at == 0.0))) return rc;
       }
       FOR_RANKS(c) { if ((rc = feahip_update_state(c, nullptr))) return rc; }   // :217-218
-    } while (fabs(tolerance) > desired_tolerance && it < max_newton); // :220-221
+    } while (fabs(tolerance) > desired_tolerance && k < max_newton); // :220-221
+    failed = k == max_newton;                                         // :225-231
+    return FEAHIP_OK;
+  };
+  ContactState none;                                                  // (the parameters are the same on every rank that has them)
+  const ContactState *with = &none;
+  for (feahip_ctx *c : R) if (c->contact.set) { with = &c->contact; break; }
+  const ContactState &contact = *with;
+  for (; step < load_increments; ++step) {                           // fea_solver.c:163
+    int it = 0;
+    bool failed = false;
+    FOR_RANKS(c) { if ((rc = feahip_update_nodes_with_bc(c, 1.0))) return rc; }   // :168 (prescribed values are replicated)
+    FOR_RANKS(c) { if ((rc = feahip_update_state(c, nullptr))) return rc; }   // :171-174
+    if ((rc = newton_pass(it, failed))) return rc;
+    // augmented Lagrangian: while the largest penetration of an active pair exceeds the tolerance, update the multipliers
+    // and iterate again at the same load (every rank reads the same all-reduced number and takes the same branch)
+    for (int aug = 0; contact.set && !failed && aug < contact.augment_max; ++aug) {
+      double info[4];
+      if ((rc = dist_contact_info(R, info))) return rc;
+      if (info[1] <= contact.gap_tolerance) break;
+      if ((rc = dist_contact_augment(R, nullptr))) return rc;
+      if ((rc = newton_pass(it, failed))) return rc;
+    }
     if (its_log) its_log[step] = it;
-    if (it == max_newton) break;                                      // :225-231
+    if (failed) break;
   }
   if (steps_done) *steps_done = step;
   for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
@@ -177,7 +200,15 @@ int dist_stable_step(std::vector<feahip_ctx *> &R, double *dt_crit)
 {
   int rc;
   FOR_RANKS(c) { if ((rc = lump_ensure(c, "feahip_stable_step"))) return rc; }
-  FOR_RANKS(c) { if ((rc = feahip_create_stiffness(c))) return rc; }   // (K is another matrix from here on: k_epoch)
+  // contact: the plain assembly, then w eps n n' of EVERY contact pair in place of the active pairs' term (positive
+  // semi-definite, so still a bound for the active ones): a node that enters contact between two estimates does not push the
+  // step over the bound.  K stays as this leaves it
+  FOR_RANKS(c) {                                                       // (K is another matrix from here on: k_epoch)
+    if (c->contact.n == 0) { if ((rc = feahip_create_stiffness(c))) return rc; continue; }
+    ++c->k_epoch; c->k_bc = false;                                     // feahip_create_stiffness, without the contact term
+    if ((rc = launch_assemble(c, true, false, true))) return rc;
+  }
+  FOR_RANKS(c) { if ((rc = launch_contact_bound(c))) return rc; }
   FOR_RANKS(c) { if ((rc = launch_gershgorin(c))) return rc; }
   double bound = 0;
   if ((rc = dist_read_scalars(R, RankReduce::max, 1, &bound))) return rc;
@@ -198,6 +229,37 @@ int dist_kinetic_energy(std::vector<feahip_ctx *> &R, double *e)
   FOR_RANKS(c) { if ((rc = lump_ensure(c, "feahip_kinetic_energy"))) return rc; }
   FOR_RANKS(c) { if ((rc = launch_kinetic_energy(c, c->d_scal + 8))) return rc; }
   return dist_read_scalars(R, RankReduce::sum, 1, e);
+}
+
+// contact over all ranks: active pairs, the largest penetration over them, sum w t, Pi_c (identical on every rank)
+int dist_contact_info(std::vector<feahip_ctx *> &R, double *out)
+{
+  int rc;
+  double s[4];
+  FOR_RANKS(c) { if ((rc = launch_contact_info(c))) return rc; }
+  if (Transport *T = R[0]->tr)                                        // three sums in [8 .. 11), the maximum in [11]
+    if ((rc = T->allreduce(R, 0, 3)) || (rc = T->allreduce_max(R, 3, 1))) return rc;
+  feahip_ctx *c0 = R[0];
+  (void)hipSetDevice(c0->device);
+  FEA_HIP_CHECK(c0, hipMemcpyAsync(s, c0->d_scal + 8, sizeof(s), hipMemcpyDeviceToHost, c0->stream));
+  FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  out[0] = s[0]; out[1] = s[3]; out[2] = s[1]; out[3] = s[2];
+  return FEAHIP_OK;
+}
+
+// the largest penetration over the active pairs as it stands (where asked for), then mu <- max(0, mu + eps p) on every
+// rank's own nodes
+int dist_contact_augment(std::vector<feahip_ctx *> &R, double *max_penetration)
+{
+  int rc;
+  double info[4];
+  if (max_penetration) {                                              // (a caller that has just read it passes null)
+    if ((rc = dist_contact_info(R, info))) return rc;
+    *max_penetration = info[1];
+  }
+  FOR_RANKS(c) { if ((rc = launch_contact_augment(c))) return rc; }
+  for (feahip_ctx *c : R) { (void)hipSetDevice(c->device); FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream)); }
+  return FEAHIP_OK;
 }
 
 // sum_e W_e over all ranks: every rank sums the shares W_e / npe of the nodes it owns, so that an element a rank holds as

@@ -1,5 +1,6 @@
 // feahip_api.hip -- extern "C" entry points of include/fea_hip.h.
 #include "feahip_internal.h"
+#include <limits>
 
 #undef hipMalloc
 hipError_t feahip_device_malloc(void **p, size_t bytes)
@@ -466,6 +467,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   delete c->h_pat; c->h_pat = nullptr;
   c->generic.release(); c->visits.release(); c->quad.release(); c->gather.release(); c->gather10.release();
   c->surf.release();
+  c->contact.release();
   c->mass.release();
   c->results.release();
   c->modal.release();
@@ -671,6 +673,130 @@ extern "C" int feahip_get_load_factor(feahip_ctx *c, double *lambda)
   if (!c || !lambda) return FEAHIP_EINVAL;
   *lambda = c->load_factor;
   return FEAHIP_OK;
+}
+
+// ---- contact with rigid obstacles (kernels_contact.hip) ----------------------
+static std::vector<feahip_ctx *> ranks_of(feahip_ctx *c);
+static int surface_error(feahip_ctx *to, const std::vector<feahip_ctx *> &R, int rc);
+
+extern "C" int feahip_set_contact(feahip_ctx *c, int n_faces, int nodes_per_face, const int *face_nodes, int n_obstacles,
+                                  const int *kind, const double *geom, double penalty, int augment_max, double gap_tolerance)
+{
+  CTX_GUARD_NOK(c);
+  return set_contact(c, n_faces, nodes_per_face, face_nodes, n_obstacles, kind, geom, penalty, augment_max, gap_tolerance);
+}
+
+// the owned contact nodes in the caller's ids, ascending: (caller id, index into ContactState::h_node)
+static std::vector<std::pair<int, int>> contact_order(const feahip_ctx *c)
+{
+  std::vector<std::pair<int, int>> order;
+  if (c->contact.n == 0) return order;
+  int n0, n1;
+  contact_owned(c, n0, n1);
+  for (int i = n0; i < n1; ++i) order.emplace_back(c->perm.empty() ? c->contact.h_node[i] : c->iperm[c->contact.h_node[i]], i);
+  std::sort(order.begin(), order.end());
+  return order;
+}
+
+extern "C" int feahip_get_contact_nodes(feahip_ctx *c, int *n, int *nodes, double *weights)
+{
+  if (!c || !n) return FEAHIP_EINVAL;
+  const auto order = contact_order(c);
+  *n = (int)order.size();
+  for (size_t k = 0; k < order.size(); ++k) {
+    if (nodes) nodes[k] = order[k].first;
+    if (weights) weights[k] = c->contact.h_w[order[k].second];
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_contact_obstacles(feahip_ctx *c, int *n_obstacles)
+{
+  if (!c || !n_obstacles) return FEAHIP_EINVAL;
+  *n_obstacles = c->contact.nobs;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_contact_multipliers(feahip_ctx *c, double *mu)
+{
+  CTX_GUARD_NOK(c);
+  if (!mu) return FEAHIP_EINVAL;
+  const ContactState &S = c->contact;
+  if (S.n == 0) return FEAHIP_OK;
+  std::vector<double> all((size_t)S.n * S.nobs);
+  FEA_HIP_CHECK(c, hipMemcpyAsync(all.data(), S.d_mu, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  const auto order = contact_order(c);
+  for (size_t k = 0; k < order.size(); ++k)
+    std::copy(all.begin() + (size_t)order[k].second * S.nobs, all.begin() + (size_t)(order[k].second + 1) * S.nobs, mu + k * S.nobs);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_set_contact_multipliers(feahip_ctx *c, const double *mu)
+{
+  CTX_GUARD_NOK(c);
+  if (!mu) return FEAHIP_EINVAL;
+  const ContactState &S = c->contact;
+  if (S.n == 0) return FEAHIP_OK;
+  const auto order = contact_order(c);
+  for (size_t k = 0; k < order.size() * S.nobs; ++k)
+    if (!(mu[k] >= 0.0)) { c->err = "feahip_set_contact_multipliers: multiplier " + std::to_string(k) + " is negative or not a number"; return FEAHIP_EINVAL; }
+  std::vector<double> all((size_t)S.n * S.nobs);          // the rows of other ranks keep what they hold
+  FEA_HIP_CHECK(c, hipMemcpyAsync(all.data(), S.d_mu, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < order.size(); ++k)
+    std::copy(mu + k * S.nobs, mu + (k + 1) * S.nobs, all.begin() + (size_t)order[k].second * S.nobs);
+  FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_mu, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_contact_forces(feahip_ctx *c, double *f)
+{
+  CTX_GUARD_NOK(c);
+  if (!f) return FEAHIP_EINVAL;
+  double *d = nullptr;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (size_t)c->ndof));
+  int rc = hipMemsetAsync(d, 0, sizeof(double) * (size_t)c->ndof, c->stream) == hipSuccess ? launch_contact(c, false, true, d) : FEAHIP_EHIP;
+  if (rc == FEAHIP_OK) rc = get_node_vec(c, d, f);
+  (void)hipFree(d);
+  return rc;
+}
+
+extern "C" int feahip_get_contact_status(feahip_ctx *c, double *gap, double *pressure)
+{
+  CTX_GUARD_NOK(c);
+  const size_t N = (size_t)c->N;
+  std::vector<double> h(2 * N, 0.0);
+  std::fill(h.begin(), h.begin() + N, std::numeric_limits<double>::infinity());
+  double *d = nullptr;
+  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * 2 * N));
+  int rc = hipMemcpyAsync(d, h.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream) == hipSuccess
+               ? launch_contact_status(c, d, d + N) : FEAHIP_EHIP;
+  if (rc == FEAHIP_OK && hipMemcpyAsync(h.data(), d, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = FEAHIP_EHIP;
+  if (rc == FEAHIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = FEAHIP_EHIP;
+  (void)hipFree(d);
+  if (rc) return rc;
+  for (int a = 0; a < c->N; ++a) {
+    if (gap) gap[a] = h[(size_t)lib_id(c, a)];
+    if (pressure) pressure[a] = h[N + (size_t)lib_id(c, a)];
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_contact_info(feahip_ctx *c, double *out)
+{
+  CTX_GUARD_NOK(c);
+  if (!out) return FEAHIP_EINVAL;
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  return surface_error(c, R, dist_contact_info(R, out));
+}
+
+extern "C" int feahip_contact_augment(feahip_ctx *c, double *max_penetration)
+{
+  CTX_GUARD_NOK(c);
+  std::vector<feahip_ctx *> R = ranks_of(c);
+  return surface_error(c, R, dist_contact_augment(R, max_penetration));
 }
 
 // ---- material table (include/fea_hip.h).  Validated in full before anything of the context changes.
@@ -1538,6 +1664,7 @@ extern "C" int feahip_solve_arclength(feahip_ctx *c, double lambda_max, int max_
   int rc;
   if ((rc = solve2_refused(c, "solve_arclength"))) return rc;
   if (c->mass.body[0] != 0.0 || c->mass.body[1] != 0.0 || c->mass.body[2] != 0.0) { c->err = "solve_arclength: a body force is set on this context (not followed by the arc length)"; return FEAHIP_EINVAL; }
+  if (c->contact.set) { c->err = "solve_arclength: contact is set on this context (not followed by the arc length)"; return FEAHIP_ESTATE; }
   if (c->surf.nfaces == 0) { c->err = "solve_arclength: no surface loads on this context"; return FEAHIP_ESTATE; }
   if ((rc = ensure_solve2(c))) return rc;
   return arclength_solve(c, lambda_max, max_steps, max_newton, desired_tolerance, solver_type, solver_tolerance,
@@ -1848,6 +1975,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
   }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
+  if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
   return time_enqueued(c, warmup, iters, avg_ms, [&](int) -> int {
     switch (what) {
     case 0: return launch_assemble(c, true, true);
@@ -1864,6 +1992,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 13: case 14: case 15: return time_modal_kernel(c, what);
     case 16: case 17: return time_deflate_kernel(c, what);
     case 18: case 19: return time_geom_kernel(c, what);
+    case 20: return launch_contact(c, true, true, c->d_f);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

@@ -404,6 +404,43 @@ struct SurfaceLoads {
   void release() { dev_free({d_fnode, d_kind, d_val, d_fc, d_lnode, d_lptr, d_lslot}); *this = SurfaceLoads(); }
 };
 
+// quadrature of a boundary face (kernels_surface.hip): tri3 one point, tri6 the 6-point degree-4 rule, quad4 2 x 2 Gauss
+#define FEA_SURF_MAX_PTS 6
+#define FEA_SURF_MAX_NPF 6
+struct FaceRule {
+  int npt;
+  double w[FEA_SURF_MAX_PTS];
+  double N[FEA_SURF_MAX_PTS][FEA_SURF_MAX_NPF];
+  double dN[FEA_SURF_MAX_PTS][2][FEA_SURF_MAX_NPF];
+};
+void face_rule(int npf, FaceRule &R);
+
+// frictionless contact of nodes with rigid obstacles (kernels_contact.hip): nothing of it exists, and nothing is
+// launched, until feahip_set_contact.  The obstacles travel to the kernels by value, their point already moved to
+// c0 + load_factor * travel.
+struct ContactObstacles {
+  int n;
+  int kind[FEAHIP_MAX_OBSTACLES];
+  double c[FEAHIP_MAX_OBSTACLES][3];   // the point at the load factor of the launch
+  double a[FEAHIP_MAX_OBSTACLES][3];   // unit normal (plane) or axis (cylinder)
+  double r[FEAHIP_MAX_OBSTACLES];
+};
+struct ContactState {
+  bool set = false;                    // feahip_set_contact was called with faces and obstacles and not cleared since
+  int n = 0, nobs = 0;                 // contact nodes this context holds (a rank: those of the faces it kept); obstacles
+  double penalty = 0, gap_tolerance = 0;
+  int augment_max = 0;
+  int kind[FEAHIP_MAX_OBSTACLES] = {0};
+  double geom[FEAHIP_MAX_OBSTACLES][10] = {{0}};   // point, unit direction, radius, travel
+  std::vector<int> h_node;             // the contact nodes, ascending (library ids)
+  std::vector<double> h_w;             // their reference-area weights
+  int *d_node = nullptr;               // [n]
+  double *d_w = nullptr;               // [n]
+  double *d_mu = nullptr;              // [n][nobs] multipliers
+  double *d_part = nullptr;            // [4][FEA_RED_BLOCKS] per-workgroup partials of k_contact_info
+  void release() { dev_free({d_node, d_w, d_mu, d_part}); *this = ContactState(); }
+};
+
 // consistent mass and the kinematic state of the Newmark steps (kernels_mass.hip).  The parameters of the last
 // feahip_set_mass call stay on the host: m holds the block rows of the shard installed when it was assembled and is
 // assembled again (mass_ensure) when the shard has changed since.
@@ -618,6 +655,7 @@ struct feahip_ctx {
   // lambda to load_factor (one increment of the loads per step, as of the prescribed displacements)
   SurfaceLoads surf;
   double load_factor = 0;
+  ContactState contact;
   // two-column solve (kernels_solve2.hip), allocated on first use: paired vectors [3N][2] (the two columns interleaved
   // per dof), the second column's solution as a plain vector, and the columns' partial sums, scalars and flags
   double *d2_f = nullptr, *d2_u = nullptr, *d2_r = nullptr, *d2_p = nullptr, *d2_q = nullptr;
@@ -643,7 +681,8 @@ void with_kf(bool doK, bool doF, F &&f)
 }
 
 // launchers (kernels_assemble.hip / kernels_patch.hip / kernels_solve.hip)
-int launch_assemble(feahip_ctx *c, bool doK, bool doF);
+// plain: without the contact term (dist_stable_step, which puts its own bound of it on top)
+int launch_assemble(feahip_ctx *c, bool doK, bool doF, bool plain = false);
 int launch_state_export(feahip_ctx *c, double *d_grads = nullptr, double *d_detj = nullptr);
 int launch_apply_bc(feahip_ctx *c, double lambda);
 int launch_update_nodes_bc(feahip_ctx *c, double lambda);
@@ -654,6 +693,21 @@ int launch_surface_loads(feahip_ctx *c, double *d_fv);
 int resolve_surface_faces(int N, int E, int npe, const int *conn, int nfaces, int npf, const int *face_nodes,
                           int *face_elem, int *face_local, std::string &why);
 int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, const int *kind, const double *values);
+// kernels_surface.hip, host only: the caller's faces in the context's node ids and their elements' face order; a rank
+// keeps those touching a node it owns (keep = their indices in the caller's list).  FEAHIP_EINVAL and the reason in c->err
+int context_surface_faces(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, std::vector<int> &fn, std::vector<int> &keep);
+// kernels_contact.hip -- node-to-rigid-surface contact on the owned contact nodes (nothing to launch without contact)
+int set_contact(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, int n_obstacles, const int *kind,
+                const double *geom, double penalty, int augment_max, double gap_tolerance);
+void contact_owned(const feahip_ctx *c, int &n0, int &n1);      // the range of ContactState::h_node this rank owns
+int launch_contact(feahip_ctx *c, bool doK, bool doF, double *d_fv);   // d_fv += F_c; K's diagonal blocks += K_c
+int launch_contact_bound(feahip_ctx *c);                       // K's diagonal blocks += w eps n n' of EVERY pair (stable step)
+int launch_contact_augment(feahip_ctx *c);                     // mu <- max(0, mu + eps p)
+int launch_contact_info(feahip_ctx *c);                        // d_scal[8 .. 12) = active pairs, sum w t, Pi_c, max penetration (own rows)
+int launch_contact_status(feahip_ctx *c, double *d_gap, double *d_pressure);   // [N] each, written at the owned contact nodes
+// drivers.hip -- the four numbers over all ranks (out: active, max penetration, force, Pi_c); the multiplier update
+int dist_contact_info(std::vector<feahip_ctx *> &R, double *out);
+int dist_contact_augment(std::vector<feahip_ctx *> &R, double *max_penetration);
 int ensure_generic_maps(feahip_ctx *c);
 int ensure_k(feahip_ctx *c);
 void release_k(feahip_ctx *c);

@@ -288,6 +288,7 @@ template <int NPE, bool LINTET>
 static void launch_rowowner_t(feahip_ctx *c, const AsmArgs &A, bool doK, bool doF)
 {
   const int grid = (c->nchunks_local + FEA_WAVES_PER_WG - 1) / FEA_WAVES_PER_WG;
+  if (grid == 0) return;                             // a rank of a row-sharded run without rows of its own
   with_kf(doK, doF, [&](auto K, auto F) {
     if (c->n_materials) hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, K, F, true>), dim3(grid), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, A);
     else hipLaunchKernelGGL((k_assemble_rowowner<NPE, LINTET, K, F, false>), dim3(grid), dim3(64 * FEA_WAVES_PER_WG), 0, c->stream, A);
@@ -409,7 +410,7 @@ static int dispatch_assembly(feahip_ctx *c, int strat, bool doK, bool doF)
   return FEAHIP_OK;
 }
 
-int launch_assemble(feahip_ctx *c, bool doK, bool doF)
+int launch_assemble(feahip_ctx *c, bool doK, bool doF, bool plain)
 {
   if (const int rc = ensure_k(c)) return rc;
   const int strat = resolve_assembly(c, doK);
@@ -417,7 +418,9 @@ int launch_assemble(feahip_ctx *c, bool doK, bool doF)
   c->last_strategy = strat;                          // the kernel that runs, after the residual-only fallbacks
   int rc = dispatch_assembly(c, strat, doK, doF);
   if (!rc && doK) c->k_valid = true;
-  if (rc || !doF) return rc;
+  if (rc) return rc;
+  if (!plain && (rc = launch_contact(c, doK, doF, c->d_f))) return rc;   // K += K_c, f += F_c (nothing to launch without contact)
+  if (!doF) return rc;
   if ((rc = launch_surface_loads(c, c->d_f))) return rc;   // f = lambda F_ext - T (nothing to launch without loads)
   return launch_body_force(c, c->d_f);               // ... + lambda F_body (nothing to launch without a body force)
 }

@@ -37,17 +37,8 @@ static int face_node(int npe, int lf, int k)
   return npe == 4 ? kTet4Faces[lf][k] : (npe == 10 ? kTet10Faces[lf][k] : kHex8Faces[lf][k]);
 }
 
-// ---- quadrature of a face: points, weights (reference area included), N and dN/d(xi, eta) at the points
-#define FEA_SURF_MAX_PTS 6
-#define FEA_SURF_MAX_NPF 6
-struct FaceRule {
-  int npt;
-  double w[FEA_SURF_MAX_PTS];
-  double N[FEA_SURF_MAX_PTS][FEA_SURF_MAX_NPF];
-  double dN[FEA_SURF_MAX_PTS][2][FEA_SURF_MAX_NPF];
-};
-
-static void face_rule(int npf, FaceRule &R)
+// ---- quadrature of a face (FaceRule, feahip_internal.h): points, weights (reference area included), N and dN/d(xi, eta)
+void face_rule(int npf, FaceRule &R)
 {
   memset(&R, 0, sizeof(R));
   if (npf == 4) {                                              // quad4: 2 x 2 Gauss on [-1, 1]^2
@@ -289,18 +280,12 @@ int resolve_surface_faces(int N, int E, int npe, const int *conn, int nfaces, in
   return -1;
 }
 
-// the context's faces from the caller's: library ids in the element's face order, incidence lists, device copies
-int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, const int *kind, const double *values)
+// the caller's faces in this context's node ids, each in its element's face order (outward normal): library ids; on a
+// rank context, the faces touching an owned node, in local ids.  keep[i] = the caller's index of face i of fn.
+int context_surface_faces(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, std::vector<int> &fn, std::vector<int> &keep)
 {
-  if (nfaces < 0 || (nfaces > 0 && (!face_nodes || !kind || !values))) { c->err = "feahip_set_surface_loads: bad arrays"; return FEAHIP_EINVAL; }
-  for (int f = 0; f < nfaces; ++f)
-    if (kind[f] != FEAHIP_LOAD_PRESSURE && kind[f] != FEAHIP_LOAD_TRACTION) {
-      c->err = "surface face " + std::to_string(f) + ": unknown load kind " + std::to_string(kind[f]); return FEAHIP_EINVAL;
-    }
-  // the faces in this context's node ids: library ids; on a rank context, the faces touching an owned node, in local ids
   // (a feahip_create_rank_local context is handed local ids: nothing to look up, nothing sized by the whole mesh)
-  std::vector<int> fn, fk, keep;
-  std::vector<double> fv;
+  fn.clear(); keep.clear();
   if (nfaces > 0 && npf != nodes_per_face(c->npe)) {
     c->err = face_text(0, face_nodes, std::min(std::max(npf, 0), FEA_SURF_MAX_NPF)) + ": a face of a " + std::to_string(c->npe) +
              "-node element has " + std::to_string(nodes_per_face(c->npe)) + " nodes, not " + std::to_string(npf);
@@ -327,8 +312,6 @@ int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes,
     }
     if (!present || !owned) continue;      // a rank keeps the faces touching its nodes: their elements are all local
     fn.insert(fn.end(), mapped, mapped + npf);
-    fk.push_back(kind[f]);
-    fv.insert(fv.end(), values + (size_t)f * 3, values + (size_t)f * 3 + 3);
     keep.push_back(f);
   }
   const int nf = (int)keep.size();
@@ -351,6 +334,25 @@ int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes,
     }
     for (int f = 0; f < nf; ++f)                               // the element's order: outward normal
       for (int k = 0; k < npf; ++k) fn[(size_t)f * npf + k] = conn[(size_t)felem[f] * c->npe + face_node(c->npe, flocal[f], k)];
+  }
+  return FEAHIP_OK;
+}
+
+// the context's faces from the caller's: library ids in the element's face order, incidence lists, device copies
+int set_surface_loads(feahip_ctx *c, int nfaces, int npf, const int *face_nodes, const int *kind, const double *values)
+{
+  if (nfaces < 0 || (nfaces > 0 && (!face_nodes || !kind || !values))) { c->err = "feahip_set_surface_loads: bad arrays"; return FEAHIP_EINVAL; }
+  for (int f = 0; f < nfaces; ++f)
+    if (kind[f] != FEAHIP_LOAD_PRESSURE && kind[f] != FEAHIP_LOAD_TRACTION) {
+      c->err = "surface face " + std::to_string(f) + ": unknown load kind " + std::to_string(kind[f]); return FEAHIP_EINVAL;
+    }
+  std::vector<int> fn, fk, keep;
+  std::vector<double> fv;
+  if (const int rc = context_surface_faces(c, nfaces, npf, face_nodes, fn, keep)) return rc;
+  const int nf = (int)keep.size();
+  for (int f : keep) {
+    fk.push_back(kind[f]);
+    fv.insert(fv.end(), values + (size_t)f * 3, values + (size_t)f * 3 + 3);
   }
   // node -> (face, slot), nodes ascending, slots ascending inside a node
   std::vector<std::pair<int, int>> inc;

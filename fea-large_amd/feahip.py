@@ -108,6 +108,15 @@ ABI = {
     "feahip_host_numbering": [C.c_int, C.c_int, C.c_int, _ip, _dp, _ip],
     "feahip_set_surface_loads": [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp],
     "feahip_get_surface_forces": [C.c_void_p, _dp],
+    "feahip_set_contact": [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, _ip, _dp, C.c_double, C.c_int, C.c_double],
+    "feahip_get_contact_nodes": [C.c_void_p, _ip, _ip, _dp],
+    "feahip_get_contact_obstacles": [C.c_void_p, _ip],
+    "feahip_get_contact_multipliers": [C.c_void_p, _dp],
+    "feahip_set_contact_multipliers": [C.c_void_p, _dp],
+    "feahip_get_contact_forces": [C.c_void_p, _dp],
+    "feahip_get_contact_status": [C.c_void_p, _dp, _dp],
+    "feahip_contact_info": [C.c_void_p, _dp],
+    "feahip_contact_augment": [C.c_void_p, _dp],
     "feahip_set_load_factor": [C.c_void_p, C.c_double],
     "feahip_get_load_factor": [C.c_void_p, _dp],
     "feahip_set_materials": [C.c_void_p, C.c_int, _dp, _ip],
@@ -212,6 +221,9 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("contact_faces_count", C.c_int), ("contact_nodes_per_face", C.c_int), ("contact_nodes", _ip),
+        ("contact_obstacles_count", C.c_int), ("contact_kind", _ip), ("contact_geom", _dp),
+        ("contact_penalty", C.c_double), ("contact_augment", C.c_int), ("contact_gap_tolerance", C.c_double),
         ("buckling_modes", C.c_int), ("buckling_tolerance", C.c_double), ("buckling_max", C.c_int),
         ("modal_count", C.c_int), ("modal_shift", C.c_double),
         ("modal_modes", C.c_int), ("modal_tolerance", C.c_double), ("modal_max", C.c_int),
@@ -220,7 +232,7 @@ class FeaDeck(C.Structure):
 
 class StepSnapshot(C.Structure):
     """struct fea_step_snapshot of host/fea_host.h."""
-    _fields_ = [("nodes", _dp), ("stress0", _dp), ("nodal_stress", _dp), ("von_mises", _dp)]
+    _fields_ = [("nodes", _dp), ("stress0", _dp), ("nodal_stress", _dp), ("von_mises", _dp), ("contact_pressure", _dp)]
 
 
 def export_gmsh(path, deck, nodes_steps, stress0_steps, nodal_stress_steps=None, von_mises_steps=None):
@@ -333,6 +345,37 @@ def _take_dynamics(obj, kw):
         raise ValueError("dynamics and body_force need a density")
 
 
+OBSTACLE_PLANE, OBSTACLE_SPHERE, OBSTACLE_SPHERE_INSIDE, OBSTACLE_CYLINDER, OBSTACLE_CYLINDER_INSIDE = 0, 1, 2, 3, 4
+MAX_OBSTACLES = 8
+
+
+def obstacle_arrays(obstacles):
+    """(kind[n], geom[n][10]) of feahip_set_contact from a list of dicts (kind, point | center, normal | axis | direction,
+    radius, travel) or tuples (kind, point, direction, radius, travel)."""
+    kind, geom = [], []
+    for ob in obstacles:
+        if isinstance(ob, dict):
+            point = ob.get("point", ob.get("center", (0.0, 0.0, 0.0)))
+            direction = ob.get("normal", ob.get("axis", ob.get("direction", (0.0, 0.0, 0.0))))
+            ob = (ob["kind"], point, direction, ob.get("radius", 0.0), ob.get("travel", (0.0, 0.0, 0.0)))
+        k, point, direction, radius, travel = ob
+        kind.append(int(k))
+        geom.append([*np.asarray(point, dtype=np.float64), *np.asarray(direction, dtype=np.float64), float(radius),
+                     *np.asarray(travel, dtype=np.float64)])
+    return (np.ascontiguousarray(kind, dtype=np.int32),
+            np.ascontiguousarray(geom, dtype=np.float64).reshape(len(kind), 10))
+
+
+def _take_contact(self, kw):
+    """The contact fields of a Deck or a Slab (feahip_set_contact): faces as surface_faces, obstacles as set_contact."""
+    faces = np.asarray(kw.get("contact_faces", np.zeros((0, 0))), dtype=np.int32)
+    self.contact_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
+    self.contact_obstacles = list(kw.get("contact_obstacles", []))
+    self.contact_penalty = float(kw.get("contact_penalty", 0.0))
+    self.contact_augment = int(kw.get("contact_augment", 0))
+    self.contact_gap_tolerance = float(kw.get("contact_gap_tolerance", 0.0))
+
+
 class Deck:
     """A task deck as numpy arrays (fields named as the reference's structs)."""
 
@@ -362,6 +405,7 @@ class Deck:
         self.surface_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
         self.surface_kind = np.ascontiguousarray(kw.get("surface_kind", []), dtype=np.int32)
         self.surface_values = np.ascontiguousarray(kw.get("surface_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+        _take_contact(self, kw)
         # material table (feahip_set_materials): materials[n][2] = lambda, mu and one id per element; none = the single
         # pair `parameters`
         self.materials = np.ascontiguousarray(kw.get("materials", np.zeros((0, 2))), dtype=np.float64).reshape(-1, 2)
@@ -415,6 +459,9 @@ class Deck:
         try:
             n, e, npe, nb = fd.nodes_count, fd.elements_count, fd.nodes_per_element, fd.prescribed_nodes_count
             ns, npf, nm = fd.surface_faces_count, fd.surface_nodes_per_face, fd.materials_count
+            nc, ncf, no = fd.contact_faces_count, fd.contact_nodes_per_face, fd.contact_obstacles_count
+            ck = np.ctypeslib.as_array(fd.contact_kind, (no,)).copy() if no else []
+            cg = np.ctypeslib.as_array(fd.contact_geom, (no, 10)).copy() if no else []
             deck = Deck(
                 model=fd.model, parameters=[fd.parameters[0], fd.parameters[1]], solver_type=fd.solver_type,
                 solver_tolerance=fd.solver_tolerance, solver_max_iter=fd.solver_max_iter, ele_type=fd.ele_type,
@@ -439,6 +486,10 @@ class Deck:
                                  if fd.dynamics_explicit else {})) if fd.has_dynamics else None,
                 results=dict(nodal_stress=bool(fd.results_nodal_stress), energy=bool(fd.results_energy),
                              reactions=bool(fd.results_reactions)),
+                **(dict(contact_faces=np.ctypeslib.as_array(fd.contact_nodes, (nc, ncf)).copy(),
+                        contact_obstacles=[(int(k), g[0:3], g[3:6], float(g[6]), g[7:10]) for k, g in zip(ck, cg)],
+                        contact_penalty=fd.contact_penalty, contact_augment=fd.contact_augment,
+                        contact_gap_tolerance=fd.contact_gap_tolerance) if nc and no else {}),
                 **(dict(modal_modes=fd.modal_modes, modal_count=fd.modal_count, modal_shift=fd.modal_shift,
                         modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
                    if fd.modal_modes or fd.modal_count else {}),
@@ -492,6 +543,14 @@ class Deck:
         fd.modal_modes = int(getattr(self, "modal_modes", 0))
         fd.modal_count, fd.modal_shift = int(getattr(self, "modal_count", 0)), float(getattr(self, "modal_shift", 0.0))
         fd.modal_tolerance, fd.modal_max = float(getattr(self, "modal_tolerance", 1e-8)), int(getattr(self, "modal_max", 1000))
+        if len(self.contact_faces) and len(self.contact_obstacles):
+            # (kept on the deck: the struct borrows the arrays)
+            self._contact_kind, self._contact_geom = obstacle_arrays(self.contact_obstacles)
+            fd.contact_faces_count, fd.contact_nodes_per_face = self.contact_faces.shape
+            fd.contact_nodes, fd.contact_obstacles_count = _i(self.contact_faces), len(self._contact_kind)
+            fd.contact_kind, fd.contact_geom = _i(self._contact_kind), _d(self._contact_geom)
+            fd.contact_penalty, fd.contact_augment = self.contact_penalty, self.contact_augment
+            fd.contact_gap_tolerance = self.contact_gap_tolerance
         fd.buckling_modes = int(getattr(self, "buckling_modes", 0))
         fd.buckling_tolerance = float(getattr(self, "buckling_tolerance", 1e-8))
         fd.buckling_max = int(getattr(self, "buckling_max", 2000))
@@ -528,6 +587,7 @@ class FeaSolver:
             self._ctx = C.c_void_p()
             raise FeaHipError(f"feahip_create failed ({rc}): {self._lib.feahip_create_error().decode()}")
         self._deck_surface_loads()
+        self._deck_contact()
         self._deck_materials()
         self._deck_mass()
 
@@ -568,6 +628,12 @@ class FeaSolver:
         if len(getattr(self.deck, "surface_kind", [])):
             d = self.deck
             self.set_surface_loads(d.surface_faces, d.surface_kind, d.surface_values)
+
+    def _deck_contact(self):
+        d = self.deck
+        if len(getattr(d, "contact_obstacles", [])) and (len(d.contact_faces) or isinstance(d, Slab)):
+            # (a slab without a contact face of its own still takes the obstacles: its rank joins the collectives)
+            self.set_contact(d.contact_faces, d.contact_obstacles, d.contact_penalty, d.contact_augment, d.contact_gap_tolerance)
 
     def close(self):
         if self._ctx:
@@ -956,6 +1022,71 @@ class FeaSolver:
         f = np.zeros(self.ndof)
         self._chk(self._lib.feahip_get_surface_forces(self._ctx, _d(f)))
         return f
+
+    # ---- contact with rigid obstacles ---------------------------------------
+    def set_contact(self, faces, obstacles, penalty, augment_max=0, gap_tolerance=0.0):
+        """feahip_set_contact: faces[F][nodes per face] as set_surface_loads takes them; obstacles a list of dicts
+        (kind, point | center, normal | axis | direction, radius, travel) or tuples (kind, point, direction, radius,
+        travel).  No faces or no obstacles clears the contact."""
+        faces = np.asarray(faces, dtype=np.int32)
+        n = len(faces) if faces.size else 0
+        faces = np.ascontiguousarray(faces.reshape(n, -1)) if n else np.zeros((0, 1), dtype=np.int32)
+        kind, geom = obstacle_arrays(obstacles)
+        self._chk(self._lib.feahip_set_contact(self._ctx, n, faces.shape[1] if n else 0, _i(faces), len(kind), _i(kind), _d(geom),
+                                               float(penalty), int(augment_max), float(gap_tolerance)))
+
+    def contact_nodes(self):
+        """(nodes[n] ascending in this solver's node ids, weights[n]) of the contact nodes the context owns."""
+        n = C.c_int(0)
+        self._chk(self._lib.feahip_get_contact_nodes(self._ctx, C.byref(n), None, None))
+        nodes, w = np.zeros(n.value, dtype=np.int32), np.zeros(n.value)
+        if n.value:
+            self._chk(self._lib.feahip_get_contact_nodes(self._ctx, C.byref(n), _i(nodes), _d(w)))
+        return nodes, w
+
+    def contact_obstacles(self):
+        """feahip_get_contact_obstacles: the obstacles of the contact in force (0 without one)."""
+        n = C.c_int(0)
+        self._chk(self._lib.feahip_get_contact_obstacles(self._ctx, C.byref(n)))
+        return n.value
+
+    def contact_multipliers(self):
+        """mu[n][obstacles] in the node order of contact_nodes()."""
+        n = len(self.contact_nodes()[0])
+        mu = np.zeros((n, self.contact_obstacles()))
+        if mu.size:
+            self._chk(self._lib.feahip_get_contact_multipliers(self._ctx, _d(mu)))
+        return mu
+
+    def set_contact_multipliers(self, mu):
+        n = len(self.contact_nodes()[0])
+        mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(n, self.contact_obstacles())
+        if mu.size:
+            self._chk(self._lib.feahip_set_contact_multipliers(self._ctx, _d(mu)))
+
+    def contact_forces(self):
+        """F_c at the current nodes, [3N] in the caller's dof order."""
+        f = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_get_contact_forces(self._ctx, _d(f)))
+        return f
+
+    def contact_status(self):
+        """(gap[N]: the smallest over the obstacles, +inf away from the contact nodes; pressure[N]: the summed t)."""
+        gap, t = np.zeros(self.N), np.zeros(self.N)
+        self._chk(self._lib.feahip_get_contact_status(self._ctx, _d(gap), _d(t)))
+        return gap, t
+
+    def contact_info(self):
+        """feahip_contact_info (collective on a group): dict(active, max_penetration, force, potential)."""
+        o = np.zeros(4)
+        self._chk(self._lib.feahip_contact_info(self._ctx, _d(o)))
+        return {"active": int(o[0]), "max_penetration": o[1], "force": o[2], "potential": o[3]}
+
+    def contact_augment(self):
+        """feahip_contact_augment (collective on a group): the largest penetration before the multiplier update."""
+        p = C.c_double(0)
+        self._chk(self._lib.feahip_contact_augment(self._ctx, C.byref(p)))
+        return p.value
 
     def load_factor(self):
         v = C.c_double(0)
@@ -1368,6 +1499,7 @@ class RankSolver(FeaSolver):
         self.elem_global = np.empty(self.E, dtype=np.int32)
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
         self._deck_surface_loads()                              # the whole face list: the rank keeps what touches its nodes
+        self._deck_contact()                                    # the same rule
         self._deck_materials()                                  # the whole mesh's ids: the rank keeps its own elements'
         self._deck_mass()
 
@@ -1449,6 +1581,7 @@ class Slab:
         self.surface_faces = np.ascontiguousarray(faces.reshape(len(faces), -1) if faces.size else np.zeros((0, 0), dtype=np.int32))
         self.surface_kind = np.ascontiguousarray(kw.get("surface_kind", []), dtype=np.int32)
         self.surface_values = np.ascontiguousarray(kw.get("surface_values", np.zeros((0, 3))), dtype=np.float64).reshape(-1, 3)
+        _take_contact(self, kw)
         # material table (feahip_set_materials): materials[n][2] = lambda, mu and one id per element; none = the single
         # pair `parameters`
         self.materials = np.ascontiguousarray(kw.get("materials", np.zeros((0, 2))), dtype=np.float64).reshape(-1, 2)
@@ -1472,6 +1605,8 @@ class Slab:
         out.presc_node = np.ascontiguousarray(new[self.presc_node]) if len(self.presc_node) else self.presc_node
         if len(self.surface_kind):
             out.surface_faces = np.ascontiguousarray(new[self.surface_faces])
+        if len(self.contact_faces):
+            out.contact_faces = np.ascontiguousarray(new[self.contact_faces])
         return out
 
     def reordered(self):
@@ -1514,6 +1649,7 @@ class LocalRankSolver(FeaSolver):
         self.elem_global = np.empty(self.E, dtype=np.int32)
         self._chk(self._lib.feahip_rank_maps(self._ctx, _i(self.node_global), _i(self.elem_global)))
         self._deck_surface_loads()                              # local ids; faces of other ranks' nodes are dropped
+        self._deck_contact()
         self._deck_materials()                                  # the slab's own ids, in its element order
         self._deck_mass()
 
@@ -1560,6 +1696,11 @@ def slab_of(deck, rank, nranks):
         fl = local_of[deck.surface_faces]
         fk = np.all(fl >= 0, axis=1)                            # all of its nodes are local (the library drops other ranks')
         kw.update(surface_faces=fl[fk], surface_kind=deck.surface_kind[fk], surface_values=deck.surface_values[fk])
+    if len(getattr(deck, "contact_faces", [])) and len(deck.contact_obstacles):
+        fl = local_of[deck.contact_faces]
+        kw.update(contact_faces=fl[np.all(fl >= 0, axis=1)], contact_obstacles=deck.contact_obstacles,
+                  contact_penalty=deck.contact_penalty, contact_augment=deck.contact_augment,
+                  contact_gap_tolerance=deck.contact_gap_tolerance)
     if len(getattr(deck, "materials", [])):
         kw.update(materials=deck.materials, element_material=deck.element_material[eg])
     slab = Slab(nodes=deck.nodes[ng], elements=local_of[deck.elements[eg]], node_global=ng, elem_global=eg, n_own=no,
@@ -1690,6 +1831,12 @@ class FeaGroup:
 
     def strain_energy(self):
         return self.ranks[0].strain_energy()                    # one call drives the group
+
+    def contact_info(self):
+        return self.ranks[0].contact_info()
+
+    def contact_augment(self):
+        return self.ranks[0].contact_augment()
 
     # ---- modal analysis over the ranks -------------------------------------
     def solve_modes(self, n_modes, tolerance=1e-8, max_iterations=1000, warm=False, check=True):

@@ -25,7 +25,8 @@ void fea_snapshots_free(fea_step_snapshot *steps, int n)
   if (!steps) return;
   for (i = 0; i < n; ++i) {
     free(steps[i].nodes); free(steps[i].stress0); free(steps[i].nodal_stress); free(steps[i].von_mises);
-    steps[i].nodes = steps[i].stress0 = steps[i].nodal_stress = steps[i].von_mises = NULL;
+    free(steps[i].contact_pressure);
+    steps[i].nodes = steps[i].stress0 = steps[i].nodal_stress = steps[i].von_mises = steps[i].contact_pressure = NULL;
   }
 }
 
@@ -53,6 +54,11 @@ static int keep_snapshot(const fea_deck *d, feahip_ctx *ctx, int step, void *use
     k->steps[step].von_mises = (double *)malloc(sizeof(double) * (size_t)d->nodes_count);
     if (!k->steps[step].nodal_stress || !k->steps[step].von_mises) return FEAHIP_ENOMEM;
     if ((rc = feahip_get_nodal_stresses(ctx, -1, k->steps[step].nodal_stress, k->steps[step].von_mises, NULL))) return rc;
+  }
+  if (d->contact_faces_count > 0 && d->contact_obstacles_count > 0) {
+    k->steps[step].contact_pressure = (double *)malloc(sizeof(double) * (size_t)d->nodes_count);
+    if (!k->steps[step].contact_pressure) return FEAHIP_ENOMEM;
+    if ((rc = feahip_get_contact_status(ctx, NULL, k->steps[step].contact_pressure))) return rc;
   }
   return 0;
 }
@@ -289,6 +295,12 @@ int fea_export_gmsh(const char *filename, const fea_deck *d, const fea_step_snap
       fprintf(f, "$EndNodeData\n");
       fprintf(f, "$NodeData\n1\n\"Von Mises\"\n1\n%f\n3\n%d\n1\n%d\n", load * 0.83333333, load, d->nodes_count);
       for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %f\n", i + 1, vm[i]);
+      fprintf(f, "$EndNodeData\n");
+    }
+    if (load && steps[load - 1].contact_pressure) {                            /* a deck with (contact ...) */
+      const double *t = steps[load - 1].contact_pressure;
+      fprintf(f, "$NodeData\n1\n\"Contact pressure\"\n1\n%f\n3\n%d\n1\n%d\n", load * 0.83333333, load, d->nodes_count);
+      for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %f\n", i + 1, t[i]);
       fprintf(f, "$EndNodeData\n");
     }
   }

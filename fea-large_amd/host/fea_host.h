@@ -91,6 +91,24 @@ typedef struct fea_deck {
    * to the .msh file; :energy and :reactions add one log line each per finished step.  Written by fea_deck_save only
    * when one of them is set; without the section the file and the log are what they were                        */
   int results_nodal_stress, results_energy, results_reactions;
+  /* contact with rigid obstacles, optional: (contact :penalty e :augment k :gap-tolerance g (faces (n ...) ...)
+   * (plane :point (x y z) :normal (x y z) :travel (x y z)) (sphere :center (..) :radius r :travel (..) :inside t)
+   * (cylinder :point (..) :axis (..) :radius r :travel (..) :inside t) ...) inside (boundary-conditions ...), beside
+   * (surface-loads ...): the faces and obstacles of feahip_set_contact, up to FEAHIP_MAX_OBSTACLES of them in deck order
+   * (:augment 0, :gap-tolerance 0, :travel (0 0 0) and :inside nil where absent).  With :augment k > 0 fea_solve_steps
+   * follows every converged increment by up to k multiplier updates (feahip_contact_augment), each with its own Newton
+   * iterations; every finished step logs "Contact: active n, force F, max penetration p" and the .msh file gets one
+   * $NodeData "Contact pressure" section per step.  Written by fea_deck_save only when there are faces and obstacles: a
+   * deck without the section is read, run and written as before                                                  */
+  int contact_faces_count;
+  int contact_nodes_per_face;
+  int *contact_nodes;           /* [count][nodes_per_face]                   */
+  int contact_obstacles_count;
+  int *contact_kind;            /* [count] FEAHIP_OBSTACLE_*                 */
+  double *contact_geom;         /* [count][10]: point, direction, radius, travel */
+  double contact_penalty;
+  int contact_augment;
+  double contact_gap_tolerance;
   /* linear buckling, optional: (buckling :modes N :tolerance t :max M) inside (solution ...), N in [1, 8] (:tolerance
    * 1e-8 and :max 2000 where absent).  After its last step -- and after the modal run of a deck that has both --
    * feasolver_hip calls feahip_solve_buckling at the state reached, logs one line per mode and appends one $NodeData
@@ -163,6 +181,8 @@ typedef struct fea_step_snapshot {
   /* (results :nodal-stress t) only, NULL otherwise: feahip_get_nodal_stresses of all elements */
   double *nodal_stress;   /* [nodes_count][6] xx yy zz xy yz xz */
   double *von_mises;      /* [nodes_count] */
+  /* a deck with (contact ...) only, NULL otherwise: the summed contact pressure of feahip_get_contact_status */
+  double *contact_pressure;   /* [nodes_count] */
 } fea_step_snapshot;
 
 /* fea_solve with snapshots for the exporter: steps[cap] are allocated by the

@@ -54,6 +54,15 @@ int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char
     *ctx = NULL;
     return rc;
   }
+  if (d->contact_faces_count > 0 && d->contact_obstacles_count > 0 &&
+      (rc = feahip_set_contact(*ctx, d->contact_faces_count, d->contact_nodes_per_face, d->contact_nodes,
+                               d->contact_obstacles_count, d->contact_kind, d->contact_geom, d->contact_penalty,
+                               d->contact_augment, d->contact_gap_tolerance))) {
+    if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
+    feahip_destroy(*ctx);
+    *ctx = NULL;
+    return rc;
+  }
   if (d->materials_count > 0 &&
       (rc = feahip_set_materials(*ctx, d->materials_count, d->material_params, d->element_material))) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", feahip_last_error(*ctx));
@@ -97,40 +106,65 @@ int fea_log_results(const fea_deck *d, feahip_ctx *ctx, void *logp, int explicit
 
 #define CALL(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
+/* One pass of Newton iterations at the nodes and the load in force (fea_solver.c:177-221): K, its stash, then
+ * iterations until the energy passes or max_newton_count of them are spent (*failed).  A load increment is one pass; a
+ * deck with (contact ... :augment k) adds one per multiplier update.  *it counts the iterations of all passes. */
+static int newton_pass(const fea_deck *d, feahip_ctx *ctx, FILE *log, int *it, int *failed)
+{
+  int k = 0;
+  double tolerance;
+  CALL(feahip_create_stiffness(ctx));                                        /* :177 */
+  CALL(feahip_stash_stiffness(ctx));                                         /* :179 */
+  do {
+    (*it)++; k++;
+    CALL(feahip_create_residual_forces(ctx));                                /* :185 */
+    if (d->modified_newton) CALL(feahip_restore_stiffness(ctx));             /* :194-195 */
+    else CALL(feahip_create_stiffness(ctx));                                 /* :200 */
+    CALL(feahip_apply_prescribed_bc(ctx, 0));                                /* :203 */
+    CALL(feahip_solve_slae(ctx, d->solver_type, d->solver_tolerance,         /* :205 */
+                           d->solver_max_iter, NULL, NULL));
+    CALL(feahip_energy(ctx, &tolerance));                                    /* :208-210 */
+    if (log) {
+      fprintf(log, "Tolerance <X,R> = %e\n", tolerance);                     /* :212 */
+      fprintf(log, "Newton iteration %d finished\n", *it);                   /* :213 */
+    }
+    CALL(feahip_update_nodes_with_solution(ctx, NULL));                      /* :216 */
+    CALL(feahip_update_state(ctx, NULL));                                    /* :217-218 */
+  } while (fabs(tolerance) > d->desired_tolerance && k < d->max_newton_count);   /* :220-221 */
+  *failed = k == d->max_newton_count;
+  return 0;
+}
+
 /* solve() of fea_solver.c:163-236: THE load-increment / Newton loop of the host side (fea_solve and
  * fea_solve_with_snapshots are this loop with two different things done after a converged increment, :233-235).
  * Returns the number of finished increments, or a negative FEAHIP_* code. */
 int fea_solve_steps(const fea_deck *d, feahip_ctx *ctx, void *logp, fea_step_fn after_step, void *user)
 {
   FILE *log = (FILE *)logp;
-  int step, it;
-  double tolerance;
+  const int contact = d->contact_faces_count > 0 && d->contact_obstacles_count > 0;
+  int step, it, failed, aug;
+  double info[4] = {0, 0, 0, 0};
   for (step = 0; step < d->load_increments_count; ++step) {                 /* :163 */
     it = 0;
     CALL(feahip_update_nodes_with_bc(ctx, 1));                               /* :168 */
     CALL(feahip_update_state(ctx, NULL));                                    /* :171-174 */
-    CALL(feahip_create_stiffness(ctx));                                      /* :177 */
-    CALL(feahip_stash_stiffness(ctx));                                       /* :179 */
-    do {
-      it++;
-      CALL(feahip_create_residual_forces(ctx));                              /* :185 */
-      if (d->modified_newton) CALL(feahip_restore_stiffness(ctx));           /* :194-195 */
-      else CALL(feahip_create_stiffness(ctx));                               /* :200 */
-      CALL(feahip_apply_prescribed_bc(ctx, 0));                              /* :203 */
-      CALL(feahip_solve_slae(ctx, d->solver_type, d->solver_tolerance,       /* :205 */
-                             d->solver_max_iter, NULL, NULL));
-      CALL(feahip_energy(ctx, &tolerance));                                  /* :208-210 */
-      if (log) {
-        fprintf(log, "Tolerance <X,R> = %e\n", tolerance);                   /* :212 */
-        fprintf(log, "Newton iteration %d finished\n", it);                  /* :213 */
-      }
-      CALL(feahip_update_nodes_with_solution(ctx, NULL));                    /* :216 */
-      CALL(feahip_update_state(ctx, NULL));                                  /* :217-218 */
-    } while (fabs(tolerance) > d->desired_tolerance && it < d->max_newton_count);   /* :220-221 */
+    CALL(newton_pass(d, ctx, log, &it, &failed));
+    /* (contact ... :augment k): while the largest penetration exceeds :gap-tolerance, update the multipliers and iterate
+     * again at the same load */
+    if (contact && !failed) CALL(feahip_contact_info(ctx, info));            /* one reduction per pass: decision and log line */
+    for (aug = 0; contact && !failed && aug < d->contact_augment && info[1] > d->contact_gap_tolerance; ++aug) {
+      if (log) fprintf(log, "Contact augmentation %d: max penetration %.17g\n", aug + 1, info[1]);
+      CALL(feahip_contact_augment(ctx, NULL));
+      CALL(newton_pass(d, ctx, log, &it, &failed));
+      if (!failed) CALL(feahip_contact_info(ctx, info));
+    }
     if (log) fprintf(log, "Load increment %d finished\n", step + 1);         /* :224 */
-    if (it == d->max_newton_count) {                                         /* :225-231 */
+    if (failed) {                                                            /* :225-231 */
       if (log) fprintf(log, "Unable to finish load step in %d Newton iterations,exit\n", d->max_newton_count);
       break;
+    }
+    if (contact && log) {
+      fprintf(log, "Contact: active %d, force %.17g, max penetration %.17g\n", (int)info[0], info[2], info[1]);
     }
     CALL(fea_log_results(d, ctx, log, 0));                                   /* (results ...): nothing without the section */
     if (after_step) CALL(after_step(d, ctx, step, user));                    /* :233-235 */

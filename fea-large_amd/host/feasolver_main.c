@@ -16,7 +16,12 @@
  * then gets its N lowest natural frequencies at the final state in the log
  * and the mode shapes in the file (feahip_solve_modes).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
- * log and their mode shapes in the file (feahip_solve_buckling).
+ * log and their mode shapes in the file (feahip_solve_buckling).  A deck
+ * with a (contact ...) section presses its contact faces against rigid
+ * obstacles in every loop above but the arc length (feahip_set_contact); the
+ * reference's loop then adds the multiplier updates of :augment, one
+ * "Contact: active n, force F, max penetration p" line per step and one
+ * "Contact pressure" section per step in the file.
  *
  * One option the reference does not have, after the deck name:
  *   --multigrid   PCG_ILU / CHOLESKY solves use the aggregation-multigrid

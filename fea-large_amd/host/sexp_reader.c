@@ -312,6 +312,135 @@ static int read_surface(reader *r, fea_deck *d)
   return 0;
 }
 
+/* (x y z) whose '(' has not been consumed */
+static int read_vec3(reader *r, double *v, const char *what)
+{
+  char buf[TOK_MAX], m[96], *end;
+  int k;
+  snprintf(m, sizeof m, "contact: %s must be a list of three numbers", what);
+  if (next_token(r, buf) != T_OPEN) return fail(r, m);
+  for (k = 0; k < 3; ++k) {
+    if (next_token(r, buf) != T_ATOM) return fail(r, m);
+    v[k] = strtod(buf, &end);
+    if (end == buf || *end) return fail(r, m);
+  }
+  if (next_token(r, buf) != T_CLOSE) return fail(r, m);
+  return 0;
+}
+
+/* (contact :penalty e :augment k :gap-tolerance g (faces (n ...) ...) (plane :point (..) :normal (..) :travel (..))
+ * (sphere :center (..) :radius r :travel (..) :inside t) (cylinder :point (..) :axis (..) :radius r :travel (..) :inside t)
+ * ...) inside (boundary-conditions ...): the faces and obstacles of feahip_set_contact, obstacles in deck order.  No
+ * counterpart in the reference.  Whether the nodes form boundary faces is checked by feahip_set_contact; what can be
+ * told from the text alone is refused here. */
+static int read_contact(reader *r, fea_deck *d)
+{
+  char buf[TOK_MAX], key[48], *end;
+  int nobs = 0, npf = 0, nfaces = 0, rc = 0, have_penalty = 0, have_faces = 0, t;
+  size_t cap = 64;
+  int *nodes = (int *)malloc(cap * 8 * sizeof(int));
+  int *kind = (int *)malloc(FEAHIP_MAX_OBSTACLES * sizeof(int));
+  double *geom = (double *)calloc(FEAHIP_MAX_OBSTACLES * 10, sizeof(double));
+  double penalty = 0, gap = 0, augment = 0;
+  if (!nodes || !kind || !geom) { free(nodes); free(kind); free(geom); return fail(r, "out of memory reading (contact ...)"); }
+  while (!rc) {
+    t = next_token(r, buf);
+    if (t == T_CLOSE) break;
+    if (t == T_EOF) { rc = fail(r, "unexpected end of file"); break; }
+    if (t == T_ATOM) {                                         /* :penalty :augment :gap-tolerance */
+      double v;
+      if (buf[0] != ':') { rc = fail(r, "contact: expected :key value or a list"); break; }
+      snprintf(key, sizeof key, "%s", buf + 1);
+      if (next_token(r, buf) != T_ATOM) { rc = fail(r, "attribute without a value"); break; }
+      v = strtod(buf, &end);
+      if (end == buf || *end) { rc = fail(r, "contact: attribute is not a number"); break; }
+      if (ieq(key, "penalty")) { penalty = v; have_penalty = 1; }
+      else if (ieq(key, "augment")) augment = v;
+      else if (ieq(key, "gap-tolerance")) gap = v;
+      else { rc = fail(r, "contact: unknown attribute (:penalty :augment :gap-tolerance)"); break; }
+      continue;
+    }
+    if (next_token(r, buf) != T_ATOM) { rc = fail(r, "contact: expected (faces ...), (plane ...), (sphere ...) or (cylinder ...)"); break; }
+    if (ieq(buf, "faces")) {
+      if (have_faces) { rc = fail(r, "contact: more than one (faces ...)"); break; }
+      have_faces = 1;
+      while (!rc && (t = next_token(r, buf)) == T_OPEN) {
+        int k, ids[8];
+        for (k = 0; (t = next_token(r, buf)) == T_ATOM; ++k) {
+          if (k == 6) { rc = fail(r, "a face has at most 6 nodes"); break; }
+          ids[k] = (int)strtol(buf, &end, 10);
+          if (end == buf || *end) { rc = fail(r, "bad node id in a contact face"); break; }
+        }
+        if (rc) break;
+        if (t != T_CLOSE || k == 0) { rc = fail(r, "a contact face must be a list of node ids"); break; }
+        if (nfaces == 0) npf = k;
+        else if (k != npf) { rc = fail(r, "every contact face must have the same number of nodes"); break; }
+        if ((size_t)nfaces == cap) {
+          int *q = (int *)realloc(nodes, 2 * cap * 8 * sizeof(int));
+          if (!q) { rc = fail(r, "out of memory reading (contact ...)"); break; }
+          nodes = q; cap *= 2;
+        }
+        memcpy(nodes + (size_t)nfaces * 8, ids, sizeof(int) * (size_t)k);
+        nfaces++;
+      }
+      if (!rc && t != T_CLOSE) rc = fail(r, "(faces ...) must be a list of faces");
+      continue;
+    }
+    {
+      const int plane = ieq(buf, "plane"), sphere = ieq(buf, "sphere"), cylinder = ieq(buf, "cylinder");
+      int inside = 0, have_point = 0, have_dir = 0, have_radius = 0;
+      double *g;
+      if (!plane && !sphere && !cylinder) { rc = fail(r, "contact: expected (faces ...), (plane ...), (sphere ...) or (cylinder ...)"); break; }
+      if (nobs == FEAHIP_MAX_OBSTACLES) { rc = fail(r, "contact: more than 8 obstacles"); break; }
+      g = geom + (size_t)nobs * 10;
+      while (!rc) {
+        t = next_token(r, buf);
+        if (t == T_CLOSE) break;
+        if (t != T_ATOM || buf[0] != ':') { rc = fail(r, "contact obstacle: expected :key value"); break; }
+        snprintf(key, sizeof key, "%s", buf + 1);
+        if (ieq(key, plane ? "point" : sphere ? "center" : "point")) { rc = read_vec3(r, g, key); have_point = 1; }
+        else if (!sphere && ieq(key, plane ? "normal" : "axis")) { rc = read_vec3(r, g + 3, key); have_dir = 1; }
+        else if (ieq(key, "travel")) rc = read_vec3(r, g + 7, key);
+        else if (!plane && ieq(key, "radius")) {
+          if (next_token(r, buf) != T_ATOM) { rc = fail(r, "attribute without a value"); break; }
+          g[6] = strtod(buf, &end);
+          if (end == buf || *end) { rc = fail(r, "contact: :radius is not a number"); break; }
+          have_radius = 1;
+        } else if (!plane && ieq(key, "inside")) {
+          if (next_token(r, buf) != T_ATOM || !(ieq(buf, "t") || ieq(buf, "nil"))) { rc = fail(r, "contact: :inside must be t or nil"); break; }
+          inside = ieq(buf, "t");
+        } else rc = fail(r, plane ? "plane: unknown attribute (:point :normal :travel)"
+                          : sphere ? "sphere: unknown attribute (:center :radius :travel :inside)"
+                                   : "cylinder: unknown attribute (:point :axis :radius :travel :inside)");
+      }
+      if (rc) break;
+      if (!have_point) { rc = fail(r, plane ? "plane needs :point" : sphere ? "sphere needs :center" : "cylinder needs :point"); break; }
+      if (!sphere && !have_dir) { rc = fail(r, plane ? "plane needs :normal" : "cylinder needs :axis"); break; }
+      if (!sphere && g[3] == 0 && g[4] == 0 && g[5] == 0) { rc = fail(r, plane ? "plane :normal is zero" : "cylinder :axis is zero"); break; }
+      if (!plane && !have_radius) { rc = fail(r, sphere ? "sphere needs :radius" : "cylinder needs :radius"); break; }
+      if (!plane && !(g[6] > 0)) { rc = fail(r, "contact: :radius must be positive"); break; }
+      kind[nobs++] = plane ? FEAHIP_OBSTACLE_PLANE : sphere ? (inside ? FEAHIP_OBSTACLE_SPHERE_INSIDE : FEAHIP_OBSTACLE_SPHERE)
+                                                           : (inside ? FEAHIP_OBSTACLE_CYLINDER_INSIDE : FEAHIP_OBSTACLE_CYLINDER);
+    }
+  }
+  if (!rc && !have_penalty) rc = fail(r, "contact needs :penalty");
+  if (!rc && !(penalty > 0)) rc = fail(r, "contact :penalty must be positive");
+  if (!rc && (!(augment >= 0 && augment <= 2147483647.0) || augment != (double)(int)augment)) rc = fail(r, "contact :augment must be a non-negative integer");
+  if (!rc && !(gap >= 0)) rc = fail(r, "contact :gap-tolerance must not be negative");
+  if (!rc && nfaces == 0) rc = fail(r, "contact without (faces ...)");
+  if (!rc && nobs == 0) rc = fail(r, "contact without an obstacle");
+  if (rc) { free(nodes); free(kind); free(geom); return rc; }
+  {
+    int i;
+    for (i = 0; i < nfaces; ++i) memmove(nodes + (size_t)i * npf, nodes + (size_t)i * 8, sizeof(int) * (size_t)npf);   /* pack */
+  }
+  free(d->contact_nodes); free(d->contact_kind); free(d->contact_geom);
+  d->contact_nodes = nodes; d->contact_kind = kind; d->contact_geom = geom;
+  d->contact_faces_count = nfaces; d->contact_nodes_per_face = npf; d->contact_obstacles_count = nobs;
+  d->contact_penalty = penalty; d->contact_augment = (int)augment; d->contact_gap_tolerance = gap;
+  return 0;
+}
+
 /* (materials (material :lambda l :mu m) ...) inside (model ...): the table of feahip_set_materials */
 static int read_materials(reader *r, fea_deck *d)
 {
@@ -383,6 +512,7 @@ static int read_list(reader *r, fea_deck *d)
   if (ieq(head, "elements")) return read_elements(r, d);
   if (ieq(head, "prescribed-displacements")) return read_prescribed(r, d);
   if (ieq(head, "surface-loads")) return read_surface(r, d);
+  if (ieq(head, "contact")) return read_contact(r, d);
   if (ieq(head, "materials")) return read_materials(r, d);
   if (ieq(head, "element-materials")) return read_element_materials(r, d, &r->n_element_material);
 
@@ -604,6 +734,9 @@ void fea_deck_free(fea_deck *d)
   free(d->nodes); free(d->elements);
   free(d->presc_node); free(d->presc_type); free(d->presc_values);
   free(d->surface_nodes); free(d->surface_kind); free(d->surface_values);
+  free(d->contact_nodes); free(d->contact_kind); free(d->contact_geom);
+  d->contact_nodes = d->contact_kind = NULL; d->contact_geom = NULL;
+  d->contact_faces_count = d->contact_obstacles_count = 0;
   free(d->material_params); free(d->element_material);
   d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
@@ -684,6 +817,33 @@ int fea_deck_save(const char *path, const fea_deck *d)
       for (k = 0; k < d->surface_nodes_per_face; ++k)
         fprintf(f, k ? " %d" : "%d", d->surface_nodes[(size_t)i * d->surface_nodes_per_face + k]);
       fprintf(f, "))");
+    }
+    fprintf(f, ")");
+  }
+  if (d->contact_faces_count > 0 && d->contact_obstacles_count > 0) {   /* written only when there is contact */
+    fprintf(f, "\n   (contact :penalty %.17g :augment %d :gap-tolerance %.17g\n    (faces", d->contact_penalty, d->contact_augment,
+            d->contact_gap_tolerance);
+    for (i = 0; i < d->contact_faces_count; ++i) {
+      fprintf(f, "\n     (");
+      for (k = 0; k < d->contact_nodes_per_face; ++k)
+        fprintf(f, k ? " %d" : "%d", d->contact_nodes[(size_t)i * d->contact_nodes_per_face + k]);
+      fprintf(f, ")");
+    }
+    fprintf(f, ")");
+    for (i = 0; i < d->contact_obstacles_count; ++i) {
+      const double *g = d->contact_geom + 10 * (size_t)i;
+      const int kd = d->contact_kind[i];
+      const int inside = kd == FEAHIP_OBSTACLE_SPHERE_INSIDE || kd == FEAHIP_OBSTACLE_CYLINDER_INSIDE;
+      if (kd == FEAHIP_OBSTACLE_PLANE)
+        fprintf(f, "\n    (plane :point (%.17g %.17g %.17g) :normal (%.17g %.17g %.17g)", g[0], g[1], g[2], g[3], g[4], g[5]);
+      else if (kd == FEAHIP_OBSTACLE_SPHERE || kd == FEAHIP_OBSTACLE_SPHERE_INSIDE)
+        fprintf(f, "\n    (sphere :center (%.17g %.17g %.17g) :radius %.17g", g[0], g[1], g[2], g[6]);
+      else
+        fprintf(f, "\n    (cylinder :point (%.17g %.17g %.17g) :axis (%.17g %.17g %.17g) :radius %.17g", g[0], g[1], g[2], g[3], g[4],
+                g[5], g[6]);
+      fprintf(f, " :travel (%.17g %.17g %.17g)", g[7], g[8], g[9]);
+      if (kd != FEAHIP_OBSTACLE_PLANE) fprintf(f, " :inside %s", inside ? "t" : "nil");
+      fprintf(f, ")");
     }
     fprintf(f, ")");
   }

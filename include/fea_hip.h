@@ -241,6 +241,88 @@ int feahip_get_surface_forces(feahip_ctx *ctx, double *f);
 int feahip_set_load_factor(feahip_ctx *ctx, double lambda);
 int feahip_get_load_factor(feahip_ctx *ctx, double *lambda);
 
+/* ---- frictionless contact with rigid obstacles -------------------------- */
+/* Node-to-rigid-surface contact by a penalty with augmented-Lagrangian
+ * (Uzawa) updates.  The contact NODES are the nodes of the contact faces,
+ * which are given and resolved exactly as the faces of
+ * feahip_set_surface_loads (same refusals, same rule for rank contexts).
+ * Each contact node a carries a reference-area weight w_a, computed once on
+ * the host from X0: tri3 A/3; quad4 the row sums of int N_a dA by the 2 x 2
+ * rule; tri6 HRZ lumping -- the diagonal of int N_a N_b dA by the 6-point rule,
+ * scaled so the six weights sum to the area (the corner functions of a tri6
+ * integrate to zero, so a consistent weight would switch the corners off).
+ * Up to FEAHIP_MAX_OBSTACLES obstacles; obstacle o sits at
+ * c = c0 + load_factor * travel, so it moves with the load increments as the
+ * prescribed displacements and the surface loads do.  With x the node:
+ *   FEAHIP_OBSTACLE_PLANE            g = (x - c).a              n = a
+ *   FEAHIP_OBSTACLE_SPHERE           g = |x - c| - r            n = (x - c)/|x - c|
+ *   FEAHIP_OBSTACLE_SPHERE_INSIDE    g = r - |x - c|            n = -(x - c)/|x - c|
+ *   FEAHIP_OBSTACLE_CYLINDER         as the sphere with q = (I - a a')(x - c) for x - c
+ *   FEAHIP_OBSTACLE_CYLINDER_INSIDE  as the sphere from inside, with q
+ * a is the plane's normal or the cylinder's axis (normalised by the library).
+ * A node ON the sphere's centre or the cylinder's axis (rho = |x - c| or |q|
+ * = 0) has no normal and is SKIPPED for that obstacle, in every kernel.
+ * With the multiplier mu_ao >= 0 (0 at feahip_set_contact), the penetration
+ * p = -g and the penalty eps (a pressure per length):
+ *   pressure  t = max(0, mu_ao + eps p)       force  F_a += w_a t n
+ *   K_aa += w_a [ eps n n' - s t (P - n n') / rho ]   (s = +1 solid, -1 inside, 0 plane;
+ *                                                       P = I, or I - a a' for cylinders)
+ *   potential Pi_c = sum w_a t^2 / (2 eps)    augmentation  mu_ao <- max(0, mu_ao + eps p)
+ * Every assembly that writes the residual produces f = lambda F_ext - T + F_c,
+ * every assembly that writes K adds K_c to the node's own diagonal block: no
+ * pattern change.  feahip_get_reactions therefore sees F_c as well.  A context
+ * without contact launches nothing and keeps the bits it had before.
+ * feahip_solve (and the group solve) with augment_max > 0: after the Newton
+ * loop of a load increment has converged, up to augment_max times -- read the
+ * maximum penetration over the active pairs; stop if it is <= gap_tolerance;
+ * update the multipliers; iterate again at the same load.  its_log[step] counts
+ * the iterations of all passes.  Modified Newton stashes the K of the pass's
+ * first assembly, contact stiffness included; with contact, full Newton is the
+ * sensible choice (the active set changes inside a step).  The Newmark and the
+ * explicit loops use the multipliers as they stand and never update them;
+ * feahip_stable_step adds w_a eps n n' of EVERY contact pair, in contact or not,
+ * to the K of the plain assembly (in place of the active pairs' own term)
+ * before the Gershgorin bound, so a node entering contact between two
+ * estimates cannot push the step over the bound.  feahip_solve_arclength
+ * refuses a context with contact (FEAHIP_ESTATE).  Modes and buckling see the K
+ * of the assembly entry, contact stiffness of the active pairs included (the
+ * bilateral linearisation); nothing more is promised there.                 */
+enum { FEAHIP_OBSTACLE_PLANE = 0, FEAHIP_OBSTACLE_SPHERE = 1, FEAHIP_OBSTACLE_SPHERE_INSIDE = 2,
+       FEAHIP_OBSTACLE_CYLINDER = 3, FEAHIP_OBSTACLE_CYLINDER_INSIDE = 4 };
+#define FEAHIP_MAX_OBSTACLES 8
+/* replaces the contact; n_faces = 0 or n_obstacles = 0 clears it (multipliers
+ * included) -- but a feahip_create_rank_local context given obstacles and no
+ * face (its slab holds none of them) keeps the obstacles and the parameters,
+ * so that its rank enters the collectives of the augmentation with the
+ * others.  kind[n_obstacles]; geom[n_obstacles][10] = point (3), direction
+ * (3), radius, travel (3).  FEAHIP_EINVAL with the offending index in
+ * feahip_last_error: a bad face, an unknown kind, penalty <= 0, a zero
+ * direction (plane, cylinders), radius <= 0 on a round kind, more than
+ * FEAHIP_MAX_OBSTACLES obstacles, negative augment_max or gap_tolerance.    */
+int feahip_set_contact(feahip_ctx *ctx, int n_faces, int nodes_per_face, const int *face_nodes,
+                       int n_obstacles, const int *kind, const double *geom, double penalty,
+                       int augment_max, double gap_tolerance);
+/* the contact nodes this context owns, ascending, in the ids of its node
+ * arrays, and their weights (either may be null: *n alone sizes the arrays)  */
+int feahip_get_contact_nodes(feahip_ctx *ctx, int *n, int *nodes, double *weights);
+/* the obstacles of the contact in force (0 without one)                     */
+int feahip_get_contact_obstacles(feahip_ctx *ctx, int *n_obstacles);
+/* mu[n][n_obstacles] in the node order of feahip_get_contact_nodes          */
+int feahip_get_contact_multipliers(feahip_ctx *ctx, double *mu);
+int feahip_set_contact_multipliers(feahip_ctx *ctx, const double *mu);
+/* F_c at the current nodes, [3N], shaped like feahip_get_surface_forces     */
+int feahip_get_contact_forces(feahip_ctx *ctx, double *f);
+/* per node: the smallest gap over the obstacles (+inf away from the owned
+ * contact nodes) and the summed pressure t (0 there); either may be null     */
+int feahip_get_contact_status(feahip_ctx *ctx, double *gap, double *pressure);
+/* collective, as feahip_kinetic_energy (one call on any context of an
+ * in-process group drives the group; every RCCL rank calls it): out[4] = active pairs (t > 0), the
+ * largest penetration over them (0 without one), sum w t, Pi_c               */
+int feahip_contact_info(feahip_ctx *ctx, double *out);
+/* collective: reports the largest penetration over the active pairs (a null
+ * max_penetration skips that reduction), then updates the multipliers        */
+int feahip_contact_augment(feahip_ctx *ctx, double *max_penetration);
+
 /* ---- heterogeneous bodies: a table of (lambda, mu) pairs and one material id
  * per element.  feahip_set_materials replaces the context's single pair by the
  * table; n_materials = 0 returns to the pair given at creation.  At most
@@ -1088,7 +1170,10 @@ int feahip_sync(feahip_ctx *ctx);
  * store filled with the hash; with zero coefficients, so nothing moves); 13-17
  * refused without a mass and where feahip_solve_modes is; 18 k_geom_elements
  * and 19 k_geom_blocks, the two passes of the geometric stiffness at the
- * current nodes (refused where feahip_solve_buckling is; no mass needed).     */
+ * current nodes (refused where feahip_solve_buckling is; no mass needed);
+ * 20 k_contact alone, K and f (refused on a context without contact; it adds
+ * K_c and F_c into the K and f in force on every launch: both are garbage
+ * afterwards, assemble again).                                              */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
