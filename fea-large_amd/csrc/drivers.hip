@@ -104,6 +104,9 @@ int dist_newton(std::vector<feahip_ctx *> &R, int load_increments, int max_newto
 // f = lambda F_ext - T - a0 M (x - xt); corrector a = a0 (x - xt), v = vt + gamma dt a.  Acceleration and velocity are
 // pointwise functions of x, which every rank holds at its halo nodes after dist_update_nodes_with_solution: no
 // exchange beyond the static loop's.
+// With Rayleigh damping C = alpha M + beta_k K_d (feahip_set_damping), c1 = gamma / (beta dt) and w = vt + c1 (x - xt), the
+// velocity the corrector will assign: the residual is f - a0 M (x - xt) - C w and the matrix K + (a0 + c1 alpha) M +
+// c1 beta_k K_d (kernels_damping.hip).  C is constant, so this tangent is exact; w is pointwise too and needs no exchange.
 namespace {
 struct NodeCopies {
   std::vector<double *> p;
@@ -116,9 +119,9 @@ int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double be
                  double *tol_log, int tol_log_cap, int *its_log, int *steps_done)
 {
   int rc, nlog = 0, step = 0;
-  const double a0 = 1.0 / (beta * dt * dt);
+  const double a0 = 1.0 / (beta * dt * dt), c1 = gamma / (beta * dt);
   NodeCopies xn;                                                      // x at the start of the step in hand
-  FOR_RANKS(c) { if ((rc = mass_ensure(c, "feahip_solve_dynamic"))) return rc; }
+  FOR_RANKS(c) { if ((rc = mass_ensure(c, "feahip_solve_dynamic")) || (rc = damping_ready(c, "feahip_solve_dynamic"))) return rc; }
   for (feahip_ctx *c : R) {
     (void)hipSetDevice(c->device);
     c->mass.ke_parts = 0;                                             // (host only: the velocities are about to change)
@@ -139,8 +142,15 @@ int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double be
     do {
       it++;
       FOR_RANKS(c) { if ((rc = feahip_create_stiffness_and_residual(c))) return rc; }
-      FOR_RANKS(c) { if ((rc = launch_mass_residual(c, a0))) return rc; }
-      FOR_RANKS(c) { if ((rc = launch_mass_add(c, a0))) return rc; }
+      FOR_RANKS(c) {                                                  // (a context without damping: the launches as before)
+        const DampingState &D = c->damping;
+        if ((rc = D.on() ? launch_damp_residual(c, a0, c1) : launch_mass_residual(c, a0))) return rc;
+      }
+      FOR_RANKS(c) {
+        const DampingState &D = c->damping;
+        if ((rc = D.beta > 0.0 ? launch_damp_add(c, a0 + c1 * D.alpha, c1 * D.beta)
+                               : launch_mass_add(c, D.on() ? a0 + c1 * D.alpha : a0))) return rc;
+      }
       FOR_RANKS(c) { if ((rc = feahip_apply_prescribed_bc(c, 0.0))) return rc; }
       if ((rc = dist_solve_pcg(R, solver_type, solver_tolerance, solver_max_iter, nullptr, nullptr))) return rc;
       if ((rc = dist_energy(R, &tolerance))) return rc;
@@ -168,11 +178,11 @@ int dist_dynamic(std::vector<feahip_ctx *> &R, int n_steps, double dt, double be
   return FEAHIP_OK;
 }
 
-// M a = lambda F_ext(x) - T(x), a = 0 on the prescribed dofs: the ordinary solve with K := M
+// M a = lambda F_ext(x) - T(x) - C v, a = 0 on the prescribed dofs: the ordinary solve with K := M
 int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, double tol, int max_iter)
 {
   int rc;
-  FOR_RANKS(c) { if ((rc = mass_ensure(c, "feahip_consistent_acceleration"))) return rc; }
+  FOR_RANKS(c) { if ((rc = mass_ensure(c, "feahip_consistent_acceleration")) || (rc = damping_ready(c, "feahip_consistent_acceleration"))) return rc; }
   for (feahip_ctx *c : R) {
     (void)hipSetDevice(c->device);
     FEA_HIP_CHECK(c, hipMemsetAsync(c->d_K_base, 0, sizeof(double) * 9 * (size_t)(c->kb1 - c->kb0), c->stream));
@@ -180,6 +190,7 @@ int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, 
   }
   FOR_RANKS(c) { if ((rc = launch_mass_add(c, 1.0))) return rc; }
   FOR_RANKS(c) { if ((rc = feahip_create_residual_forces(c))) return rc; }
+  FOR_RANKS(c) { if (c->damping.on() && (rc = launch_damp_force(c))) return rc; }   // the velocities are valid on halo nodes
   FOR_RANKS(c) { if ((rc = feahip_apply_prescribed_bc(c, 0.0))) return rc; }
   if ((rc = dist_solve_pcg(R, solver_type, tol, max_iter, nullptr, nullptr))) return rc;
   if (R[0]->tr && (rc = R[0]->tr->exchange(R, 1))) return rc;        // the owners' rows of u to the halo copies
@@ -194,6 +205,10 @@ int dist_consistent_acceleration(std::vector<feahip_ctx *> &R, int solver_type, 
 // ONE residual assembly f = lambda (F_surf + F_body) - T(x); finish (a = f / ml, v = vh + dt/2 a).  No K is assembled, no
 // system solved; with a fixed dt nothing is read back between the first and the last step.  v and a are authoritative on
 // owned nodes only: a halo node gets v = u / dt and a = 0, which needs no second exchange.
+// Mass-proportional damping (feahip_set_damping with beta_k = 0) changes the finish alone: M_L a = f - alpha M_L v with the
+// end-of-step v, a = (f / ml - alpha vh) / (1 + alpha dt / 2).  In vh this is central differences with the centred velocity
+// (vh_- + vh_+) / 2, whose stability limit stays 2 / omega_max for every alpha >= 0: dist_stable_step is as it was.  A
+// stiffness-proportional part is refused: there is no K in this loop, and a lagged K_d vh would shrink the stable step.
 
 // Gershgorin: omega_max^2 <= max_i (sum_j |K_ij|) / ml(i), K the unmasked tangent at x; dt_crit = 2 / sqrt(bound)
 int dist_stable_step(std::vector<feahip_ctx *> &R, double *dt_crit)
@@ -276,6 +291,13 @@ int dist_explicit(std::vector<feahip_ctx *> &R, int n_steps, double dt_fixed, do
 {
   int rc, step = 0, checked = 0, result = FEAHIP_OK;
   double dt = dt_fixed;
+  for (feahip_ctx *c : R)
+    if (c->damping.beta > 0.0) {
+      for (feahip_ctx *e : R)
+        e->err = "solve_explicit: the damping has beta_k = " + std::to_string(c->damping.beta) +
+                 " > 0; the explicit loop takes mass-proportional damping only (feahip_set_damping(ctx, alpha, 0))";
+      return FEAHIP_EINVAL;
+    }
   FOR_RANKS(c) { if ((rc = lump_ensure(c, "feahip_solve_explicit"))) return rc; }
   for (feahip_ctx *c : R) {
     (void)hipSetDevice(c->device);

@@ -469,6 +469,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->surf.release();
   c->contact.release();
   c->mass.release();
+  c->damping.release();
   c->results.release();
   c->modal.release();
   c->buckling.release();
@@ -1154,6 +1155,47 @@ extern "C" int feahip_mass_spmv(feahip_ctx *c, const double *x, double *y)
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream));   // rows of other ranks: 0
   if ((rc = launch_mass_product(c, c->mass.d_xt, c->d_q))) return rc;
   return get_node_vec(c, c->d_q, y);
+}
+
+// ---- Rayleigh damping C = alpha M + beta_k K_d (kernels_damping.hip) --------------------------------------------------
+extern "C" int feahip_set_damping(feahip_ctx *c, double alpha, double beta_k)
+{
+  CTX_GUARD_NOK(c);
+  return damping_set(c, alpha, beta_k);
+}
+
+extern "C" int feahip_get_damping(feahip_ctx *c, double *alpha, double *beta_k)
+{
+  if (!c || !alpha || !beta_k) return FEAHIP_EINVAL;
+  *alpha = c->damping.alpha; *beta_k = c->damping.beta;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_damping_spmv(feahip_ctx *c, const double *v, double *y)
+{
+  CTX_GUARD(c);
+  if (!v || !y) return FEAHIP_EINVAL;
+  if (!c->damping.on()) { c->err = "feahip_damping_spmv: no damping on this context (feahip_set_damping)"; return FEAHIP_ESTATE; }
+  int rc;
+  if ((rc = damping_ready(c, "feahip_damping_spmv"))) return rc;
+  double *d_v4 = nullptr;                                          // (a context with beta_k alone may have no mass vectors)
+  FEA_HIP_CHECK(c, hipMalloc((void **)&d_v4, sizeof(double) * 4 * (size_t)c->N));
+  rc = set_node4(c, d_v4, v);
+  if (!rc && hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream) != hipSuccess) rc = FEAHIP_EHIP;   // rows of other ranks: 0
+  if (!rc) rc = launch_damp_product(c, d_v4, c->d_q);
+  if (!rc) rc = get_node_vec(c, c->d_q, y);                        // (synchronises)
+  dev_free({d_v4});
+  return rc;
+}
+
+extern "C" int feahip_host_rayleigh(double omega1, double zeta1, double omega2, double zeta2, double *alpha, double *beta_k)
+{
+  if (!alpha || !beta_k) return FEAHIP_EINVAL;
+  if (!(omega1 > 0.0) || !(omega2 > 0.0) || !std::isfinite(omega1) || !std::isfinite(omega2) || omega1 == omega2) return FEAHIP_EINVAL;
+  const double den = omega2 * omega2 - omega1 * omega1;
+  *alpha = 2.0 * omega1 * omega2 * (zeta1 * omega2 - zeta2 * omega1) / den;
+  *beta_k = 2.0 * (zeta2 * omega2 - zeta1 * omega1) / den;
+  return FEAHIP_OK;
 }
 
 // the ranks a collective call made on one context drives: the members of its in-process group, or the context alone
@@ -1952,6 +1994,16 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     const int rk = mass_ensure(c, "time_kernel");
     if (rk) return rk;
   }
+  if (what == 21 || what == 22) {
+    const std::string who = "time_kernel(" + std::to_string(what) + ")";
+    if (!c->damping.on() || (what == 21 && !(c->damping.beta > 0.0))) {
+      c->err = who + (what == 21 ? ": no damping with beta_k > 0 on this context (feahip_set_damping)" : ": no damping on this context (feahip_set_damping)");
+      return FEAHIP_EINVAL;
+    }
+    if (!c->mass.set || c->mass.stale) { c->err = who + ": no mass on this context (feahip_set_mass)"; return FEAHIP_EINVAL; }
+    int rk;
+    if ((rk = mass_ensure(c, "time_kernel")) || (rk = damping_ready(c, "time_kernel"))) return rk;
+  }
   if (what == 10 || what == 11) {
     if (!c->mass.set || c->mass.stale) { c->err = std::string(what == 10 ? "time_kernel(10)" : "time_kernel(11)") + ": no mass on this context (feahip_set_mass)"; return FEAHIP_EINVAL; }
     const int rk = lump_ensure(c, "time_kernel");
@@ -1993,6 +2045,8 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 16: case 17: return time_deflate_kernel(c, what);
     case 18: case 19: return time_geom_kernel(c, what);
     case 20: return launch_contact(c, true, true, c->d_f);
+    case 21: return launch_damp_add(c, 1.0, 1.0);
+    case 22: return launch_damp_residual(c, 1.0, 1.0);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

@@ -467,6 +467,19 @@ struct MassState {
   void release() { dev_free({d_m_base, d_vel, d_acc, d_xt, d_vt, d_body, d_ml, d_ke_part}); *this = MassState(); }
 };
 
+// Rayleigh damping C = alpha M + beta K_d (kernels_damping.hip).  M is the mass of the loop that runs (it is not copied);
+// K_d is a snapshot of the plain tangent at the x of feahip_set_damping, stored like d_K over the owned window of the
+// shard installed then.  Nothing of it exists, and nothing of kernels_damping.hip is launched, while both are 0.
+struct DampingState {
+  double alpha = 0, beta = 0;
+  double *d_Kd_alloc = nullptr;        // the allocation; d_Kd_base = d_Kd_alloc + (kb0 & 1), the 16-byte phase of K
+  double *d_Kd_base = nullptr;         // [kb1 - kb0][3][3], null unless beta > 0
+  double *d_Kd = nullptr;              // d_Kd_base - 9 kb0: indexed by GLOBAL block number, as d_K
+  int row0 = -1, row1 = -1;            // the shard the snapshot was taken for
+  bool on() const { return alpha > 0.0 || beta > 0.0; }
+  void release() { dev_free({d_Kd_alloc}); *this = DampingState(); }
+};
+
 // result recovery (kernels_results.hip): nothing of it exists until a results entry is called
 struct ResultState {
   double *d_rec = nullptr;             // [E][8] element records: sum vol sigma (6), sum vol, W_e
@@ -665,6 +678,7 @@ struct feahip_ctx {
   int *d2_flag = nullptr;      // [2]
   // consistent mass (kernels_mass.hip): nothing of it exists, and nothing below is launched, until feahip_set_mass
   MassState mass;
+  DampingState damping;
   ResultState results;
   ModalState modal;
   BucklingState buckling;
@@ -816,6 +830,14 @@ int lump_ensure(feahip_ctx *c, const char *who);               // mass_ensure, t
 int launch_explicit_kick(feahip_ctx *c, double dt);            // vh = v + dt/2 a (d_vt), u = dt vh; 0 on prescribed dofs
 int launch_explicit_presc(feahip_ctx *c, double dlambda, double dt);   // vh = prescribed increment / dt on the prescribed dofs
 int launch_explicit_finish(feahip_ctx *c, double dt);          // a = f / ml, v = vh + dt/2 a; partial sums of the kinetic energy
+                                                               // (damped: a = (f / ml - alpha vh) / (1 + alpha dt / 2))
+// kernels_damping.hip -- Rayleigh damping C = alpha M + beta K_d
+int damping_set(feahip_ctx *c, double alpha, double beta);
+int damping_ready(feahip_ctx *c, const char *who);             // FEAHIP_ESTATE when K_d is of another shard, or alpha > 0 has no mass
+int launch_damp_residual(feahip_ctx *c, double a0, double c1); // f -= M (a0 d + alpha w) + beta K_d w, d = x - xt, w = vt + c1 d
+int launch_damp_product(feahip_ctx *c, const double *d_v4, double *d_y);   // y = C v on the owned rows, v in the node layout
+int launch_damp_add(feahip_ctx *c, double cm, double ck);      // K += cm M + ck K_d on the owned values (beta > 0 only)
+int launch_damp_force(feahip_ctx *c);                          // f -= C v on the owned rows (through d_q)
 int launch_kinetic_energy(feahip_ctx *c, double *d_out);       // *d_out = 1/2 sum ml |v|^2 over the owned rows
 int launch_count_inverted(feahip_ctx *c);                      // d_flag[1] = elements with det J <= 0 (or NaN) at a Gauss point of x
 // kernels_solve.hip -- Gershgorin bound max_i sum_j |K_ij| / ml(i) over the owned rows into d_scal[8]

@@ -18,7 +18,8 @@
 // (k_mass_lump: m_e d_a / sum_b d_b with d_a = sum_g rho w det J0 N_a^2 -- positive on every element type and the
 // element's mass exactly; the row sum of a 10-node tetrahedron is <= 0 at its corners).  It is built on first use by
 // lump_ensure and framed by two pointwise kernels per step, k_explicit_kick and k_explicit_finish.  A context that
-// never makes an explicit call allocates and launches none of it.
+// never makes an explicit call allocates and launches none of it.  The kernels of Rayleigh damping are in
+// kernels_damping.hip; only the damped finish of an explicit step (k_explicit_finish<.., DAMP>) is here.
 #include "feahip_internal.h"
 #include "reduce_device.h"
 #include <cmath>
@@ -342,11 +343,13 @@ void k_explicit_presc(int n_cdof, const int *__restrict__ cdof, const double *__
 // piece's share of 1/2 ml |v|^2 into the workgroup's partial sum.  Other nodes: v = u / dt, a = 0 -- u is what the
 // exchange brought (0 on nodes that are not in the halo), so no second exchange is needed; v and a are authoritative on
 // owned nodes only.  KE_ONLY: nothing is written but the partial sums of the velocities in force.
-template <bool KE_ONLY>
+// DAMP (mass-proportional damping C = alpha M_L): M_L a = f - alpha M_L v with the END-of-step velocity v = vh + dt/2 a,
+// solved pointwise: a = (f / ml - alpha vh) / (1 + alpha dt / 2).
+template <bool KE_ONLY, bool DAMP>
 __global__ __launch_bounds__(256)
 void k_explicit_finish(int N, int a0, int a1, double dt, const double *__restrict__ f, const double *__restrict__ ml,
                        const uint8_t *__restrict__ mask, const double *__restrict__ u, const mass_v2d *__restrict__ vh,
-                       mass_v2d *__restrict__ v, mass_v2d *__restrict__ a, double *__restrict__ part)
+                       mass_v2d *__restrict__ v, mass_v2d *__restrict__ a, double *__restrict__ part, double alpha)
 {
   __shared__ double sh[4];
   const size_t n = (size_t)N * 2, stride = (size_t)gridDim.x * 256;
@@ -363,9 +366,16 @@ void k_explicit_finish(int N, int a0, int a1, double dt, const double *__restric
       mass_v2d vv, aa;
       if (own) {
         const double m = ml[node];
-        aa.x = mask[d] ? 0.0 : f[d] / m;
-        aa.y = lo ? (mask[d + 1] ? 0.0 : f[d + 1] / m) : 0.0;
-        vv = vh[p] + hdt * aa;
+        const mass_v2d wh = vh[p];
+        if constexpr (DAMP) {
+          const double den = 1.0 + alpha * hdt;
+          aa.x = mask[d] ? 0.0 : (f[d] / m - alpha * wh.x) / den;
+          aa.y = lo ? (mask[d + 1] ? 0.0 : (f[d + 1] / m - alpha * wh.y) / den) : 0.0;
+        } else {
+          aa.x = mask[d] ? 0.0 : f[d] / m;
+          aa.y = lo ? (mask[d + 1] ? 0.0 : f[d + 1] / m) : 0.0;
+        }
+        vv = wh + hdt * aa;
         ke += 0.5 * m * (vv.x * vv.x + vv.y * vv.y);
       } else {
         aa.x = 0.0; aa.y = 0.0;
@@ -497,8 +507,13 @@ int launch_explicit_finish(feahip_ctx *c, double dt)
 {
   MassState &M = c->mass;
   const int g = piece_grid((size_t)c->N * 2);
-  hipLaunchKernelGGL(k_explicit_finish<false>, dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, dt, c->d_f, M.d_ml,
-                     (const uint8_t *)c->d_dofmask, c->d_u, (const mass_v2d *)M.d_vt, (mass_v2d *)M.d_vel, (mass_v2d *)M.d_acc, M.d_ke_part);
+  if (c->damping.alpha > 0.0)
+    hipLaunchKernelGGL((k_explicit_finish<false, true>), dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, dt, c->d_f, M.d_ml,
+                       (const uint8_t *)c->d_dofmask, c->d_u, (const mass_v2d *)M.d_vt, (mass_v2d *)M.d_vel, (mass_v2d *)M.d_acc, M.d_ke_part,
+                       c->damping.alpha);
+  else
+    hipLaunchKernelGGL((k_explicit_finish<false, false>), dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, dt, c->d_f, M.d_ml,
+                       (const uint8_t *)c->d_dofmask, c->d_u, (const mass_v2d *)M.d_vt, (mass_v2d *)M.d_vel, (mass_v2d *)M.d_acc, M.d_ke_part, 0.0);
   FEA_HIP_CHECK(c, hipGetLastError());
   M.ke_parts = g;
   return FEAHIP_OK;
@@ -509,9 +524,9 @@ int launch_kinetic_energy(feahip_ctx *c, double *d_out)
   MassState &M = c->mass;
   if (M.ke_parts == 0) {                                   // no explicit step left the sums of these velocities
     const int g = piece_grid((size_t)c->N * 2);
-    hipLaunchKernelGGL(k_explicit_finish<true>, dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, 0.0, (const double *)nullptr,
+    hipLaunchKernelGGL((k_explicit_finish<true, false>), dim3(g), dim3(256), 0, c->stream, c->N, c->row0, c->row1, 0.0, (const double *)nullptr,
                        M.d_ml, (const uint8_t *)nullptr, (const double *)nullptr, (const mass_v2d *)nullptr, (mass_v2d *)M.d_vel,
-                       (mass_v2d *)nullptr, M.d_ke_part);
+                       (mass_v2d *)nullptr, M.d_ke_part, 0.0);
     M.ke_parts = g;
   }
   enq_reduce_final(c, M.ke_parts, 1, 0, M.d_ke_part, d_out);

@@ -132,6 +132,10 @@ ABI = {
     "feahip_set_mass": [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "feahip_mass_spmv": [C.c_void_p, _dp, _dp],
     "feahip_set_body_force": [C.c_void_p, _dp],
+    "feahip_set_damping": [C.c_void_p, C.c_double, C.c_double],
+    "feahip_get_damping": [C.c_void_p, _dp, _dp],
+    "feahip_damping_spmv": [C.c_void_p, _dp, _dp],
+    "feahip_host_rayleigh": [C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp],
     "feahip_set_velocities": [C.c_void_p, _dp],
     "feahip_get_velocities": [C.c_void_p, _dp],
     "feahip_set_accelerations": [C.c_void_p, _dp],
@@ -221,6 +225,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("damping_alpha", C.c_double), ("damping_beta", C.c_double),
         ("contact_faces_count", C.c_int), ("contact_nodes_per_face", C.c_int), ("contact_nodes", _ip),
         ("contact_obstacles_count", C.c_int), ("contact_kind", _ip), ("contact_geom", _dp),
         ("contact_penalty", C.c_double), ("contact_augment", C.c_int), ("contact_gap_tolerance", C.c_double),
@@ -310,6 +315,16 @@ def host_buckling_factor(nu):
     return factor
 
 
+def host_rayleigh(omega1, zeta1, omega2, zeta2):
+    """feahip_host_rayleigh (no device): (alpha, beta_k) of C = alpha M + beta_k K that give the damping ratios zeta1, zeta2
+    at the circular frequencies omega1, omega2.  A negative coefficient is returned as it is (set_damping refuses it)."""
+    a, b = C.c_double(0), C.c_double(0)
+    rc = load_library().feahip_host_rayleigh(omega1, zeta1, omega2, zeta2, C.byref(a), C.byref(b))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_rayleigh: two different positive frequencies, please ({rc})")
+    return a.value, b.value
+
+
 def element_tables(ele_type, gauss_count):
     """(weights[G], forms[G][npe], dforms[G][3][npe]) from the host plug-in."""
     h = load_host_library()
@@ -327,7 +342,12 @@ def _take_dynamics(obj, kw):
     """The implicit-dynamics fields of a Deck or a Slab: density (a number, or one per material for FeaSolver.set_mass; the
     .sexp grammar holds one number), body_force[3] (an acceleration per unit mass) and dynamics = dict(steps, dt, beta,
     gamma, dlambda) -- or, for the explicit scheme, dict(steps, dt, dlambda, scheme="explicit", safety, restep), where
-    dt = 0 asks for safety times the stable-step estimate, made again every restep steps."""
+    dt = 0 asks for safety times the stable-step estimate, made again every restep steps.  damping = (alpha, beta_k) of
+    FeaSolver.set_damping, taken at the reference configuration when the solver is made."""
+    dm = kw.get("damping")
+    obj.damping = None if dm is None else (float(dm[0]), float(dm[1]))
+    if obj.damping is not None and not all(0.0 <= v < np.inf for v in obj.damping):
+        raise ValueError("damping: two finite coefficients that are not negative")
     obj.density = kw.get("density")
     bf = kw.get("body_force")
     obj.body_force = None if bf is None else np.ascontiguousarray(bf, dtype=np.float64).reshape(3)
@@ -484,6 +504,7 @@ class Deck:
                               dlambda=fd.dynamics_dlambda,
                               **(dict(scheme="explicit", safety=fd.dynamics_safety, restep=fd.dynamics_restep)
                                  if fd.dynamics_explicit else {})) if fd.has_dynamics else None,
+                damping=(fd.damping_alpha, fd.damping_beta) if fd.has_dynamics and (fd.damping_alpha or fd.damping_beta) else None,
                 results=dict(nodal_stress=bool(fd.results_nodal_stress), energy=bool(fd.results_energy),
                              reactions=bool(fd.results_reactions)),
                 **(dict(contact_faces=np.ctypeslib.as_array(fd.contact_nodes, (nc, ncf)).copy(),
@@ -533,10 +554,14 @@ class Deck:
             fd.dynamics_beta, fd.dynamics_gamma, fd.dynamics_dlambda = dyn["beta"], dyn["gamma"], dyn["dlambda"]
             if dyn.get("scheme") == "explicit":
                 fd.dynamics_explicit, fd.dynamics_safety, fd.dynamics_restep = 1, dyn["safety"], dyn["restep"]
+            if getattr(self, "damping", None) is not None:
+                fd.damping_alpha, fd.damping_beta = self.damping
             if getattr(self, "body_force", None) is not None:
                 fd.has_body_force = 1
                 for k in range(3):
                     fd.body_force[k] = float(self.body_force[k])
+        elif getattr(self, "damping", None) is not None and any(self.damping):
+            raise ValueError("the deck grammar holds the damping inside (dynamics ...): it needs a density")
         res = getattr(self, "results", None) or {}
         fd.results_nodal_stress, fd.results_energy = int(res.get("nodal_stress", False)), int(res.get("energy", False))
         fd.results_reactions = int(res.get("reactions", False))
@@ -592,11 +617,13 @@ class FeaSolver:
         self._deck_mass()
 
     def _deck_mass(self):
-        """Installs the deck's (or the slab's) density and body force, where it has them."""
+        """Installs the deck's (or the slab's) density, body force and damping, where it has them."""
         if getattr(self.deck, "density", None) is not None:
             self.set_mass(self.deck.density)
             if getattr(self.deck, "body_force", None) is not None:
                 self.set_body_force(self.deck.body_force)
+        if getattr(self.deck, "damping", None) is not None and any(self.deck.damping):
+            self.set_damping(*self.deck.damping)
 
     def _deck_materials(self):
         """Installs the deck's (or the slab's) material table, where it has one."""
@@ -778,6 +805,24 @@ class FeaSolver:
         assert len(x) == self.ndof
         y = np.zeros(self.ndof)
         self._chk(self._lib.feahip_mass_spmv(self._ctx, _d(x), _d(y)))
+        return y
+
+    def set_damping(self, alpha, beta=0.0):
+        """feahip_set_damping: C = alpha M + beta K_d, K_d the plain tangent at the nodes in force (a snapshot, kept in a
+        store as large as K when beta > 0).  (0, 0) clears it."""
+        self._chk(self._lib.feahip_set_damping(self._ctx, float(alpha), float(beta)))
+
+    def damping(self):
+        a, b = C.c_double(0), C.c_double(0)
+        self._chk(self._lib.feahip_get_damping(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def damping_spmv(self, v):
+        """y = C v on the owned rows (zero on the others), as mass_spmv."""
+        v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+        assert len(v) == self.ndof
+        y = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_damping_spmv(self._ctx, _d(v), _d(y)))
         return y
 
     def set_body_force(self, b):
@@ -1707,7 +1752,7 @@ def slab_of(deck, rank, nranks):
                 n_global_nodes=N, halo_owner=owner[ng[no:]], presc_node=local_of[deck.presc_node[keep]] if keep.any() else [],
                 presc_type=deck.presc_type[keep] if keep.any() else [],
                 presc_values=deck.presc_values[keep] if keep.any() else np.zeros((0, 3)), **kw)
-    for k in ("linesearch_max", "arclength_max", "density", "body_force", "dynamics"):
+    for k in ("linesearch_max", "arclength_max", "density", "body_force", "dynamics", "damping"):
         if hasattr(deck, k):
             setattr(slab, k, getattr(deck, k))
     return slab
@@ -1737,6 +1782,9 @@ class FeaGroup:
         self._lib = load_library()
         self._arr = (C.c_void_p * n)(*[r._ctx for r in self.ranks])
         self._chk(self._lib.feahip_group_init(self._arr, n))
+        dm = getattr(slabs[0] if slabs is not None else deck, "damping", None)
+        if dm is not None and dm[1] > 0.0:                      # K_d is keyed by the row shard, which the line above installed
+            self.set_damping(*dm)
         self.rows = [r.owned_rows() for r in self.ranks]        # library ids (local ids for rank contexts)
         if rank_contexts:
             self.nodes = [r.node_global[:r.n_own].astype(np.int64) for r in self.ranks]
@@ -1809,6 +1857,10 @@ class FeaGroup:
 
     def set_body_force(self, b):
         self.each("set_body_force", b)
+
+    def set_damping(self, alpha, beta=0.0):
+        """Every member takes the snapshot of its own rows (the call is per context)."""
+        self.each("set_damping", alpha, beta)
 
     def consistent_acceleration(self, solver_type, tolerance=1e-14, max_iterations=20000):
         self.ranks[0].consistent_acceleration(solver_type, tolerance, max_iterations)   # one call drives the group

@@ -91,6 +91,13 @@ typedef struct fea_deck {
    * to the .msh file; :energy and :reactions add one log line each per finished step.  Written by fea_deck_save only
    * when one of them is set; without the section the file and the log are what they were                        */
   int results_nodal_stress, results_energy, results_reactions;
+  /* Rayleigh damping, optional: :damping-alpha a :damping-beta b inside (dynamics ...), both >= 0 and 0 where absent:
+   * C = a M + b K_d, K_d the tangent at the reference configuration (fea_deck_create_solver calls feahip_set_damping
+   * after the mass).  :scheme explicit with a non-zero :damping-beta is a load error (the explicit loop takes the
+   * mass-proportional part only).  Written by fea_deck_save only when non-zero, with 17 digits: a deck without the keys
+   * is read, run and written as before.  The two fields are the newest of the struct and stand in front of the contact
+   * fields, whose place (with the buckling and modal ones behind them) the host tests pin                        */
+  double damping_alpha, damping_beta;
   /* contact with rigid obstacles, optional: (contact :penalty e :augment k :gap-tolerance g (faces (n ...) ...)
    * (plane :point (x y z) :normal (x y z) :travel (x y z)) (sphere :center (..) :radius r :travel (..) :inside t)
    * (cylinder :point (..) :axis (..) :radius r :travel (..) :inside t) ...) inside (boundary-conditions ...), beside

@@ -18,7 +18,7 @@ int fea_mass_points(int ele_type)
   return ele_type == FEA_TETRAHEDRA4 ? 4 : ele_type == FEA_TETRAHEDRA10 ? 27 : ele_type == FEA_HEXAHEDRA8 ? 8 : 0;
 }
 
-/* the deck's uniform mass and its body force */
+/* the deck's uniform mass, its body force and its damping (at the reference configuration the context starts from) */
 static int install_mass(const fea_deck *d, feahip_ctx *ctx)
 {
   double w[32], forms[32 * 10], dforms[32 * 3 * 10];
@@ -26,7 +26,8 @@ static int install_mass(const fea_deck *d, feahip_ctx *ctx)
   int rc;
   if (gm <= 0 || fea_element_tables(d->ele_type, gm, w, forms, dforms) != d->nodes_per_element) return FEAHIP_EINVAL;
   if ((rc = feahip_set_mass(ctx, 1, &d->density, gm, w, forms, dforms))) return rc;
-  return d->has_body_force ? feahip_set_body_force(ctx, d->body_force) : 0;
+  if (d->has_body_force && (rc = feahip_set_body_force(ctx, d->body_force))) return rc;
+  return (d->damping_alpha != 0 || d->damping_beta != 0) ? feahip_set_damping(ctx, d->damping_alpha, d->damping_beta) : 0;
 }
 
 int fea_deck_create_solver(const fea_deck *d, int device, feahip_ctx **ctx, char *errbuf, int errlen)

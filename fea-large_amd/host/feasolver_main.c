@@ -62,6 +62,8 @@ int main(int argc, char **argv)
     fea_deck_free(&deck);
     return 1;
   }
+  if (deck.has_dynamics && (deck.damping_alpha != 0 || deck.damping_beta != 0))
+    printf("Damping: alpha %.17g, beta %.17g\n", deck.damping_alpha, deck.damping_beta);
   cap = deck.load_increments_count > 0 ? deck.load_increments_count : 1;
   steps = (fea_step_snapshot *)calloc((size_t)cap, sizeof *steps);
   /* (arc-length :max N) with N > 0 and surface loads: path following instead of load control */

@@ -16,6 +16,7 @@
  */
 #include <ctype.h>
 #include <errno.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -596,6 +597,13 @@ static int read_list(reader *r, fea_deck *d)
     if (!(d->dynamics_gamma >= 0)) return fail(r, "dynamics :gamma must not be negative");
     if (need_num(r, a, na, "density", &d->density)) return -1;
     if (!(d->density > 0)) return fail(r, "dynamics :density must be positive");
+    d->damping_alpha = d->damping_beta = 0;
+    if (attr_get(a, na, "damping-alpha") && need_num(r, a, na, "damping-alpha", &d->damping_alpha)) return -1;
+    if (attr_get(a, na, "damping-beta") && need_num(r, a, na, "damping-beta", &d->damping_beta)) return -1;
+    if (!(d->damping_alpha >= 0 && d->damping_alpha < HUGE_VAL) || !(d->damping_beta >= 0 && d->damping_beta < HUGE_VAL))
+      return fail(r, "dynamics :damping-alpha and :damping-beta must be finite and not negative");
+    if (d->dynamics_explicit && d->damping_beta != 0)
+      return fail(r, "dynamics :scheme explicit takes mass-proportional damping only: :damping-beta must be 0");
     d->has_dynamics = 1;
   } else if (ieq(head, "results")) {                          /* no counterpart in the reference */
     static const char *key[3] = {"nodal-stress", "energy", "reactions"};
@@ -774,6 +782,8 @@ int fea_deck_save(const char *path, const fea_deck *d)
             d->dynamics_dt, d->dynamics_beta, d->dynamics_gamma, d->dynamics_dlambda, d->density);
   if (d->has_dynamics && d->dynamics_explicit)
     fprintf(f, " :scheme explicit :safety %.17g :restep %d", d->dynamics_safety, d->dynamics_restep);
+  if (d->has_dynamics && d->damping_alpha != 0) fprintf(f, " :damping-alpha %.17g", d->damping_alpha);
+  if (d->has_dynamics && d->damping_beta != 0) fprintf(f, " :damping-beta %.17g", d->damping_beta);
   if (d->has_dynamics) fprintf(f, ")");
   if (d->results_nodal_stress || d->results_energy || d->results_reactions)   /* written only when asked for */
     fprintf(f, "\n   (results :nodal-stress %s :energy %s :reactions %s)", d->results_nodal_stress ? "t" : "nil",

@@ -418,6 +418,48 @@ int feahip_consistent_acceleration(feahip_ctx *ctx, int solver_type, double tole
 int feahip_solve_dynamic(feahip_ctx *ctx, int n_steps, double dt, double beta, double gamma, double dlambda,
                          int max_newton, double desired_tolerance, int solver_type, double solver_tolerance,
                          int solver_max_iter, double *tol_log, int tol_log_cap, int *its_log, int *steps_done);
+/* ---- Rayleigh damping ------------------------------------------------------
+ * feahip_set_damping gives the context the viscous damping
+ *   C = alpha M + beta_k K_d.
+ * M is the mass of the loop that runs: the consistent mass of feahip_set_mass
+ * in feahip_solve_dynamic and feahip_consistent_acceleration, the HRZ-lumped
+ * mass in feahip_solve_explicit.  It is not copied: a later feahip_set_mass is
+ * followed by the alpha part.  K_d is a SNAPSHOT: the plain tangent at the x
+ * of this call (no contact term, unmasked), assembled once and copied into a
+ * store of its own over the owned rows -- allocated only when beta_k > 0, as
+ * large as K.  After such a call K holds that plain assembly and counts as
+ * changed; f, u and x are untouched.  feahip_set_materials leaves K_d alone.
+ * A constant C keeps the damping linear: with K_d = K(X0), every undamped mode
+ * omega gets zeta = (alpha / omega + beta_k omega) / 2.
+ *   feahip_solve_dynamic: with c1 = gamma / (beta dt) and w = vt + c1 (x - xt)
+ *   the residual is f - a0 M (x - xt) - C w, the matrix
+ *   K + (a0 + c1 alpha) M + c1 beta_k K_d.
+ *   feahip_consistent_acceleration: M a = lambda F_ext - T - C v.
+ *   feahip_solve_explicit: a = (f / ml - alpha vh) / (1 + alpha dt / 2), the
+ *   central-difference scheme with the centred velocity; its stability limit
+ *   is 2 / omega_max for every alpha >= 0, so feahip_stable_step is unchanged.
+ *   A context with beta_k > 0 is refused there (FEAHIP_EINVAL).
+ * Static solves, the arc length, modes and buckling ignore the damping.
+ * (0, 0) clears it and frees the store; a context without damping launches
+ * nothing new.  A negative or non-finite coefficient is FEAHIP_EINVAL and
+ * leaves the context as it was.  The call is per context, not collective: a
+ * rank assembles its own rows (x current on its halo nodes, as for every
+ * assembly).  After a change of the row shard every entry that needs K_d
+ * returns FEAHIP_ESTATE until the damping is set again; alpha > 0 without a
+ * mass is FEAHIP_ESTATE at the use.                                          */
+int feahip_set_damping(feahip_ctx *ctx, double alpha, double beta_k);
+int feahip_get_damping(feahip_ctx *ctx, double *alpha, double *beta_k);
+/* y = C v, host vectors [3N] in the caller's dof order (test hook, the
+ * conventions of feahip_mass_spmv).  FEAHIP_ESTATE without damping.          */
+int feahip_damping_spmv(feahip_ctx *ctx, const double *v, double *y);
+/* Host only: the two coefficients that give the damping ratios zeta1, zeta2 at
+ * the circular frequencies omega1, omega2:
+ *   alpha  = 2 w1 w2 (z1 w2 - z2 w1) / (w2^2 - w1^2),
+ *   beta_k = 2 (z2 w2 - z1 w1) / (w2^2 - w1^2).
+ * FEAHIP_EINVAL for equal or non-positive frequencies.  A negative result (the
+ * two ratios cannot both be met with C >= 0) is returned as it is;
+ * feahip_set_damping refuses it.                                             */
+int feahip_host_rayleigh(double omega1, double zeta1, double omega2, double zeta2, double *alpha, double *beta_k);
 
 /* Host-only (no device): resolve faces to (owning element, local face) exactly
  * as feahip_set_surface_loads does; returns FEAHIP_EINVAL with the index of
@@ -1173,7 +1215,10 @@ int feahip_sync(feahip_ctx *ctx);
  * current nodes (refused where feahip_solve_buckling is; no mass needed);
  * 20 k_contact alone, K and f (refused on a context without contact; it adds
  * K_c and F_c into the K and f in force on every launch: both are garbage
- * afterwards, assemble again).                                              */
+ * afterwards, assemble again); 21 k_damp_add (K += M + K_d, refused without a
+ * damping with beta_k > 0) and 22 k_damp_residual on the vectors in force with
+ * a0 = c1 = 1 (refused without damping; both need a mass and leave K or f
+ * garbage as 8 and 9 do).                                                   */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
