@@ -472,6 +472,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->damping.release();
   c->results.release();
   c->modal.release();
+  c->response.release();
   c->buckling.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
@@ -1587,6 +1588,138 @@ extern "C" int feahip_modal_deflate(feahip_ctx *c, int n_locked, const double *q
   return FEAHIP_OK;
 }
 
+// ---- frequency response by mode superposition on the locked store (kernels_response.hip) -------------------------------
+extern "C" int feahip_response_set_basis(feahip_ctx *c, int n, const double *lam, const double *phi)
+{
+  CTX_GUARD(c);
+  if (!lam || !phi) return FEAHIP_EINVAL;
+  if (n < 1 || n > FEA_MODAL_MAX_LOCKED) { c->err = "response_set_basis: n must be in [1, 64]"; return FEAHIP_EINVAL; }
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(lam[k])) { c->err = "response_set_basis: lam is not finite"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = modal_ready(c, "response_set_basis")) || (rc = ensure_modal(c)) || (rc = ensure_locked(c, n))) return rc;
+  ModalState &S = c->modal;
+  S.have = false;                                                    // the block vectors are scratch here
+  const size_t nd = (size_t)c->ndof, n8 = nd * FEA_MODAL_COLS;
+  double *v = S.d_v;                                                 // W <- the host layout, X <- a panel, zero on the prescribed dofs
+  for (int p = 0; p * FEA_MODAL_COLS < n; ++p) {
+    FEA_HIP_CHECK(c, hipMemsetAsync(v + n8, 0, sizeof(double) * n8, c->stream));
+    for (int k = 0; k < FEA_MODAL_COLS && p * FEA_MODAL_COLS + k < n; ++k)
+      if ((rc = set_node_vec(c, v + n8 + (size_t)k * nd, phi + ((size_t)p * FEA_MODAL_COLS + k) * nd))) return rc;
+    if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_response_mask8(c, v))) return rc;
+    FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
+  }
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < n; ++k) S.lock_order[k] = k;                   // column k holds the caller's pair k; read in ascending lam
+  std::stable_sort(S.lock_order, S.lock_order + n, [&](int x, int y) { return lam[x] < lam[y]; });
+  for (int k = 0; k < n; ++k) S.lam[k] = lam[S.lock_order[k]];
+  S.shift = 0.0;
+  S.n_locked = n;
+  ++S.lock_gen;
+  S.have_locked = true;
+  return FEAHIP_OK;
+}
+
+// the load held belongs to the modes held
+static int response_loaded(feahip_ctx *c, const char *who)
+{
+  if (!c->modal.have_locked) { c->err = std::string(who) + ": no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)"; return FEAHIP_ESTATE; }
+  if (!c->response.loaded || c->response.gen != c->modal.lock_gen) {
+    c->err = std::string(who) + ": no load held for these modes (feahip_response_load first)";
+    return FEAHIP_ESTATE;
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_load(feahip_ctx *c, const double *F, int static_correction, int solver_type, double tolerance,
+                                    int max_iterations, double *q, int *iters, double *resid)
+{
+  CTX_GUARD(c);
+  if (iters) *iters = 0;
+  if (resid) *resid = 0.0;
+  if (!F) { c->err = "response_load: null F"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = modal_ready(c, "response_load"))) return rc;
+  const ModalState &S = c->modal;
+  if (!S.have_locked) { c->err = "response_load: no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)"; return FEAHIP_ESTATE; }
+  if (static_correction) {
+    if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "response_load: unknown solver type"; return FEAHIP_EINVAL; }
+    if (max_iterations <= 0) { c->err = "response_load: max_iterations must be positive"; return FEAHIP_EINVAL; }
+    if (S.shift > 0.0) { c->err = "response_load: the modes come from a solve with a shift, a body whose K may be singular: no static correction"; return FEAHIP_EINVAL; }
+    for (int k = 0; k < S.n_locked; ++k)
+      if (!(S.lam[k] > 0.0)) { c->err = "response_load: lam of mode " + std::to_string(k + 1) + " is not positive: no static correction"; return FEAHIP_EINVAL; }
+  }
+  std::vector<double> tmp((size_t)c->ndof);
+  for (int a = 0; a < c->N; ++a)
+    for (int j = 0; j < 3; ++j) {
+      const double f = F[(size_t)a * 3 + j];
+      if (!std::isfinite(f)) { c->err = "response_load: F is not finite"; return FEAHIP_EINVAL; }
+      tmp[(size_t)lib_id(c, a) * 3 + j] = f;
+    }
+  return response_load(c, tmp.data(), static_correction, solver_type, tolerance, max_iterations, q, iters, resid);
+}
+
+extern "C" int feahip_get_response_static(feahip_ctx *c, double *u_s)
+{
+  CTX_GUARD_NOK(c);
+  if (!u_s) return FEAHIP_EINVAL;
+  const int rc = response_loaded(c, "get_response_static");
+  return rc ? rc : get_node_vec(c, c->response.d_us, u_s);
+}
+
+// [3N] of T in library ids into the caller's dof order
+template <class T>
+static void to_caller_dofs(const feahip_ctx *c, const T *lib, T *out)
+{
+  for (int a = 0; a < c->N; ++a)
+    for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = lib[(size_t)lib_id(c, a) * 3 + j];
+}
+
+extern "C" int feahip_response_sweep(feahip_ctx *c, int n_freq, const double *omega, double alpha, double beta_k,
+                                     const double *zeta, double *peak, int *peak_at, int n_probe, const int *probe_dof,
+                                     double *probe_re, double *probe_im)
+{
+  CTX_GUARD_NOK(c);
+  if (!omega || !peak || !peak_at) { c->err = "response_sweep: null omega, peak or peak_at"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = response_loaded(c, "response_sweep"))) return rc;
+  if (n_freq < 1 || n_freq > FEA_RESPONSE_MAX_FREQ) { c->err = "response_sweep: n_freq must be in [1, 4096]"; return FEAHIP_EINVAL; }
+  if (n_probe < 0 || n_probe > 64) { c->err = "response_sweep: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
+  if (n_probe > 0 && (!probe_dof || !probe_re || !probe_im)) { c->err = "response_sweep: null probe arrays"; return FEAHIP_EINVAL; }
+  int probe[64];
+  for (int r = 0; r < n_probe; ++r) {
+    if (probe_dof[r] < 0 || probe_dof[r] >= c->ndof) { c->err = "response_sweep: probe dof outside [0, 3N)"; return FEAHIP_EINVAL; }
+    probe[r] = 3 * lib_id(c, probe_dof[r] / 3) + probe_dof[r] % 3;
+  }
+  std::vector<double> pk((size_t)c->ndof);
+  std::vector<int> at((size_t)c->ndof);
+  if ((rc = response_sweep(c, false, n_freq, omega, alpha, beta_k, zeta, pk.data(), at.data(), n_probe, probe, probe_re, probe_im))) return rc;
+  to_caller_dofs(c, pk.data(), peak);
+  to_caller_dofs(c, at.data(), peak_at);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_field(feahip_ctx *c, double omega, double alpha, double beta_k, const double *zeta, double *re,
+                                     double *im)
+{
+  CTX_GUARD_NOK(c);
+  if (!re || !im) { c->err = "response_field: null re or im"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = response_loaded(c, "response_field"))) return rc;
+  std::vector<double> a((size_t)c->ndof), b((size_t)c->ndof);
+  if ((rc = response_sweep(c, true, 1, &omega, alpha, beta_k, zeta, a.data(), b.data(), 0, nullptr, nullptr, nullptr))) return rc;
+  to_caller_dofs(c, a.data(), re);
+  to_caller_dofs(c, b.data(), im);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_host_response_coefficients(int n_modes, const double *lam, const double *q, int n_freq, const double *omega,
+                                                 double alpha, double beta_k, const double *zeta, int static_correction,
+                                                 double *coef)
+{
+  return response_coefficients(n_modes, lam, q, nullptr, n_freq, omega, alpha, beta_k, zeta, static_correction, coef, nullptr);
+}
+
 extern "C" int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const double *gram_k, double *theta, double *coef)
 {
   if (!gram_m || !gram_k || !theta || !coef || (n_dirs != 8 && n_dirs != 16 && n_dirs != 24)) return FEAHIP_EINVAL;
@@ -2025,6 +2158,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     int rk;
     if ((rk = solve2_refused(c, what == 18 ? "time_kernel(18)" : "time_kernel(19)")) || (rk = geom_assemble(c))) return rk;
   }
+  if (what == 23 || what == 24) {                      // the table, the store and f as the last response_sweep left them
+    const int rk = response_loaded(c, what == 23 ? "time_kernel(23)" : "time_kernel(24)");
+    if (rk) return rk;
+    if (c->response.swept_freq == 0) { c->err = "time_kernel: no sweep made yet (feahip_response_sweep first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2047,6 +2185,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 20: return launch_contact(c, true, true, c->d_f);
     case 21: return launch_damp_add(c, 1.0, 1.0);
     case 22: return launch_damp_residual(c, 1.0, 1.0);
+    case 23: case 24: return time_response_kernel(c, what);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

@@ -515,6 +515,9 @@ struct ModalState {
   int lock_panels = 0;                 // panels allocated (once, for the n_modes asked; a larger request reallocates)
   int n_locked = 0;                    // modes in the store
   int lock_order[64] = {0};            // mode j of the ascending lambda is column lock_order[j] of the store
+  double lam[64] = {0};                // the UNSHIFTED lambda of mode j, ascending (the response entries read it)
+  double shift = 0;                    // the shift of the solve that filled the store (0: feahip_response_set_basis)
+  int lock_gen = 0;                    // counts the fillings of the store: a response load belongs to one of them
   bool have_locked = false;            // the store holds the modes of a locked solve (feahip_get_locked_modes)
   bool have_buckling = false;          // X holds the buckling modes of feahip_solve_buckling (feahip_get_buckling_modes)
   // the sharded solve (feahip_solve_modes_sharded, feahip_group_spmm_km): nothing of it exists until one of them is called
@@ -526,6 +529,22 @@ struct ModalState {
   bool have_sharded = false;           // X holds, on the rows [sh_row0, sh_row1), the modes of a finished sharded solve
   int sh_row0 = -1, sh_row1 = -1;
   void release() { dev_free({d_v, d_part, d_small, d_lock, d_lpart, d_lcoef, d_bsend, d_brecv, d_key}); *this = ModalState(); }
+};
+
+// frequency response by mode superposition (kernels_response.hip): nothing of it exists until a response entry is called.
+// It reads the locked store of ModalState (Q's panels, lock_order, lam, shift) and owns what one load adds to it.
+struct ResponseState {
+  double *d_us = nullptr;              // [3N] the static correction u_s in library ids; zero without one
+  double *d_part = nullptr;            // [64][FEA_RED_BLOCKS] per-workgroup partial sums of Q' F, by store column
+  double *d_q = nullptr;               // [64] Q' F by store column
+  double *d_coef = nullptr;            // [FEA_RESPONSE_MAX_FREQ][2][64] the coefficient table of a sweep: re, im by store column
+  double *d_out = nullptr;             // [2][3N]: peak and (as int) peak_at of a sweep, or re and im of a field
+  double q[64] = {0};                  // q_k of the ascending mode k
+  bool loaded = false;                 // a load is held ...
+  int gen = -1;                        // ... for the filling ModalState::lock_gen == gen of the store
+  int correction = 0;                  // it was made with the static correction
+  int swept_freq = 0;                  // frequencies in d_coef from the last sweep (feahip_time_kernel 23)
+  void release() { dev_free({d_us, d_part, d_q, d_coef, d_out}); *this = ResponseState(); }
 };
 
 // linear buckling (kernels_buckling.hip): nothing of it exists until feahip_solve_buckling (or one of its hooks,
@@ -681,6 +700,7 @@ struct feahip_ctx {
   DampingState damping;
   ResultState results;
   ModalState modal;
+  ResponseState response;
   BucklingState buckling;
 };
 
@@ -808,6 +828,20 @@ struct Lobpcg {
   // which counts the steps over all calls, reaches max_it.  One of LOBPCG_*, or an error code
   int run(int want, int max_it, int *it);
 };
+// kernels_response.hip -- frequency response by mode superposition on the locked store
+int launch_response_mask8(feahip_ctx *c, double *d_v8);                 // a block vector [3N][8]: zero on the prescribed dofs
+// the coefficient table [n_freq][2][64] (re, im; zero past n_modes) of mode k at column order[k] (null: k); host only.
+// FEAHIP_EINVAL and *why for a negative or non-finite input and for a coefficient that is not finite
+int response_coefficients(int n_modes, const double *lam, const double *q, const int *order, int n_freq, const double *omega,
+                          double alpha, double beta, const double *zeta, int correction, double *coef, std::string *why);
+// F (library ids, host) projected on the modes held and, with correction, K u_s = F solved; q[n_locked] ascending
+int response_load(feahip_ctx *c, const double *h_F, int correction, int solver_type, double tol, int max_it, double *q,
+                  int *iters, double *resid);
+// one launch of k_response_sweep over the table of n_freq frequencies: peak / peak_at, or (field, n_freq = 1) re / im,
+// [3N] in library ids; the curves of the probe dofs (library ids) on the host, [n_probe][n_freq]
+int response_sweep(feahip_ctx *c, bool field, int n_freq, const double *omega, double alpha, double beta, const double *zeta,
+                   double *h_out0, void *h_out1, int n_probe, const int *probe, double *probe_re, double *probe_im);
+int time_response_kernel(feahip_ctx *c, int what);                      // feahip_time_kernel 23 (sweep), 24 (projection)
 // kernels_buckling.hip -- K_sigma as one double per block, and the lowest eigenpairs of K_sigma phi = nu K phi
 int geom_assemble(feahip_ctx *c);                                       // buckling.d_kg at the current nodes
 int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters);

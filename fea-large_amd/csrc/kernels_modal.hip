@@ -1032,6 +1032,9 @@ int modal_solve_locked(feahip_ctx *c, int n_modes, double shift, double tol, int
     for (int j = 0; j < locked; ++j) { S.lock_order[j] = j; lam[j] = lambda[j]; res[j] = resid ? resid[j] : 0.0; }
     std::stable_sort(S.lock_order, S.lock_order + locked, [&](int x, int y) { return lam[x] < lam[y]; });
     for (int j = 0; j < locked; ++j) { lambda[j] = lam[S.lock_order[j]]; if (resid) resid[j] = res[S.lock_order[j]]; }
+    for (int j = 0; j < locked; ++j) S.lam[j] = lambda[j];              // kept, unshifted, for the response entries
+    S.shift = shift;
+    ++S.lock_gen;
     S.n_locked = locked;
     S.have_locked = true;                                               // the pairs locked so far stay readable
     if (iters) *iters = it;

@@ -167,6 +167,12 @@ ABI = {
     "feahip_get_locked_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_get_locked_count": [C.c_void_p, _ip],
     "feahip_modal_deflate": [C.c_void_p, C.c_int, _dp, _dp, _dp],
+    "feahip_response_set_basis": [C.c_void_p, C.c_int, _dp, _dp],
+    "feahip_response_load": [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp],
+    "feahip_get_response_static": [C.c_void_p, _dp],
+    "feahip_response_sweep": [C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _ip, C.c_int, _ip, _dp, _dp],
+    "feahip_response_field": [C.c_void_p, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp],
+    "feahip_host_response_coefficients": [C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp],
     "feahip_solve_buckling": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
     "feahip_get_buckling_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_geometric_spmv": [C.c_void_p, _dp, _dp],
@@ -174,6 +180,7 @@ ABI = {
 }
 MODAL_COLS = 8                                          # FEA_MODAL_COLS of include/fea_hip.h
 MODAL_MAX_LOCKED = 64                                   # FEA_MODAL_MAX_LOCKED
+RESPONSE_MAX_FREQ = 4096                                # FEA_RESPONSE_MAX_FREQ
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
 COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
@@ -225,6 +232,8 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("harmonic_count", C.c_int), ("harmonic_from", C.c_double), ("harmonic_to", C.c_double),
+        ("harmonic_zeta", C.c_double), ("harmonic_static", C.c_int),
         ("damping_alpha", C.c_double), ("damping_beta", C.c_double),
         ("contact_faces_count", C.c_int), ("contact_nodes_per_face", C.c_int), ("contact_nodes", _ip),
         ("contact_obstacles_count", C.c_int), ("contact_kind", _ip), ("contact_geom", _dp),
@@ -313,6 +322,23 @@ def host_buckling_factor(nu):
     if lib.feahip_host_buckling_factor(len(nu), _d(nu), _d(factor)) != 0:
         raise FeaHipError("feahip_host_buckling_factor failed")
     return factor
+
+
+def host_response_coefficients(lam, q, omega, alpha=0.0, beta=0.0, zeta=None, static_correction=True):
+    """feahip_host_response_coefficients (no device): the complex table a[n_freq][64] of a sweep, a_k = q_k H_k or, with
+    the correction, q_k (H_k - 1 / lam_k), H_k = 1 / (lam_k - w^2 + i w (alpha + beta lam_k + 2 zeta_k sqrt(lam_k))); zero
+    past the modes given.  Raises where the sweep refuses (a negative input, a coefficient that is not finite)."""
+    lam, q = np.ascontiguousarray(lam, dtype=np.float64), np.ascontiguousarray(q, dtype=np.float64)
+    omega = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
+    z = None if zeta is None else np.ascontiguousarray(zeta, dtype=np.float64)
+    assert lam.shape == q.shape and lam.ndim == 1 and (z is None or z.shape == lam.shape)
+    coef = np.zeros((len(omega), 2, MODAL_MAX_LOCKED))
+    rc = load_library().feahip_host_response_coefficients(len(lam), _d(lam), _d(q), len(omega), _d(omega), float(alpha),
+                                                          float(beta), None if z is None else _d(z), int(bool(static_correction)),
+                                                          _d(coef))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_response_coefficients refused its input ({rc})")
+    return coef[:, 0, :] + 1j * coef[:, 1, :]
 
 
 def host_rayleigh(omega1, zeta1, omega2, zeta2):
@@ -457,6 +483,24 @@ class Deck:
             raise ValueError("modal_shift needs modal_modes or modal_count")
         if (self.modal_modes or self.modal_count) and self.density is None:
             raise ValueError("modal_modes needs a density")
+        # (harmonic :from f0 :to f1 :count n :zeta z :static-correction t): the frequency sweep feasolver_hip makes on the
+        # locked modes after the modal run, n linearly spaced frequencies in Hz under the surface load of the state reached
+        self.harmonic_count = int(kw.get("harmonic_count", 0))
+        self.harmonic_from = float(kw.get("harmonic_from", 0.0))
+        self.harmonic_to = float(kw.get("harmonic_to", 0.0))
+        self.harmonic_zeta = float(kw.get("harmonic_zeta", 0.0))
+        self.harmonic_static = bool(kw.get("harmonic_static", True))
+        if not 0 <= self.harmonic_count <= RESPONSE_MAX_FREQ:
+            raise ValueError("harmonic_count: 1 to 4096")
+        if self.harmonic_count:
+            if not (0.0 <= self.harmonic_from <= self.harmonic_to < np.inf):
+                raise ValueError("harmonic_from and harmonic_to: 0 <= from <= to, finite")
+            if not (0.0 <= self.harmonic_zeta < np.inf):
+                raise ValueError("harmonic_zeta: finite and not negative")
+            if not (self.modal_count or self.modal_shift):
+                raise ValueError("harmonic_count needs the locked modes: modal_count or modal_shift")
+            if self.harmonic_static and self.modal_shift:
+                raise ValueError("harmonic_static (the static correction) and a non-zero modal_shift exclude each other")
         # (buckling :modes N :tolerance t :max M): the load factors feasolver_hip computes after its last step
         self.buckling_modes = int(kw.get("buckling_modes", 0))
         self.buckling_tolerance = float(kw.get("buckling_tolerance", 1e-8))
@@ -514,6 +558,9 @@ class Deck:
                 **(dict(modal_modes=fd.modal_modes, modal_count=fd.modal_count, modal_shift=fd.modal_shift,
                         modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
                    if fd.modal_modes or fd.modal_count else {}),
+                **(dict(harmonic_count=fd.harmonic_count, harmonic_from=fd.harmonic_from, harmonic_to=fd.harmonic_to,
+                        harmonic_zeta=fd.harmonic_zeta, harmonic_static=bool(fd.harmonic_static))
+                   if fd.harmonic_count else {}),
                 **(dict(buckling_modes=fd.buckling_modes, buckling_tolerance=fd.buckling_tolerance,
                         buckling_max=fd.buckling_max) if fd.buckling_modes else {}))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
@@ -568,6 +615,9 @@ class Deck:
         fd.modal_modes = int(getattr(self, "modal_modes", 0))
         fd.modal_count, fd.modal_shift = int(getattr(self, "modal_count", 0)), float(getattr(self, "modal_shift", 0.0))
         fd.modal_tolerance, fd.modal_max = float(getattr(self, "modal_tolerance", 1e-8)), int(getattr(self, "modal_max", 1000))
+        if getattr(self, "harmonic_count", 0):
+            fd.harmonic_count, fd.harmonic_from, fd.harmonic_to = int(self.harmonic_count), float(self.harmonic_from), float(self.harmonic_to)
+            fd.harmonic_zeta, fd.harmonic_static = float(self.harmonic_zeta), int(bool(self.harmonic_static))
         if len(self.contact_faces) and len(self.contact_obstacles):
             # (kept on the deck: the struct borrows the arrays)
             self._contact_kind, self._contact_geom = obstacle_arrays(self.contact_obstacles)
@@ -1013,6 +1063,59 @@ class FeaSolver:
         out = np.zeros_like(x8)
         self._chk(self._lib.feahip_modal_deflate(self._ctx, len(q), _d(q), _d(x8), _d(out)))
         return out
+
+    # ---- frequency response by mode superposition on the locked modes -----------
+    def response_set_basis(self, lam, phi):
+        """feahip_response_set_basis: installs the caller's M-orthonormal pairs lam[n], phi[n][3N] (n <= 64) into the locked
+        store, as the modes of a solve with shift 0 (locked_modes returns them ascending in lam)."""
+        lam, phi = np.ascontiguousarray(lam, dtype=np.float64), np.ascontiguousarray(phi, dtype=np.float64)
+        assert lam.ndim == 1 and phi.shape == (len(lam), self.ndof)
+        self._chk(self._lib.feahip_response_set_basis(self._ctx, len(lam), _d(lam), _d(phi)))
+
+    def response_load(self, F, static_correction=True, solver_type=None, tolerance=None, max_iterations=None):
+        """feahip_response_load: the participations q_k = phi_k' F of the real load F[3N] on the modes held and, with
+        static_correction, K u_s = F by the context's PCG (the deck's solver settings where not given).  Returns
+        (q[n_locked] ascending in lam, PCG iterations, PCG residual).  K, f and u hold other values afterwards."""
+        d = self.deck
+        F = np.ascontiguousarray(F, dtype=np.float64).reshape(self.ndof)
+        q, it, res = np.zeros(MODAL_MAX_LOCKED), C.c_int(0), C.c_double(0)
+        self._chk(self._lib.feahip_response_load(
+            self._ctx, _d(F), int(bool(static_correction)), d.solver_type if solver_type is None else solver_type,
+            d.solver_tolerance if tolerance is None else tolerance,
+            d.solver_max_iter if max_iterations is None else max_iterations, _d(q), C.byref(it), C.byref(res)))
+        return q[:self.locked_count()].copy(), it.value, res.value
+
+    def response_static(self):
+        """feahip_get_response_static: u_s[3N] of the load held (zero without the correction)."""
+        u = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_get_response_static(self._ctx, _d(u)))
+        return u
+
+    def _zeta(self, zeta):
+        if zeta is None:
+            return None, None
+        z = np.ascontiguousarray(np.broadcast_to(np.asarray(zeta, dtype=np.float64), (self.locked_count(),)))
+        return z, _d(z)
+
+    def response_sweep(self, omega, alpha=0.0, beta=0.0, zeta=None, probes=()):
+        """feahip_response_sweep over the circular frequencies omega: (peak[3N] = max_j |u_i(w_j)|, peak_at[3N] = the
+        lowest j that attains it, the complex curves [n_probe][n_freq] of the probe dofs 3 node + axis).  zeta: one
+        ratio for all modes, one per mode, or None."""
+        omega = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
+        pr = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        peak, at = np.zeros(self.ndof), np.zeros(self.ndof, dtype=np.int32)
+        re, im = np.zeros((len(pr), len(omega))), np.zeros((len(pr), len(omega)))
+        z, zp = self._zeta(zeta)
+        self._chk(self._lib.feahip_response_sweep(self._ctx, len(omega), _d(omega), float(alpha), float(beta), zp, _d(peak),
+                                                  _i(at), len(pr), _i(pr), _d(re), _d(im)))
+        return peak, at, re + 1j * im
+
+    def response_field(self, omega, alpha=0.0, beta=0.0, zeta=None):
+        """feahip_response_field: the complex amplitude u[3N] at one circular frequency."""
+        re, im = np.zeros(self.ndof), np.zeros(self.ndof)
+        z, zp = self._zeta(zeta)
+        self._chk(self._lib.feahip_response_field(self._ctx, float(omega), float(alpha), float(beta), zp, _d(re), _d(im)))
+        return re + 1j * im
 
     # ---- linear buckling ---------------------------------------------------
     def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):

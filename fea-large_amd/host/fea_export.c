@@ -205,6 +205,55 @@ int fea_modal_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *ms
   return 0;
 }
 
+int fea_harmonic_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
+{
+  FILE *log = (FILE *)log_, *f;
+  const int n = d->harmonic_count, nd = 3 * d->nodes_count;
+  const double two_pi = 6.283185307179586;
+  double *F, *peak, *omega, zeta[FEA_MODAL_MAX_LOCKED], best = -1.0;
+  int *at, i, k, m = 0, rc, any = 0, best_dof = 0;
+  if (n <= 0) return 0;
+  if ((rc = feahip_get_locked_count(ctx, &m))) return rc;
+  F = (double *)malloc(sizeof(double) * 2 * (size_t)nd);
+  omega = (double *)malloc(sizeof(double) * (size_t)n);
+  at = (int *)malloc(sizeof(int) * (size_t)nd);
+  if (!F || !omega || !at) { free(F); free(omega); free(at); return FEAHIP_ENOMEM; }
+  peak = F + nd;
+  for (k = 0; k < n; ++k)                               /* n linearly spaced frequencies in Hz, the ends included */
+    omega[k] = two_pi * (n > 1 ? d->harmonic_from + (d->harmonic_to - d->harmonic_from) * k / (n - 1) : d->harmonic_from);
+  for (k = 0; k < FEA_MODAL_MAX_LOCKED; ++k) zeta[k] = d->harmonic_zeta;
+  rc = feahip_get_surface_forces(ctx, F);
+  for (i = 0; !rc && i < nd; ++i) any |= F[i] != 0.0;
+  if (!rc && !any) {
+    if (log) fprintf(log, "Harmonic: the surface load at the state reached is zero, nothing to sweep\n");
+    rc = FEAHIP_EINVAL;
+  }
+  if (!rc && log)
+    fprintf(log, "Harmonic: %d frequencies %.17g .. %.17g Hz, %d modes, static correction %s\n", n, d->harmonic_from,
+            d->harmonic_to, m, d->harmonic_static ? "on" : "off");
+  if (!rc) rc = feahip_response_load(ctx, F, d->harmonic_static, d->solver_type, d->solver_tolerance, d->solver_max_iter, NULL, NULL, NULL);
+  if (!rc) rc = feahip_response_sweep(ctx, n, omega, d->has_dynamics ? d->damping_alpha : 0.0, d->has_dynamics ? d->damping_beta : 0.0,
+                                      d->harmonic_zeta > 0 ? zeta : NULL, peak, at, 0, NULL, NULL, NULL);
+  if (rc) { free(F); free(omega); free(at); return rc; }
+  for (i = 0; i < nd; ++i) if (peak[i] > best) { best = peak[i]; best_dof = i; }
+  if (log)
+    fprintf(log, "Harmonic peak: |u| = %.17g at f = %.17g Hz, node %d dof %d\n", best, omega[at[best_dof]] / two_pi,
+            best_dof / 3 + 1, best_dof % 3);
+  if (msh_path) {
+    if (!(f = fopen(msh_path, "a"))) { free(F); free(omega); free(at); return FEAHIP_EINVAL; }
+    fprintf(f, "$NodeData\n1\n\"Harmonic peak amplitude\"\n1\n%f\n3\n0\n3\n%d\n", omega[at[best_dof]] / two_pi, d->nodes_count);
+    for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %.9e %.9e %.9e\n", i + 1, peak[3 * i], peak[3 * i + 1], peak[3 * i + 2]);
+    fprintf(f, "$EndNodeData\n");
+    fprintf(f, "$NodeData\n1\n\"Harmonic peak frequency\"\n1\n%f\n3\n0\n3\n%d\n", omega[at[best_dof]] / two_pi, d->nodes_count);
+    for (i = 0; i < d->nodes_count; ++i)
+      fprintf(f, "%d %.9e %.9e %.9e\n", i + 1, omega[at[3 * i]] / two_pi, omega[at[3 * i + 1]] / two_pi, omega[at[3 * i + 2]] / two_pi);
+    fprintf(f, "$EndNodeData\n");
+    fclose(f);
+  }
+  free(F); free(omega); free(at);
+  return 0;
+}
+
 int fea_buckling_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   FILE *log = (FILE *)log_, *f;

@@ -91,6 +91,18 @@ typedef struct fea_deck {
    * to the .msh file; :energy and :reactions add one log line each per finished step.  Written by fea_deck_save only
    * when one of them is set; without the section the file and the log are what they were                        */
   int results_nodal_stress, results_energy, results_reactions;
+  /* frequency response, optional: (harmonic :from f0 :to f1 :count n :zeta z :static-correction t) inside (solution ...):
+   * n <= FEA_RESPONSE_MAX_FREQ linearly spaced frequencies in Hz, 0 <= f0 <= f1, a modal damping ratio z >= 0 for every
+   * mode (:zeta 0 and :static-correction t where absent).  It uses the locked store, so it needs (modal ...) with :count or
+   * :shift, and the static correction excludes a non-zero :shift: load errors otherwise.  After the modal run
+   * feasolver_hip calls feahip_response_load with the surface load of the state reached and feahip_response_sweep with
+   * :damping-alpha and :damping-beta of (dynamics ...) (fea_harmonic_run), logs two lines and appends two $NodeData
+   * sections to the .msh file.  Written by fea_deck_save only when n > 0: a deck without the section is read, run and
+   * written as before.  The five fields are the newest of the struct and stand in front of damping_alpha, whose place
+   * (with everything behind it) the host tests pin                                                                 */
+  int harmonic_count;
+  double harmonic_from, harmonic_to, harmonic_zeta;
+  int harmonic_static;
   /* Rayleigh damping, optional: :damping-alpha a :damping-beta b inside (dynamics ...), both >= 0 and 0 where absent:
    * C = a M + b K_d, K_d the tangent at the reference configuration (fea_deck_create_solver calls feahip_set_damping
    * after the mass).  :scheme explicit with a non-zero :damping-beta is a load error (the explicit loop takes the
@@ -234,6 +246,15 @@ int fea_export_gmsh(const char *filename, const fea_deck *deck,
  * $NodeData section "Mode k" per mode shape appended to that file, tagged with the frequency.  A solve that runs out
  * of steps is logged and its modes are written as they stand.  Returns 0, or a negative FEAHIP_E* code.        */
 int fea_modal_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
+
+/* The frequency sweep of a deck with (harmonic :count n ...), n > 0, right after fea_modal_run, on the locked modes that
+ * run left: the load is feahip_get_surface_forces at the state reached (FEAHIP_EINVAL when it is all zero),
+ * feahip_response_load with the deck's solver settings, then feahip_response_sweep over the n frequencies with the
+ * deck's :damping-alpha, :damping-beta and :zeta.  Log: "Harmonic: n frequencies f0 .. f1 Hz, m modes, static correction
+ * on|off" and "Harmonic peak: |u| = p at f = x Hz, node a dof j" (the largest peak of all dofs, the lowest dof among
+ * equals, node from 1, dof 0-2).  With msh_path not NULL two $NodeData sections of three components per node are
+ * appended: "Harmonic peak amplitude" and "Harmonic peak frequency" (Hz).  Returns 0, or a negative FEAHIP_E* code.  */
+int fea_harmonic_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 
 /* The buckling analysis of a deck with (buckling :modes N ...), N > 0, at the state the context is in:
  * feahip_solve_buckling, one log line per mode ("Buckling mode k: factor = f, nu = v") and, with msh_path not NULL, one

@@ -15,6 +15,9 @@
  * reaction sums in the log (fea_host.h).  A deck with (modal :modes N ...)
  * then gets its N lowest natural frequencies at the final state in the log
  * and the mode shapes in the file (feahip_solve_modes).  A deck with
+ * (harmonic ...) then gets the frequency sweep of its surface load on those
+ * modes: two log lines and the peak amplitude and peak frequency of every dof
+ * in the file (feahip_response_load, feahip_response_sweep).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid
@@ -89,6 +92,10 @@ int main(int argc, char **argv)
     } else if ((deck.modal_modes > 0 || deck.modal_count > 0) && (rc = fea_modal_run(&deck, ctx, stdout, msh))) {
       /* (modal :modes N ...): the natural frequencies at the state reached, the mode shapes behind the steps */
       fprintf(stderr, "feasolve error encountered: %s\n", feahip_last_error(ctx));
+      status = 1;
+    } else if (deck.harmonic_count > 0 && (rc = fea_harmonic_run(&deck, ctx, stdout, msh))) {
+      /* (harmonic ...): the frequency sweep on the locked modes the modal run left, before anything drops them */
+      fprintf(stderr, "feasolve error encountered: harmonic sweep refused or failed (%d): %s\n", rc, feahip_last_error(ctx));
       status = 1;
     } else if (deck.buckling_modes > 0 && (rc = fea_buckling_run(&deck, ctx, stdout, msh))) {
       /* (buckling :modes N ...): the load factors at the state reached, the mode shapes behind everything else */

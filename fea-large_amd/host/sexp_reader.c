@@ -640,6 +640,21 @@ static int read_list(reader *r, fea_deck *d)
       if (!(v >= 0 && v <= 2147483647.0) || v != (double)(int)v) return fail(r, "modal :max must be a non-negative integer");
       d->modal_max = (int)v;
     }
+  } else if (ieq(head, "harmonic")) {                         /* no counterpart in the reference */
+    if (need_num(r, a, na, "count", &v)) return -1;
+    if (!(v >= 1 && v <= FEA_RESPONSE_MAX_FREQ) || v != (double)(int)v) return fail(r, "harmonic :count must be an integer in [1, 4096]");
+    d->harmonic_count = (int)v;
+    if (need_num(r, a, na, "from", &d->harmonic_from)) return -1;
+    if (need_num(r, a, na, "to", &d->harmonic_to)) return -1;
+    if (!(d->harmonic_from >= 0 && d->harmonic_from <= d->harmonic_to && d->harmonic_to <= 1.7976931348623157e308))
+      return fail(r, "harmonic needs 0 <= :from <= :to, both finite");
+    d->harmonic_zeta = 0; d->harmonic_static = 1;
+    if (attr_get(a, na, "zeta") && need_num(r, a, na, "zeta", &d->harmonic_zeta)) return -1;
+    if (!(d->harmonic_zeta >= 0 && d->harmonic_zeta <= 1.7976931348623157e308)) return fail(r, "harmonic :zeta must be finite and not negative");
+    if ((s = attr_get(a, na, "static-correction"))) {
+      if (ieq(s, "nil") || ieq(s, "no") || ieq(s, "false")) d->harmonic_static = 0;
+      else if (!(ieq(s, "t") || ieq(s, "yes") || ieq(s, "true"))) return fail(r, "harmonic :static-correction takes t or nil");
+    }
   } else if (ieq(head, "buckling")) {                         /* no counterpart in the reference */
     if (need_num(r, a, na, "modes", &v)) return -1;
     if (!(v >= 1 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "buckling :modes must be an integer in [1, 8]");
@@ -727,6 +742,12 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
     if (rc == 0 && (deck->modal_modes > 0 || deck->modal_count > 0) && !deck->has_dynamics) {
       rc = -1; snprintf(r.err, sizeof r.err, "deck has (modal ...) but no density: add (dynamics :steps 0 :dt 1 :density rho)");
     }
+    if (rc == 0 && deck->harmonic_count > 0 && !(deck->modal_count > 0 || (deck->modal_modes > 0 && deck->modal_shift != 0.0))) {
+      rc = -1; snprintf(r.err, sizeof r.err, "deck has (harmonic ...) but no locked modes: add (modal :count N ...) or a :shift");
+    }
+    if (rc == 0 && deck->harmonic_count > 0 && deck->harmonic_static && deck->modal_shift != 0.0) {
+      rc = -1; snprintf(r.err, sizeof r.err, "harmonic :static-correction t and a non-zero modal :shift exclude each other");
+    }
   }
   if (rc) {
     if (errbuf) snprintf(errbuf, (size_t)errlen, "%s", r.err);
@@ -794,6 +815,9 @@ int fea_deck_save(const char *path, const fea_deck *d)
     if (d->modal_shift != 0.0) fprintf(f, " :shift %.17g", d->modal_shift);    /* (the old text without the new keys) */
     fprintf(f, ")");
   }
+  if (d->harmonic_count > 0)                                                   /* written only when asked for */
+    fprintf(f, "\n   (harmonic :from %.17g :to %.17g :count %d :zeta %.17g :static-correction %s)", d->harmonic_from,
+            d->harmonic_to, d->harmonic_count, d->harmonic_zeta, d->harmonic_static ? "t" : "nil");
   if (d->buckling_modes > 0)                                                   /* written only when asked for */
     fprintf(f, "\n   (buckling :modes %d :tolerance %.17g :max %d)", d->buckling_modes, d->buckling_tolerance, d->buckling_max);
   fprintf(f, ")\n");

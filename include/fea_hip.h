@@ -876,6 +876,111 @@ int feahip_get_locked_count(feahip_ctx *ctx, int *count);
  * modes held from either solve are dropped.                                   */
 int feahip_modal_deflate(feahip_ctx *ctx, int n_locked, const double *q, const double *x8, double *out8);
 
+/* ---- frequency response by mode superposition on the locked modes -------------
+ * The steady-state amplitude u(w) e^{iwt} under a harmonic load F e^{iwt}, F real,
+ * from the n_locked <= 64 M-orthonormal pairs (lam_k, phi_k) the locked store
+ * holds.  A context that never calls the entries below allocates and launches
+ * nothing for them.
+ *     q_k    = phi_k' F                                     (participation)
+ *     d_k    = alpha + beta_k lam_k + 2 zeta_k sqrt(max(lam_k, 0))
+ *     H_k(w) = 1 / (lam_k - w^2 + i w d_k)
+ *     u(w)   = u_s + sum_k phi_k a_k(w)
+ *   mode displacement (static_correction == 0):  u_s = 0,   a_k = q_k H_k
+ *   mode acceleration (static_correction != 0):  K u_s = F on the free dofs,
+ *                                                a_k = q_k (H_k - 1 / lam_k)
+ * K is the tangent at the current nodes, masked as feahip_apply_prescribed_bc
+ * with factor 0 masks it.  The three parts of d_k are additive; zeta (one ratio
+ * per mode, ascending lam) may be NULL, which means zero.  With all modes of the
+ * body the sum is the solution of (K - w^2 M + i w (alpha M + beta_k K)) u = F;
+ * with the lowest m the correction carries the static part of the modes left
+ * out, which is most of their share below the m-th frequency (DESIGN.md 21
+ * has the truncation errors measured).  No system in K - w^2 M is ever solved.
+ * The damping of feahip_set_damping is NOT read: its K_d is a snapshot at other
+ * nodes which these modes do not diagonalise.  alpha, beta_k and zeta are the
+ * caller's, per call.
+ *
+ * feahip_response_set_basis: installs the caller's pairs, lam[n] in any order
+ * and phi[n][3N] in the caller's dof order, M-orthonormal on the caller's word
+ * (no M-product is made), zeroed on the prescribed dofs, into the locked store
+ * as modes of a solve with shift 0: feahip_get_locked_modes and
+ * feahip_get_locked_count then return them, ascending in lam.  For modes kept
+ * from an earlier run.  Refused: the contexts feahip_solve_modes_locked refuses
+ * and a context without a mass, n outside [1, 64], a lam that is not finite.
+ * The block of feahip_solve_modes is scratch, as under feahip_modal_deflate.
+ *
+ * feahip_response_load: q (k_response_project: one read of F and of the panels
+ * in use, a fixed grid, a two-stage sum in a fixed order, no atomics) and, with
+ * static_correction != 0, u_s: K assembled at the current nodes, masked with
+ * factor 0, and K u_s = F solved by the context's PCG and preconditioner
+ * (solver_type, tolerance, max_iterations, *iters and *resid as under
+ * feahip_solve_slae; they are not read without the correction, where *iters is
+ * 0).  F[3N] is in the caller's dof order; its entries on the prescribed dofs
+ * are not read.  q[n_locked] (may be NULL): ascending lam.  Afterwards K, f
+ * and u hold other values, as after feahip_consistent_acceleration; x, v, a,
+ * the time, the load factor and the locked store are untouched.
+ * FEAHIP_ESTATE without modes held.  FEAHIP_EINVAL: a correction asked for
+ * when the modes come from a solve with shift > 0 or any lam_k <= 0 (a free
+ * body's K is singular; such a body may still be swept without correction);
+ * the contexts feahip_solve_modes_locked refuses (a transport, a row shard,
+ * feahip_create_rank*, preconditioner 2); an F that is not finite; with the
+ * correction an unknown solver_type or max_iterations <= 0.
+ * FEAHIP_ENOTCONVERGED from the solve is passed on, and returned as well when
+ * its iterations run out above the tolerance (a u_s that is not one would be
+ * wrong at every frequency); no load is held then.
+ * A later locked solve, feahip_response_set_basis or any entry that drops the
+ * locked modes (feahip_modal_deflate, feahip_solve_buckling, the timing hooks
+ * 16-17) invalidates the load: the entries below return FEAHIP_ESTATE until
+ * the next load.
+ * feahip_get_response_static: u_s[3N] of the load held, caller's dof order,
+ * exactly 0 on the prescribed dofs (all zero without the correction).
+ *
+ * feahip_response_sweep: the host makes the table a_k(w_j) of all frequencies
+ * (the code behind feahip_host_response_coefficients), it goes to the device
+ * in one copy and ONE launch of k_response_sweep walks it: a lane owns a dof,
+ * holds its n_locked mode values in registers and keeps the largest
+ * |u_i(w_j)|^2 and its index.
+ *   peak[i]     max_j |u_i(w_j)|
+ *   peak_at[i]  the lowest j that attains it
+ * both [3N], caller's dof order, exactly 0 on the prescribed dofs.  Probes:
+ * n_probe <= 64 dofs (3 node + axis, caller's numbering) whose full complex
+ * curves come back, probe_re / probe_im [n_probe][n_freq] (may be NULL with
+ * n_probe == 0); the host sums them from the probes' rows of the store and of
+ * u_s and from the same table, in the kernel's order.  omega[n_freq] are
+ * circular frequencies in any order.  The same input gives the same bits.
+ * FEAHIP_ESTATE without a load held for the modes held.  FEAHIP_EINVAL: n_freq
+ * outside [1, FEA_RESPONSE_MAX_FREQ]; a negative or non-finite omega, alpha,
+ * beta_k or zeta_k; a coefficient that is not finite (w = 0 on a zero mode,
+ * w^2 = lam_k with d_k = 0); n_probe outside [0, 64]; a probe dof outside
+ * [0, 3N).  Nothing of the context's state changes.
+ * feahip_response_field: re[3N] and im[3N] of u(omega), caller's dof order, by
+ * the field-writing instantiation of the same kernel at one frequency.
+ *
+ * feahip_host_response_coefficients (no device): coef[n_freq][2][64], re then
+ * im, mode k of the arrays given at column k, zero past n_modes.  Returns
+ * FEAHIP_EINVAL where the sweep does, and for lam_k <= 0 with the correction.
+ * The corrected coefficient is evaluated as q (w^2 a - b^2 - i b lam) /
+ * (lam (a^2 + b^2)), a = lam - w^2, b = w d, which has no cancellation where
+ * w^2 << lam.
+ * Memory: 3 x 3N doubles, 1 MB of partial sums and the 4 MB table, on top of
+ * the locked store, allocated by the first load.  Not offered: sharded runs,
+ * complex loads and a phase between loads, transient modal superposition, base
+ * excitation, residual vectors beyond the one static correction.              */
+#define FEA_RESPONSE_MAX_FREQ 4096
+int feahip_response_set_basis(feahip_ctx *ctx, int n, const double *lam /*[n]*/, const double *phi /*[n][3N], caller's dofs*/);
+int feahip_response_load(feahip_ctx *ctx, const double *F /*[3N]*/, int static_correction, int solver_type, double tolerance,
+                         int max_iterations, double *q /*[n_locked], may be NULL*/, int *iters /*may be NULL*/,
+                         double *resid /*may be NULL*/);
+int feahip_get_response_static(feahip_ctx *ctx, double *u_s /*[3N]*/);
+int feahip_response_sweep(feahip_ctx *ctx, int n_freq, const double *omega /*[n_freq]*/, double alpha, double beta_k,
+                          const double *zeta /*[n_locked] or NULL*/, double *peak /*[3N]*/, int *peak_at /*[3N]*/,
+                          int n_probe, const int *probe_dof /*[n_probe]*/, double *probe_re,
+                          double *probe_im /*[n_probe][n_freq], may be NULL with n_probe == 0*/);
+int feahip_response_field(feahip_ctx *ctx, double omega, double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/,
+                          double *re /*[3N]*/, double *im /*[3N]*/);
+int feahip_host_response_coefficients(int n_modes, const double *lam, const double *q, int n_freq, const double *omega,
+                                      double alpha, double beta_k, const double *zeta /*[n_modes] or NULL*/,
+                                      int static_correction, double *coef /*[n_freq][2][64], zero past n_modes*/);
+
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
  *     K_sigma(x) phi = nu K(x) phi          on the free dofs,
@@ -1218,7 +1323,10 @@ int feahip_sync(feahip_ctx *ctx);
  * afterwards, assemble again); 21 k_damp_add (K += M + K_d, refused without a
  * damping with beta_k > 0) and 22 k_damp_residual on the vectors in force with
  * a0 = c1 = 1 (refused without damping; both need a mass and leave K or f
- * garbage as 8 and 9 do).                                                   */
+ * garbage as 8 and 9 do); 23 k_response_sweep over the coefficient table, the
+ * store and the u_s the last feahip_response_sweep used, 24 k_response_project
+ * on the f in force (both FEAHIP_ESTATE before a sweep; nothing but the sweep's
+ * own output buffers and partial sums is written).                           */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
