@@ -1451,9 +1451,16 @@ int dist_solve_pcg(std::vector<feahip_ctx *> &R, int type, double tol, int max_i
     FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
     if (flag != 0) break;           // every rank holds the same all-reduced sums, hence the same flag
   }
-  double sc[5];
+  double sc[11];
   FEA_HIP_CHECK(c0, hipMemcpyAsync(sc, c0->d_scal, sizeof(sc), hipMemcpyDeviceToHost, c0->stream));
   FEA_HIP_CHECK(c0, hipStreamSynchronize(c0->stream));
+  if (cgcg && flag == 0 && it > 0) {
+    // The cap ended the single-reduction loop: k_cgcg_update of iteration it - 1 left in scal[3] the r.r of the state
+    // it started from and moved x on; the stop test of the iterate returned would have run in iteration `it`.  Its
+    // r.r is the third of the sums reduced last (d_scal[8..11), all ranks alike): report it, and the stop if it is one.
+    sc[3] = sc[8 + 2];
+    if (sc[3] <= sc[4] * sc[2]) flag = it;
+  }
   const bool broke = pcg_outcome(flag, it, sc, iters, resid);
   // leave the flag clear so stand-alone SpMV launches are not skipped
   FOR_RANKS(c) {
