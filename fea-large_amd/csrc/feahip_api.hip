@@ -14,6 +14,7 @@ hipError_t feahip_device_malloc(void **p, size_t bytes)
 #define hipMalloc(p, bytes) feahip_device_malloc((void **)(p), (bytes))
 #include "amg.h"
 #include "coarse.h"
+#include "node_views.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -27,6 +28,107 @@ extern "C" const char *feahip_last_error(const feahip_ctx *c) { return c ? c->er
 
 // library id of a caller's node
 static inline int lib_id(const feahip_ctx *c, int a) { return c->perm.empty() ? a : c->perm[a]; }
+
+// ---- node-ordered views: the caller's numbering on the host side, the library's on the device (node_views.h) --------
+static NodeView view_of(const feahip_ctx *c, bool owned_only = false)
+{
+  const int *perm = c->perm.empty() ? nullptr : c->perm.data();
+  return owned_only ? NodeView(perm, c->N, c->row0, c->row1) : NodeView(perm, c->N);
+}
+
+static int get_vec(feahip_ctx *c, const double *d, double *h, size_t n)
+{
+  if (!h) return FEAHIP_EINVAL;
+  FEA_HIP_CHECK(c, hipMemcpyAsync(h, d, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+// device d[N][lib_stride] in library ids into the caller's h[N][width].  owned_only: the rows of the shard installed
+// now are all that is copied, the nodes of other ranks read as +0
+static int get_view(feahip_ctx *c, const double *d, double *h, int width, int lib_stride, bool owned_only = false)
+{
+  if (!h) return FEAHIP_EINVAL;
+  const NodeView v = view_of(c, owned_only);
+  if (!v.perm && width == lib_stride && v.all_rows()) return get_vec(c, d, h, (size_t)v.N * width);
+  std::vector<double> tmp((size_t)v.N * lib_stride);
+  const size_t lo = (size_t)v.row0 * lib_stride;
+  int rc;
+  if (v.row1 > v.row0 && (rc = get_vec(c, d + lo, tmp.data() + lo, (size_t)(v.row1 - v.row0) * lib_stride))) return rc;
+  to_caller(v, width, lib_stride, tmp.data(), h);
+  return FEAHIP_OK;
+}
+
+// the caller's h[N][width] into device d[N][lib_stride] in library ids, the pad lanes zero
+static int set_view(feahip_ctx *c, double *d, const double *h, int width, int lib_stride)
+{
+  if (!h) return FEAHIP_EINVAL;
+  const NodeView v = view_of(c);
+  std::vector<double> tmp;
+  if (v.perm || width != lib_stride) {
+    tmp.resize((size_t)v.N * lib_stride);
+    to_library(v, width, lib_stride, h, tmp.data());
+    h = tmp.data();
+  }
+  FEA_HIP_CHECK(c, hipMemcpyAsync(d, h, sizeof(double) * (size_t)v.N * lib_stride, hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  return FEAHIP_OK;
+}
+
+// a device buffer of n doubles that lives for one entry point
+struct DevTemp {
+  double *p = nullptr;
+  DevTemp() = default;
+  DevTemp(const DevTemp &) = delete;
+  DevTemp &operator=(const DevTemp &) = delete;
+  ~DevTemp() { if (p) (void)hipFree(p); }
+  int alloc(feahip_ctx *c, size_t n, bool zero = false)
+  {
+    FEA_HIP_CHECK(c, hipMalloc((void **)&p, sizeof(double) * n));
+    return zero && hipMemsetAsync(p, 0, sizeof(double) * n, c->stream) != hipSuccess ? FEAHIP_EHIP : FEAHIP_OK;
+  }
+};
+
+// Block vectors ([3N][8], kernels_modal.hip) to and from host columns [3N] in the caller's order, through the W block
+// of ModalState::d_v as [8][3N] staging.  Up: columns [first, first + count) of host, count <= 8, the columns left of
+// the panel zero.  Down: the first count columns; owned_only as in get_view.  One column per transfer.
+static int upload_columns(feahip_ctx *c, double *dst_block, const double *host, int first, int count)
+{
+  const size_t n = (size_t)c->ndof;
+  double *w = c->modal.d_v + n * FEA_MODAL_COLS;
+  int rc;
+  if (count < FEA_MODAL_COLS) FEA_HIP_CHECK(c, hipMemsetAsync(w + count * n, 0, sizeof(double) * (FEA_MODAL_COLS - count) * n, c->stream));
+  for (int k = 0; k < count; ++k)
+    if ((rc = set_view(c, w + k * n, host + (size_t)(first + k) * n, 3, 3))) return rc;
+  return launch_modal_pack(c, w, dst_block, 0);
+}
+
+static int download_columns(feahip_ctx *c, const double *src_block, double *host, int count, bool owned_only = false)
+{
+  const size_t n = (size_t)c->ndof;
+  double *w = c->modal.d_v + n * FEA_MODAL_COLS;
+  int rc;
+  if ((rc = launch_modal_pack(c, src_block, w, 1))) return rc;
+  for (int k = 0; k < count; ++k)
+    if ((rc = get_view(c, w + k * n, host + k * n, 3, 3, owned_only))) return rc;
+  return FEAHIP_OK;
+}
+
+// the ranks a collective call made on one context drives: the members of its in-process group, or the context alone
+static std::vector<feahip_ctx *> ranks_of(feahip_ctx *c)
+{
+  if (c->tr && c->tr->members()) return *c->tr->members();
+  return std::vector<feahip_ctx *>(1, c);
+}
+
+// The one way the error text of a collective call reaches the caller: a failed call (rc != 0) whose handle `to` holds
+// no message gets the first one any of the ranks R holds.  Returns rc.
+static int surface_error(feahip_ctx *to, const std::vector<feahip_ctx *> &R, int rc)
+{
+  if (rc && to->err.empty())
+    for (feahip_ctx *r : R) if (!r->err.empty()) { to->err = r->err; break; }
+  return rc;
+}
 
 template <class T>
 static int dev_upload(feahip_ctx *c, T **dst, const T *src, size_t n)
@@ -622,8 +724,7 @@ extern "C" int feahip_update_nodes_with_solution(feahip_ctx *c, const double *u)
   std::vector<double> tmp;
   if (u && !c->perm.empty()) {
     tmp.resize((size_t)c->ndof);
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 3; ++j) tmp[(size_t)c->perm[a] * 3 + j] = u[(size_t)a * 3 + j];
+    to_library(view_of(c), 3, 3, u, tmp.data());
     u = tmp.data();
   }
   return dist_update_nodes_with_solution(R, u);
@@ -642,8 +743,6 @@ extern "C" int feahip_solve(feahip_ctx *c, int load_increments, int max_newton, 
 
 // ---- surface loads (kernels_surface.hip) ------------------------------------
 
-static int get_node_vec(feahip_ctx *c, const double *d, double *h);
-
 extern "C" int feahip_set_surface_loads(feahip_ctx *c, int n_faces, int nodes_per_face, const int *face_nodes,
                                         const int *kind, const double *values)
 {
@@ -655,12 +754,10 @@ extern "C" int feahip_get_surface_forces(feahip_ctx *c, double *f)
 {
   CTX_GUARD_NOK(c);
   if (!f) return FEAHIP_EINVAL;
-  double *d = nullptr;
-  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (size_t)c->ndof));
-  int rc = hipMemsetAsync(d, 0, sizeof(double) * (size_t)c->ndof, c->stream) == hipSuccess ? launch_surface_loads(c, d) : FEAHIP_EHIP;
-  if (rc == FEAHIP_OK) rc = get_node_vec(c, d, f);
-  (void)hipFree(d);
-  return rc;
+  DevTemp d;
+  int rc;
+  if ((rc = d.alloc(c, (size_t)c->ndof, true)) || (rc = launch_surface_loads(c, d.p))) return rc;
+  return get_view(c, d.p, f, 3, 3);
 }
 
 extern "C" int feahip_set_load_factor(feahip_ctx *c, double lambda)
@@ -678,9 +775,6 @@ extern "C" int feahip_get_load_factor(feahip_ctx *c, double *lambda)
 }
 
 // ---- contact with rigid obstacles (kernels_contact.hip) ----------------------
-static std::vector<feahip_ctx *> ranks_of(feahip_ctx *c);
-static int surface_error(feahip_ctx *to, const std::vector<feahip_ctx *> &R, int rc);
-
 extern "C" int feahip_set_contact(feahip_ctx *c, int n_faces, int nodes_per_face, const int *face_nodes, int n_obstacles,
                                   const int *kind, const double *geom, double penalty, int augment_max, double gap_tolerance)
 {
@@ -757,32 +851,25 @@ extern "C" int feahip_get_contact_forces(feahip_ctx *c, double *f)
 {
   CTX_GUARD_NOK(c);
   if (!f) return FEAHIP_EINVAL;
-  double *d = nullptr;
-  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * (size_t)c->ndof));
-  int rc = hipMemsetAsync(d, 0, sizeof(double) * (size_t)c->ndof, c->stream) == hipSuccess ? launch_contact(c, false, true, d) : FEAHIP_EHIP;
-  if (rc == FEAHIP_OK) rc = get_node_vec(c, d, f);
-  (void)hipFree(d);
-  return rc;
+  DevTemp d;
+  int rc;
+  if ((rc = d.alloc(c, (size_t)c->ndof, true)) || (rc = launch_contact(c, false, true, d.p))) return rc;
+  return get_view(c, d.p, f, 3, 3);
 }
 
 extern "C" int feahip_get_contact_status(feahip_ctx *c, double *gap, double *pressure)
 {
   CTX_GUARD_NOK(c);
   const size_t N = (size_t)c->N;
-  std::vector<double> h(2 * N, 0.0);
+  std::vector<double> h(2 * N, 0.0);                                 // where no contact node is: gap +inf, pressure 0
   std::fill(h.begin(), h.begin() + N, std::numeric_limits<double>::infinity());
-  double *d = nullptr;
-  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * 2 * N));
-  int rc = hipMemcpyAsync(d, h.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream) == hipSuccess
-               ? launch_contact_status(c, d, d + N) : FEAHIP_EHIP;
-  if (rc == FEAHIP_OK && hipMemcpyAsync(h.data(), d, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = FEAHIP_EHIP;
-  if (rc == FEAHIP_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = FEAHIP_EHIP;
-  (void)hipFree(d);
-  if (rc) return rc;
-  for (int a = 0; a < c->N; ++a) {
-    if (gap) gap[a] = h[(size_t)lib_id(c, a)];
-    if (pressure) pressure[a] = h[N + (size_t)lib_id(c, a)];
-  }
+  DevTemp d;
+  int rc;
+  if ((rc = d.alloc(c, 2 * N))) return rc;
+  if (hipMemcpyAsync(d.p, h.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream) != hipSuccess) return FEAHIP_EHIP;
+  if ((rc = launch_contact_status(c, d.p, d.p + N))) return rc;
+  if (gap && (rc = get_view(c, d.p, gap, 1, 1))) return rc;
+  if (pressure && (rc = get_view(c, d.p + N, pressure, 1, 1))) return rc;
   return FEAHIP_OK;
 }
 
@@ -932,15 +1019,6 @@ static int group_vec(feahip_ctx **ctxs, int n, std::vector<feahip_ctx *> &R)
   return FEAHIP_OK;
 }
 
-// The one way the error text of a collective call reaches the caller: a failed call (rc != 0) whose handle `to` holds
-// no message gets the first one any of the ranks R holds.  Returns rc.
-static int surface_error(feahip_ctx *to, const std::vector<feahip_ctx *> &R, int rc)
-{
-  if (rc && to->err.empty())
-    for (feahip_ctx *r : R) if (!r->err.empty()) { to->err = r->err; break; }
-  return rc;
-}
-
 extern "C" int feahip_group_solve_slae(feahip_ctx **ctxs, int n, int type, double tol, int max_iter, int *iters, double *resid)
 {
   std::vector<feahip_ctx *> R;
@@ -1024,67 +1102,15 @@ extern "C" int feahip_host_numbering(int n_nodes, int n_elems, int npe, const in
 extern "C" int feahip_set_nodes(feahip_ctx *c, const double *nodes)
 {
   CTX_GUARD_NOK(c);
-  if (!nodes) return FEAHIP_EINVAL;
-  std::vector<double> pad((size_t)c->N * 4, 0.0);
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) pad[(size_t)lib_id(c, a) * 4 + j] = nodes[(size_t)a * 3 + j];
-  FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_x, pad.data(), sizeof(double) * pad.size(), hipMemcpyHostToDevice, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  c->state_valid = false;
-  return FEAHIP_OK;
+  const int rc = set_view(c, c->d_x, nodes, 3, 4);
+  if (rc == FEAHIP_OK) c->state_valid = false;
+  return rc;
 }
 
-extern "C" int feahip_get_nodes(feahip_ctx *c, double *nodes)
-{
-  CTX_GUARD_NOK(c);
-  if (!nodes) return FEAHIP_EINVAL;
-  std::vector<double> pad((size_t)c->N * 4);
-  FEA_HIP_CHECK(c, hipMemcpyAsync(pad.data(), c->d_x, sizeof(double) * pad.size(), hipMemcpyDeviceToHost, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) nodes[(size_t)a * 3 + j] = pad[(size_t)lib_id(c, a) * 4 + j];
-  return FEAHIP_OK;
-}
-
-static int get_vec(feahip_ctx *c, const double *d, double *h, size_t n)
-{
-  if (!h) return FEAHIP_EINVAL;
-  FEA_HIP_CHECK(c, hipMemcpyAsync(h, d, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  return FEAHIP_OK;
-}
-
-// node vectors (3 doubles per node) between the caller's numbering (host) and the library's (device)
-static int get_node_vec(feahip_ctx *c, const double *d, double *h)
-{
-  if (c->perm.empty()) return get_vec(c, d, h, (size_t)c->ndof);
-  if (!h) return FEAHIP_EINVAL;
-  std::vector<double> tmp((size_t)c->ndof);
-  const int rc = get_vec(c, d, tmp.data(), tmp.size());
-  if (rc) return rc;
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) h[(size_t)a * 3 + j] = tmp[(size_t)c->perm[a] * 3 + j];
-  return FEAHIP_OK;
-}
-
-static int set_node_vec(feahip_ctx *c, double *d, const double *h)
-{
-  if (!h) return FEAHIP_EINVAL;
-  std::vector<double> tmp;
-  if (!c->perm.empty()) {
-    tmp.resize((size_t)c->ndof);
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 3; ++j) tmp[(size_t)c->perm[a] * 3 + j] = h[(size_t)a * 3 + j];
-    h = tmp.data();
-  }
-  FEA_HIP_CHECK(c, hipMemcpyAsync(d, h, sizeof(double) * (size_t)c->ndof, hipMemcpyHostToDevice, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  return FEAHIP_OK;
-}
-
-extern "C" int feahip_get_forces(feahip_ctx *c, double *f) { CTX_GUARD(c); return get_node_vec(c, c->d_f, f); }
-extern "C" int feahip_get_solution(feahip_ctx *c, double *u) { CTX_GUARD(c); return get_node_vec(c, c->d_u, u); }
-extern "C" int feahip_set_forces(feahip_ctx *c, const double *f) { CTX_GUARD(c); return set_node_vec(c, c->d_f, f); }
+extern "C" int feahip_get_nodes(feahip_ctx *c, double *nodes) { CTX_GUARD_NOK(c); return get_view(c, c->d_x, nodes, 3, 4); }
+extern "C" int feahip_get_forces(feahip_ctx *c, double *f) { CTX_GUARD(c); return get_view(c, c->d_f, f, 3, 3); }
+extern "C" int feahip_get_solution(feahip_ctx *c, double *u) { CTX_GUARD(c); return get_view(c, c->d_u, u, 3, 3); }
+extern "C" int feahip_set_forces(feahip_ctx *c, const double *f) { CTX_GUARD(c); return set_view(c, c->d_f, f, 3, 3); }
 
 // ---- consistent mass, body force and implicit dynamics (kernels_mass.hip, drivers.hip) ----------------------------
 extern "C" int feahip_set_mass(feahip_ctx *c, int n_rho, const double *rho, int mass_points, const double *weights,
@@ -1101,37 +1127,15 @@ extern "C" int feahip_set_body_force(feahip_ctx *c, const double *b)
   return mass_set_body_force(c, b);
 }
 
-// node records ([N][4], library ids) to and from [N][3] in the caller's ids
-static int get_node4(feahip_ctx *c, const double *d, double *h)
-{
-  if (!h) return FEAHIP_EINVAL;
-  std::vector<double> pad((size_t)c->N * 4);
-  FEA_HIP_CHECK(c, hipMemcpyAsync(pad.data(), d, sizeof(double) * pad.size(), hipMemcpyDeviceToHost, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) h[(size_t)a * 3 + j] = pad[(size_t)lib_id(c, a) * 4 + j];
-  return FEAHIP_OK;
-}
-
-static int set_node4(feahip_ctx *c, double *d, const double *h)
-{
-  if (!h) return FEAHIP_EINVAL;
-  std::vector<double> pad((size_t)c->N * 4, 0.0);
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) pad[(size_t)lib_id(c, a) * 4 + j] = h[(size_t)a * 3 + j];
-  FEA_HIP_CHECK(c, hipMemcpyAsync(d, pad.data(), sizeof(double) * pad.size(), hipMemcpyHostToDevice, c->stream));
-  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  return FEAHIP_OK;
-}
-
 #define MASS_GUARD(c, who)                                         \
   CTX_GUARD_NOK(c);                                                \
   { const int _rm = mass_ensure(c, who); if (_rm) return _rm; }
 
-extern "C" int feahip_set_velocities(feahip_ctx *c, const double *v) { MASS_GUARD(c, "feahip_set_velocities"); c->mass.ke_parts = 0; return set_node4(c, c->mass.d_vel, v); }
-extern "C" int feahip_get_velocities(feahip_ctx *c, double *v) { MASS_GUARD(c, "feahip_get_velocities"); return get_node4(c, c->mass.d_vel, v); }
-extern "C" int feahip_set_accelerations(feahip_ctx *c, const double *a) { MASS_GUARD(c, "feahip_set_accelerations"); return set_node4(c, c->mass.d_acc, a); }
-extern "C" int feahip_get_accelerations(feahip_ctx *c, double *a) { MASS_GUARD(c, "feahip_get_accelerations"); return get_node4(c, c->mass.d_acc, a); }
+// (the kinematic vectors are node records [N][4] that carry 3)
+extern "C" int feahip_set_velocities(feahip_ctx *c, const double *v) { MASS_GUARD(c, "feahip_set_velocities"); c->mass.ke_parts = 0; return set_view(c, c->mass.d_vel, v, 3, 4); }
+extern "C" int feahip_get_velocities(feahip_ctx *c, double *v) { MASS_GUARD(c, "feahip_get_velocities"); return get_view(c, c->mass.d_vel, v, 3, 4); }
+extern "C" int feahip_set_accelerations(feahip_ctx *c, const double *a) { MASS_GUARD(c, "feahip_set_accelerations"); return set_view(c, c->mass.d_acc, a, 3, 4); }
+extern "C" int feahip_get_accelerations(feahip_ctx *c, double *a) { MASS_GUARD(c, "feahip_get_accelerations"); return get_view(c, c->mass.d_acc, a, 3, 4); }
 
 extern "C" int feahip_get_time(feahip_ctx *c, double *t)
 {
@@ -1152,10 +1156,10 @@ extern "C" int feahip_mass_spmv(feahip_ctx *c, const double *x, double *y)
   MASS_GUARD(c, "feahip_mass_spmv");
   if (!x || !y) return FEAHIP_EINVAL;
   int rc;
-  if ((rc = set_node4(c, c->mass.d_xt, x))) return rc;             // (xt is free outside a step)
+  if ((rc = set_view(c, c->mass.d_xt, x, 3, 4))) return rc;        // (xt is free outside a step)
   FEA_HIP_CHECK(c, hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream));   // rows of other ranks: 0
   if ((rc = launch_mass_product(c, c->mass.d_xt, c->d_q))) return rc;
-  return get_node_vec(c, c->d_q, y);
+  return get_view(c, c->d_q, y, 3, 3);
 }
 
 // ---- Rayleigh damping C = alpha M + beta_k K_d (kernels_damping.hip) --------------------------------------------------
@@ -1179,14 +1183,11 @@ extern "C" int feahip_damping_spmv(feahip_ctx *c, const double *v, double *y)
   if (!c->damping.on()) { c->err = "feahip_damping_spmv: no damping on this context (feahip_set_damping)"; return FEAHIP_ESTATE; }
   int rc;
   if ((rc = damping_ready(c, "feahip_damping_spmv"))) return rc;
-  double *d_v4 = nullptr;                                          // (a context with beta_k alone may have no mass vectors)
-  FEA_HIP_CHECK(c, hipMalloc((void **)&d_v4, sizeof(double) * 4 * (size_t)c->N));
-  rc = set_node4(c, d_v4, v);
-  if (!rc && hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream) != hipSuccess) rc = FEAHIP_EHIP;   // rows of other ranks: 0
-  if (!rc) rc = launch_damp_product(c, d_v4, c->d_q);
-  if (!rc) rc = get_node_vec(c, c->d_q, y);                        // (synchronises)
-  dev_free({d_v4});
-  return rc;
+  DevTemp v4;                                                      // (a context with beta_k alone may have no mass vectors)
+  if ((rc = v4.alloc(c, 4 * (size_t)c->N)) || (rc = set_view(c, v4.p, v, 3, 4))) return rc;
+  if (hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream) != hipSuccess) return FEAHIP_EHIP;   // rows of other ranks: 0
+  if ((rc = launch_damp_product(c, v4.p, c->d_q))) return rc;
+  return get_view(c, c->d_q, y, 3, 3);                             // (synchronises)
 }
 
 extern "C" int feahip_host_rayleigh(double omega1, double zeta1, double omega2, double zeta2, double *alpha, double *beta_k)
@@ -1197,13 +1198,6 @@ extern "C" int feahip_host_rayleigh(double omega1, double zeta1, double omega2, 
   *alpha = 2.0 * omega1 * omega2 * (zeta1 * omega2 - zeta2 * omega1) / den;
   *beta_k = 2.0 * (zeta2 * omega2 - zeta1 * omega1) / den;
   return FEAHIP_OK;
-}
-
-// the ranks a collective call made on one context drives: the members of its in-process group, or the context alone
-static std::vector<feahip_ctx *> ranks_of(feahip_ctx *c)
-{
-  if (c->tr && c->tr->members()) return *c->tr->members();
-  return std::vector<feahip_ctx *>(1, c);
 }
 
 extern "C" int feahip_consistent_acceleration(feahip_ctx *c, int solver_type, double tol, int max_iter)
@@ -1261,10 +1255,7 @@ extern "C" int feahip_get_lumped_mass(feahip_ctx *c, double *ml)
   if (!ml) return FEAHIP_EINVAL;
   int rc;
   if ((rc = lump_ensure(c, "feahip_get_lumped_mass"))) return rc;
-  std::vector<double> tmp((size_t)c->N);
-  if ((rc = get_vec(c, c->mass.d_ml, tmp.data(), tmp.size()))) return rc;
-  for (int a = 0; a < c->N; ++a) ml[a] = tmp[(size_t)lib_id(c, a)];
-  return FEAHIP_OK;
+  return get_view(c, c->mass.d_ml, ml, 1, 1);
 }
 
 extern "C" int feahip_stable_step(feahip_ctx *c, double *dt_crit)
@@ -1326,30 +1317,15 @@ static int results_material(feahip_ctx *c, int material, const char *who)
   return FEAHIP_OK;
 }
 
-// a node scalar [N] from the library's ids to the caller's
-static int get_node_scalar(feahip_ctx *c, const double *d, double *h)
-{
-  std::vector<double> tmp((size_t)c->N);
-  const int rc = get_vec(c, d, tmp.data(), tmp.size());
-  if (rc) return rc;
-  for (int a = 0; a < c->N; ++a) h[a] = tmp[(size_t)lib_id(c, a)];
-  return FEAHIP_OK;
-}
-
 extern "C" int feahip_get_nodal_stresses(feahip_ctx *c, int material, double *sig6, double *von_mises, double *weight)
 {
   CTX_GUARD_NOK(c);
   int rc;
   if ((rc = results_material(c, material, "feahip_get_nodal_stresses"))) return rc;
   if ((rc = launch_results(c, material, nullptr))) return rc;
-  if (sig6) {
-    std::vector<double> tmp((size_t)c->N * 6);
-    if ((rc = get_vec(c, c->results.d_sig6, tmp.data(), tmp.size()))) return rc;
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 6; ++j) sig6[(size_t)a * 6 + j] = tmp[(size_t)lib_id(c, a) * 6 + j];
-  }
-  if (von_mises && (rc = get_node_scalar(c, c->results.d_vm, von_mises))) return rc;
-  if (weight && (rc = get_node_scalar(c, c->results.d_wt, weight))) return rc;
+  if (sig6 && (rc = get_view(c, c->results.d_sig6, sig6, 6, 6))) return rc;
+  if (von_mises && (rc = get_view(c, c->results.d_vm, von_mises, 1, 1))) return rc;
+  if (weight && (rc = get_view(c, c->results.d_wt, weight, 1, 1))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   return FEAHIP_OK;
 }
@@ -1360,7 +1336,7 @@ extern "C" int feahip_get_nodal_energy(feahip_ctx *c, double *w_node)
   if (!w_node) return FEAHIP_EINVAL;
   int rc;
   if ((rc = launch_results(c, -1, nullptr))) return rc;
-  return get_node_scalar(c, c->results.d_wn, w_node);
+  return get_view(c, c->results.d_wn, w_node, 1, 1);
 }
 
 extern "C" int feahip_strain_energy(feahip_ctx *c, double *W)
@@ -1375,12 +1351,10 @@ extern "C" int feahip_get_reactions(feahip_ctx *c, double *r)
 {
   CTX_GUARD(c);
   if (!r) return FEAHIP_EINVAL;
-  double *d = nullptr;
-  FEA_HIP_CHECK(c, hipMalloc((void **)&d, sizeof(double) * 2 * (size_t)c->ndof));
-  int rc = launch_reactions(c, d, d + c->ndof);
-  if (rc == FEAHIP_OK) rc = get_node_vec(c, d, r);
-  (void)hipFree(d);
-  return rc;
+  DevTemp d;
+  int rc;
+  if ((rc = d.alloc(c, 2 * (size_t)c->ndof)) || (rc = launch_reactions(c, d.p, d.p + c->ndof))) return rc;
+  return get_view(c, d.p, r, 3, 3);
 }
 
 // ---- modal analysis (kernels_modal.hip) --------------------------------------
@@ -1391,16 +1365,40 @@ static int modal_ready(feahip_ctx *c, const char *who)
   return mass_ensure(c, who);
 }
 
+// what the four eigenvalue entries ask of their arguments: `who` the entry, `limit` the modes it can hold, `out` its
+// required output array (a shift is an argument of solve_modes_locked alone)
+static int eigen_args(feahip_ctx *c, const char *who, int n_modes, int limit, double tol, int max_iter, const void *out,
+                      const char *out_name, double shift = 0.0)
+{
+  auto refuse = [c, who](const std::string &why) { c->err = std::string(who) + ": " + why; return FEAHIP_EINVAL; };
+  if (n_modes < 1 || n_modes > limit) return refuse("n_modes must be in [1, " + std::to_string(limit) + "]");
+  if (!(shift >= 0.0) || !std::isfinite(shift)) return refuse("shift must be finite and not negative");
+  if (!(tol > 0.0) || !std::isfinite(tol)) return refuse("tolerance must be positive");
+  if (max_iter < 0) return refuse("max_iterations must not be negative");
+  if (!out) return refuse(std::string("null ") + out_name);
+  return FEAHIP_OK;
+}
+
+// modes [first, first + count) as `get` hands them over ([3N] on the host, library ids) into phi in the caller's order
+template <class Get>
+static int modes_to_caller(feahip_ctx *c, const NodeView &v, int first, int count, double *phi, Get get)
+{
+  std::vector<double> tmp((size_t)c->ndof);
+  for (int k = 0; k < count; ++k) {
+    const int rc = get(c, first + k, tmp.data());
+    if (rc) return rc;
+    to_caller(v, 3, 3, tmp.data(), phi + (size_t)k * c->ndof);
+  }
+  return FEAHIP_OK;
+}
+
 extern "C" int feahip_solve_modes(feahip_ctx *c, int n_modes, double tol, int max_iter, int warm, double *lambda,
                                   double *resid, int *iters)
 {
   CTX_GUARD(c);
   if (iters) *iters = 0;
-  if (n_modes < 1 || n_modes > FEA_MODAL_COLS) { c->err = "solve_modes: n_modes must be in [1, 8]"; return FEAHIP_EINVAL; }
-  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_modes: tolerance must be positive"; return FEAHIP_EINVAL; }
-  if (max_iter < 0) { c->err = "solve_modes: max_iterations must not be negative"; return FEAHIP_EINVAL; }
-  if (!lambda) { c->err = "solve_modes: null lambda"; return FEAHIP_EINVAL; }
   int rc;
+  if ((rc = eigen_args(c, "solve_modes", n_modes, FEA_MODAL_COLS, tol, max_iter, lambda, "lambda"))) return rc;
   if ((rc = modal_ready(c, "solve_modes"))) return rc;
   return modal_solve(c, n_modes, tol, max_iter, warm, lambda, resid, iters);
 }
@@ -1411,19 +1409,7 @@ extern "C" int feahip_get_modes(feahip_ctx *c, int first, int count, double *phi
   if (!c->modal.have && !c->modal.have_sharded) { c->err = "get_modes: no modes held (feahip_solve_modes first)"; return FEAHIP_ESTATE; }
   if (first < 0 || count < 0 || first + count > FEA_MODAL_COLS) { c->err = "get_modes: modes [first, first + count) outside the eight held"; return FEAHIP_EINVAL; }
   if (!phi) { c->err = "get_modes: null phi"; return FEAHIP_EINVAL; }
-  std::vector<double> tmp((size_t)c->ndof);
-  for (int k = 0; k < count; ++k) {
-    const int rc = modal_get(c, first + k, tmp.data());
-    if (rc) return rc;
-    if (c->modal.have_sharded) {                                       // a sharded solve: the rank's own rows, zero elsewhere
-      std::fill(tmp.begin(), tmp.begin() + (size_t)3 * c->row0, 0.0);
-      std::fill(tmp.begin() + (size_t)3 * c->row1, tmp.end(), 0.0);
-    }
-    double *out = phi + (size_t)k * c->ndof;
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
-  }
-  return FEAHIP_OK;
+  return modes_to_caller(c, view_of(c, c->modal.have_sharded), first, count, phi, modal_get);   // a sharded solve: the rank's own rows
 }
 
 extern "C" int feahip_spmm_km(feahip_ctx *c, const double *x8, double *y8, double *z8)
@@ -1435,17 +1421,11 @@ extern "C" int feahip_spmm_km(feahip_ctx *c, const double *x8, double *y8, doubl
   if (!c->k_valid) { c->err = "spmm_km: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
   if ((rc = ensure_modal(c))) return rc;
   c->modal.have = false;                                             // the block vectors are scratch here
-  const size_t n = (size_t)c->ndof, n8 = n * FEA_MODAL_COLS;
-  double *v = c->modal.d_v;                                          // X, W <- the host layout, KX, MX <- the products
-  for (int k = 0; k < FEA_MODAL_COLS; ++k)
-    if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, x8 + (size_t)k * n))) return rc;
-  if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, v, v + 3 * n8, v + 6 * n8))) return rc;
-  for (int which = 0; which < 2; ++which) {
-    if ((rc = launch_modal_pack(c, v + (which ? 6 : 3) * n8, v + n8, 1))) return rc;
-    for (int k = 0; k < FEA_MODAL_COLS; ++k)
-      if ((rc = get_node_vec(c, v + n8 + (size_t)k * n, (which ? z8 : y8) + (size_t)k * n))) return rc;
-  }
-  return FEAHIP_OK;
+  const size_t n8 = (size_t)c->ndof * FEA_MODAL_COLS;
+  double *v = c->modal.d_v;                                          // X <- the host layout, KX, MX <- the products
+  if ((rc = upload_columns(c, v, x8, 0, FEA_MODAL_COLS)) || (rc = launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, v, v + 3 * n8, v + 6 * n8))) return rc;
+  if ((rc = download_columns(c, v + 3 * n8, y8, FEA_MODAL_COLS))) return rc;
+  return download_columns(c, v + 6 * n8, z8, FEA_MODAL_COLS);
 }
 
 // ---- the same solve over the ranks of a sharded run (modal_solve_dist, kernels_modal.hip) ------------------------------
@@ -1454,10 +1434,7 @@ extern "C" int feahip_solve_modes_sharded(feahip_ctx *c, int n_modes, double tol
 {
   CTX_GUARD(c);
   if (iters) *iters = 0;
-  if (n_modes < 1 || n_modes > FEA_MODAL_COLS) { c->err = "solve_modes_sharded: n_modes must be in [1, 8]"; return FEAHIP_EINVAL; }
-  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_modes_sharded: tolerance must be positive"; return FEAHIP_EINVAL; }
-  if (max_iter < 0) { c->err = "solve_modes_sharded: max_iterations must not be negative"; return FEAHIP_EINVAL; }
-  if (!lambda) { c->err = "solve_modes_sharded: null lambda"; return FEAHIP_EINVAL; }
+  { const int rc = eigen_args(c, "solve_modes_sharded", n_modes, FEA_MODAL_COLS, tol, max_iter, lambda, "lambda"); if (rc) return rc; }
   if (!c->tr) {
     c->err = "solve_modes_sharded: the context has no transport (feahip_group_init, feahip_comm_init); feahip_solve_modes solves on one context";
     return FEAHIP_EINVAL;
@@ -1465,18 +1442,6 @@ extern "C" int feahip_solve_modes_sharded(feahip_ctx *c, int n_modes, double tol
   std::vector<feahip_ctx *> R = ranks_of(c);
   for (feahip_ctx *r : R) { CTX_GUARD(r); }
   return surface_error(c, R, modal_solve_dist(R, n_modes, tol, max_iter, warm, lambda, resid, iters));
-}
-
-// the rows a sharded context owns of a device vector in library ids, into the caller's dof order; zero elsewhere
-static int get_owned_node_vec(feahip_ctx *c, const double *d, double *h)
-{
-  std::vector<double> tmp((size_t)c->ndof, 0.0);
-  int rc;
-  if (c->row1 > c->row0 &&
-      (rc = get_vec(c, d + (size_t)3 * c->row0, tmp.data() + (size_t)3 * c->row0, (size_t)3 * (c->row1 - c->row0)))) return rc;
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) h[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
-  return FEAHIP_OK;
 }
 
 extern "C" int feahip_group_spmm_km(feahip_ctx **ctxs, int n, const double *const *x8, double *const *y8, double *const *z8)
@@ -1493,23 +1458,15 @@ extern "C" int feahip_group_spmm_km(feahip_ctx **ctxs, int n, const double *cons
     if (!c->k_valid) { R[0]->err = c->err = "group_spmm_km: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
     if ((rc = surface_error(R[0], R, ensure_modal_dist(c)))) return rc;
     c->modal.have = c->modal.have_sharded = false;                     // the block vectors are scratch here
-    const size_t nd = (size_t)c->ndof, n8 = nd * FEA_MODAL_COLS;
-    double *v = c->modal.d_v;                                          // X, W <- the host layout, KX, MX <- the products
-    for (int q = 0; q < FEA_MODAL_COLS; ++q)
-      if ((rc = set_node_vec(c, v + n8 + (size_t)q * nd, x8[k] + (size_t)q * nd))) return rc;
-    if ((rc = launch_modal_pack(c, v + n8, v, 0))) return rc;
+    if ((rc = upload_columns(c, c->modal.d_v, x8[k], 0, FEA_MODAL_COLS))) return rc;   // X <- the host layout; KX, MX <- the products
   }
   if ((rc = surface_error(R[0], R, modal_spmm_km_dist(R)))) return rc;
   for (int k = 0; k < n; ++k) {
     feahip_ctx *c = R[k];
     FEA_HIP_CHECK(c, hipSetDevice(c->device));
-    const size_t nd = (size_t)c->ndof, n8 = nd * FEA_MODAL_COLS;
-    double *v = c->modal.d_v;
-    for (int which = 0; which < 2; ++which) {
-      if ((rc = launch_modal_pack(c, v + (which ? 6 : 3) * n8, v + n8, 1))) return rc;
-      for (int q = 0; q < FEA_MODAL_COLS; ++q)
-        if ((rc = get_owned_node_vec(c, v + n8 + (size_t)q * nd, (which ? z8[k] : y8[k]) + (size_t)q * nd))) return rc;
-    }
+    const size_t n8 = (size_t)c->ndof * FEA_MODAL_COLS;
+    if ((rc = download_columns(c, c->modal.d_v + 3 * n8, y8[k], FEA_MODAL_COLS, true))) return rc;
+    if ((rc = download_columns(c, c->modal.d_v + 6 * n8, z8[k], FEA_MODAL_COLS, true))) return rc;
   }
   return FEAHIP_OK;
 }
@@ -1520,12 +1477,8 @@ extern "C" int feahip_solve_modes_locked(feahip_ctx *c, int n_modes, double shif
   CTX_GUARD(c);
   if (iters) *iters = 0;
   if (sweeps) *sweeps = 0;
-  if (n_modes < 1 || n_modes > FEA_MODAL_MAX_LOCKED) { c->err = "solve_modes_locked: n_modes must be in [1, 64]"; return FEAHIP_EINVAL; }
-  if (!(shift >= 0.0) || !std::isfinite(shift)) { c->err = "solve_modes_locked: shift must be finite and not negative"; return FEAHIP_EINVAL; }
-  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_modes_locked: tolerance must be positive"; return FEAHIP_EINVAL; }
-  if (max_iter < 0) { c->err = "solve_modes_locked: max_iterations must not be negative"; return FEAHIP_EINVAL; }
-  if (!lambda) { c->err = "solve_modes_locked: null lambda"; return FEAHIP_EINVAL; }
   int rc;
+  if ((rc = eigen_args(c, "solve_modes_locked", n_modes, FEA_MODAL_MAX_LOCKED, tol, max_iter, lambda, "lambda", shift))) return rc;
   if ((rc = modal_ready(c, "solve_modes_locked"))) return rc;
   return modal_solve_locked(c, n_modes, shift, tol, max_iter, lambda, resid, iters, sweeps);
 }
@@ -1548,15 +1501,7 @@ extern "C" int feahip_get_locked_modes(feahip_ctx *c, int first, int count, doub
     return FEAHIP_EINVAL;
   }
   if (!phi) { c->err = "get_locked_modes: null phi"; return FEAHIP_EINVAL; }
-  std::vector<double> tmp((size_t)c->ndof);
-  for (int k = 0; k < count; ++k) {
-    const int rc = modal_get_locked(c, first + k, tmp.data());
-    if (rc) return rc;
-    double *out = phi + (size_t)k * c->ndof;
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
-  }
-  return FEAHIP_OK;
+  return modes_to_caller(c, view_of(c), first, count, phi, modal_get_locked);
 }
 
 extern "C" int feahip_modal_deflate(feahip_ctx *c, int n_locked, const double *q, const double *x8, double *out8)
@@ -1569,23 +1514,17 @@ extern "C" int feahip_modal_deflate(feahip_ctx *c, int n_locked, const double *q
   if (!c->k_valid) { c->err = "modal_deflate: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
   if ((rc = ensure_modal(c)) || (rc = ensure_locked(c, n_locked))) return rc;
   c->modal.have = false;                                             // the block vectors and the store are scratch here
-  const size_t n = (size_t)c->ndof, n8 = n * FEA_MODAL_COLS;
-  double *v = c->modal.d_v;                                          // W <- the host layout, X <- a panel of q, MX <- mask(M X)
+  const size_t n8 = (size_t)c->ndof * FEA_MODAL_COLS;
+  double *v = c->modal.d_v;                                          // X <- a panel of q, MX <- mask(M X)
   for (int p = 0; p * FEA_MODAL_COLS < n_locked; ++p) {
-    FEA_HIP_CHECK(c, hipMemsetAsync(v + n8, 0, sizeof(double) * n8, c->stream));
-    for (int k = 0; k < FEA_MODAL_COLS && p * FEA_MODAL_COLS + k < n_locked; ++k)
-      if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, q + ((size_t)p * FEA_MODAL_COLS + k) * n))) return rc;
-    if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, v, v + 3 * n8, v + 6 * n8))) return rc;
+    const int first = p * FEA_MODAL_COLS;
+    if ((rc = upload_columns(c, v, q, first, std::min(FEA_MODAL_COLS, n_locked - first)))) return rc;
+    if ((rc = launch_spmm_km(c, 0, c->nchunks_local, c->mass.d_m, v, v + 3 * n8, v + 6 * n8))) return rc;
     FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
     FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 1, p), v + 6 * n8, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
   }
-  for (int k = 0; k < FEA_MODAL_COLS; ++k)
-    if ((rc = set_node_vec(c, v + n8 + (size_t)k * n, x8 + (size_t)k * n))) return rc;
-  if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_deflate(c, v, n_locked))) return rc;
-  if ((rc = launch_modal_pack(c, v, v + n8, 1))) return rc;
-  for (int k = 0; k < FEA_MODAL_COLS; ++k)
-    if ((rc = get_node_vec(c, v + n8 + (size_t)k * n, out8 + (size_t)k * n))) return rc;
-  return FEAHIP_OK;
+  if ((rc = upload_columns(c, v, x8, 0, FEA_MODAL_COLS)) || (rc = launch_deflate(c, v, n_locked))) return rc;
+  return download_columns(c, v, out8, FEA_MODAL_COLS);
 }
 
 // ---- frequency response by mode superposition on the locked store (kernels_response.hip) -------------------------------
@@ -1600,14 +1539,11 @@ extern "C" int feahip_response_set_basis(feahip_ctx *c, int n, const double *lam
   if ((rc = modal_ready(c, "response_set_basis")) || (rc = ensure_modal(c)) || (rc = ensure_locked(c, n))) return rc;
   ModalState &S = c->modal;
   S.have = false;                                                    // the block vectors are scratch here
-  const size_t nd = (size_t)c->ndof, n8 = nd * FEA_MODAL_COLS;
-  double *v = S.d_v;                                                 // W <- the host layout, X <- a panel, zero on the prescribed dofs
+  double *v = S.d_v;                                                 // X <- a panel, zero on the prescribed dofs
   for (int p = 0; p * FEA_MODAL_COLS < n; ++p) {
-    FEA_HIP_CHECK(c, hipMemsetAsync(v + n8, 0, sizeof(double) * n8, c->stream));
-    for (int k = 0; k < FEA_MODAL_COLS && p * FEA_MODAL_COLS + k < n; ++k)
-      if ((rc = set_node_vec(c, v + n8 + (size_t)k * nd, phi + ((size_t)p * FEA_MODAL_COLS + k) * nd))) return rc;
-    if ((rc = launch_modal_pack(c, v + n8, v, 0)) || (rc = launch_response_mask8(c, v))) return rc;
-    FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * n8, hipMemcpyDeviceToDevice, c->stream));
+    const int first = p * FEA_MODAL_COLS;
+    if ((rc = upload_columns(c, v, phi, first, std::min(FEA_MODAL_COLS, n - first))) || (rc = launch_response_mask8(c, v))) return rc;
+    FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * (size_t)c->ndof * FEA_MODAL_COLS, hipMemcpyDeviceToDevice, c->stream));
   }
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < n; ++k) S.lock_order[k] = k;                   // column k holds the caller's pair k; read in ascending lam
@@ -1649,13 +1585,10 @@ extern "C" int feahip_response_load(feahip_ctx *c, const double *F, int static_c
     for (int k = 0; k < S.n_locked; ++k)
       if (!(S.lam[k] > 0.0)) { c->err = "response_load: lam of mode " + std::to_string(k + 1) + " is not positive: no static correction"; return FEAHIP_EINVAL; }
   }
+  for (int i = 0; i < c->ndof; ++i)
+    if (!std::isfinite(F[i])) { c->err = "response_load: F is not finite"; return FEAHIP_EINVAL; }
   std::vector<double> tmp((size_t)c->ndof);
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) {
-      const double f = F[(size_t)a * 3 + j];
-      if (!std::isfinite(f)) { c->err = "response_load: F is not finite"; return FEAHIP_EINVAL; }
-      tmp[(size_t)lib_id(c, a) * 3 + j] = f;
-    }
+  to_library(view_of(c), 3, 3, F, tmp.data());
   return response_load(c, tmp.data(), static_correction, solver_type, tolerance, max_iterations, q, iters, resid);
 }
 
@@ -1664,15 +1597,7 @@ extern "C" int feahip_get_response_static(feahip_ctx *c, double *u_s)
   CTX_GUARD_NOK(c);
   if (!u_s) return FEAHIP_EINVAL;
   const int rc = response_loaded(c, "get_response_static");
-  return rc ? rc : get_node_vec(c, c->response.d_us, u_s);
-}
-
-// [3N] of T in library ids into the caller's dof order
-template <class T>
-static void to_caller_dofs(const feahip_ctx *c, const T *lib, T *out)
-{
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = lib[(size_t)lib_id(c, a) * 3 + j];
+  return rc ? rc : get_view(c, c->response.d_us, u_s, 3, 3);
 }
 
 extern "C" int feahip_response_sweep(feahip_ctx *c, int n_freq, const double *omega, double alpha, double beta_k,
@@ -1694,8 +1619,8 @@ extern "C" int feahip_response_sweep(feahip_ctx *c, int n_freq, const double *om
   std::vector<double> pk((size_t)c->ndof);
   std::vector<int> at((size_t)c->ndof);
   if ((rc = response_sweep(c, false, n_freq, omega, alpha, beta_k, zeta, pk.data(), at.data(), n_probe, probe, probe_re, probe_im))) return rc;
-  to_caller_dofs(c, pk.data(), peak);
-  to_caller_dofs(c, at.data(), peak_at);
+  to_caller(view_of(c), 3, 3, pk.data(), peak);
+  to_caller(view_of(c), 3, 3, at.data(), peak_at);
   return FEAHIP_OK;
 }
 
@@ -1708,8 +1633,8 @@ extern "C" int feahip_response_field(feahip_ctx *c, double omega, double alpha, 
   if ((rc = response_loaded(c, "response_field"))) return rc;
   std::vector<double> a((size_t)c->ndof), b((size_t)c->ndof);
   if ((rc = response_sweep(c, true, 1, &omega, alpha, beta_k, zeta, a.data(), b.data(), 0, nullptr, nullptr, nullptr))) return rc;
-  to_caller_dofs(c, a.data(), re);
-  to_caller_dofs(c, b.data(), im);
+  to_caller(view_of(c), 3, 3, a.data(), re);
+  to_caller(view_of(c), 3, 3, b.data(), im);
   return FEAHIP_OK;
 }
 
@@ -1739,11 +1664,8 @@ extern "C" int feahip_solve_buckling(feahip_ctx *c, int n_modes, double tol, int
 {
   CTX_GUARD(c);
   if (iters) *iters = 0;
-  if (n_modes < 1 || n_modes > FEA_MODAL_COLS) { c->err = "solve_buckling: n_modes must be in [1, 8]"; return FEAHIP_EINVAL; }
-  if (!(tol > 0.0) || !std::isfinite(tol)) { c->err = "solve_buckling: tolerance must be positive"; return FEAHIP_EINVAL; }
-  if (max_iter < 0) { c->err = "solve_buckling: max_iterations must not be negative"; return FEAHIP_EINVAL; }
-  if (!factor) { c->err = "solve_buckling: null factor"; return FEAHIP_EINVAL; }
   int rc;
+  if ((rc = eigen_args(c, "solve_buckling", n_modes, FEA_MODAL_COLS, tol, max_iter, factor, "factor"))) return rc;
   if ((rc = solve2_refused(c, "solve_buckling"))) return rc;
   double v[FEA_MODAL_COLS];
   for (int j = 0; j < n_modes; ++j) { v[j] = NAN; factor[j] = NAN; if (nu) nu[j] = NAN; if (resid) resid[j] = NAN; }
@@ -1761,15 +1683,7 @@ extern "C" int feahip_get_buckling_modes(feahip_ctx *c, int first, int count, do
   if (!c->modal.have_buckling) { c->err = "get_buckling_modes: no buckling modes held (feahip_solve_buckling first)"; return FEAHIP_ESTATE; }
   if (first < 0 || count < 0 || first + count > FEA_MODAL_COLS) { c->err = "get_buckling_modes: modes [first, first + count) outside the eight held"; return FEAHIP_EINVAL; }
   if (!phi) { c->err = "get_buckling_modes: null phi"; return FEAHIP_EINVAL; }
-  std::vector<double> tmp((size_t)c->ndof);
-  for (int k = 0; k < count; ++k) {
-    const int rc = modal_get(c, first + k, tmp.data());
-    if (rc) return rc;
-    double *out = phi + (size_t)k * c->ndof;
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 3; ++j) out[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
-  }
-  return FEAHIP_OK;
+  return modes_to_caller(c, view_of(c), first, count, phi, modal_get);
 }
 
 extern "C" int feahip_geometric_spmv(feahip_ctx *c, const double *x, double *y)
@@ -1780,9 +1694,9 @@ extern "C" int feahip_geometric_spmv(feahip_ctx *c, const double *x, double *y)
   if ((rc = solve2_refused(c, "geometric_spmv")) || (rc = geom_assemble(c))) return rc;
   BucklingState &B = c->buckling;
   if (!B.d_x4) FEA_HIP_CHECK(c, hipMalloc((void **)&B.d_x4, sizeof(double) * 4 * (size_t)c->N));
-  if ((rc = set_node4(c, B.d_x4, x))) return rc;
+  if ((rc = set_view(c, B.d_x4, x, 3, 4))) return rc;
   if ((rc = launch_block_product(c, B.d_kg, B.d_x4, c->d_q))) return rc;
-  return get_node_vec(c, c->d_q, y);
+  return get_view(c, c->d_q, y, 3, 3);
 }
 
 // ---- two-column solve (kernels_solve2.hip) ---------------------------------
@@ -1802,7 +1716,7 @@ extern "C" int feahip_solve_slae2(feahip_ctx *c, int type, double tol, int max_i
   if (!f2) { c->err = "solve_slae2: null second right-hand side"; return FEAHIP_EINVAL; }
   int rc;
   if ((rc = solve2_ready(c, "solve_slae2"))) return rc;
-  if ((rc = set_node_vec(c, c->d_q, f2))) return rc;             // (q is scratch of any solve)
+  if ((rc = set_view(c, c->d_q, f2, 3, 3))) return rc;           // (q is scratch of any solve)
   if ((rc = launch_interleave(c, c->d_f, c->d_q, c->d2_f))) return rc;
   return solve_pcg2(c, type, tol, max_iter, iters, resid);
 }
@@ -1811,7 +1725,7 @@ extern "C" int feahip_get_solution2(feahip_ctx *c, double *u2)
 {
   CTX_GUARD(c);
   if (!c->d_u2) { c->err = "get_solution2 before solve_slae2"; return FEAHIP_ESTATE; }
-  return get_node_vec(c, c->d_u2, u2);
+  return get_view(c, c->d_u2, u2, 3, 3);
 }
 
 extern "C" int feahip_spmv2(feahip_ctx *c, const double *x2, double *y2)
@@ -1820,12 +1734,12 @@ extern "C" int feahip_spmv2(feahip_ctx *c, const double *x2, double *y2)
   if (!x2 || !y2) return FEAHIP_EINVAL;
   int rc;
   if ((rc = solve2_ready(c, "spmv2"))) return rc;
-  if ((rc = set_node_vec(c, c->d_p, x2)) || (rc = set_node_vec(c, c->d_q, x2 + (size_t)c->ndof))) return rc;
+  if ((rc = set_view(c, c->d_p, x2, 3, 3)) || (rc = set_view(c, c->d_q, x2 + (size_t)c->ndof, 3, 3))) return rc;
   if ((rc = launch_interleave(c, c->d_p, c->d_q, c->d2_p))) return rc;
   if ((rc = launch_spmv2(c, c->d2_p, c->d2_q))) return rc;
   if ((rc = launch_deinterleave(c, c->d2_q, c->d_p, c->d_q))) return rc;
-  if ((rc = get_node_vec(c, c->d_p, y2))) return rc;
-  return get_node_vec(c, c->d_q, y2 + (size_t)c->ndof);
+  if ((rc = get_view(c, c->d_p, y2, 3, 3))) return rc;
+  return get_view(c, c->d_q, y2 + (size_t)c->ndof, 3, 3);
 }
 
 extern "C" int feahip_solve_arclength(feahip_ctx *c, double lambda_max, int max_steps, int max_newton, double desired_tolerance,
@@ -1891,14 +1805,11 @@ extern "C" int feahip_get_shape_gradients(feahip_ctx *c, double *grads, double *
   int rc = ensure_state(c);                                  // allocates F / sigma (the kernel writes them too)
   if (rc) return rc;
   const size_t ng = (size_t)c->E * c->G * 3 * c->npe, nd = (size_t)c->E * c->G;
-  double *dg = nullptr, *dd = nullptr;
-  FEA_HIP_CHECK(c, hipMalloc((void **)&dg, sizeof(double) * ng));
-  if (hipMalloc((void **)&dd, sizeof(double) * nd) != hipSuccess) { (void)hipFree(dg); c->err = "out of device memory"; return FEAHIP_ENOMEM; }
-  rc = launch_state_export(c, dg, dd);
-  if (!rc) rc = get_vec(c, dg, grads, ng);
-  if (!rc) rc = get_vec(c, dd, detj, nd);
-  (void)hipFree(dg); (void)hipFree(dd);
-  return rc;
+  DevTemp dg, dd;
+  if ((rc = dg.alloc(c, ng))) return rc;
+  if (dd.alloc(c, nd)) { c->err = "out of device memory"; return FEAHIP_ENOMEM; }
+  if ((rc = launch_state_export(c, dg.p, dd.p)) || (rc = get_vec(c, dg.p, grads, ng))) return rc;
+  return get_vec(c, dd.p, detj, nd);
 }
 
 extern "C" int feahip_matrix_nnz(feahip_ctx *c, long long *nnz)
@@ -1959,11 +1870,11 @@ extern "C" int feahip_spmv(feahip_ctx *c, const double *x, double *y)
 {
   CTX_GUARD(c);
   if (!x || !y) return FEAHIP_EINVAL;
-  int rc = set_node_vec(c, c->d_p, x);
+  int rc = set_view(c, c->d_p, x, 3, 3);
   if (rc) return rc;
   rc = launch_spmv(c, c->d_p, c->d_q);
   if (rc) return rc;
-  return get_node_vec(c, c->d_q, y);
+  return get_view(c, c->d_q, y, 3, 3);
 }
 
 extern "C" int feahip_apply_preconditioner(feahip_ctx *c, const double *r, double *z)
@@ -1971,15 +1882,11 @@ extern "C" int feahip_apply_preconditioner(feahip_ctx *c, const double *r, doubl
   CTX_GUARD(c);
   if (!r || !z) return FEAHIP_EINVAL;
   if (!c->k_valid) { c->err = "apply_preconditioner: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
-  int rc = set_node_vec(c, c->d_r, r);
+  int rc = set_view(c, c->d_r, r, 3, 3);
   if (rc) return rc;
   const double *dz = nullptr;
   if ((rc = precond_apply(c, c->d_r, &dz))) return rc;
-  std::vector<double> tmp((size_t)c->ndof, 0.0);                 // rows of other ranks: 0
-  if ((rc = get_vec(c, dz + (size_t)3 * c->row0, tmp.data() + (size_t)3 * c->row0, (size_t)3 * (c->row1 - c->row0)))) return rc;
-  for (int a = 0; a < c->N; ++a)
-    for (int j = 0; j < 3; ++j) z[(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
-  return FEAHIP_OK;
+  return get_view(c, dz, z, 3, 3, true);                         // rows of other ranks: 0
 }
 
 // z = M^-1 r on every rank of a group at once: what the group's PCG applies.  Under kind 2 the operator spans the
@@ -1996,17 +1903,14 @@ extern "C" int feahip_group_apply_preconditioner(feahip_ctx **ctxs, int n, const
     if (!r[k] || !z[k]) return FEAHIP_EINVAL;
     CTX_GUARD(c);
     if (!c->k_valid) { c->err = "apply_preconditioner: no stiffness matrix assembled"; return FEAHIP_ESTATE; }
-    if ((rc = set_node_vec(c, c->d_r, r[k]))) return rc;
+    if ((rc = set_view(c, c->d_r, r[k], 3, 3))) return rc;
   }
   std::vector<const double *> dz((size_t)n, nullptr);
   if ((rc = surface_error(R[0], R, dist_precond_apply(R, dz.data())))) return rc;
   for (int k = 0; k < n; ++k) {
     feahip_ctx *c = R[k];
     FEA_HIP_CHECK(c, hipSetDevice(c->device));
-    std::vector<double> tmp((size_t)c->ndof, 0.0);               // rows of other ranks: 0
-    if ((rc = get_vec(c, dz[k] + (size_t)3 * c->row0, tmp.data() + (size_t)3 * c->row0, (size_t)3 * (c->row1 - c->row0)))) return rc;
-    for (int a = 0; a < c->N; ++a)
-      for (int j = 0; j < 3; ++j) z[k][(size_t)a * 3 + j] = tmp[(size_t)lib_id(c, a) * 3 + j];
+    if ((rc = get_view(c, dz[k], z[k], 3, 3, true))) return rc;  // rows of other ranks: 0
   }
   return FEAHIP_OK;
 }
@@ -2106,9 +2010,11 @@ extern "C" int feahip_amg_level(feahip_ctx *c, int level, long long *counts, dou
       pos++;
     }
     rowptr[a + 1] = (int)pos;
-    agg[a] = e.agg[(size_t)la]; type[a] = e.type[(size_t)la];
-    for (int d = 0; d < 3; ++d) doff[(size_t)a * 3 + d] = e.doff[(size_t)la * 3 + d];
   }
+  const NodeView v = view_of(c);
+  to_caller(v, 1, 1, e.agg.data(), agg);
+  to_caller(v, 1, 1, e.type.data(), type);
+  to_caller(v, 3, 3, e.doff.data(), doff);
   return FEAHIP_OK;
 }
 
