@@ -1645,7 +1645,94 @@ extern "C" int feahip_host_response_coefficients(int n_modes, const double *lam,
   return response_coefficients(n_modes, lam, q, nullptr, n_freq, omega, alpha, beta_k, zeta, static_correction, coef, nullptr);
 }
 
-extern "C" int feahip_host_modal_ritz(int n_dirs, const double *gram_m, const double *gram_k, double *theta, double *coef)
+// ---- transient response by mode superposition, base excitation (kernels_transient.hip, transient_table.cpp) -------------
+extern "C" int feahip_response_base_load(feahip_ctx *c, const double *dir, int static_correction, int solver_type,
+                                         double tolerance, int max_iterations, double *q, double *gamma, double *eff_mass,
+                                         double *total_mass, int *iters, double *resid)
+{
+  CTX_GUARD(c);
+  if (iters) *iters = 0;
+  if (resid) *resid = 0.0;
+  if (!dir) { c->err = "response_base_load: null dir"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = modal_ready(c, "response_base_load"))) return rc;
+  const ModalState &S = c->modal;
+  if (!S.have_locked) { c->err = "response_base_load: no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)"; return FEAHIP_ESTATE; }
+  if (static_correction) {
+    if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "response_base_load: unknown solver type"; return FEAHIP_EINVAL; }
+    if (max_iterations <= 0) { c->err = "response_base_load: max_iterations must be positive"; return FEAHIP_EINVAL; }
+    if (S.shift > 0.0) { c->err = "response_base_load: the modes come from a solve with a shift, a body whose K may be singular: no static correction"; return FEAHIP_EINVAL; }
+    for (int k = 0; k < S.n_locked; ++k)
+      if (!(S.lam[k] > 0.0)) { c->err = "response_base_load: lam of mode " + std::to_string(k + 1) + " is not positive: no static correction"; return FEAHIP_EINVAL; }
+  }
+  if (!std::isfinite(dir[0]) || !std::isfinite(dir[1]) || !std::isfinite(dir[2])) { c->err = "response_base_load: dir is not finite"; return FEAHIP_EINVAL; }
+  if (dir[0] == 0.0 && dir[1] == 0.0 && dir[2] == 0.0) { c->err = "response_base_load: dir is zero"; return FEAHIP_EINVAL; }
+  // r = dir on every node, the prescribed ones included, in the node layout (xt is free outside a step); y = M r
+  std::vector<double> r4(4 * (size_t)c->N), mr((size_t)c->ndof);
+  for (int i = 0; i < c->N; ++i) { r4[4 * (size_t)i] = dir[0]; r4[4 * (size_t)i + 1] = dir[1]; r4[4 * (size_t)i + 2] = dir[2]; r4[4 * (size_t)i + 3] = 0.0; }
+  FEA_HIP_CHECK(c, hipMemcpyAsync(c->mass.d_xt, r4.data(), sizeof(double) * r4.size(), hipMemcpyHostToDevice, c->stream));
+  FEA_HIP_CHECK(c, hipMemsetAsync(c->d_q, 0, sizeof(double) * (size_t)c->ndof, c->stream));
+  if ((rc = launch_mass_product(c, c->mass.d_xt, c->d_q)) || (rc = launch_base_load(c, c->d_q, c->d_f))) return rc;
+  FEA_HIP_CHECK(c, hipMemcpyAsync(mr.data(), c->d_q, sizeof(double) * mr.size(), hipMemcpyDeviceToHost, c->stream));
+  FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+  long double total = 0;                                             // r' M r, the dofs in the library's order
+  for (int i = 0; i < c->ndof; ++i) total += (long double)dir[i % 3] * mr[i];
+  double qs[FEA_MODAL_MAX_LOCKED];
+  if ((rc = response_load(c, nullptr, static_correction, solver_type, tolerance, max_iterations, qs, iters, resid))) return rc;
+  for (int k = 0; k < S.n_locked; ++k) {
+    if (q) q[k] = qs[k];
+    if (gamma) gamma[k] = -qs[k];
+    if (eff_mass) eff_mass[k] = qs[k] * qs[k];
+  }
+  if (total_mass) *total_mass = (double)total;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta_k,
+                                         const double *zeta, int quantity, double *peak, int *peak_at, int n_probe,
+                                         const int *probe_dof, double *probe, int n_snap, const int *snap_step, double *snap)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = solve2_refused(c, "response_transient")) || (rc = response_loaded(c, "response_transient"))) return rc;
+  if (!g || !peak || !peak_at) { c->err = "response_transient: null g, peak or peak_at"; return FEAHIP_EINVAL; }
+  if (n_steps < 1 || n_steps > FEA_TRANSIENT_MAX_STEPS) { c->err = "response_transient: n_steps must be in [1, 1048576]"; return FEAHIP_EINVAL; }
+  if (n_probe < 0 || n_probe > 64) { c->err = "response_transient: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
+  if (n_probe > 0 && (!probe_dof || !probe)) { c->err = "response_transient: null probe arrays"; return FEAHIP_EINVAL; }
+  if (n_snap < 0 || n_snap > 4096) { c->err = "response_transient: n_snap must be in [0, 4096]"; return FEAHIP_EINVAL; }
+  if (n_snap > 0 && (!snap_step || !snap)) { c->err = "response_transient: null snapshot arrays"; return FEAHIP_EINVAL; }
+  int lib_probe[64];
+  for (int r = 0; r < n_probe; ++r) {
+    if (probe_dof[r] < 0 || probe_dof[r] >= c->ndof) { c->err = "response_transient: probe dof outside [0, 3N)"; return FEAHIP_EINVAL; }
+    lib_probe[r] = 3 * lib_id(c, probe_dof[r] / 3) + probe_dof[r] % 3;
+  }
+  for (int s = 0; s < n_snap; ++s)
+    if (snap_step[s] < 0 || snap_step[s] > n_steps) { c->err = "response_transient: snapshot step outside [0, n_steps]"; return FEAHIP_EINVAL; }
+  const size_t nd = (size_t)c->ndof;
+  std::vector<double> pk(nd), fields((size_t)n_snap * nd);
+  std::vector<int> at(nd);
+  if ((rc = response_transient(c, n_steps, dt, g, alpha, beta_k, zeta, quantity, pk.data(), at.data(), n_probe, lib_probe, probe,
+                               n_snap, snap_step, fields.data()))) return rc;
+  to_caller(view_of(c), 3, 3, pk.data(), peak);
+  to_caller(view_of(c), 3, 3, at.data(), peak_at);
+  for (int s = 0; s < n_snap; ++s) to_caller(view_of(c), 3, 3, fields.data() + (size_t)s * nd, snap + (size_t)s * nd);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_host_transient_coefficients(int n_modes, const double *lam, const double *q, int n_steps, double dt,
+                                                  const double *g, double alpha, double beta_k, const double *zeta,
+                                                  int static_correction, int quantity, double *coef)
+{
+  int rc;
+  if (!coef) return FEAHIP_EINVAL;
+  if ((rc = transient_check(n_modes, lam, q, n_steps, dt, g, alpha, beta_k, zeta, static_correction, quantity, nullptr))) return rc;
+  TransientTable *T = transient_begin(n_modes, lam, q, nullptr, n_steps, dt, alpha, beta_k, zeta, static_correction, quantity);
+  rc = transient_rows(T, g, n_steps + 1, coef, nullptr);
+  transient_end(T);
+  return rc;
+}
+
+extern "C" int feahip_host_modal_ritz(int n_dirs,const double *gram_m, const double *gram_k, double *theta, double *coef)
 {
   if (!gram_m || !gram_k || !theta || !coef || (n_dirs != 8 && n_dirs != 16 && n_dirs != 24)) return FEAHIP_EINVAL;
   return modal_ritz(n_dirs, gram_m, gram_k, FEA_MODAL_COLS, theta, coef);
@@ -2069,6 +2156,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (rk) return rk;
     if (c->response.swept_freq == 0) { c->err = "time_kernel: no sweep made yet (feahip_response_sweep first)"; return FEAHIP_ESTATE; }
   }
+  if (what == 25) {                                    // the last chunk of the last transient, the store and u_s as it left them
+    const int rk = response_loaded(c, "time_kernel(25)");
+    if (rk) return rk;
+    if (c->response.trans_rows == 0) { c->err = "time_kernel: no transient made yet (feahip_response_transient first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2092,6 +2184,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 21: return launch_damp_add(c, 1.0, 1.0);
     case 22: return launch_damp_residual(c, 1.0, 1.0);
     case 23: case 24: return time_response_kernel(c, what);
+    case 25: return time_transient_kernel(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

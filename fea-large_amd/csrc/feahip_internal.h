@@ -544,6 +544,8 @@ struct ResponseState {
   int gen = -1;                        // ... for the filling ModalState::lock_gen == gen of the store
   int correction = 0;                  // it was made with the static correction
   int swept_freq = 0;                  // frequencies in d_coef from the last sweep (feahip_time_kernel 23)
+  int trans_rows = 0;                  // rows in d_coef from the last chunk of the last transient (feahip_time_kernel 25) ...
+  int trans_step0 = 0;                 // ... and the step of its first row
   void release() { dev_free({d_us, d_part, d_q, d_coef, d_out}); *this = ResponseState(); }
 };
 
@@ -834,7 +836,8 @@ int launch_response_mask8(feahip_ctx *c, double *d_v8);                 // a blo
 // FEAHIP_EINVAL and *why for a negative or non-finite input and for a coefficient that is not finite
 int response_coefficients(int n_modes, const double *lam, const double *q, const int *order, int n_freq, const double *omega,
                           double alpha, double beta, const double *zeta, int correction, double *coef, std::string *why);
-// F (library ids, host) projected on the modes held and, with correction, K u_s = F solved; q[n_locked] ascending
+// F (library ids, host; null: f holds it already, zero on the prescribed dofs) projected on the modes held and, with
+// correction, K u_s = F solved; q[n_locked] ascending
 int response_load(feahip_ctx *c, const double *h_F, int correction, int solver_type, double tol, int max_it, double *q,
                   int *iters, double *resid);
 // one launch of k_response_sweep over the table of n_freq frequencies: peak / peak_at, or (field, n_freq = 1) re / im,
@@ -842,6 +845,25 @@ int response_load(feahip_ctx *c, const double *h_F, int correction, int solver_t
 int response_sweep(feahip_ctx *c, bool field, int n_freq, const double *omega, double alpha, double beta, const double *zeta,
                    double *h_out0, void *h_out1, int n_probe, const int *probe, double *probe_re, double *probe_im);
 int time_response_kernel(feahip_ctx *c, int what);                      // feahip_time_kernel 23 (sweep), 24 (projection)
+// transient_table.cpp -- the coefficient rows of a transient, host only: the exact propagator of every mode in long double.
+// transient_check: FEAHIP_EINVAL and *why for what both transient entries refuse.  transient_begin: mode k of the arrays
+// at column order[k] (null: k).  transient_rows: the rows of the next `count` steps, coef[count][64], zero past the modes;
+// FEAHIP_EINVAL and *why for an entry that is not finite
+struct TransientTable;
+int transient_check(int n_modes, const double *lam, const double *q, int n_steps, double dt, const double *g, double alpha,
+                    double beta, const double *zeta, int correction, int quantity, std::string *why);
+TransientTable *transient_begin(int n_modes, const double *lam, const double *q, const int *order, int n_steps, double dt,
+                                double alpha, double beta, const double *zeta, int correction, int quantity);
+int transient_rows(TransientTable *T, const double *g, int count, double *coef, std::string *why);
+void transient_end(TransientTable *T);
+// kernels_transient.hip -- transient response by mode superposition on the load held, and the base-excitation load
+int launch_base_load(feahip_ctx *c, const double *d_mr, double *d_f);   // f = -(M r) on the free dofs, 0 on the prescribed
+// the chunked launches of k_transient_sweep over the whole history: peak / peak_at [3N] and the snapshots [n_snap][3N] in
+// library ids, the histories of the probe dofs (library ids) on the host, [n_probe][n_steps + 1]
+int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta, const double *zeta,
+                       int quantity, double *h_peak, int *h_at, int n_probe, const int *probe, double *h_probe, int n_snap,
+                       const int *snap_step, double *h_snap);
+int time_transient_kernel(feahip_ctx *c);                               // feahip_time_kernel 25
 // kernels_buckling.hip -- K_sigma as one double per block, and the lowest eigenpairs of K_sigma phi = nu K phi
 int geom_assemble(feahip_ctx *c);                                       // buckling.d_kg at the current nodes
 int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters);

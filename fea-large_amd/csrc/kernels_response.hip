@@ -241,10 +241,12 @@ int response_load(feahip_ctx *c, const double *h_F, int correction, int solver_t
   if ((rc = ensure_response(c))) return rc;
   const int n = S.n_locked, panels = (n + MC - 1) / MC;
   const size_t nd = (size_t)c->ndof;
-  // f <- F, zero on the prescribed dofs; q = Q' f
-  FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_f, h_F, sizeof(double) * nd, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_response_mask, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, c->stream, nd, 0,
-                     (const uint8_t *)c->d_dofmask, c->d_f);
+  // f <- F, zero on the prescribed dofs (the base load is made there: kernels_transient.hip); q = Q' f
+  if (h_F) {
+    FEA_HIP_CHECK(c, hipMemcpyAsync(c->d_f, h_F, sizeof(double) * nd, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_response_mask, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, c->stream, nd, 0,
+                       (const uint8_t *)c->d_dofmask, c->d_f);
+  }
   enq_project(c, panels);
   hipLaunchKernelGGL(k_response_reduce, dim3(panels * MC), dim3(256), 0, c->stream, project_grid(c),
                      (const double *)R.d_part, R.d_q);
@@ -319,6 +321,7 @@ int response_sweep(feahip_ctx *c, bool field, int n_freq, const double *omega, d
   if (field) enq_sweep<true>(c, panels, n_freq); else enq_sweep<false>(c, panels, n_freq);
   FEA_HIP_CHECK(c, hipGetLastError());
   R.swept_freq = n_freq;
+  R.trans_rows = 0;                                                    // (a transient's last chunk is gone from d_coef)
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_out0, R.d_out, sizeof(double) * nd, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_out1, R.d_out + nd, (field ? sizeof(double) : sizeof(int)) * nd, hipMemcpyDeviceToHost, c->stream));
   // the probes: their rows of Q and of u_s read back, the kernel's sum in the kernel's order on the host

@@ -173,6 +173,11 @@ ABI = {
     "feahip_response_sweep": [C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _ip, C.c_int, _ip, _dp, _dp],
     "feahip_response_field": [C.c_void_p, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp],
     "feahip_host_response_coefficients": [C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp],
+    "feahip_response_base_load": [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp],
+    "feahip_response_transient": [C.c_void_p, C.c_int, C.c_double, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp, _ip,
+                                  C.c_int, _ip, _dp, C.c_int, _ip, _dp],
+    "feahip_host_transient_coefficients": [C.c_int, _dp, _dp, C.c_int, C.c_double, _dp, C.c_double, C.c_double, _dp, C.c_int,
+                                           C.c_int, _dp],
     "feahip_solve_buckling": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
     "feahip_get_buckling_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_geometric_spmv": [C.c_void_p, _dp, _dp],
@@ -181,6 +186,9 @@ ABI = {
 MODAL_COLS = 8                                          # FEA_MODAL_COLS of include/fea_hip.h
 MODAL_MAX_LOCKED = 64                                   # FEA_MODAL_MAX_LOCKED
 RESPONSE_MAX_FREQ = 4096                                # FEA_RESPONSE_MAX_FREQ
+TRANSIENT_MAX_STEPS = 1048576                           # FEA_TRANSIENT_MAX_STEPS
+TRANSIENT_CHUNK = 8064                                  # FEA_TRANSIENT_CHUNK
+TRANSIENT_SHAPES = ("step", "ramp", "half-sine")        # FEA_SHAPE_* of host/fea_host.h
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
 COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
@@ -232,6 +240,9 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("transient_steps", C.c_int), ("transient_dt", C.c_double), ("transient_zeta", C.c_double),
+        ("transient_static", C.c_int), ("transient_shape", C.c_int), ("transient_rise", C.c_double),
+        ("transient_has_base", C.c_int), ("transient_base", C.c_double * 3),
         ("harmonic_count", C.c_int), ("harmonic_from", C.c_double), ("harmonic_to", C.c_double),
         ("harmonic_zeta", C.c_double), ("harmonic_static", C.c_int),
         ("damping_alpha", C.c_double), ("damping_beta", C.c_double),
@@ -339,6 +350,24 @@ def host_response_coefficients(lam, q, omega, alpha=0.0, beta=0.0, zeta=None, st
     if rc != 0:
         raise FeaHipError(f"feahip_host_response_coefficients refused its input ({rc})")
     return coef[:, 0, :] + 1j * coef[:, 1, :]
+
+
+def host_transient_coefficients(lam, q, g, dt, alpha=0.0, beta=0.0, zeta=None, static_correction=True, quantity=0):
+    """feahip_host_transient_coefficients (no device): the table a[n_steps + 1][64] of a transient under q_k g(t), g given
+    at t_n = n dt and linear in between, every mode advanced from rest by its exact propagator.  quantity 0: q_k(t_n), or
+    with the correction q_k(t_n) - q_k g_n / lam_k; 1: q_k'(t_n); 2: q_k g_n - d_k q_k' - lam_k q_k.  Zero past the modes
+    given.  Raises where the transient refuses."""
+    lam, q = np.ascontiguousarray(lam, dtype=np.float64), np.ascontiguousarray(q, dtype=np.float64)
+    g = np.ascontiguousarray(np.atleast_1d(g), dtype=np.float64)
+    z = None if zeta is None else np.ascontiguousarray(np.broadcast_to(np.asarray(zeta, dtype=np.float64), lam.shape))
+    assert lam.shape == q.shape and lam.ndim == 1 and g.ndim == 1
+    coef = np.zeros((max(len(g), 1), MODAL_MAX_LOCKED))
+    rc = load_library().feahip_host_transient_coefficients(len(lam), _d(lam), _d(q), len(g) - 1, float(dt), _d(g), float(alpha),
+                                                           float(beta), None if z is None else _d(z),
+                                                           int(bool(static_correction)), int(quantity), _d(coef))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_transient_coefficients refused its input ({rc})")
+    return coef
 
 
 def host_rayleigh(omega1, zeta1, omega2, zeta2):
@@ -501,6 +530,35 @@ class Deck:
                 raise ValueError("harmonic_count needs the locked modes: modal_count or modal_shift")
             if self.harmonic_static and self.modal_shift:
                 raise ValueError("harmonic_static (the static correction) and a non-zero modal_shift exclude each other")
+        # (transient :steps n :dt x :shape step|ramp|half-sine :rise T :zeta z :static-correction t :base (bx by bz)): the
+        # time history feasolver_hip runs on the locked modes after the harmonic sweep, under the surface load of the state
+        # reached or, with a base direction, under the base load
+        self.transient_steps = int(kw.get("transient_steps", 0))
+        self.transient_dt = float(kw.get("transient_dt", 0.0))
+        self.transient_zeta = float(kw.get("transient_zeta", 0.0))
+        self.transient_static = bool(kw.get("transient_static", True))
+        self.transient_shape = kw.get("transient_shape", "step")
+        self.transient_rise = float(kw.get("transient_rise", 0.0))
+        base = kw.get("transient_base")
+        self.transient_base = None if base is None else tuple(float(b) for b in base)
+        if not 0 <= self.transient_steps <= TRANSIENT_MAX_STEPS:
+            raise ValueError("transient_steps: 1 to 1048576")
+        if self.transient_steps:
+            if not (0.0 < self.transient_dt < np.inf):
+                raise ValueError("transient_dt: positive and finite")
+            if not (0.0 <= self.transient_zeta < np.inf):
+                raise ValueError("transient_zeta: finite and not negative")
+            if self.transient_shape not in TRANSIENT_SHAPES:
+                raise ValueError("transient_shape: step, ramp or half-sine")
+            if self.transient_shape != "step" and not (0.0 < self.transient_rise < np.inf):
+                raise ValueError("transient_rise: positive and finite for a ramp or a half-sine")
+            if self.transient_base is not None and (len(self.transient_base) != 3 or not np.all(np.isfinite(self.transient_base))
+                                                    or not any(self.transient_base)):
+                raise ValueError("transient_base: three finite components, not all zero")
+            if not (self.modal_count or self.modal_shift):
+                raise ValueError("transient_steps needs the locked modes: modal_count or modal_shift")
+            if self.transient_static and self.modal_shift:
+                raise ValueError("transient_static (the static correction) and a non-zero modal_shift exclude each other")
         # (buckling :modes N :tolerance t :max M): the load factors feasolver_hip computes after its last step
         self.buckling_modes = int(kw.get("buckling_modes", 0))
         self.buckling_tolerance = float(kw.get("buckling_tolerance", 1e-8))
@@ -561,6 +619,11 @@ class Deck:
                 **(dict(harmonic_count=fd.harmonic_count, harmonic_from=fd.harmonic_from, harmonic_to=fd.harmonic_to,
                         harmonic_zeta=fd.harmonic_zeta, harmonic_static=bool(fd.harmonic_static))
                    if fd.harmonic_count else {}),
+                **(dict(transient_steps=fd.transient_steps, transient_dt=fd.transient_dt, transient_zeta=fd.transient_zeta,
+                        transient_static=bool(fd.transient_static), transient_shape=TRANSIENT_SHAPES[fd.transient_shape],
+                        transient_rise=fd.transient_rise,
+                        transient_base=[fd.transient_base[k] for k in range(3)] if fd.transient_has_base else None)
+                   if fd.transient_steps else {}),
                 **(dict(buckling_modes=fd.buckling_modes, buckling_tolerance=fd.buckling_tolerance,
                         buckling_max=fd.buckling_max) if fd.buckling_modes else {}))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
@@ -618,6 +681,14 @@ class Deck:
         if getattr(self, "harmonic_count", 0):
             fd.harmonic_count, fd.harmonic_from, fd.harmonic_to = int(self.harmonic_count), float(self.harmonic_from), float(self.harmonic_to)
             fd.harmonic_zeta, fd.harmonic_static = float(self.harmonic_zeta), int(bool(self.harmonic_static))
+        if getattr(self, "transient_steps", 0):
+            fd.transient_steps, fd.transient_dt, fd.transient_zeta = int(self.transient_steps), float(self.transient_dt), float(self.transient_zeta)
+            fd.transient_static, fd.transient_shape = int(bool(self.transient_static)), TRANSIENT_SHAPES.index(self.transient_shape)
+            fd.transient_rise = float(self.transient_rise)
+            if self.transient_base is not None:
+                fd.transient_has_base = 1
+                for k in range(3):
+                    fd.transient_base[k] = self.transient_base[k]
         if len(self.contact_faces) and len(self.contact_obstacles):
             # (kept on the deck: the struct borrows the arrays)
             self._contact_kind, self._contact_geom = obstacle_arrays(self.contact_obstacles)
@@ -1116,6 +1187,39 @@ class FeaSolver:
         z, zp = self._zeta(zeta)
         self._chk(self._lib.feahip_response_field(self._ctx, float(omega), float(alpha), float(beta), zp, _d(re), _d(im)))
         return re + 1j * im
+
+    # ---- transient response by mode superposition, base excitation -------------
+    def response_base_load(self, direction, static_correction=True, solver_type=None, tolerance=None, max_iterations=None):
+        """feahip_response_base_load: the load F = -M r of a rigid base acceleration along `direction` (r the translation on
+        all dofs), held like the load of response_load.  Returns (q[n_locked], the participation factors gamma = -q, the
+        effective masses gamma^2, the total mass r' M r, PCG iterations, PCG residual)."""
+        d = self.deck
+        r = np.ascontiguousarray(direction, dtype=np.float64).reshape(3)
+        q, gamma, eff = np.zeros(MODAL_MAX_LOCKED), np.zeros(MODAL_MAX_LOCKED), np.zeros(MODAL_MAX_LOCKED)
+        total, it, res = C.c_double(0), C.c_int(0), C.c_double(0)
+        self._chk(self._lib.feahip_response_base_load(
+            self._ctx, _d(r), int(bool(static_correction)), d.solver_type if solver_type is None else solver_type,
+            d.solver_tolerance if tolerance is None else tolerance,
+            d.solver_max_iter if max_iterations is None else max_iterations, _d(q), _d(gamma), _d(eff), C.byref(total),
+            C.byref(it), C.byref(res)))
+        n = self.locked_count()
+        return q[:n].copy(), gamma[:n].copy(), eff[:n].copy(), total.value, it.value, res.value
+
+    def response_transient(self, g, dt, alpha=0.0, beta=0.0, zeta=None, quantity=0, probes=(), snapshots=()):
+        """feahip_response_transient under the load held times g(t), g[n_steps + 1] at t_n = n dt: (peak[3N] = max_n
+        |u_i(t_n)|, peak_at[3N] = the lowest step that attains it, the histories [n_probe][n_steps + 1] of the probe dofs
+        3 node + axis, the fields [n_snap][3N] at the snapshot steps).  quantity 0 displacement, 1 velocity, 2 acceleration
+        relative to the base."""
+        g = np.ascontiguousarray(np.atleast_1d(g), dtype=np.float64)
+        pr = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        sn = np.ascontiguousarray(snapshots, dtype=np.int32).reshape(-1)
+        peak, at = np.zeros(self.ndof), np.zeros(self.ndof, dtype=np.int32)
+        hist, snap = np.zeros((len(pr), len(g))), np.zeros((len(sn), self.ndof))
+        z, zp = self._zeta(zeta)
+        self._chk(self._lib.feahip_response_transient(self._ctx, len(g) - 1, float(dt), _d(g), float(alpha), float(beta), zp,
+                                                      int(quantity), _d(peak), _i(at), len(pr), _i(pr), _d(hist), len(sn),
+                                                      _i(sn), _d(snap)))
+        return peak, at, hist, snap
 
     # ---- linear buckling ---------------------------------------------------
     def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):

@@ -254,6 +254,78 @@ int fea_harmonic_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char 
   return 0;
 }
 
+/* g(t) of (transient :shape ...) */
+static double transient_shape_at(const fea_deck *d, double t)
+{
+  const double pi = 3.141592653589793;
+  if (d->transient_shape == FEA_SHAPE_RAMP) return t < d->transient_rise ? t / d->transient_rise : 1.0;
+  if (d->transient_shape == FEA_SHAPE_HALF_SINE) return t < d->transient_rise ? sin(pi * t / d->transient_rise) : 0.0;
+  return 1.0;
+}
+
+int fea_transient_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
+{
+  static const char *shape[] = {"step", "ramp", "half-sine"};
+  FILE *log = (FILE *)log_, *f;
+  const int n = d->transient_steps, nd = 3 * d->nodes_count;
+  double *F, *peak, *g, zeta[FEA_MODAL_MAX_LOCKED], gamma[FEA_MODAL_MAX_LOCKED], eff[FEA_MODAL_MAX_LOCKED], total = 0, best = -1.0;
+  int *at, i, k, m = 0, rc, any = 0, best_dof = 0;
+  if (n <= 0) return 0;
+  if ((rc = feahip_get_locked_count(ctx, &m))) return rc;
+  F = (double *)malloc(sizeof(double) * 2 * (size_t)nd);
+  g = (double *)malloc(sizeof(double) * ((size_t)n + 1));
+  at = (int *)malloc(sizeof(int) * (size_t)nd);
+  if (!F || !g || !at) { free(F); free(g); free(at); return FEAHIP_ENOMEM; }
+  peak = F + nd;
+  for (k = 0; k <= n; ++k) g[k] = transient_shape_at(d, k * d->transient_dt);
+  for (k = 0; k < FEA_MODAL_MAX_LOCKED; ++k) zeta[k] = d->transient_zeta;
+  if (!d->transient_has_base) {
+    rc = feahip_get_surface_forces(ctx, F);
+    for (i = 0; !rc && i < nd; ++i) any |= F[i] != 0.0;
+    if (!rc && !any) {
+      if (log) fprintf(log, "Transient: the surface load at the state reached is zero, nothing to run\n");
+      rc = FEAHIP_EINVAL;
+    }
+  }
+  if (!rc && log)
+    fprintf(log, "Transient: %d steps of %.17g, shape %s, %d modes, static correction %s\n", n, d->transient_dt,
+            shape[d->transient_shape], m, d->transient_static ? "on" : "off");
+  if (!rc && d->transient_has_base) {
+    rc = feahip_response_base_load(ctx, d->transient_base, d->transient_static, d->solver_type, d->solver_tolerance,
+                                   d->solver_max_iter, NULL, gamma, eff, &total, NULL, NULL);
+    if (!rc && log) {
+      double sum = 0;
+      for (k = 0; k < m; ++k) {
+        sum += eff[k];
+        fprintf(log, "Effective mass: mode %d, gamma %.17g, m_eff %.17g, cumulative fraction %.17g of total %.17g\n", k + 1,
+                gamma[k], eff[k], sum / total, total);
+      }
+    }
+  } else if (!rc)
+    rc = feahip_response_load(ctx, F, d->transient_static, d->solver_type, d->solver_tolerance, d->solver_max_iter, NULL, NULL, NULL);
+  if (!rc) rc = feahip_response_transient(ctx, n, d->transient_dt, g, d->has_dynamics ? d->damping_alpha : 0.0,
+                                          d->has_dynamics ? d->damping_beta : 0.0, d->transient_zeta > 0 ? zeta : NULL, 0, peak, at,
+                                          0, NULL, NULL, 0, NULL, NULL);
+  if (rc) { free(F); free(g); free(at); return rc; }
+  for (i = 0; i < nd; ++i) if (peak[i] > best) { best = peak[i]; best_dof = i; }
+  if (log)
+    fprintf(log, "Transient peak: |u| = %.17g at t = %.17g, node %d dof %d\n", best, at[best_dof] * d->transient_dt,
+            best_dof / 3 + 1, best_dof % 3);
+  if (msh_path) {
+    if (!(f = fopen(msh_path, "a"))) { free(F); free(g); free(at); return FEAHIP_EINVAL; }
+    fprintf(f, "$NodeData\n1\n\"Transient peak displacement\"\n1\n%f\n3\n0\n3\n%d\n", at[best_dof] * d->transient_dt, d->nodes_count);
+    for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %.9e %.9e %.9e\n", i + 1, peak[3 * i], peak[3 * i + 1], peak[3 * i + 2]);
+    fprintf(f, "$EndNodeData\n");
+    fprintf(f, "$NodeData\n1\n\"Transient peak time\"\n1\n%f\n3\n0\n3\n%d\n", at[best_dof] * d->transient_dt, d->nodes_count);
+    for (i = 0; i < d->nodes_count; ++i)
+      fprintf(f, "%d %.9e %.9e %.9e\n", i + 1, at[3 * i] * d->transient_dt, at[3 * i + 1] * d->transient_dt, at[3 * i + 2] * d->transient_dt);
+    fprintf(f, "$EndNodeData\n");
+    fclose(f);
+  }
+  free(F); free(g); free(at);
+  return 0;
+}
+
 int fea_buckling_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   FILE *log = (FILE *)log_, *f;

@@ -21,6 +21,8 @@ extern "C" {
 #define FEA_MAX_MATERIAL_PARAMETERS 10   /* defines.h:22 */
 
 typedef enum { FEA_TETRAHEDRA10 = 0, FEA_TETRAHEDRA4 = 1, FEA_HEXAHEDRA8 = 2 } fea_element_type;
+/* g(t) of (transient :shape ...): 1 from t = 0; min(t / T, 1); sin(pi t / T) up to T and 0 after */
+enum { FEA_SHAPE_STEP = 0, FEA_SHAPE_RAMP = 1, FEA_SHAPE_HALF_SINE = 2 };
 
 /* fea_task + fea_solution_params + the three input arrays of the reference
  * (fea_solver.h:94-155), as one flat record                                 */
@@ -100,6 +102,21 @@ typedef struct fea_deck {
    * sections to the .msh file.  Written by fea_deck_save only when n > 0: a deck without the section is read, run and
    * written as before.  The five fields are the newest of the struct and stand in front of damping_alpha, whose place
    * (with everything behind it) the host tests pin                                                                 */
+  /* transient response, optional: (transient :steps n :dt x :shape step|ramp|half-sine :rise T :zeta z :static-correction t
+   * :base (bx by bz)) inside (solution ...): n <= FEA_TRANSIENT_MAX_STEPS steps of x > 0 under the load times g(t), g = 1
+   * from t = 0 (step), min(t / T, 1) (ramp) or sin(pi t / T) up to T and 0 after (half-sine); :shape step, :zeta 0 and
+   * :static-correction t where absent, :rise T > 0 needed by ramp and half-sine.  Without :base the load is the surface load
+   * of the state reached, as for (harmonic ...); with it the base load of feahip_response_base_load along (bx by bz), which
+   * needs no surface load.  It uses the locked store like (harmonic ...), with the same load errors.  After the harmonic
+   * sweep feasolver_hip runs fea_transient_run.  Written by fea_deck_save only when n > 0: a deck without the section is
+   * read, run and written as before.  The fields are the newest of the struct and stand in front of harmonic_count,
+   * whose place (with everything behind it) the host tests pin                                                     */
+  int transient_steps;
+  double transient_dt, transient_zeta;
+  int transient_static, transient_shape;      /* FEA_SHAPE_* */
+  double transient_rise;
+  int transient_has_base;
+  double transient_base[3];
   int harmonic_count;
   double harmonic_from, harmonic_to, harmonic_zeta;
   int harmonic_static;
@@ -255,6 +272,15 @@ int fea_modal_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, 
  * equals, node from 1, dof 0-2).  With msh_path not NULL two $NodeData sections of three components per node are
  * appended: "Harmonic peak amplitude" and "Harmonic peak frequency" (Hz).  Returns 0, or a negative FEAHIP_E* code.  */
 int fea_harmonic_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
+/* The time history of a deck with (transient :steps n ...), n > 0, after fea_harmonic_run and before anything drops the
+ * locked modes: feahip_response_load with the surface load of the state reached (all zero: a log line and FEAHIP_EINVAL)
+ * or, with :base, feahip_response_base_load, then feahip_response_transient of the displacement with the deck's
+ * :damping-alpha, :damping-beta and :zeta.  Log: "Transient: n steps of dt, shape s, m modes, static correction on|off",
+ * with :base one "Effective mass: mode k, gamma g, m_eff e, cumulative fraction c of total t" line per mode, and
+ * "Transient peak: |u| = p at t = x, node a dof j" (the largest peak of all dofs, the lowest dof among equals).  With
+ * msh_path two $NodeData sections are appended: "Transient peak displacement" and "Transient peak time".  Returns 0, or a
+ * negative FEAHIP_E* code.  */
+int fea_transient_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 
 /* The buckling analysis of a deck with (buckling :modes N ...), N > 0, at the state the context is in:
  * feahip_solve_buckling, one log line per mode ("Buckling mode k: factor = f, nu = v") and, with msh_path not NULL, one

@@ -18,6 +18,9 @@
  * (harmonic ...) then gets the frequency sweep of its surface load on those
  * modes: two log lines and the peak amplitude and peak frequency of every dof
  * in the file (feahip_response_load, feahip_response_sweep).  A deck with
+ * (transient ...) then gets the time history of that load, or of a base
+ * acceleration, on the same modes: the peak displacement and its time per dof
+ * (feahip_response_base_load, feahip_response_transient).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid
@@ -96,6 +99,10 @@ int main(int argc, char **argv)
     } else if (deck.harmonic_count > 0 && (rc = fea_harmonic_run(&deck, ctx, stdout, msh))) {
       /* (harmonic ...): the frequency sweep on the locked modes the modal run left, before anything drops them */
       fprintf(stderr, "feasolve error encountered: harmonic sweep refused or failed (%d): %s\n", rc, feahip_last_error(ctx));
+      status = 1;
+    } else if (deck.transient_steps > 0 && (rc = fea_transient_run(&deck, ctx, stdout, msh))) {
+      /* (transient ...): the time history on the same locked modes, before the buckling run drops them */
+      fprintf(stderr, "feasolve error encountered: transient run refused or failed (%d): %s\n", rc, feahip_last_error(ctx));
       status = 1;
     } else if (deck.buckling_modes > 0 && (rc = fea_buckling_run(&deck, ctx, stdout, msh))) {
       /* (buckling :modes N ...): the load factors at the state reached, the mode shapes behind everything else */

@@ -189,6 +189,18 @@ static int read_attrs(reader *r, fea_deck *d, attr *a, int *na, int recurse)
       char key[48];
       snprintf(key, sizeof key, "%s", buf + 1);
       t = next_token(r, buf);
+      if (t == T_OPEN && ieq(key, "base")) {                 /* :base (bx by bz) of (transient ...): its atoms, blank-separated */
+        size_t len = 0;
+        buf[0] = 0;
+        for (;;) {
+          char tok[TOK_MAX];
+          t = next_token(r, tok);
+          if (t == T_CLOSE) break;
+          if (t != T_ATOM || len + strlen(tok) + 2 > sizeof buf) return fail(r, ":base takes a list of three numbers");
+          len += (size_t)snprintf(buf + len, sizeof buf - len, len ? " %s" : "%s", tok);
+        }
+        t = T_ATOM;
+      }
       if (t == T_OPEN) { if (skip_list(r)) return -1; continue; }
       if (t != T_ATOM) return fail(r, "attribute without a value");
       if (*na < ATTR_MAX) {
@@ -655,6 +667,43 @@ static int read_list(reader *r, fea_deck *d)
       if (ieq(s, "nil") || ieq(s, "no") || ieq(s, "false")) d->harmonic_static = 0;
       else if (!(ieq(s, "t") || ieq(s, "yes") || ieq(s, "true"))) return fail(r, "harmonic :static-correction takes t or nil");
     }
+  } else if (ieq(head, "transient")) {                        /* no counterpart in the reference */
+    if (need_num(r, a, na, "steps", &v)) return -1;
+    if (!(v >= 1 && v <= FEA_TRANSIENT_MAX_STEPS) || v != (double)(int)v) return fail(r, "transient :steps must be an integer in [1, 1048576]");
+    d->transient_steps = (int)v;
+    if (need_num(r, a, na, "dt", &d->transient_dt)) return -1;
+    if (!(d->transient_dt > 0 && d->transient_dt <= 1.7976931348623157e308)) return fail(r, "transient :dt must be positive and finite");
+    d->transient_zeta = 0; d->transient_static = 1; d->transient_shape = FEA_SHAPE_STEP; d->transient_rise = 0;
+    d->transient_has_base = 0; d->transient_base[0] = d->transient_base[1] = d->transient_base[2] = 0;
+    if (attr_get(a, na, "zeta") && need_num(r, a, na, "zeta", &d->transient_zeta)) return -1;
+    if (!(d->transient_zeta >= 0 && d->transient_zeta <= 1.7976931348623157e308)) return fail(r, "transient :zeta must be finite and not negative");
+    if ((s = attr_get(a, na, "static-correction"))) {
+      if (ieq(s, "nil") || ieq(s, "no") || ieq(s, "false")) d->transient_static = 0;
+      else if (!(ieq(s, "t") || ieq(s, "yes") || ieq(s, "true"))) return fail(r, "transient :static-correction takes t or nil");
+    }
+    if ((s = attr_get(a, na, "shape"))) {
+      if (ieq(s, "step")) d->transient_shape = FEA_SHAPE_STEP;
+      else if (ieq(s, "ramp")) d->transient_shape = FEA_SHAPE_RAMP;
+      else if (ieq(s, "half-sine")) d->transient_shape = FEA_SHAPE_HALF_SINE;
+      else return fail(r, "transient :shape must be step, ramp or half-sine");
+    }
+    if (attr_get(a, na, "rise") && need_num(r, a, na, "rise", &d->transient_rise)) return -1;
+    if (d->transient_shape != FEA_SHAPE_STEP && !(d->transient_rise > 0 && d->transient_rise <= 1.7976931348623157e308))
+      return fail(r, "transient :rise must be positive and finite for a ramp or a half-sine");
+    if ((s = attr_get(a, na, "base"))) {
+      char *end;
+      int k;
+      for (k = 0; k < 3; ++k) {
+        d->transient_base[k] = strtod(s, &end);
+        if (end == s || !(d->transient_base[k] >= -1.7976931348623157e308 && d->transient_base[k] <= 1.7976931348623157e308))
+          return fail(r, "transient :base takes three finite numbers");
+        s = end;
+      }
+      while (*s == ' ') ++s;
+      if (*s) return fail(r, "transient :base takes three finite numbers");
+      if (d->transient_base[0] == 0 && d->transient_base[1] == 0 && d->transient_base[2] == 0) return fail(r, "transient :base must not be zero");
+      d->transient_has_base = 1;
+    }
   } else if (ieq(head, "buckling")) {                         /* no counterpart in the reference */
     if (need_num(r, a, na, "modes", &v)) return -1;
     if (!(v >= 1 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "buckling :modes must be an integer in [1, 8]");
@@ -745,6 +794,12 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
     if (rc == 0 && deck->harmonic_count > 0 && !(deck->modal_count > 0 || (deck->modal_modes > 0 && deck->modal_shift != 0.0))) {
       rc = -1; snprintf(r.err, sizeof r.err, "deck has (harmonic ...) but no locked modes: add (modal :count N ...) or a :shift");
     }
+    if (rc == 0 && deck->transient_steps > 0 && !(deck->modal_count > 0 || (deck->modal_modes > 0 && deck->modal_shift != 0.0))) {
+      rc = -1; snprintf(r.err, sizeof r.err, "deck has (transient ...) but no locked modes: add (modal :count N ...) or a :shift");
+    }
+    if (rc == 0 && deck->transient_steps > 0 && deck->transient_static && deck->modal_shift != 0.0) {
+      rc = -1; snprintf(r.err, sizeof r.err, "transient :static-correction t and a non-zero modal :shift exclude each other");
+    }
     if (rc == 0 && deck->harmonic_count > 0 && deck->harmonic_static && deck->modal_shift != 0.0) {
       rc = -1; snprintf(r.err, sizeof r.err, "harmonic :static-correction t and a non-zero modal :shift exclude each other");
     }
@@ -818,6 +873,14 @@ int fea_deck_save(const char *path, const fea_deck *d)
   if (d->harmonic_count > 0)                                                   /* written only when asked for */
     fprintf(f, "\n   (harmonic :from %.17g :to %.17g :count %d :zeta %.17g :static-correction %s)", d->harmonic_from,
             d->harmonic_to, d->harmonic_count, d->harmonic_zeta, d->harmonic_static ? "t" : "nil");
+  if (d->transient_steps > 0) {                                                /* written only when asked for */
+    static const char *shape[] = {"step", "ramp", "half-sine"};
+    fprintf(f, "\n   (transient :steps %d :dt %.17g :shape %s :rise %.17g :zeta %.17g :static-correction %s", d->transient_steps,
+            d->transient_dt, shape[d->transient_shape], d->transient_rise, d->transient_zeta, d->transient_static ? "t" : "nil");
+    if (d->transient_has_base)
+      fprintf(f, " :base (%.17g %.17g %.17g)", d->transient_base[0], d->transient_base[1], d->transient_base[2]);
+    fprintf(f, ")");
+  }
   if (d->buckling_modes > 0)                                                   /* written only when asked for */
     fprintf(f, "\n   (buckling :modes %d :tolerance %.17g :max %d)", d->buckling_modes, d->buckling_tolerance, d->buckling_max);
   fprintf(f, ")\n");

@@ -963,8 +963,8 @@ int feahip_modal_deflate(feahip_ctx *ctx, int n_locked, const double *q, const d
  * w^2 << lam.
  * Memory: 3 x 3N doubles, 1 MB of partial sums and the 4 MB table, on top of
  * the locked store, allocated by the first load.  Not offered: sharded runs,
- * complex loads and a phase between loads, transient modal superposition, base
- * excitation, residual vectors beyond the one static correction.              */
+ * complex loads and a phase between loads, residual vectors beyond the one
+ * static correction.                                                          */
 #define FEA_RESPONSE_MAX_FREQ 4096
 int feahip_response_set_basis(feahip_ctx *ctx, int n, const double *lam /*[n]*/, const double *phi /*[n][3N], caller's dofs*/);
 int feahip_response_load(feahip_ctx *ctx, const double *F /*[3N]*/, int static_correction, int solver_type, double tolerance,
@@ -980,6 +980,90 @@ int feahip_response_field(feahip_ctx *ctx, double omega, double alpha, double be
 int feahip_host_response_coefficients(int n_modes, const double *lam, const double *q, int n_freq, const double *omega,
                                       double alpha, double beta_k, const double *zeta /*[n_modes] or NULL*/,
                                       int static_correction, double *coef /*[n_freq][2][64], zero past n_modes*/);
+
+/* ---- transient response by mode superposition, base excitation ----------------
+ * The response to F g(t) from rest, F the load held (feahip_response_load or
+ * feahip_response_base_load), g given at the n_steps + 1 times t_n = n dt and
+ * linear in between.  Every mode held obeys
+ *     q'' + d_k q' + lam_k q = q_k g(t),     d_k as above,
+ * and is advanced by the exact propagator of a linear load,
+ *     (q, q')_{n+1} = A_k (q, q')_n + b0_k q_k g_n + b1_k q_k g_{n+1},
+ *     A_k = exp(dt [[0, 1], [-lam_k, -d_k]]),
+ * so there is no stability limit on dt: a mode with omega dt = 50 is as safe as
+ * one with 0.01.  A_k, b0_k and b1_k come from power series on a step
+ * dt / 2^s with |lam_k| (dt / 2^s)^2 <= 1/2 and d_k dt / 2^s <= 1/2, doubled s
+ * times, in long double: under-, critically and over-damped modes, lam_k = 0
+ * and lam_k = +-1e-12 are no special cases.  One coefficient row per step:
+ *   quantity 0  u(t_n) = u_s g_n + sum_k phi_k a_k(n), a_k = q(t_n) without the
+ *               static correction (u_s = 0), a_k = q(t_n) - q_k g_n / lam_k with
+ *               it (mode acceleration: the modes left out respond statically)
+ *   quantity 1  v(t_n) = sum_k phi_k q'(t_n)
+ *   quantity 2  a(t_n) = sum_k phi_k (q_k g_n - d_k q' - lam_k q), relative to
+ *               the base under a base load
+ * Velocity and acceleration carry no static term, correction or not.
+ *
+ * feahip_response_base_load: the load of a rigid base acceleration along dir,
+ *     F = -M r on the free dofs, 0 on the prescribed ones,
+ * r the translation dir on ALL dofs, the prescribed ones included (the supports
+ * move with the ground; the response is relative to the base).  M r is one
+ * launch of the mass product, which reads every column.  The rest is
+ * feahip_response_load: the projection, with static_correction != 0 the solve
+ * K u_s = F, and the load is held for sweep, field and transient alike.
+ *   q[n_locked]         phi_k' F, ascending lam
+ *   gamma[n_locked]     the participation factors phi_k' M r = -q_k
+ *   eff_mass[n_locked]  gamma_k^2 (the modes are M-orthonormal)
+ *   *total_mass         r' M r over all dofs (|dir|^2 times the body's mass)
+ * Each may be NULL.  Refused where feahip_response_load is, and with
+ * FEAHIP_EINVAL for a dir that is zero or not finite.
+ *
+ * feahip_response_transient: the host makes the rows (the code behind
+ * feahip_host_transient_coefficients), FEA_TRANSIENT_CHUNK at a time; a chunk
+ * and its g_n go through the coefficient buffer of the frequency sweep, so no
+ * device allocation grows with n_steps, and one launch of k_transient_sweep per
+ * chunk walks it: a lane owns a dof, holds its n_locked mode values in
+ * registers, and keeps the largest |u_i(t_n)| and its step; every launch after
+ * the first continues from what the one before left.  The host fills the next
+ * chunk while one runs.
+ *   peak[i]     max_n |u_i(t_n)| of the quantity asked for
+ *   peak_at[i]  the lowest step n that attains it
+ * both [3N], caller's dof order, exactly 0 on the prescribed dofs.  Probes:
+ * n_probe <= 64 dofs whose whole histories come back, probe[n_probe][n_steps +
+ * 1], summed on the host in the kernel's order.  Snapshots: n_snap <= 4096
+ * steps whose field comes back, snap[n_snap][3N], one launch of the
+ * field-writing instantiation each; a snapshot's value at a probe dof has the
+ * bits of the probe's history at that step.  The same input gives the same
+ * bits.  FEAHIP_ESTATE without modes held or without a load held for them, as
+ * feahip_response_sweep.  FEAHIP_EINVAL: a row-sharded or feahip_create_rank*
+ * context; n_steps outside [1, FEA_TRANSIENT_MAX_STEPS]; dt not positive or
+ * not finite; a g that is not finite; quantity outside 0..2; a negative or
+ * non-finite alpha, beta_k or zeta_k; n_probe outside [0, 64] or a probe dof
+ * outside [0, 3N); n_snap outside [0, 4096] or a snapshot step outside [0,
+ * n_steps]; a null required array; a coefficient that is not finite.  x, v, a,
+ * the time, the load factor, K, f, u and the locked store are untouched; the
+ * table of the last frequency sweep is gone (hook 23 of feahip_time_kernel is
+ * refused until the next sweep, and hook 25 after one).
+ *
+ * feahip_host_transient_coefficients (no device): coef[n_steps + 1][64], mode k
+ * of the arrays given at column k, zero past n_modes; the very rows the device
+ * entry uses, bit for bit.  Refuses what the device entry refuses of the same
+ * arguments, and lam_k <= 0 with the correction.
+ * Not offered: sharded runs, several load patterns with their own histories in
+ * one call, non-zero initial conditions, a static term in velocity and
+ * acceleration.                                                                */
+#define FEA_TRANSIENT_MAX_STEPS 1048576
+#define FEA_TRANSIENT_CHUNK     8064    /* rows of a launch: 8064 x 64 coefficients and 8064 g_n fill the sweep's 4 MB table */
+int feahip_response_base_load(feahip_ctx *ctx, const double *dir /*[3]*/, int static_correction, int solver_type,
+                              double tolerance, int max_iterations, double *q /*[n_locked]*/, double *gamma /*[n_locked]*/,
+                              double *eff_mass /*[n_locked]*/, double *total_mass, int *iters, double *resid /*each may be NULL*/);
+int feahip_response_transient(feahip_ctx *ctx, int n_steps, double dt, const double *g /*[n_steps + 1]*/, double alpha,
+                              double beta_k, const double *zeta /*[n_locked] or NULL*/, int quantity, double *peak /*[3N]*/,
+                              int *peak_at /*[3N]*/, int n_probe, const int *probe_dof /*[n_probe]*/,
+                              double *probe /*[n_probe][n_steps + 1]*/, int n_snap, const int *snap_step /*[n_snap]*/,
+                              double *snap /*[n_snap][3N]*/);
+int feahip_host_transient_coefficients(int n_modes, const double *lam, const double *q, int n_steps, double dt,
+                                       const double *g /*[n_steps + 1]*/, double alpha, double beta_k,
+                                       const double *zeta /*[n_modes] or NULL*/, int static_correction, int quantity,
+                                       double *coef /*[n_steps + 1][64], zero past n_modes*/);
 
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
@@ -1326,7 +1410,9 @@ int feahip_sync(feahip_ctx *ctx);
  * garbage as 8 and 9 do); 23 k_response_sweep over the coefficient table, the
  * store and the u_s the last feahip_response_sweep used, 24 k_response_project
  * on the f in force (both FEAHIP_ESTATE before a sweep; nothing but the sweep's
- * own output buffers and partial sums is written).                           */
+ * own output buffers and partial sums is written); 25 one launch of
+ * k_transient_sweep over the last chunk of the last feahip_response_transient
+ * (FEAHIP_ESTATE, "no transient", before one).                               */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
