@@ -48,6 +48,10 @@ SHARDED = {
     "bar_54_one_super": (lambda: mesh.bar_deck(dims=(2, 5, 2)), (3,)),
 }
 MULTIGRID_DIMS = (3, 12, 3)
+# the environment knobs of the multigrid hierarchy: a test that compares with the reference cycle clears them
+AMG_ENV = ("FEAHIP_AMG_TAIL", "FEAHIP_AMG_TAIL_ELL", "FEAHIP_AMG_TAIL_BLOB", "FEAHIP_AMG_TAIL_COP", "FEAHIP_AMG_FUSED_POST",
+           "FEAHIP_AMG_FINE_BITS", "FEAHIP_AMG_F32", "FEAHIP_AMG_GAMMA", "FEAHIP_AMG_GAMMA_UNTIL", "FEAHIP_AMG_GAMMA_FROM",
+           "FEAHIP_AMG_SWEEPS", "FEAHIP_AMG_COARSEST", "FEAHIP_AMG_OVER")
 BATCH_DIMS = (3, 8, 3)
 
 

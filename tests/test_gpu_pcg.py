@@ -26,9 +26,7 @@ SOLVERS = {"cg": feahip.CG, "block_jacobi": feahip.PCG_ILU}
 RESID_TOL = 1e-10        # `resid` against the restatement's recurrence residual, relative
 MG_FLOOR = 1e-11         # the multigrid loop: the cycle itself is held to 1e-12 (test_gpu_multigrid.Z_TOL)
 TOL_BATCH = 1e-6
-AMG_ENV = ("FEAHIP_AMG_TAIL", "FEAHIP_AMG_TAIL_ELL", "FEAHIP_AMG_TAIL_BLOB", "FEAHIP_AMG_TAIL_COP", "FEAHIP_AMG_FUSED_POST",
-           "FEAHIP_AMG_FINE_BITS", "FEAHIP_AMG_F32", "FEAHIP_AMG_GAMMA", "FEAHIP_AMG_GAMMA_UNTIL", "FEAHIP_AMG_GAMMA_FROM",
-           "FEAHIP_AMG_SWEEPS", "FEAHIP_AMG_COARSEST", "FEAHIP_AMG_OVER")
+AMG_ENV = pc.AMG_ENV
 
 _SYSTEMS = {}            # what a test computes once: K, f of a mesh and the restatement's runs on them
 _CHECKS = {}
