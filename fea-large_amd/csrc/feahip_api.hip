@@ -1483,6 +1483,16 @@ extern "C" int feahip_solve_modes_locked(feahip_ctx *c, int n_modes, double shif
   return modal_solve_locked(c, n_modes, shift, tol, max_iter, lambda, resid, iters, sweeps);
 }
 
+extern "C" int feahip_get_locked_lambda(feahip_ctx *c, int first, int count, double *lambda)
+{
+  CTX_GUARD_NOK(c);
+  if (!lambda) return FEAHIP_EINVAL;
+  if (!c->modal.have_locked) { c->err = "get_locked_lambda: no locked modes held (feahip_solve_modes_locked first)"; return FEAHIP_ESTATE; }
+  if (first < 0 || count < 0 || first + count > c->modal.n_locked) { c->err = "get_locked_lambda: range outside the modes held"; return FEAHIP_EINVAL; }
+  for (int k = 0; k < count; ++k) lambda[k] = c->modal.lam[first + k];
+  return FEAHIP_OK;
+}
+
 extern "C" int feahip_get_locked_count(feahip_ctx *c, int *count)
 {
   CTX_GUARD_NOK(c);
@@ -1730,6 +1740,92 @@ extern "C" int feahip_host_transient_coefficients(int n_modes, const double *lam
   rc = transient_rows(T, g, n_steps + 1, coef, nullptr);
   transient_end(T);
   return rc;
+}
+
+// ---- response spectrum and random vibration: one quadratic form per dof (kernels_combine.hip, combine_table.cpp) ---------
+static int combine_ready(feahip_ctx *c, const char *who)
+{
+  int rc;
+  if ((rc = solve2_refused(c, who))) return rc;
+  return response_loaded(c, who);
+}
+
+static int combine_to_caller(feahip_ctx *c, const double *C, const double *b, double s, bool absx, double *out)
+{
+  std::vector<double> tmp((size_t)c->ndof);
+  const int rc = response_combine(c, C, b, s, absx, tmp.data());
+  if (rc) return rc;
+  to_caller(view_of(c), 3, 3, tmp.data(), out);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_combine(feahip_ctx *c, const double *C, const double *b, double s, int absolute, double *out)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = combine_ready(c, "response_combine"))) return rc;
+  if (!C || !out) { c->err = "response_combine: null C or out"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  for (int j = 0; j < n; ++j) {
+    for (int k = 0; k < n; ++k) {
+      const double v = C[(size_t)j * n + k];
+      if (!std::isfinite(v)) { c->err = "response_combine: C is not finite"; return FEAHIP_EINVAL; }
+      if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) { c->err = "response_combine: C is not symmetric to the bit"; return FEAHIP_EINVAL; }
+      if (j != k && !std::isfinite(2.0 * v)) { c->err = "response_combine: twice an entry of C is not finite"; return FEAHIP_EINVAL; }
+    }
+    if (b && !std::isfinite(b[j])) { c->err = "response_combine: b is not finite"; return FEAHIP_EINVAL; }
+  }
+  if (!std::isfinite(s)) { c->err = "response_combine: s is not finite"; return FEAHIP_EINVAL; }
+  return combine_to_caller(c, C, b, s, absolute != 0, out);
+}
+
+extern "C" int feahip_response_random(feahip_ctx *c, int n_freq, const double *omega, const double *S, double alpha, double beta_k,
+                                      const double *zeta, int quantity, double *rms, double *modal_cov)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = combine_ready(c, "response_random"))) return rc;
+  if (!omega || !S || !rms) { c->err = "response_random: null omega, S or rms"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  std::vector<double> C((size_t)n * n), b(n);
+  double s = 0.0;
+  std::string why;
+  if (random_form(n, c->modal.lam, c->response.q, n_freq, omega, S, alpha, beta_k, zeta, c->response.correction, quantity,
+                  C.data(), b.data(), &s, &why)) {
+    c->err = "response_random: " + why;
+    return FEAHIP_EINVAL;
+  }
+  if ((rc = combine_to_caller(c, C.data(), b.data(), s, false, rms))) return rc;
+  if (modal_cov) std::copy(C.begin(), C.end(), modal_cov);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_spectrum(feahip_ctx *c, int n_pts, const double *w, const double *sa, int loglog, int rule,
+                                        double alpha, double beta_k, const double *zeta, double zpa, int quantity, double *peak,
+                                        double *modal_peak)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = combine_ready(c, "response_spectrum"))) return rc;
+  if (!w || !sa || !peak) { c->err = "response_spectrum: null w, sa or peak"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  double sak[FEA_MODAL_MAX_LOCKED], a[FEA_MODAL_MAX_LOCKED];
+  for (int k = 0; k < n; ++k) {
+    if (!(c->modal.lam[k] > 0.0)) { c->err = "response_spectrum: lam of mode " + std::to_string(k + 1) + " is not positive"; return FEAHIP_EINVAL; }
+    sak[k] = feahip_host_spectrum_value(n_pts, w, sa, loglog, std::sqrt(c->modal.lam[k]));
+    if (std::isnan(sak[k])) { c->err = "response_spectrum: the spectrum's points must be finite, their w strictly ascending"; return FEAHIP_EINVAL; }
+  }
+  std::vector<double> C((size_t)n * n), b(n);
+  double s = 0.0;
+  std::string why;
+  if (spectrum_form(n, c->modal.lam, c->response.q, sak, alpha, beta_k, zeta, rule, c->response.correction, zpa, quantity,
+                    C.data(), b.data(), &s, a, &why)) {
+    c->err = "response_spectrum: " + why;
+    return FEAHIP_EINVAL;
+  }
+  if ((rc = combine_to_caller(c, C.data(), b.data(), s, rule == FEAHIP_ABS, peak))) return rc;
+  if (modal_peak) for (int k = 0; k < n; ++k) modal_peak[k] = a[k];
+  return FEAHIP_OK;
 }
 
 extern "C" int feahip_host_modal_ritz(int n_dirs,const double *gram_m, const double *gram_k, double *theta, double *coef)
@@ -2161,6 +2257,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (rk) return rk;
     if (c->response.trans_rows == 0) { c->err = "time_kernel: no transient made yet (feahip_response_transient first)"; return FEAHIP_ESTATE; }
   }
+  if (what == 26) {                                    // the form of the last combination, the store and u_s as it left them
+    const int rk = response_loaded(c, "time_kernel(26)");
+    if (rk) return rk;
+    if (!c->response.form_set || c->response.form_gen != c->modal.lock_gen) { c->err = "time_kernel: no form set yet (feahip_response_combine, _random or _spectrum first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2185,6 +2286,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 22: return launch_damp_residual(c, 1.0, 1.0);
     case 23: case 24: return time_response_kernel(c, what);
     case 25: return time_transient_kernel(c);
+    case 26: return time_combine_kernel(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

@@ -546,7 +546,12 @@ struct ResponseState {
   int swept_freq = 0;                  // frequencies in d_coef from the last sweep (feahip_time_kernel 23)
   int trans_rows = 0;                  // rows in d_coef from the last chunk of the last transient (feahip_time_kernel 25) ...
   int trans_step0 = 0;                 // ... and the step of its first row
-  void release() { dev_free({d_us, d_part, d_q, d_coef, d_out}); *this = ResponseState(); }
+  double *d_form = nullptr;            // [FEA_COMBINE_TABLE] the form of the last combination, by store column: T[64][64] (C folded
+                                       // onto its upper triangle), b[64], s (kernels_combine.hip); allocated by the first one
+  bool form_set = false;               // d_form holds a form (feahip_time_kernel 26) ...
+  bool form_abs = false;               // ... to be taken on |phi| ...
+  int form_gen = -1;                   // ... laid out for the filling form_gen of the store
+  void release() { dev_free({d_us, d_part, d_q, d_coef, d_out, d_form}); *this = ResponseState(); }
 };
 
 // linear buckling (kernels_buckling.hip): nothing of it exists until feahip_solve_buckling (or one of its hooks,
@@ -864,6 +869,18 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
                        int quantity, double *h_peak, int *h_at, int n_probe, const int *probe, double *h_probe, int n_snap,
                        const int *snap_step, double *h_snap);
 int time_transient_kernel(feahip_ctx *c);                               // feahip_time_kernel 25
+// kernels_combine.hip -- one quadratic form of the mode values per dof: response spectrum and random vibration
+#define FEA_COMBINE_TABLE (66 * 64)                                     // T[64][64], b[64], s, and padding to a whole row
+// C[n_locked][n_locked], b[n_locked] (null: zero) and s by ascending mode; h_out[3N] in library ids
+int response_combine(feahip_ctx *c, const double *C, const double *b, double s, bool absx, double *h_out);
+int time_combine_kernel(feahip_ctx *c);                                 // feahip_time_kernel 26
+// combine_table.cpp -- the forms of a PSD and of a response spectrum, host only, in long double.  Mode k of the arrays is
+// row and column k of C[n_modes][n_modes] and entry k of b; FEAHIP_EINVAL and *why for what the entries refuse
+int random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
+                double beta, const double *zeta, int correction, int quantity, double *C, double *b, double *s, std::string *why);
+int spectrum_form(int n_modes, const double *lam, const double *q, const double *sa, double alpha, double beta, const double *zeta,
+                  int rule, int correction, double zpa, int quantity, double *C, double *b, double *s, double *a /*[n_modes] the peak
+                  modal values, or null*/, std::string *why);
 // kernels_buckling.hip -- K_sigma as one double per block, and the lowest eigenpairs of K_sigma phi = nu K phi
 int geom_assemble(feahip_ctx *c);                                       // buckling.d_kg at the current nodes
 int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters);

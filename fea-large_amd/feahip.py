@@ -166,6 +166,7 @@ ABI = {
     "feahip_solve_modes_locked": [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _ip, _ip],
     "feahip_get_locked_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_get_locked_count": [C.c_void_p, _ip],
+    "feahip_get_locked_lambda": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_modal_deflate": [C.c_void_p, C.c_int, _dp, _dp, _dp],
     "feahip_response_set_basis": [C.c_void_p, C.c_int, _dp, _dp],
     "feahip_response_load": [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp],
@@ -178,6 +179,17 @@ ABI = {
                                   C.c_int, _ip, _dp, C.c_int, _ip, _dp],
     "feahip_host_transient_coefficients": [C.c_int, _dp, _dp, C.c_int, C.c_double, _dp, C.c_double, C.c_double, _dp, C.c_int,
                                            C.c_int, _dp],
+    "feahip_response_combine": [C.c_void_p, _dp, _dp, C.c_double, C.c_int, _dp],
+    "feahip_response_random": [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp, _dp],
+    "feahip_response_spectrum": [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_double,
+                                 C.c_int, _dp, _dp],
+    "feahip_host_random_form": [C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp, _dp,
+                                _dp],
+    "feahip_host_random_grid": [C.c_int, _dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _ip],
+    "feahip_host_psd_value": [C.c_int, _dp, _dp, C.c_int, C.c_double],
+    "feahip_host_spectrum_value": [C.c_int, _dp, _dp, C.c_int, C.c_double],
+    "feahip_host_spectrum_form": [C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
+                                  _dp, _dp, _dp],
     "feahip_solve_buckling": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
     "feahip_get_buckling_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_geometric_spmv": [C.c_void_p, _dp, _dp],
@@ -189,6 +201,10 @@ RESPONSE_MAX_FREQ = 4096                                # FEA_RESPONSE_MAX_FREQ
 TRANSIENT_MAX_STEPS = 1048576                           # FEA_TRANSIENT_MAX_STEPS
 TRANSIENT_CHUNK = 8064                                  # FEA_TRANSIENT_CHUNK
 TRANSIENT_SHAPES = ("step", "ramp", "half-sine")        # FEA_SHAPE_* of host/fea_host.h
+RANDOM_MAX_FREQ = 262144                                # FEA_RANDOM_MAX_FREQ
+DECK_MAX_POINTS = 4096                                  # FEA_DECK_MAX_POINTS of host/fea_host.h
+SPECTRUM_RULES = ("srss", "cqc", "abs")                 # :rule of (spectrum ...), the values of FEAHIP_SRSS, _CQC, _ABS
+SRSS, CQC, ABS = 0, 1, 2                                # FEAHIP_SRSS, FEAHIP_CQC, FEAHIP_ABS: the rules of a response spectrum
 # the mass rule FeaSolver.set_mass picks (exact for straight-sided elements; fea_mass_points of host/fea_host.h)
 MASS_POINTS = {TETRAHEDRA4: 4, TETRAHEDRA10: 27, HEXAHEDRA8: 8}
 COARSE_INFO_KEYS = ("aggregates", "first_aggregate", "local_aggregates", "unknowns", "epoch", "owned_rows", "m", "pairs")
@@ -217,7 +233,8 @@ def load_library():
             fn = getattr(lib, name)          # AttributeError if the symbol is absent
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("feahip_last_error", "feahip_create_error") else (
-                None if name == "feahip_destroy" else C.c_int)
+                None if name == "feahip_destroy" else
+                C.c_double if name in ("feahip_host_psd_value", "feahip_host_spectrum_value") else C.c_int)
         _lib = lib
     return _lib
 
@@ -240,6 +257,12 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("has_spectrum", C.c_int), ("spectrum_count", C.c_int), ("spectrum_points", _dp), ("spectrum_rule", C.c_int),
+        ("spectrum_static", C.c_int), ("spectrum_loglog", C.c_int), ("spectrum_has_base", C.c_int),
+        ("spectrum_zeta", C.c_double), ("spectrum_zpa", C.c_double), ("spectrum_base", C.c_double * 3),
+        ("has_random", C.c_int), ("random_count", C.c_int), ("random_points", _dp), ("random_static", C.c_int),
+        ("random_loglog", C.c_int), ("random_per_mode", C.c_int), ("random_background", C.c_int), ("random_has_base", C.c_int),
+        ("random_zeta", C.c_double), ("random_base", C.c_double * 3),
         ("transient_steps", C.c_int), ("transient_dt", C.c_double), ("transient_zeta", C.c_double),
         ("transient_static", C.c_int), ("transient_shape", C.c_int), ("transient_rise", C.c_double),
         ("transient_has_base", C.c_int), ("transient_base", C.c_double * 3),
@@ -368,6 +391,84 @@ def host_transient_coefficients(lam, q, g, dt, alpha=0.0, beta=0.0, zeta=None, s
     if rc != 0:
         raise FeaHipError(f"feahip_host_transient_coefficients refused its input ({rc})")
     return coef
+
+
+def _modal_arrays(lam, q, zeta):
+    lam, q = np.ascontiguousarray(lam, dtype=np.float64), np.ascontiguousarray(q, dtype=np.float64)
+    z = None if zeta is None else np.ascontiguousarray(np.broadcast_to(np.asarray(zeta, dtype=np.float64), lam.shape))
+    assert lam.shape == q.shape and lam.ndim == 1
+    return lam, q, z
+
+
+def host_random_form(lam, q, omega, S, alpha=0.0, beta=0.0, zeta=None, static_correction=True, quantity=0):
+    """feahip_host_random_form (no device): (C[n][n], b[n], s) of the RMS under the one-sided PSD S(omega) per rad/s of the
+    load factor, omega strictly ascending, trapezoid weights: C_kl = sum_j wt_j S_j w_j^(2p) Re(a_k conj(a_l)), b_k = sum_j
+    wt_j S_j w_j^(2p) Re(a_k), s = sum_j wt_j S_j w_j^(2p), a the rows of host_response_coefficients, p = quantity.  b and s
+    are zero without the correction.  Raises where the entry refuses."""
+    lam, q, z = _modal_arrays(lam, q, zeta)
+    omega, S = np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+    assert omega.ndim == 1 and omega.shape == S.shape
+    n = len(lam)
+    Cm, b, s = np.zeros((n, n)), np.zeros(n), C.c_double(0)
+    rc = load_library().feahip_host_random_form(n, _d(lam), _d(q), len(omega), _d(omega), _d(S), float(alpha), float(beta),
+                                                None if z is None else _d(z), int(bool(static_correction)), int(quantity),
+                                                _d(Cm), _d(b), C.byref(s))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_random_form refused its input ({rc})")
+    return Cm, b, s.value
+
+
+def host_random_grid(lam, alpha=0.0, beta=0.0, zeta=None, w_lo=0.0, w_hi=1.0, n_background=257, n_per_mode=64, breakpoints=()):
+    """feahip_host_random_grid (no device): the sorted union, clipped to [w_lo, w_hi] and without duplicates, of n_background
+    points of linspace(w_lo, w_hi), per mode with lam_k > 0 and d_k > 0 the n_per_mode points w_k + (d_k / 2) tan(theta_i),
+    theta_i = ((i + 1/2) / n_per_mode) pi - pi / 2, and the breakpoints given."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    z = None if zeta is None else np.ascontiguousarray(np.broadcast_to(np.asarray(zeta, dtype=np.float64), lam.shape))
+    bp = np.ascontiguousarray(breakpoints, dtype=np.float64).reshape(-1)
+    out = np.zeros(max(int(n_background), 0) + len(lam) * max(int(n_per_mode), 0) + len(bp) + 1)
+    out[:len(bp)] = bp
+    n = C.c_int(len(bp))
+    rc = load_library().feahip_host_random_grid(len(lam), _d(lam), float(alpha), float(beta), None if z is None else _d(z),
+                                                float(w_lo), float(w_hi), int(n_background), int(n_per_mode), _d(out), C.byref(n))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_random_grid refused its input ({rc})")
+    return out[:n.value].copy()
+
+
+def _table_value(fn, w, v, at, loglog):
+    w, v = np.ascontiguousarray(w, dtype=np.float64), np.ascontiguousarray(v, dtype=np.float64)
+    assert w.ndim == 1 and w.shape == v.shape
+    out = np.array([fn(len(w), _d(w), _d(v), int(bool(loglog)), float(x)) for x in np.atleast_1d(at)])
+    if np.isnan(out).any():
+        raise FeaHipError("the table's points must be finite, their abscissae strictly ascending, and so the argument")
+    return out if np.ndim(at) else float(out[0])
+
+
+def host_psd_value(w, S, at, loglog=False):
+    """feahip_host_psd_value (no device): the table (w, S) at `at` (a number or an array), linear or log-log, zero outside."""
+    return _table_value(load_library().feahip_host_psd_value, w, S, at, loglog)
+
+
+def host_spectrum_value(w, sa, at, loglog=False):
+    """feahip_host_spectrum_value (no device): as host_psd_value, with the end values outside the table."""
+    return _table_value(load_library().feahip_host_spectrum_value, w, sa, at, loglog)
+
+
+def host_spectrum_form(lam, q, sa, rule=SRSS, alpha=0.0, beta=0.0, zeta=None, static_correction=False, zpa=0.0, quantity=0):
+    """feahip_host_spectrum_form (no device): (C[n][n], b[n], s) of a response spectrum with the spectral accelerations
+    sa[n] at the modes: a_k = q_k sa_k / lam_k (times sqrt(lam_k), lam_k for quantity 1, 2), SRSS C = diag(a^2), CQC C_jk =
+    rho_jk a_j a_k (Der Kiureghian), ABS C = |a||a|'; with static_correction and zpa > 0 the missing mass, C += zpa^2 c c',
+    b = zpa^2 c, s = zpa^2, c = -q / lam.  Raises where the entry refuses."""
+    lam, q, z = _modal_arrays(lam, q, zeta)
+    sa = np.ascontiguousarray(np.broadcast_to(np.asarray(sa, dtype=np.float64), lam.shape))
+    n = len(lam)
+    Cm, b, s = np.zeros((n, n)), np.zeros(n), C.c_double(0)
+    rc = load_library().feahip_host_spectrum_form(n, _d(lam), _d(q), _d(sa), float(alpha), float(beta),
+                                                  None if z is None else _d(z), int(rule), int(bool(static_correction)),
+                                                  float(zpa), int(quantity), _d(Cm), _d(b), C.byref(s))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_spectrum_form refused its input ({rc})")
+    return Cm, b, s.value
 
 
 def host_rayleigh(omega1, zeta1, omega2, zeta2):
@@ -559,6 +660,49 @@ class Deck:
                 raise ValueError("transient_steps needs the locked modes: modal_count or modal_shift")
             if self.transient_static and self.modal_shift:
                 raise ValueError("transient_static (the static correction) and a non-zero modal_shift exclude each other")
+        # (spectrum :base (bx by bz) :rule srss|cqc|abs :zeta z :static-correction t :zpa a :interp linear|loglog (points (f sa)
+        # ...)) and (random :base (bx by bz) :zeta z :static-correction t :interp linear|loglog :per-mode n :background n (psd
+        # (f s) ...)): the design peak under a response spectrum and the RMS under a PSD that feasolver_hip computes on the
+        # locked modes after the transient run; f in Hz, s per Hz
+        for name, floor in (("spectrum", 1), ("random", 2)):
+            pts = kw.get(f"{name}_points")
+            pts = np.zeros((0, 2)) if pts is None else np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+            setattr(self, f"{name}_points", pts)
+            setattr(self, f"{name}_zeta", float(kw.get(f"{name}_zeta", 0.0)))
+            setattr(self, f"{name}_static", bool(kw.get(f"{name}_static", True)))
+            setattr(self, f"{name}_interp", kw.get(f"{name}_interp", "linear"))
+            base = kw.get(f"{name}_base")
+            base = None if base is None else tuple(float(b) for b in base)
+            setattr(self, f"{name}_base", base)
+            if not len(pts):
+                continue
+            if not floor <= len(pts) <= DECK_MAX_POINTS:
+                raise ValueError(f"{name}_points: {floor} to {DECK_MAX_POINTS} pairs")
+            if not (np.all(np.isfinite(pts)) and np.all(pts >= 0) and np.all(np.diff(pts[:, 0]) > 0)):
+                raise ValueError(f"{name}_points: finite and not negative, the frequencies strictly ascending")
+            if not (0.0 <= getattr(self, f"{name}_zeta") < np.inf):
+                raise ValueError(f"{name}_zeta: finite and not negative")
+            if getattr(self, f"{name}_interp") not in ("linear", "loglog"):
+                raise ValueError(f"{name}_interp: linear or loglog")
+            if base is not None and (len(base) != 3 or not np.all(np.isfinite(base)) or not any(base)):
+                raise ValueError(f"{name}_base: three finite components, not all zero")
+            if not (self.modal_count or self.modal_shift):
+                raise ValueError(f"{name}_points needs the locked modes: modal_count or modal_shift")
+            if getattr(self, f"{name}_static") and self.modal_shift:
+                raise ValueError(f"{name}_static (the static correction) and a non-zero modal_shift exclude each other")
+        self.spectrum_rule = kw.get("spectrum_rule", "srss")
+        self.spectrum_zpa = float(kw.get("spectrum_zpa", 0.0))
+        self.random_per_mode = int(kw.get("random_per_mode", 32))
+        self.random_background = int(kw.get("random_background", 257))
+        if len(self.spectrum_points):
+            if self.spectrum_rule not in SPECTRUM_RULES:
+                raise ValueError("spectrum_rule: srss, cqc or abs")
+            if not (0.0 <= self.spectrum_zpa < np.inf):
+                raise ValueError("spectrum_zpa: finite and not negative")
+            if self.spectrum_zpa and (not self.spectrum_static or self.spectrum_rule == "abs"):
+                raise ValueError("spectrum_zpa needs spectrum_static and a rule other than abs")
+        if len(self.random_points) and not (0 <= self.random_per_mode <= 4096 and 2 <= self.random_background <= 131072):
+            raise ValueError("random_per_mode: 0 to 4096, random_background: 2 to 131072")
         # (buckling :modes N :tolerance t :max M): the load factors feasolver_hip computes after its last step
         self.buckling_modes = int(kw.get("buckling_modes", 0))
         self.buckling_tolerance = float(kw.get("buckling_tolerance", 1e-8))
@@ -624,6 +768,17 @@ class Deck:
                         transient_rise=fd.transient_rise,
                         transient_base=[fd.transient_base[k] for k in range(3)] if fd.transient_has_base else None)
                    if fd.transient_steps else {}),
+                **(dict(spectrum_points=np.ctypeslib.as_array(fd.spectrum_points, (fd.spectrum_count, 2)).copy(),
+                        spectrum_rule=SPECTRUM_RULES[fd.spectrum_rule], spectrum_zeta=fd.spectrum_zeta, spectrum_zpa=fd.spectrum_zpa,
+                        spectrum_static=bool(fd.spectrum_static), spectrum_interp="loglog" if fd.spectrum_loglog else "linear",
+                        spectrum_base=[fd.spectrum_base[k] for k in range(3)] if fd.spectrum_has_base else None)
+                   if fd.has_spectrum else {}),
+                **(dict(random_points=np.ctypeslib.as_array(fd.random_points, (fd.random_count, 2)).copy(),
+                        random_zeta=fd.random_zeta, random_static=bool(fd.random_static),
+                        random_interp="loglog" if fd.random_loglog else "linear", random_per_mode=fd.random_per_mode,
+                        random_background=fd.random_background,
+                        random_base=[fd.random_base[k] for k in range(3)] if fd.random_has_base else None)
+                   if fd.has_random else {}),
                 **(dict(buckling_modes=fd.buckling_modes, buckling_tolerance=fd.buckling_tolerance,
                         buckling_max=fd.buckling_max) if fd.buckling_modes else {}))
             deck.linesearch_max, deck.arclength_max = fd.linesearch_max, fd.arclength_max
@@ -689,6 +844,22 @@ class Deck:
                 fd.transient_has_base = 1
                 for k in range(3):
                     fd.transient_base[k] = self.transient_base[k]
+        if len(getattr(self, "spectrum_points", ())):                   # (the struct borrows the arrays of points)
+            fd.has_spectrum, fd.spectrum_count, fd.spectrum_points = 1, len(self.spectrum_points), _d(self.spectrum_points)
+            fd.spectrum_rule, fd.spectrum_static = SPECTRUM_RULES.index(self.spectrum_rule), int(bool(self.spectrum_static))
+            fd.spectrum_loglog, fd.spectrum_zeta, fd.spectrum_zpa = int(self.spectrum_interp == "loglog"), self.spectrum_zeta, self.spectrum_zpa
+            if self.spectrum_base is not None:
+                fd.spectrum_has_base = 1
+                for k in range(3):
+                    fd.spectrum_base[k] = self.spectrum_base[k]
+        if len(getattr(self, "random_points", ())):
+            fd.has_random, fd.random_count, fd.random_points = 1, len(self.random_points), _d(self.random_points)
+            fd.random_static, fd.random_loglog, fd.random_zeta = int(bool(self.random_static)), int(self.random_interp == "loglog"), self.random_zeta
+            fd.random_per_mode, fd.random_background = int(self.random_per_mode), int(self.random_background)
+            if self.random_base is not None:
+                fd.random_has_base = 1
+                for k in range(3):
+                    fd.random_base[k] = self.random_base[k]
         if len(self.contact_faces) and len(self.contact_obstacles):
             # (kept on the deck: the struct borrows the arrays)
             self._contact_kind, self._contact_geom = obstacle_arrays(self.contact_obstacles)
@@ -1119,6 +1290,12 @@ class FeaSolver:
         self._chk(self._lib.feahip_get_locked_count(self._ctx, C.byref(n)))
         return n.value
 
+    def locked_lambda(self):
+        """feahip_get_locked_lambda: the eigenvalues of the modes held, ascending and unshifted."""
+        lam = np.zeros(self.locked_count())
+        self._chk(self._lib.feahip_get_locked_lambda(self._ctx, 0, len(lam), _d(lam)))
+        return lam
+
     def locked_modes(self, first=0, count=None):
         """feahip_get_locked_modes: phi[count][3N] of the last solve_modes_locked, M-orthonormal, zero on the prescribed
         dofs (count=None: from `first` to the last one locked)."""
@@ -1220,6 +1397,51 @@ class FeaSolver:
                                                       int(quantity), _d(peak), _i(at), len(pr), _i(pr), _d(hist), len(sn),
                                                       _i(sn), _d(snap)))
         return peak, at, hist, snap
+
+    # ---- response spectrum and random vibration: one quadratic form per dof ------
+    def _held(self):
+        """The modes held, or None where there are none (the entry called then says why)."""
+        n = C.c_int(0)
+        return n.value if self._lib.feahip_get_locked_count(self._ctx, C.byref(n)) == 0 else None
+
+    def response_combine(self, C_, b=None, s=0.0, absolute=False):
+        """feahip_response_combine: out[3N] = sqrt(max(0, x' C x + 2 u_s (b' x) + s u_s^2)) on every dof, x its values of the
+        modes held (|x| with absolute), u_s the static correction of the load held.  C[n_locked][n_locked] symmetric to the
+        bit and b[n_locked] by ascending mode."""
+        n = self._held()
+        Cm = np.ascontiguousarray(C_, dtype=np.float64)
+        bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        assert n is None or (Cm.shape == (n, n) and (bb is None or bb.shape == (n,)))
+        out = np.zeros(self.ndof)
+        self._chk(self._lib.feahip_response_combine(self._ctx, _d(Cm), None if bb is None else _d(bb), float(s),
+                                                    int(bool(absolute)), _d(out)))
+        return out
+
+    def response_random(self, omega, S, alpha=0.0, beta=0.0, zeta=None, quantity=0):
+        """feahip_response_random: (rms[3N], the modal covariance C[n_locked][n_locked]) of the quantity (0 displacement, 1
+        velocity, 2 acceleration) under the load held times a load factor of one-sided PSD S(omega) per rad/s, omega
+        strictly ascending (host_random_grid makes a grid that resolves the peaks)."""
+        omega, S = np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+        assert omega.ndim == 1 and omega.shape == S.shape
+        n = self._held()
+        rms, cov = np.zeros(self.ndof), np.zeros((n or MODAL_MAX_LOCKED,) * 2)
+        z, zp = (None, None) if n is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_random(self._ctx, len(omega), _d(omega), _d(S), float(alpha), float(beta), zp,
+                                                   int(quantity), _d(rms), _d(cov)))
+        return rms, cov
+
+    def response_spectrum(self, w, sa, rule=SRSS, alpha=0.0, beta=0.0, zeta=None, zpa=0.0, quantity=0, loglog=False):
+        """feahip_response_spectrum: (peak[3N], the peak modal values a[n_locked]) under the response spectrum sa(w), w in
+        rad/s, with the load held (a base load: q_k = -gamma_k), combined by rule SRSS, CQC or ABS; zpa > 0 adds the
+        missing mass of a load held with the static correction."""
+        w, sa = np.ascontiguousarray(w, dtype=np.float64), np.ascontiguousarray(sa, dtype=np.float64)
+        assert w.ndim == 1 and w.shape == sa.shape
+        n = self._held()
+        peak, a = np.zeros(self.ndof), np.zeros(MODAL_MAX_LOCKED)
+        z, zp = (None, None) if n is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_spectrum(self._ctx, len(w), _d(w), _d(sa), int(bool(loglog)), int(rule),
+                                                     float(alpha), float(beta), zp, float(zpa), int(quantity), _d(peak), _d(a)))
+        return peak, a[:n or 0].copy()
 
     # ---- linear buckling ---------------------------------------------------
     def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):

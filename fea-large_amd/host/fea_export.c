@@ -326,6 +326,107 @@ int fea_transient_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char
   return 0;
 }
 
+/* the load of (spectrum ...) and (random ...): with a base direction the base load, else the surface load of the state
+ * reached (all zero: a log line and FEAHIP_EINVAL); F[3N] is scratch */
+static int combine_load(const fea_deck *d, feahip_ctx *ctx, FILE *log, const char *who, int has_base, const double *base,
+                        int correction, double *F)
+{
+  const int nd = 3 * d->nodes_count;
+  int i, rc, any = 0;
+  if (has_base)
+    return feahip_response_base_load(ctx, base, correction, d->solver_type, d->solver_tolerance, d->solver_max_iter, NULL, NULL,
+                                     NULL, NULL, NULL, NULL);
+  if ((rc = feahip_get_surface_forces(ctx, F))) return rc;
+  for (i = 0; i < nd; ++i) any |= F[i] != 0.0;
+  if (!any) {
+    if (log) fprintf(log, "%s: the surface load at the state reached is zero, nothing to run\n", who);
+    return FEAHIP_EINVAL;
+  }
+  return feahip_response_load(ctx, F, correction, d->solver_type, d->solver_tolerance, d->solver_max_iter, NULL, NULL, NULL);
+}
+
+/* one $NodeData section of three components per node behind the file */
+static int append_field(const char *msh_path, const fea_deck *d, const char *name, const double *v)
+{
+  FILE *f = fopen(msh_path, "a");
+  int i;
+  if (!f) return FEAHIP_EINVAL;
+  fprintf(f, "$NodeData\n1\n\"%s\"\n1\n%f\n3\n0\n3\n%d\n", name, 0.0, d->nodes_count);
+  for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %.9e %.9e %.9e\n", i + 1, v[3 * i], v[3 * i + 1], v[3 * i + 2]);
+  fprintf(f, "$EndNodeData\n");
+  fclose(f);
+  return 0;
+}
+
+int fea_spectrum_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
+{
+  static const char *rule[] = {"srss", "cqc", "abs"};
+  FILE *log = (FILE *)log_;
+  const int n = d->spectrum_count, nd = 3 * d->nodes_count;
+  const double two_pi = 6.283185307179586;
+  double *F, *peak, *w, *sa, zeta[FEA_MODAL_MAX_LOCKED], best = -1.0;
+  int i, k, m = 0, rc, best_dof = 0;
+  if (!d->has_spectrum || n <= 0) return 0;
+  if ((rc = feahip_get_locked_count(ctx, &m))) return rc;
+  F = (double *)malloc(sizeof(double) * 2 * (size_t)nd);
+  w = (double *)malloc(sizeof(double) * 2 * (size_t)n);
+  if (!F || !w) { free(F); free(w); return FEAHIP_ENOMEM; }
+  peak = F + nd; sa = w + n;
+  for (k = 0; k < n; ++k) { w[k] = two_pi * d->spectrum_points[2 * k]; sa[k] = d->spectrum_points[2 * k + 1]; }
+  for (k = 0; k < FEA_MODAL_MAX_LOCKED; ++k) zeta[k] = d->spectrum_zeta;
+  rc = combine_load(d, ctx, log, "Spectrum", d->spectrum_has_base, d->spectrum_base, d->spectrum_static, F);
+  if (!rc) rc = feahip_response_spectrum(ctx, n, w, sa, d->spectrum_loglog, d->spectrum_rule, d->has_dynamics ? d->damping_alpha : 0.0,
+                                         d->has_dynamics ? d->damping_beta : 0.0, d->spectrum_zeta > 0 ? zeta : NULL, d->spectrum_zpa,
+                                         0, peak, NULL);
+  if (rc) { free(F); free(w); return rc; }
+  for (i = 0; i < nd; ++i) if (peak[i] > best) { best = peak[i]; best_dof = i; }
+  if (log)
+    fprintf(log, "Spectrum peak: |u| = %.17g, node %d dof %d, rule %s, %d modes\n", best, best_dof / 3 + 1, best_dof % 3,
+            rule[d->spectrum_rule], m);
+  if (msh_path) rc = append_field(msh_path, d, "Spectrum peak displacement", peak);
+  free(F); free(w);
+  return rc;
+}
+
+int fea_random_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
+{
+  FILE *log = (FILE *)log_;
+  const int n = d->random_count, nd = 3 * d->nodes_count;
+  const double two_pi = 6.283185307179586;
+  const double alpha = d->has_dynamics ? d->damping_alpha : 0.0, beta = d->has_dynamics ? d->damping_beta : 0.0;
+  double *F, *rms, *w, *S, *omega = NULL, *Sw, lam[FEA_MODAL_MAX_LOCKED], zeta[FEA_MODAL_MAX_LOCKED], best = -1.0;
+  int i, k, m = 0, rc, best_dof = 0, n_grid = 0, cap;
+  if (!d->has_random || n < 2) return 0;
+  if ((rc = feahip_get_locked_count(ctx, &m))) return rc;
+  F = (double *)malloc(sizeof(double) * 2 * (size_t)nd);
+  w = (double *)malloc(sizeof(double) * 2 * (size_t)n);
+  cap = d->random_background + FEA_MODAL_MAX_LOCKED * d->random_per_mode + n;
+  omega = (double *)malloc(sizeof(double) * 2 * (size_t)cap);
+  if (!F || !w || !omega) { free(F); free(w); free(omega); return FEAHIP_ENOMEM; }
+  rms = F + nd; S = w + n; Sw = omega + cap;
+  for (k = 0; k < n; ++k) {                             /* per Hz over Hz to per rad/s over rad/s: S_f df = S_w dw */
+    w[k] = two_pi * d->random_points[2 * k]; S[k] = d->random_points[2 * k + 1] / two_pi;
+    omega[k] = w[k];                                    /* the table's abscissae are breakpoints of the grid */
+  }
+  for (k = 0; k < FEA_MODAL_MAX_LOCKED; ++k) zeta[k] = d->random_zeta;
+  rc = combine_load(d, ctx, log, "Random", d->random_has_base, d->random_base, d->random_static, F);
+  if (!rc) rc = feahip_get_locked_lambda(ctx, 0, m, lam);
+  if (!rc) {
+    n_grid = n;
+    rc = feahip_host_random_grid(m, lam, alpha, beta, d->random_zeta > 0 ? zeta : NULL, w[0], w[n - 1], d->random_background,
+                                 d->random_per_mode, omega, &n_grid);
+  }
+  for (k = 0; !rc && k < n_grid; ++k) Sw[k] = feahip_host_psd_value(n, w, S, d->random_loglog, omega[k]);
+  if (!rc) rc = feahip_response_random(ctx, n_grid, omega, Sw, alpha, beta, d->random_zeta > 0 ? zeta : NULL, 0, rms, NULL);
+  if (rc) { free(F); free(w); free(omega); return rc; }
+  for (i = 0; i < nd; ++i) if (rms[i] > best) { best = rms[i]; best_dof = i; }
+  if (log)
+    fprintf(log, "Random RMS: |u| = %.17g, node %d dof %d, %d grid points, %d modes\n", best, best_dof / 3 + 1, best_dof % 3, n_grid, m);
+  if (msh_path) rc = append_field(msh_path, d, "RMS displacement", rms);
+  free(F); free(w); free(omega);
+  return rc;
+}
+
 int fea_buckling_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   FILE *log = (FILE *)log_, *f;

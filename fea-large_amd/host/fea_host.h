@@ -21,6 +21,7 @@ extern "C" {
 #define FEA_MAX_MATERIAL_PARAMETERS 10   /* defines.h:22 */
 
 typedef enum { FEA_TETRAHEDRA10 = 0, FEA_TETRAHEDRA4 = 1, FEA_HEXAHEDRA8 = 2 } fea_element_type;
+#define FEA_DECK_MAX_POINTS 4096               /* points of (spectrum (points ...)) and of (random (psd ...)) */
 /* g(t) of (transient :shape ...): 1 from t = 0; min(t / T, 1); sin(pi t / T) up to T and 0 after */
 enum { FEA_SHAPE_STEP = 0, FEA_SHAPE_RAMP = 1, FEA_SHAPE_HALF_SINE = 2 };
 
@@ -111,6 +112,28 @@ typedef struct fea_deck {
    * sweep feasolver_hip runs fea_transient_run.  Written by fea_deck_save only when n > 0: a deck without the section is
    * read, run and written as before.  The fields are the newest of the struct and stand in front of harmonic_count,
    * whose place (with everything behind it) the host tests pin                                                     */
+  /* response spectrum and random vibration, optional, inside (solution ...) beside a (modal ...) with :count or :shift:
+   *   (spectrum :base (bx by bz) :rule srss|cqc|abs :zeta z :static-correction t :zpa a :interp linear|loglog
+   *             (points (f1 sa1) (f2 sa2) ...))
+   *   (random   :base (bx by bz) :zeta z :static-correction t :interp linear|loglog :per-mode n :background n
+   *             (psd (f1 s1) (f2 s2) ...))
+   * f in Hz, strictly ascending and not negative, as in (harmonic ...); sa a spectral acceleration, s a one-sided PSD of the
+   * load factor per Hz, both not negative; up to FEA_DECK_MAX_POINTS points.  :rule srss, :zeta 0, :static-correction t,
+   * :zpa 0, :interp linear, :per-mode 32 and :background 257 where absent.  Without :base the load is the surface load of
+   * the state reached; both have the load errors of (transient ...), and :zpa > 0 needs :static-correction t and a rule
+   * other than abs.  After the transient run feasolver_hip runs fea_spectrum_run and fea_random_run.  Written by
+   * fea_deck_save only when present: a deck without the sections is read, run and written as before.  The fields are the
+   * newest of the struct and stand in front of transient_steps, whose place (with everything behind it) the host tests
+   * pin                                                                                                            */
+  int has_spectrum, spectrum_count;
+  double *spectrum_points;                    /* [spectrum_count][2] = f in Hz, sa */
+  int spectrum_rule;                          /* FEAHIP_SRSS, FEAHIP_CQC, FEAHIP_ABS */
+  int spectrum_static, spectrum_loglog, spectrum_has_base;
+  double spectrum_zeta, spectrum_zpa, spectrum_base[3];
+  int has_random, random_count;
+  double *random_points;                      /* [random_count][2] = f in Hz, S per Hz */
+  int random_static, random_loglog, random_per_mode, random_background, random_has_base;
+  double random_zeta, random_base[3];
   int transient_steps;
   double transient_dt, transient_zeta;
   int transient_static, transient_shape;      /* FEA_SHAPE_* */
@@ -281,6 +304,19 @@ int fea_harmonic_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* *
  * msh_path two $NodeData sections are appended: "Transient peak displacement" and "Transient peak time".  Returns 0, or a
  * negative FEAHIP_E* code.  */
 int fea_transient_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
+/* The design peak of a deck with (spectrum ...), after fea_transient_run and before anything drops the locked modes: the
+ * load as in fea_transient_run (the surface load of the state reached, or with :base the base load), then
+ * feahip_response_spectrum of the displacement with the deck's points (Hz to rad/s), :rule, :zpa, :damping-alpha,
+ * :damping-beta and :zeta.  Log: "Spectrum peak: |u| = p, node a dof j, rule r, m modes" (the largest of all dofs, the
+ * lowest dof among equals, node from 1, dof 0-2).  With msh_path one $NodeData section "Spectrum peak displacement" is
+ * appended.  Returns 0, or a negative FEAHIP_E* code.  */
+int fea_spectrum_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
+/* The RMS displacement of a deck with (random ...), after fea_spectrum_run: the load likewise, the PSD table from per Hz
+ * over Hz to per rad/s over rad/s, the grid of feahip_host_random_grid over the table's band with the table's abscissae
+ * as breakpoints, the PSD read there by feahip_host_psd_value, then feahip_response_random.  Log: "Random RMS: |u| = p,
+ * node a dof j, n grid points, m modes".  With msh_path one $NodeData section "RMS displacement" is appended.  Returns 0,
+ * or a negative FEAHIP_E* code.  */
+int fea_random_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 
 /* The buckling analysis of a deck with (buckling :modes N ...), N > 0, at the state the context is in:
  * feahip_solve_buckling, one log line per mode ("Buckling mode k: factor = f, nu = v") and, with msh_path not NULL, one

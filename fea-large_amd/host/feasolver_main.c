@@ -21,6 +21,9 @@
  * (transient ...) then gets the time history of that load, or of a base
  * acceleration, on the same modes: the peak displacement and its time per dof
  * (feahip_response_base_load, feahip_response_transient).  A deck with
+ * (spectrum ...) or (random ...) then gets the design peak under a response
+ * spectrum or the RMS under a PSD on the same modes, one log line and one
+ * field each (feahip_response_spectrum, feahip_response_random).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid
@@ -103,6 +106,14 @@ int main(int argc, char **argv)
     } else if (deck.transient_steps > 0 && (rc = fea_transient_run(&deck, ctx, stdout, msh))) {
       /* (transient ...): the time history on the same locked modes, before the buckling run drops them */
       fprintf(stderr, "feasolve error encountered: transient run refused or failed (%d): %s\n", rc, feahip_last_error(ctx));
+      status = 1;
+    } else if (deck.has_spectrum && (rc = fea_spectrum_run(&deck, ctx, stdout, msh))) {
+      /* (spectrum ...): the design peak under a response spectrum on the same locked modes */
+      fprintf(stderr, "feasolve error encountered: spectrum run refused or failed (%d): %s\n", rc, feahip_last_error(ctx));
+      status = 1;
+    } else if (deck.has_random && (rc = fea_random_run(&deck, ctx, stdout, msh))) {
+      /* (random ...): the RMS under a PSD on the same locked modes, before the buckling run drops them */
+      fprintf(stderr, "feasolve error encountered: random run refused or failed (%d): %s\n", rc, feahip_last_error(ctx));
       status = 1;
     } else if (deck.buckling_modes > 0 && (rc = fea_buckling_run(&deck, ctx, stdout, msh))) {
       /* (buckling :modes N ...): the load factors at the state reached, the mode shapes behind everything else */

@@ -505,6 +505,72 @@ static int read_element_materials(reader *r, fea_deck *d, int *count)
   return 0;
 }
 
+/* (points (f v) ...) of (spectrum ...) and (psd (f v) ...) of (random ...): pairs of numbers, f strictly ascending and not
+ * negative, v not negative, all finite */
+static int read_pairs(reader *r, double **out, int *count, const char *what)
+{
+  char buf[TOK_MAX], m[96];
+  size_t cap = 64, n = 0;
+  double *p = (double *)malloc(cap * 2 * sizeof(double));
+  int t, k;
+  if (!p) return fail(r, "out of memory reading a list of points");
+  while ((t = next_token(r, buf)) == T_OPEN) {
+    if (n == FEA_DECK_MAX_POINTS) { free(p); snprintf(m, sizeof m, "%s: more than %d points", what, FEA_DECK_MAX_POINTS); return fail(r, m); }
+    if (n == cap) {
+      double *q = (double *)realloc(p, 2 * cap * 2 * sizeof(double));
+      if (!q) { free(p); return fail(r, "out of memory reading a list of points"); }
+      p = q; cap *= 2;
+    }
+    for (k = 0; k < 2; ++k) {
+      char *end;
+      double v;
+      if (next_token(r, buf) != T_ATOM) { free(p); snprintf(m, sizeof m, "%s: a point is a pair of numbers", what); return fail(r, m); }
+      v = strtod(buf, &end);
+      if (end == buf || *end || !(v >= 0 && v <= 1.7976931348623157e308)) {
+        free(p); snprintf(m, sizeof m, "%s: the numbers of a point must be finite and not negative", what); return fail(r, m);
+      }
+      p[2 * n + k] = v;
+    }
+    if (next_token(r, buf) != T_CLOSE) { free(p); snprintf(m, sizeof m, "%s: a point is a pair of numbers", what); return fail(r, m); }
+    if (n > 0 && !(p[2 * n] > p[2 * n - 2])) { free(p); snprintf(m, sizeof m, "%s: the frequencies must be strictly ascending", what); return fail(r, m); }
+    n++;
+  }
+  if (t != T_CLOSE) { free(p); snprintf(m, sizeof m, "%s: expected a list of (f value) pairs", what); return fail(r, m); }
+  free(*out);
+  *out = p; *count = (int)n;
+  return 0;
+}
+
+/* t or nil; the value given stays where the attribute is absent */
+static int read_flag(reader *r, const attr *a, int na, const char *key, int *flag, const char *msg)
+{
+  const char *s = attr_get(a, na, key);
+  if (!s) return 0;
+  if (ieq(s, "nil") || ieq(s, "no") || ieq(s, "false")) *flag = 0;
+  else if (ieq(s, "t") || ieq(s, "yes") || ieq(s, "true")) *flag = 1;
+  else return fail(r, msg);
+  return 0;
+}
+
+/* :base (bx by bz), its atoms blank-separated by read_attrs: three finite numbers, not all zero */
+static int read_base(reader *r, const attr *a, int na, int *has, double *base, const char *msg)
+{
+  const char *s = attr_get(a, na, "base");
+  char *end;
+  int k;
+  *has = 0; base[0] = base[1] = base[2] = 0;
+  if (!s) return 0;
+  for (k = 0; k < 3; ++k) {
+    base[k] = strtod(s, &end);
+    if (end == s || !(base[k] >= -1.7976931348623157e308 && base[k] <= 1.7976931348623157e308)) return fail(r, msg);
+    s = end;
+  }
+  while (*s == ' ') ++s;
+  if (*s || (base[0] == 0 && base[1] == 0 && base[2] == 0)) return fail(r, msg);
+  *has = 1;
+  return 0;
+}
+
 /* one list, '(' consumed: dispatch on the head like traverse_function
  * (sexp_loader.c:249-272) */
 static int read_list(reader *r, fea_deck *d)
@@ -528,6 +594,8 @@ static int read_list(reader *r, fea_deck *d)
   if (ieq(head, "contact")) return read_contact(r, d);
   if (ieq(head, "materials")) return read_materials(r, d);
   if (ieq(head, "element-materials")) return read_element_materials(r, d, &r->n_element_material);
+  if (ieq(head, "points")) return read_pairs(r, &d->spectrum_points, &d->spectrum_count, "spectrum (points ...)");
+  if (ieq(head, "psd")) return read_pairs(r, &d->random_points, &d->random_count, "random (psd ...)");
 
   if (read_attrs(r, d, a, &na, 1)) return -1;
 
@@ -704,6 +772,50 @@ static int read_list(reader *r, fea_deck *d)
       if (d->transient_base[0] == 0 && d->transient_base[1] == 0 && d->transient_base[2] == 0) return fail(r, "transient :base must not be zero");
       d->transient_has_base = 1;
     }
+  } else if (ieq(head, "spectrum")) {                         /* no counterpart in the reference */
+    d->spectrum_rule = FEAHIP_SRSS; d->spectrum_zeta = 0; d->spectrum_zpa = 0; d->spectrum_static = 1; d->spectrum_loglog = 0;
+    if ((s = attr_get(a, na, "rule"))) {
+      if (ieq(s, "srss")) d->spectrum_rule = FEAHIP_SRSS;
+      else if (ieq(s, "cqc")) d->spectrum_rule = FEAHIP_CQC;
+      else if (ieq(s, "abs")) d->spectrum_rule = FEAHIP_ABS;
+      else return fail(r, "spectrum :rule must be srss, cqc or abs");
+    }
+    if (attr_get(a, na, "zeta") && need_num(r, a, na, "zeta", &d->spectrum_zeta)) return -1;
+    if (!(d->spectrum_zeta >= 0 && d->spectrum_zeta <= 1.7976931348623157e308)) return fail(r, "spectrum :zeta must be finite and not negative");
+    if (attr_get(a, na, "zpa") && need_num(r, a, na, "zpa", &d->spectrum_zpa)) return -1;
+    if (!(d->spectrum_zpa >= 0 && d->spectrum_zpa <= 1.7976931348623157e308)) return fail(r, "spectrum :zpa must be finite and not negative");
+    if (read_flag(r, a, na, "static-correction", &d->spectrum_static, "spectrum :static-correction takes t or nil")) return -1;
+    if ((s = attr_get(a, na, "interp"))) {
+      if (ieq(s, "loglog")) d->spectrum_loglog = 1;
+      else if (!ieq(s, "linear")) return fail(r, "spectrum :interp must be linear or loglog");
+    }
+    if (read_base(r, a, na, &d->spectrum_has_base, d->spectrum_base, "spectrum :base takes three finite numbers, not all zero")) return -1;
+    if (d->spectrum_zpa > 0 && !d->spectrum_static) return fail(r, "spectrum :zpa needs :static-correction t");
+    if (d->spectrum_zpa > 0 && d->spectrum_rule == FEAHIP_ABS) return fail(r, "spectrum :zpa needs a rule other than abs");
+    if (d->spectrum_count < 1) return fail(r, "spectrum needs (points (f sa) ...)");
+    d->has_spectrum = 1;
+  } else if (ieq(head, "random")) {                           /* no counterpart in the reference */
+    d->random_zeta = 0; d->random_static = 1; d->random_loglog = 0; d->random_per_mode = 32; d->random_background = 257;
+    if (attr_get(a, na, "zeta") && need_num(r, a, na, "zeta", &d->random_zeta)) return -1;
+    if (!(d->random_zeta >= 0 && d->random_zeta <= 1.7976931348623157e308)) return fail(r, "random :zeta must be finite and not negative");
+    if (read_flag(r, a, na, "static-correction", &d->random_static, "random :static-correction takes t or nil")) return -1;
+    if ((s = attr_get(a, na, "interp"))) {
+      if (ieq(s, "loglog")) d->random_loglog = 1;
+      else if (!ieq(s, "linear")) return fail(r, "random :interp must be linear or loglog");
+    }
+    if (attr_get(a, na, "per-mode")) {
+      if (need_num(r, a, na, "per-mode", &v)) return -1;
+      if (!(v >= 0 && v <= 4096) || v != (double)(int)v) return fail(r, "random :per-mode must be an integer in [0, 4096]");
+      d->random_per_mode = (int)v;
+    }
+    if (attr_get(a, na, "background")) {
+      if (need_num(r, a, na, "background", &v)) return -1;
+      if (!(v >= 2 && v <= 131072) || v != (double)(int)v) return fail(r, "random :background must be an integer in [2, 131072]");
+      d->random_background = (int)v;
+    }
+    if (read_base(r, a, na, &d->random_has_base, d->random_base, "random :base takes three finite numbers, not all zero")) return -1;
+    if (d->random_count < 2) return fail(r, "random needs (psd (f s) ...) with two points at least");
+    d->has_random = 1;
   } else if (ieq(head, "buckling")) {                         /* no counterpart in the reference */
     if (need_num(r, a, na, "modes", &v)) return -1;
     if (!(v >= 1 && v <= FEA_MODAL_COLS) || v != (double)(int)v) return fail(r, "buckling :modes must be an integer in [1, 8]");
@@ -797,6 +909,15 @@ int fea_deck_load(const char *path, fea_deck *deck, char *errbuf, int errlen)
     if (rc == 0 && deck->transient_steps > 0 && !(deck->modal_count > 0 || (deck->modal_modes > 0 && deck->modal_shift != 0.0))) {
       rc = -1; snprintf(r.err, sizeof r.err, "deck has (transient ...) but no locked modes: add (modal :count N ...) or a :shift");
     }
+    if (rc == 0 && (deck->has_spectrum || deck->has_random) && !(deck->modal_count > 0 || (deck->modal_modes > 0 && deck->modal_shift != 0.0))) {
+      rc = -1; snprintf(r.err, sizeof r.err, "deck has (%s ...) but no locked modes: add (modal :count N ...) or a :shift", deck->has_spectrum ? "spectrum" : "random");
+    }
+    if (rc == 0 && deck->has_spectrum && deck->spectrum_static && deck->modal_shift != 0.0) {
+      rc = -1; snprintf(r.err, sizeof r.err, "spectrum :static-correction t and a non-zero modal :shift exclude each other");
+    }
+    if (rc == 0 && deck->has_random && deck->random_static && deck->modal_shift != 0.0) {
+      rc = -1; snprintf(r.err, sizeof r.err, "random :static-correction t and a non-zero modal :shift exclude each other");
+    }
     if (rc == 0 && deck->transient_steps > 0 && deck->transient_static && deck->modal_shift != 0.0) {
       rc = -1; snprintf(r.err, sizeof r.err, "transient :static-correction t and a non-zero modal :shift exclude each other");
     }
@@ -821,6 +942,8 @@ void fea_deck_free(fea_deck *d)
   free(d->contact_nodes); free(d->contact_kind); free(d->contact_geom);
   d->contact_nodes = d->contact_kind = NULL; d->contact_geom = NULL;
   d->contact_faces_count = d->contact_obstacles_count = 0;
+  free(d->spectrum_points); free(d->random_points);
+  d->spectrum_points = d->random_points = NULL; d->spectrum_count = d->random_count = d->has_spectrum = d->has_random = 0;
   free(d->material_params); free(d->element_material);
   d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
@@ -880,6 +1003,25 @@ int fea_deck_save(const char *path, const fea_deck *d)
     if (d->transient_has_base)
       fprintf(f, " :base (%.17g %.17g %.17g)", d->transient_base[0], d->transient_base[1], d->transient_base[2]);
     fprintf(f, ")");
+  }
+  if (d->has_spectrum) {                                                       /* written only when present */
+    static const char *rule[] = {"srss", "cqc", "abs"};
+    fprintf(f, "\n   (spectrum :rule %s :zeta %.17g :static-correction %s :zpa %.17g :interp %s", rule[d->spectrum_rule],
+            d->spectrum_zeta, d->spectrum_static ? "t" : "nil", d->spectrum_zpa, d->spectrum_loglog ? "loglog" : "linear");
+    if (d->spectrum_has_base)
+      fprintf(f, " :base (%.17g %.17g %.17g)", d->spectrum_base[0], d->spectrum_base[1], d->spectrum_base[2]);
+    fprintf(f, "\n    (points");
+    for (i = 0; i < d->spectrum_count; ++i) fprintf(f, " (%.17g %.17g)", d->spectrum_points[2 * i], d->spectrum_points[2 * i + 1]);
+    fprintf(f, "))");
+  }
+  if (d->has_random) {                                                         /* written only when present */
+    fprintf(f, "\n   (random :zeta %.17g :static-correction %s :interp %s :per-mode %d :background %d", d->random_zeta,
+            d->random_static ? "t" : "nil", d->random_loglog ? "loglog" : "linear", d->random_per_mode, d->random_background);
+    if (d->random_has_base)
+      fprintf(f, " :base (%.17g %.17g %.17g)", d->random_base[0], d->random_base[1], d->random_base[2]);
+    fprintf(f, "\n    (psd");
+    for (i = 0; i < d->random_count; ++i) fprintf(f, " (%.17g %.17g)", d->random_points[2 * i], d->random_points[2 * i + 1]);
+    fprintf(f, "))");
   }
   if (d->buckling_modes > 0)                                                   /* written only when asked for */
     fprintf(f, "\n   (buckling :modes %d :tolerance %.17g :max %d)", d->buckling_modes, d->buckling_tolerance, d->buckling_max);

@@ -870,6 +870,10 @@ int feahip_solve_modes_locked(feahip_ctx *ctx, int n_modes, double shift, double
                               int *sweeps /*may be NULL*/);
 int feahip_get_locked_modes(feahip_ctx *ctx, int first, int count, double *phi /*[count][3N], caller's dof order*/);
 int feahip_get_locked_count(feahip_ctx *ctx, int *count);
+/* lambda[count] of the modes first .. first + count - 1 held (feahip_solve_modes_locked or feahip_response_set_basis),
+ * ascending and unshifted: the values the response entries use.  FEAHIP_ESTATE without modes held, FEAHIP_EINVAL for a
+ * range outside them. */
+int feahip_get_locked_lambda(feahip_ctx *ctx, int first, int count, double *lambda /*[count]*/);
 /* Test hook for the deflation kernels: out8 = x8 - Q (MQ' x8) with MQ = mask(M Q)
  * from the block product, q[n_locked][3N], x8 and out8 [8][3N] host vectors in
  * the caller's dof order, 1 <= n_locked <= 64.  Refused where feahip_spmm_km is;
@@ -1064,6 +1068,104 @@ int feahip_host_transient_coefficients(int n_modes, const double *lam, const dou
                                        const double *g /*[n_steps + 1]*/, double alpha, double beta_k,
                                        const double *zeta /*[n_modes] or NULL*/, int static_correction, int quantity,
                                        double *coef /*[n_steps + 1][64], zero past n_modes*/);
+
+/* ---- response spectrum and random vibration on the locked modes ----
+ * Both ask one thing of the modes and the load held: on every dof a quadratic
+ * form of its own mode values x_i = (phi_i1 .. phi_im),
+ *     out_i = sqrt(max(0, x_i' C x_i + 2 u_s,i (b' x_i) + s u_s,i^2)),
+ * C[m][m] symmetric, b[m] and s the same for every dof and made on the host.
+ * k_response_combine evaluates it in one launch: a lane owns a dof, holds its
+ * mode values in registers and reads the table, folded onto its upper triangle,
+ * through the scalar data cache; m (m + 1) / 2 + 2 m FMAs per dof, whatever the
+ * number of frequencies behind C.  A context that never calls the entries below
+ * allocates and launches nothing for them; the table is a device buffer of its
+ * own (about 33 KB, made by the first call), so the tables of the last sweep
+ * and of the last transient stay (hooks 23 and 25 of feahip_time_kernel).
+ *
+ * feahip_response_combine: the form as given.  C[n_locked][n_locked] and
+ * b[n_locked] (NULL: zero) by ascending mode, `absolute` != 0 takes |phi_ik|
+ * for every mode value (the ABS rule is the form C = |a||a|').  out[3N] in the
+ * caller's dof order, exactly 0 on the prescribed dofs and where the form is
+ * negative.  The same input gives the same bits.  FEAHIP_EINVAL: C not
+ * symmetric to the bit, or C, twice an off-diagonal entry of C (the table holds
+ * the upper triangle doubled), b or s not finite.
+ *
+ * feahip_response_random: the RMS under a one-sided PSD S(w) per rad/s of the
+ * load factor g (the load is F g(t), int S dw the mean square of g), given at
+ * n_freq strictly ascending omega_j.  With a(w_j) the coefficient row of
+ * feahip_response_sweep (that very code), wt_j the trapezoid weights and p =
+ * quantity (0 displacement, 1 velocity, 2 acceleration)
+ *     C_kl = sum_j wt_j S_j w_j^(2p) Re(a_k conj(a_l))
+ *     b_k  = sum_j wt_j S_j w_j^(2p) Re(a_k),   s = sum_j wt_j S_j w_j^(2p)
+ * (b = 0, s = 0 for a load held without the static correction), accumulated in
+ * long double: rms_i^2 is the trapezoid rule of S |(i w)^p u_i(w)|^2 over the
+ * fields feahip_response_field returns.  modal_cov[n_locked][n_locked] (may be
+ * NULL) receives C.  n_freq in [2, FEA_RANDOM_MAX_FREQ].
+ * feahip_host_random_form is the same builder without a device; it refuses what
+ * feahip_response_sweep refuses of the same arguments, an omega that is not
+ * strictly ascending and an S that is negative or not finite.
+ * feahip_host_random_grid: a grid that resolves every peak, the union of
+ * n_background >= 2 points of linspace(w_lo, w_hi), for every mode with lam_k >
+ * 0 and d_k > 0 the n_per_mode points w_k + (d_k / 2) tan(theta_i), theta_i =
+ * ((i + 1/2) / n_per_mode) pi - pi / 2 (the substitution that makes a
+ * Lorentzian peak flat), and the caller's breakpoints: *n_out of them at the
+ * front of omega_out on entry.  Clipped to [w_lo, w_hi], sorted, duplicates
+ * removed; *n_out is the count on return.  omega_out holds n_background +
+ * n_modes n_per_mode + the breakpoints; NULL asks for the count alone (no
+ * breakpoints then).  FEAHIP_EINVAL also for more than FEA_RANDOM_MAX_FREQ
+ * points.
+ * feahip_host_psd_value: the table (w[n_pts] strictly ascending, S[n_pts]) at
+ * `at`, linear or (loglog != 0) linear in the logarithms, a point's own value at
+ * a point, zero outside the table.  feahip_host_spectrum_value: the same with
+ * the end values outside.  NaN for a table that is none.
+ *
+ * feahip_response_spectrum: the design peak under a response spectrum Sa(w)
+ * (n_pts points, w in rad/s) with the load held; under a base load q_k =
+ * -gamma_k.  sa_k = Sa(sqrt(lam_k)), a_k = q_k sa_k / lam_k the peak modal
+ * displacement (times sqrt(lam_k), lam_k for quantity 1, 2: pseudo-velocity and
+ * -acceleration).  rule FEAHIP_SRSS: C = diag(a_k^2).  FEAHIP_CQC: C_jk =
+ * rho_jk a_j a_k,
+ *     rho_jk = 8 sqrt(z_j z_k) (z_j + r z_k) r^1.5 /
+ *              ((1 - r^2)^2 + 4 z_j z_k r (1 + r^2) + 4 (z_j^2 + z_k^2) r^2),
+ * r = w_k / w_j, z_k = d_k / (2 w_k) (Der Kiureghian, unequal damping); rho_kk
+ * = 1 exactly, a zero denominator off the diagonal gives 1, all z = 0 gives the
+ * SRSS table.  FEAHIP_ABS: C = |a||a|' on |phi|.  Missing mass: with a load
+ * held with the static correction, zpa > 0 and quantity 0 the rigid residual
+ * zpa (u_s + sum_k phi_k c_k), c_k = -q_k / lam_k, is added by SRSS: C += zpa^2
+ * c c', b = zpa^2 c, s = zpa^2.  modal_peak[n_locked] (may be NULL) receives
+ * a_k.  FEAHIP_EINVAL: lam_k <= 0 for any mode, an unknown rule or quantity, a
+ * negative or non-finite sa or zpa, zpa != 0 at quantity 1 or 2, without the
+ * static correction or with FEAHIP_ABS (the residual needs the signed values).
+ * feahip_host_spectrum_form is the builder without a device, sa[n_modes] given.
+ *
+ * The three device entries: FEAHIP_ESTATE without modes held or without a load
+ * held for them, FEAHIP_EINVAL on a row-sharded or feahip_create_rank* context,
+ * as feahip_response_transient; x, v, a, the time, the load factor, K, f, u,
+ * the locked store, the load held and both coefficient tables are untouched.
+ * Not offered: sharded runs, combining several excitation directions, absolute
+ * (base-plus-relative) acceleration, closed-form PSD integrals, cross-spectra
+ * between several loads, zero-crossing rates and fatigue counts.               */
+#define FEA_RANDOM_MAX_FREQ 262144
+enum { FEAHIP_SRSS = 0, FEAHIP_CQC = 1, FEAHIP_ABS = 2 };
+int feahip_response_combine(feahip_ctx *ctx, const double *C /*[n_locked][n_locked]*/, const double *b /*[n_locked] or NULL*/,
+                            double s, int absolute, double *out /*[3N]*/);
+int feahip_response_random(feahip_ctx *ctx, int n_freq, const double *omega /*[n_freq]*/, const double *S /*[n_freq]*/,
+                           double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/, int quantity,
+                           double *rms /*[3N]*/, double *modal_cov /*[n_locked][n_locked] or NULL*/);
+int feahip_response_spectrum(feahip_ctx *ctx, int n_pts, const double *w /*[n_pts]*/, const double *sa /*[n_pts]*/, int loglog,
+                             int rule, double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/, double zpa,
+                             int quantity, double *peak /*[3N]*/, double *modal_peak /*[n_locked] or NULL*/);
+int feahip_host_random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S,
+                            double alpha, double beta_k, const double *zeta /*[n_modes] or NULL*/, int static_correction,
+                            int quantity, double *C /*[n_modes][n_modes]*/, double *b /*[n_modes]*/, double *s);
+int feahip_host_random_grid(int n_modes, const double *lam, double alpha, double beta_k, const double *zeta /*[n_modes] or NULL*/,
+                            double w_lo, double w_hi, int n_background, int n_per_mode, double *omega_out /*or NULL*/,
+                            int *n_out);
+double feahip_host_psd_value(int n_pts, const double *w, const double *S, int loglog, double at);
+double feahip_host_spectrum_value(int n_pts, const double *w, const double *sa, int loglog, double at);
+int feahip_host_spectrum_form(int n_modes, const double *lam, const double *q, const double *sa /*[n_modes]*/, double alpha,
+                              double beta_k, const double *zeta /*[n_modes] or NULL*/, int rule, int static_correction,
+                              double zpa, int quantity, double *C /*[n_modes][n_modes]*/, double *b /*[n_modes]*/, double *s);
 
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
@@ -1412,7 +1514,9 @@ int feahip_sync(feahip_ctx *ctx);
  * on the f in force (both FEAHIP_ESTATE before a sweep; nothing but the sweep's
  * own output buffers and partial sums is written); 25 one launch of
  * k_transient_sweep over the last chunk of the last feahip_response_transient
- * (FEAHIP_ESTATE, "no transient", before one).                               */
+ * (FEAHIP_ESTATE, "no transient", before one); 26 k_response_combine over the
+ * form of the last feahip_response_combine, _random or _spectrum
+ * (FEAHIP_ESTATE, "no form", before one).                                    */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
