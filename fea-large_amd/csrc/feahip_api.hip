@@ -1566,15 +1566,51 @@ extern "C" int feahip_response_set_basis(feahip_ctx *c, int n, const double *lam
   return FEAHIP_OK;
 }
 
+static int modes_held(feahip_ctx *c, const char *who)
+{
+  if (c->modal.have_locked) return FEAHIP_OK;
+  c->err = std::string(who) + ": no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)";
+  return FEAHIP_ESTATE;
+}
+
 // the load held belongs to the modes held
 static int response_loaded(feahip_ctx *c, const char *who)
 {
-  if (!c->modal.have_locked) { c->err = std::string(who) + ": no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)"; return FEAHIP_ESTATE; }
+  if (const int rc = modes_held(c, who)) return rc;
   if (!c->response.loaded || c->response.gen != c->modal.lock_gen) {
     c->err = std::string(who) + ": no load held for these modes (feahip_response_load first)";
     return FEAHIP_ESTATE;
   }
   return FEAHIP_OK;
+}
+
+// a load with the static correction: K u_s = F needs a solver and modes of a K that is not singular
+static int static_correction_args(feahip_ctx *c, const std::string &who, int solver_type, int max_iterations)
+{
+  const ModalState &S = c->modal;
+  if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = who + ": unknown solver type"; return FEAHIP_EINVAL; }
+  if (max_iterations <= 0) { c->err = who + ": max_iterations must be positive"; return FEAHIP_EINVAL; }
+  if (S.shift > 0.0) { c->err = who + ": the modes come from a solve with a shift, a body whose K may be singular: no static correction"; return FEAHIP_EINVAL; }
+  for (int k = 0; k < S.n_locked; ++k)
+    if (!(S.lam[k] > 0.0)) { c->err = who + ": lam of mode " + std::to_string(k + 1) + " is not positive: no static correction"; return FEAHIP_EINVAL; }
+  return FEAHIP_OK;
+}
+
+// lib[r] = the library's dof of the caller's probe_dof[r], each inside [0, 3N)
+static int probe_dofs(feahip_ctx *c, const char *who, int n_probe, const int *probe_dof, int *lib)
+{
+  for (int r = 0; r < n_probe; ++r) {
+    if (probe_dof[r] < 0 || probe_dof[r] >= c->ndof) { c->err = std::string(who) + ": probe dof outside [0, 3N)"; return FEAHIP_EINVAL; }
+    lib[r] = 3 * lib_id(c, probe_dof[r] / 3) + probe_dof[r] % 3;
+  }
+  return FEAHIP_OK;
+}
+
+// peak [3N] and peak_at [3N] from the library's order into the caller's
+static void peaks_to_caller(feahip_ctx *c, const double *lib_peak, double *peak, const int *lib_at, int *peak_at)
+{
+  to_caller(view_of(c), 3, 3, lib_peak, peak);
+  to_caller(view_of(c), 3, 3, lib_at, peak_at);
 }
 
 extern "C" int feahip_response_load(feahip_ctx *c, const double *F, int static_correction, int solver_type, double tolerance,
@@ -1585,16 +1621,8 @@ extern "C" int feahip_response_load(feahip_ctx *c, const double *F, int static_c
   if (resid) *resid = 0.0;
   if (!F) { c->err = "response_load: null F"; return FEAHIP_EINVAL; }
   int rc;
-  if ((rc = modal_ready(c, "response_load"))) return rc;
-  const ModalState &S = c->modal;
-  if (!S.have_locked) { c->err = "response_load: no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)"; return FEAHIP_ESTATE; }
-  if (static_correction) {
-    if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "response_load: unknown solver type"; return FEAHIP_EINVAL; }
-    if (max_iterations <= 0) { c->err = "response_load: max_iterations must be positive"; return FEAHIP_EINVAL; }
-    if (S.shift > 0.0) { c->err = "response_load: the modes come from a solve with a shift, a body whose K may be singular: no static correction"; return FEAHIP_EINVAL; }
-    for (int k = 0; k < S.n_locked; ++k)
-      if (!(S.lam[k] > 0.0)) { c->err = "response_load: lam of mode " + std::to_string(k + 1) + " is not positive: no static correction"; return FEAHIP_EINVAL; }
-  }
+  if ((rc = modal_ready(c, "response_load")) || (rc = modes_held(c, "response_load"))) return rc;
+  if (static_correction && (rc = static_correction_args(c, "response_load", solver_type, max_iterations))) return rc;
   for (int i = 0; i < c->ndof; ++i)
     if (!std::isfinite(F[i])) { c->err = "response_load: F is not finite"; return FEAHIP_EINVAL; }
   std::vector<double> tmp((size_t)c->ndof);
@@ -1622,15 +1650,11 @@ extern "C" int feahip_response_sweep(feahip_ctx *c, int n_freq, const double *om
   if (n_probe < 0 || n_probe > 64) { c->err = "response_sweep: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
   if (n_probe > 0 && (!probe_dof || !probe_re || !probe_im)) { c->err = "response_sweep: null probe arrays"; return FEAHIP_EINVAL; }
   int probe[64];
-  for (int r = 0; r < n_probe; ++r) {
-    if (probe_dof[r] < 0 || probe_dof[r] >= c->ndof) { c->err = "response_sweep: probe dof outside [0, 3N)"; return FEAHIP_EINVAL; }
-    probe[r] = 3 * lib_id(c, probe_dof[r] / 3) + probe_dof[r] % 3;
-  }
+  if ((rc = probe_dofs(c, "response_sweep", n_probe, probe_dof, probe))) return rc;
   std::vector<double> pk((size_t)c->ndof);
   std::vector<int> at((size_t)c->ndof);
   if ((rc = response_sweep(c, false, n_freq, omega, alpha, beta_k, zeta, pk.data(), at.data(), n_probe, probe, probe_re, probe_im))) return rc;
-  to_caller(view_of(c), 3, 3, pk.data(), peak);
-  to_caller(view_of(c), 3, 3, at.data(), peak_at);
+  peaks_to_caller(c, pk.data(), peak, at.data(), peak_at);
   return FEAHIP_OK;
 }
 
@@ -1665,16 +1689,8 @@ extern "C" int feahip_response_base_load(feahip_ctx *c, const double *dir, int s
   if (resid) *resid = 0.0;
   if (!dir) { c->err = "response_base_load: null dir"; return FEAHIP_EINVAL; }
   int rc;
-  if ((rc = modal_ready(c, "response_base_load"))) return rc;
-  const ModalState &S = c->modal;
-  if (!S.have_locked) { c->err = "response_base_load: no modes held (feahip_solve_modes_locked or feahip_response_set_basis first)"; return FEAHIP_ESTATE; }
-  if (static_correction) {
-    if (solver_type < FEAHIP_CG || solver_type > FEAHIP_CHOLESKY) { c->err = "response_base_load: unknown solver type"; return FEAHIP_EINVAL; }
-    if (max_iterations <= 0) { c->err = "response_base_load: max_iterations must be positive"; return FEAHIP_EINVAL; }
-    if (S.shift > 0.0) { c->err = "response_base_load: the modes come from a solve with a shift, a body whose K may be singular: no static correction"; return FEAHIP_EINVAL; }
-    for (int k = 0; k < S.n_locked; ++k)
-      if (!(S.lam[k] > 0.0)) { c->err = "response_base_load: lam of mode " + std::to_string(k + 1) + " is not positive: no static correction"; return FEAHIP_EINVAL; }
-  }
+  if ((rc = modal_ready(c, "response_base_load")) || (rc = modes_held(c, "response_base_load"))) return rc;
+  if (static_correction && (rc = static_correction_args(c, "response_base_load", solver_type, max_iterations))) return rc;
   if (!std::isfinite(dir[0]) || !std::isfinite(dir[1]) || !std::isfinite(dir[2])) { c->err = "response_base_load: dir is not finite"; return FEAHIP_EINVAL; }
   if (dir[0] == 0.0 && dir[1] == 0.0 && dir[2] == 0.0) { c->err = "response_base_load: dir is zero"; return FEAHIP_EINVAL; }
   // r = dir on every node, the prescribed ones included, in the node layout (xt is free outside a step); y = M r
@@ -1689,7 +1705,7 @@ extern "C" int feahip_response_base_load(feahip_ctx *c, const double *dir, int s
   for (int i = 0; i < c->ndof; ++i) total += (long double)dir[i % 3] * mr[i];
   double qs[FEA_MODAL_MAX_LOCKED];
   if ((rc = response_load(c, nullptr, static_correction, solver_type, tolerance, max_iterations, qs, iters, resid))) return rc;
-  for (int k = 0; k < S.n_locked; ++k) {
+  for (int k = 0; k < c->modal.n_locked; ++k) {
     if (q) q[k] = qs[k];
     if (gamma) gamma[k] = -qs[k];
     if (eff_mass) eff_mass[k] = qs[k] * qs[k];
@@ -1712,10 +1728,7 @@ extern "C" int feahip_response_transient(feahip_ctx *c, int n_steps, double dt, 
   if (n_snap < 0 || n_snap > 4096) { c->err = "response_transient: n_snap must be in [0, 4096]"; return FEAHIP_EINVAL; }
   if (n_snap > 0 && (!snap_step || !snap)) { c->err = "response_transient: null snapshot arrays"; return FEAHIP_EINVAL; }
   int lib_probe[64];
-  for (int r = 0; r < n_probe; ++r) {
-    if (probe_dof[r] < 0 || probe_dof[r] >= c->ndof) { c->err = "response_transient: probe dof outside [0, 3N)"; return FEAHIP_EINVAL; }
-    lib_probe[r] = 3 * lib_id(c, probe_dof[r] / 3) + probe_dof[r] % 3;
-  }
+  if ((rc = probe_dofs(c, "response_transient", n_probe, probe_dof, lib_probe))) return rc;
   for (int s = 0; s < n_snap; ++s)
     if (snap_step[s] < 0 || snap_step[s] > n_steps) { c->err = "response_transient: snapshot step outside [0, n_steps]"; return FEAHIP_EINVAL; }
   const size_t nd = (size_t)c->ndof;
@@ -1723,8 +1736,7 @@ extern "C" int feahip_response_transient(feahip_ctx *c, int n_steps, double dt, 
   std::vector<int> at(nd);
   if ((rc = response_transient(c, n_steps, dt, g, alpha, beta_k, zeta, quantity, pk.data(), at.data(), n_probe, lib_probe, probe,
                                n_snap, snap_step, fields.data()))) return rc;
-  to_caller(view_of(c), 3, 3, pk.data(), peak);
-  to_caller(view_of(c), 3, 3, at.data(), peak_at);
+  peaks_to_caller(c, pk.data(), peak, at.data(), peak_at);
   for (int s = 0; s < n_snap; ++s) to_caller(view_of(c), 3, 3, fields.data() + (size_t)s * nd, snap + (size_t)s * nd);
   return FEAHIP_OK;
 }

@@ -5,8 +5,8 @@
 //   out_i = sqrt(max(0,  x_i' C x_i  +  2 u_s,i (b' x_i)  +  s u_s,i^2 ))
 // C, b and s are the same for every dof and come from the host: a PSD's covariance of the modal coordinates, rho_jk a_j a_k
 // of SRSS and CQC, |a||a|' of ABS; the missing-mass term and the mode-acceleration correction enter through b and s.
-//   k_response_combine<P, ABSX>   the structure of k_response_sweep: a lane owns one dof and loads its 8 P mode values once,
-//                           as 16-byte loads, and its u_s.  The form table is a device buffer of its own, [64][64] by
+//   k_response_combine<P, ABSX>   the structure of k_response_sweep: a lane owns one dof and loads its 8 P mode values once
+//                           (superpose.h) and its u_s.  The form table is a device buffer of its own, [64][64] by
 //                           store column, then b[64], then s.  The host folds C onto its upper triangle (the diagonal as
 //                           it is, the entries above it doubled, which is exact, zero below), so the kernel evaluates
 //                             sum_j x_j (sum_{k >= j} T_jk x_k):  m (m + 1) / 2 + m v_fma_f64 where the full form has
@@ -17,20 +17,14 @@
 //                           (sum_k |phi_ik| |a_k|)^2, is the form with C = |a||a|'.
 // d_coef is not touched: the tables of the last sweep and transient stay (hooks 23 and 25).  No atomics, the same bits on
 // every call.  A context that never calls a combine entry allocates and launches nothing of this file.
-#include "feahip_internal.h"
-#include <cmath>
-#include <vector>
+#include "superpose.h"
 
-#define MC FEA_MODAL_COLS
-#define ML FEA_MODAL_MAX_LOCKED
-static_assert(MC == 8 && ML == 64, "the kernel below is written for eight panels of eight columns");
 // Rows of the triangle evaluated together: so many independent FMA chains per dof.  Measured;
 // `make variant NAME=cr4 VSRC=kernels_combine VFLAGS=-DCOMBINE_ROWS=4` forces another value
 #ifndef COMBINE_ROWS
 #define COMBINE_ROWS 2
 #endif
 static_assert(COMBINE_ROWS == 1 || COMBINE_ROWS == 2 || COMBINE_ROWS == 4 || COMBINE_ROWS == 8, "COMBINE_ROWS divides 8");
-typedef double comb_v2d __attribute__((ext_vector_type(2)));
 
 // out[d] = sqrt(max(0, x' T x + us (2 b' x + s us))) over the columns c < 8 P, T the folded table (see above).
 // A workgroup takes 256 consecutive dofs
@@ -44,15 +38,7 @@ void k_response_combine(int ndof, const double *__restrict__ Q, size_t pstride, 
   const bool in = d < ndof;
   double x[M];
   const double u0 = in ? us[d] : 0.0;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const comb_v2d *Qd = reinterpret_cast<const comb_v2d *>(Q + (size_t)p * pstride) + (size_t)(in ? d : 0) * 4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const comb_v2d t = in ? Qd[k] : comb_v2d{0.0, 0.0};
-      x[p * MC + 2 * k] = ABSX ? fabs(t.x) : t.x; x[p * MC + 2 * k + 1] = ABSX ? fabs(t.y) : t.y;
-    }
-  }
+  load_mode_values<P, ABSX>(Q, pstride, d, in, x);
   // R rows together (R divides 8): t[r] = sum_{k >= j + r} T_{j+r,k} x_k, column by column over the R chains, then
   // acc += x_{j+r} t[r] (uniform addresses: scalar loads)
   constexpr int R = COMBINE_ROWS;
@@ -86,31 +72,17 @@ void k_response_combine(int ndof, const double *__restrict__ Q, size_t pstride, 
 // ------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------
-template <int P>
-static void enq_combine_p(feahip_ctx *c, bool absx)
+template <int P, bool ABSX>
+static void enq_combine_p(feahip_ctx *c)
 {
   ResponseState &R = c->response;
-  const dim3 grid((c->ndof + 255) / 256), block(256);
-  if (absx)
-    hipLaunchKernelGGL((k_response_combine<P, true>), grid, block, 0, c->stream, c->ndof, (const double *)locked_panel(c, 0, 0),
-                       (size_t)c->ndof * MC, (const double *)R.d_us, (const double *)R.d_form, R.d_out);
-  else
-    hipLaunchKernelGGL((k_response_combine<P, false>), grid, block, 0, c->stream, c->ndof, (const double *)locked_panel(c, 0, 0),
-                       (size_t)c->ndof * MC, (const double *)R.d_us, (const double *)R.d_form, R.d_out);
+  hipLaunchKernelGGL((k_response_combine<P, ABSX>), dim3((c->ndof + 255) / 256), dim3(256), 0, c->stream, c->ndof,
+                     (const double *)locked_panel(c, 0, 0), (size_t)c->ndof * MC, (const double *)R.d_us, (const double *)R.d_form, R.d_out);
 }
 
-static void enq_combine(feahip_ctx *c, int panels, bool absx)
+static void enq_combine(feahip_ctx *c, bool absx)
 {
-  switch (panels) {
-  case 1: return enq_combine_p<1>(c, absx);
-  case 2: return enq_combine_p<2>(c, absx);
-  case 3: return enq_combine_p<3>(c, absx);
-  case 4: return enq_combine_p<4>(c, absx);
-  case 5: return enq_combine_p<5>(c, absx);
-  case 6: return enq_combine_p<6>(c, absx);
-  case 7: return enq_combine_p<7>(c, absx);
-  default: return enq_combine_p<8>(c, absx);
-  }
+  for_panels(panels_of(c), [&](auto P) { absx ? enq_combine_p<decltype(P)::value, true>(c) : enq_combine_p<decltype(P)::value, false>(c); });
 }
 
 // C[n][n], b[n] (null: zero) and s by ascending mode; the table goes to the device folded and by store column
@@ -118,7 +90,7 @@ int response_combine(feahip_ctx *c, const double *C, const double *b, double s, 
 {
   ModalState &S = c->modal;
   ResponseState &R = c->response;
-  const int n = S.n_locked, panels = (n + MC - 1) / MC;
+  const int n = S.n_locked;
   if (!R.d_form) FEA_HIP_CHECK(c, hipMalloc((void **)&R.d_form, sizeof(double) * FEA_COMBINE_TABLE));
   std::vector<double> T(FEA_COMBINE_TABLE, 0.0);
   for (int j = 0; j < n; ++j) {
@@ -134,7 +106,7 @@ int response_combine(feahip_ctx *c, const double *C, const double *b, double s, 
   // (pageable memory: the copy has left T when the call returns)
   FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_form, T.data(), sizeof(double) * FEA_COMBINE_TABLE, hipMemcpyHostToDevice, c->stream));
   R.form_set = false;
-  enq_combine(c, panels, absx);
+  enq_combine(c, absx);
   FEA_HIP_CHECK(c, hipGetLastError());
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_out, R.d_out, sizeof(double) * (size_t)c->ndof, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
@@ -147,7 +119,7 @@ int response_combine(feahip_ctx *c, const double *C, const double *b, double s, 
 // hook 26 of feahip_time_kernel: the kernel over the last form, the store and the u_s in force
 int time_combine_kernel(feahip_ctx *c)
 {
-  enq_combine(c, (c->modal.n_locked + MC - 1) / MC, c->response.form_abs);
+  enq_combine(c, c->response.form_abs);
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }

@@ -11,8 +11,8 @@
 //                           every panel over its share of the dofs; the lanes of a wave that hold the same column meet in
 //                           a butterfly, the four waves in LDS in wave order, the workgroups in k_response_reduce.  No
 //                           atomics, the same bits on every call
-//   k_response_sweep<P, D, FIELD>   a lane owns D dofs and loads their 8 P mode values once, as 16-byte loads (a wave reads
-//                           4 KiB contiguous per panel and dof slice of the [3N][8] layout); it then walks the coefficient
+//   k_response_sweep<P, D, FIELD>   a lane owns D dofs and loads their 8 P mode values once (the layout and the instance
+//                           for the panels in use: superpose.h); it then walks the coefficient
 //                           table [n_freq][2][64]: the 16 P coefficients of a frequency are wave-uniform (the compiler takes
 //                           them through the scalar data cache), 16 P D v_fma_f64 follow.  It keeps the largest re^2 + im^2
 //                           and its index -- a strict comparison, so ties keep the lowest frequency -- and writes one sqrt
@@ -20,20 +20,16 @@
 // The host builds the table (response_coefficients): it is small, and where it would not be finite -- w = 0 on a zero
 // mode, w^2 = lam_k without damping -- the sweep is refused before anything is launched.
 // A context that never calls a response entry allocates and launches nothing of this file.
-#include "feahip_internal.h"
+#include "superpose.h"
 #include "reduce_device.h"
-#include <cmath>
 
 #define RB FEA_RED_BLOCKS
-#define MC FEA_MODAL_COLS
 #define RESPONSE_PANELS (FEA_MODAL_MAX_LOCKED / MC)
-static_assert(MC == 8 && RESPONSE_PANELS == 8, "the kernels below are written for eight panels of eight columns");
 // dofs per lane of k_response_sweep: 1 keeps three waves on a SIMD at eight panels, 2 halves the coefficient traffic of
 // a dof and leaves one (DESIGN.md section 21 has both measured; `make variant VSRC=kernels_response VFLAGS=-DRESPONSE_DOFS=2`)
 #ifndef RESPONSE_DOFS
 #define RESPONSE_DOFS 1
 #endif
-typedef double resp_v2d __attribute__((ext_vector_type(2)));
 
 // v[e] = 0 where the dof e >> shift is prescribed: a vector [3N] (shift 0) or a block vector [3N][8] (shift 3)
 __global__ __launch_bounds__(256)
@@ -105,12 +101,14 @@ void k_response_sweep(int ndof, int n_freq, const double *__restrict__ Q, size_t
     u0[i] = in ? us[d] : 0.0;
     best[i] = -1.0;
     at[i] = 0;
+    // load_mode_values (superpose.h) written out, every load under its own predicate: with the helper's one branch the
+    // frequency loop is scheduled differently and measures 0.3 % slower at eight panels
 #pragma unroll
     for (int p = 0; p < P; ++p) {
-      const resp_v2d *Qd = reinterpret_cast<const resp_v2d *>(Q + (size_t)p * pstride) + (size_t)(in ? d : 0) * 4;
+      const mode_v2d *Qd = reinterpret_cast<const mode_v2d *>(Q + (size_t)p * pstride) + (size_t)(in ? d : 0) * 4;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const resp_v2d t = in ? Qd[k] : resp_v2d{0.0, 0.0};
+        const mode_v2d t = in ? Qd[k] : mode_v2d{0.0, 0.0};
         phi[i][p * MC + 2 * k] = t.x; phi[i][p * MC + 2 * k + 1] = t.y;
       }
     }
@@ -239,7 +237,7 @@ int response_load(feahip_ctx *c, const double *h_F, int correction, int solver_t
   R.loaded = false;
   int rc;
   if ((rc = ensure_response(c))) return rc;
-  const int n = S.n_locked, panels = (n + MC - 1) / MC;
+  const int n = S.n_locked, panels = panels_of(c);
   const size_t nd = (size_t)c->ndof;
   // f <- F, zero on the prescribed dofs (the base load is made there: kernels_transient.hip); q = Q' f
   if (h_F) {
@@ -290,18 +288,9 @@ static void enq_sweep_p(feahip_ctx *c, int n_freq)
 }
 
 template <bool FIELD>
-static void enq_sweep(feahip_ctx *c, int panels, int n_freq)
+static void enq_sweep(feahip_ctx *c, int n_freq)
 {
-  switch (panels) {
-  case 1: return enq_sweep_p<1, FIELD>(c, n_freq);
-  case 2: return enq_sweep_p<2, FIELD>(c, n_freq);
-  case 3: return enq_sweep_p<3, FIELD>(c, n_freq);
-  case 4: return enq_sweep_p<4, FIELD>(c, n_freq);
-  case 5: return enq_sweep_p<5, FIELD>(c, n_freq);
-  case 6: return enq_sweep_p<6, FIELD>(c, n_freq);
-  case 7: return enq_sweep_p<7, FIELD>(c, n_freq);
-  default: return enq_sweep_p<8, FIELD>(c, n_freq);
-  }
+  for_panels(panels_of(c), [&](auto P) { enq_sweep_p<decltype(P)::value, FIELD>(c, n_freq); });
 }
 
 int response_sweep(feahip_ctx *c, bool field, int n_freq, const double *omega, double alpha, double beta, const double *zeta,
@@ -309,7 +298,7 @@ int response_sweep(feahip_ctx *c, bool field, int n_freq, const double *omega, d
 {
   ModalState &S = c->modal;
   ResponseState &R = c->response;
-  const int n = S.n_locked, panels = (n + MC - 1) / MC;
+  const int n = S.n_locked;
   const size_t nd = (size_t)c->ndof;
   std::vector<double> coef((size_t)n_freq * 2 * FEA_MODAL_MAX_LOCKED);
   std::string why;
@@ -318,44 +307,30 @@ int response_sweep(feahip_ctx *c, bool field, int n_freq, const double *omega, d
     return FEAHIP_EINVAL;
   }
   FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice, c->stream));
-  if (field) enq_sweep<true>(c, panels, n_freq); else enq_sweep<false>(c, panels, n_freq);
+  if (field) enq_sweep<true>(c, n_freq); else enq_sweep<false>(c, n_freq);
   FEA_HIP_CHECK(c, hipGetLastError());
   R.swept_freq = n_freq;
   R.trans_rows = 0;                                                    // (a transient's last chunk is gone from d_coef)
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_out0, R.d_out, sizeof(double) * nd, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_out1, R.d_out + nd, (field ? sizeof(double) : sizeof(int)) * nd, hipMemcpyDeviceToHost, c->stream));
-  // the probes: their rows of Q and of u_s read back, the kernel's sum in the kernel's order on the host
-  std::vector<double> rows((size_t)n_probe * (panels * MC + 1));
-  for (int r = 0; r < n_probe; ++r) {
-    double *row = rows.data() + (size_t)r * (panels * MC + 1);
-    for (int p = 0; p < panels; ++p)
-      FEA_HIP_CHECK(c, hipMemcpyAsync(row + p * MC, locked_panel(c, 0, p) + (size_t)probe[r] * MC, sizeof(double) * MC,
-                                      hipMemcpyDeviceToHost, c->stream));
-    FEA_HIP_CHECK(c, hipMemcpyAsync(row + panels * MC, R.d_us + probe[r], sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  }
+  // the probes: re from u_s, im from 0, as the kernel sums them
+  ProbeRows rows;
+  if (const int rc = rows.read(c, n_probe, probe)) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  for (int r = 0; r < n_probe; ++r) {
-    const double *row = rows.data() + (size_t)r * (panels * MC + 1);
+  for (int r = 0; r < n_probe; ++r)
     for (int j = 0; j < n_freq; ++j) {
       const double *cr = coef.data() + (size_t)j * 2 * FEA_MODAL_MAX_LOCKED;
-      double re = row[panels * MC], im = 0.0;
-      for (int col = 0; col < panels * MC; ++col) {
-        re = std::fma(row[col], cr[col], re);
-        im = std::fma(row[col], cr[FEA_MODAL_MAX_LOCKED + col], im);
-      }
-      probe_re[(size_t)r * n_freq + j] = re;
-      probe_im[(size_t)r * n_freq + j] = im;
+      probe_re[(size_t)r * n_freq + j] = rows.sum(r, cr, rows.us(r));
+      probe_im[(size_t)r * n_freq + j] = rows.sum(r, cr + FEA_MODAL_MAX_LOCKED, 0.0);
     }
-  }
   return FEAHIP_OK;
 }
 
 // hooks of feahip_time_kernel: 23 the sweep over the table of the last feahip_response_sweep, 24 the projection of f
 int time_response_kernel(feahip_ctx *c, int what)
 {
-  const int panels = (c->modal.n_locked + MC - 1) / MC;
-  if (what == 23) enq_sweep<false>(c, panels, c->response.swept_freq);
-  else enq_project(c, panels);
+  if (what == 23) enq_sweep<false>(c, c->response.swept_freq);
+  else enq_project(c, panels_of(c));
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }

@@ -4,7 +4,7 @@
 // The load held by feahip_response_load or feahip_response_base_load is F g(t), g piecewise linear on a uniform grid.
 // The host integrates every mode exactly (transient_table.cpp) and hands one real coefficient row per step to
 //   k_transient_sweep<P, D, S, FIELD>   the structure of k_response_sweep, real: a lane owns D dofs and loads their 8 P
-//                           mode values once, as 16-byte loads; it then walks the rows of a chunk: the 8 P coefficients
+//                           mode values once (superpose.h); it then walks the rows of a chunk: the 8 P coefficients
 //                           and g_n of a step are wave-uniform (scalar loads), u = fma(us, g_n, 0) and 8 P v_fma_f64 in
 //                           column order follow per dof, S rows at a time (S independent chains).  It keeps the largest
 //                           |u| and its GLOBAL step -- a strict comparison, so ties keep the lowest step -- and every
@@ -14,13 +14,9 @@
 // The history goes through the coefficient buffer of the response state, FEA_TRANSIENT_CHUNK rows of 64 at a time with
 // their g_n behind them: no device allocation grows with the step count.  No atomics, the same bits on every call.
 // A context that never calls a transient entry allocates and launches nothing of this file.
-#include "feahip_internal.h"
+#include "superpose.h"
 #include <algorithm>
-#include <cmath>
-#include <vector>
 
-#define MC FEA_MODAL_COLS
-static_assert(MC == 8 && FEA_MODAL_MAX_LOCKED == 64, "the kernels below are written for eight panels of eight columns");
 // the chunk's rows and their g_n share the table of a frequency sweep: [CHUNK][64] coefficients, then [CHUNK] g
 static_assert((size_t)FEA_TRANSIENT_CHUNK * (FEA_MODAL_MAX_LOCKED + 1) <= (size_t)FEA_RESPONSE_MAX_FREQ * 2 * FEA_MODAL_MAX_LOCKED,
               "a chunk and its g fit the coefficient buffer of the response state");
@@ -33,7 +29,6 @@ static_assert((size_t)FEA_TRANSIENT_CHUNK * (FEA_MODAL_MAX_LOCKED + 1) <= (size_
 #else
 #define TRANSIENT_STEPS_OF(P) ((P) >= 2 ? 2 : 1)
 #endif
-typedef double trans_v2d __attribute__((ext_vector_type(2)));
 
 // u_d(t_j) = us[d] g[j] + sum_c Q[d][c] coef[j][c] over the columns c < 8 P, summed in column order.
 // !FIELD: o0[d] = max_j |u_d(t_j)| and o1[d] = step0 + the lowest j that attains it, over the rows of this launch and,
@@ -57,15 +52,7 @@ void k_transient_sweep(int ndof, int n_rows, int step0, int first, const double 
     at[i] = 0;
     if constexpr (!FIELD)
       if (!first && in) { best[i] = o0[d]; at[i] = o1[d]; }
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const trans_v2d *Qd = reinterpret_cast<const trans_v2d *>(Q + (size_t)p * pstride) + (size_t)(in ? d : 0) * 4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const trans_v2d t = in ? Qd[k] : trans_v2d{0.0, 0.0};
-        phi[i][p * MC + 2 * k] = t.x; phi[i][p * MC + 2 * k + 1] = t.y;
-      }
-    }
+    load_mode_values<P>(Q, pstride, d, in, phi[i]);
   }
   int j = 0;
   // S rows per iteration: S independent FMA chains per dof and S rows' loads in flight.  The comparisons keep the order
@@ -161,18 +148,9 @@ static void enq_transient_p(feahip_ctx *c, int n_rows, int step0, int first, con
 }
 
 template <bool FIELD>
-static void enq_transient(feahip_ctx *c, int panels, int n_rows, int step0, int first, const double *d_coef, double g0, double *d_o0)
+static void enq_transient(feahip_ctx *c, int n_rows, int step0, int first, const double *d_coef, double g0, double *d_o0)
 {
-  switch (panels) {
-  case 1: return enq_transient_p<1, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  case 2: return enq_transient_p<2, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  case 3: return enq_transient_p<3, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  case 4: return enq_transient_p<4, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  case 5: return enq_transient_p<5, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  case 6: return enq_transient_p<6, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  case 7: return enq_transient_p<7, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  default: return enq_transient_p<8, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0);
-  }
+  for_panels(panels_of(c), [&](auto P) { enq_transient_p<decltype(P)::value, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0); });
 }
 
 namespace {
@@ -195,7 +173,7 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
 {
   ModalState &S = c->modal;
   ResponseState &R = c->response;
-  const int n = S.n_locked, panels = (n + MC - 1) / MC, width = panels * MC;
+  const int n = S.n_locked;
   const size_t nd = (size_t)c->ndof;
   const int n_rows = n_steps + 1, CH = FEA_TRANSIENT_CHUNK;
   std::string why;
@@ -212,15 +190,9 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
     B.buf[b].resize(chunk_doubles);
     FEA_HIP_CHECK(c, hipEventCreateWithFlags(&B.copied[b], hipEventDisableTiming));
   }
-  // the probes' rows of Q and of u_s, read back once
-  std::vector<double> rows((size_t)n_probe * (width + 1));
-  for (int r = 0; r < n_probe; ++r) {
-    double *row = rows.data() + (size_t)r * (width + 1);
-    for (int p = 0; p < panels; ++p)
-      FEA_HIP_CHECK(c, hipMemcpyAsync(row + p * MC, locked_panel(c, 0, p) + (size_t)probe[r] * MC, sizeof(double) * MC,
-                                      hipMemcpyDeviceToHost, c->stream));
-    FEA_HIP_CHECK(c, hipMemcpyAsync(row + width, R.d_us + probe[r], sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  }
+  ProbeRows rows;                                                      // read back once
+  int rc;
+  if ((rc = rows.read(c, n_probe, probe))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
   // the static term u_s g_n belongs to the displacement alone
   auto g_of = [&](int step) { return quantity == 0 ? g[step] : 0.0; };
@@ -230,15 +202,9 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
     double *coef = B.buf[b].data(), *gs = coef + (size_t)count * FEA_MODAL_MAX_LOCKED;
     if (transient_rows(B.table, g, count, coef, &why)) { c->err = "response_transient: " + why; return FEAHIP_EINVAL; }
     for (int j = 0; j < count; ++j) gs[j] = g_of(step0 + j);
-    for (int r = 0; r < n_probe; ++r) {
-      const double *row = rows.data() + (size_t)r * (width + 1);
-      for (int j = 0; j < count; ++j) {
-        const double *cr = coef + (size_t)j * FEA_MODAL_MAX_LOCKED;
-        double u = std::fma(row[width], gs[j], 0.0);
-        for (int col = 0; col < width; ++col) u = std::fma(row[col], cr[col], u);
-        h_probe[(size_t)r * n_rows + step0 + j] = u;
-      }
-    }
+    for (int r = 0; r < n_probe; ++r)
+      for (int j = 0; j < count; ++j)
+        h_probe[(size_t)r * n_rows + step0 + j] = rows.sum(r, coef + (size_t)j * FEA_MODAL_MAX_LOCKED, std::fma(rows.us(r), gs[j], 0.0));
     for (int s = 0; s < n_snap; ++s)
       if (snap_step[s] >= step0 && snap_step[s] < step0 + count) {
         double *keep = snap_rows.data() + (size_t)s * (FEA_MODAL_MAX_LOCKED + 1);
@@ -247,7 +213,6 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
       }
     return FEAHIP_OK;
   };
-  int rc;
   if ((rc = fill(0, 0, std::min(CH, n_rows)))) return rc;
   int last0 = 0, last_count = 0;
   for (int step0 = 0, k = 0; step0 < n_rows; step0 += CH, ++k) {
@@ -257,7 +222,7 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
     FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_coef + (size_t)CH * FEA_MODAL_MAX_LOCKED, src + (size_t)count * FEA_MODAL_MAX_LOCKED,
                                     sizeof(double) * (size_t)count, hipMemcpyHostToDevice, c->stream));
     FEA_HIP_CHECK(c, hipEventRecord(B.copied[b], c->stream));
-    enq_transient<false>(c, panels, count, step0, step0 == 0, R.d_coef, 0.0, R.d_out);
+    enq_transient<false>(c, count, step0, step0 == 0, R.d_coef, 0.0, R.d_out);
     FEA_HIP_CHECK(c, hipGetLastError());
     last0 = step0; last_count = count;
     // the next chunk on the host while this one runs; its buffer's last copy (of the chunk before) has to be over
@@ -273,7 +238,7 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
   for (int s = 0; s < n_snap; ++s) {
     const double *keep = snap_rows.data() + (size_t)s * (FEA_MODAL_MAX_LOCKED + 1);
     FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_q, keep, sizeof(double) * FEA_MODAL_MAX_LOCKED, hipMemcpyHostToDevice, c->stream));
-    enq_transient<true>(c, panels, 1, snap_step[s], 1, R.d_q, keep[FEA_MODAL_MAX_LOCKED], R.d_out);
+    enq_transient<true>(c, 1, snap_step[s], 1, R.d_q, keep[FEA_MODAL_MAX_LOCKED], R.d_out);
     FEA_HIP_CHECK(c, hipGetLastError());
     FEA_HIP_CHECK(c, hipMemcpyAsync(h_snap + (size_t)s * nd, R.d_out, sizeof(double) * nd, hipMemcpyDeviceToHost, c->stream));
   }
@@ -286,8 +251,7 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
 // hook 25 of feahip_time_kernel: the sweep over the last chunk of the last feahip_response_transient, as a first launch
 int time_transient_kernel(feahip_ctx *c)
 {
-  const int panels = (c->modal.n_locked + MC - 1) / MC;
-  enq_transient<false>(c, panels, c->response.trans_rows, c->response.trans_step0, 1, c->response.d_coef, 0.0, c->response.d_out);
+  enq_transient<false>(c, c->response.trans_rows, c->response.trans_step0, 1, c->response.d_coef, 0.0, c->response.d_out);
   FEA_HIP_CHECK(c, hipGetLastError());
   return FEAHIP_OK;
 }
