@@ -575,6 +575,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->results.release();
   c->modal.release();
   c->response.release();
+  c->stress.release();
   c->buckling.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
@@ -1840,6 +1841,175 @@ extern "C" int feahip_response_spectrum(feahip_ctx *c, int n_pts, const double *
   return FEAHIP_OK;
 }
 
+// ---- stress from mode superposition (kernels_modal_stress.hip, kernels_stress_combine.hip) -----------------------------
+extern "C" int feahip_stress_increment(feahip_ctx *c, const double *du, int material, double *sig6)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = solve2_refused(c, "stress_increment")) || (rc = results_material(c, material, "stress_increment"))) return rc;
+  if (!du || !sig6) { c->err = "stress_increment: null du or sig6"; return FEAHIP_EINVAL; }
+  for (int i = 0; i < c->ndof; ++i)
+    if (!std::isfinite(du[i])) { c->err = "stress_increment: du is not finite"; return FEAHIP_EINVAL; }
+  if ((rc = stress_ensure(c)) || (rc = set_view(c, c->stress.d_vec, du, 3, 3)) ||
+      (rc = launch_stress_vector(c, c->stress.d_vec, material, c->stress.d_out6))) return rc;
+  return get_view(c, c->stress.d_out6, sig6, 6, 6);
+}
+
+extern "C" int feahip_response_stress_basis(feahip_ctx *c, int material)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = solve2_refused(c, "response_stress_basis")) || (rc = modes_held(c, "response_stress_basis")) ||
+      (rc = results_material(c, material, "response_stress_basis"))) return rc;
+  return stress_basis(c, material);
+}
+
+// the stress store belongs to the modes held, and T_s to the last load made
+static int stress_ready(feahip_ctx *c, const char *who)
+{
+  int rc;
+  if ((rc = solve2_refused(c, who)) || (rc = modes_held(c, who))) return rc;
+  const StressState &S = c->stress;
+  if (!S.have || S.gen != c->modal.lock_gen) {
+    c->err = std::string(who) + ": no stress store for these modes (feahip_response_stress_basis first)";
+    return FEAHIP_ESTATE;
+  }
+  if (S.load_count != c->response.load_count) {
+    c->err = std::string(who) + ": a load was made after the stress store (feahip_response_stress_basis again)";
+    return FEAHIP_ESTATE;
+  }
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_modal_stresses(feahip_ctx *c, int first, int count, double *sig6)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_ready(c, "get_modal_stresses"))) return rc;
+  if (first < 0 || count < 0 || first + count > c->modal.n_locked) {
+    c->err = "get_modal_stresses: modes [first, first + count) outside the " + std::to_string(c->modal.n_locked) + " held";
+    return FEAHIP_EINVAL;
+  }
+  if (!sig6) { c->err = "get_modal_stresses: null sig6"; return FEAHIP_EINVAL; }
+  for (int j = 0; j < count; ++j)
+    if ((rc = launch_stress_mode(c, c->modal.lock_order[first + j], c->stress.d_out6)) ||
+        (rc = get_view(c, c->stress.d_out6, sig6 + (size_t)j * 6 * c->N, 6, 6))) return rc;
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_get_response_static_stress(feahip_ctx *c, double *sig6)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_ready(c, "get_response_static_stress"))) return rc;
+  if (!sig6) { c->err = "get_response_static_stress: null sig6"; return FEAHIP_EINVAL; }
+  return get_view(c, c->stress.d_ts, sig6, 6, 6);
+}
+
+extern "C" int feahip_response_stress_field(feahip_ctx *c, const double *coef, double cs, double *sig6, double *vm)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_ready(c, "response_stress_field"))) return rc;
+  if (!coef || !sig6 || !vm) { c->err = "response_stress_field: null coef, sig6 or vm"; return FEAHIP_EINVAL; }
+  for (int k = 0; k < c->modal.n_locked; ++k)
+    if (!std::isfinite(coef[k])) { c->err = "response_stress_field: coef is not finite"; return FEAHIP_EINVAL; }
+  if (!std::isfinite(cs)) { c->err = "response_stress_field: cs is not finite"; return FEAHIP_EINVAL; }
+  std::vector<double> t6(6 * (size_t)c->N), tv((size_t)c->N);
+  if ((rc = stress_field(c, coef, cs, t6.data(), tv.data()))) return rc;
+  to_caller(view_of(c), 6, 6, t6.data(), sig6);
+  to_caller(view_of(c), 1, 1, tv.data(), vm);
+  return FEAHIP_OK;
+}
+
+// the form entries need the load the store was made with as well
+static int stress_form_ready(feahip_ctx *c, const char *who)
+{
+  int rc;
+  if ((rc = solve2_refused(c, who)) || (rc = response_loaded(c, who))) return rc;
+  return stress_ready(c, who);
+}
+
+static int stress_to_caller(feahip_ctx *c, const double *C, const double *b, double s, bool absx, double *out6, double *vm)
+{
+  std::vector<double> t6(6 * (size_t)c->N), tv((size_t)c->N);
+  const int rc = stress_combine(c, C, b, s, absx, t6.data(), tv.data());
+  if (rc) return rc;
+  to_caller(view_of(c), 6, 6, t6.data(), out6);
+  if (vm) to_caller(view_of(c), 1, 1, tv.data(), vm);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_stress_combine(feahip_ctx *c, const double *C, const double *b, double s, double *out6, double *vm)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_combine"))) return rc;
+  if (!C || !out6) { c->err = "response_stress_combine: null C or out6"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  for (int j = 0; j < n; ++j) {
+    for (int k = 0; k < n; ++k) {
+      const double v = C[(size_t)j * n + k];
+      if (!std::isfinite(v)) { c->err = "response_stress_combine: C is not finite"; return FEAHIP_EINVAL; }
+      if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) { c->err = "response_stress_combine: C is not symmetric to the bit"; return FEAHIP_EINVAL; }
+      if (j != k && !std::isfinite(2.0 * v)) { c->err = "response_stress_combine: twice an entry of C is not finite"; return FEAHIP_EINVAL; }
+    }
+    if (b && !std::isfinite(b[j])) { c->err = "response_stress_combine: b is not finite"; return FEAHIP_EINVAL; }
+  }
+  if (!std::isfinite(s)) { c->err = "response_stress_combine: s is not finite"; return FEAHIP_EINVAL; }
+  return stress_to_caller(c, C, b, s, false, out6, vm);
+}
+
+extern "C" int feahip_response_stress_random(feahip_ctx *c, int n_freq, const double *omega, const double *S, double alpha,
+                                             double beta_k, const double *zeta, double *rms6, double *rms_vm, double *modal_cov)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_random"))) return rc;
+  if (!omega || !S || !rms6) { c->err = "response_stress_random: null omega, S or rms6"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  std::vector<double> C((size_t)n * n), b(n);
+  double s = 0.0;
+  std::string why;
+  if (random_form(n, c->modal.lam, c->response.q, n_freq, omega, S, alpha, beta_k, zeta, c->response.correction, 0,
+                  C.data(), b.data(), &s, &why)) {
+    c->err = "response_stress_random: " + why;
+    return FEAHIP_EINVAL;
+  }
+  if ((rc = stress_to_caller(c, C.data(), b.data(), s, false, rms6, rms_vm))) return rc;
+  if (modal_cov) std::copy(C.begin(), C.end(), modal_cov);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_stress_spectrum(feahip_ctx *c, int n_pts, const double *w, const double *sa, int loglog, int rule,
+                                               double alpha, double beta_k, const double *zeta, double zpa, double *peak6,
+                                               double *peak_vm, double *modal_peak)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_spectrum"))) return rc;
+  if (!w || !sa || !peak6) { c->err = "response_stress_spectrum: null w, sa or peak6"; return FEAHIP_EINVAL; }
+  if (rule == FEAHIP_ABS && peak_vm) { c->err = "response_stress_spectrum: no von Mises peak under FEAHIP_ABS (the differences need the signs): peak_vm must be NULL"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  double sak[FEA_MODAL_MAX_LOCKED], a[FEA_MODAL_MAX_LOCKED];
+  for (int k = 0; k < n; ++k) {
+    if (!(c->modal.lam[k] > 0.0)) { c->err = "response_stress_spectrum: lam of mode " + std::to_string(k + 1) + " is not positive"; return FEAHIP_EINVAL; }
+    sak[k] = feahip_host_spectrum_value(n_pts, w, sa, loglog, std::sqrt(c->modal.lam[k]));
+    if (std::isnan(sak[k])) { c->err = "response_stress_spectrum: the spectrum's points must be finite, their w strictly ascending"; return FEAHIP_EINVAL; }
+  }
+  std::vector<double> C((size_t)n * n), b(n);
+  double s = 0.0;
+  std::string why;
+  if (spectrum_form(n, c->modal.lam, c->response.q, sak, alpha, beta_k, zeta, rule, c->response.correction, zpa, 0,
+                    C.data(), b.data(), &s, a, &why)) {
+    c->err = "response_stress_spectrum: " + why;
+    return FEAHIP_EINVAL;
+  }
+  if ((rc = stress_to_caller(c, C.data(), b.data(), s, rule == FEAHIP_ABS, peak6, peak_vm))) return rc;
+  if (modal_peak) for (int k = 0; k < n; ++k) modal_peak[k] = a[k];
+  return FEAHIP_OK;
+}
+
 extern "C" int feahip_host_modal_ritz(int n_dirs,const double *gram_m, const double *gram_k, double *theta, double *coef)
 {
   if (!gram_m || !gram_k || !theta || !coef || (n_dirs != 8 && n_dirs != 16 && n_dirs != 24)) return FEAHIP_EINVAL;
@@ -2274,6 +2444,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (rk) return rk;
     if (!c->response.form_set || c->response.form_gen != c->modal.lock_gen) { c->err = "time_kernel: no form set yet (feahip_response_combine, _random or _spectrum first)"; return FEAHIP_ESTATE; }
   }
+  if (what == 27 || what == 28) {                      // the stress store in force; 28: the form of the last stress combination
+    const int rk = what == 27 ? stress_ready(c, "time_kernel(27)") : stress_form_ready(c, "time_kernel(28)");
+    if (rk) return rk;
+    if (what == 28 && !c->stress.form_set) { c->err = "time_kernel: no stress form set yet (feahip_response_stress_combine, _random or _spectrum first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2299,6 +2474,8 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 23: case 24: return time_response_kernel(c, what);
     case 25: return time_transient_kernel(c);
     case 26: return time_combine_kernel(c);
+    case 27: return time_stress_store(c);
+    case 28: return time_stress_combine(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

@@ -551,7 +551,32 @@ struct ResponseState {
   bool form_set = false;               // d_form holds a form (feahip_time_kernel 26) ...
   bool form_abs = false;               // ... to be taken on |phi| ...
   int form_gen = -1;                   // ... laid out for the filling form_gen of the store
+  int load_count = 0;                  // counts the loads made: T_s of the stress store belongs to one of them
   void release() { dev_free({d_us, d_part, d_q, d_coef, d_out, d_form}); *this = ResponseState(); }
+};
+
+// stress from mode superposition (kernels_modal_stress.hip, kernels_stress_combine.hip): nothing of it exists until a stress
+// entry is called.  The store belongs to the filling `gen` of the locked store and T_s to the load number `load_count`.
+struct StressState {
+  double *d_rec = nullptr;             // [E][6][8] element records of one panel: sum_g vol dsigma, component by column
+  double *d_evol = nullptr;            // [E] sum_g vol
+  double *d_vec = nullptr;             // [3N] a single vector in library ids (feahip_stress_increment)
+  double *d_in = nullptr;              // [3N][8] the panel of a single vector: column 0 live
+  double *d_one = nullptr;             // [6N][8] its stress panel (and where feahip_time_kernel 27 writes)
+  double *d_out6 = nullptr;            // [6N] an output of six components per node (library ids)
+  double *d_vm = nullptr;              // [N] a von Mises output
+  double *d_ts = nullptr;              // [6N] T_s, the stress of the static correction; zero without one
+  double *d_store = nullptr;           // [store_panels][6N][8] the stress store, column for column the locked store's
+  double *d_form = nullptr;            // [FEA_COMBINE_TABLE] the form of the last stress combination (feahip_time_kernel 28)
+  double *d_fcoef = nullptr;           // [64 + 8] the coefficients of the last feahip_response_stress_field, then cs
+  int store_panels = 0;                // panels allocated
+  bool have = false;                   // the store holds the stresses of the modes held ...
+  int gen = -1;                        // ... of the filling ModalState::lock_gen == gen ...
+  int load_count = -1;                 // ... and T_s that of the load ResponseState::load_count == load_count ...
+  int material = -1;                   // ... over the elements of this material (-1: all)
+  bool form_set = false;               // d_form holds a form for this store ...
+  bool form_abs = false;               // ... to be taken on |T|
+  void release() { dev_free({d_rec, d_evol, d_vec, d_in, d_one, d_out6, d_vm, d_ts, d_store, d_form, d_fcoef}); *this = StressState(); }
 };
 
 // linear buckling (kernels_buckling.hip): nothing of it exists until feahip_solve_buckling (or one of its hooks,
@@ -708,6 +733,7 @@ struct feahip_ctx {
   ResultState results;
   ModalState modal;
   ResponseState response;
+  StressState stress;
   BucklingState buckling;
 };
 
@@ -874,6 +900,16 @@ int time_transient_kernel(feahip_ctx *c);                               // feahi
 // C[n_locked][n_locked], b[n_locked] (null: zero) and s by ascending mode; h_out[3N] in library ids
 int response_combine(feahip_ctx *c, const double *C, const double *b, double s, bool absx, double *h_out);
 int time_combine_kernel(feahip_ctx *c);                                 // feahip_time_kernel 26
+// kernels_modal_stress.hip -- the linearised nodal stress of a panel of eight columns: the stress store and single vectors
+int stress_ensure(feahip_ctx *c);                                       // the buffers, on the first call
+int launch_stress_vector(feahip_ctx *c, const double *d_v, int material, double *d_out);   // d_out[6N] from d_v[3N], library ids
+int stress_basis(feahip_ctx *c, int material);                          // the store of the modes held, T_s of the load held
+int launch_stress_mode(feahip_ctx *c, int col, double *d_out);          // d_out[6N] = column col of the stress store
+int time_stress_store(feahip_ctx *c);                                   // feahip_time_kernel 27
+// kernels_stress_combine.hip -- quadratic forms and one linear combination of the modal stresses per node
+int stress_combine(feahip_ctx *c, const double *C, const double *b, double s, bool absx, double *h_out6, double *h_vm);
+int stress_field(feahip_ctx *c, const double *coef, double cs, double *h_out6, double *h_vm);
+int time_stress_combine(feahip_ctx *c);                                 // feahip_time_kernel 28
 // combine_table.cpp -- the forms of a PSD and of a response spectrum, host only, in long double.  Mode k of the arrays is
 // row and column k of C[n_modes][n_modes] and entry k of b; FEAHIP_EINVAL and *why for what the entries refuse
 int random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,

@@ -90,19 +90,8 @@ int response_combine(feahip_ctx *c, const double *C, const double *b, double s, 
 {
   ModalState &S = c->modal;
   ResponseState &R = c->response;
-  const int n = S.n_locked;
   if (!R.d_form) FEA_HIP_CHECK(c, hipMalloc((void **)&R.d_form, sizeof(double) * FEA_COMBINE_TABLE));
-  std::vector<double> T(FEA_COMBINE_TABLE, 0.0);
-  for (int j = 0; j < n; ++j) {
-    const int cj = S.lock_order[j];
-    for (int k = j; k < n; ++k) {
-      const int ck = S.lock_order[k];
-      const int lo = cj < ck ? cj : ck, hi = cj < ck ? ck : cj;
-      T[(size_t)lo * ML + hi] = j == k ? C[(size_t)j * n + j] : 2.0 * C[(size_t)j * n + k];
-    }
-    T[(size_t)ML * ML + cj] = b ? b[j] : 0.0;
-  }
-  T[(size_t)ML * ML + ML] = s;
+  const std::vector<double> T = folded_form(S, C, b, s);
   // (pageable memory: the copy has left T when the call returns)
   FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_form, T.data(), sizeof(double) * FEA_COMBINE_TABLE, hipMemcpyHostToDevice, c->stream));
   R.form_set = false;

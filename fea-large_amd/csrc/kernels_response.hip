@@ -274,6 +274,7 @@ int response_load(feahip_ctx *c, const double *h_F, int correction, int solver_t
   R.correction = correction ? 1 : 0;
   R.gen = S.lock_gen;
   R.loaded = true;
+  ++R.load_count;
   return FEAHIP_OK;
 }
 

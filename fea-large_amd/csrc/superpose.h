@@ -2,7 +2,8 @@
 // k_response_combine) and the host code around them.  The store is 8 panels of [3N][8] doubles, `pstride` doubles apart,
 // the eight columns of a dof contiguous; n modes fill the first P = (n + 7) / 8 panels.  A lane owns a dof and keeps its
 // 8 P mode values in registers (load_mode_values; k_response_sweep has the same loads written out, and says why); the host
-// picks the instance from the panel count (panels_of, for_panels) and sums the probes in the kernels' order (ProbeRows).
+// picks the instance from the panel count (panels_of, for_panels), folds a form into the table of the combine kernels
+// (folded_form) and sums the probes in the kernels' order (ProbeRows).
 #pragma once
 #include "feahip_internal.h"
 #include <cmath>
@@ -42,6 +43,26 @@ static inline void for_panels(int panels, F &&f)
   if constexpr (P == ML / MC) f(std::integral_constant<int, P>());
   else if (panels == P) f(std::integral_constant<int, P>());
   else for_panels<P + 1>(panels, f);
+}
+
+// The form (C[n][n], b[n] or null: zero, s) by ascending mode as the table the combine kernels read (k_response_combine,
+// k_stress_combine), FEA_COMBINE_TABLE doubles: T[64][64] by store column with C folded onto its upper triangle -- the
+// diagonal as it is, the entries above it doubled, which is exact, zero below --, then b[64], then s
+static inline std::vector<double> folded_form(const ModalState &S, const double *C, const double *b, double s)
+{
+  const int n = S.n_locked;
+  std::vector<double> T(FEA_COMBINE_TABLE, 0.0);
+  for (int j = 0; j < n; ++j) {
+    const int cj = S.lock_order[j];
+    for (int k = j; k < n; ++k) {
+      const int ck = S.lock_order[k];
+      const int lo = cj < ck ? cj : ck, hi = cj < ck ? ck : cj;
+      T[(size_t)lo * ML + hi] = j == k ? C[(size_t)j * n + j] : 2.0 * C[(size_t)j * n + k];
+    }
+    T[(size_t)ML * ML + cj] = b ? b[j] : 0.0;
+  }
+  T[(size_t)ML * ML + ML] = s;
+  return T;
 }
 
 // The probes' rows of Q and of u_s on the host.  sum() is the kernels' sum in the kernels' order -- one fma per store

@@ -183,6 +183,15 @@ ABI = {
     "feahip_response_random": [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, _dp, _dp],
     "feahip_response_spectrum": [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_double,
                                  C.c_int, _dp, _dp],
+    "feahip_stress_increment": [C.c_void_p, _dp, C.c_int, _dp],
+    "feahip_response_stress_basis": [C.c_void_p, C.c_int],
+    "feahip_get_modal_stresses": [C.c_void_p, C.c_int, C.c_int, _dp],
+    "feahip_get_response_static_stress": [C.c_void_p, _dp],
+    "feahip_response_stress_field": [C.c_void_p, _dp, C.c_double, _dp, _dp],
+    "feahip_response_stress_combine": [C.c_void_p, _dp, _dp, C.c_double, _dp, _dp],
+    "feahip_response_stress_random": [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp],
+    "feahip_response_stress_spectrum": [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_double,
+                                        _dp, _dp, _dp],
     "feahip_host_random_form": [C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp, _dp,
                                 _dp],
     "feahip_host_random_grid": [C.c_int, _dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _ip],
@@ -257,6 +266,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("spectrum_stress", C.c_int), ("random_stress", C.c_int),
         ("has_spectrum", C.c_int), ("spectrum_count", C.c_int), ("spectrum_points", _dp), ("spectrum_rule", C.c_int),
         ("spectrum_static", C.c_int), ("spectrum_loglog", C.c_int), ("spectrum_has_base", C.c_int),
         ("spectrum_zeta", C.c_double), ("spectrum_zpa", C.c_double), ("spectrum_base", C.c_double * 3),
@@ -674,7 +684,10 @@ class Deck:
             base = kw.get(f"{name}_base")
             base = None if base is None else tuple(float(b) for b in base)
             setattr(self, f"{name}_base", base)
+            setattr(self, f"{name}_stress", bool(kw.get(f"{name}_stress", False)))     # :stress t: the von Mises result as well
             if not len(pts):
+                if getattr(self, f"{name}_stress"):
+                    raise ValueError(f"{name}_stress needs {name}_points")
                 continue
             if not floor <= len(pts) <= DECK_MAX_POINTS:
                 raise ValueError(f"{name}_points: {floor} to {DECK_MAX_POINTS} pairs")
@@ -701,6 +714,8 @@ class Deck:
                 raise ValueError("spectrum_zpa: finite and not negative")
             if self.spectrum_zpa and (not self.spectrum_static or self.spectrum_rule == "abs"):
                 raise ValueError("spectrum_zpa needs spectrum_static and a rule other than abs")
+            if self.spectrum_stress and self.spectrum_rule == "abs":
+                raise ValueError("spectrum_stress needs a rule other than abs")
         if len(self.random_points) and not (0 <= self.random_per_mode <= 4096 and 2 <= self.random_background <= 131072):
             raise ValueError("random_per_mode: 0 to 4096, random_background: 2 to 131072")
         # (buckling :modes N :tolerance t :max M): the load factors feasolver_hip computes after its last step
@@ -771,13 +786,15 @@ class Deck:
                 **(dict(spectrum_points=np.ctypeslib.as_array(fd.spectrum_points, (fd.spectrum_count, 2)).copy(),
                         spectrum_rule=SPECTRUM_RULES[fd.spectrum_rule], spectrum_zeta=fd.spectrum_zeta, spectrum_zpa=fd.spectrum_zpa,
                         spectrum_static=bool(fd.spectrum_static), spectrum_interp="loglog" if fd.spectrum_loglog else "linear",
-                        spectrum_base=[fd.spectrum_base[k] for k in range(3)] if fd.spectrum_has_base else None)
+                        spectrum_base=[fd.spectrum_base[k] for k in range(3)] if fd.spectrum_has_base else None,
+                        spectrum_stress=bool(fd.spectrum_stress))
                    if fd.has_spectrum else {}),
                 **(dict(random_points=np.ctypeslib.as_array(fd.random_points, (fd.random_count, 2)).copy(),
                         random_zeta=fd.random_zeta, random_static=bool(fd.random_static),
                         random_interp="loglog" if fd.random_loglog else "linear", random_per_mode=fd.random_per_mode,
                         random_background=fd.random_background,
-                        random_base=[fd.random_base[k] for k in range(3)] if fd.random_has_base else None)
+                        random_base=[fd.random_base[k] for k in range(3)] if fd.random_has_base else None,
+                        random_stress=bool(fd.random_stress))
                    if fd.has_random else {}),
                 **(dict(buckling_modes=fd.buckling_modes, buckling_tolerance=fd.buckling_tolerance,
                         buckling_max=fd.buckling_max) if fd.buckling_modes else {}))
@@ -848,6 +865,7 @@ class Deck:
             fd.has_spectrum, fd.spectrum_count, fd.spectrum_points = 1, len(self.spectrum_points), _d(self.spectrum_points)
             fd.spectrum_rule, fd.spectrum_static = SPECTRUM_RULES.index(self.spectrum_rule), int(bool(self.spectrum_static))
             fd.spectrum_loglog, fd.spectrum_zeta, fd.spectrum_zpa = int(self.spectrum_interp == "loglog"), self.spectrum_zeta, self.spectrum_zpa
+            fd.spectrum_stress = int(bool(getattr(self, "spectrum_stress", False)))
             if self.spectrum_base is not None:
                 fd.spectrum_has_base = 1
                 for k in range(3):
@@ -856,6 +874,7 @@ class Deck:
             fd.has_random, fd.random_count, fd.random_points = 1, len(self.random_points), _d(self.random_points)
             fd.random_static, fd.random_loglog, fd.random_zeta = int(bool(self.random_static)), int(self.random_interp == "loglog"), self.random_zeta
             fd.random_per_mode, fd.random_background = int(self.random_per_mode), int(self.random_background)
+            fd.random_stress = int(bool(getattr(self, "random_stress", False)))
             if self.random_base is not None:
                 fd.random_has_base = 1
                 for k in range(3):
@@ -1442,6 +1461,85 @@ class FeaSolver:
         self._chk(self._lib.feahip_response_spectrum(self._ctx, len(w), _d(w), _d(sa), int(bool(loglog)), int(rule),
                                                      float(alpha), float(beta), zp, float(zpa), int(quantity), _d(peak), _d(a)))
         return peak, a[:n or 0].copy()
+
+    # ---- stress from mode superposition: modal stresses, RMS and peak von Mises -----
+    def stress_increment(self, du, material=-1):
+        """feahip_stress_increment: sig6[N][6] (xx yy zz xy yz xz), the nodal stress the displacement increment du[3N]
+        causes at the current nodes with the weights of nodal_stresses held fixed; material = -1 takes all elements."""
+        du = np.ascontiguousarray(du, dtype=np.float64).reshape(-1)
+        assert du.shape == (self.ndof,)
+        sig6 = np.zeros((self.ndof // 3, 6))
+        self._chk(self._lib.feahip_stress_increment(self._ctx, _d(du), int(material), _d(sig6)))
+        return sig6
+
+    def response_stress_basis(self, material=-1):
+        """feahip_response_stress_basis: builds the stress store of the modes held at the current nodes, and T_s of the
+        load held with the static correction."""
+        self._chk(self._lib.feahip_response_stress_basis(self._ctx, int(material)))
+
+    def modal_stresses(self, first=0, count=None):
+        """feahip_get_modal_stresses: sig6[count][N][6] of the modes held, by ascending lam."""
+        n = self._held()
+        count = (n or 0) - first if count is None else count
+        out = np.zeros((max(count, 0), self.ndof // 3, 6))
+        self._chk(self._lib.feahip_get_modal_stresses(self._ctx, int(first), int(count), _d(out)))
+        return out
+
+    def response_static_stress(self):
+        """feahip_get_response_static_stress: T_s[N][6], the stress of u_s (zero without the correction)."""
+        out = np.zeros((self.ndof // 3, 6))
+        self._chk(self._lib.feahip_get_response_static_stress(self._ctx, _d(out)))
+        return out
+
+    def response_stress_field(self, coef, cs=0.0):
+        """feahip_response_stress_field: (sig6[N][6] = cs T_s + sum_k coef_k T_k, its von Mises stress [N]), coef by
+        ascending mode: the stress of one row of host_response_coefficients or host_transient_coefficients."""
+        n = self._held()
+        co = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        assert n is None or len(co) >= n
+        sig6, vm = np.zeros((self.ndof // 3, 6)), np.zeros(self.ndof // 3)
+        self._chk(self._lib.feahip_response_stress_field(self._ctx, _d(co), float(cs), _d(sig6), _d(vm)))
+        return sig6, vm
+
+    def response_stress_combine(self, C_, b=None, s=0.0):
+        """feahip_response_stress_combine: (out6[N][6], vm[N]) of the form (C, b, s) on the modal stresses: the root of the
+        form on each component, and the von Mises root of its own nine forms."""
+        n = self._held()
+        Cm = np.ascontiguousarray(C_, dtype=np.float64)
+        bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        assert n is None or (Cm.shape == (n, n) and (bb is None or bb.shape == (n,)))
+        out6, vm = np.zeros((self.ndof // 3, 6)), np.zeros(self.ndof // 3)
+        self._chk(self._lib.feahip_response_stress_combine(self._ctx, _d(Cm), None if bb is None else _d(bb), float(s),
+                                                           _d(out6), _d(vm)))
+        return out6, vm
+
+    def response_stress_random(self, omega, S, alpha=0.0, beta=0.0, zeta=None):
+        """feahip_response_stress_random: (rms6[N][6], the RMS von Mises stress [N], the modal covariance) under the load
+        held times a load factor of one-sided PSD S(omega)."""
+        omega, S = np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+        assert omega.ndim == 1 and omega.shape == S.shape
+        n = self._held()
+        rms6, vm, cov = np.zeros((self.ndof // 3, 6)), np.zeros(self.ndof // 3), np.zeros((n or MODAL_MAX_LOCKED,) * 2)
+        z, zp = (None, None) if n is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_stress_random(self._ctx, len(omega), _d(omega), _d(S), float(alpha), float(beta),
+                                                          zp, _d(rms6), _d(vm), _d(cov)))
+        return rms6, vm, cov
+
+    def response_stress_spectrum(self, w, sa, rule=SRSS, alpha=0.0, beta=0.0, zeta=None, zpa=0.0, loglog=False, von_mises=None):
+        """feahip_response_stress_spectrum: (peak6[N][6], the peak von Mises stress [N] or None, the peak modal values)
+        under the response spectrum sa(w).  Under ABS the components take |T| and there is no von Mises peak (von_mises
+        defaults to rule != ABS; asking for it under ABS is refused)."""
+        w, sa = np.ascontiguousarray(w, dtype=np.float64), np.ascontiguousarray(sa, dtype=np.float64)
+        assert w.ndim == 1 and w.shape == sa.shape
+        n = self._held()
+        want_vm = (rule != ABS) if von_mises is None else bool(von_mises)
+        peak6, a = np.zeros((self.ndof // 3, 6)), np.zeros(MODAL_MAX_LOCKED)
+        vm = np.zeros(self.ndof // 3) if want_vm else None
+        z, zp = (None, None) if n is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_stress_spectrum(self._ctx, len(w), _d(w), _d(sa), int(bool(loglog)), int(rule),
+                                                            float(alpha), float(beta), zp, float(zpa), _d(peak6),
+                                                            None if vm is None else _d(vm), _d(a)))
+        return peak6, vm, a[:n or 0].copy()
 
     # ---- linear buckling ---------------------------------------------------
     def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):

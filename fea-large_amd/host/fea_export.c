@@ -358,6 +358,29 @@ static int append_field(const char *msh_path, const fea_deck *d, const char *nam
   return 0;
 }
 
+/* one $NodeData section of one component per node behind the file */
+static int append_scalar(const char *msh_path, const fea_deck *d, const char *name, const double *v)
+{
+  FILE *f = fopen(msh_path, "a");
+  int i;
+  if (!f) return FEAHIP_EINVAL;
+  fprintf(f, "$NodeData\n1\n\"%s\"\n1\n%f\n3\n0\n1\n%d\n", name, 0.0, d->nodes_count);
+  for (i = 0; i < d->nodes_count; ++i) fprintf(f, "%d %.9e\n", i + 1, v[i]);
+  fprintf(f, "$EndNodeData\n");
+  fclose(f);
+  return 0;
+}
+
+/* the largest of vm[n] and its node (the lowest among equals) */
+static double largest_of(const double *vm, int n, int *node)
+{
+  double best = -1.0;
+  int i;
+  *node = 0;
+  for (i = 0; i < n; ++i) if (vm[i] > best) { best = vm[i]; *node = i; }
+  return best;
+}
+
 int fea_spectrum_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   static const char *rule[] = {"srss", "cqc", "abs"};
@@ -384,6 +407,22 @@ int fea_spectrum_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char 
     fprintf(log, "Spectrum peak: |u| = %.17g, node %d dof %d, rule %s, %d modes\n", best, best_dof / 3 + 1, best_dof % 3,
             rule[d->spectrum_rule], m);
   if (msh_path) rc = append_field(msh_path, d, "Spectrum peak displacement", peak);
+  if (!rc && d->spectrum_stress) {                      /* :stress t: the peak von Mises stress on the same modes and load */
+    double *p6 = (double *)malloc(sizeof(double) * 7 * (size_t)d->nodes_count), *vm;
+    int node = 0;
+    if (!p6) { free(F); free(w); return FEAHIP_ENOMEM; }
+    vm = p6 + 6 * (size_t)d->nodes_count;
+    rc = feahip_response_stress_basis(ctx, -1);
+    if (!rc) rc = feahip_response_stress_spectrum(ctx, n, w, sa, d->spectrum_loglog, d->spectrum_rule, d->has_dynamics ? d->damping_alpha : 0.0,
+                                                  d->has_dynamics ? d->damping_beta : 0.0, d->spectrum_zeta > 0 ? zeta : NULL,
+                                                  d->spectrum_zpa, p6, vm, NULL);
+    if (!rc && log) {
+      best = largest_of(vm, d->nodes_count, &node);
+      fprintf(log, "Spectrum peak von Mises: vm = %.17g, node %d, rule %s, %d modes\n", best, node + 1, rule[d->spectrum_rule], m);
+    }
+    if (!rc && msh_path) rc = append_scalar(msh_path, d, "Spectrum peak von Mises stress", vm);
+    free(p6);
+  }
   free(F); free(w);
   return rc;
 }
@@ -423,6 +462,20 @@ int fea_random_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *m
   if (log)
     fprintf(log, "Random RMS: |u| = %.17g, node %d dof %d, %d grid points, %d modes\n", best, best_dof / 3 + 1, best_dof % 3, n_grid, m);
   if (msh_path) rc = append_field(msh_path, d, "RMS displacement", rms);
+  if (!rc && d->random_stress) {                        /* :stress t: the RMS von Mises stress on the same modes, load and grid */
+    double *p6 = (double *)malloc(sizeof(double) * 7 * (size_t)d->nodes_count), *vm;
+    int node = 0;
+    if (!p6) { free(F); free(w); free(omega); return FEAHIP_ENOMEM; }
+    vm = p6 + 6 * (size_t)d->nodes_count;
+    rc = feahip_response_stress_basis(ctx, -1);
+    if (!rc) rc = feahip_response_stress_random(ctx, n_grid, omega, Sw, alpha, beta, d->random_zeta > 0 ? zeta : NULL, p6, vm, NULL);
+    if (!rc && log) {
+      best = largest_of(vm, d->nodes_count, &node);
+      fprintf(log, "Random RMS von Mises: vm = %.17g, node %d, %d grid points, %d modes\n", best, node + 1, n_grid, m);
+    }
+    if (!rc && msh_path) rc = append_scalar(msh_path, d, "RMS von Mises stress", vm);
+    free(p6);
+  }
   free(F); free(w); free(omega);
   return rc;
 }

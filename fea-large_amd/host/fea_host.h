@@ -112,6 +112,13 @@ typedef struct fea_deck {
    * sweep feasolver_hip runs fea_transient_run.  Written by fea_deck_save only when n > 0: a deck without the section is
    * read, run and written as before.  The fields are the newest of the struct and stand in front of harmonic_count,
    * whose place (with everything behind it) the host tests pin                                                     */
+  /* :stress t inside (spectrum ...) and (random ...): after the displacement result, the peak (the RMS) of the von Mises
+   * stress on the same modes and load (feahip_response_stress_basis, then feahip_response_stress_spectrum or _random), one
+   * more log line and one more $NodeData section each.  :stress nil where absent; with :rule abs it is refused (the von
+   * Mises form needs the signs); any other section refuses the key.  Written by fea_deck_save only when set.  The two
+   * fields are the newest of the struct and stand in front of the fields of the two sections, which the next comment
+   * describes                                                                                                        */
+  int spectrum_stress, random_stress;
   /* response spectrum and random vibration, optional, inside (solution ...) beside a (modal ...) with :count or :shift:
    *   (spectrum :base (bx by bz) :rule srss|cqc|abs :zeta z :static-correction t :zpa a :interp linear|loglog
    *             (points (f1 sa1) (f2 sa2) ...))
@@ -122,9 +129,8 @@ typedef struct fea_deck {
    * :zpa 0, :interp linear, :per-mode 32 and :background 257 where absent.  Without :base the load is the surface load of
    * the state reached; both have the load errors of (transient ...), and :zpa > 0 needs :static-correction t and a rule
    * other than abs.  After the transient run feasolver_hip runs fea_spectrum_run and fea_random_run.  Written by
-   * fea_deck_save only when present: a deck without the sections is read, run and written as before.  The fields are the
-   * newest of the struct and stand in front of transient_steps, whose place (with everything behind it) the host tests
-   * pin                                                                                                            */
+   * fea_deck_save only when present: a deck without the sections is read, run and written as before.  The fields stand
+   * in front of transient_steps, whose place (with everything behind it) the host tests pin                         */
   int has_spectrum, spectrum_count;
   double *spectrum_points;                    /* [spectrum_count][2] = f in Hz, sa */
   int spectrum_rule;                          /* FEAHIP_SRSS, FEAHIP_CQC, FEAHIP_ABS */
@@ -308,7 +314,9 @@ int fea_transient_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* 
  * load as in fea_transient_run (the surface load of the state reached, or with :base the base load), then
  * feahip_response_spectrum of the displacement with the deck's points (Hz to rad/s), :rule, :zpa, :damping-alpha,
  * :damping-beta and :zeta.  Log: "Spectrum peak: |u| = p, node a dof j, rule r, m modes" (the largest of all dofs, the
- * lowest dof among equals, node from 1, dof 0-2).  With msh_path one $NodeData section "Spectrum peak displacement" is
+ * lowest dof among equals, node from 1, dof 0-2).  With :stress t also "Spectrum peak von Mises: vm = p, node a, rule r, m
+ * modes" and a one-component section "Spectrum peak von Mises stress" (fea_random_run: "Random RMS von Mises: vm = p, node
+ * a, g grid points, m modes" and "RMS von Mises stress").  With msh_path one $NodeData section "Spectrum peak displacement" is
  * appended.  Returns 0, or a negative FEAHIP_E* code.  */
 int fea_spectrum_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 /* The RMS displacement of a deck with (random ...), after fea_spectrum_run: the load likewise, the PSD table from per Hz

@@ -23,7 +23,10 @@
  * (feahip_response_base_load, feahip_response_transient).  A deck with
  * (spectrum ...) or (random ...) then gets the design peak under a response
  * spectrum or the RMS under a PSD on the same modes, one log line and one
- * field each (feahip_response_spectrum, feahip_response_random).  A deck with
+ * field each (feahip_response_spectrum, feahip_response_random), and with
+ * :stress t in the section the peak or the RMS of the von Mises stress as
+ * well, one more log line and one more field (feahip_response_stress_basis,
+ * feahip_response_stress_spectrum, feahip_response_stress_random).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid

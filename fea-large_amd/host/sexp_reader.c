@@ -598,6 +598,8 @@ static int read_list(reader *r, fea_deck *d)
   if (ieq(head, "psd")) return read_pairs(r, &d->random_points, &d->random_count, "random (psd ...)");
 
   if (read_attrs(r, d, a, &na, 1)) return -1;
+  if (attr_get(a, na, "stress") && !ieq(head, "spectrum") && !ieq(head, "random"))
+    return fail(r, ":stress belongs to (spectrum ...) and (random ...)");
 
   if (ieq(head, "model")) {                                   /* :32-54 */
     if ((s = attr_get(a, na, "name"))) {
@@ -792,6 +794,9 @@ static int read_list(reader *r, fea_deck *d)
     if (read_base(r, a, na, &d->spectrum_has_base, d->spectrum_base, "spectrum :base takes three finite numbers, not all zero")) return -1;
     if (d->spectrum_zpa > 0 && !d->spectrum_static) return fail(r, "spectrum :zpa needs :static-correction t");
     if (d->spectrum_zpa > 0 && d->spectrum_rule == FEAHIP_ABS) return fail(r, "spectrum :zpa needs a rule other than abs");
+    d->spectrum_stress = 0;
+    if (read_flag(r, a, na, "stress", &d->spectrum_stress, "spectrum :stress takes t or nil")) return -1;
+    if (d->spectrum_stress && d->spectrum_rule == FEAHIP_ABS) return fail(r, "spectrum :stress needs a rule other than abs");
     if (d->spectrum_count < 1) return fail(r, "spectrum needs (points (f sa) ...)");
     d->has_spectrum = 1;
   } else if (ieq(head, "random")) {                           /* no counterpart in the reference */
@@ -814,6 +819,8 @@ static int read_list(reader *r, fea_deck *d)
       d->random_background = (int)v;
     }
     if (read_base(r, a, na, &d->random_has_base, d->random_base, "random :base takes three finite numbers, not all zero")) return -1;
+    d->random_stress = 0;
+    if (read_flag(r, a, na, "stress", &d->random_stress, "random :stress takes t or nil")) return -1;
     if (d->random_count < 2) return fail(r, "random needs (psd (f s) ...) with two points at least");
     d->has_random = 1;
   } else if (ieq(head, "buckling")) {                         /* no counterpart in the reference */
@@ -944,6 +951,7 @@ void fea_deck_free(fea_deck *d)
   d->contact_faces_count = d->contact_obstacles_count = 0;
   free(d->spectrum_points); free(d->random_points);
   d->spectrum_points = d->random_points = NULL; d->spectrum_count = d->random_count = d->has_spectrum = d->has_random = 0;
+  d->spectrum_stress = d->random_stress = 0;
   free(d->material_params); free(d->element_material);
   d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
@@ -1010,6 +1018,7 @@ int fea_deck_save(const char *path, const fea_deck *d)
             d->spectrum_zeta, d->spectrum_static ? "t" : "nil", d->spectrum_zpa, d->spectrum_loglog ? "loglog" : "linear");
     if (d->spectrum_has_base)
       fprintf(f, " :base (%.17g %.17g %.17g)", d->spectrum_base[0], d->spectrum_base[1], d->spectrum_base[2]);
+    if (d->spectrum_stress) fprintf(f, " :stress t");                          /* written only when set */
     fprintf(f, "\n    (points");
     for (i = 0; i < d->spectrum_count; ++i) fprintf(f, " (%.17g %.17g)", d->spectrum_points[2 * i], d->spectrum_points[2 * i + 1]);
     fprintf(f, "))");
@@ -1019,6 +1028,7 @@ int fea_deck_save(const char *path, const fea_deck *d)
             d->random_static ? "t" : "nil", d->random_loglog ? "loglog" : "linear", d->random_per_mode, d->random_background);
     if (d->random_has_base)
       fprintf(f, " :base (%.17g %.17g %.17g)", d->random_base[0], d->random_base[1], d->random_base[2]);
+    if (d->random_stress) fprintf(f, " :stress t");
     fprintf(f, "\n    (psd");
     for (i = 0; i < d->random_count; ++i) fprintf(f, " (%.17g %.17g)", d->random_points[2 * i], d->random_points[2 * i + 1]);
     fprintf(f, "))");

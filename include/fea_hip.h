@@ -1167,6 +1167,97 @@ int feahip_host_spectrum_form(int n_modes, const double *lam, const double *q, c
                               double beta_k, const double *zeta /*[n_modes] or NULL*/, int rule, int static_correction,
                               double zpa, int quantity, double *C /*[n_modes][n_modes]*/, double *b /*[n_modes]*/, double *s);
 
+/* ---- stress from mode superposition: modal stresses, RMS and peak von Mises ----
+ * The linear map from a displacement increment du at the current nodes x to
+ * the nodal Cauchy stress it causes.  At a Gauss point, g[a][j] = dN_a/dx_j,
+ *     l_ij = sum_a du_a,i g[a][j],   d = (l + l') / 2
+ *     dsigma = c : d + l sigma + sigma l' - tr(d) sigma
+ * sigma the Cauchy stress of the point, c the spatial tangent of the model:
+ *   Neo-Hookean  c : d = (lambda / J) tr(d) I + 2 ((mu - lambda ln J) / J) d
+ *   A5, b = F F' c : d = (lambda (b : d) b + 2 mu b d b) / J
+ * (the coefficients l1, m1 of the stiffness; for A5 the stiffness takes them on
+ * the identity, the stress increment on b).  The nodal value keeps the weights
+ * of feahip_get_nodal_stresses, held fixed,
+ *     T_a = sum_e sum_g vol_g dsigma_g / sum_e sum_g vol_g,  vol_g = w_g |det J_g|
+ * over all elements at the node (material = -1) or over those of one material
+ * id; a node that touches no selected element returns 0.  Components xx yy zz
+ * xy yz xz.  At an unstressed state this is exactly the derivative of
+ * feahip_get_nodal_stresses; at a prestressed state it leaves out the variation
+ * of the weights.  Two kernels (k_mstress_elements, k_mstress_nodes) work a
+ * panel of eight columns at a time; no atomics, the same input gives the same
+ * bits.  A context that never calls the entries below allocates and launches
+ * nothing for them; the first call allocates the element records [E][6][8],
+ * the [6N] outputs, the two panels of the single-vector path ([3N][8] in,
+ * [6N][8] out: 72 N doubles) and, for the basis, the stress store of 6N x 8
+ * doubles per panel of eight modes -- twice the locked store.
+ *
+ * feahip_stress_increment: the map for one vector du[3N] in the caller's dof
+ * order, sig6[N][6] in the caller's node order.  Needs no modes and no mass.
+ * FEAHIP_EINVAL: a material outside the table, du not finite.
+ * feahip_response_stress_basis: the stress store of the modes held, at the
+ * current nodes: T_k for every mode, column for column the locked store.  With
+ * a load held with the static correction also T_s from u_s (bit for bit
+ * feahip_stress_increment of u_s); T_s = 0 otherwise.  FEAHIP_ESTATE without
+ * modes held.  Whatever invalidates the load invalidates the store: a later
+ * locked solve, feahip_response_set_basis, feahip_modal_deflate,
+ * feahip_solve_buckling, hooks 16-17 of feahip_time_kernel; a new load
+ * invalidates T_s, and with it the entries below until the basis is built
+ * again.  The store is that of the nodes at the call: it does not follow x.
+ * feahip_get_modal_stresses: sig6[count][N][6] of the modes [first, first +
+ * count) by ascending lam.  feahip_get_response_static_stress: T_s[N][6].
+ * feahip_response_stress_field: sig6 = cs T_s + sum_k coef_k T_k (coef by
+ * ascending mode, one fma per store column onto cs T_s) and vm[N], its von
+ * Mises stress: the stress of one row of feahip_host_response_coefficients
+ * (the real and the imaginary part each with a call of its own, cs = 1 for the
+ * real part of a load held with the correction) or of
+ * feahip_host_transient_coefficients (cs = g_n).
+ *
+ * The forms.  For a linear combination y = L T_a of the rows of a node (an
+ * m-vector of mode values) and y_s = L T_s,a, with (C, b, s) as
+ * feahip_response_combine takes them,
+ *     q(y) = y' C y + 2 y_s (b' y) + s y_s^2
+ *     out6[a][c] = sqrt(max(0, q(T_a,c)))
+ *     vm[a] = sqrt(max(0, (q(xx-yy) + q(yy-zz) + q(zz-xx)) / 2
+ *                          + 3 (q(xy) + q(yz) + q(xz))))
+ * -- the RMS (or design peak) of the von Mises stress is a quadratic form of
+ * its own in the modal covariance (Segalman et al.), not a function of the
+ * component values.  k_stress_combine evaluates the nine forms of a node in one
+ * launch, a lane per node, one combination in registers at a time.
+ * feahip_response_stress_combine: the form as given, with the checks of
+ * feahip_response_combine; vm may be NULL.  feahip_response_stress_random: the
+ * form of feahip_host_random_form at quantity 0; modal_cov as
+ * feahip_response_random.  feahip_response_stress_spectrum: the form of
+ * feahip_host_spectrum_form at quantity 0; with FEAHIP_ABS the components take
+ * |T| and peak_vm must be NULL (FEAHIP_EINVAL otherwise: the differences need
+ * the signs); peak_vm may be NULL under the other rules.
+ *
+ * All entries but feahip_stress_increment: FEAHIP_ESTATE without modes held;
+ * the entries after the basis also without a store for these modes or with a
+ * load made since; the three with a form also without a load held.  Every
+ * entry: FEAHIP_EINVAL on a row-sharded or feahip_create_rank* context, as
+ * feahip_response_transient.  x, v, a, the time, the load factor, K, f, u, the
+ * locked store, the load held and all three coefficient tables (hooks 23, 25,
+ * 26) are untouched: the form table of the stresses is a buffer of its own.
+ * Not offered: sharded runs, stress peaks over a whole sweep or transient in
+ * one launch (feahip_response_stress_field gives single rows), principal
+ * stresses, a signed von Mises stress, the variation of the weights at a
+ * prestressed state, superconvergent recovery.                               */
+int feahip_stress_increment(feahip_ctx *ctx, const double *du /*[3N]*/, int material, double *sig6 /*[N][6]*/);
+int feahip_response_stress_basis(feahip_ctx *ctx, int material);
+int feahip_get_modal_stresses(feahip_ctx *ctx, int first, int count, double *sig6 /*[count][N][6]*/);
+int feahip_get_response_static_stress(feahip_ctx *ctx, double *sig6 /*[N][6]*/);
+int feahip_response_stress_field(feahip_ctx *ctx, const double *coef /*[n_locked]*/, double cs, double *sig6 /*[N][6]*/,
+                                 double *vm /*[N]*/);
+int feahip_response_stress_combine(feahip_ctx *ctx, const double *C /*[n_locked][n_locked]*/, const double *b /*[n_locked] or NULL*/,
+                                   double s, double *out6 /*[N][6]*/, double *vm /*[N] or NULL*/);
+int feahip_response_stress_random(feahip_ctx *ctx, int n_freq, const double *omega /*[n_freq]*/, const double *S /*[n_freq]*/,
+                                  double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/, double *rms6 /*[N][6]*/,
+                                  double *rms_vm /*[N] or NULL*/, double *modal_cov /*[n_locked][n_locked] or NULL*/);
+int feahip_response_stress_spectrum(feahip_ctx *ctx, int n_pts, const double *w /*[n_pts]*/, const double *sa /*[n_pts]*/,
+                                    int loglog, int rule, double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/,
+                                    double zpa, double *peak6 /*[N][6]*/, double *peak_vm /*[N] or NULL; NULL with FEAHIP_ABS*/,
+                                    double *modal_peak /*[n_locked] or NULL*/);
+
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
  *     K_sigma(x) phi = nu K(x) phi          on the free dofs,
@@ -1516,7 +1607,12 @@ int feahip_sync(feahip_ctx *ctx);
  * k_transient_sweep over the last chunk of the last feahip_response_transient
  * (FEAHIP_ESTATE, "no transient", before one); 26 k_response_combine over the
  * form of the last feahip_response_combine, _random or _spectrum
- * (FEAHIP_ESTATE, "no form", before one).                                    */
+ * (FEAHIP_ESTATE, "no form", before one); 27 k_mstress_elements and
+ * k_mstress_nodes over every panel of the locked store in use at the current
+ * nodes, into the scratch panel of the single-vector path: the stress store in
+ * force is needed (FEAHIP_ESTATE without one) and is not written; 28 k_stress_combine over the form
+ * of the last feahip_response_stress_combine, _random or _spectrum
+ * (FEAHIP_ESTATE, "no stress form", before one).                             */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
