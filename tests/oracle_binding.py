@@ -125,6 +125,51 @@ def elem_table(kind, ngauss):
     return w, forms, dforms
 
 
+def gauss_rule(kind, ngauss):
+    """(weights[G], points[G][3]) of the HOST library's rule (fea_elements.c) for "tet4" / "tet10" / "hex8", the points
+    exactly as the library holds them.  Its tables carry no points, only what it evaluates at them, so they are read
+    back from entries that are a point's coordinate times a power of two: the linear tetrahedron's shape functions
+    (1-r-s-t, r, s, t), which the library tabulates for every tetrahedral rule.  The brick has no such entry; its two
+    abscissae are estimated from N_6 = r s t over its derivative, and the one pair within four units in the last place
+    that reproduces the library's derivative table to the bit, at all eight points, is taken."""
+    import feahip
+    if kind in ("tet4", "tet10"):
+        w, forms, _ = feahip.element_tables(feahip.TETRAHEDRA4, ngauss)
+        w10 = feahip.element_tables(feahip.TETRAHEDRA10 if kind == "tet10" else feahip.TETRAHEDRA4, ngauss)[0]
+        assert np.array_equal(w, w10)
+        return w, np.ascontiguousarray(forms[:, 1:4])
+    w, forms, dforms = feahip.element_tables(feahip.HEXAHEDRA8, ngauss)
+    corner = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)]
+
+    def table(p):                                             # h8_dN's products, in its order
+        out = np.empty((3, 8))
+        for dd in range(3):
+            for i in range(8):
+                v = 1.0
+                for d in range(3):
+                    v *= (1.0 if corner[i][d] else -1.0) if d == dd else (p[d] if corner[i][d] else 1 - p[d])
+                out[dd, i] = v
+        return out
+
+    def near(v, k):
+        for _ in range(abs(k)):
+            v = np.nextafter(v, np.inf if k > 0 else -np.inf)
+        return v
+
+    lo = forms[0, 6] / dforms[0, 0, 6]                       # point 0 is (a, a, a): r s t / (s t)
+    hi = forms[ngauss - 1, 6] / dforms[ngauss - 1, 0, 6]     # the last is (b, b, b)
+    fits = []
+    for ka in range(-4, 5):
+        for kb in range(-4, 5):
+            a, b = near(lo, ka), near(hi, kb)
+            pts = np.array([[b if (g >> d) & 1 else a for d in range(3)] for g in range(ngauss)])
+            if all(np.array_equal(table(pts[g]), dforms[g]) for g in range(ngauss)):
+                fits.append(pts)
+    if len(fits) != 1:
+        raise ValueError(f"{len(fits)} pairs of abscissae reproduce the brick's table of the host library; expected one")
+    return w, fits[0]
+
+
 class OracleSolver:
     """orc_solver with the reference's method names."""
 
