@@ -13,6 +13,10 @@ __device__ __forceinline__ double dpp_move_f64(double x)
   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
   return __hiloint2double(hi, lo);
 }
+// the whole wave moved by one lane, across the rows of sixteen: lane l takes lane l + 1 (wave_shl:1) or lane l - 1
+// (wave_shr:1); the lane at the end of the wave takes zero
+__device__ __forceinline__ double dpp_wave_up1(double x) { return dpp_move_f64<0x130>(x); }
+__device__ __forceinline__ double dpp_wave_down1(double x) { return dpp_move_f64<0x138>(x); }
 // lanes 4k .. 4k+3
 __device__ __forceinline__ double dpp_quad_sum(double v)
 {

@@ -92,14 +92,15 @@ struct DevTemp {
 // Block vectors ([3N][8], kernels_modal.hip) to and from host columns [3N] in the caller's order, through the W block
 // of ModalState::d_v as [8][3N] staging.  Up: columns [first, first + count) of host, count <= 8, the columns left of
 // the panel zero.  Down: the first count columns; owned_only as in get_view.  One column per transfer.
-static int upload_columns(feahip_ctx *c, double *dst_block, const double *host, int first, int count)
+// (pick: the host column of panel column k is pick[first + k] instead of first + k)
+static int upload_columns(feahip_ctx *c, double *dst_block, const double *host, int first, int count, const int *pick = nullptr)
 {
   const size_t n = (size_t)c->ndof;
   double *w = c->modal.d_v + n * FEA_MODAL_COLS;
   int rc;
   if (count < FEA_MODAL_COLS) FEA_HIP_CHECK(c, hipMemsetAsync(w + count * n, 0, sizeof(double) * (FEA_MODAL_COLS - count) * n, c->stream));
   for (int k = 0; k < count; ++k)
-    if ((rc = set_view(c, w + k * n, host + (size_t)(first + k) * n, 3, 3))) return rc;
+    if ((rc = set_view(c, w + k * n, host + (size_t)(pick ? pick[first + k] : first + k) * n, 3, 3))) return rc;
   return launch_modal_pack(c, w, dst_block, 0);
 }
 
@@ -1550,16 +1551,19 @@ extern "C" int feahip_response_set_basis(feahip_ctx *c, int n, const double *lam
   if ((rc = modal_ready(c, "response_set_basis")) || (rc = ensure_modal(c)) || (rc = ensure_locked(c, n))) return rc;
   ModalState &S = c->modal;
   S.have = false;                                                    // the block vectors are scratch here
+  // The pairs go into the store by ascending lam (equal ones in the caller's order), column k the k-th of them: the sums of
+  // the superposition kernels run in column order, so the order the caller lists the pairs in does not reach their bits
+  int pick[FEA_MODAL_MAX_LOCKED];
+  for (int k = 0; k < n; ++k) pick[k] = k;
+  std::stable_sort(pick, pick + n, [&](int x, int y) { return lam[x] < lam[y]; });
   double *v = S.d_v;                                                 // X <- a panel, zero on the prescribed dofs
   for (int p = 0; p * FEA_MODAL_COLS < n; ++p) {
     const int first = p * FEA_MODAL_COLS;
-    if ((rc = upload_columns(c, v, phi, first, std::min(FEA_MODAL_COLS, n - first))) || (rc = launch_response_mask8(c, v))) return rc;
+    if ((rc = upload_columns(c, v, phi, first, std::min(FEA_MODAL_COLS, n - first), pick)) || (rc = launch_response_mask8(c, v))) return rc;
     FEA_HIP_CHECK(c, hipMemcpyAsync(locked_panel(c, 0, p), v, sizeof(double) * (size_t)c->ndof * FEA_MODAL_COLS, hipMemcpyDeviceToDevice, c->stream));
   }
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < n; ++k) S.lock_order[k] = k;                   // column k holds the caller's pair k; read in ascending lam
-  std::stable_sort(S.lock_order, S.lock_order + n, [&](int x, int y) { return lam[x] < lam[y]; });
-  for (int k = 0; k < n; ++k) S.lam[k] = lam[S.lock_order[k]];
+  for (int k = 0; k < n; ++k) { S.lock_order[k] = k; S.lam[k] = lam[pick[k]]; }
   S.shift = 0.0;
   S.n_locked = n;
   ++S.lock_gen;
@@ -2010,6 +2014,83 @@ extern "C" int feahip_response_stress_spectrum(feahip_ctx *c, int n_pts, const d
   return FEAHIP_OK;
 }
 
+// ---- stress peaks over a sweep or a transient (kernels_stress_sweep.hip) ------------------------------------------------
+// lib[r] = the library's node of the caller's probe_node[r], each inside [0, N)
+static int probe_nodes(feahip_ctx *c, const char *who, int n_probe, const int *probe_node, int *lib)
+{
+  for (int r = 0; r < n_probe; ++r) {
+    if (probe_node[r] < 0 || probe_node[r] >= c->N) { c->err = std::string(who) + ": probe node outside [0, N)"; return FEAHIP_EINVAL; }
+    lib[r] = lib_id(c, probe_node[r]);
+  }
+  return FEAHIP_OK;
+}
+
+namespace {
+// the four outputs in the library's order, and their way to the caller's
+struct StressPeaks {
+  std::vector<double> p6, vm;
+  std::vector<int> a6, avm;
+  explicit StressPeaks(const feahip_ctx *c) : p6(6 * (size_t)c->N), vm((size_t)c->N), a6(6 * (size_t)c->N), avm((size_t)c->N) {}
+  void to_caller_ids(feahip_ctx *c, double *peak6, int *peak6_at, double *vm_out, int *vm_at) const
+  {
+    to_caller(view_of(c), 6, 6, p6.data(), peak6);
+    to_caller(view_of(c), 6, 6, a6.data(), peak6_at);
+    to_caller(view_of(c), 1, 1, vm.data(), vm_out);
+    to_caller(view_of(c), 1, 1, avm.data(), vm_at);
+  }
+};
+}
+
+extern "C" int feahip_response_stress_sweep(feahip_ctx *c, int n_freq, const double *omega, double alpha, double beta_k,
+                                            const double *zeta, double *peak6, int *peak6_at, double *vm, int *vm_at,
+                                            int n_probe, const int *probe_node, double *probe_re, double *probe_im)
+{
+  CTX_GUARD_NOK(c);
+  if (!omega || !peak6 || !peak6_at || !vm || !vm_at) { c->err = "response_stress_sweep: null omega, peak6, peak6_at, vm or vm_at"; return FEAHIP_EINVAL; }
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_sweep"))) return rc;
+  if (n_freq < 1 || n_freq > FEA_RESPONSE_MAX_FREQ) { c->err = "response_stress_sweep: n_freq must be in [1, 4096]"; return FEAHIP_EINVAL; }
+  if (n_probe < 0 || n_probe > 64) { c->err = "response_stress_sweep: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
+  if (n_probe > 0 && (!probe_node || !probe_re || !probe_im)) { c->err = "response_stress_sweep: null probe arrays"; return FEAHIP_EINVAL; }
+  int probe[64];
+  if ((rc = probe_nodes(c, "response_stress_sweep", n_probe, probe_node, probe))) return rc;
+  StressPeaks out(c);
+  std::vector<double> pre((size_t)n_probe * n_freq * 6), pim(pre.size());   // (the caller's arrays stay as they are on a refusal)
+  if ((rc = stress_sweep(c, n_freq, omega, alpha, beta_k, zeta, out.p6.data(), out.a6.data(), out.vm.data(), out.avm.data(), n_probe,
+                         probe, pre.data(), pim.data()))) return rc;
+  out.to_caller_ids(c, peak6, peak6_at, vm, vm_at);
+  std::copy(pre.begin(), pre.end(), probe_re);
+  std::copy(pim.begin(), pim.end(), probe_im);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_stress_transient(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta_k,
+                                                const double *zeta, double *peak6, int *peak6_at, double *vm, int *vm_at,
+                                                int n_probe, const int *probe_node, double *probe)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_transient"))) return rc;
+  if (!g || !peak6 || !peak6_at || !vm || !vm_at) { c->err = "response_stress_transient: null g, peak6, peak6_at, vm or vm_at"; return FEAHIP_EINVAL; }
+  if (n_steps < 1 || n_steps > FEA_TRANSIENT_MAX_STEPS) { c->err = "response_stress_transient: n_steps must be in [1, 1048576]"; return FEAHIP_EINVAL; }
+  if (n_probe < 0 || n_probe > 64) { c->err = "response_stress_transient: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
+  if (n_probe > 0 && (!probe_node || !probe)) { c->err = "response_stress_transient: null probe arrays"; return FEAHIP_EINVAL; }
+  int lib_probe[64];
+  if ((rc = probe_nodes(c, "response_stress_transient", n_probe, probe_node, lib_probe))) return rc;
+  StressPeaks out(c);
+  std::vector<double> hist((size_t)n_probe * ((size_t)n_steps + 1) * 6);
+  if ((rc = stress_transient(c, n_steps, dt, g, alpha, beta_k, zeta, out.p6.data(), out.a6.data(), out.vm.data(), out.avm.data(),
+                             n_probe, lib_probe, hist.data()))) return rc;
+  out.to_caller_ids(c, peak6, peak6_at, vm, vm_at);
+  std::copy(hist.begin(), hist.end(), probe);
+  return FEAHIP_OK;
+}
+
+extern "C" double feahip_host_harmonic_von_mises(const double re6[6], const double im6[6])
+{
+  return harmonic_von_mises(re6, im6);
+}
+
 extern "C" int feahip_host_modal_ritz(int n_dirs,const double *gram_m, const double *gram_k, double *theta, double *coef)
 {
   if (!gram_m || !gram_k || !theta || !coef || (n_dirs != 8 && n_dirs != 16 && n_dirs != 24)) return FEAHIP_EINVAL;
@@ -2449,6 +2530,13 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (rk) return rk;
     if (what == 28 && !c->stress.form_set) { c->err = "time_kernel: no stress form set yet (feahip_response_stress_combine, _random or _spectrum first)"; return FEAHIP_ESTATE; }
   }
+  if (what == 29 || what == 30) {                      // the table of the last stress sweep / the last chunk of the last stress transient
+    const int rk = stress_form_ready(c, what == 29 ? "time_kernel(29)" : "time_kernel(30)");
+    if (rk) return rk;
+    const bool laid = c->stress.table_gen == c->modal.lock_gen;
+    if (what == 29 && !(laid && c->stress.swept_freq > 0)) { c->err = "time_kernel: no stress sweep made yet (feahip_response_stress_sweep first)"; return FEAHIP_ESTATE; }
+    if (what == 30 && !(laid && c->stress.trans_rows > 0)) { c->err = "time_kernel: no stress transient made yet (feahip_response_stress_transient first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2476,6 +2564,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 26: return time_combine_kernel(c);
     case 27: return time_stress_store(c);
     case 28: return time_stress_combine(c);
+    case 29: case 30: return time_stress_sweep_kernel(c, what);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

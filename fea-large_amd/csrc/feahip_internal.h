@@ -569,6 +569,14 @@ struct StressState {
   double *d_store = nullptr;           // [store_panels][6N][8] the stress store, column for column the locked store's
   double *d_form = nullptr;            // [FEA_COMBINE_TABLE] the form of the last stress combination (feahip_time_kernel 28)
   double *d_fcoef = nullptr;           // [64 + 8] the coefficients of the last feahip_response_stress_field, then cs
+  double *d_scoef = nullptr;           // [FEA_RESPONSE_MAX_FREQ][2][64] the table of the stress sweeps (kernels_stress_sweep.hip): its
+                                       // own, so the tables of the displacement sweeps stay; allocated by the first one
+  int *d_at6 = nullptr;                // [6N] the row index of every stress row's peak ...
+  int *d_vmat = nullptr;               // [N] ... and of every node's von Mises peak
+  int swept_freq = 0;                  // frequencies in d_scoef from the last stress sweep (feahip_time_kernel 29)
+  int trans_rows = 0;                  // rows in d_scoef from the last chunk of the last stress transient (hook 30) ...
+  int trans_step0 = 0;                 // ... and the step of its first row
+  int table_gen = -1;                  // the filling of the locked store d_scoef was laid out for
   int store_panels = 0;                // panels allocated
   bool have = false;                   // the store holds the stresses of the modes held ...
   int gen = -1;                        // ... of the filling ModalState::lock_gen == gen ...
@@ -576,7 +584,7 @@ struct StressState {
   int material = -1;                   // ... over the elements of this material (-1: all)
   bool form_set = false;               // d_form holds a form for this store ...
   bool form_abs = false;               // ... to be taken on |T|
-  void release() { dev_free({d_rec, d_evol, d_vec, d_in, d_one, d_out6, d_vm, d_ts, d_store, d_form, d_fcoef}); *this = StressState(); }
+  void release() { dev_free({d_rec, d_evol, d_vec, d_in, d_one, d_out6, d_vm, d_ts, d_store, d_form, d_fcoef, d_scoef, d_at6, d_vmat}); *this = StressState(); }
 };
 
 // linear buckling (kernels_buckling.hip): nothing of it exists until feahip_solve_buckling (or one of its hooks,
@@ -910,6 +918,14 @@ int time_stress_store(feahip_ctx *c);                                   // feahi
 int stress_combine(feahip_ctx *c, const double *C, const double *b, double s, bool absx, double *h_out6, double *h_vm);
 int stress_field(feahip_ctx *c, const double *coef, double cs, double *h_out6, double *h_vm);
 int time_stress_combine(feahip_ctx *c);                                 // feahip_time_kernel 28
+// kernels_stress_sweep.hip -- stress peaks over a frequency sweep or a transient: peak6 / at6 [6N], vm / vm_at [N] in library
+// ids, the probes (library node ids) [n_probe][rows][6]
+int stress_sweep(feahip_ctx *c, int n_freq, const double *omega, double alpha, double beta, const double *zeta, double *h_peak6,
+                 int *h_at6, double *h_vm, int *h_vmat, int n_probe, const int *probe, double *probe_re, double *probe_im);
+int stress_transient(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta, const double *zeta,
+                     double *h_peak6, int *h_at6, double *h_vm, int *h_vmat, int n_probe, const int *probe, double *h_probe);
+double harmonic_von_mises(const double re6[6], const double im6[6]);    // host only: the cycle peak, the kernel's arithmetic
+int time_stress_sweep_kernel(feahip_ctx *c, int what);                  // feahip_time_kernel 29 (sweep), 30 (transient)
 // combine_table.cpp -- the forms of a PSD and of a response spectrum, host only, in long double.  Mode k of the arrays is
 // row and column k of C[n_modes][n_modes] and entry k of b; FEAHIP_EINVAL and *why for what the entries refuse
 int random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,

@@ -192,6 +192,11 @@ ABI = {
     "feahip_response_stress_random": [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp],
     "feahip_response_stress_spectrum": [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_double,
                                         _dp, _dp, _dp],
+    "feahip_response_stress_sweep": [C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _ip, _dp, _ip, C.c_int, _ip,
+                                     _dp, _dp],
+    "feahip_response_stress_transient": [C.c_void_p, C.c_int, C.c_double, _dp, C.c_double, C.c_double, _dp, _dp, _ip, _dp, _ip,
+                                         C.c_int, _ip, _dp],
+    "feahip_host_harmonic_von_mises": [_dp, _dp],
     "feahip_host_random_form": [C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp, _dp,
                                 _dp],
     "feahip_host_random_grid": [C.c_int, _dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _ip],
@@ -243,7 +248,8 @@ def load_library():
             fn.argtypes = args
             fn.restype = C.c_char_p if name in ("feahip_last_error", "feahip_create_error") else (
                 None if name == "feahip_destroy" else
-                C.c_double if name in ("feahip_host_psd_value", "feahip_host_spectrum_value") else C.c_int)
+                C.c_double if name in ("feahip_host_psd_value", "feahip_host_spectrum_value",
+                                       "feahip_host_harmonic_von_mises") else C.c_int)
         _lib = lib
     return _lib
 
@@ -266,6 +272,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("harmonic_stress", C.c_int), ("transient_stress", C.c_int),
         ("spectrum_stress", C.c_int), ("random_stress", C.c_int),
         ("has_spectrum", C.c_int), ("spectrum_count", C.c_int), ("spectrum_points", _dp), ("spectrum_rule", C.c_int),
         ("spectrum_static", C.c_int), ("spectrum_loglog", C.c_int), ("spectrum_has_base", C.c_int),
@@ -401,6 +408,20 @@ def host_transient_coefficients(lam, q, g, dt, alpha=0.0, beta=0.0, zeta=None, s
     if rc != 0:
         raise FeaHipError(f"feahip_host_transient_coefficients refused its input ({rc})")
     return coef
+
+
+def host_harmonic_von_mises(sig6):
+    """feahip_host_harmonic_von_mises (no device): the largest von Mises stress over the cycle of the harmonic stress
+    state Re(sig6 exp(i w t)), sig6 complex [..., 6] as xx yy zz xy yz xz; vectorised over the leading axes."""
+    lib = load_library()
+    s = np.asarray(sig6, dtype=np.complex128)
+    assert s.shape[-1] == 6
+    flat = s.reshape(-1, 6)
+    re, im = np.ascontiguousarray(flat.real), np.ascontiguousarray(flat.imag)
+    out = np.zeros(len(flat))
+    for k in range(len(flat)):
+        out[k] = lib.feahip_host_harmonic_von_mises(_d(re[k]), _d(im[k]))
+    return out.reshape(s.shape[:-1])
 
 
 def _modal_arrays(lam, q, zeta):
@@ -630,6 +651,9 @@ class Deck:
         self.harmonic_to = float(kw.get("harmonic_to", 0.0))
         self.harmonic_zeta = float(kw.get("harmonic_zeta", 0.0))
         self.harmonic_static = bool(kw.get("harmonic_static", True))
+        self.harmonic_stress = bool(kw.get("harmonic_stress", False))          # :stress t: the peak von Mises stress as well
+        if self.harmonic_stress and not self.harmonic_count:
+            raise ValueError("harmonic_stress needs harmonic_count")
         if not 0 <= self.harmonic_count <= RESPONSE_MAX_FREQ:
             raise ValueError("harmonic_count: 1 to 4096")
         if self.harmonic_count:
@@ -652,6 +676,9 @@ class Deck:
         self.transient_rise = float(kw.get("transient_rise", 0.0))
         base = kw.get("transient_base")
         self.transient_base = None if base is None else tuple(float(b) for b in base)
+        self.transient_stress = bool(kw.get("transient_stress", False))        # :stress t: the peak von Mises stress as well
+        if self.transient_stress and not self.transient_steps:
+            raise ValueError("transient_stress needs transient_steps")
         if not 0 <= self.transient_steps <= TRANSIENT_MAX_STEPS:
             raise ValueError("transient_steps: 1 to 1048576")
         if self.transient_steps:
@@ -776,12 +803,14 @@ class Deck:
                         modal_tolerance=fd.modal_tolerance, modal_max=fd.modal_max)
                    if fd.modal_modes or fd.modal_count else {}),
                 **(dict(harmonic_count=fd.harmonic_count, harmonic_from=fd.harmonic_from, harmonic_to=fd.harmonic_to,
-                        harmonic_zeta=fd.harmonic_zeta, harmonic_static=bool(fd.harmonic_static))
+                        harmonic_zeta=fd.harmonic_zeta, harmonic_static=bool(fd.harmonic_static),
+                        harmonic_stress=bool(fd.harmonic_stress))
                    if fd.harmonic_count else {}),
                 **(dict(transient_steps=fd.transient_steps, transient_dt=fd.transient_dt, transient_zeta=fd.transient_zeta,
                         transient_static=bool(fd.transient_static), transient_shape=TRANSIENT_SHAPES[fd.transient_shape],
                         transient_rise=fd.transient_rise,
-                        transient_base=[fd.transient_base[k] for k in range(3)] if fd.transient_has_base else None)
+                        transient_base=[fd.transient_base[k] for k in range(3)] if fd.transient_has_base else None,
+                        transient_stress=bool(fd.transient_stress))
                    if fd.transient_steps else {}),
                 **(dict(spectrum_points=np.ctypeslib.as_array(fd.spectrum_points, (fd.spectrum_count, 2)).copy(),
                         spectrum_rule=SPECTRUM_RULES[fd.spectrum_rule], spectrum_zeta=fd.spectrum_zeta, spectrum_zpa=fd.spectrum_zpa,
@@ -853,10 +882,12 @@ class Deck:
         if getattr(self, "harmonic_count", 0):
             fd.harmonic_count, fd.harmonic_from, fd.harmonic_to = int(self.harmonic_count), float(self.harmonic_from), float(self.harmonic_to)
             fd.harmonic_zeta, fd.harmonic_static = float(self.harmonic_zeta), int(bool(self.harmonic_static))
+            fd.harmonic_stress = int(bool(getattr(self, "harmonic_stress", False)))
         if getattr(self, "transient_steps", 0):
             fd.transient_steps, fd.transient_dt, fd.transient_zeta = int(self.transient_steps), float(self.transient_dt), float(self.transient_zeta)
             fd.transient_static, fd.transient_shape = int(bool(self.transient_static)), TRANSIENT_SHAPES.index(self.transient_shape)
             fd.transient_rise = float(self.transient_rise)
+            fd.transient_stress = int(bool(getattr(self, "transient_stress", False)))
             if self.transient_base is not None:
                 fd.transient_has_base = 1
                 for k in range(3):
@@ -1540,6 +1571,37 @@ class FeaSolver:
                                                             float(alpha), float(beta), zp, float(zpa), _d(peak6),
                                                             None if vm is None else _d(vm), _d(a)))
         return peak6, vm, a[:n or 0].copy()
+
+    # ---- stress peaks over a sweep or a transient, one launch each ----------------
+    def response_stress_sweep(self, omega, alpha=0.0, beta=0.0, zeta=None, probes=()):
+        """feahip_response_stress_sweep over the circular frequencies omega: (peak6[N][6] = max_j |s_c(w_j)|, peak6_at[N][6],
+        vm[N] = the largest von Mises stress over the cycle and the frequencies, vm_at[N], the complex curves
+        [n_probe][n_freq][6] of the probe nodes); every _at the lowest j that attains its peak."""
+        omega = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
+        pr = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        N = self.ndof // 3
+        peak6, at6 = np.zeros((N, 6)), np.zeros((N, 6), dtype=np.int32)
+        vm, vat = np.zeros(N), np.zeros(N, dtype=np.int32)
+        re, im = np.zeros((len(pr), len(omega), 6)), np.zeros((len(pr), len(omega), 6))
+        z, zp = (None, None) if self._held() is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_stress_sweep(self._ctx, len(omega), _d(omega), float(alpha), float(beta), zp,
+                                                         _d(peak6), _i(at6), _d(vm), _i(vat), len(pr), _i(pr), _d(re), _d(im)))
+        return peak6, at6, vm, vat, re + 1j * im
+
+    def response_stress_transient(self, g, dt, alpha=0.0, beta=0.0, zeta=None, probes=()):
+        """feahip_response_stress_transient under the load held times g(t), g[n_steps + 1] at t_n = n dt: (peak6[N][6] =
+        max_n |sigma_c(t_n)|, peak6_at[N][6], vm[N] = the largest von Mises stress, vm_at[N], the histories
+        [n_probe][n_steps + 1][6] of the probe nodes); every _at the lowest step that attains its peak."""
+        g = np.ascontiguousarray(np.atleast_1d(g), dtype=np.float64)
+        pr = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        N = self.ndof // 3
+        peak6, at6 = np.zeros((N, 6)), np.zeros((N, 6), dtype=np.int32)
+        vm, vat = np.zeros(N), np.zeros(N, dtype=np.int32)
+        hist = np.zeros((len(pr), len(g), 6))
+        z, zp = (None, None) if self._held() is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_stress_transient(self._ctx, len(g) - 1, float(dt), _d(g), float(alpha), float(beta),
+                                                             zp, _d(peak6), _i(at6), _d(vm), _i(vat), len(pr), _i(pr), _d(hist)))
+        return peak6, at6, vm, vat, hist
 
     # ---- linear buckling ---------------------------------------------------
     def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):

@@ -205,6 +205,34 @@ int fea_modal_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *ms
   return 0;
 }
 
+static int append_scalar(const char *msh_path, const fea_deck *d, const char *name, const double *v);
+static double largest_of(const double *vm, int n, int *node);
+
+/* :stress t of (harmonic ...) and (transient ...): the stress store on the modes and the load held, then the largest von
+ * Mises stress of every node over the sweep (g NULL: n frequencies omega) or over the history (n steps of dt under g), one
+ * log line and one $NodeData section */
+static int stress_peak_run(const fea_deck *d, feahip_ctx *ctx, FILE *log, const char *msh_path, int n, const double *omega,
+                           const double *g, double dt, const double *zeta)
+{
+  const size_t N = (size_t)d->nodes_count;
+  const double alpha = d->has_dynamics ? d->damping_alpha : 0.0, beta = d->has_dynamics ? d->damping_beta : 0.0;
+  double *p6 = (double *)malloc(sizeof(double) * 7 * N), *vm, best;
+  int *a6 = (int *)malloc(sizeof(int) * 7 * N), *vat, node = 0, rc;
+  if (!p6 || !a6) { free(p6); free(a6); return FEAHIP_ENOMEM; }
+  vm = p6 + 6 * N; vat = a6 + 6 * N;
+  rc = feahip_response_stress_basis(ctx, -1);
+  if (!rc) rc = g ? feahip_response_stress_transient(ctx, n, dt, g, alpha, beta, zeta, p6, a6, vm, vat, 0, NULL, NULL)
+                  : feahip_response_stress_sweep(ctx, n, omega, alpha, beta, zeta, p6, a6, vm, vat, 0, NULL, NULL, NULL);
+  if (!rc && log) {
+    best = largest_of(vm, d->nodes_count, &node);
+    if (g) fprintf(log, "Transient peak von Mises: vm = %.17g, node %d, t = %.17g\n", best, node + 1, vat[node] * dt);
+    else fprintf(log, "Harmonic peak von Mises: vm = %.17g, node %d, f = %.17g Hz\n", best, node + 1, omega[vat[node]] / 6.283185307179586);
+  }
+  if (!rc && msh_path) rc = append_scalar(msh_path, d, g ? "Transient peak von Mises stress" : "Harmonic peak von Mises stress", vm);
+  free(p6); free(a6);
+  return rc;
+}
+
 int fea_harmonic_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   FILE *log = (FILE *)log_, *f;
@@ -250,8 +278,9 @@ int fea_harmonic_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char 
     fprintf(f, "$EndNodeData\n");
     fclose(f);
   }
+  if (d->harmonic_stress) rc = stress_peak_run(d, ctx, log, msh_path, n, omega, NULL, 0.0, d->harmonic_zeta > 0 ? zeta : NULL);
   free(F); free(omega); free(at);
-  return 0;
+  return rc;
 }
 
 /* g(t) of (transient :shape ...) */
@@ -322,8 +351,9 @@ int fea_transient_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char
     fprintf(f, "$EndNodeData\n");
     fclose(f);
   }
+  if (d->transient_stress) rc = stress_peak_run(d, ctx, log, msh_path, n, NULL, g, d->transient_dt, d->transient_zeta > 0 ? zeta : NULL);
   free(F); free(g); free(at);
-  return 0;
+  return rc;
 }
 
 /* the load of (spectrum ...) and (random ...): with a base direction the base load, else the surface load of the state

@@ -112,10 +112,17 @@ typedef struct fea_deck {
    * sweep feasolver_hip runs fea_transient_run.  Written by fea_deck_save only when n > 0: a deck without the section is
    * read, run and written as before.  The fields are the newest of the struct and stand in front of harmonic_count,
    * whose place (with everything behind it) the host tests pin                                                     */
+  /* :stress t inside (harmonic ...) and (transient ...): after the displacement peaks, the largest von Mises stress of every
+   * node over the sweep (over the cycle and the frequencies) or over the history, on the same modes and load
+   * (feahip_response_stress_basis, then feahip_response_stress_sweep or _transient), one more log line and one more
+   * $NodeData section each.  :stress nil where absent.  Written by fea_deck_save only when set: a deck without the key is
+   * read, run and written as before.  The two fields are the newest of the struct and stand in front of the two of the next
+   * comment, whose place (with everything behind it) the host tests pin                                                */
+  int harmonic_stress, transient_stress;
   /* :stress t inside (spectrum ...) and (random ...): after the displacement result, the peak (the RMS) of the von Mises
    * stress on the same modes and load (feahip_response_stress_basis, then feahip_response_stress_spectrum or _random), one
    * more log line and one more $NodeData section each.  :stress nil where absent; with :rule abs it is refused (the von
-   * Mises form needs the signs); any other section refuses the key.  Written by fea_deck_save only when set.  The two
+   * Mises form needs the signs); any section but these two, (harmonic ...) and (transient ...) refuses the key.  Written by fea_deck_save only when set.  The two
    * fields are the newest of the struct and stand in front of the fields of the two sections, which the next comment
    * describes                                                                                                        */
   int spectrum_stress, random_stress;
@@ -299,7 +306,11 @@ int fea_modal_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, 
  * deck's :damping-alpha, :damping-beta and :zeta.  Log: "Harmonic: n frequencies f0 .. f1 Hz, m modes, static correction
  * on|off" and "Harmonic peak: |u| = p at f = x Hz, node a dof j" (the largest peak of all dofs, the lowest dof among
  * equals, node from 1, dof 0-2).  With msh_path not NULL two $NodeData sections of three components per node are
- * appended: "Harmonic peak amplitude" and "Harmonic peak frequency" (Hz).  Returns 0, or a negative FEAHIP_E* code.  */
+ * appended: "Harmonic peak amplitude" and "Harmonic peak frequency" (Hz).  With :stress t then feahip_response_stress_basis
+ * and feahip_response_stress_sweep over the same frequencies: "Harmonic peak von Mises: vm = p, node a, f = x Hz" (the
+ * largest of all nodes, the lowest node among equals) and a one-component section "Harmonic peak von Mises stress";
+ * fea_transient_run likewise: "Transient peak von Mises: vm = p, node a, t = x" and "Transient peak von Mises stress"
+ * (feahip_response_stress_transient).  Returns 0, or a negative FEAHIP_E* code.  */
 int fea_harmonic_run(const fea_deck *deck, feahip_ctx *ctx, void *log /* FILE* */, const char *msh_path);
 /* The time history of a deck with (transient :steps n ...), n > 0, after fea_harmonic_run and before anything drops the
  * locked modes: feahip_response_load with the surface load of the state reached (all zero: a log line and FEAHIP_EINVAL)

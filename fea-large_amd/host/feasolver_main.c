@@ -26,7 +26,10 @@
  * field each (feahip_response_spectrum, feahip_response_random), and with
  * :stress t in the section the peak or the RMS of the von Mises stress as
  * well, one more log line and one more field (feahip_response_stress_basis,
- * feahip_response_stress_spectrum, feahip_response_stress_random).  A deck with
+ * feahip_response_stress_spectrum, feahip_response_stress_random); :stress t
+ * in (harmonic ...) or (transient ...) likewise adds the largest von Mises
+ * stress of every node over the sweep or the history
+ * (feahip_response_stress_sweep, feahip_response_stress_transient).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid

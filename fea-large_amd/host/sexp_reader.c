@@ -598,8 +598,8 @@ static int read_list(reader *r, fea_deck *d)
   if (ieq(head, "psd")) return read_pairs(r, &d->random_points, &d->random_count, "random (psd ...)");
 
   if (read_attrs(r, d, a, &na, 1)) return -1;
-  if (attr_get(a, na, "stress") && !ieq(head, "spectrum") && !ieq(head, "random"))
-    return fail(r, ":stress belongs to (spectrum ...) and (random ...)");
+  if (attr_get(a, na, "stress") && !ieq(head, "spectrum") && !ieq(head, "random") && !ieq(head, "harmonic") && !ieq(head, "transient"))
+    return fail(r, ":stress belongs to (harmonic ...), (transient ...), (spectrum ...) and (random ...)");
 
   if (ieq(head, "model")) {                                   /* :32-54 */
     if ((s = attr_get(a, na, "name"))) {
@@ -737,6 +737,8 @@ static int read_list(reader *r, fea_deck *d)
       if (ieq(s, "nil") || ieq(s, "no") || ieq(s, "false")) d->harmonic_static = 0;
       else if (!(ieq(s, "t") || ieq(s, "yes") || ieq(s, "true"))) return fail(r, "harmonic :static-correction takes t or nil");
     }
+    d->harmonic_stress = 0;
+    if (read_flag(r, a, na, "stress", &d->harmonic_stress, "harmonic :stress takes t or nil")) return -1;
   } else if (ieq(head, "transient")) {                        /* no counterpart in the reference */
     if (need_num(r, a, na, "steps", &v)) return -1;
     if (!(v >= 1 && v <= FEA_TRANSIENT_MAX_STEPS) || v != (double)(int)v) return fail(r, "transient :steps must be an integer in [1, 1048576]");
@@ -774,6 +776,8 @@ static int read_list(reader *r, fea_deck *d)
       if (d->transient_base[0] == 0 && d->transient_base[1] == 0 && d->transient_base[2] == 0) return fail(r, "transient :base must not be zero");
       d->transient_has_base = 1;
     }
+    d->transient_stress = 0;
+    if (read_flag(r, a, na, "stress", &d->transient_stress, "transient :stress takes t or nil")) return -1;
   } else if (ieq(head, "spectrum")) {                         /* no counterpart in the reference */
     d->spectrum_rule = FEAHIP_SRSS; d->spectrum_zeta = 0; d->spectrum_zpa = 0; d->spectrum_static = 1; d->spectrum_loglog = 0;
     if ((s = attr_get(a, na, "rule"))) {
@@ -951,7 +955,7 @@ void fea_deck_free(fea_deck *d)
   d->contact_faces_count = d->contact_obstacles_count = 0;
   free(d->spectrum_points); free(d->random_points);
   d->spectrum_points = d->random_points = NULL; d->spectrum_count = d->random_count = d->has_spectrum = d->has_random = 0;
-  d->spectrum_stress = d->random_stress = 0;
+  d->spectrum_stress = d->random_stress = d->harmonic_stress = d->transient_stress = 0;
   free(d->material_params); free(d->element_material);
   d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
@@ -1001,15 +1005,19 @@ int fea_deck_save(const char *path, const fea_deck *d)
     if (d->modal_shift != 0.0) fprintf(f, " :shift %.17g", d->modal_shift);    /* (the old text without the new keys) */
     fprintf(f, ")");
   }
-  if (d->harmonic_count > 0)                                                   /* written only when asked for */
-    fprintf(f, "\n   (harmonic :from %.17g :to %.17g :count %d :zeta %.17g :static-correction %s)", d->harmonic_from,
+  if (d->harmonic_count > 0) {                                                 /* written only when asked for */
+    fprintf(f, "\n   (harmonic :from %.17g :to %.17g :count %d :zeta %.17g :static-correction %s", d->harmonic_from,
             d->harmonic_to, d->harmonic_count, d->harmonic_zeta, d->harmonic_static ? "t" : "nil");
+    if (d->harmonic_stress) fprintf(f, " :stress t");                          /* written only when set */
+    fprintf(f, ")");
+  }
   if (d->transient_steps > 0) {                                                /* written only when asked for */
     static const char *shape[] = {"step", "ramp", "half-sine"};
     fprintf(f, "\n   (transient :steps %d :dt %.17g :shape %s :rise %.17g :zeta %.17g :static-correction %s", d->transient_steps,
             d->transient_dt, shape[d->transient_shape], d->transient_rise, d->transient_zeta, d->transient_static ? "t" : "nil");
     if (d->transient_has_base)
       fprintf(f, " :base (%.17g %.17g %.17g)", d->transient_base[0], d->transient_base[1], d->transient_base[2]);
+    if (d->transient_stress) fprintf(f, " :stress t");                         /* written only when set */
     fprintf(f, ")");
   }
   if (d->has_spectrum) {                                                       /* written only when present */

@@ -906,8 +906,11 @@ int feahip_modal_deflate(feahip_ctx *ctx, int n_locked, const double *q, const d
  * feahip_response_set_basis: installs the caller's pairs, lam[n] in any order
  * and phi[n][3N] in the caller's dof order, M-orthonormal on the caller's word
  * (no M-product is made), zeroed on the prescribed dofs, into the locked store
- * as modes of a solve with shift 0: feahip_get_locked_modes and
- * feahip_get_locked_count then return them, ascending in lam.  For modes kept
+ * as modes of a solve with shift 0, column k of the store the k-th pair by
+ * ascending lam (equal ones in the caller's order): the superposition kernels
+ * sum in column order, so the order the pairs are listed in does not reach the
+ * bits of any result.  feahip_get_locked_modes and feahip_get_locked_count then
+ * return them, ascending in lam.  For modes kept
  * from an earlier run.  Refused: the contexts feahip_solve_modes_locked refuses
  * and a context without a mass, n outside [1, 64], a lam that is not finite.
  * The block of feahip_solve_modes is scratch, as under feahip_modal_deflate.
@@ -1238,8 +1241,8 @@ int feahip_host_spectrum_form(int n_modes, const double *lam, const double *q, c
  * feahip_response_transient.  x, v, a, the time, the load factor, K, f, u, the
  * locked store, the load held and all three coefficient tables (hooks 23, 25,
  * 26) are untouched: the form table of the stresses is a buffer of its own.
- * Not offered: sharded runs, stress peaks over a whole sweep or transient in
- * one launch (feahip_response_stress_field gives single rows), principal
+ * Not offered: sharded runs (stress peaks over a whole sweep or transient in
+ * one launch are feahip_response_stress_sweep and _transient below), principal
  * stresses, a signed von Mises stress, the variation of the weights at a
  * prestressed state, superconvergent recovery.                               */
 int feahip_stress_increment(feahip_ctx *ctx, const double *du /*[3N]*/, int material, double *sig6 /*[N][6]*/);
@@ -1257,6 +1260,68 @@ int feahip_response_stress_spectrum(feahip_ctx *ctx, int n_pts, const double *w 
                                     int loglog, int rule, double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/,
                                     double zpa, double *peak6 /*[N][6]*/, double *peak_vm /*[N] or NULL; NULL with FEAHIP_ABS*/,
                                     double *modal_peak /*[n_locked] or NULL*/);
+
+/* ---- stress peaks over a frequency sweep or a transient, one launch each ----
+ * The largest stress of every node over all rows of a coefficient table, where
+ * feahip_response_stress_field gives the stress of one row.  With T_k[N][6] the
+ * stress store of feahip_response_stress_basis and T_s the stress of the
+ * static correction, components xx yy zz xy yz xz:
+ *   sweep      a_k = coef[j][0][k] + i coef[j][1][k], the table of
+ *              feahip_response_sweep:  s_c = T_s,a,c + sum_k T_k,a,c a_k
+ *   transient  the rows of feahip_response_transient at quantity 0:
+ *              sigma_c = T_s,a,c g_n + sum_k T_k,a,c a_k(n)
+ * one fma per store column in ascending column order onto the static term,
+ * the order of feahip_response_stress_field: the components of a row have the
+ * bits of that entry for (coef_row, cs).
+ *   peak6[a][c]    = max_j |s_c|   or   max_n |sigma_c|
+ *   vm[a]          = the largest von Mises stress.  Transient: of sigma,
+ *                    sqrt(1.5 (dx^2 + dy^2 + dz^2 + 2 (xy^2 + yz^2 + xz^2))) on
+ *                    the deviator d = sigma - mean.  Sweep: the largest value
+ *                    over the CYCLE of sigma(t) = re cos wt - im sin wt, which
+ *                    is not the von Mises stress of the amplitudes: with V the
+ *                    von Mises form, A = re' V re, B = im' V im, C = re' V im,
+ *                      vm^2(t) = (A + B)/2 + ((A - B)/2) cos 2wt - C sin 2wt
+ *                      vm_peak^2 = (A + B)/2 + sqrt(((A - B)/2)^2 + C^2)
+ *                    evaluated on the deviators of re and im (the expanded form
+ *                    sum p^2 - (sum p)^2 / 3 loses a nearly hydrostatic state).
+ *   peak6_at, vm_at  the lowest row that attains the peak (a strict comparison).
+ * All four in the caller's node ids.  Up to 64 probe nodes (caller's ids): the
+ * six components of every row, probe_re / probe_im [n_probe][n_freq][6] and
+ * probe [n_probe][n_steps + 1][6], summed on the host in the kernels' order:
+ * bit for bit feahip_response_stress_field of that row.
+ * k_stress_sweep / k_stress_transient (kernels_stress_sweep.hip): a lane owns
+ * a stress row and keeps its 8 P store values in registers, a wave takes ten
+ * nodes; the six lanes of a node meet across lanes for the von Mises form.
+ * The transient goes FEA_TRANSIENT_CHUNK rows at a time, each launch continuing
+ * from the peaks of the one before.  No LDS memory, no atomics, the same bits on
+ * every call.
+ * FEAHIP_EINVAL: what feahip_response_sweep and feahip_response_transient
+ * refuse, for the same arguments (n_freq outside [1, FEA_RESPONSE_MAX_FREQ], a
+ * negative or non-finite omega, a coefficient that is not finite, n_steps, dt,
+ * g, the damping), n_probe outside [0, 64], a probe node outside [0, N); a
+ * row-sharded or feahip_create_rank* context.  FEAHIP_ESTATE where
+ * feahip_response_stress_random gives it: no modes, no load, no stress store for
+ * them, a load made since.  A refused call leaves its outputs as they were.
+ * The first call allocates a coefficient table of its own (4 MB) and the two
+ * index arrays: the table of the last displacement sweep, the last chunk of the
+ * last transient and both forms stay (hooks 23, 25, 26, 28), as do x, v, a, the
+ * time, K, f and u.  Hooks 29 and 30 of feahip_time_kernel launch over the last
+ * table again.  A context that never calls these entries allocates and launches
+ * nothing for them.
+ * feahip_host_harmonic_von_mises: vm_peak of one complex stress state, the
+ * kernel's arithmetic on the host (no device).
+ * Not offered: sharded runs, principal stresses, a signed von Mises stress,
+ * stress rates (velocity, acceleration), several loads with a phase between
+ * them.                                                                       */
+int feahip_response_stress_sweep(feahip_ctx *ctx, int n_freq, const double *omega /*[n_freq]*/, double alpha, double beta_k,
+                                 const double *zeta /*[n_locked] or NULL*/, double *peak6 /*[N][6]*/, int *peak6_at /*[N][6]*/,
+                                 double *vm /*[N]*/, int *vm_at /*[N]*/, int n_probe, const int *probe_node /*[n_probe]*/,
+                                 double *probe_re /*[n_probe][n_freq][6]*/, double *probe_im /*[n_probe][n_freq][6]*/);
+int feahip_response_stress_transient(feahip_ctx *ctx, int n_steps, double dt, const double *g /*[n_steps + 1]*/, double alpha,
+                                     double beta_k, const double *zeta /*[n_locked] or NULL*/, double *peak6 /*[N][6]*/,
+                                     int *peak6_at /*[N][6]*/, double *vm /*[N]*/, int *vm_at /*[N]*/, int n_probe,
+                                     const int *probe_node /*[n_probe]*/, double *probe /*[n_probe][n_steps + 1][6]*/);
+double feahip_host_harmonic_von_mises(const double re6[6], const double im6[6]);
 
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
@@ -1612,7 +1677,12 @@ int feahip_sync(feahip_ctx *ctx);
  * nodes, into the scratch panel of the single-vector path: the stress store in
  * force is needed (FEAHIP_ESTATE without one) and is not written; 28 k_stress_combine over the form
  * of the last feahip_response_stress_combine, _random or _spectrum
- * (FEAHIP_ESTATE, "no stress form", before one).                             */
+ * (FEAHIP_ESTATE, "no stress form", before one); 29 k_stress_sweep over the
+ * table of the last feahip_response_stress_sweep and 30 one launch of
+ * k_stress_transient over the last chunk of the last
+ * feahip_response_stress_transient, as a first and last launch (FEAHIP_ESTATE,
+ * "no stress sweep" / "no stress transient", before one; only the peak buffers
+ * of the stress entries are written).                                        */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
