@@ -7,6 +7,8 @@
 //                     s = sum_j wt_j S_j w_j^(2p),  a(w_j) the row of response_coefficients -- that very code, so out_i^2 is
 //                   the trapezoid rule of S |(i w)^p u_i(w)|^2 over the fields feahip_response_field returns.
 //                   b = 0 and s = 0 without the static correction
+//   moment_form     the same form with the weight wt_j S_j w_j^n, n in {0, 1, 2, 4}: the spectral moment m_n of every linear
+//                   combination of the response (the orders 0, 2, 4 are random_form at quantity 0, 1, 2, bit for bit)
 //   random_grid     a grid that resolves every peak: a uniform background, and per damped mode the points
 //                   w_k + (d_k / 2) tan(theta), theta uniform in (-pi / 2, pi / 2) -- the substitution that makes a
 //                   Lorentzian of half width d_k / 2 flat
@@ -30,14 +32,16 @@ int response_coefficients(int n_modes, const double *lam, const double *q, const
 
 static double to_double(long double v) { return fabsl(v) <= 1.7976931348623157e308L ? (double)v : (v != v ? NAN : (v > 0 ? HUGE_VAL : -HUGE_VAL)); }
 
-int random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
-                double beta, const double *zeta, int correction, int quantity, double *C, double *b, double *s, std::string *why)
+// the form with the weight wt_j S_j w_j^order: order 2 p is the quantity p of random_form, order 1 the first spectral
+// moment.  w^order is taken as order / 2 factors w^2 and then one w for an odd order, so the even orders keep the bits
+// random_form always gave
+static int weighted_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
+                         double beta, const double *zeta, int correction, int order, double *C, double *b, double *s, std::string *why)
 {
   auto refuse = [&](const std::string &t) { if (why) *why = t; return FEAHIP_EINVAL; };
   if (n_modes < 1 || n_modes > ML) return refuse("the number of modes must be in [1, 64]");
   if (n_freq < 2 || n_freq > FEA_RANDOM_MAX_FREQ) return refuse("n_freq must be in [2, " + std::to_string(FEA_RANDOM_MAX_FREQ) + "]");
   if (!lam || !q || !omega || !S || !C || !b || !s) return refuse("null argument");
-  if (quantity < 0 || quantity > 2) return refuse("quantity must be 0 (displacement), 1 (velocity) or 2 (acceleration)");
   for (int j = 0; j < n_freq; ++j) {
     if (!(omega[j] >= 0.0) || !std::isfinite(omega[j])) return refuse("omega must be finite and not negative");
     if (j > 0 && !(omega[j] > omega[j - 1])) return refuse("omega must be strictly ascending");
@@ -56,7 +60,8 @@ int random_form(int n_modes, const double *lam, const double *q, int n_freq, con
       const long double lo = j > 0 ? omega[j - 1] : omega[0], hi = j + 1 < n_freq ? omega[j + 1] : omega[n_freq - 1];
       const long double w = omega[j];
       long double g = 0.5L * (hi - lo) * (long double)S[j];
-      for (int e = 0; e < quantity; ++e) g *= w * w;
+      for (int e = 0; e < order / 2; ++e) g *= w * w;
+      if (order & 1) g *= w;
       if (g == 0.0L) continue;
       const double *re = coef.data() + (size_t)r * 2 * ML, *im = re + ML;
       for (int k = 0; k < n; ++k) {
@@ -79,6 +84,26 @@ int random_form(int n_modes, const double *lam, const double *q, int n_freq, con
     if (!std::isfinite(b[k])) return refuse("the form is not finite");
   if (!std::isfinite(*s)) return refuse("the form is not finite");
   return FEAHIP_OK;
+}
+
+int random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
+                double beta, const double *zeta, int correction, int quantity, double *C, double *b, double *s, std::string *why)
+{
+  if (quantity < 0 || quantity > 2) {
+    if (why) *why = "quantity must be 0 (displacement), 1 (velocity) or 2 (acceleration)";
+    return FEAHIP_EINVAL;
+  }
+  return weighted_form(n_modes, lam, q, n_freq, omega, S, alpha, beta, zeta, correction, 2 * quantity, C, b, s, why);
+}
+
+int moment_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
+                double beta, const double *zeta, int correction, int order, double *C, double *b, double *s, std::string *why)
+{
+  if (order != 0 && order != 1 && order != 2 && order != 4) {
+    if (why) *why = "the order of a spectral moment must be 0, 1, 2 or 4";
+    return FEAHIP_EINVAL;
+  }
+  return weighted_form(n_modes, lam, q, n_freq, omega, S, alpha, beta, zeta, correction, order, C, b, s, why);
 }
 
 // d_k in long double, as transient_table.cpp takes it; FEAHIP_EINVAL for what the sweep refuses of the damping
@@ -186,6 +211,13 @@ extern "C" int feahip_host_random_form(int n_modes, const double *lam, const dou
                                        int quantity, double *C, double *b, double *s)
 {
   return random_form(n_modes, lam, q, n_freq, omega, S, alpha, beta_k, zeta, static_correction, quantity, C, b, s, nullptr);
+}
+
+extern "C" int feahip_host_moment_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega,
+                                       const double *S, double alpha, double beta_k, const double *zeta, int static_correction,
+                                       int order, double *C, double *b, double *s)
+{
+  return moment_form(n_modes, lam, q, n_freq, omega, S, alpha, beta_k, zeta, static_correction, order, C, b, s, nullptr);
 }
 
 extern "C" int feahip_host_spectrum_form(int n_modes, const double *lam, const double *q, const double *sa, double alpha,

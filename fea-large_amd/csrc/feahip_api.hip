@@ -578,6 +578,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->response.release();
   c->stress.release();
   c->buckling.release();
+  c->fatigue.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -2014,6 +2015,82 @@ extern "C" int feahip_response_stress_spectrum(feahip_ctx *c, int n_pts, const d
   return FEAHIP_OK;
 }
 
+// ---- random-vibration fatigue on the stress store (kernels_stress_fatigue.hip) ------------------------------------------
+// lib[4][N][7] (library ids) into the caller's moments[N][7][4]
+static void moments_to_caller(feahip_ctx *c, const double *lib, double *moments)
+{
+  const NodeView v = view_of(c);
+  const size_t N = (size_t)c->N;
+  for (int a = 0; a < c->N; ++a) {
+    const size_t la = (size_t)v.lib(a);
+    for (int k = 0; k < 7; ++k)
+      for (int n = 0; n < 4; ++n) moments[((size_t)a * 7 + k) * 4 + n] = lib[(n * N + la) * 7 + k];
+  }
+}
+
+extern "C" int feahip_response_stress_moments(feahip_ctx *c, const double *C4, const double *b4, const double *s4, double *moments)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_moments"))) return rc;
+  if (!C4 || !moments) { c->err = "response_stress_moments: null C4 or moments"; return FEAHIP_EINVAL; }
+  const int n = c->modal.n_locked;
+  for (int f = 0; f < 4; ++f) {
+    const double *C = C4 + (size_t)f * n * n;
+    for (int j = 0; j < n; ++j) {
+      for (int k = 0; k < n; ++k) {
+        const double v = C[(size_t)j * n + k];
+        if (!std::isfinite(v)) { c->err = "response_stress_moments: C4 is not finite"; return FEAHIP_EINVAL; }
+        if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) { c->err = "response_stress_moments: a form of C4 is not symmetric to the bit"; return FEAHIP_EINVAL; }
+        if (j != k && !std::isfinite(2.0 * v)) { c->err = "response_stress_moments: twice an entry of C4 is not finite"; return FEAHIP_EINVAL; }
+      }
+      if (b4 && !std::isfinite(b4[(size_t)f * n + j])) { c->err = "response_stress_moments: b4 is not finite"; return FEAHIP_EINVAL; }
+    }
+    if (s4 && !std::isfinite(s4[f])) { c->err = "response_stress_moments: s4 is not finite"; return FEAHIP_EINVAL; }
+  }
+  std::vector<double> lib(28 * (size_t)c->N);
+  if ((rc = stress_moments(c, C4, b4, s4, lib.data()))) return rc;
+  moments_to_caller(c, lib.data(), moments);
+  return FEAHIP_OK;
+}
+
+extern "C" int feahip_response_stress_fatigue(feahip_ctx *c, int n_freq, const double *omega, const double *S, double alpha,
+                                              double beta_k, const double *zeta, double sn_b, double sn_a, double *moments,
+                                              double *rates, double *damage, int *status)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_fatigue"))) return rc;
+  if (!omega || !S) { c->err = "response_stress_fatigue: null omega or S"; return FEAHIP_EINVAL; }
+  double k[5];
+  if (fatigue_constants(sn_b, sn_a, k)) {
+    c->err = "response_stress_fatigue: the S-N curve N s^b = A needs a finite b in [1, 64] and a finite A > 0";
+    return FEAHIP_EINVAL;
+  }
+  const int n = c->modal.n_locked;
+  static const int order[4] = {0, 1, 2, 4};
+  std::vector<double> C4(4 * (size_t)n * n), b4(4 * (size_t)n);
+  double s4[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int f = 0; f < 4; ++f) {
+    std::string why;
+    if (moment_form(n, c->modal.lam, c->response.q, n_freq, omega, S, alpha, beta_k, zeta, c->response.correction, order[f],
+                    C4.data() + (size_t)f * n * n, b4.data() + (size_t)f * n, &s4[f], &why)) {
+      c->err = "response_stress_fatigue: " + why;
+      return FEAHIP_EINVAL;
+    }
+  }
+  const size_t N = (size_t)c->N;
+  std::vector<double> lm(moments ? 28 * N : 0), lr(rates ? 14 * N : 0), ld(damage ? 21 * N : 0);
+  std::vector<int> ls(status ? 7 * N : 0);
+  if ((rc = stress_moments(c, C4.data(), b4.data(), s4, moments ? lm.data() : nullptr)) ||
+      (rc = stress_fatigue_rates(c, k, rates ? lr.data() : nullptr, damage ? ld.data() : nullptr, status ? ls.data() : nullptr))) return rc;
+  if (moments) moments_to_caller(c, lm.data(), moments);
+  if (rates) to_caller(view_of(c), 14, 14, lr.data(), rates);
+  if (damage) to_caller(view_of(c), 21, 21, ld.data(), damage);
+  if (status) to_caller(view_of(c), 7, 7, ls.data(), status);
+  return FEAHIP_OK;
+}
+
 // ---- stress peaks over a sweep or a transient (kernels_stress_sweep.hip) ------------------------------------------------
 // lib[r] = the library's node of the caller's probe_node[r], each inside [0, N)
 static int probe_nodes(feahip_ctx *c, const char *who, int n_probe, const int *probe_node, int *lib)
@@ -2537,6 +2614,12 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (what == 29 && !(laid && c->stress.swept_freq > 0)) { c->err = "time_kernel: no stress sweep made yet (feahip_response_stress_sweep first)"; return FEAHIP_ESTATE; }
     if (what == 30 && !(laid && c->stress.trans_rows > 0)) { c->err = "time_kernel: no stress transient made yet (feahip_response_stress_transient first)"; return FEAHIP_ESTATE; }
   }
+  if (what == 31 || what == 32) {                      // the four forms of the last moments / the moments and the curve of the last rates
+    const int rk = stress_form_ready(c, what == 31 ? "time_kernel(31)" : "time_kernel(32)");
+    if (rk) return rk;
+    if (what == 31 && !c->fatigue.forms_set) { c->err = "time_kernel: no stress moments made yet (feahip_response_stress_moments or _fatigue first)"; return FEAHIP_ESTATE; }
+    if (what == 32 && !(c->fatigue.mom_set && c->fatigue.rates_set)) { c->err = "time_kernel: no fatigue rates made yet (feahip_response_stress_fatigue first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2565,6 +2648,8 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 27: return time_stress_store(c);
     case 28: return time_stress_combine(c);
     case 29: case 30: return time_stress_sweep_kernel(c, what);
+    case 31: return time_stress_moments(c);
+    case 32: return time_fatigue_rates(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

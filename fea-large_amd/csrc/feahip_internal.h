@@ -598,6 +598,22 @@ struct BucklingState {
   void release() { dev_free({d_rec, d_kg_base, d_x4}); *this = BucklingState(); }
 };
 
+// random-vibration fatigue on the stress store (kernels_stress_fatigue.hip): nothing of it exists until a fatigue entry is
+// called.  It reads the stress store and T_s of StressState; a new stress basis drops what it holds (stress_basis).
+struct FatigueState {
+  double *d_forms = nullptr;           // [4][FEA_COMBINE_TABLE] the four forms of the last moments, folded as StressState::d_form
+  double *d_mom = nullptr;             // [4][N][7] the moments of order 0, 1, 2, 4: six components, then the von Mises process
+  double *d_rates = nullptr;           // [N][7][2] nu0, nup
+  double *d_damage = nullptr;          // [N][7][3] narrow band, Dirlik, Tovo-Benasciutti, per unit time
+  int *d_status = nullptr;             // [N][7] the bits FEA_FATIGUE_* of fatigue_point.h
+  double consts[5] = {0};              // the S-N curve of the last rates (fatigue_constants)
+  bool forms_set = false;              // d_forms holds four forms for the stress store in force (feahip_time_kernel 31) ...
+  bool mom_set = false;                // ... d_mom their moments ...
+  bool rates_set = false;              // ... and consts a curve (feahip_time_kernel 32)
+  void drop() { forms_set = mom_set = rates_set = false; }
+  void release() { dev_free({d_forms, d_mom, d_rates, d_damage, d_status}); *this = FatigueState(); }
+};
+
 struct feahip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -743,6 +759,7 @@ struct feahip_ctx {
   ResponseState response;
   StressState stress;
   BucklingState buckling;
+  FatigueState fatigue;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -926,6 +943,16 @@ int stress_transient(feahip_ctx *c, int n_steps, double dt, const double *g, dou
                      double *h_peak6, int *h_at6, double *h_vm, int *h_vmat, int n_probe, const int *probe, double *h_probe);
 double harmonic_von_mises(const double re6[6], const double im6[6]);    // host only: the cycle peak, the kernel's arithmetic
 int time_stress_sweep_kernel(feahip_ctx *c, int what);                  // feahip_time_kernel 29 (sweep), 30 (transient)
+// kernels_stress_fatigue.hip -- four forms on the nine combinations of every node in one launch, and the fatigue statistics
+// of the seven processes per node; every host array in library ids, null where not wanted
+int stress_moments(feahip_ctx *c, const double *C4, const double *b4, const double *s4, double *h_mom /*[4][N][7]*/);
+int stress_fatigue_rates(feahip_ctx *c, const double *k /*[5] fatigue_constants*/, double *h_rates /*[N][7][2]*/,
+                         double *h_damage /*[N][7][3]*/, int *h_status /*[N][7]*/);
+int time_stress_moments(feahip_ctx *c);                                 // feahip_time_kernel 31
+int time_fatigue_rates(feahip_ctx *c);                                  // feahip_time_kernel 32
+// fatigue_table.cpp -- k[5] = b, 1 / A, Gamma(1 + b), Gamma(1 + b / 2), 2^(b / 2) of the S-N curve N s^b = A, made in long
+// double; FEAHIP_EINVAL for b outside [1, 64], A not positive, either not finite
+int fatigue_constants(double sn_b, double sn_a, double *k);
 // combine_table.cpp -- the forms of a PSD and of a response spectrum, host only, in long double.  Mode k of the arrays is
 // row and column k of C[n_modes][n_modes] and entry k of b; FEAHIP_EINVAL and *why for what the entries refuse
 int random_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
@@ -933,6 +960,9 @@ int random_form(int n_modes, const double *lam, const double *q, int n_freq, con
 int spectrum_form(int n_modes, const double *lam, const double *q, const double *sa, double alpha, double beta, const double *zeta,
                   int rule, int correction, double zpa, int quantity, double *C, double *b, double *s, double *a /*[n_modes] the peak
                   modal values, or null*/, std::string *why);
+int moment_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S, double alpha,
+                double beta, const double *zeta, int correction, int order /*0, 1, 2 or 4*/, double *C, double *b, double *s,
+                std::string *why);
 // kernels_buckling.hip -- K_sigma as one double per block, and the lowest eigenpairs of K_sigma phi = nu K phi
 int geom_assemble(feahip_ctx *c);                                       // buckling.d_kg at the current nodes
 int buckling_solve(feahip_ctx *c, int n_modes, double tol, int max_it, double *nu, double *resid, int *iters);

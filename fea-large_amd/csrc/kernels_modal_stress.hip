@@ -304,6 +304,7 @@ int stress_basis(feahip_ctx *c, int material)
   int rc;
   S.have = false;
   S.form_set = false;
+  c->fatigue.drop();                                                   // (the moments were those of the old store)
   if ((rc = stress_ensure(c))) return rc;
   const int panels = panels_of(c);
   if (panels > S.store_panels) {

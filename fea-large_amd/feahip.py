@@ -204,6 +204,12 @@ ABI = {
     "feahip_host_spectrum_value": [C.c_int, _dp, _dp, C.c_int, C.c_double],
     "feahip_host_spectrum_form": [C.c_int, _dp, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
                                   _dp, _dp, _dp],
+    "feahip_host_moment_form": [C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_int, _dp, _dp,
+                                _dp],
+    "feahip_host_fatigue": [C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, _ip],
+    "feahip_response_stress_moments": [C.c_void_p, _dp, _dp, _dp, _dp],
+    "feahip_response_stress_fatigue": [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double, _dp,
+                                       _dp, _dp, _ip],
     "feahip_solve_buckling": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
     "feahip_get_buckling_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_geometric_spmv": [C.c_void_p, _dp, _dp],
@@ -272,6 +278,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("random_sn_exponent", C.c_double), ("random_sn_coefficient", C.c_double), ("random_duration", C.c_double),
         ("harmonic_stress", C.c_int), ("transient_stress", C.c_int),
         ("spectrum_stress", C.c_int), ("random_stress", C.c_int),
         ("has_spectrum", C.c_int), ("spectrum_count", C.c_int), ("spectrum_points", _dp), ("spectrum_rule", C.c_int),
@@ -447,6 +454,43 @@ def host_random_form(lam, q, omega, S, alpha=0.0, beta=0.0, zeta=None, static_co
     if rc != 0:
         raise FeaHipError(f"feahip_host_random_form refused its input ({rc})")
     return Cm, b, s.value
+
+
+def host_moment_form(lam, q, omega, S, alpha=0.0, beta=0.0, zeta=None, static_correction=True, order=0):
+    """feahip_host_moment_form (no device): (C[n][n], b[n], s) of the spectral moment m_order = integral of w^order G(w) dw of
+    every linear combination of the response, order in (0, 1, 2, 4): host_random_form with the weight wt_j S_j w_j^order.  The
+    orders 0, 2, 4 are that entry at quantity 0, 1, 2, bit for bit.  Raises where the entry refuses."""
+    lam, q, z = _modal_arrays(lam, q, zeta)
+    omega, S = np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+    assert omega.ndim == 1 and omega.shape == S.shape
+    n = len(lam)
+    Cm, b, s = np.zeros((n, n)), np.zeros(n), C.c_double(0)
+    rc = load_library().feahip_host_moment_form(n, _d(lam), _d(q), len(omega), _d(omega), _d(S), float(alpha), float(beta),
+                                                None if z is None else _d(z), int(bool(static_correction)), int(order),
+                                                _d(Cm), _d(b), C.byref(s))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_moment_form refused its input ({rc})")
+    return Cm, b, s.value
+
+
+FATIGUE_NO_STRESS, FATIGUE_NARROW, FATIGUE_NO_DIRLIK = 1, 2, 4      # the status bits of csrc/fatigue_point.h
+FATIGUE_DAMAGE = ("narrow-band", "dirlik", "tovo-benasciutti")      # the last axis of a damage array
+
+
+def host_fatigue(m, sn_exponent, sn_coefficient):
+    """feahip_host_fatigue (no device): (rates[...][2], damage[...][3], status[...]) of the moments m[...][4] = (m0, m1, m2,
+    m4) on the S-N curve N s^b = A (s the stress amplitude), in long double and rounded once: nu0 and nup in cycles per
+    unit time, the damage per unit time by the narrow-band formula, Dirlik and Tovo-Benasciutti, the status bits
+    FATIGUE_*.  Raises where the entry refuses (b outside [1, 64], A <= 0, a moment negative or not finite)."""
+    m = np.ascontiguousarray(m, dtype=np.float64)
+    assert m.ndim >= 1 and m.shape[-1] == 4
+    lead = m.shape[:-1]
+    n = int(np.prod(lead, dtype=np.int64))
+    rates, damage, status = np.zeros(lead + (2,)), np.zeros(lead + (3,)), np.zeros(lead, dtype=np.int32)
+    rc = load_library().feahip_host_fatigue(n, _d(m), float(sn_exponent), float(sn_coefficient), _d(rates), _d(damage), _i(status))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_fatigue refused its input ({rc})")
+    return rates, damage, status
 
 
 def host_random_grid(lam, alpha=0.0, beta=0.0, zeta=None, w_lo=0.0, w_hi=1.0, n_background=257, n_per_mode=64, breakpoints=()):
@@ -743,6 +787,17 @@ class Deck:
                 raise ValueError("spectrum_zpa needs spectrum_static and a rule other than abs")
             if self.spectrum_stress and self.spectrum_rule == "abs":
                 raise ValueError("spectrum_stress needs a rule other than abs")
+        # :sn-exponent b :sn-coefficient A :duration T inside (random ...): fatigue of the von Mises process on N s^b = A over T
+        self.random_sn_exponent = float(kw.get("random_sn_exponent", 0.0))
+        self.random_sn_coefficient = float(kw.get("random_sn_coefficient", 0.0))
+        self.random_duration = float(kw.get("random_duration", 1.0))
+        if self.random_sn_exponent:
+            if not len(self.random_points):
+                raise ValueError("random_sn_exponent needs random_points")
+            if not (1.0 <= self.random_sn_exponent <= 64.0 and 0.0 < self.random_sn_coefficient < np.inf and 0.0 < self.random_duration < np.inf):
+                raise ValueError("random_sn_exponent: 1 to 64, random_sn_coefficient and random_duration: positive and finite")
+        elif self.random_sn_coefficient or self.random_duration != 1.0:
+            raise ValueError("random_sn_coefficient and random_duration need random_sn_exponent")
         if len(self.random_points) and not (0 <= self.random_per_mode <= 4096 and 2 <= self.random_background <= 131072):
             raise ValueError("random_per_mode: 0 to 4096, random_background: 2 to 131072")
         # (buckling :modes N :tolerance t :max M): the load factors feasolver_hip computes after its last step
@@ -823,7 +878,9 @@ class Deck:
                         random_interp="loglog" if fd.random_loglog else "linear", random_per_mode=fd.random_per_mode,
                         random_background=fd.random_background,
                         random_base=[fd.random_base[k] for k in range(3)] if fd.random_has_base else None,
-                        random_stress=bool(fd.random_stress))
+                        random_stress=bool(fd.random_stress),
+                        **(dict(random_sn_exponent=fd.random_sn_exponent, random_sn_coefficient=fd.random_sn_coefficient,
+                                random_duration=fd.random_duration) if fd.random_sn_exponent else {}))
                    if fd.has_random else {}),
                 **(dict(buckling_modes=fd.buckling_modes, buckling_tolerance=fd.buckling_tolerance,
                         buckling_max=fd.buckling_max) if fd.buckling_modes else {}))
@@ -906,6 +963,9 @@ class Deck:
             fd.random_static, fd.random_loglog, fd.random_zeta = int(bool(self.random_static)), int(self.random_interp == "loglog"), self.random_zeta
             fd.random_per_mode, fd.random_background = int(self.random_per_mode), int(self.random_background)
             fd.random_stress = int(bool(getattr(self, "random_stress", False)))
+            if getattr(self, "random_sn_exponent", 0.0):
+                fd.random_sn_exponent, fd.random_sn_coefficient = self.random_sn_exponent, self.random_sn_coefficient
+                fd.random_duration = self.random_duration
             if self.random_base is not None:
                 fd.random_has_base = 1
                 for k in range(3):
@@ -1555,6 +1615,38 @@ class FeaSolver:
         self._chk(self._lib.feahip_response_stress_random(self._ctx, len(omega), _d(omega), _d(S), float(alpha), float(beta),
                                                           zp, _d(rms6), _d(vm), _d(cov)))
         return rms6, vm, cov
+
+    def response_stress_moments(self, C4, b4=None, s4=None):
+        """feahip_response_stress_moments: moments[N][7][4], four forms (C4[k], b4[k], s4[k]) on the six stress components and
+        on the von Mises combination of the nine forms of every node, in one launch: max(0, form), no root.  b4 and s4, or
+        single entries of them, may be None: zero."""
+        n = self._held()
+        Cm = np.ascontiguousarray(C4, dtype=np.float64)
+        assert Cm.ndim == 3 and Cm.shape[0] == 4 and (n is None or Cm.shape[1:] == (n, n))
+        m = Cm.shape[1]
+        bb = None if b4 is None else np.ascontiguousarray([np.zeros(m) if b is None else np.asarray(b, dtype=np.float64) for b in b4])
+        ss = None if s4 is None else np.ascontiguousarray([0.0 if v is None else float(v) for v in s4], dtype=np.float64)
+        assert (bb is None or bb.shape == (4, m)) and (ss is None or ss.shape == (4,))
+        mom = np.zeros((self.ndof // 3, 7, 4))
+        self._chk(self._lib.feahip_response_stress_moments(self._ctx, _d(Cm), None if bb is None else _d(bb),
+                                                           None if ss is None else _d(ss), _d(mom)))
+        return mom
+
+    def response_stress_fatigue(self, omega, S, alpha=0.0, beta=0.0, zeta=None, sn_exponent=3.0, sn_coefficient=1.0):
+        """feahip_response_stress_fatigue: (moments[N][7][4], rates[N][7][2], damage[N][7][3], status[N][7]) under the load
+        held times a load factor of one-sided PSD S(omega): the spectral moments m0, m1, m2, m4 of the six stress components
+        and of the equivalent von Mises process, nu0 and nup in cycles per unit time, the damage per unit time on the
+        S-N curve N s^b = A (s the stress amplitude) by FATIGUE_DAMAGE, and the status bits FATIGUE_*."""
+        omega, S = np.ascontiguousarray(omega, dtype=np.float64), np.ascontiguousarray(S, dtype=np.float64)
+        assert omega.ndim == 1 and omega.shape == S.shape
+        n = self._held()
+        N = self.ndof // 3
+        mom, rates, damage, status = np.zeros((N, 7, 4)), np.zeros((N, 7, 2)), np.zeros((N, 7, 3)), np.zeros((N, 7), dtype=np.int32)
+        z, zp = (None, None) if n is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_stress_fatigue(self._ctx, len(omega), _d(omega), _d(S), float(alpha), float(beta), zp,
+                                                           float(sn_exponent), float(sn_coefficient), _d(mom), _d(rates),
+                                                           _d(damage), _i(status)))
+        return mom, rates, damage, status
 
     def response_stress_spectrum(self, w, sa, rule=SRSS, alpha=0.0, beta=0.0, zeta=None, zpa=0.0, loglog=False, von_mises=None):
         """feahip_response_stress_spectrum: (peak6[N][6], the peak von Mises stress [N] or None, the peak modal values)

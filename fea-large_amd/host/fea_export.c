@@ -506,6 +506,28 @@ int fea_random_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *m
     if (!rc && msh_path) rc = append_scalar(msh_path, d, "RMS von Mises stress", vm);
     free(p6);
   }
+  if (!rc && d->random_sn_exponent > 0) {               /* :sn-exponent b: fatigue of the von Mises process on the same modes, load and grid */
+    const size_t N = (size_t)d->nodes_count;
+    double *rates = (double *)malloc(sizeof(double) * (14 + 21 + 2) * N), *damage, *dk, *nu0;
+    int node = 0;
+    if (!rates) { free(F); free(w); free(omega); return FEAHIP_ENOMEM; }
+    damage = rates + 14 * N; dk = damage + 21 * N; nu0 = dk + N;
+    rc = feahip_response_stress_basis(ctx, -1);
+    if (!rc) rc = feahip_response_stress_fatigue(ctx, n_grid, omega, Sw, alpha, beta, d->random_zeta > 0 ? zeta : NULL, d->random_sn_exponent,
+                                                 d->random_sn_coefficient, NULL, rates, damage, NULL);
+    for (i = 0; !rc && i < d->nodes_count; ++i) {       /* process 6: von Mises; damage 1: Dirlik */
+      dk[i] = d->random_duration * damage[((size_t)i * 7 + 6) * 3 + 1];
+      nu0[i] = rates[((size_t)i * 7 + 6) * 2];
+    }
+    if (!rc && log) {
+      best = largest_of(dk, d->nodes_count, &node);
+      fprintf(log, "Random fatigue: damage = %.17g (Dirlik), node %d, nu0 = %.17g, life = %.17g\n", best, node + 1, nu0[node],
+              d->random_duration / best);
+    }
+    if (!rc && msh_path) rc = append_scalar(msh_path, d, "Fatigue damage (Dirlik)", dk);
+    if (!rc && msh_path) rc = append_scalar(msh_path, d, "Zero-upcrossing rate", nu0);
+    free(rates);
+  }
   free(F); free(w); free(omega);
   return rc;
 }

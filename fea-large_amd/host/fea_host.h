@@ -112,6 +112,16 @@ typedef struct fea_deck {
    * sweep feasolver_hip runs fea_transient_run.  Written by fea_deck_save only when n > 0: a deck without the section is
    * read, run and written as before.  The fields are the newest of the struct and stand in front of harmonic_count,
    * whose place (with everything behind it) the host tests pin                                                     */
+  /* :sn-exponent b :sn-coefficient A :duration T inside (random ...), flat keys as :stress t is: random-vibration fatigue of the
+   * equivalent von Mises process on the S-N curve N s^b = A (s the stress amplitude), 1 <= b <= 64, A > 0, over the
+   * duration T > 0 (1 where absent).  The exponent turns the analysis on and needs the coefficient; the other two are refused
+   * without it.  After the RMS results fea_random_run calls feahip_response_stress_basis and
+   * feahip_response_stress_fatigue on the same modes, load and grid, logs the largest Dirlik damage T D_DK with its node,
+   * its nu0 and the life 1 / D_DK, and appends two $NodeData sections, "Fatigue damage (Dirlik)" (T D_DK) and
+   * "Zero-upcrossing rate".  random_sn_exponent = 0: off.  Written by fea_deck_save only when set: a deck without the keys is
+   * read, run and written as before.  The three fields are the newest of the struct and stand in front of the two of the
+   * next comment                                                                                                       */
+  double random_sn_exponent, random_sn_coefficient, random_duration;
   /* :stress t inside (harmonic ...) and (transient ...): after the displacement peaks, the largest von Mises stress of every
    * node over the sweep (over the cycle and the frequencies) or over the history, on the same modes and load
    * (feahip_response_stress_basis, then feahip_response_stress_sweep or _transient), one more log line and one more

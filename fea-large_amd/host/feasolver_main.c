@@ -29,7 +29,10 @@
  * feahip_response_stress_spectrum, feahip_response_stress_random); :stress t
  * in (harmonic ...) or (transient ...) likewise adds the largest von Mises
  * stress of every node over the sweep or the history
- * (feahip_response_stress_sweep, feahip_response_stress_transient).  A deck with
+ * (feahip_response_stress_sweep, feahip_response_stress_transient);
+ * :sn-exponent b :sn-coefficient A :duration T in (random ...) adds the fatigue
+ * of the von Mises process, one log line with the largest Dirlik damage and
+ * two fields (feahip_response_stress_fatigue).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid

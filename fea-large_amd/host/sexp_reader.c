@@ -825,6 +825,16 @@ static int read_list(reader *r, fea_deck *d)
     if (read_base(r, a, na, &d->random_has_base, d->random_base, "random :base takes three finite numbers, not all zero")) return -1;
     d->random_stress = 0;
     if (read_flag(r, a, na, "stress", &d->random_stress, "random :stress takes t or nil")) return -1;
+    d->random_sn_exponent = d->random_sn_coefficient = 0; d->random_duration = 1;
+    if (attr_get(a, na, "sn-exponent")) {
+      if (need_num(r, a, na, "sn-exponent", &d->random_sn_exponent)) return -1;
+      if (!(d->random_sn_exponent >= 1 && d->random_sn_exponent <= 64)) return fail(r, "random :sn-exponent must be in [1, 64]");
+      if (need_num(r, a, na, "sn-coefficient", &d->random_sn_coefficient)) return -1;
+      if (!(d->random_sn_coefficient > 0 && d->random_sn_coefficient <= 1.7976931348623157e308)) return fail(r, "random :sn-coefficient must be positive and finite");
+      if (attr_get(a, na, "duration") && need_num(r, a, na, "duration", &d->random_duration)) return -1;
+      if (!(d->random_duration > 0 && d->random_duration <= 1.7976931348623157e308)) return fail(r, "random :duration must be positive and finite");
+    } else if (attr_get(a, na, "sn-coefficient") || attr_get(a, na, "duration"))
+      return fail(r, "random :sn-coefficient and :duration need :sn-exponent");
     if (d->random_count < 2) return fail(r, "random needs (psd (f s) ...) with two points at least");
     d->has_random = 1;
   } else if (ieq(head, "buckling")) {                         /* no counterpart in the reference */
@@ -956,6 +966,7 @@ void fea_deck_free(fea_deck *d)
   free(d->spectrum_points); free(d->random_points);
   d->spectrum_points = d->random_points = NULL; d->spectrum_count = d->random_count = d->has_spectrum = d->has_random = 0;
   d->spectrum_stress = d->random_stress = d->harmonic_stress = d->transient_stress = 0;
+  d->random_sn_exponent = d->random_sn_coefficient = d->random_duration = 0;
   free(d->material_params); free(d->element_material);
   d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
@@ -1037,6 +1048,8 @@ int fea_deck_save(const char *path, const fea_deck *d)
     if (d->random_has_base)
       fprintf(f, " :base (%.17g %.17g %.17g)", d->random_base[0], d->random_base[1], d->random_base[2]);
     if (d->random_stress) fprintf(f, " :stress t");
+    if (d->random_sn_exponent > 0)                                             /* written only when set */
+      fprintf(f, " :sn-exponent %.17g :sn-coefficient %.17g :duration %.17g", d->random_sn_exponent, d->random_sn_coefficient, d->random_duration);
     fprintf(f, "\n    (psd");
     for (i = 0; i < d->random_count; ++i) fprintf(f, " (%.17g %.17g)", d->random_points[2 * i], d->random_points[2 * i + 1]);
     fprintf(f, "))");

@@ -1323,6 +1323,67 @@ int feahip_response_stress_transient(feahip_ctx *ctx, int n_steps, double dt, co
                                      const int *probe_node /*[n_probe]*/, double *probe /*[n_probe][n_steps + 1][6]*/);
 double feahip_host_harmonic_von_mises(const double re6[6], const double im6[6]);
 
+/* ---- random-vibration fatigue: spectral moments, rates and damage per node ----
+ * A part under random vibration is qualified on fatigue life.  Seven stress
+ * processes per node: the six components xx yy zz xy yz xz, and as the seventh
+ * the equivalent von Mises process of Preumont and Piefort, whose PSD is
+ * trace(V G_sigma(w)): its moments are the von Mises combination of the nine
+ * forms, (q(xx-yy) + q(yy-zz) + q(zz-xx)) / 2 + 3 (q(xy) + q(yz) + q(xz)),
+ * evaluated as k_stress_combine evaluates it.
+ *   moments  m_n = integral of w^n G(w) dw, n = 0, 1, 2, 4, w in rad per unit
+ *            time, by the trapezoid rule of feahip_host_random_form with the
+ *            weight wt_j S_j w_j^n (feahip_host_moment_form: order 0, 2, 4 are
+ *            that entry at quantity 0, 1, 2 bit for bit; it refuses what that
+ *            entry refuses, and any other order).  A moment is max(0, form):
+ *            sqrt(m0) has the bits of feahip_response_stress_random.
+ *   rates    nu0 = sqrt(m2 / m0) / 2 pi (zero up-crossings) and nup =
+ *            sqrt(m4 / m2) / 2 pi (peaks), cycles per unit time; 0 where a
+ *            moment under the root is 0.
+ *   damage   per unit time on the S-N curve N s^b = A, s the stress
+ *            AMPLITUDE, 1 <= b <= 64, A > 0, by three estimators: [0] narrow
+ *            band, (nu0 / A) (2 m0)^(b/2) Gamma(1 + b/2); [1] Dirlik's density
+ *            in closed form; [2] Tovo and Benasciutti, [bw + (1 - bw)
+ *            alpha2^(b - 1)] D_NB, with alpha1 = m1 / sqrt(m0 m2) and alpha2 =
+ *            m2 / sqrt(m0 m4) clamped to [0, 1] (csrc/fatigue_point.h has every
+ *            formula, one copy for the device and the host).
+ *   status   bit 0: m0 = 0 or m2 = 0 (no stress: a node outside the material of
+ *            the stress basis), every rate and damage 0; bit 1: 1 - alpha2 <=
+ *            1e-6, the narrow-band limit, where Dirlik's parameters leave their
+ *            range: the three damages are equal; bit 2: Dirlik's parameters are
+ *            no density (one not finite, a negative weight, Q <= 0): [1] takes
+ *            the value of [2].  No value is NaN for finite input.
+ * feahip_response_stress_moments: four forms of the caller's own, C4[4][n][n],
+ * b4[4][n] and s4[4] by ascending mode as feahip_response_stress_combine takes
+ * one (b4, s4 NULL: zero), evaluated on the nine combinations of every node in
+ * ONE launch (k_stress_moments, the form as the grid's second dimension).
+ * feahip_response_stress_fatigue: the four forms of feahip_host_moment_form on
+ * the load held, then k_fatigue_rates, a lane per (node, process) pair; any of
+ * the four outputs may be NULL.  feahip_host_fatigue: the statistics of n sets
+ * of moments in long double, rounded once (no device): the reference of the
+ * kernel, and an entry for moments of the caller's own; rates, damage, status
+ * may be NULL; FEAHIP_EINVAL for a moment that is negative or not finite.
+ * Both device entries need what feahip_response_stress_random needs and refuse
+ * what it refuses, with the same codes; FEAHIP_EINVAL for b outside [1, 64], A
+ * not positive, either not finite.  K, f, u, x, v, a, the time, the tables of
+ * the sweeps and both forms (hooks 26, 28) stay: the four tables are a buffer
+ * of their own.  No atomics, the same bits on every call; a context that never
+ * calls these entries allocates and launches nothing for them.
+ * Not offered: sharded runs, a mean-stress correction, multi-slope S-N curves,
+ * rainflow counting of a transient, the expected extreme over a duration,
+ * principal or signed von Mises stress, several loads with cross-spectra.    */
+int feahip_host_moment_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S,
+                            double alpha, double beta_k, const double *zeta /*[n_modes] or NULL*/, int static_correction,
+                            int order /*0, 1, 2 or 4*/, double *C /*[n_modes][n_modes]*/, double *b /*[n_modes]*/, double *s);
+int feahip_host_fatigue(int n, const double *m /*[n][4]: m0, m1, m2, m4*/, double sn_b, double sn_a, double *rates /*[n][2] or NULL*/,
+                        double *damage /*[n][3] or NULL*/, int *status /*[n] or NULL*/);
+int feahip_response_stress_moments(feahip_ctx *ctx, const double *C4 /*[4][n_locked][n_locked]*/,
+                                   const double *b4 /*[4][n_locked] or NULL*/, const double *s4 /*[4] or NULL*/,
+                                   double *moments /*[N][7][4]*/);
+int feahip_response_stress_fatigue(feahip_ctx *ctx, int n_freq, const double *omega /*[n_freq]*/, const double *S /*[n_freq]*/,
+                                   double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/, double sn_b, double sn_a,
+                                   double *moments /*[N][7][4] or NULL*/, double *rates /*[N][7][2] or NULL*/,
+                                   double *damage /*[N][7][3] or NULL*/, int *status /*[N][7] or NULL*/);
+
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
  *     K_sigma(x) phi = nu K(x) phi          on the free dofs,
@@ -1682,7 +1743,12 @@ int feahip_sync(feahip_ctx *ctx);
  * k_stress_transient over the last chunk of the last
  * feahip_response_stress_transient, as a first and last launch (FEAHIP_ESTATE,
  * "no stress sweep" / "no stress transient", before one; only the peak buffers
- * of the stress entries are written).                                        */
+ * of the stress entries are written); 31 k_stress_moments over the four forms
+ * of the last feahip_response_stress_moments or _fatigue and 32 k_fatigue_rates
+ * over the last moments and the S-N curve of the last
+ * feahip_response_stress_fatigue (FEAHIP_ESTATE, "no stress moments" / "no
+ * fatigue rates", before one; only the buffers of the fatigue entries are
+ * written).                                                                  */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
