@@ -579,6 +579,7 @@ extern "C" void feahip_destroy(feahip_ctx *c)
   c->stress.release();
   c->buckling.release();
   c->fatigue.release();
+  c->rainflow.release();
   void *ptrs[] = {c->d_table, c->d_conn, c->d_X0, c->d_x, c->d_rowptr, c->d_colidx, c->d_K_alloc, c->d_Kstash_alloc,
                   c->d_chunk, c->d_diag, c->d_f, c->d_u, c->d_r, c->d_p,
                   c->d_q, c->d_minv, c->d_part, c->d_scal, c->d_flag, c->d_cdof, c->d_cval,
@@ -2163,6 +2164,46 @@ extern "C" int feahip_response_stress_transient(feahip_ctx *c, int n_steps, doub
   return FEAHIP_OK;
 }
 
+// ---- rainflow counting of a transient (kernels_stress_rainflow.hip) --------------------------------------------------------
+extern "C" int feahip_response_stress_rainflow(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta_k,
+                                               const double *zeta, double sn_b, double sn_a, int depth, int n_proj,
+                                               const double *proj, double *damage, double *cycles, double *max_range, int *status,
+                                               int *depth_used, int n_probe, const int *probe_node, double *probe)
+{
+  CTX_GUARD_NOK(c);
+  int rc;
+  if ((rc = stress_form_ready(c, "response_stress_rainflow"))) return rc;
+  if (!g) { c->err = "response_stress_rainflow: null g"; return FEAHIP_EINVAL; }
+  if (n_steps < 1 || n_steps > FEA_TRANSIENT_MAX_STEPS) { c->err = "response_stress_rainflow: n_steps must be in [1, 1048576]"; return FEAHIP_EINVAL; }
+  if (n_probe < 0 || n_probe > 64) { c->err = "response_stress_rainflow: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
+  if (n_probe > 0 && (!probe_node || !probe)) { c->err = "response_stress_rainflow: null probe arrays"; return FEAHIP_EINVAL; }
+  if (!rainflow_arguments(sn_b, sn_a, depth)) {
+    c->err = "response_stress_rainflow: the S-N curve N s^b = A needs a finite b in [1, 64] and a finite A > 0, the stack a depth in [4, 1024]";
+    return FEAHIP_EINVAL;
+  }
+  if (n_proj < 0 || n_proj > FEA_RAINFLOW_MAX_PROJ) { c->err = "response_stress_rainflow: n_proj must be in [0, 48]"; return FEAHIP_EINVAL; }
+  if (n_proj > 0 && !proj) { c->err = "response_stress_rainflow: null proj"; return FEAHIP_EINVAL; }
+  for (int e = 0; e < 6 * n_proj; ++e)
+    if (!std::isfinite(proj[e])) { c->err = "response_stress_rainflow: proj is not finite"; return FEAHIP_EINVAL; }
+  int lib_probe[64];
+  if ((rc = probe_nodes(c, "response_stress_rainflow", n_probe, probe_node, lib_probe))) return rc;
+  const int W = 6 + n_proj;
+  const size_t NW = (size_t)c->N * W;
+  std::vector<double> ld(damage ? NW : 0), lc(cycles ? NW : 0), lr(max_range ? NW : 0);
+  std::vector<int> ls(status ? NW : 0), lu(depth_used ? NW : 0);
+  std::vector<double> hist((size_t)n_probe * ((size_t)n_steps + 1) * W);  // (the caller's arrays stay as they are on a refusal)
+  if ((rc = stress_rainflow(c, n_steps, dt, g, alpha, beta_k, zeta, sn_b, sn_a, depth, n_proj, proj, damage ? ld.data() : nullptr,
+                            cycles ? lc.data() : nullptr, max_range ? lr.data() : nullptr, status ? ls.data() : nullptr,
+                            depth_used ? lu.data() : nullptr, n_probe, lib_probe, hist.data()))) return rc;
+  if (damage) to_caller(view_of(c), W, W, ld.data(), damage);
+  if (cycles) to_caller(view_of(c), W, W, lc.data(), cycles);
+  if (max_range) to_caller(view_of(c), W, W, lr.data(), max_range);
+  if (status) to_caller(view_of(c), W, W, ls.data(), status);
+  if (depth_used) to_caller(view_of(c), W, W, lu.data(), depth_used);
+  std::copy(hist.begin(), hist.end(), probe);
+  return FEAHIP_OK;
+}
+
 extern "C" double feahip_host_harmonic_von_mises(const double re6[6], const double im6[6])
 {
   return harmonic_von_mises(re6, im6);
@@ -2620,6 +2661,11 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     if (what == 31 && !c->fatigue.forms_set) { c->err = "time_kernel: no stress moments made yet (feahip_response_stress_moments or _fatigue first)"; return FEAHIP_ESTATE; }
     if (what == 32 && !(c->fatigue.mom_set && c->fatigue.rates_set)) { c->err = "time_kernel: no fatigue rates made yet (feahip_response_stress_fatigue first)"; return FEAHIP_ESTATE; }
   }
+  if (what == 33) {                                    // the last chunk of the last stress rainflow, its curve and its depth
+    const int rk = stress_form_ready(c, "time_kernel(33)");
+    if (rk) return rk;
+    if (!(c->rainflow.table_gen == c->modal.lock_gen && c->rainflow.rows > 0 && c->rainflow.d_stack && c->rainflow.depth <= c->rainflow.depth_cap)) { c->err = "time_kernel: no stress rainflow made yet (feahip_response_stress_rainflow first)"; return FEAHIP_ESTATE; }
+  }
   if (what == 12) { const int rk = launch_results(c, -1, c->d_scal + 8); if (rk) return rk; }   // (allocates on first use)
   if (what == 5 && c->surf.nfaces == 0) { c->err = "time_kernel(5): no surface loads on this context"; return FEAHIP_EINVAL; }
   if (what == 20 && c->contact.n == 0) { c->err = "time_kernel(20): no contact on this context"; return FEAHIP_EINVAL; }
@@ -2650,6 +2696,7 @@ extern "C" int feahip_time_kernel(feahip_ctx *c, int what, int warmup, int iters
     case 29: case 30: return time_stress_sweep_kernel(c, what);
     case 31: return time_stress_moments(c);
     case 32: return time_fatigue_rates(c);
+    case 33: return time_rainflow_kernel(c);
     default: c->err = "unknown kernel selector"; return FEAHIP_EINVAL;
     }
   });

@@ -614,6 +614,23 @@ struct FatigueState {
   void release() { dev_free({d_forms, d_mom, d_rates, d_damage, d_status}); *this = FatigueState(); }
 };
 
+// rainflow counting of a transient on the stress store (kernels_stress_rainflow.hip): nothing of it exists until
+// feahip_response_stress_rainflow is called.  It reads the stress store and T_s of StressState and has a coefficient chunk
+// of its own, so the tables of the other entries stay.
+struct RainflowBuffers {
+  double *d_coef = nullptr;            // [FEA_TRANSIENT_CHUNK][64] the rows of a chunk, then its g[FEA_TRANSIENT_CHUNK]
+  double *d_proj = nullptr;            // [FEA_RAINFLOW_MAX_PROJ][6] the projections of the last call
+  double *d_stack = nullptr;           // [depth_cap][6N] the ring of every stress row, slot by slot
+  double *d_real = nullptr;            // [4][6N] per row: the last kept sample, the damage, the cycles, the largest range
+  int *d_int = nullptr;                // [6][6N] per row: direction, base, count, depth used, status, seen
+  int depth_cap = 0;                   // slots d_stack is allocated for
+  int depth = 0;                       // the depth of the last call ...
+  double sn[2] = {0, 0};               // ... its b and 1 / A ...
+  int rows = 0, step0 = 0;             // ... and the rows of its last chunk in d_coef (feahip_time_kernel 33)
+  int table_gen = -1;                  // the filling of the locked store d_coef was laid out for
+  void release() { dev_free({d_coef, d_proj, d_stack, d_real, d_int}); *this = RainflowBuffers(); }
+};
+
 struct feahip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -760,6 +777,7 @@ struct feahip_ctx {
   StressState stress;
   BucklingState buckling;
   FatigueState fatigue;
+  RainflowBuffers rainflow;
 };
 
 // calls f(std::integral_constant<bool, DOK>, std::integral_constant<bool, DOF>) for the assembly asked for: K and f,
@@ -950,6 +968,14 @@ int stress_fatigue_rates(feahip_ctx *c, const double *k /*[5] fatigue_constants*
                          double *h_damage /*[N][7][3]*/, int *h_status /*[N][7]*/);
 int time_stress_moments(feahip_ctx *c);                                 // feahip_time_kernel 31
 int time_fatigue_rates(feahip_ctx *c);                                  // feahip_time_kernel 32
+// kernels_stress_rainflow.hip -- the rainflow count of every stress row and of n_proj projections over a transient: the five
+// outputs [N][6 + n_proj] in library ids (null where not wanted), the probes (library node ids) [n_probe][rows][6 + n_proj]
+int stress_rainflow(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta, const double *zeta,
+                    double sn_b, double sn_a, int depth, int n_proj, const double *proj, double *h_damage, double *h_cycles,
+                    double *h_range, int *h_status, int *h_used, int n_probe, const int *probe, double *h_probe);
+int time_rainflow_kernel(feahip_ctx *c);                                // feahip_time_kernel 33
+// rainflow_table.cpp -- false for what the rainflow entries refuse of the S-N curve and the ring
+bool rainflow_arguments(double sn_b, double sn_a, int depth);
 // fatigue_table.cpp -- k[5] = b, 1 / A, Gamma(1 + b), Gamma(1 + b / 2), 2^(b / 2) of the S-N curve N s^b = A, made in long
 // double; FEAHIP_EINVAL for b outside [1, 64], A not positive, either not finite
 int fatigue_constants(double sn_b, double sn_a, double *k);

@@ -210,6 +210,9 @@ ABI = {
     "feahip_response_stress_moments": [C.c_void_p, _dp, _dp, _dp, _dp],
     "feahip_response_stress_fatigue": [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double, _dp,
                                        _dp, _dp, _ip],
+    "feahip_host_rainflow": [C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _ip, _ip, C.c_int, _ip, _dp, _dp, _dp],
+    "feahip_response_stress_rainflow": [C.c_void_p, C.c_int, C.c_double, _dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double,
+                                        C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, C.c_int, _ip, _dp],
     "feahip_solve_buckling": [C.c_void_p, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp, _ip],
     "feahip_get_buckling_modes": [C.c_void_p, C.c_int, C.c_int, _dp],
     "feahip_geometric_spmv": [C.c_void_p, _dp, _dp],
@@ -278,6 +281,7 @@ class FeaDeck(C.Structure):
         ("has_body_force", C.c_int), ("body_force", C.c_double * 3),
         ("dynamics_explicit", C.c_int), ("dynamics_safety", C.c_double), ("dynamics_restep", C.c_int),
         ("results_nodal_stress", C.c_int), ("results_energy", C.c_int), ("results_reactions", C.c_int),
+        ("transient_sn_exponent", C.c_double), ("transient_sn_coefficient", C.c_double), ("transient_rainflow_depth", C.c_int),
         ("random_sn_exponent", C.c_double), ("random_sn_coefficient", C.c_double), ("random_duration", C.c_double),
         ("harmonic_stress", C.c_int), ("transient_stress", C.c_int),
         ("spectrum_stress", C.c_int), ("random_stress", C.c_int),
@@ -491,6 +495,46 @@ def host_fatigue(m, sn_exponent, sn_coefficient):
     if rc != 0:
         raise FeaHipError(f"feahip_host_fatigue refused its input ({rc})")
     return rates, damage, status
+
+
+RAINFLOW_MAX_DEPTH = 1024                               # FEA_RAINFLOW_MAX_DEPTH of include/fea_hip.h
+RAINFLOW_MAX_PROJ = 48                                  # FEA_RAINFLOW_MAX_PROJ
+RAINFLOW_CONSTANT, RAINFLOW_OVERFLOW = 1, 2             # the status bits of csrc/rainflow_point.h
+
+
+def host_rainflow(series, sn_exponent, sn_coefficient, depth=32):
+    """feahip_host_rainflow (no device): the rainflow count of one history by ASTM E1049-85's three-point rule on a ring of
+    `depth` points, as a dict: damage (Miner's sum of count (range / 2)^b / A on the S-N curve N s^b = A, summed in long
+    double and rounded once), cycles, max_range, depth_used, status (the bits RAINFLOW_*), and the counted cycles in
+    counting order as ranges, means, counts.  Raises where the entry refuses (no sample, a sample that is not finite, b
+    outside [1, 64], A <= 0, depth outside [4, RAINFLOW_MAX_DEPTH])."""
+    x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
+    n = len(x)
+    cap = max(n, 1)
+    dmg, cyc, rng = C.c_double(0), C.c_double(0), C.c_double(0)
+    used, status, counted = C.c_int(0), C.c_int(0), C.c_int(0)
+    r, m, k = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+    rc = load_library().feahip_host_rainflow(n, _d(x), float(sn_exponent), float(sn_coefficient), int(depth), C.byref(dmg),
+                                             C.byref(cyc), C.byref(rng), C.byref(used), C.byref(status), cap, C.byref(counted),
+                                             _d(r), _d(m), _d(k))
+    if rc != 0:
+        raise FeaHipError(f"feahip_host_rainflow refused its input ({rc})")
+    c = counted.value
+    return dict(damage=dmg.value, cycles=cyc.value, max_range=rng.value, depth_used=used.value, status=status.value,
+                ranges=r[:c].copy(), means=m[:c].copy(), counts=k[:c].copy())
+
+
+def plane_projections(normals):
+    """The rows [n][6] that project a stress state (xx, yy, zz, xy, yz, xz) onto the normal stress n' sigma n of the planes
+    with the normals given: (nx^2, ny^2, nz^2, 2 nx ny, 2 ny nz, 2 nx nz) of the normalised normals -- the `projections`
+    of FeaSolver.response_stress_rainflow."""
+    nn = np.atleast_2d(np.asarray(normals, dtype=np.float64))
+    assert nn.ndim == 2 and nn.shape[1] == 3
+    length = np.sqrt((nn * nn).sum(axis=1))
+    assert np.all(length > 0) and np.all(np.isfinite(length))
+    u = nn / length[:, None]
+    x, y, z = u[:, 0], u[:, 1], u[:, 2]
+    return np.ascontiguousarray(np.stack([x * x, y * y, z * z, 2 * x * y, 2 * y * z, 2 * x * z], axis=1))
 
 
 def host_random_grid(lam, alpha=0.0, beta=0.0, zeta=None, w_lo=0.0, w_hi=1.0, n_background=257, n_per_mode=64, breakpoints=()):
@@ -723,6 +767,18 @@ class Deck:
         self.transient_stress = bool(kw.get("transient_stress", False))        # :stress t: the peak von Mises stress as well
         if self.transient_stress and not self.transient_steps:
             raise ValueError("transient_stress needs transient_steps")
+        # :sn-exponent b :sn-coefficient A :rainflow-depth d inside (transient ... :stress t): the rainflow count on N s^b = A
+        self.transient_sn_exponent = float(kw.get("transient_sn_exponent", 0.0))
+        self.transient_sn_coefficient = float(kw.get("transient_sn_coefficient", 0.0))
+        self.transient_rainflow_depth = int(kw.get("transient_rainflow_depth", 32))
+        if self.transient_sn_exponent:
+            if not self.transient_stress:
+                raise ValueError("transient_sn_exponent needs transient_stress")
+            if not (1.0 <= self.transient_sn_exponent <= 64.0 and 0.0 < self.transient_sn_coefficient < np.inf
+                    and 4 <= self.transient_rainflow_depth <= 1024):
+                raise ValueError("transient_sn_exponent: 1 to 64, transient_sn_coefficient: positive and finite, transient_rainflow_depth: 4 to 1024")
+        elif self.transient_sn_coefficient or self.transient_rainflow_depth != 32:
+            raise ValueError("transient_sn_coefficient and transient_rainflow_depth need transient_sn_exponent")
         if not 0 <= self.transient_steps <= TRANSIENT_MAX_STEPS:
             raise ValueError("transient_steps: 1 to 1048576")
         if self.transient_steps:
@@ -865,7 +921,9 @@ class Deck:
                         transient_static=bool(fd.transient_static), transient_shape=TRANSIENT_SHAPES[fd.transient_shape],
                         transient_rise=fd.transient_rise,
                         transient_base=[fd.transient_base[k] for k in range(3)] if fd.transient_has_base else None,
-                        transient_stress=bool(fd.transient_stress))
+                        transient_stress=bool(fd.transient_stress),
+                        **(dict(transient_sn_exponent=fd.transient_sn_exponent, transient_sn_coefficient=fd.transient_sn_coefficient,
+                                transient_rainflow_depth=fd.transient_rainflow_depth) if fd.transient_sn_exponent else {}))
                    if fd.transient_steps else {}),
                 **(dict(spectrum_points=np.ctypeslib.as_array(fd.spectrum_points, (fd.spectrum_count, 2)).copy(),
                         spectrum_rule=SPECTRUM_RULES[fd.spectrum_rule], spectrum_zeta=fd.spectrum_zeta, spectrum_zpa=fd.spectrum_zpa,
@@ -945,6 +1003,9 @@ class Deck:
             fd.transient_static, fd.transient_shape = int(bool(self.transient_static)), TRANSIENT_SHAPES.index(self.transient_shape)
             fd.transient_rise = float(self.transient_rise)
             fd.transient_stress = int(bool(getattr(self, "transient_stress", False)))
+            if getattr(self, "transient_sn_exponent", 0.0):
+                fd.transient_sn_exponent, fd.transient_sn_coefficient = self.transient_sn_exponent, self.transient_sn_coefficient
+                fd.transient_rainflow_depth = self.transient_rainflow_depth
             if self.transient_base is not None:
                 fd.transient_has_base = 1
                 for k in range(3):
@@ -1694,6 +1755,30 @@ class FeaSolver:
         self._chk(self._lib.feahip_response_stress_transient(self._ctx, len(g) - 1, float(dt), _d(g), float(alpha), float(beta),
                                                              zp, _d(peak6), _i(at6), _d(vm), _i(vat), len(pr), _i(pr), _d(hist)))
         return peak6, at6, vm, vat, hist
+
+    # ---- rainflow counting of a transient ----------------------------------------
+    def response_stress_rainflow(self, g, dt, alpha=0.0, beta=0.0, zeta=None, sn_exponent=3.0, sn_coefficient=1.0, depth=32,
+                                 projections=None, probes=()):
+        """feahip_response_stress_rainflow under the load held times g(t), g[n_steps + 1] at t_n = n dt: the rainflow count
+        of the six stress components of every node and of the linear projections given ([n_proj][6], plane_projections
+        makes those of planes), as a dict of damage, cycles, max_range, status, depth_used, each [N][6 + n_proj], and
+        probes, the histories [n_probe][n_steps + 1][6 + n_proj] of the probe nodes.  Damage is Miner's sum on the S-N curve
+        N s^b = A (s the stress amplitude); status has the bits RAINFLOW_*."""
+        g = np.ascontiguousarray(np.atleast_1d(g), dtype=np.float64)
+        pr = np.ascontiguousarray(probes, dtype=np.int32).reshape(-1)
+        pj = None if projections is None else np.ascontiguousarray(projections, dtype=np.float64)
+        assert pj is None or (pj.ndim == 2 and pj.shape[1] == 6)
+        n_proj = 0 if pj is None else pj.shape[0]
+        N, W = self.ndof // 3, 6 + n_proj
+        damage, cycles, max_range = np.zeros((N, W)), np.zeros((N, W)), np.zeros((N, W))
+        status, used = np.zeros((N, W), dtype=np.int32), np.zeros((N, W), dtype=np.int32)
+        hist = np.zeros((len(pr), len(g), W))
+        z, zp = (None, None) if self._held() is None else self._zeta(zeta)
+        self._chk(self._lib.feahip_response_stress_rainflow(self._ctx, len(g) - 1, float(dt), _d(g), float(alpha), float(beta), zp,
+                                                            float(sn_exponent), float(sn_coefficient), int(depth), n_proj,
+                                                            None if n_proj == 0 else _d(pj), _d(damage), _d(cycles),
+                                                            _d(max_range), _i(status), _i(used), len(pr), _i(pr), _d(hist)))
+        return dict(damage=damage, cycles=cycles, max_range=max_range, status=status, depth_used=used, probes=hist)
 
     # ---- linear buckling ---------------------------------------------------
     def solve_buckling(self, n_modes, tolerance=1e-8, max_iterations=2000, check=True):

@@ -233,6 +233,36 @@ static int stress_peak_run(const fea_deck *d, feahip_ctx *ctx, FILE *log, const 
   return rc;
 }
 
+/* :sn-exponent b of (transient ... :stress t): the rainflow count of the six components of every node over the history on
+ * the stress store stress_peak_run made, one log line (two if a stack overflowed) and one $NodeData section */
+static int rainflow_run(const fea_deck *d, feahip_ctx *ctx, FILE *log, const char *msh_path, int n, const double *g, double dt,
+                        const double *zeta)
+{
+  const size_t N = (size_t)d->nodes_count;
+  const double alpha = d->has_dynamics ? d->damping_alpha : 0.0, beta = d->has_dynamics ? d->damping_beta : 0.0;
+  double *dmg = (double *)malloc(sizeof(double) * 13 * N), *cyc, *top, best = -1.0;
+  int *st = (int *)malloc(sizeof(int) * 6 * N), rc, over = 0, at = 0;
+  size_t i;
+  if (!dmg || !st) { free(dmg); free(st); return FEAHIP_ENOMEM; }
+  cyc = dmg + 6 * N; top = dmg + 12 * N;
+  rc = feahip_response_stress_rainflow(ctx, n, dt, g, alpha, beta, zeta, d->transient_sn_exponent, d->transient_sn_coefficient,
+                                       d->transient_rainflow_depth, 0, NULL, dmg, cyc, NULL, st, NULL, 0, NULL, NULL);
+  if (!rc) {
+    for (i = 0; i < 6 * N; ++i) {                        /* the largest damage (the lowest row among equals), per node the largest of six */
+      if (dmg[i] > best) { best = dmg[i]; at = (int)i; }
+      if (i % 6 == 0 || dmg[i] > top[i / 6]) top[i / 6] = dmg[i];
+      over += (st[i] & FEAHIP_RAINFLOW_OVERFLOW) != 0;
+    }
+    if (log) {
+      fprintf(log, "Transient fatigue: damage = %.17g (rainflow), node %d, component %d, cycles = %.17g\n", best, at / 6 + 1, at % 6, cyc[at]);
+      if (over) fprintf(log, "Transient fatigue: %d of %d stress rows overflowed the stack of %d points\n", over, (int)(6 * N), d->transient_rainflow_depth);
+    }
+    if (msh_path) rc = append_scalar(msh_path, d, "Fatigue damage (rainflow)", top);
+  }
+  free(dmg); free(st);
+  return rc;
+}
+
 int fea_harmonic_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char *msh_path)
 {
   FILE *log = (FILE *)log_, *f;
@@ -352,6 +382,8 @@ int fea_transient_run(const fea_deck *d, feahip_ctx *ctx, void *log_, const char
     fclose(f);
   }
   if (d->transient_stress) rc = stress_peak_run(d, ctx, log, msh_path, n, NULL, g, d->transient_dt, d->transient_zeta > 0 ? zeta : NULL);
+  if (!rc && d->transient_stress && d->transient_sn_exponent > 0)
+    rc = rainflow_run(d, ctx, log, msh_path, n, g, d->transient_dt, d->transient_zeta > 0 ? zeta : NULL);
   free(F); free(g); free(at);
   return rc;
 }

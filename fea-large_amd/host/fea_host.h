@@ -112,6 +112,17 @@ typedef struct fea_deck {
    * sweep feasolver_hip runs fea_transient_run.  Written by fea_deck_save only when n > 0: a deck without the section is
    * read, run and written as before.  The fields are the newest of the struct and stand in front of harmonic_count,
    * whose place (with everything behind it) the host tests pin                                                     */
+  /* :sn-exponent b :sn-coefficient A :rainflow-depth d inside (transient ... :stress t), flat keys: the rainflow count of the six
+   * stress components of every node over the history and Miner's sum on the S-N curve N s^b = A (s the stress amplitude),
+   * 1 <= b <= 64, A > 0, on a stack of d points, 4 <= d <= FEA_RAINFLOW_MAX_DEPTH (32 where absent).  The exponent turns the
+   * analysis on and needs the coefficient and :stress t; the other two are refused without it.  After the von Mises peaks
+   * fea_transient_run calls feahip_response_stress_rainflow, logs the largest damage with its node, its component and its
+   * cycles (and how many rows overflowed the stack, if any did) and appends "Fatigue damage (rainflow)", the largest of the
+   * six components per node.  transient_sn_exponent = 0: off.  Written by fea_deck_save only when set: a deck without the
+   * keys is read, run and written as before.  The three fields are the newest of the struct and stand in front of the
+   * three of the next comment                                                                                          */
+  double transient_sn_exponent, transient_sn_coefficient;
+  int transient_rainflow_depth;
   /* :sn-exponent b :sn-coefficient A :duration T inside (random ...), flat keys as :stress t is: random-vibration fatigue of the
    * equivalent von Mises process on the S-N curve N s^b = A (s the stress amplitude), 1 <= b <= 64, A > 0, over the
    * duration T > 0 (1 where absent).  The exponent turns the analysis on and needs the coefficient; the other two are refused

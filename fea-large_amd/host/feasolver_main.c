@@ -32,7 +32,10 @@
  * (feahip_response_stress_sweep, feahip_response_stress_transient);
  * :sn-exponent b :sn-coefficient A :duration T in (random ...) adds the fatigue
  * of the von Mises process, one log line with the largest Dirlik damage and
- * two fields (feahip_response_stress_fatigue).  A deck with
+ * two fields (feahip_response_stress_fatigue); :sn-exponent b
+ * :sn-coefficient A :rainflow-depth d in (transient ... :stress t) adds the
+ * rainflow count of the history, one log line with the largest Miner damage
+ * and one field (feahip_response_stress_rainflow).  A deck with
  * (buckling :modes N ...) then gets its N lowest buckling load factors in the
  * log and their mode shapes in the file (feahip_solve_buckling).  A deck
  * with a (contact ...) section presses its contact faces against rigid

@@ -778,6 +778,20 @@ static int read_list(reader *r, fea_deck *d)
     }
     d->transient_stress = 0;
     if (read_flag(r, a, na, "stress", &d->transient_stress, "transient :stress takes t or nil")) return -1;
+    d->transient_sn_exponent = d->transient_sn_coefficient = 0; d->transient_rainflow_depth = 32;
+    if (attr_get(a, na, "sn-exponent")) {
+      if (!d->transient_stress) return fail(r, "transient :sn-exponent needs :stress t");
+      if (need_num(r, a, na, "sn-exponent", &d->transient_sn_exponent)) return -1;
+      if (!(d->transient_sn_exponent >= 1 && d->transient_sn_exponent <= 64)) return fail(r, "transient :sn-exponent must be in [1, 64]");
+      if (need_num(r, a, na, "sn-coefficient", &d->transient_sn_coefficient)) return -1;
+      if (!(d->transient_sn_coefficient > 0 && d->transient_sn_coefficient <= 1.7976931348623157e308)) return fail(r, "transient :sn-coefficient must be positive and finite");
+      if (attr_get(a, na, "rainflow-depth")) {
+        if (need_num(r, a, na, "rainflow-depth", &v)) return -1;
+        if (!(v >= 4 && v <= FEA_RAINFLOW_MAX_DEPTH) || v != (double)(int)v) return fail(r, "transient :rainflow-depth must be an integer in [4, 1024]");
+        d->transient_rainflow_depth = (int)v;
+      }
+    } else if (attr_get(a, na, "sn-coefficient") || attr_get(a, na, "rainflow-depth"))
+      return fail(r, "transient :sn-coefficient and :rainflow-depth need :sn-exponent");
   } else if (ieq(head, "spectrum")) {                         /* no counterpart in the reference */
     d->spectrum_rule = FEAHIP_SRSS; d->spectrum_zeta = 0; d->spectrum_zpa = 0; d->spectrum_static = 1; d->spectrum_loglog = 0;
     if ((s = attr_get(a, na, "rule"))) {
@@ -967,6 +981,7 @@ void fea_deck_free(fea_deck *d)
   d->spectrum_points = d->random_points = NULL; d->spectrum_count = d->random_count = d->has_spectrum = d->has_random = 0;
   d->spectrum_stress = d->random_stress = d->harmonic_stress = d->transient_stress = 0;
   d->random_sn_exponent = d->random_sn_coefficient = d->random_duration = 0;
+  d->transient_sn_exponent = d->transient_sn_coefficient = 0; d->transient_rainflow_depth = 0;
   free(d->material_params); free(d->element_material);
   d->material_params = NULL; d->element_material = NULL; d->materials_count = 0;
   d->nodes = NULL; d->elements = NULL;
@@ -1029,6 +1044,9 @@ int fea_deck_save(const char *path, const fea_deck *d)
     if (d->transient_has_base)
       fprintf(f, " :base (%.17g %.17g %.17g)", d->transient_base[0], d->transient_base[1], d->transient_base[2]);
     if (d->transient_stress) fprintf(f, " :stress t");                         /* written only when set */
+    if (d->transient_sn_exponent > 0)                                          /* written only when set */
+      fprintf(f, " :sn-exponent %.17g :sn-coefficient %.17g :rainflow-depth %d", d->transient_sn_exponent, d->transient_sn_coefficient,
+              d->transient_rainflow_depth);
     fprintf(f, ")");
   }
   if (d->has_spectrum) {                                                       /* written only when present */

@@ -1369,8 +1369,8 @@ double feahip_host_harmonic_von_mises(const double re6[6], const double im6[6]);
  * of their own.  No atomics, the same bits on every call; a context that never
  * calls these entries allocates and launches nothing for them.
  * Not offered: sharded runs, a mean-stress correction, multi-slope S-N curves,
- * rainflow counting of a transient, the expected extreme over a duration,
- * principal or signed von Mises stress, several loads with cross-spectra.    */
+ * the expected extreme over a duration, principal or signed von Mises stress,
+ * several loads with cross-spectra.                                          */
 int feahip_host_moment_form(int n_modes, const double *lam, const double *q, int n_freq, const double *omega, const double *S,
                             double alpha, double beta_k, const double *zeta /*[n_modes] or NULL*/, int static_correction,
                             int order /*0, 1, 2 or 4*/, double *C /*[n_modes][n_modes]*/, double *b /*[n_modes]*/, double *s);
@@ -1383,6 +1383,81 @@ int feahip_response_stress_fatigue(feahip_ctx *ctx, int n_freq, const double *om
                                    double alpha, double beta_k, const double *zeta /*[n_locked] or NULL*/, double sn_b, double sn_a,
                                    double *moments /*[N][7][4] or NULL*/, double *rates /*[N][7][2] or NULL*/,
                                    double *damage /*[N][7][3] or NULL*/, int *status /*[N][7] or NULL*/);
+
+/* ---- rainflow fatigue of a transient: cycles and Miner damage per node ---------
+ * A part under a shock, a drop, a sine burst or any measured history is
+ * qualified on the cycles it has seen.  feahip_response_stress_rainflow counts
+ * them for every stress row of the transient of feahip_response_stress_transient
+ * in the launches that make the history: ASTM E1049-85's three-point rule,
+ * streamed a sample at a time on a bounded stack (csrc/rainflow_point.h has the
+ * rule, one copy for the device and the host).
+ *   processes  0..5 the six components xx yy zz xy yz xz: the very rows of
+ *              feahip_response_stress_transient, same table, same fma order,
+ *              the same bits.  6 + p the linear projection sum_c proj[p][c]
+ *              sigma_c, n_proj <= FEA_RAINFLOW_MAX_PROJ: the normal stress on a
+ *              plane of normal n is the row (nx^2, ny^2, nz^2, 2 nx ny, 2 ny nz,
+ *              2 nx nz), so up to 48 planes give a critical-plane search on the
+ *              normal stress.  A projection is formed on the store, one fma per
+ *              component in ascending order from 0, before the time loop.
+ *   damage     sum of count (range / 2)^b / A in counting order: Miner's sum on
+ *              the S-N curve N s^b = A, s the stress AMPLITUDE, 1 <= b <= 64,
+ *              A > 0, 1 / A made once on the host.  A whole b takes the power
+ *              by squaring and multiplying, any other by pow: the two differ
+ *              in the last bits.
+ *   cycles     the sum of the counts, a multiple of 0.5;  max_range the largest
+ *              counted range;  depth_used the most points the stack held.
+ *   status     bit 0 (FEAHIP_RAINFLOW_CONSTANT): fewer than two reversals, a
+ *              constant history (a node outside the material of the stress
+ *              basis), everything 0.  Bit 1 (FEAHIP_RAINFLOW_OVERFLOW): the stack
+ *              is a ring of `depth` points, 4 <= depth <=
+ *              FEA_RAINFLOW_MAX_DEPTH; a push onto a full ring first counts the
+ *              two oldest points as half a cycle and drops the oldest, the rule
+ *              ASTM has for the start point and the residue.  A ring-down, whose
+ *              ranges only shrink, is counted exactly at any depth; only a later
+ *              range large enough to close a dropped one makes the count
+ *              approximate.  No value is NaN for finite input.
+ * Outputs [N][6 + n_proj] in the caller's node ids, any of them NULL.  Up to 64
+ * probe nodes: their histories [n_probe][n_steps + 1][6 + n_proj], summed on the
+ * host in the kernel's order, so feahip_host_rainflow of a probe's history is
+ * the device's count of that row in everything but the rounding of the damage
+ * sum.  k_stress_rainflow (kernels_stress_rainflow.hip) has the lane layout of
+ * k_stress_transient; the stack lives in device memory as [depth][6N], depth x
+ * 6N doubles allocated by the first call and grown when a larger depth is
+ * asked.  A pass of launches counts six processes per node; the passes of the
+ * projections reuse the state of the one before.  No atomics, the same bits on
+ * every call.
+ * feahip_host_rainflow (no device): the count of one history of n samples in
+ * the same arithmetic with the damage sum in long double, and the list of the
+ * counted cycles in counting order (range, mean, count) into arrays of
+ * `capacity` entries each (any of them NULL; n is always enough); *n_counted
+ * the number counted.  FEAHIP_EINVAL for n < 1, a sample that is not finite, b,
+ * A or depth out of range, a list too short (*n_counted then holds the number
+ * needed).
+ * The device entry needs what feahip_response_stress_transient needs and refuses
+ * what it refuses, with the same codes; FEAHIP_EINVAL in addition for b, A,
+ * depth or n_proj out of range, a proj entry that is not finite, proj NULL with
+ * n_proj > 0.  A refused call leaves its outputs as they were.  x, v, a, the
+ * time, K, f, u, the locked store, the load held and every table of the other
+ * entries stay (hooks 23, 25, 26, 28, 29, 30): the coefficient chunk is a buffer
+ * of its own.  A context that never calls the entry allocates and launches
+ * nothing for it.
+ * Not offered: sharded runs, a mean-stress correction (the cycle means are in
+ * the host's list only), multi-slope S-N curves, an amplitude gate or racetrack
+ * filter, a range histogram per node, signed von Mises and principal stresses,
+ * critical planes on shear, counting the residue as a closed repeated block.  */
+#define FEA_RAINFLOW_MAX_DEPTH 1024
+#define FEA_RAINFLOW_MAX_PROJ  48
+#define FEAHIP_RAINFLOW_CONSTANT 1
+#define FEAHIP_RAINFLOW_OVERFLOW 2
+int feahip_host_rainflow(int n, const double *series /*[n]*/, double sn_b, double sn_a, int depth, double *damage, double *cycles,
+                         double *max_range, int *depth_used, int *status, int capacity, int *n_counted,
+                         double *range /*[capacity] or NULL*/, double *mean /*[capacity] or NULL*/, double *count /*[capacity] or NULL*/);
+int feahip_response_stress_rainflow(feahip_ctx *ctx, int n_steps, double dt, const double *g /*[n_steps + 1]*/, double alpha,
+                                    double beta_k, const double *zeta /*[n_locked] or NULL*/, double sn_b, double sn_a, int depth,
+                                    int n_proj, const double *proj /*[n_proj][6] or NULL*/, double *damage, double *cycles,
+                                    double *max_range /*[N][6 + n_proj] or NULL, all three*/, int *status,
+                                    int *depth_used /*[N][6 + n_proj] or NULL, both*/, int n_probe,
+                                    const int *probe_node /*[n_probe]*/, double *probe /*[n_probe][n_steps + 1][6 + n_proj]*/);
 
 /* ---- linear buckling: load factors and modes from K and its geometric part ----
  * feahip_solve_buckling: the n_modes lowest eigenpairs of
@@ -1748,7 +1823,10 @@ int feahip_sync(feahip_ctx *ctx);
  * over the last moments and the S-N curve of the last
  * feahip_response_stress_fatigue (FEAHIP_ESTATE, "no stress moments" / "no
  * fatigue rates", before one; only the buffers of the fatigue entries are
- * written).                                                                  */
+ * written); 33 one launch of k_stress_rainflow over the last chunk of the last
+ * feahip_response_stress_rainflow, the component pass as a first and last
+ * launch (FEAHIP_ESTATE, "no stress rainflow", before one or after a new
+ * filling of the store; only the buffers of that entry are written).         */
 int feahip_time_kernel(feahip_ctx *ctx, int what, int warmup, int iters,
                        double *avg_ms);
 /* Streaming copy of `bytes` bytes (16 bytes per lane, read + written counted)
