@@ -102,11 +102,8 @@ __device__ __forceinline__ GRead g_fetch_cheap(const double *sT, unsigned w)
 // one visit (element slot, local node la) to a row's diagonal block: K_aa^e = (vl + vm) g_a (x) g_a + (g_a . t_a) I,
 // symmetric: a = { 00, 01, 02, 11, 12, 22 }
 template <bool DOF>
-__device__ __forceinline__ void g_consume_diag(const double *sT, unsigned w, double (&a)[6], double (&fa)[3])
+__device__ __forceinline__ void g_apply_diag(const double2 pa, const double2 qa, const double2 za, const double2 vv, double (&a)[6], double (&fa)[3])
 {
-  const double2 *T = reinterpret_cast<const double2 *>(sT + G_SLOT(w) * GREC);
-  const int la = G_LA(w);
-  const double2 pa = T[la], qa = T[4 + la], za = T[8 + la], vv = T[12];
   const double s = vv.x + vv.y;
   const double d = pa.x * qa.x + pa.y * qa.y + za.x * za.y;
   const double h0 = s * pa.x, h1 = s * pa.y, h2 = s * za.x;
@@ -117,6 +114,13 @@ __device__ __forceinline__ void g_consume_diag(const double *sT, unsigned w, dou
     // as it was when t_a was formed (no fused multiply-add on either side): a stress-free state gives f = 0 to the bit
     fa[0] -= __dsub_rn(qa.x, __dmul_rn(vv.y, pa.x)); fa[1] -= __dsub_rn(qa.y, __dmul_rn(vv.y, pa.y)); fa[2] -= __dsub_rn(za.y, __dmul_rn(vv.y, za.x));
   }
+}
+template <bool DOF>
+__device__ __forceinline__ void g_consume_diag(const double *sT, unsigned w, double (&a)[6], double (&fa)[3])
+{
+  const double2 *T = reinterpret_cast<const double2 *>(sT + G_SLOT(w) * GREC);
+  const int la = G_LA(w);
+  g_apply_diag<DOF>(T[la], T[4 + la], T[8 + la], T[12], a, fa);
 }
 
 // residual contribution of one (element, local node) visit: -vol sigma g_a (fea_solver.c:1096-1109)
@@ -376,6 +380,80 @@ struct GMaps {
 };
 
 #define G_TASK_THREADS FEA_G_TASK_THREADS
+
+// The map words DECODED: what the words stand for, as LDS byte addresses.
+// The words hold chunk-local indices only, and most chunks run with their predecessor's words (GatherHeader::flags & 1);
+// the kernel then decoded the same words again in every chunk -- slot mask, slot x 208, two field extracts, two shifts
+// and adds per contribution, all of them inside the gather phase.  Decoded once, where the words arrive.
+// A contribution reads at three addresses: piece la, piece lb, the record (for its last piece).  The first G_DEC_FULL
+// of them have a register each and cost nothing per contribution; the others share a register between the word's two
+// entries (entry 0: the address, 18 bits; entry 1: address / 16, 14 bits: 256 KB, more than a CU has) and cost a mask, or
+// a shift and a mask.  All three in full registers spill (DESIGN.md has the counts).
+#define G_DEC_W 3                     // contribution words held decoded (a lattice needs 3); words beyond stay as they are
+#ifndef G_DEC_FULL
+#define G_DEC_FULL 1
+#endif
+#define G_DEC_RW (3 + G_DEC_FULL)     // registers per decoded word
+struct GDecoded {
+  unsigned eids, tpos;                // element lanes: the node slots; block lanes: the tile positions: as they were
+  unsigned cw[G_DEC_RW * G_DEC_W];
+  unsigned rw[FEA_G_REGW - G_DEC_W];  // the words beyond G_DEC_W, undecoded
+  unsigned kd;                        // diagonal lanes: byte offset of the row's diagonal block in the tile
+  // address F (0: piece la, 1: piece lb, 2: record) of entry E (0, 1) of word K
+  template <int K, int E, int F> __device__ __forceinline__ unsigned at() const
+  {
+    if constexpr (F < G_DEC_FULL) return cw[G_DEC_RW * K + 2 * F + E];
+    else {
+      const unsigned x = cw[G_DEC_RW * K + G_DEC_FULL + F];
+      return E ? (x >> 14) & 0x3FFF0u : x & 0x3FFFFu;
+    }
+  }
+  template <int K, int F> __device__ __forceinline__ void put(unsigned a0, unsigned a1)
+  {
+    if constexpr (F < G_DEC_FULL) { cw[G_DEC_RW * K + 2 * F] = a0; cw[G_DEC_RW * K + 2 * F + 1] = a1; }
+    else cw[G_DEC_RW * K + G_DEC_FULL + F] = a0 | (a1 << 14);
+  }
+};
+// oT: LDS address of the records (a multiple of 16, as is the record size)
+template <int K>
+__device__ __forceinline__ void g_decode_word(unsigned w, unsigned oT, bool diag_lane, GDecoded &d)
+{
+  const unsigned w0 = w & 0xFFFFu, w1 = w >> 16;
+  const unsigned r0 = oT + G_SLOT(w0) * (GREC * 8u), r1 = oT + G_SLOT(w1) * (GREC * 8u);
+  d.template put<K, 0>(r0 + G_LA(w0) * 16u, r1 + G_LA(w1) * 16u);
+  if (diag_lane) d.template put<K, 1>(0u, 0u);          // (wave-uniform) a visit has no column node
+  else d.template put<K, 1>(r0 + G_LB(w0) * 16u, r1 + G_LB(w1) * 16u);
+  d.template put<K, 2>(r0, r1);
+}
+__device__ __forceinline__ void g_decode(const GMaps &m, unsigned oT, bool diag_lane, GDecoded &d)
+{
+  d.eids = m.eids; d.tpos = m.tpos; d.kd = (unsigned)m.kd * 72u;
+#pragma unroll
+  for (int k = G_DEC_W; k < FEA_G_REGW; ++k) d.rw[k - G_DEC_W] = m.cw[k];
+  static_assert(G_DEC_W == 3, "g_decode: one line per decoded word");
+  g_decode_word<0>(m.cw[0], oT, diag_lane, d); g_decode_word<1>(m.cw[1], oT, diag_lane, d); g_decode_word<2>(m.cw[2], oT, diag_lane, d);
+}
+// g_fetch / g_consume_diag by decoded addresses: the same reads
+__device__ __forceinline__ unsigned g_lds_addr(const void *p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p; }
+__device__ __forceinline__ double2 g_piece(unsigned at, int piece)
+{
+  const g_v2d v = *(const __attribute__((address_space(3))) g_v2d *)(size_t)(at + piece * 16);
+  return make_double2(v.x, v.y);
+}
+__device__ __forceinline__ GRead g_fetch_dec(unsigned a, unsigned b, unsigned r0)
+{
+  GRead r;
+  r.pa = g_piece(a, 0);
+  r.za = make_double2(*(const __attribute__((address_space(3))) double *)(size_t)(a + 8 * 16), 0.0);     // (g_apply takes g_a.z of it, as the compiler knew)
+  r.pb = g_piece(b, 0); r.qb = g_piece(b, 4); r.zb = g_piece(b, 8);
+  r.vv = g_piece(r0, 12);
+  return r;
+}
+template <bool DOF>
+__device__ __forceinline__ void g_consume_diag_dec(unsigned a, unsigned r0, double (&dg)[6], double (&fa)[3])
+{
+  g_apply_diag<DOF>(g_piece(a, 0), g_piece(a, 4), g_piece(a, 8), g_piece(r0, 12), dg, fa);
+}
 
 template <bool DOK, bool DOF>
 __device__ __forceinline__ void g_load_maps(const GatherLayout &lay, const unsigned char *rec, int t, GMaps &m)

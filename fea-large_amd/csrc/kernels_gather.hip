@@ -45,13 +45,20 @@
 // follow the node ids and coordinates through the pipeline -- the id is requested two chunks ahead, the pair one chunk
 // ahead by the id that has arrived by then -- so the state phase waits for neither.  HET = false is the kernel as it
 // was: no further load, register or LDS byte.
-template <bool DOK, bool DOF, bool NH, bool HET>
+//
+// DEC (stiffness kernels): the map words are held decoded (GDecoded, gather_device.h) -- decoded where the words arrive,
+// which is where they are waited for anyway, and only for a chunk that requested them; a chunk that runs with its
+// predecessor's words finds the addresses where they were.  No sum changes order: K and f are the same to the bit.
+// DEC = false is the kernel as it was (FEAHIP_GATHER_DECODE=0, and the instantiations that have no registers for it).
+template <bool DOK, bool DOF, bool NH, bool HET, bool DEC>
 __global__ __launch_bounds__(FEA_G_THREADS, FEA_G_BIG ? 4 : 3)
 void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nruns)
 {
+  static_assert(DOK || !DEC, "decoded map words: the stiffness kernels only");
   extern __shared__ double2 g_smem[];
   double2 *sC = g_smem;                                       // per node slot 3 x 16 bytes: (x0,x1) (x2,X0) (X1,X2)
   double *sT = reinterpret_cast<double *>(g_smem + A.lay.max_nodes * 3);   // element records; later the K tile and the residual partials
+  const unsigned oT = g_lds_addr(sT);                         // LDS address of the records
   const int t = threadIdx.x;
 #ifdef FEAHIP_DEBUG
   unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -106,6 +113,8 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
   // flight" and the compiler waits for everything (s_waitcnt vmcnt(0)) at the top of EVERY iteration
   asm volatile("" : : "v"(mn.eids), "v"(mn.tpos), "v"(mn.cw[0]), "v"(mn.cw[1]), "v"(mn.cw[2]), "v"(mn.cw[3]), "v"(mn.cw[4]), "v"(mn.cw[5]),
                "v"(mn.vw[0]), "v"(mn.vw[1]), "v"(mn.kd), "v"(mn.vb), "v"(mn.ve), "v"(node1), "v"(gauss_w));
+  GDecoded dm;                                                // the words of the chunk being worked on, decoded
+  if constexpr (DEC) g_decode(mn, oT, wslot >= G_TASK_THREADS / 64, dm);
   G_BARRIER();
 
   for (;;) {
@@ -124,8 +133,8 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
 
     __builtin_amdgcn_s_setprio(PRIO_STATE);
     // ---- phase 1: one state evaluation per element of the chunk
-    if (t < h.nelem && m.eids != 0xFFFFFFFFu) {
-      const unsigned eids = m.eids;
+    if (t < h.nelem && (DEC ? dm.eids : m.eids) != 0xFFFFFFFFu) {
+      const unsigned eids = DEC ? dm.eids : m.eids;
       const int nd[4] = {(int)(eids & 255u), (int)((eids >> 8) & 255u), (int)((eids >> 16) & 255u), (int)(eids >> 24)};
       double xe[4][3], Xe[4][3];
 #pragma unroll
@@ -208,9 +217,18 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
       // walked as 2n entries whatever it holds (empty entries read the all-zero record)
 #define G_FETCH(w) (G_ABL(4) ? g_fetch_cheap(sT, w) : g_fetch(sT, w))
 #define G_APPLY(r) do { if (G_ABL(2)) g_apply_cheap(r, acc); else g_apply(r, acc, accd); } while (0)
+      if constexpr (DEC) {
+#define G_WORD_DEC(k) if (k < wd) { { const GRead r = g_fetch_dec(dm.template at<k, 0, 0>(), dm.template at<k, 0, 1>(), dm.template at<k, 0, 2>()); G_APPLY(r); } \
+                                   { const GRead r = g_fetch_dec(dm.template at<k, 1, 0>(), dm.template at<k, 1, 1>(), dm.template at<k, 1, 2>()); G_APPLY(r); } }
+        G_WORD_DEC(0) G_WORD_DEC(1) G_WORD_DEC(2)
+#pragma unroll
+        for (int k = G_DEC_W; k < FEA_G_REGW; ++k)
+          if (k < wd) { { const GRead r = G_FETCH(dm.rw[k - G_DEC_W] & 0xFFFFu); G_APPLY(r); } { const GRead r = G_FETCH(dm.rw[k - G_DEC_W] >> 16); G_APPLY(r); } }
+      } else {
 #pragma unroll
       for (int k = 0; k < FEA_G_REGW; ++k)
         if (k < wd) { { const GRead r = G_FETCH(m.cw[k] & 0xFFFFu); G_APPLY(r); } { const GRead r = G_FETCH(m.cw[k] >> 16); G_APPLY(r); } }
+      }
       for (int k = FEA_G_REGW; k < wd; ++k) {               // blocks with more than 12 contributions
         const unsigned w = reinterpret_cast<const unsigned *>(rec + A.lay.o_clist)[k * FEA_G_THREADS + t];
         g_consume(sT, w & 0xFFFFu, acc, accd); g_consume(sT, w >> 16, acc, accd);
@@ -220,9 +238,18 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
     double dg[6] = {0, 0, 0, 0, 0, 0};
     double fa[3] = {0, 0, 0};
     if (DOK && t >= G_TASK_THREADS && t - G_TASK_THREADS < 4 * nrows) {
+      if constexpr (DEC) {
+#define G_DIAG_DEC(k) if (k < h.ddepth) { g_consume_diag_dec<DOF>(dm.template at<k, 0, 0>(), dm.template at<k, 0, 2>(), dg, fa); \
+                                         g_consume_diag_dec<DOF>(dm.template at<k, 1, 0>(), dm.template at<k, 1, 2>(), dg, fa); }
+        G_DIAG_DEC(0) G_DIAG_DEC(1) G_DIAG_DEC(2)
+#pragma unroll
+        for (int k = G_DEC_W; k < FEA_G_REGW; ++k)
+          if (k < h.ddepth) { g_consume_diag<DOF>(sT, dm.rw[k - G_DEC_W] & 0xFFFFu, dg, fa); g_consume_diag<DOF>(sT, dm.rw[k - G_DEC_W] >> 16, dg, fa); }
+      } else {
 #pragma unroll
       for (int k = 0; k < FEA_G_REGW; ++k)
         if (k < h.ddepth) { g_consume_diag<DOF>(sT, m.cw[k] & 0xFFFFu, dg, fa); g_consume_diag<DOF>(sT, m.cw[k] >> 16, dg, fa); }
+      }
       for (int k = FEA_G_REGW; k < h.ddepth; ++k) {        // nodes with more than 48 elements around them
         const unsigned w = reinterpret_cast<const unsigned *>(rec + A.lay.o_dlist)[k * FEA_G_DIAG_LANES + t - G_TASK_THREADS];
         g_consume_diag<DOF>(sT, w & 0xFFFFu, dg, fa); g_consume_diag<DOF>(sT, w >> 16, dg, fa);
@@ -245,7 +272,8 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
     double *sK = sT + odd;
     double *sF = DOK ? sT + ((A.lay.max_tile * 9 + 3) & ~1) : sT;
     if (DOK && t < h.noffd && !G_ABL(16)) {
-      const int bpos = (int)(m.tpos & 0xFFFFu), mpos = (int)(m.tpos >> 16);
+      const unsigned tpos = DEC ? dm.tpos : m.tpos;
+      const int bpos = (int)(tpos & 0xFFFFu), mpos = (int)(tpos >> 16);
       if (bpos != 0xFFFF) {                            // (a thread slot the host left without a block)
 #pragma unroll
         for (int q = 0; q < 9; ++q) sK[bpos * 9 + q] = acc[q];
@@ -265,7 +293,7 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
         for (int q = 0; q < 3; ++q) fa[q] = g_quad_sum(fa[q]);
       }
       if ((t & 3) == 0 && t - G_TASK_THREADS < 4 * nrows) {
-        double *o = sK + m.kd * 9;
+        double *o = DEC ? reinterpret_cast<double *>(reinterpret_cast<char *>(sK) + dm.kd) : sK + m.kd * 9;
         o[0] = dg[0]; o[1] = dg[1]; o[2] = dg[2]; o[3] = dg[1]; o[4] = dg[3]; o[5] = dg[4]; o[6] = dg[2]; o[7] = dg[4]; o[8] = dg[5];
       }
     }
@@ -277,6 +305,15 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
     // prefetches themselves are younger, they were requested a state + gather phase ago, and nothing ever waits
     // for a store.
     G_STAMP(4);
+    if constexpr (DEC) {
+      // the decode IS the use of the words, and only of words that were requested: the others are dead, and so are
+      // their registers.  node1, the youngest of the prefetches, first: the wait for it covers the words.
+      asm volatile("" : : "v"(node1), "v"(hword));
+      if (!(h.flags & 1) || G_ABL(64)) {
+        asm volatile("" : : "v"(mn.eids), "v"(mn.tpos), "v"(mn.cw[0]), "v"(mn.cw[1]), "v"(mn.cw[2]), "v"(mn.cw[3]), "v"(mn.cw[4]), "v"(mn.cw[5]), "v"(mn.kd));
+        g_decode(mn, oT, wslot >= G_TASK_THREADS / 64, dm);
+      }
+    } else
     asm volatile("" : : "v"(mn.eids), "v"(mn.tpos), "v"(mn.cw[0]), "v"(mn.cw[1]), "v"(mn.cw[2]), "v"(mn.cw[3]), "v"(mn.cw[4]), "v"(mn.cw[5]),
                  "v"(mn.vw[0]), "v"(mn.vw[1]), "v"(mn.kd), "v"(mn.vb), "v"(mn.ve), "v"(node1), "v"(hword));
     if constexpr (HET) asm volatile("" : : "v"(mid1), "v"(pn.x), "v"(pn.y));
@@ -340,6 +377,13 @@ void k_assemble_gather(GatherArgs A, const int *__restrict__ run_start, int nrun
     o[7] = __builtin_amdgcn_s_memrealtime() - real0;     // ... and 100 MHz ticks: their ratio is the in-kernel clock
   }
 #endif
+}
+
+// The instantiations that hold their map words decoded: those that still fit the 128 vector registers of a 1024-thread
+// workgroup without scratch (DESIGN.md has the table).  The others run the kernel as it was.
+static constexpr bool g_has_decoded(bool K, bool F, bool NH, bool HET)
+{
+  return K && !HET && (G_DEC_FULL < 2 || NH || !F);
 }
 
 // compute units of a device: one workgroup of the gather kernel is resident on each
@@ -439,18 +483,29 @@ int launch_assemble_gather(feahip_ctx *c, bool doK, bool doF)
     A.f = c->d_f_discard;
     doF = true;
   }
-  auto launch = [&](auto K, auto F, auto M, auto H) -> int {
+  // The decoded kernel pays where the decode is shared: a chunk that requests words decodes them AND shifts and masks
+  // the packed addresses (about 40 instructions per lane more than the undecoded kernel), a chunk that keeps its
+  // predecessor's words saves about 30.  So it runs where more than half of the chunks keep their words (a lattice:
+  // 95 %) and not on a mesh whose chunks are all unlike (measured there: 1.4 % slower), which runs the kernel as it was.
+  // FEAHIP_GATHER_DECODE=0 / 1: never / wherever it is instantiated (A/B and tests only: no result changes)
+  const char *dec_env = getenv("FEAHIP_GATHER_DECODE");
+  const bool dec = dec_env ? atoi(dec_env) != 0 : 2 * g.same_words > g.nchunks;
+  auto launch = [&](auto K, auto F, auto M, auto H, auto D) -> int {
     if constexpr (H && K && !F && !M) { c->err = "gather assembly: no K-only A5 kernel with a material table"; return FEAHIP_ESTATE; }
     else {
     const int lds = K ? ldsK : ldsF;
-    FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M, H>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((k_assemble_gather<K, F, M, H>), grid, blk, lds, c->stream, A, g.d_run_start, nruns);
+    FEA_HIP_CHECK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_assemble_gather<K, F, M, H, D>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((k_assemble_gather<K, F, M, H, D>), grid, blk, lds, c->stream, A, g.d_run_start, nruns);
     return FEAHIP_OK;
     }
   };
   int rc;
   with_kf(doK, doF, [&](auto K, auto F) {
-    auto model = [&](auto H) { return nh ? launch(K, F, std::true_type(), H) : launch(K, F, std::false_type(), H); };
+    auto decoded = [&](auto M, auto H) {
+      if constexpr (g_has_decoded(K, F, M, H)) { if (dec) return launch(K, F, M, H, std::true_type()); }
+      return launch(K, F, M, H, std::false_type());
+    };
+    auto model = [&](auto H) { return nh ? decoded(std::true_type(), H) : decoded(std::false_type(), H); };
     rc = het ? model(std::true_type()) : model(std::false_type());
   });
   if (rc) return rc;
