@@ -1603,6 +1603,30 @@ static int static_correction_args(feahip_ctx *c, const std::string &who, int sol
   return FEAHIP_OK;
 }
 
+// the ranges of a sweep's n_freq and of a history's n_steps
+static int sweep_args(feahip_ctx *c, const char *who, int n_freq)
+{
+  if (n_freq >= 1 && n_freq <= FEA_RESPONSE_MAX_FREQ) return FEAHIP_OK;
+  c->err = std::string(who) + ": n_freq must be in [1, 4096]";
+  return FEAHIP_EINVAL;
+}
+
+static int history_args(feahip_ctx *c, const char *who, int n_steps)
+{
+  if (n_steps >= 1 && n_steps <= FEA_TRANSIENT_MAX_STEPS) return FEAHIP_OK;
+  c->err = std::string(who) + ": n_steps must be in [1, 1048576]";
+  return FEAHIP_EINVAL;
+}
+
+// at most 64 probes, and none of their arrays null where there are any
+template <class... A>
+static int probe_args(feahip_ctx *c, const char *who, int n_probe, const A *...arrays)
+{
+  if (n_probe < 0 || n_probe > 64) { c->err = std::string(who) + ": n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
+  if (n_probe > 0 && (... || !arrays)) { c->err = std::string(who) + ": null probe arrays"; return FEAHIP_EINVAL; }
+  return FEAHIP_OK;
+}
+
 // lib[r] = the library's dof of the caller's probe_dof[r], each inside [0, 3N)
 static int probe_dofs(feahip_ctx *c, const char *who, int n_probe, const int *probe_dof, int *lib)
 {
@@ -1652,12 +1676,10 @@ extern "C" int feahip_response_sweep(feahip_ctx *c, int n_freq, const double *om
   CTX_GUARD_NOK(c);
   if (!omega || !peak || !peak_at) { c->err = "response_sweep: null omega, peak or peak_at"; return FEAHIP_EINVAL; }
   int rc;
-  if ((rc = response_loaded(c, "response_sweep"))) return rc;
-  if (n_freq < 1 || n_freq > FEA_RESPONSE_MAX_FREQ) { c->err = "response_sweep: n_freq must be in [1, 4096]"; return FEAHIP_EINVAL; }
-  if (n_probe < 0 || n_probe > 64) { c->err = "response_sweep: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
-  if (n_probe > 0 && (!probe_dof || !probe_re || !probe_im)) { c->err = "response_sweep: null probe arrays"; return FEAHIP_EINVAL; }
   int probe[64];
-  if ((rc = probe_dofs(c, "response_sweep", n_probe, probe_dof, probe))) return rc;
+  if ((rc = response_loaded(c, "response_sweep")) || (rc = sweep_args(c, "response_sweep", n_freq)) ||
+      (rc = probe_args(c, "response_sweep", n_probe, probe_dof, probe_re, probe_im)) ||
+      (rc = probe_dofs(c, "response_sweep", n_probe, probe_dof, probe))) return rc;
   std::vector<double> pk((size_t)c->ndof);
   std::vector<int> at((size_t)c->ndof);
   if ((rc = response_sweep(c, false, n_freq, omega, alpha, beta_k, zeta, pk.data(), at.data(), n_probe, probe, probe_re, probe_im))) return rc;
@@ -1729,9 +1751,7 @@ extern "C" int feahip_response_transient(feahip_ctx *c, int n_steps, double dt, 
   int rc;
   if ((rc = solve2_refused(c, "response_transient")) || (rc = response_loaded(c, "response_transient"))) return rc;
   if (!g || !peak || !peak_at) { c->err = "response_transient: null g, peak or peak_at"; return FEAHIP_EINVAL; }
-  if (n_steps < 1 || n_steps > FEA_TRANSIENT_MAX_STEPS) { c->err = "response_transient: n_steps must be in [1, 1048576]"; return FEAHIP_EINVAL; }
-  if (n_probe < 0 || n_probe > 64) { c->err = "response_transient: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
-  if (n_probe > 0 && (!probe_dof || !probe)) { c->err = "response_transient: null probe arrays"; return FEAHIP_EINVAL; }
+  if ((rc = history_args(c, "response_transient", n_steps)) || (rc = probe_args(c, "response_transient", n_probe, probe_dof, probe))) return rc;
   if (n_snap < 0 || n_snap > 4096) { c->err = "response_transient: n_snap must be in [0, 4096]"; return FEAHIP_EINVAL; }
   if (n_snap > 0 && (!snap_step || !snap)) { c->err = "response_transient: null snapshot arrays"; return FEAHIP_EINVAL; }
   int lib_probe[64];
@@ -1778,23 +1798,80 @@ static int combine_to_caller(feahip_ctx *c, const double *C, const double *b, do
   return FEAHIP_OK;
 }
 
+// A caller's form (C[n][n], b[n] or null, s or null): finite, C symmetric to the bit, and finite still when an entry off
+// the diagonal is doubled (folded_form).  The arrays are called C, b and s with `suffix` behind them, C in the symmetry
+// text `sym`
+static int form_args(feahip_ctx *c, const char *who, const char *suffix, const char *sym, int n, const double *C, const double *b,
+                     const double *s)
+{
+  auto refuse = [&](const std::string &what) { c->err = std::string(who) + ": " + what; return FEAHIP_EINVAL; };
+  const std::string x = suffix;
+  for (int j = 0; j < n; ++j) {
+    for (int k = 0; k < n; ++k) {
+      const double v = C[(size_t)j * n + k];
+      if (!std::isfinite(v)) return refuse("C" + x + " is not finite");
+      if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) return refuse(std::string(sym) + " is not symmetric to the bit");
+      if (j != k && !std::isfinite(2.0 * v)) return refuse("twice an entry of C" + x + " is not finite");
+    }
+    if (b && !std::isfinite(b[j])) return refuse("b" + x + " is not finite");
+  }
+  if (s && !std::isfinite(*s)) return refuse("s" + x + " is not finite");
+  return FEAHIP_OK;
+}
+
+// The form of random vibration on the modes and the load held (random_form), handed to emit(C, b, s, absx); the modal
+// covariance to the caller, if asked for, once emit is through
+template <class Emit>
+static int random_on_held(feahip_ctx *c, const char *who, int n_freq, const double *omega, const double *S, double alpha,
+                          double beta_k, const double *zeta, int quantity, double *modal_cov, Emit emit)
+{
+  const int n = c->modal.n_locked;
+  std::vector<double> C((size_t)n * n), b(n);
+  double s = 0.0;
+  std::string why;
+  if (random_form(n, c->modal.lam, c->response.q, n_freq, omega, S, alpha, beta_k, zeta, c->response.correction, quantity,
+                  C.data(), b.data(), &s, &why)) {
+    c->err = std::string(who) + ": " + why;
+    return FEAHIP_EINVAL;
+  }
+  if (const int rc = emit(C.data(), b.data(), s, false)) return rc;
+  if (modal_cov) std::copy(C.begin(), C.end(), modal_cov);
+  return FEAHIP_OK;
+}
+
+// The same for a response spectrum (spectrum_form on the spectrum's value at every mode held) and the modal peaks.  The
+// stress entry passes its peak_vm: FEAHIP_ABS takes magnitudes, and the von Mises form needs the signs
+template <class Emit>
+static int spectrum_on_held(feahip_ctx *c, const char *who, int n_pts, const double *w, const double *sa, int loglog, int rule,
+                            double alpha, double beta_k, const double *zeta, double zpa, int quantity, const double *peak_vm,
+                            double *modal_peak, Emit emit)
+{
+  auto refuse = [&](const std::string &what) { c->err = std::string(who) + ": " + what; return FEAHIP_EINVAL; };
+  if (rule == FEAHIP_ABS && peak_vm) return refuse("no von Mises peak under FEAHIP_ABS (the differences need the signs): peak_vm must be NULL");
+  const int n = c->modal.n_locked;
+  double sak[FEA_MODAL_MAX_LOCKED], a[FEA_MODAL_MAX_LOCKED];
+  for (int k = 0; k < n; ++k) {
+    if (!(c->modal.lam[k] > 0.0)) return refuse("lam of mode " + std::to_string(k + 1) + " is not positive");
+    sak[k] = feahip_host_spectrum_value(n_pts, w, sa, loglog, std::sqrt(c->modal.lam[k]));
+    if (std::isnan(sak[k])) return refuse("the spectrum's points must be finite, their w strictly ascending");
+  }
+  std::vector<double> C((size_t)n * n), b(n);
+  double s = 0.0;
+  std::string why;
+  if (spectrum_form(n, c->modal.lam, c->response.q, sak, alpha, beta_k, zeta, rule, c->response.correction, zpa, quantity,
+                    C.data(), b.data(), &s, a, &why)) return refuse(why);
+  if (const int rc = emit(C.data(), b.data(), s, rule == FEAHIP_ABS)) return rc;
+  if (modal_peak) std::copy_n(a, n, modal_peak);
+  return FEAHIP_OK;
+}
+
 extern "C" int feahip_response_combine(feahip_ctx *c, const double *C, const double *b, double s, int absolute, double *out)
 {
   CTX_GUARD_NOK(c);
   int rc;
   if ((rc = combine_ready(c, "response_combine"))) return rc;
   if (!C || !out) { c->err = "response_combine: null C or out"; return FEAHIP_EINVAL; }
-  const int n = c->modal.n_locked;
-  for (int j = 0; j < n; ++j) {
-    for (int k = 0; k < n; ++k) {
-      const double v = C[(size_t)j * n + k];
-      if (!std::isfinite(v)) { c->err = "response_combine: C is not finite"; return FEAHIP_EINVAL; }
-      if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) { c->err = "response_combine: C is not symmetric to the bit"; return FEAHIP_EINVAL; }
-      if (j != k && !std::isfinite(2.0 * v)) { c->err = "response_combine: twice an entry of C is not finite"; return FEAHIP_EINVAL; }
-    }
-    if (b && !std::isfinite(b[j])) { c->err = "response_combine: b is not finite"; return FEAHIP_EINVAL; }
-  }
-  if (!std::isfinite(s)) { c->err = "response_combine: s is not finite"; return FEAHIP_EINVAL; }
+  if ((rc = form_args(c, "response_combine", "", "C", c->modal.n_locked, C, b, &s))) return rc;
   return combine_to_caller(c, C, b, s, absolute != 0, out);
 }
 
@@ -1805,18 +1882,8 @@ extern "C" int feahip_response_random(feahip_ctx *c, int n_freq, const double *o
   int rc;
   if ((rc = combine_ready(c, "response_random"))) return rc;
   if (!omega || !S || !rms) { c->err = "response_random: null omega, S or rms"; return FEAHIP_EINVAL; }
-  const int n = c->modal.n_locked;
-  std::vector<double> C((size_t)n * n), b(n);
-  double s = 0.0;
-  std::string why;
-  if (random_form(n, c->modal.lam, c->response.q, n_freq, omega, S, alpha, beta_k, zeta, c->response.correction, quantity,
-                  C.data(), b.data(), &s, &why)) {
-    c->err = "response_random: " + why;
-    return FEAHIP_EINVAL;
-  }
-  if ((rc = combine_to_caller(c, C.data(), b.data(), s, false, rms))) return rc;
-  if (modal_cov) std::copy(C.begin(), C.end(), modal_cov);
-  return FEAHIP_OK;
+  return random_on_held(c, "response_random", n_freq, omega, S, alpha, beta_k, zeta, quantity, modal_cov,
+                        [&](const double *C, const double *b, double s, bool absx) { return combine_to_caller(c, C, b, s, absx, rms); });
 }
 
 extern "C" int feahip_response_spectrum(feahip_ctx *c, int n_pts, const double *w, const double *sa, int loglog, int rule,
@@ -1827,24 +1894,8 @@ extern "C" int feahip_response_spectrum(feahip_ctx *c, int n_pts, const double *
   int rc;
   if ((rc = combine_ready(c, "response_spectrum"))) return rc;
   if (!w || !sa || !peak) { c->err = "response_spectrum: null w, sa or peak"; return FEAHIP_EINVAL; }
-  const int n = c->modal.n_locked;
-  double sak[FEA_MODAL_MAX_LOCKED], a[FEA_MODAL_MAX_LOCKED];
-  for (int k = 0; k < n; ++k) {
-    if (!(c->modal.lam[k] > 0.0)) { c->err = "response_spectrum: lam of mode " + std::to_string(k + 1) + " is not positive"; return FEAHIP_EINVAL; }
-    sak[k] = feahip_host_spectrum_value(n_pts, w, sa, loglog, std::sqrt(c->modal.lam[k]));
-    if (std::isnan(sak[k])) { c->err = "response_spectrum: the spectrum's points must be finite, their w strictly ascending"; return FEAHIP_EINVAL; }
-  }
-  std::vector<double> C((size_t)n * n), b(n);
-  double s = 0.0;
-  std::string why;
-  if (spectrum_form(n, c->modal.lam, c->response.q, sak, alpha, beta_k, zeta, rule, c->response.correction, zpa, quantity,
-                    C.data(), b.data(), &s, a, &why)) {
-    c->err = "response_spectrum: " + why;
-    return FEAHIP_EINVAL;
-  }
-  if ((rc = combine_to_caller(c, C.data(), b.data(), s, rule == FEAHIP_ABS, peak))) return rc;
-  if (modal_peak) for (int k = 0; k < n; ++k) modal_peak[k] = a[k];
-  return FEAHIP_OK;
+  return spectrum_on_held(c, "response_spectrum", n_pts, w, sa, loglog, rule, alpha, beta_k, zeta, zpa, quantity, nullptr, modal_peak,
+                          [&](const double *C, const double *b, double s, bool absx) { return combine_to_caller(c, C, b, s, absx, peak); });
 }
 
 // ---- stress from mode superposition (kernels_modal_stress.hip, kernels_stress_combine.hip) -----------------------------
@@ -1952,17 +2003,7 @@ extern "C" int feahip_response_stress_combine(feahip_ctx *c, const double *C, co
   int rc;
   if ((rc = stress_form_ready(c, "response_stress_combine"))) return rc;
   if (!C || !out6) { c->err = "response_stress_combine: null C or out6"; return FEAHIP_EINVAL; }
-  const int n = c->modal.n_locked;
-  for (int j = 0; j < n; ++j) {
-    for (int k = 0; k < n; ++k) {
-      const double v = C[(size_t)j * n + k];
-      if (!std::isfinite(v)) { c->err = "response_stress_combine: C is not finite"; return FEAHIP_EINVAL; }
-      if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) { c->err = "response_stress_combine: C is not symmetric to the bit"; return FEAHIP_EINVAL; }
-      if (j != k && !std::isfinite(2.0 * v)) { c->err = "response_stress_combine: twice an entry of C is not finite"; return FEAHIP_EINVAL; }
-    }
-    if (b && !std::isfinite(b[j])) { c->err = "response_stress_combine: b is not finite"; return FEAHIP_EINVAL; }
-  }
-  if (!std::isfinite(s)) { c->err = "response_stress_combine: s is not finite"; return FEAHIP_EINVAL; }
+  if ((rc = form_args(c, "response_stress_combine", "", "C", c->modal.n_locked, C, b, &s))) return rc;
   return stress_to_caller(c, C, b, s, false, out6, vm);
 }
 
@@ -1973,18 +2014,8 @@ extern "C" int feahip_response_stress_random(feahip_ctx *c, int n_freq, const do
   int rc;
   if ((rc = stress_form_ready(c, "response_stress_random"))) return rc;
   if (!omega || !S || !rms6) { c->err = "response_stress_random: null omega, S or rms6"; return FEAHIP_EINVAL; }
-  const int n = c->modal.n_locked;
-  std::vector<double> C((size_t)n * n), b(n);
-  double s = 0.0;
-  std::string why;
-  if (random_form(n, c->modal.lam, c->response.q, n_freq, omega, S, alpha, beta_k, zeta, c->response.correction, 0,
-                  C.data(), b.data(), &s, &why)) {
-    c->err = "response_stress_random: " + why;
-    return FEAHIP_EINVAL;
-  }
-  if ((rc = stress_to_caller(c, C.data(), b.data(), s, false, rms6, rms_vm))) return rc;
-  if (modal_cov) std::copy(C.begin(), C.end(), modal_cov);
-  return FEAHIP_OK;
+  return random_on_held(c, "response_stress_random", n_freq, omega, S, alpha, beta_k, zeta, 0, modal_cov,
+                        [&](const double *C, const double *b, double s, bool absx) { return stress_to_caller(c, C, b, s, absx, rms6, rms_vm); });
 }
 
 extern "C" int feahip_response_stress_spectrum(feahip_ctx *c, int n_pts, const double *w, const double *sa, int loglog, int rule,
@@ -1995,25 +2026,8 @@ extern "C" int feahip_response_stress_spectrum(feahip_ctx *c, int n_pts, const d
   int rc;
   if ((rc = stress_form_ready(c, "response_stress_spectrum"))) return rc;
   if (!w || !sa || !peak6) { c->err = "response_stress_spectrum: null w, sa or peak6"; return FEAHIP_EINVAL; }
-  if (rule == FEAHIP_ABS && peak_vm) { c->err = "response_stress_spectrum: no von Mises peak under FEAHIP_ABS (the differences need the signs): peak_vm must be NULL"; return FEAHIP_EINVAL; }
-  const int n = c->modal.n_locked;
-  double sak[FEA_MODAL_MAX_LOCKED], a[FEA_MODAL_MAX_LOCKED];
-  for (int k = 0; k < n; ++k) {
-    if (!(c->modal.lam[k] > 0.0)) { c->err = "response_stress_spectrum: lam of mode " + std::to_string(k + 1) + " is not positive"; return FEAHIP_EINVAL; }
-    sak[k] = feahip_host_spectrum_value(n_pts, w, sa, loglog, std::sqrt(c->modal.lam[k]));
-    if (std::isnan(sak[k])) { c->err = "response_stress_spectrum: the spectrum's points must be finite, their w strictly ascending"; return FEAHIP_EINVAL; }
-  }
-  std::vector<double> C((size_t)n * n), b(n);
-  double s = 0.0;
-  std::string why;
-  if (spectrum_form(n, c->modal.lam, c->response.q, sak, alpha, beta_k, zeta, rule, c->response.correction, zpa, 0,
-                    C.data(), b.data(), &s, a, &why)) {
-    c->err = "response_stress_spectrum: " + why;
-    return FEAHIP_EINVAL;
-  }
-  if ((rc = stress_to_caller(c, C.data(), b.data(), s, rule == FEAHIP_ABS, peak6, peak_vm))) return rc;
-  if (modal_peak) for (int k = 0; k < n; ++k) modal_peak[k] = a[k];
-  return FEAHIP_OK;
+  return spectrum_on_held(c, "response_stress_spectrum", n_pts, w, sa, loglog, rule, alpha, beta_k, zeta, zpa, 0, peak_vm, modal_peak,
+                          [&](const double *C, const double *b, double s, bool absx) { return stress_to_caller(c, C, b, s, absx, peak6, peak_vm); });
 }
 
 // ---- random-vibration fatigue on the stress store (kernels_stress_fatigue.hip) ------------------------------------------
@@ -2036,19 +2050,9 @@ extern "C" int feahip_response_stress_moments(feahip_ctx *c, const double *C4, c
   if ((rc = stress_form_ready(c, "response_stress_moments"))) return rc;
   if (!C4 || !moments) { c->err = "response_stress_moments: null C4 or moments"; return FEAHIP_EINVAL; }
   const int n = c->modal.n_locked;
-  for (int f = 0; f < 4; ++f) {
-    const double *C = C4 + (size_t)f * n * n;
-    for (int j = 0; j < n; ++j) {
-      for (int k = 0; k < n; ++k) {
-        const double v = C[(size_t)j * n + k];
-        if (!std::isfinite(v)) { c->err = "response_stress_moments: C4 is not finite"; return FEAHIP_EINVAL; }
-        if (std::memcmp(&v, &C[(size_t)k * n + j], sizeof(double))) { c->err = "response_stress_moments: a form of C4 is not symmetric to the bit"; return FEAHIP_EINVAL; }
-        if (j != k && !std::isfinite(2.0 * v)) { c->err = "response_stress_moments: twice an entry of C4 is not finite"; return FEAHIP_EINVAL; }
-      }
-      if (b4 && !std::isfinite(b4[(size_t)f * n + j])) { c->err = "response_stress_moments: b4 is not finite"; return FEAHIP_EINVAL; }
-    }
-    if (s4 && !std::isfinite(s4[f])) { c->err = "response_stress_moments: s4 is not finite"; return FEAHIP_EINVAL; }
-  }
+  for (int f = 0; f < 4; ++f)
+    if ((rc = form_args(c, "response_stress_moments", "4", "a form of C4", n, C4 + (size_t)f * n * n, b4 ? b4 + (size_t)f * n : nullptr,
+                        s4 ? s4 + f : nullptr))) return rc;
   std::vector<double> lib(28 * (size_t)c->N);
   if ((rc = stress_moments(c, C4, b4, s4, lib.data()))) return rc;
   moments_to_caller(c, lib.data(), moments);
@@ -2126,12 +2130,10 @@ extern "C" int feahip_response_stress_sweep(feahip_ctx *c, int n_freq, const dou
   CTX_GUARD_NOK(c);
   if (!omega || !peak6 || !peak6_at || !vm || !vm_at) { c->err = "response_stress_sweep: null omega, peak6, peak6_at, vm or vm_at"; return FEAHIP_EINVAL; }
   int rc;
-  if ((rc = stress_form_ready(c, "response_stress_sweep"))) return rc;
-  if (n_freq < 1 || n_freq > FEA_RESPONSE_MAX_FREQ) { c->err = "response_stress_sweep: n_freq must be in [1, 4096]"; return FEAHIP_EINVAL; }
-  if (n_probe < 0 || n_probe > 64) { c->err = "response_stress_sweep: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
-  if (n_probe > 0 && (!probe_node || !probe_re || !probe_im)) { c->err = "response_stress_sweep: null probe arrays"; return FEAHIP_EINVAL; }
   int probe[64];
-  if ((rc = probe_nodes(c, "response_stress_sweep", n_probe, probe_node, probe))) return rc;
+  if ((rc = stress_form_ready(c, "response_stress_sweep")) || (rc = sweep_args(c, "response_stress_sweep", n_freq)) ||
+      (rc = probe_args(c, "response_stress_sweep", n_probe, probe_node, probe_re, probe_im)) ||
+      (rc = probe_nodes(c, "response_stress_sweep", n_probe, probe_node, probe))) return rc;
   StressPeaks out(c);
   std::vector<double> pre((size_t)n_probe * n_freq * 6), pim(pre.size());   // (the caller's arrays stay as they are on a refusal)
   if ((rc = stress_sweep(c, n_freq, omega, alpha, beta_k, zeta, out.p6.data(), out.a6.data(), out.vm.data(), out.avm.data(), n_probe,
@@ -2150,11 +2152,10 @@ extern "C" int feahip_response_stress_transient(feahip_ctx *c, int n_steps, doub
   int rc;
   if ((rc = stress_form_ready(c, "response_stress_transient"))) return rc;
   if (!g || !peak6 || !peak6_at || !vm || !vm_at) { c->err = "response_stress_transient: null g, peak6, peak6_at, vm or vm_at"; return FEAHIP_EINVAL; }
-  if (n_steps < 1 || n_steps > FEA_TRANSIENT_MAX_STEPS) { c->err = "response_stress_transient: n_steps must be in [1, 1048576]"; return FEAHIP_EINVAL; }
-  if (n_probe < 0 || n_probe > 64) { c->err = "response_stress_transient: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
-  if (n_probe > 0 && (!probe_node || !probe)) { c->err = "response_stress_transient: null probe arrays"; return FEAHIP_EINVAL; }
   int lib_probe[64];
-  if ((rc = probe_nodes(c, "response_stress_transient", n_probe, probe_node, lib_probe))) return rc;
+  if ((rc = history_args(c, "response_stress_transient", n_steps)) ||
+      (rc = probe_args(c, "response_stress_transient", n_probe, probe_node, probe)) ||
+      (rc = probe_nodes(c, "response_stress_transient", n_probe, probe_node, lib_probe))) return rc;
   StressPeaks out(c);
   std::vector<double> hist((size_t)n_probe * ((size_t)n_steps + 1) * 6);
   if ((rc = stress_transient(c, n_steps, dt, g, alpha, beta_k, zeta, out.p6.data(), out.a6.data(), out.vm.data(), out.avm.data(),
@@ -2174,9 +2175,8 @@ extern "C" int feahip_response_stress_rainflow(feahip_ctx *c, int n_steps, doubl
   int rc;
   if ((rc = stress_form_ready(c, "response_stress_rainflow"))) return rc;
   if (!g) { c->err = "response_stress_rainflow: null g"; return FEAHIP_EINVAL; }
-  if (n_steps < 1 || n_steps > FEA_TRANSIENT_MAX_STEPS) { c->err = "response_stress_rainflow: n_steps must be in [1, 1048576]"; return FEAHIP_EINVAL; }
-  if (n_probe < 0 || n_probe > 64) { c->err = "response_stress_rainflow: n_probe must be in [0, 64]"; return FEAHIP_EINVAL; }
-  if (n_probe > 0 && (!probe_node || !probe)) { c->err = "response_stress_rainflow: null probe arrays"; return FEAHIP_EINVAL; }
+  if ((rc = history_args(c, "response_stress_rainflow", n_steps)) ||
+      (rc = probe_args(c, "response_stress_rainflow", n_probe, probe_node, probe))) return rc;
   if (!rainflow_arguments(sn_b, sn_a, depth)) {
     c->err = "response_stress_rainflow: the S-N curve N s^b = A needs a finite b in [1, 64] and a finite A > 0, the stack a depth in [4, 1024]";
     return FEAHIP_EINVAL;

@@ -21,14 +21,17 @@
 //               pow (RainflowPower), which costs some sixty VGPRs beside the lane's 8 P values: 182 against 256 and 16 in
 //               AGPRs at eight panels, two waves on a SIMD against one (DESIGN.md section 27 has both measured).
 // The host builds the coefficient chunks once per call and keeps them for the later passes where the whole table fits
-// RAINFLOW_TABLE_CACHE bytes; above that every pass builds its chunks again, two buffers as stress_transient has them.
+// RAINFLOW_TABLE_CACHE bytes; above that every pass builds its chunks again through the two buffers of transient_stream.h
+// (`make variant NAME=rfnocache VSRC=kernels_stress_rainflow VFLAGS=-DRAINFLOW_TABLE_CACHE=0` takes every call that way).
 // No LDS memory, no atomics, the same bits on every call.  A context that never calls the entry allocates and launches
 // nothing here.
 #include "stress_form.h"
+#include "transient_stream.h"
 #include "rainflow_point.h"
-#include <algorithm>
 
+#ifndef RAINFLOW_TABLE_CACHE
 #define RAINFLOW_TABLE_CACHE ((size_t)256 << 20)
+#endif
 #define RF_REAL 4                      // d_real: last, damage, cycles, max_range
 #define RF_INT 6                       // d_int: dir, base, count, depth_used, status, seen
 
@@ -156,8 +159,8 @@ static void enq_rainflow(feahip_ctx *c, int count, int first, int last, const do
     constexpr int PP = decltype(P)::value;
     hipLaunchKernelGGL((k_stress_rainflow<PP, STRESS_SWEEP_STEPS_OF(PP), decltype(curve)>), stress_sweep_grid(c), dim3(256), 0,
                        c->stream, c->N, count, first, last, (const double *)S.d_store, (size_t)6 * c->N * MC, (const double *)S.d_ts,
-                       (const double *)R.d_coef, (const double *)(R.d_coef + (size_t)FEA_TRANSIENT_CHUNK * ML), d_proj, n_live,
-                       curve, R.depth, R.d_stack, R.d_real, R.d_int);
+                       (const double *)R.d_coef, (const double *)chunk_g(R.d_coef), d_proj, n_live, curve, R.depth, R.d_stack,
+                       R.d_real, R.d_int);
   };
   // a whole exponent takes the instance without pow (RainflowIntPower): 182 registers at eight panels where pow takes all 256
   const bool whole = R.sn[0] == (double)(int)R.sn[0];
@@ -171,20 +174,16 @@ int stress_rainflow(feahip_ctx *c, int n_steps, double dt, const double *g, doub
                     double sn_b, double sn_a, int depth, int n_proj, const double *proj, double *h_damage, double *h_cycles,
                     double *h_range, int *h_status, int *h_used, int n_probe, const int *probe, double *h_probe)
 {
-  ModalState &M = c->modal;
-  ResponseState &Rs = c->response;
   RainflowBuffers &R = c->rainflow;
-  const int n = M.n_locked, n_rows = n_steps + 1, CH = FEA_TRANSIENT_CHUNK;
-  const int W = 6 + n_proj, passes = 1 + (n_proj + 5) / 6, n_chunks = (n_rows + CH - 1) / CH;
+  const int n_rows = n_steps + 1, W = 6 + n_proj, passes = 1 + (n_proj + 5) / 6;
   const size_t rows6 = (size_t)6 * c->N;
-  std::string why;
-  if (transient_check(n, M.lam, Rs.q, n_steps, dt, g, alpha, beta, zeta, Rs.correction, 0, &why)) {
-    c->err = "response_stress_rainflow: " + why;
-    return FEAHIP_EINVAL;
-  }
+  // the host keeps the whole table where later passes read it again and it fits
+  TransientStream T;
+  int rc;
+  if ((rc = T.open(c, "response_stress_rainflow", n_steps, dt, g, alpha, beta, zeta, 0, true, passes > 1 ? RAINFLOW_TABLE_CACHE : 0)))
+    return rc;
   double k[5];
   if (fatigue_constants(sn_b, sn_a, k)) { c->err = "response_stress_rainflow: the S-N curve was refused"; return FEAHIP_EINVAL; }
-  int rc;
   R.rows = 0;                                                          // (nothing for hook 33 to time until this call is through)
   if ((rc = ensure_rainflow(c, depth))) return rc;
   R.depth = depth; R.sn[0] = k[0]; R.sn[1] = k[1];
@@ -204,26 +203,8 @@ int stress_rainflow(feahip_ctx *c, int n_steps, double dt, const double *g, doub
         for (int col = 0; col <= width; ++col) dst[col] = std::fma(proj[6 * p + e], src[col], dst[col]);
       }
     }
-  // the host chunks: the whole table where later passes read it again and it fits, two buffers otherwise
-  const bool cached = passes > 1 && (size_t)n_rows * (ML + 1) * sizeof(double) <= RAINFLOW_TABLE_CACHE;
-  StressChunkBuffers B;
-  std::vector<double> cache;
-  bool recorded[2] = {false, false};
-  const size_t chunk_doubles = (size_t)std::min(CH, n_rows) * (ML + 1);
-  if (cached) cache.resize((size_t)n_chunks * chunk_doubles);
-  else
-    for (int b = 0; b < 2; ++b) {
-      B.buf[b].resize(chunk_doubles);
-      FEA_HIP_CHECK(c, hipEventCreateWithFlags(&B.copied[b], hipEventDisableTiming));
-    }
-  auto host_chunk = [&](int kc) { return cached ? cache.data() + (size_t)kc * chunk_doubles : B.buf[kc & 1].data(); };
-  // chunk kc into its host buffer, rows then g; the probes' values taken on the way in the first pass
-  auto fill = [&](int kc, bool with_probes) -> int {
-    const int step0 = kc * CH, count = std::min(CH, n_rows - step0);
-    double *coef = host_chunk(kc), *gs = coef + (size_t)count * ML;
-    if (transient_rows(B.table, g, count, coef, &why)) { c->err = "response_stress_rainflow: " + why; return FEAHIP_EINVAL; }
-    for (int j = 0; j < count; ++j) gs[j] = g[step0 + j];
-    if (!with_probes) return FEAHIP_OK;
+  // the probes' values, taken from a chunk as the host fills it in the first pass
+  auto on_host = [&](int step0, int count, const double *coef, const double *gs) {
     for (int r = 0; r < n_probe; ++r)
       for (int j = 0; j < count; ++j) {
         double *out = h_probe + ((size_t)r * n_rows + step0 + j) * W;
@@ -236,38 +217,15 @@ int stress_rainflow(feahip_ctx *c, int n_steps, double dt, const double *g, doub
           out[6 + p] = y;
         }
       }
-    return FEAHIP_OK;
   };
   const bool want_real = h_damage || h_cycles || h_range, want_int = h_status || h_used;
   std::vector<double> preal(want_real ? 3 * rows6 : 0);               // one pass's results, scattered before the next pass's arrive
   std::vector<int> pint(want_int ? 2 * rows6 : 0);
-  int last_count = 0, last0 = 0;
   for (int pass = 0; pass < passes; ++pass) {
-    const bool build = !cached || pass == 0;
-    if (build) {
-      if (B.table) transient_end(B.table);
-      B.table = transient_begin(n, M.lam, Rs.q, M.lock_order, n_steps, dt, alpha, beta, zeta, Rs.correction, 0);
-      if (!cached && recorded[0]) FEA_HIP_CHECK(c, hipEventSynchronize(B.copied[0]));
-      if ((rc = fill(0, pass == 0))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    }
     const double *d_proj = pass == 0 ? nullptr : R.d_proj + (size_t)36 * (pass - 1);
     const int n_live = std::min(6, W - 6 * pass);
-    for (int kc = 0; kc < n_chunks; ++kc) {
-      const int step0 = kc * CH, count = std::min(CH, n_rows - step0);
-      const double *src = host_chunk(kc);
-      FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_coef, src, sizeof(double) * (size_t)count * ML, hipMemcpyHostToDevice, c->stream));
-      FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_coef + (size_t)CH * ML, src + (size_t)count * ML, sizeof(double) * (size_t)count,
-                                      hipMemcpyHostToDevice, c->stream));
-      if (!cached) { FEA_HIP_CHECK(c, hipEventRecord(B.copied[kc & 1], c->stream)); recorded[kc & 1] = true; }
-      enq_rainflow(c, count, kc == 0, kc == n_chunks - 1, d_proj, n_live);
-      FEA_HIP_CHECK(c, hipGetLastError());
-      last_count = count; last0 = step0;
-      // the next chunk on the host while this one runs; its buffer's last copy has to be over
-      if (build && kc + 1 < n_chunks) {
-        if (!cached && recorded[(kc + 1) & 1]) FEA_HIP_CHECK(c, hipEventSynchronize(B.copied[(kc + 1) & 1]));
-        if ((rc = fill(kc + 1, pass == 0))) { (void)hipStreamSynchronize(c->stream); return rc; }
-      }
-    }
+    auto launch = [&](int count, int, bool first, bool last) { enq_rainflow(c, count, first, last, d_proj, n_live); };
+    if ((rc = T.pass(R.d_coef, pass == 0, on_host, launch))) return rc;
     // the pass's results, before the next pass starts the state again: process 6 pass + e of node a from row 6 a + e
     if (want_real)
       FEA_HIP_CHECK(c, hipMemcpyAsync(preal.data(), R.d_real + rows6, sizeof(double) * 3 * rows6, hipMemcpyDeviceToHost, c->stream));
@@ -286,9 +244,9 @@ int stress_rainflow(feahip_ctx *c, int n_steps, double dt, const double *g, doub
         if (h_status) h_status[dst] = pi[rows6 + src];
       }
   }
-  R.rows = last_count;
-  R.step0 = last0;
-  R.table_gen = M.lock_gen;
+  R.rows = T.last_count;
+  R.step0 = T.last_step0;
+  R.table_gen = c->modal.lock_gen;
   return FEAHIP_OK;
 }
 

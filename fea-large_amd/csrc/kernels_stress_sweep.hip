@@ -27,11 +27,8 @@
 // `make variant NAME=ssshfl VSRC=kernels_stress_sweep VFLAGS=-DSTRESS_SWEEP_SHFL`).
 // A context that never calls these entries allocates and launches nothing here.
 #include "stress_form.h"
+#include "transient_stream.h"
 #include "dpp_device.h"
-#include <algorithm>
-
-static_assert((size_t)FEA_TRANSIENT_CHUNK * (FEA_MODAL_MAX_LOCKED + 1) <= (size_t)FEA_RESPONSE_MAX_FREQ * 2 * FEA_MODAL_MAX_LOCKED,
-              "a chunk and its g fit the coefficient buffer of the stress sweeps");
 
 #ifdef STRESS_SWEEP_SHFL
 // the mean of the three normal components of the lane's node, (s0 + s1) + s2 as k_stress_field has it, on every lane of
@@ -215,8 +212,7 @@ static void enq_stress_transient(feahip_ctx *c, int n_rows, int step0, int first
     constexpr int PP = decltype(P)::value;
     hipLaunchKernelGGL((k_stress_transient<PP, STRESS_SWEEP_STEPS_OF(PP)>), stress_sweep_grid(c), dim3(256), 0, c->stream, c->N,
                        n_rows, step0, first, last, (const double *)S.d_store, (size_t)6 * c->N * MC, (const double *)S.d_ts,
-                       (const double *)S.d_scoef, (const double *)(S.d_scoef + (size_t)FEA_TRANSIENT_CHUNK * ML), S.d_out6,
-                       S.d_at6, S.d_vm, S.d_vmat);
+                       (const double *)S.d_scoef, (const double *)chunk_g(S.d_scoef), S.d_out6, S.d_at6, S.d_vm, S.d_vmat);
   });
 }
 
@@ -270,68 +266,35 @@ int stress_sweep(feahip_ctx *c, int n_freq, const double *omega, double alpha, d
   return FEAHIP_OK;
 }
 
-// the chunked launches of k_stress_transient over the whole displacement history, as response_transient makes them:
-// the probes' histories [n_probe][n_steps + 1][6]
+// the chunked launches of k_stress_transient over the whole displacement history (transient_stream.h): the probes'
+// histories [n_probe][n_steps + 1][6]
 int stress_transient(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta, const double *zeta,
                      double *h_peak6, int *h_at6, double *h_vm, int *h_vmat, int n_probe, const int *probe, double *h_probe)
 {
-  ModalState &M = c->modal;
-  ResponseState &R = c->response;
   StressState &S = c->stress;
-  const int n = M.n_locked, n_rows = n_steps + 1, CH = FEA_TRANSIENT_CHUNK;
-  std::string why;
-  if (transient_check(n, M.lam, R.q, n_steps, dt, g, alpha, beta, zeta, R.correction, 0, &why)) {
-    c->err = "response_stress_transient: " + why;
-    return FEAHIP_EINVAL;
-  }
+  const int n_rows = n_steps + 1;
+  TransientStream T;
   int rc;
-  if ((rc = ensure_stress_sweep(c))) return rc;
+  if ((rc = T.open(c, "response_stress_transient", n_steps, dt, g, alpha, beta, zeta, 0, true, 0)) || (rc = ensure_stress_sweep(c)))
+    return rc;
   S.swept_freq = 0;
   S.trans_rows = 0;
-  StressChunkBuffers B;
-  B.table = transient_begin(n, M.lam, R.q, M.lock_order, n_steps, dt, alpha, beta, zeta, R.correction, 0);
-  const size_t chunk_doubles = (size_t)std::min(CH, n_rows) * (ML + 1);
-  for (int b = 0; b < 2; ++b) {
-    B.buf[b].resize(chunk_doubles);
-    FEA_HIP_CHECK(c, hipEventCreateWithFlags(&B.copied[b], hipEventDisableTiming));
-  }
   StressProbeRows rows;                                                // read back once
   if ((rc = rows.read(c, n_probe, probe))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  // a chunk of rows and its g into a host buffer; the probes' values taken on the way
-  auto fill = [&](int b, int step0, int count) -> int {
-    double *coef = B.buf[b].data(), *gs = coef + (size_t)count * ML;
-    if (transient_rows(B.table, g, count, coef, &why)) { c->err = "response_stress_transient: " + why; return FEAHIP_EINVAL; }
-    for (int j = 0; j < count; ++j) gs[j] = g[step0 + j];
+  // the probes' values, taken from a chunk as the host fills it
+  auto on_host = [&](int step0, int count, const double *coef, const double *gs) {
     for (int r = 0; r < n_probe; ++r)
       for (int j = 0; j < count; ++j)
         for (int e = 0; e < 6; ++e)
           h_probe[((size_t)r * n_rows + step0 + j) * 6 + e] = rows.sum(r, e, coef + (size_t)j * ML, gs[j]);
-    return FEAHIP_OK;
   };
-  if ((rc = fill(0, 0, std::min(CH, n_rows)))) return rc;
-  int last0 = 0, last_count = 0;
-  for (int step0 = 0, k = 0; step0 < n_rows; step0 += CH, ++k) {
-    const int b = k & 1, count = std::min(CH, n_rows - step0);
-    const double *src = B.buf[b].data();
-    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_scoef, src, sizeof(double) * (size_t)count * ML, hipMemcpyHostToDevice, c->stream));
-    FEA_HIP_CHECK(c, hipMemcpyAsync(S.d_scoef + (size_t)CH * ML, src + (size_t)count * ML, sizeof(double) * (size_t)count,
-                                    hipMemcpyHostToDevice, c->stream));
-    FEA_HIP_CHECK(c, hipEventRecord(B.copied[b], c->stream));
-    enq_stress_transient(c, count, step0, step0 == 0, step0 + CH >= n_rows);
-    FEA_HIP_CHECK(c, hipGetLastError());
-    last0 = step0; last_count = count;
-    // the next chunk on the host while this one runs; its buffer's last copy (of the chunk before) has to be over
-    if (step0 + CH < n_rows) {
-      if (k >= 1) FEA_HIP_CHECK(c, hipEventSynchronize(B.copied[b ^ 1]));
-      if ((rc = fill(b ^ 1, step0 + CH, std::min(CH, n_rows - step0 - CH)))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    }
-  }
-  if ((rc = read_stress_peaks(c, h_peak6, h_at6, h_vm, h_vmat))) return rc;
+  auto launch = [&](int count, int step0, bool first, bool last) { enq_stress_transient(c, count, step0, first, last); };
+  if ((rc = T.pass(S.d_scoef, true, on_host, launch)) || (rc = read_stress_peaks(c, h_peak6, h_at6, h_vm, h_vmat))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  S.trans_rows = last_count;
-  S.trans_step0 = last0;
-  S.table_gen = M.lock_gen;
+  S.trans_rows = T.last_count;
+  S.trans_step0 = T.last_step0;
+  S.table_gen = c->modal.lock_gen;
   return FEAHIP_OK;
 }
 

@@ -12,14 +12,11 @@
 //                           buffer.  FIELD writes u of one row (a snapshot) instead.
 //   k_base_load             f = -(M r) on the free dofs, 0 on the prescribed ones
 // The history goes through the coefficient buffer of the response state, FEA_TRANSIENT_CHUNK rows of 64 at a time with
-// their g_n behind them: no device allocation grows with the step count.  No atomics, the same bits on every call.
+// their g_n behind them (transient_stream.h owns the host side of that): no device allocation grows with the step count.
+// No atomics, the same bits on every call.
 // A context that never calls a transient entry allocates and launches nothing of this file.
-#include "superpose.h"
-#include <algorithm>
+#include "transient_stream.h"
 
-// the chunk's rows and their g_n share the table of a frequency sweep: [CHUNK][64] coefficients, then [CHUNK] g
-static_assert((size_t)FEA_TRANSIENT_CHUNK * (FEA_MODAL_MAX_LOCKED + 1) <= (size_t)FEA_RESPONSE_MAX_FREQ * 2 * FEA_MODAL_MAX_LOCKED,
-              "a chunk and its g fit the coefficient buffer of the response state");
 // Rows per loop iteration of k_transient_sweep.  One row is a single chain of 8 P dependent v_fma_f64 per dof, which at
 // eight panels runs at the rate of ONE frequency of the complex sweep (two chains); two rows give two chains.  Measured
 // (DESIGN.md section 22): two rows win from two panels on, one row with a single panel.  TRANSIENT_STEPS forces one value
@@ -143,8 +140,7 @@ static void enq_transient_p(feahip_ctx *c, int n_rows, int step0, int first, con
   ResponseState &R = c->response;
   hipLaunchKernelGGL((k_transient_sweep<P, D, S, FIELD>), dim3((c->ndof + 256 * D - 1) / (256 * D)), dim3(256), 0, c->stream,
                      c->ndof, n_rows, step0, first, (const double *)locked_panel(c, 0, 0), (size_t)c->ndof * MC,
-                     (const double *)R.d_us, d_coef, (const double *)(R.d_coef + (size_t)FEA_TRANSIENT_CHUNK * FEA_MODAL_MAX_LOCKED),
-                     g0, d_o0, (int *)(R.d_out + c->ndof));
+                     (const double *)R.d_us, d_coef, (const double *)chunk_g(R.d_coef), g0, d_o0, (int *)(R.d_out + c->ndof));
 }
 
 template <bool FIELD>
@@ -153,55 +149,24 @@ static void enq_transient(feahip_ctx *c, int n_rows, int step0, int first, const
   for_panels(panels_of(c), [&](auto P) { enq_transient_p<decltype(P)::value, FIELD>(c, n_rows, step0, first, d_coef, g0, d_o0); });
 }
 
-namespace {
-// two host buffers of one chunk each and the event behind the last copy out of either
-struct ChunkBuffers {
-  std::vector<double> buf[2];
-  hipEvent_t copied[2] = {nullptr, nullptr};
-  TransientTable *table = nullptr;
-  ~ChunkBuffers()
-  {
-    for (hipEvent_t e : copied) if (e) (void)hipEventDestroy(e);
-    if (table) transient_end(table);
-  }
-};
-}
-
 int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, double alpha, double beta, const double *zeta,
                        int quantity, double *h_peak, int *h_at, int n_probe, const int *probe, double *h_probe, int n_snap,
                        const int *snap_step, double *h_snap)
 {
-  ModalState &S = c->modal;
   ResponseState &R = c->response;
-  const int n = S.n_locked;
   const size_t nd = (size_t)c->ndof;
-  const int n_rows = n_steps + 1, CH = FEA_TRANSIENT_CHUNK;
-  std::string why;
-  if (transient_check(n, S.lam, R.q, n_steps, dt, g, alpha, beta, zeta, R.correction, quantity, &why)) {
-    c->err = "response_transient: " + why;
-    return FEAHIP_EINVAL;
-  }
+  const int n_rows = n_steps + 1;
+  TransientStream T;                                                   // (the static term u_s g_n belongs to the displacement alone)
+  int rc;
+  if ((rc = T.open(c, "response_transient", n_steps, dt, g, alpha, beta, zeta, quantity, quantity == 0, 0))) return rc;
   R.swept_freq = 0;                                                    // the table of a frequency sweep is gone from d_coef
   R.trans_rows = 0;
-  ChunkBuffers B;
-  B.table = transient_begin(n, S.lam, R.q, S.lock_order, n_steps, dt, alpha, beta, zeta, R.correction, quantity);
-  const size_t chunk_doubles = (size_t)std::min(CH, n_rows) * (FEA_MODAL_MAX_LOCKED + 1);
-  for (int b = 0; b < 2; ++b) {
-    B.buf[b].resize(chunk_doubles);
-    FEA_HIP_CHECK(c, hipEventCreateWithFlags(&B.copied[b], hipEventDisableTiming));
-  }
   ProbeRows rows;                                                      // read back once
-  int rc;
   if ((rc = rows.read(c, n_probe, probe))) return rc;
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  // the static term u_s g_n belongs to the displacement alone
-  auto g_of = [&](int step) { return quantity == 0 ? g[step] : 0.0; };
-  // a chunk of rows and its g into a host buffer; the probes' values and the snapshots' rows taken on the way
+  // the probes' values and the snapshots' rows, taken from a chunk as the host fills it
   std::vector<double> snap_rows((size_t)n_snap * (FEA_MODAL_MAX_LOCKED + 1));
-  auto fill = [&](int b, int step0, int count) -> int {
-    double *coef = B.buf[b].data(), *gs = coef + (size_t)count * FEA_MODAL_MAX_LOCKED;
-    if (transient_rows(B.table, g, count, coef, &why)) { c->err = "response_transient: " + why; return FEAHIP_EINVAL; }
-    for (int j = 0; j < count; ++j) gs[j] = g_of(step0 + j);
+  auto on_host = [&](int step0, int count, const double *coef, const double *gs) {
     for (int r = 0; r < n_probe; ++r)
       for (int j = 0; j < count; ++j)
         h_probe[(size_t)r * n_rows + step0 + j] = rows.sum(r, coef + (size_t)j * FEA_MODAL_MAX_LOCKED, std::fma(rows.us(r), gs[j], 0.0));
@@ -211,26 +176,9 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
         std::copy_n(coef + (size_t)(snap_step[s] - step0) * FEA_MODAL_MAX_LOCKED, FEA_MODAL_MAX_LOCKED, keep);
         keep[FEA_MODAL_MAX_LOCKED] = gs[snap_step[s] - step0];
       }
-    return FEAHIP_OK;
   };
-  if ((rc = fill(0, 0, std::min(CH, n_rows)))) return rc;
-  int last0 = 0, last_count = 0;
-  for (int step0 = 0, k = 0; step0 < n_rows; step0 += CH, ++k) {
-    const int b = k & 1, count = std::min(CH, n_rows - step0);
-    const double *src = B.buf[b].data();
-    FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_coef, src, sizeof(double) * (size_t)count * FEA_MODAL_MAX_LOCKED, hipMemcpyHostToDevice, c->stream));
-    FEA_HIP_CHECK(c, hipMemcpyAsync(R.d_coef + (size_t)CH * FEA_MODAL_MAX_LOCKED, src + (size_t)count * FEA_MODAL_MAX_LOCKED,
-                                    sizeof(double) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    FEA_HIP_CHECK(c, hipEventRecord(B.copied[b], c->stream));
-    enq_transient<false>(c, count, step0, step0 == 0, R.d_coef, 0.0, R.d_out);
-    FEA_HIP_CHECK(c, hipGetLastError());
-    last0 = step0; last_count = count;
-    // the next chunk on the host while this one runs; its buffer's last copy (of the chunk before) has to be over
-    if (step0 + CH < n_rows) {
-      if (k >= 1) FEA_HIP_CHECK(c, hipEventSynchronize(B.copied[b ^ 1]));
-      if ((rc = fill(b ^ 1, step0 + CH, std::min(CH, n_rows - step0 - CH)))) { (void)hipStreamSynchronize(c->stream); return rc; }
-    }
-  }
+  auto launch = [&](int count, int step0, bool first, bool) { enq_transient<false>(c, count, step0, first, R.d_coef, 0.0, R.d_out); };
+  if ((rc = T.pass(R.d_coef, true, on_host, launch))) return rc;
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_peak, R.d_out, sizeof(double) * nd, hipMemcpyDeviceToHost, c->stream));
   FEA_HIP_CHECK(c, hipMemcpyAsync(h_at, R.d_out + nd, sizeof(int) * nd, hipMemcpyDeviceToHost, c->stream));
   // the snapshots: one launch each, its row through the 64 doubles of d_q (free between two loads), its g by value;
@@ -243,8 +191,8 @@ int response_transient(feahip_ctx *c, int n_steps, double dt, const double *g, d
     FEA_HIP_CHECK(c, hipMemcpyAsync(h_snap + (size_t)s * nd, R.d_out, sizeof(double) * nd, hipMemcpyDeviceToHost, c->stream));
   }
   FEA_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-  R.trans_rows = last_count;
-  R.trans_step0 = last0;
+  R.trans_rows = T.last_count;
+  R.trans_step0 = T.last_step0;
   return FEAHIP_OK;
 }
 

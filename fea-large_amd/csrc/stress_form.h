@@ -61,8 +61,8 @@ __device__ __forceinline__ double stress_form(const double (&x)[MC * P], double 
 
 // ------------------------------------------------------------------------
 // What the kernels that walk a coefficient table with a lane per stress ROW share (k_stress_sweep and k_stress_transient of
-// kernels_stress_sweep.hip, k_stress_rainflow of kernels_stress_rainflow.hip): the lane layout, the grid, the probes' rows
-// on the host and the host buffers of a chunked transient.
+// kernels_stress_sweep.hip, k_stress_rainflow of kernels_stress_rainflow.hip): the lane layout, the grid and the probes'
+// rows on the host.  (The host side of a chunked transient is transient_stream.h.)
 // ------------------------------------------------------------------------
 #define SS_NODES_PER_WAVE 10
 #define SS_NODES_PER_BLOCK (4 * SS_NODES_PER_WAVE)
@@ -130,18 +130,6 @@ struct StressProbeRows {
     double y = cs * row[width];
     for (int col = 0; col < width; ++col) y = std::fma(row[col], coef[col], y);
     return y;
-  }
-};
-
-// two host buffers of one chunk each and the event behind the last copy out of either (kernels_transient.hip has the same)
-struct StressChunkBuffers {
-  std::vector<double> buf[2];
-  hipEvent_t copied[2] = {nullptr, nullptr};
-  TransientTable *table = nullptr;
-  ~StressChunkBuffers()
-  {
-    for (hipEvent_t e : copied) if (e) (void)hipEventDestroy(e);
-    if (table) transient_end(table);
   }
 };
 }
