@@ -47,9 +47,9 @@ def omega_max(K, ml):
 
 
 def hub_fan(spokes=150):
-    """Linear tetrahedra around one hub node whose block row has spokes + 3 blocks (more than the 128-block tile):
-    a ring of `spokes` nodes around the hub, a pole above; tetrahedron k = (hub, ring k, ring k + 1, pole).  Clamped
-    at the pole, so the hub is free."""
+    """Linear tetrahedra around one hub node whose block row has spokes + 2 blocks (the hub, the ring and the pole: 152,
+    more than the 128-block tile, for the 150 spokes of the default): a ring of `spokes` nodes around the hub, a pole
+    above; tetrahedron k = (hub, ring k, ring k + 1, pole).  Clamped at the pole, so the hub is free."""
     ang = 2.0 * np.pi * np.arange(spokes) / spokes
     ring = np.stack([np.cos(ang), np.sin(ang), 0.05 * np.cos(3 * ang)], axis=1)
     nodes = np.vstack([[0.0, 0.0, 0.0], ring, [0.0, 0.0, 0.8]])

@@ -66,14 +66,12 @@ def case(name):
 CHUNK_ROWS, CHUNK_BLOCKS, SUPER_CHUNKS = 16, 128, 8    # FEA_CHUNK_ROWS, FEA_CHUNK_BLOCKS, FEA_SUPER_CHUNKS (feahip_internal.h)
 
 
-def shard_chunks(deck, n):
-    """Host only.  What install_plan (dist.hip) finds for every rank of FeaGroup(deck, n), restated: the SpMV chunks
-    (pattern.cpp: consecutive rows in the library's numbering, closed at 16 rows or 128 blocks), the rank's rows (shard.cpp:
-    whole supers of 8 chunks, supers s with n_super r / n <= s < n_super (r + 1) / n), and the longest run of its chunks
-    whose rows have no column outside the rank's rows.  Per rank: dict(row0, row1, chunks, lo, hi) -- enq_spmv_interior
-    multiplies chunks [lo, hi) of the rank, enq_spmv_boundary the lo in front and the chunks - hi behind."""
+def spmv_chunks(deck):
+    """Host only.  The SpMV chunks of pattern.cpp, restated: consecutive rows in the library's numbering, closed at 16 rows
+    or 128 blocks (a row with more blocks than that is a chunk of its own).  (first row of every chunk and N at the end,
+    neighbour set of every row -- its blocks --, renumbered?)."""
     N = len(deck.nodes)
-    lib, _ = feahip.host_numbering(deck.elements, deck.nodes)
+    lib, renumbered = feahip.host_numbering(deck.elements, deck.nodes)
     el = lib[np.asarray(deck.elements)]
     nbr = [set([a]) for a in range(N)]
     for e in el:
@@ -85,6 +83,16 @@ def shard_chunks(deck, n):
             chunk.append(a); rows = blocks = 0
         rows += 1; blocks += len(nbr[a])
     chunk.append(N)
+    return chunk, nbr, renumbered
+
+
+def shard_chunks(deck, n):
+    """Host only.  What install_plan (dist.hip) finds for every rank of FeaGroup(deck, n), restated: the SpMV chunks
+    (spmv_chunks above), the rank's rows (shard.cpp: whole supers of 8 chunks, supers s with
+    n_super r / n <= s < n_super (r + 1) / n), and the longest run of its chunks whose rows have no column outside the
+    rank's rows.  Per rank: dict(row0, row1, chunks, lo, hi) -- enq_spmv_interior multiplies chunks [lo, hi) of the rank,
+    enq_spmv_boundary the lo in front and the chunks - hi behind."""
+    chunk, nbr, _ = spmv_chunks(deck)
     nchunks = len(chunk) - 1
     nsuper = (nchunks + SUPER_CHUNKS - 1) // SUPER_CHUNKS
     out = []

@@ -33,11 +33,11 @@ def prescribed_mask(deck):
     return m
 
 
-def fan_on_block():
-    """A block with, beside it, the 140-tetrahedron-pair fan of test_node_with_more_neighbours_than_the_spmv_tile: its hub
-    row has 143 blocks, more than the SpMV tile.  The fan alone is too small for a hierarchy."""
+def fan_on_block(m=140):
+    """A block with, beside it, the fan of m tetrahedron pairs of test_node_with_more_neighbours_than_the_spmv_tile: its hub
+    row has m + 3 blocks -- 143, more than the SpMV tile, for the 140 pairs of that test.  The fan alone is too small for a
+    hierarchy."""
     b = mesh.bar_deck(dims=(6, 36, 6))
-    m = 140
     ang = 2 * np.pi * np.arange(m) / m
     ring = np.stack([np.cos(ang), np.sin(ang), np.zeros(m)], axis=1)
     fan = np.vstack([[0.0, 0.0, 0.0], ring, [0.0, 0.0, 0.7], [0.0, 0.0, -0.7]]) + np.array([4.0, 3.0, 0.5])
@@ -194,6 +194,24 @@ def test_multigrid_matches_reference_on_meshes(name, monkeypatch):
         assert s.N > 65536 and levels[0]["bits"] == 16           # the bf16 copy's column index needs its high half
     if name == "tet4_isolated_node":
         assert np.all(levels[0]["K"][levels[0]["rowptr"][-2]:] == 0)  # its block is zero: the identity stands in for D
+    s.close()
+
+
+@pytest.mark.parametrize("bits", [16, 32, 64])
+@pytest.mark.parametrize("pairs", [125, 126])
+def test_hub_row_at_the_tile_limit(pairs, bits, monkeypatch):
+    """A hub row of 128 blocks (a full tile, a chunk of its own) and of 129 (the smallest long row) under the bfloat16, the
+    float and the double smoother matrix of level 0: the three bodies of the SpMV and of the fused Jacobi sweep that run
+    only inside the cycle."""
+    set_env(monkeypatch, {"FEAHIP_AMG_FINE_BITS": str(bits)})
+    deck = fan_on_block(pairs)
+    s = prepared(deck)
+    info, levels = check_operator(s, deck)
+    assert info["fine_bits"] == bits and levels[0]["bits"] == bits
+    # the hub row has pairs + 3 blocks and is the longest; the two poles of the fan have pairs + 2 (at 126 pairs they are
+    # full tiles beside the long hub row); no row of the block comes near
+    rows = np.sort(np.diff(levels[0]["rowptr"]))
+    assert list(rows[-3:]) == [pairs + 2, pairs + 2, pairs + 3] and rows[-4] < 64, rows[-4:]
     s.close()
 
 
